@@ -8,7 +8,9 @@ demod -> soft bits) over one device-resident batch of synthetic bursts: BASELINE
 
   python bench.py --gpus N --steps K --warmup W          (driver launches N>1 under torch.distributed.run)
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field); `ms_per_step` is the wall time of one
+of the K timed steps.  `--dump-outputs DIR` also writes what the last timed step computed (a fixed, seeded sample of
+bursts) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -387,6 +389,28 @@ def strong_leg(trx, synth, shard, dev, rank, world, out):
         del iq, res_s, soft_s
 
 
+DUMP_SAMPLE = 65536            # bursts written by --dump-outputs: 65536 x 148 float32 soft bits = 38.8 MB, results ~2.4 MB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, trx, results, soft):
+    """What a caller of the timed path receives -- the result records (one .npy per field) and the soft bits -- for a fixed,
+    seeded sample of the batch's bursts (all of them when the batch is small), as float32 (float fields) or float64
+    (integer fields, exact).  burst_index.npy says which bursts were sampled."""
+    import numpy as np
+    import torch
+    n = results.shape[0]
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    sel = torch.from_numpy(idx).to(results.device)
+    rec = trx.results_to_numpy(results[sel])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "burst_index.npy"), idx.astype(np.float64))
+    for name in rec.dtype.names:
+        col = rec[name]
+        np.save(os.path.join(out_dir, f"{name}.npy"), col.astype(np.float32 if col.dtype.kind == "f" else np.float64))
+    np.save(os.path.join(out_dir, "soft.npy"), soft[sel].cpu().numpy().astype(np.float32))
+
+
 def free_port():
     import socket
     so = socket.socket()
@@ -455,7 +479,12 @@ def main():
                                                   "(strong = configs[4]'s fixed 8M batch; default only when N > 1)")
     ap.add_argument("--sustain-seconds", type=float, default=1.0,
                     help="length of the sustained leg (back-to-back launches behind the timed region; 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (a fixed, seeded sample of rank 0's "
+                         "bursts: every result field and the soft bits) as DIR/<name>.npy, for output-by-output comparison of builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:             # plain `python bench.py --gpus N`: launch the ranks here
         raise SystemExit(spawn_ranks(args.gpus))
@@ -514,6 +543,9 @@ def main():
     elapsed = shard.max_over_ranks(elapsed, dev if shard.backend_name() else None)
     kernel_ms = ev_a.elapsed_time(ev_b) / max(1, args.steps)
     kernel_ms = shard.max_over_ranks(kernel_ms, dev if shard.backend_name() else None)
+    if args.dump_outputs and rank == 0:
+        # before anything else reuses `results` / `soft`: they still hold what the last timed step computed
+        dump_outputs(args.dump_outputs, trx, results, soft)
 
     # sustained leg (not `value`): >= --sustain-seconds of back-to-back launches of the same step, queued without a host
     # synchronisation in between, so that the 20-step timed region can be read against a second of continuous load

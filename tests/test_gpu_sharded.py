@@ -123,10 +123,10 @@ import numpy as np, torch, torch.distributed as dist
 from osmo_trx_amd import TrxHip, shard
 N, base_path, out = int(sys.argv[2]), sys.argv[3], sys.argv[4]
 rank, _, world = shard.init_distributed("gloo")
-dev = "cuda:0"
-torch.cuda.set_device(0)
+dev = f"cuda:{rank}"                                                # one rank per GPU, as configs[4] lays it out
+torch.cuda.set_device(rank)
 blob = shard.broadcast_tables(dev)
-trx = TrxHip(0, tables_blob=blob)
+trx = TrxHip(rank, tables_blob=blob)
 stamp("imports + rendezvous + tables + context")
 lo, hi = shard.shard_range(N, rank, world)
 base = np.load(base_path)
@@ -153,14 +153,17 @@ dist.destroy_process_group()
 
 
 def test_eight_shards_of_the_8m_batch_equal_one_unsharded_launch(tmp_path):
-    """BASELINE.json configs[4] in its real form, time-sliced on one GPU: a fixed 8M-burst mixed batch (7:1 NB:RACH) as 8
-    contiguous shards -- 8 ranks over gloo, each  broadcast_tables -> TrxHip(tables_blob) -> detect_demod  on its 1M bursts --
+    """BASELINE.json configs[4] in its real form on an 8-GPU node: a fixed 8M-burst mixed batch (7:1 NB:RACH) as 8
+    contiguous shards -- 8 ranks over gloo, rank r on cuda:r, each  broadcast_tables -> TrxHip(tables_blob) -> detect_demod  on its 1M bursts --
     against ONE unsharded 8M-burst launch (21 GB of IQ, resident): position-weighted 64-bit checksums of every shard's result
     records and soft bits equal those of the same rows of the unsharded output, 2048 random rows per shard bit for bit.
     The batch is 65536 generated bursts tiled by a fixed index map (every rank reads the same base file: no generator, FFT
-    or convolution library in the workers -- eight fresh processes compiling those at once cost 20 minutes)."""
+    or convolution library in the workers -- eight fresh processes compiling those at once cost 20 minutes).
+    Eight ranks time-sliced on one GPU would hold it open from nine processes at once: with fewer than 8 GPUs the test skips."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
+    if torch.cuda.device_count() < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {torch.cuda.device_count()}")
     if torch.cuda.get_device_properties(0).total_memory < 100 << 30:
         pytest.skip("needs ~60 GB of device memory")
     from osmo_trx_amd import TrxHip, synth
@@ -204,14 +207,18 @@ def test_eight_shards_of_the_8m_batch_equal_one_unsharded_launch(tmp_path):
 
 
 def test_plain_bench_py_gpus_8_full_strong_batch(tmp_path):
-    """`python bench.py --gpus 8`, self-spawned, every rank on cuda:0 over gloo, with configs[4]'s REAL fixed batch: 8388608
-    mixed bursts, 1M per rank (the driver's 8-GPU run does the same over RCCL)."""
+    """`python bench.py --gpus 8`, self-spawned, rank r on cuda:r over gloo, with configs[4]'s REAL fixed batch: 8388608
+    mixed bursts, 1M per rank (the driver's 8-GPU run does the same over RCCL).  Eight ranks
+    time-sliced on one GPU would hold it open from eight processes at once: with fewer than 8 GPUs the test skips."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
+    if torch.cuda.device_count() < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {torch.cuda.device_count()}")
     if torch.cuda.get_device_properties(0).total_memory < 100 << 30:
         pytest.skip("needs ~40 GB of device memory")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TRXHIP_BENCH_STRONG_TOTAL")}
-    env.update(TRXHIP_DIST_BACKEND="gloo", TRXHIP_ONE_DEVICE="1")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TRXHIP_BENCH_STRONG_TOTAL",
+                                                             "TRXHIP_ONE_DEVICE")}
+    env.update(TRXHIP_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
            "--bursts", str(1 << 16), "--no-host-fed", "--legs", "strong", "--sustain-seconds", "0"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500, cwd=ROOT)
@@ -220,7 +227,7 @@ def test_plain_bench_py_gpus_8_full_strong_batch(tmp_path):
     assert len(line) == 1, r.stdout[-2000:]
     j = json.loads(line[0])
     assert j["n_gpus"] == 8 and j["world"] == 8 and j["backend"] == "gloo" and j["launcher"] == "bench.py self-spawn"
-    assert len(j["devices"]) == 8 and all(d.startswith(f"rank {k}: cuda:0") for k, d in enumerate(j["devices"]))
+    assert len(j["devices"]) == 8 and all(d.startswith(f"rank {k}: cuda:{k}") for k, d in enumerate(j["devices"]))
     s = j["config"]["other_configs"]["configs[4]_strong"]
     assert s["scaling"] == "strong" and s["global_bursts"] == 8388608 and s["bursts_this_rank"] == 1 << 20
     assert 0.9 < s["detected_fraction"] < 1.0 and s["mbursts_per_s_all_gpus"] > 0
