@@ -59,7 +59,7 @@ def build_lib(force=False, verbose=False):
 
 
 def build_diag(force=False):
-    """Profiling-only variant with the phase-ablation hooks (-DTRX_DIAG); never loaded by the product."""
+    """Profiling-only variant with per-phase cycle accounting (-DTRX_DIAG, tools/phase_cycles*.py); never loaded by the product."""
     out = os.path.join(LIBDIR, "libtrxhip_diag.so")
     srcs = [os.path.join(CSRC, s) for s in LIB_SOURCES]
     if force or _stale(out, [os.path.join(CSRC, f) for f in os.listdir(CSRC)]):

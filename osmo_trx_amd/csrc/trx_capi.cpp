@@ -53,10 +53,6 @@ extern "C" int trx_launch_vector_slicer(float *d_dst, const float *d_src, size_t
 
 #include "trx_ctx.h"
 
-#define TRXHIP_FLAG_DIAG_MASK 0x7fffff00   /* phase-ablation bits of the -DTRX_DIAG profiling build (tools/) */
-#define TRXHIP_IFLAG_NO_UNIT  0x40         /* internal: see trx_device.h */
-#define TRXHIP_IFLAG_NO_SYM   0x80
-#define TRXHIP_IFLAG_NO_FAST  0x20
 extern "C" int trx_fast_stats_read(unsigned long long *out4, int reset);   /* trx_kernel4.hip */
 
 extern "C" {
@@ -154,7 +150,6 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 		ctx->redo[i].n_last = 0;
 	}
 	ctx->split_backoff = 0;
-	ctx->no_backoff = getenv("TRXHIP_NO_BACKOFF") ? 1 : 0;         /* measurement switch: the split path whatever it leaves */
 	ctx->no_sym = 0;                                           /* the straight-line decimator reads taps 0..7 and mirrors them */
 	for (int k = 0; k < 8; k++)
 		if (memcmp(&t->dec_taps[k], &t->dec_taps[15 - k], sizeof(float)) != 0)
@@ -281,16 +276,16 @@ static int pull_common(trxhip_ctx *ctx, const void *d_iq, int cf32, const trxhip
 		return TRXHIP_EINVAL;
 	if (with_device(ctx))
 		return TRXHIP_EIO;
-	if (flags & ~(TRXHIP_FLAG_SLICE | TRXHIP_FLAG_EXACT_DEMOD | TRXHIP_FLAG_IDLE_DUMMY | TRXHIP_FLAG_FEW_NB_SLOTS | TRXHIP_FLAG_DIAG_MASK))
+	if (flags & ~(TRXHIP_FLAG_SLICE | TRXHIP_FLAG_EXACT_DEMOD | TRXHIP_FLAG_IDLE_DUMMY | TRXHIP_FLAG_FEW_NB_SLOTS))
 		return TRXHIP_EINVAL;
 	const bool few_nb = (flags & TRXHIP_FLAG_FEW_NB_SLOTS) != 0;  /* a hint, not a kernel flag */
 	flags &= ~TRXHIP_FLAG_FEW_NB_SLOTS;
 	if (ctx->no_unit)
-		flags |= TRXHIP_IFLAG_NO_UNIT;
+		flags |= TRX_IFLAG_NO_UNIT;
 	if (ctx->no_sym)
-		flags |= TRXHIP_IFLAG_NO_SYM;
+		flags |= TRX_IFLAG_NO_SYM;
 	if (ctx->no_fast)
-		flags |= TRXHIP_IFLAG_NO_FAST;
+		flags |= TRX_IFLAG_NO_FAST;
 	/* A launch that is being captured into a HIP graph keeps whatever it is handed for as long as the graph lives, and replays
 	 * may overlap later launches: it gets neither a pool counter pair (static split) nor a leftover list (general kernel only) --
 	 * both are recycled between launches. */
@@ -317,7 +312,7 @@ static int pull_common(trxhip_ctx *ctx, const void *d_iq, int cf32, const trxhip
 			ok = hipEventSynchronize(sl.ev) == hipSuccess;
 			sl.busy = 0;
 			if (ok && sl.h_left && sl.n_last && (size_t)*reinterpret_cast<volatile unsigned *>(sl.h_left) * 32 > sl.n_last)
-				ctx->split_backoff = ctx->no_backoff ? 0 : 63;
+				ctx->split_backoff = 63;
 		}
 		if (ok && !sl.h_left)
 			ok = hipHostMalloc(reinterpret_cast<void **>(&sl.h_left), 64, hipHostMallocDefault) == hipSuccess;
@@ -333,7 +328,7 @@ static int pull_common(trxhip_ctx *ctx, const void *d_iq, int cf32, const trxhip
 			sl.cap = 0;
 			const size_t cap_new = n_bursts < 65536 ? 65536 : n_bursts;
 			/* header words + one flag byte per burst, padded to whole chunks of 256; all zero between launches */
-			const size_t bytes = TRX_REDO_HDR_WORDS * sizeof(unsigned) + ((cap_new + 255) & ~(size_t)255);
+			const size_t bytes = TRX_REDO_HDR * sizeof(unsigned) + ((cap_new + 255) & ~(size_t)255);
 			/* (the memset runs on the null stream: drained before a kernel on the caller's -- possibly non-blocking -- stream
 			 * may touch the buffer; this is the allocation path, a handful of calls per context) */
 			ok = hipMalloc(reinterpret_cast<void **>(&sl.d), bytes) == hipSuccess && hipMemset(sl.d, 0, bytes) == hipSuccess &&
@@ -736,9 +731,8 @@ int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t
 	char *const hist = static_cast<char *>(f->d_chan_hist);
 	void *const hist_in = hist + (size_t)f->hist_cur * 4 * 16 * 8, *const hist_out = hist + (size_t)(f->hist_cur ^ 1) * 4 * 16 * 8;
 	/* one pass, the channel-rate streams stay on the chip (trx_aux_kernels.hip, frontend_fused_kernel) ... */
-	static const bool no_fused = getenv("TRXHIP_NO_FUSED_FRONTEND") != nullptr;
-	int rc = no_fused ? 1 : trx_launch_frontend_fused(d_wide, d_out, n_total, f->p, f->q, out_stride, f->d_parts, f->ctx->d_tables,
-							  f->d_wide_hist, hist_in, hist_out, s);
+	int rc = trx_launch_frontend_fused(d_wide, d_out, n_total, f->p, f->q, out_stride, f->d_parts, f->ctx->d_tables,
+					   f->d_wide_hist, hist_in, hist_out, s);
 	if (rc == 0)
 		f->hist_cur ^= 1;
 	if (rc != 1)

@@ -38,11 +38,9 @@ struct trxhip_ctx {
 	 * slots of other types the caller gave no hint about -- makes the next 63 eligible launches run the general kernel alone
 	 * (every left burst is read twice and stalls the first kernel's prefetch), then one launch probes again. */
 	unsigned split_backoff;
-	int no_backoff;                    /* TRXHIP_NO_BACKOFF at creation: measurement switch */
 };
 #define TRX_POOL_SLOTS 1024
 #define TRX_REDO_SLOTS 4
-#define TRX_REDO_HDR_WORDS 16           /* = TRX_REDO_HDR of the kernels */
 
 /* the TRXD wire packer's launcher (trx_aux_kernels.hip); d_results_copy (may be NULL): every result record is also written
  * there -- the host pipe points it at pinned memory and saves the download */

@@ -53,11 +53,9 @@ typedef float2 c32;
 		}                                                                                                \
 	} while (0)
 
-// Diagnostic build only (-DTRX_DIAG, libtrxhip_diag.so): the upper bits of `slice` carry a phase-ablation
-// mask so that per-phase cost can be measured on the GPU.  The product library is built without it.
+// Diagnostic build only (-DTRX_DIAG, libtrxhip_diag.so): per-phase cycle accounting (s_memtime deltas summed over all
+// bursts by lane 0 of every wave; tools/phase_cycles.py, tools/phase_cycles_nb.py).  The product library is built without it.
 #ifdef TRX_DIAG
-#define ABL(bit) ((slice >> (8 + (bit))) & 1)
-// per-phase cycle accounting (s_memtime deltas summed over all bursts by lane 0 of every wave)
 #define TRX_DIAG_WAVES 8192
 static __device__ unsigned long long g_trx_diag[TRX_DIAG_WAVES * 24];   // per wave (no atomics); one copy per translation unit
 // slots 20..23 are not sums: wall-clock start / end of the wave (s_memrealtime, 100 MHz), HW_ID and XCC_ID
@@ -86,36 +84,11 @@ static __device__ unsigned long long g_trx_diag[TRX_DIAG_WAVES * 24];   // per w
 		}                                                                               \
 	} while (0)
 #else
-// tools/pmc_phase_r03.sh: per-phase instruction counts of the PRODUCT kernel (the COMMON instantiation takes no run-time
-// flags) come from measurement builds with a compile-time ablation mask; the product library is built without it
-#ifdef TRX_ABL_MASK
-#define ABL(bit) ((TRX_ABL_MASK >> (bit)) & 1)
-#else
-#define ABL(bit) 0
-#endif
 #define DIAG_DECL
 #define DIAG_ARG
 #define DIAG_PASS
 #define DIAG_MARK(k)
 #define DIAG_FLUSH()
-#endif
-
-// Measurement build only (-DTRX_WHATIF_PAIR, tools/build_variants.py): an UPPER BOUND on what packing two bursts into one
-// wave for correlation / arg-max / the two gates / computeCI could buy.  Every other normal burst of a
-// wave skips exactly those phases and reuses the previous burst's peak index -- as if the neighbour's pass had produced both
-// results at no extra cost -- while decimation, both bisection rounds and the demodulator (phases whose lanes are full, or
-// whose 34 + 34 samples do not fit 64 lanes) run as always.  Results are wrong by construction: timing and counters only.
-#ifdef TRX_WHATIF_PAIR
-struct WhatIf { int bidx; int skip; };
-#define WI_ARG , WhatIf &wi
-#define WI_PASS , wi
-#define WI_LOCAL WhatIf wi = { 0, 0 }
-#define WI_SKIP (wi.skip != 0)
-#else
-#define WI_ARG
-#define WI_PASS
-#define WI_LOCAL
-#define WI_SKIP false
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -341,9 +314,6 @@ __device__ __forceinline__ float norm2(c32 v) { return v.y * v.y + v.x * v.x; }
 // path when they do not match what the table generator derived from the taps.
 // ------------------------------------------------------------------------------------------------
 #define TRX_UNIT_RATIO_LOG2 17
-#define TRX_IFLAG_NO_UNIT 0x40      // bit of the kernels' `slice` argument set by the C ABI when the tables lack the unit structure
-#define TRX_IFLAG_NO_SYM  0x80      // ... when the /4 decimator's taps are not bitwise symmetric (g[k] == g[15-k]): no straight-line paths
-#define TRX_IFLAG_NO_FAST 0x20      // ... when the sinc LUT's absolute row sums exceed TRX_FAST_W (the FAST detector's proven margin): exact TOA search
 // bit k set: the +-1 component of tap k is -1 (from the generated tables; tests/test_capi_cpu.py pins them)
 #define TRX_UNIT_NEG_TSC0   0x447bull
 #define TRX_UNIT_NEG_TSC1   0xc5bbull
@@ -851,18 +821,17 @@ struct NoToaHook { __device__ __forceinline__ void operator()(int) const {} };
 template <bool FAST, typename Hook>
 __device__ __forceinline__ int detect_tail_h(const c32 *sig, int sig_len, c32 *cz, const float *hdr, int N, float thresh,
 					      int start, int len, int bidx, const float *sincv, const PeakConst &pc, int lane,
-					      float *toa_out, c32 *amp_out, float *ci_out, Hook on_toa, const float4 *wa4, int slice DIAG_ARG WI_ARG)
+					      float *toa_out, c32 *amp_out, float *ci_out, Hook on_toa, const float4 *wa4, int slice DIAG_ARG)
 {
-	if (!WI_SKIP && ((bidx < 3) || (bidx > len - 3)))   // :1683
+	if ((bidx < 3) || (bidx > len - 3))   // :1683
 		return 0;
 	wave_sync();
 	const c32 amp0 = cz[bidx];
 
-	if (ABL(9)) { *toa_out = (float)bidx; *amp_out = amp0; *ci_out = 0.0f; return 1; }
 	DIAG_MARK(4);
 	// ---- computePeakRatio (:1541-1571): terms in the reference's order; out-of-range terms read the
 	// zero pads (adding +0 is exact), their count is arithmetic
-	const float pwr = WI_SKIP ? 0.0f : norm2(cz[bidx + pc.ratio_off]);   // (read before cz[len - 1] is zeroed below)
+	const float pwr = norm2(cz[bidx + pc.ratio_off]);   // (read before cz[len - 1] is zeroed below)
 	auto ratio_gate = [&]() -> bool {
 		// lane k (mod 8) squares the k-th term of the reference's loop (peak-2, peak+2, peak-3, ... peak+5; out-of-range
 		// ones read the zero pads), a serial DPP scan adds them left to right: lane 7 holds the reference's avg
@@ -920,7 +889,7 @@ __device__ __forceinline__ int detect_tail_h(const c32 *sig, int sig_len, c32 *c
 	// (Round 5 measured the other order for the 4-SPS kernel -- TOA search first, so that its hook's loads of the demodulator's
 	// low-edge tap rows have the gate's ~250 cycles more to arrive; the wait for those rows is 1.8 % of the kernel -- and did
 	// not keep it: -0.8 %, the extra search on the slots that fail the gate costs more; profiles/r05_ab_runs.txt.)
-	if (!WI_SKIP && !ratio_gate())
+	if (!ratio_gate())
 		return 0;
 
 	DIAG_MARK(5);
@@ -931,8 +900,7 @@ __device__ __forceinline__ int detect_tail_h(const c32 *sig, int sig_len, c32 *c
 	if (lane == 0 && len - 1 - bidx <= TRX_CZ_PAD)       // (farther from the peak nothing reads it)
 		cz[len - 1] = make_float2(0.0f, 0.0f);
 	wave_sync();
-	if (ABL(1)) { toa512 = bidx * 512; xcorr = amp0; }
-	else if (FAST && !(slice & TRX_IFLAG_NO_FAST)) {
+	if (FAST && !(slice & TRX_IFLAG_NO_FAST)) {
 		// FMA sums, decisions certified against m = |corr[bidx]|^2 (no correlation sample is larger); the exact search
 		// only for the bursts with an uncertified decision on their path
 		bool unsure;
@@ -957,7 +925,7 @@ __device__ __forceinline__ int detect_tail_h(const c32 *sig, int sig_len, c32 *c
 		// roundf(toa): toa is k/512 -> round half away from zero on integers
 		const int rt = (toa512 >= 0) ? ((toa512 + 256) >> 9) : -((-toa512 + 256) >> 9);
 		const int ps = start + 1 - N + rt;
-		if (ps >= 0 && ps + N <= sig_len && !ABL(7) && !WI_SKIP) {
+		if (ps >= 0 && ps + N <= sig_len) {
 			// S = sum_i |sig[ps+i]|^2 in index order: lane i squares one sample, the sum walks the lanes
 			const float pw = norm2(sig[ps + (lane < N ? lane : 0)]);
 			// serial scan along the lanes: after step s lane k holds pw[k-s] + ... + pw[k] added left to right, so
@@ -1015,9 +983,8 @@ __device__ __forceinline__ int detect_tail(const c32 *sig, int sig_len, c32 *cz,
 					    int start, int len, int bidx, const float *sincv, const PeakConst &pc, int lane,
 					    float *toa_out, c32 *amp_out, float *ci_out, int slice DIAG_ARG)
 {
-	WI_LOCAL;
 	return detect_tail_h<false>(sig, sig_len, cz, hdr, N, thresh, start, len, bidx, sincv, pc, lane, toa_out, amp_out, ci_out,
-				    NoToaHook(), nullptr, slice DIAG_PASS WI_PASS);
+				    NoToaHook(), nullptr, slice DIAG_PASS);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1035,13 +1002,8 @@ __device__ __forceinline__ int detect_tail(const c32 *sig, int sig_len, c32 *cz,
 template <bool PADDED, bool NARROW, bool FAST, typename Hook>
 __device__ __forceinline__ int detect_burst_h(const c32 *sig, int sig_len, c32 *cz, const c32 *taps, const float *hdr,
 					       int N, float thresh, int start, int len, const float *sincv, const PeakConst &pc, int lane,
-					       float *toa_out, c32 *amp_out, float *ci_out, Hook on_toa, const float4 *wa4, int slice, int unit_slot DIAG_ARG WI_ARG)
+					       float *toa_out, c32 *amp_out, float *ci_out, Hook on_toa, const float4 *wa4, int slice, int unit_slot DIAG_ARG)
 {
-#ifdef TRX_WHATIF_PAIR
-	if (wi.skip)                                     // the neighbour's pass "already" correlated and gated this burst
-		return detect_tail_h<FAST>(sig, sig_len, cz, hdr, N, thresh, start, len, wi.bidx, sincv, pc, lane, toa_out, amp_out, ci_out,
-					   on_toa, wa4, slice DIAG_PASS WI_PASS);
-#endif
 	const bool wide = NARROW && (len > TRX_CORR_NARROW || start + len > TRX_DEC_NARROW);
 	// corr[i] with range-checked reads, taps in order (cold: wide windows only)
 	auto corr_at = [&](int i) {
@@ -1169,11 +1131,8 @@ __device__ __forceinline__ int detect_burst_h(const c32 *sig, int sig_len, c32 *
 		}
 		czp = win - (bidx - TRX_CZ_PAD);
 	}
-#ifdef TRX_WHATIF_PAIR
-	wi.bidx = (bidx < 3) ? 3 : (bidx > len - 3 ? len - 3 : bidx);
-#endif
 	const int r = detect_tail_h<FAST>(sig, sig_len, czp, hdr, N, thresh, start, len, bidx, sincv, pc, lane, toa_out, amp_out, ci_out,
-					  on_toa, wa4, slice DIAG_PASS WI_PASS);
+					  on_toa, wa4, slice DIAG_PASS);
 	if (wide) {
 		wave_sync();
 		if (lane < TRX_CZ_PAD)
@@ -1187,9 +1146,8 @@ __device__ __forceinline__ int detect_burst(const c32 *sig, int sig_len, c32 *cz
 					     int N, float thresh, int start, int len, const float *sincv, const PeakConst &pc, int lane,
 					     float *toa_out, c32 *amp_out, float *ci_out, int slice, int unit_slot DIAG_ARG)
 {
-	WI_LOCAL;
 	return detect_burst_h<PADDED, NARROW, false>(sig, sig_len, cz, taps, hdr, N, thresh, start, len, sincv, pc, lane, toa_out, amp_out,
-						     ci_out, NoToaHook(), nullptr, slice, unit_slot DIAG_PASS WI_PASS);
+						     ci_out, NoToaHook(), nullptr, slice, unit_slot DIAG_PASS);
 }
 
 

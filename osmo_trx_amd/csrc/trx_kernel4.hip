@@ -92,14 +92,9 @@ __device__ __forceinline__ int cdiv4(int a) { return (a + 3) >> 2; }
 // atomics: a type-mixed batch leaves a million of them).  redo[0] != 0: something was left; a launch that finds 0 returns at
 // once.  A wave scans the flags 256 at a time (one dword per lane; chunks gw, gw + waves, ...), clears what it read and works
 // through the set ones; the next burst is known when the current one is prefetched, as in the claiming form.
-#define TRX_REDO_HDR 16                   /* words: [0] anything left, [1] workgroups done (this kernel); flag bytes behind them */
 // wave priority: the demodulator's filters at 0, everything else at 2 (measured on the normal-burst kernel: trx_kernel_nb.hip;
-// here: profiles/r06_ab_runs.txt section 8).  -DTRX_K4_NO_PRIO: measurement build without it.
-#ifdef TRX_K4_NO_PRIO
-#define K4_PRIO(p)
-#else
+// here: profiles/r06_ab_runs.txt section 8).
 #define K4_PRIO(p) asm volatile("s_setprio %0" :: "n"(p))
-#endif
 template <bool CF32, bool EXACT, bool COMMON, bool LIST = false>
 __global__ void __launch_bounds__(K4_WPB(CF32, EXACT) * WAVE)
 burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__restrict__ params,
@@ -131,9 +126,6 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 	c32 pre_c[CF32 ? NLD : 1];
 	uint32_t pre_prm = 0u;
 	auto prefetch = [&](unsigned bb) {
-#ifdef TRX_WHATIF_L2INPUT   /* timing only (tools/): every burst reads one of the first 4096 (cache-resident input): what HBM latency costs */
-		bb &= 4095u;
-#endif
 		pre_prm = reinterpret_cast<const uint32_t *>(params)[2 * (size_t)bb];
 		if (CF32) {
 			const c32 *src = reinterpret_cast<const c32 *>(iq_) + (size_t)bb * L;
@@ -424,10 +416,6 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 	};
 
 	DIAG_DECL;
-#ifdef TRX_WHATIF_PAIR
-	WhatIf wi = { 8, 1 };                                          /* (the first normal burst of a wave runs in full) */
-	WhatIf wi_full = { 0, 0 };
-#endif
 	unsigned j_next = 0, b_next = K4_NO_BURST;
 	for (unsigned b = b_first; b != K4_NO_BURST; b = b_next) {
 		// Re-materialise the lane id per burst (2 VALU ops): otherwise every lane-derived address, tree-node
@@ -441,11 +429,6 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 		const int type = prm0 & 0xff;
 		const int tsc = (prm0 >> 8) & 0xff;
 		const int max_toa = prm0 >> 16;
-#ifdef TRX_HOT_ONLY   /* reading aid (tools/): the instruction stream of a normal burst alone; not a product build */
-		__builtin_assume(type == TRXHIP_TSC);
-		__builtin_assume(tsc < 8);
-		__builtin_assume(max_toa == 3);
-#endif
 
 		int rc = 0;
 		float toa = 0.0f, ci = 0.0f, energy = 0.0f, rssi = 0.0f;
@@ -489,13 +472,8 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 			idle = 0;
 			// park the low-edge rows: lane l < 48 holds floats 4l .. 4l+3 of the 8 x 24 block
 			float *const stage = reinterpret_cast<float *>(dec);
-#ifdef TRX_WHATIF_NOFETCHWAIT   /* timing only (tools/): what the wait for the edge8 rows costs -- the rows are not used */
-			if (lane < 2 * K4_NTP)
-				*reinterpret_cast<float4 *>(stage + 4 * lane) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#else
 			if (lane < 2 * K4_NTP)
 				*reinterpret_cast<float4 *>(stage + 4 * lane) = fast_rows;
-#endif
 			wave_sync();
 			// lanes 0..49: outputs 3l .. 3l+2 with the burst's composite row; lanes 52..55: output l - 52, main part of its
 			// truncated row; lanes 56..59: the same outputs' taps u < 8 (window 8 samples = 2 outputs earlier); the rest idle
@@ -506,8 +484,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 			const int c = -24 - w + K4_U0;                              // tap u = K4_U0 of output i reads sample 4i + c
 			const PhBase pb = ph_bases(P, c & 3, ic + (c >> 2));
 			v2f acc[3] = { { 0.0f, 0.0f }, { 0.0f, 0.0f }, { 0.0f, 0.0f } };
-			if (!ABL(5))
-				fir24x3(pb, reinterpret_cast<const float4 *>(tp), acc);
+			fir24x3(pb, reinterpret_cast<const float4 *>(tp), acc);
 			// low-edge outputs: main part (lane 52 + i) + taps u < 8 (lane 56 + i), row_shl:4 inside the last row of 16
 			float er = acc[0].x, ei = acc[0].y;
 			asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
@@ -577,8 +554,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 			clip = __ballot(amax > TRX_CLIP_THRESH) != 0ull;
 			epart = wave_sum_quad0(epart);                          // energyDetect partial sums (lanes = 0 mod 4 hold them)
 			energy = epart * 0.0125f;                               // energyDetect(burst, 20*sps): / 80
-			if (!ABL(2))
-				rssi = fs_db - 3.01029996f * __log2f(energy);       // 20*log10(fs/sqrt(e)), Transceiver.cpp:741,751
+			rssi = fs_db - 3.01029996f * __log2f(energy);       // 20*log10(fs/sqrt(e)), Transceiver.cpp:741,751
 			wave_sync();
 			DIAG_MARK(1);
 
@@ -588,7 +564,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 				toa = unif(e.x);
 				amp = make_float2(unif(e.y), unif(e.z));
 				out_tsc = tsc;
-			} else if ((type != TRXHIP_IDLE || (slice & TRXHIP_FLAG_IDLE_DUMMY)) && !ABL(3)) {   // Transceiver.cpp:754-755
+			} else if ((type != TRXHIP_IDLE || (slice & TRXHIP_FLAG_IDLE_DUMMY))) {   // Transceiver.cpp:754-755
 				// ---- detectAnyBurst (:1926-1957); decimation on the polyphase layout:
 				// dec[i] = sum_k x[4i-15+k] * g[k];  x[4(i-4) + k'] with k' = k+1 -> phase k'&3, m = i-4 + k'>>2
 				PeakConst pkc;
@@ -639,11 +615,8 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 					// all multiples of 1/512) and, in the usual geometry, the fetch of its low-edge tap rows (fast_fetch)
 					const float *const hdr = lhdr + 8 * tsc;
 					auto on_toa = [&](int toa512) { fast_fetch(toa512 - (int)(hdr[5] * 512.0f) - 10 * 512); };
-#ifdef TRX_WHATIF_PAIR
-					wi.skip ^= 1;
-#endif
 					const int hit = detect_burst_h<true, true, !EXACT>(dec, 156, cz, lseq + LSEQ_TSC(tsc), hdr, 16, thresh, 71, len, sincv,
-										   pkc, lane, &toa, &amp, &ci, on_toa, wa4, slice, unit_bad ? -1 : tsc DIAG_PASS WI_PASS);
+										   pkc, lane, &toa, &amp, &ci, on_toa, wa4, slice, unit_bad ? -1 : tsc DIAG_PASS);
 					wave_sync();
 					rc = hit ? TRXHIP_TSC : (clip ? -TRXHIP_SIGERR_CLIP : 0);                 // :1764, :1953-1954
 					toa -= 10.0f;                                                              // :1768
@@ -668,22 +641,14 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 					wave_sync();
 					DIAG_MARK(2);
 					int hit = detect_burst_h<true, true, !EXACT>(dec, 156, cz, lseq + LSEQ_RACH(0), lhdr + 8 * 8, 40, thresh, 39, len, sincv,
-									     pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, unit_bad ? -1 : 8 DIAG_PASS
-#ifdef TRX_WHATIF_PAIR
-									     , wi_full
-#endif
-									     );
+									     pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, unit_bad ? -1 : 8 DIAG_PASS);
 					wave_sync();
 					out_tsc = 0;                                                               // ebp->tsc = i (:1797)
 					if (!hit && type == TRXHIP_EXT_RACH) {
 						// extended access bursts: TS1, then TS2 over the same window, first hit wins (:1791-1800)
 						for (int c = 1; c < 3 && !hit; c++) {
 							hit = detect_burst_h<true, true, !EXACT>(dec, 156, cz, lseq + LSEQ_RACH(c), lhdr + 8 * (8 + c), 40, thresh, 39, len,
-											 sincv, pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, unit_bad ? -1 : 8 + c DIAG_PASS
-#ifdef TRX_WHATIF_PAIR
-											 , wi_full
-#endif
-											 );
+											 sincv, pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, unit_bad ? -1 : 8 + c DIAG_PASS);
 							wave_sync();
 							out_tsc = c;
 						}
@@ -705,22 +670,14 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 					}
 					DIAG_MARK(2);
 					int hit = detect_burst_h<true, true, !EXACT>(dec, 156, cz, lseq + LSEQ_EDGE(tsc), lhdr + 8 * (11 + tsc), 16, thresh, 75, len - 4,
-									     sincv, pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, -1 DIAG_PASS
-#ifdef TRX_WHATIF_PAIR
-									     , wi_full
-#endif
-									     );
+									     sincv, pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, -1 DIAG_PASS);
 					wave_sync();
 					if (hit) {
 						rc = TRXHIP_EDGE;                                                          // :1953-1954
 						toa -= 6.0f;                                                               // :1768
 					} else {
 						hit = detect_burst_h<true, true, !EXACT>(dec, 156, cz, lseq + LSEQ_TSC(tsc), lhdr + 8 * tsc, 16, thresh, 71, len, sincv,
-										 pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, unit_bad ? -1 : tsc DIAG_PASS
-#ifdef TRX_WHATIF_PAIR
-										 , wi_full
-#endif
-										 );
+										 pkc, lane, &toa, &amp, &ci, NoToaHook(), wa4, slice, unit_bad ? -1 : tsc DIAG_PASS);
 						wave_sync();
 						rc = hit ? TRXHIP_TSC : (clip ? -TRXHIP_SIGERR_CLIP : 0);
 						toa -= 10.0f;
@@ -735,44 +692,10 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 			}
 		}
 
-#if defined(TRX_SENS_VALU) || defined(TRX_SENS_PLAIN) || defined(TRX_SENS_LDS) || defined(TRX_SENS_SALU) || defined(TRX_SENS_LDSW)
-		// measurement builds only (tools/build_variants.py): N extra instructions of one kind per burst, results unused --
-		// the slope of throughput against N is what one instruction of that kind costs (or its removal buys)
-		{
-			v2f sx = { toa, ci }, sy = sx;
-			float sp = toa, sq = ci;
-			int ss = (int)b;
-#ifdef TRX_SENS_VALU
-			asm volatile(".rept %c4\n v_pk_add_f32 %0, %0, %2\n v_pk_add_f32 %1, %1, %2\n .endr" : "+v"(sx), "+v"(sy) : "v"(sx), "v"(sy), "n"(TRX_SENS_VALU / 2));
-#endif
-#ifdef TRX_SENS_PLAIN
-			asm volatile(".rept %c2\n v_add_f32 %0, %0, %0\n v_add_f32 %1, %1, %1\n .endr" : "+v"(sp), "+v"(sq) : "n"(TRX_SENS_PLAIN / 2));
-#endif
-#ifdef TRX_SENS_LDS
-			{
-				const unsigned la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)sincv + lane * 8;
-				asm volatile(".rept %c3\n ds_read_b64 %0, %2\n ds_read_b64 %1, %2 offset:512\n .endr\n s_waitcnt lgkmcnt(0)" : "=&v"(sx), "=&v"(sy) : "v"(la), "n"(TRX_SENS_LDS / 2) : "memory");
-			}
-#endif
-#ifdef TRX_SENS_LDSW
-			{
-				// N extra ds_write_b64 into this wave's correlation pad area (cz[64 + ...] is beyond anything a burst reads back;
-				// zeros, so the pads stay zero)
-				const unsigned la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) c32 *)(cz + 64) + (lane & 7) * 8;
-				const v2f zz = { 0.0f, 0.0f };
-				asm volatile(".rept %c2\n ds_write_b64 %0, %1\n .endr" :: "v"(la), "v"(zz), "n"(TRX_SENS_LDSW) : "memory");
-			}
-#endif
-#ifdef TRX_SENS_SALU
-			asm volatile(".rept %c1\n s_add_u32 %0, %0, 3\n .endr" : "+s"(ss) : "n"(TRX_SENS_SALU) : "scc");
-#endif
-			if (sx.x + sy.y + sp + sq == 1.2345e-30f || ss == 0x7fffffff) energy += 1.0f;      // keep the results alive
-		}
-#endif
 		// The burst's result record (wave-uniform fields dropped into lanes 0..7 of one register; written by flush() at the top
 		// of the next burst).  Assembled in front of the demodulator when the straight-line one is about to run -- its ~25
 		// scalar and vector instructions then sit between the fetch of the low-edge tap rows (issued when the TOA was known)
-		// and the first use of those rows (TRX_EARLY_RECORD; the wait for the rows is 1.8 % of the kernel) -- else behind it.
+		// and the first use of those rows (the wait for the rows is 1.8 % of the kernel) -- else behind it.
 		auto assemble_record = [&]() {
 			const bool det = rc > 0;
 			pend_flags = (uint32_t)(det ? out_tsc : 0) | ((uint32_t)clip << 8) | ((uint32_t)idle << 16) | ((uint32_t)(nbits / 4) << 24);
@@ -800,18 +723,16 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 		bool record_done = false;
 		// ---- demodAnyBurst -> demodGmskBurst (:2055-2072) ----
 		K4_PRIO(0);                                                 // the filters: dense vector work, lowest priority (see trx_kernel_nb.hip)
-		if (COMMON && !EXACT && rc == TRXHIP_TSC && fast_nk != (1 << 30) && !fast_done && !ABL(0)) {
-#ifndef TRX_LATE_RECORD
+		if (COMMON && !EXACT && rc == TRXHIP_TSC && fast_nk != (1 << 30) && !fast_done) {
 			nbits = 148;                                                // (what fast_demod() sets)
 			idle = 0;
 			assemble_record();
 			record_done = true;
-#endif
 			fast_demod();
 			fast_done = true;
 		}
 		if (fast_done) {
-		} else if (rc > 0 && !ABL(0)) {
+		} else if (rc > 0) {
 			// demodCommon (:2030-2048): delayVector(burst, -toa*sps) -> scaleVector(1/amp) -> downsampleBurst
 			// delay = -toa * 4 samples: whole = floor(delay), frac = delay - whole, filter floorf(frac * 64) if frac > 0.01
 			// (:1049-1057).  A detected TOA is a multiple of 1/512 symbol (bisection step, table toa, integer head), so
@@ -823,13 +744,13 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 				const float delay = -toa * 4.0f;
 				w = uni((int)floorf(delay));
 				const float frac = delay - (float)w;
-				const bool use_filt = ((double)fabsf(frac) > 1e-2) && !ABL(4);
+				const bool use_filt = ((double)fabsf(frac) > 1e-2);
 				fidx = uni(use_filt ? (int)floorf(frac * (float)TRX_DELAY_FILTS) : TRX_DELAY_FILTS);
 			} else {
 				const int nk = -uni((int)(toa * 512.0f));
 				w = nk >> 7;
 				const int fr = nk & 127;
-				fidx = (fr >= 2 && !ABL(4)) ? (fr >> 1) : TRX_DELAY_FILTS;
+				fidx = (fr >= 2) ? (fr >> 1) : TRX_DELAY_FILTS;
 			}
 			// (complex) 1.0 / amp = (1,0) * amp.inv()   (Complex.h:75,144-150)
 			const float an = norm2(amp);
@@ -954,7 +875,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 					const int nloop = is_edge ? 156 : soft_stride;
 					for (int i = lane; i < nloop; i += WAVE) {
 						float sv = 0.0f;
-						if (i < nwrite && !ABL(5)) {
+						if (i < nwrite) {
 							const c32 *pd = P + PH_M0 + i - 4;
 							float yr = 0.0f, yi = 0.0f;
 							if (!(slice & TRX_IFLAG_NO_SYM)) {                  // the detector's decimator: same sums, same order, taps in registers
@@ -998,7 +919,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 				// lanes of row e, lane t of the row taking taps t, t+16, t+32; the table values are fetched HERE, before the
 				// main filter, so that their latency is covered by it.  Requires that no high-side truncation touches
 				// these outputs (bursts shorter than the window: generic edge_round() below).
-				const bool lo_tab = need_lo && (n_hi >= 4 * (i_full_lo - 1)) && (so || is_edge) && !ABL(6);
+				const bool lo_tab = need_lo && (n_hi >= 4 * (i_full_lo - 1)) && (so || is_edge);
 				float ct0 = 0.0f, ct1 = 0.0f, ct2 = 0.0f;
 				const int le = lane >> 4, lt = lane & 15;
 				const int li = i0l + le;                                    // this row's output
@@ -1015,7 +936,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 				// High-side partial outputs the same way (trx_tables.edge_hi): a burst shifted left by w <= -2 ends at delayed
 				// sample n_hi = L - 1 + w and output i0h + e sees decimator taps t <= tm = n_hi + 15 - 4 (i0h + e) only.  Access
 				// bursts live here (TOA up to 63 symbols); the masked two-stage sum of edge_round() was a third of their time.
-				const bool hi_tab = need_hi && (w <= -2) && (n_lo <= 4 * i0h - 15) && (so || is_edge) && !ABL(6);
+				const bool hi_tab = need_hi && (w <= -2) && (n_lo <= 4 * i0h - 15) && (so || is_edge);
 				float ch0 = 0.0f, ch1 = 0.0f, ch2 = 0.0f;
 				const int hi_i = i0h + le;                                  // this row's output
 				const int htm = n_hi + 15 - 4 * hi_i;                       // last decimator tap that sees an existing sample
@@ -1047,7 +968,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 					if (ic > i_max - 2) ic = i_max - 2;
 					const PhBase pb = ph_bases(P, c & 3, ic + (c >> 2));
 					v2f acc[3] = { { 0.0f, 0.0f }, { 0.0f, 0.0f }, { 0.0f, 0.0f } };
-					if (!ABL(5) && lane < 52)                                   // 52 lanes x 3 outputs = 156; the rest would compute discarded values
+					if (lane < 52)                                   // 52 lanes x 3 outputs = 156; the rest would compute discarded values
 						fir24x3(pb, c4, acc);
 					DIAG_MARK(10);
 					// the 1-SPS symbols go through dec[] (free once detection is done; the 8-PSK tail wants them there
@@ -1131,8 +1052,8 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 					}
 					if ((need_lo && !lo_tab) || (need_hi && !hi_tab))
 						load_hh();                                          // only now: 20 registers the main filter does not carry
-					if (need_lo && !lo_tab && !ABL(6)) edge_round(i0l);
-					if (need_hi && !hi_tab && !ABL(6)) edge_round(i0h);
+					if (need_lo && !lo_tab) edge_round(i0l);
+					if (need_hi && !hi_tab) edge_round(i0h);
 					DIAG_MARK(9);
 					wave_sync();
 
@@ -1274,16 +1195,10 @@ extern "C" int trx_launch_pull4(unsigned *d_pool_ctr, const void *d_iq, int cf32
 	if (n_bursts == 0)
 		return 0;
 	const bool exact = (flags & TRXHIP_FLAG_EXACT_DEMOD) != 0;      // two kernels: the demodulator is a compile-time choice
-	int wpb = K4_WPB(cf32 != 0, exact);
-#ifdef TRX_DIAG
-	if (const char *e = getenv("TRXHIP_WPB")) { const int v = atoi(e); if (v >= 1 && v <= wpb) wpb = v; }   // occupancy scan
-#endif
+	const int wpb = K4_WPB(cf32 != 0, exact);
 	const size_t lds = K4_TABLES_BYTES + (size_t)wpb * K4_SLICE * sizeof(c32) + K4_LDS_TAIL;   // + work counter + pool ring
 	size_t need = (n_bursts + 15) / 16;                             // work is handed out in groups of 16 bursts
 	size_t grid = (size_t)n_cu;
-#ifdef TRX_DIAG
-	if (const char *e = getenv("TRXHIP_GRID")) { const int v = atoi(e); if (v >= 1) grid = (size_t)v; }
-#endif
 	if (grid > need) grid = need;
 	/* the instantiation with the common launch parameters folded (see the kernel) */
 	const bool common = (!cf32 || !exact) && L == 625 && d_soft && !d_ebp_in && soft_stride == 148 &&

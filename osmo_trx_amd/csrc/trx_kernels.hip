@@ -136,12 +136,6 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 		prefetch(burst_of((unsigned)wave));
 
 	DIAG_DECL;
-#ifdef TRX_WHATIF_PAIR
-	WhatIf wi_none = { 0, 0 };
-#define WI_1SPS , wi_none
-#else
-#define WI_1SPS
-#endif
 	unsigned j_next = 0;
 	for (unsigned j = (unsigned)wave; j < items; j = j_next) {
 		const unsigned b = burst_of(j);
@@ -203,8 +197,7 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 			clip = __ballot(amax > TRX_CLIP_THRESH) != 0ull;        // maxAmplitude() > 30000 (:1711-1722, :1746): some lane saw a larger component
 			// energyDetect(burst, 20*sps) (:1573-1585), tree-summed; RSSI (Transceiver.cpp:741,751) in fp32
 			energy = wave_sum(epart) / (float)win;
-			if (!ABL(2))
-				rssi = fs_db - 3.01029996f * __log2f(energy);       // 20*log10(fs/sqrt(e)), Transceiver.cpp:741,751
+			rssi = fs_db - 3.01029996f * __log2f(energy);           // 20*log10(fs/sqrt(e)), Transceiver.cpp:741,751
 			wave_sync();
 
 			if (ebp_in) {
@@ -214,7 +207,7 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 				toa = unif(e.x);
 				amp = make_float2(unif(e.y), unif(e.z));
 				out_tsc = tsc;
-			} else if ((type != TRXHIP_IDLE || (slice & TRXHIP_FLAG_IDLE_DUMMY)) && !ABL(3)) {   // Transceiver.cpp:754-755
+			} else if (type != TRXHIP_IDLE || (slice & TRXHIP_FLAG_IDLE_DUMMY)) {   // Transceiver.cpp:754-755
 				// ---- detectAnyBurst (:1926-1957)
 				DetectOut d;
 				if (SPS == 4) {
@@ -249,7 +242,7 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 					const int unit_bad = (__ballot(unit_unsafe(xs[56 + lane]) && lane < 15 + len) != 0ull) ? 1 : 0;
 					const float *const hdr = lhdr + 8 * tsc;
 					const int hit = detect_burst_h<true, false, false>(xs, L, cz, lseq + LSEQ_TSC(tsc), hdr, 16, thresh, 71, len, sincv, pkc, lane,
-										    &d.toa, &d.amp, &d.ci, NoToaHook(), nullptr, slice, unit_bad ? -1 : tsc DIAG_PASS WI_1SPS);
+										    &d.toa, &d.amp, &d.ci, NoToaHook(), nullptr, slice, unit_bad ? -1 : tsc DIAG_PASS);
 					wave_sync();
 					rc = hit ? TRXHIP_TSC : (clip ? -TRXHIP_SIGERR_CLIP : 0);                      // :1764, :1953-1954
 					d.toa -= 10.0f;                                                                 // :1768
@@ -264,12 +257,12 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 		}
 
 		// ---- demodAnyBurst -> demodGmskBurst (:2055-2072) ----
-		if (rc > 0 && !ABL(0)) {
+		if (rc > 0) {
 			// demodCommon (:2030-2048): delayVector(burst, -toa*sps), scaleVector(1/amp)
 			const float delay = -toa * (float)SPS;
 			const int whole = (int)floorf(delay);
 			const float frac = delay - (float)whole;
-			const bool use_filt = ((double)fabsf(frac) > 1e-2) && !ABL(4);  // :1056
+			const bool use_filt = (double)fabsf(frac) > 1e-2;  // :1056
 			const int fidx = use_filt ? (int)floorf(frac * (float)TRX_DELAY_FILTS) : 0;   // :1057
 			const float4 *hf4 = reinterpret_cast<const float4 *>(dfilt + uni(fidx) * TRX_DELAY_HLEN);
 			// (complex) 1.0 / amp = (1,0) * amp.inv()   (Complex.h:75,144-150)
@@ -393,7 +386,7 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 				const int nwrite = (slice & 1) ? nbits : nsoft;
 				for (int i = lane; i < soft_stride; i += WAVE) {
 					float sv = 0.0f;
-					if (i < nwrite && !ABL(5)) {
+					if (i < nwrite) {
 						c32 d;
 						if (SPS == 4) {
 							const c32 *xp = xs + 4 * i - 15;

@@ -18,15 +18,10 @@ struct trx_c32 { float re, im; };
 // The fused demodulator evaluates composite taps u = TRX_FUSED_U0 .. TRX_FUSED_U0 + TRX_FUSED_NT - 1 of the 35 (trx_kernel4.hip,
 // fir24x3): 6 .. 29 since round 5 (rounds 2-4: 8 .. 31 -- but taps 30 / 31 carry 3.7e-7 / 2e-9 of a filter whose taps sum to 1 and
 // taps 6 / 7 carry 6.2e-7 / 3e-8: the same 24 multiply-adds two taps lower halve the error, profiles/r05_fused_taps.txt).
-// Measurement builds (tools/build_variants.py name:all:-DTRX_FUSED_U0=..,-DTRX_FUSED_NT=..) override them to price other windows.
 // Taps are fetched four at a time from 16-byte aligned LDS addresses: the kernel's LDS copy of a composite row is shifted by
 // TRX_FUSED_SH so that tap U0 sits at a multiple of 4.
-#ifndef TRX_FUSED_U0
 #define TRX_FUSED_U0 6
-#endif
-#ifndef TRX_FUSED_NT
 #define TRX_FUSED_NT 24
-#endif
 #define TRX_FUSED_SH ((4 - TRX_FUSED_U0 % 4) % 4)          /* shift of the LDS copy of a composite row */
 #define TRX_FUSED_NTP ((TRX_FUSED_NT + 3) / 4 * 4)        /* taps per edge8 row (rows are fetched as float4) */
 
@@ -99,6 +94,16 @@ struct trx_tables {
 static_assert(offsetof(trx_tables, edge8) % 16 == 0, "edge8 rows are fetched as float4");
 static_assert(TRX_FUSED_U0 >= 0 && TRX_FUSED_U0 <= 8 && TRX_FUSED_U0 + TRX_FUSED_NTP + TRX_FUSED_SH <= 36 && TRX_FUSED_NTP <= 32,
 	      "fused demodulator tap window");
+
+// Constants shared by the C ABI (trx_capi.cpp, host compiler) and the kernels.
+// Internal bits of the kernels' `slice` argument, set by the C ABI from what trxhip_create*() found in the tables; they sit
+// in bits the public flags (include/trxhip.h) leave free:
+#define TRX_IFLAG_NO_UNIT 0x40      // the tables lack the unit structure: multiplying correlation (trx_device.h, corr_unit())
+#define TRX_IFLAG_NO_SYM  0x80      // the /4 decimator's taps are not bitwise symmetric (g[k] == g[15-k]): no straight-line paths
+#define TRX_IFLAG_NO_FAST 0x20      // the sinc LUT's absolute row sums exceed TRX_FAST_W (the FAST detector's proven margin): exact TOA search
+// Header of a leftover list of the normal-burst kernel (trx_kernel4.hip), in 32-bit words: [0] anything left, [1] workgroups
+// done (general kernel); one flag byte per burst behind it
+#define TRX_REDO_HDR 16
 
 #define TRX_TABLES_MAGIC   0x54585254u
 #define TRX_TABLES_VERSION 8u   /* 8: edge8 rows for taps U0 = 6 .. 29 (round 5), window recorded in fused_u0 / fused_nt */

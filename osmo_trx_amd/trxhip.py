@@ -241,7 +241,7 @@ class TrxHip:
 
     # ---- hot path ------------------------------------------------------------------------------
     def detect_demod(self, iq, params, sps=4, threshold=4.0, full_scale=32767.0, soft_stride=148, slice_bits=True,
-                     results=None, soft=None, stream=None, want_soft=True, exact=False, idle_dummy=False, _diag_mask=0,
+                     results=None, soft=None, stream=None, want_soft=True, exact=False, idle_dummy=False,
                      host_params=None, hint=None):
         """iq: int16[n, burst_len, 2] or complex64[n, burst_len] (device).  params: uint8[n, 8] (device).
         host_params: the caller's host copy of the parameters (PARAMS_DTYPE[n]), if it has one: the slot types decide the
@@ -271,7 +271,7 @@ class TrxHip:
         rc = fn(self.h, ip, self._dev(params), self._dev(results), sp, n, burst_len, sps,
                 threshold, full_scale, soft_stride,
                 (FLAG_SLICE if slice_bits else 0) | (FLAG_EXACT_DEMOD if exact else 0) |
-                (FLAG_IDLE_DUMMY if idle_dummy else 0) | (int(_diag_mask) << 8) | (few_nb_hint(host_params) if hint is None else int(hint)),
+                (FLAG_IDLE_DUMMY if idle_dummy else 0) | (few_nb_hint(host_params) if hint is None else int(hint)),
                 self._stream(stream))
         _check(rc, "trxhip_detect_demod_batch")
         return results, soft

@@ -284,6 +284,15 @@ def test_argument_errors(trx):
         trx.detect_demod(iq[:, :600].contiguous(), p, sps=4)
     # empty batch is a no-op
     trx.detect_demod(iq[:0], p[:0], sps=4)
+    # a flag bit include/trxhip.h does not define is refused before anything is launched
+    import re
+    from osmo_trx_amd.trxhip import FLAG_SLICE
+    einval = int(re.search(r"#define\s+TRXHIP_EINVAL\s+\((-?\d+)\)", open(os.path.join(O.ROOT, "include", "trxhip.h")).read()).group(1))
+    res = torch.empty((4, 32), dtype=torch.uint8, device="cuda:0")
+    soft = torch.empty((4, 148), dtype=torch.float32, device="cuda:0")
+    rc = trx.L.trxhip_detect_demod_batch(trx.h, trx._dev(iq), trx._dev(p), trx._dev(res), trx._dev(soft), 4, 625, 4, 4.0, 32767.0,
+                                         148, FLAG_SLICE | 0x100, trx._stream())
+    assert rc == einval
 
 
 def test_full_size_access_bursts(trx):
