@@ -120,7 +120,7 @@ def load_library():
         raise TrxHipError(f"cannot load {path}: {e}") from e
     for name, (res, args) in SYMBOLS.items():
         if (name == "trxhip_fast_stats" or name.startswith("trxhip_hostpipe_")) and os.environ.get("TRXHIP_LIB") and not hasattr(L, name):
-            continue          # tools/ab_multi.sh against an older measurement build of the library (product: always bound)
+            continue          # tools/measure.py ab against an older measurement build of the library (product: always bound)
         f = getattr(L, name)  # AttributeError if the export is missing
         f.restype = res
         f.argtypes = args

@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from osmo_trx_amd import TrxHip, synth, trxhip
+from workloads import make
 
 REPS = int(os.environ.get("REPS", 5))
 N = int(os.environ.get("N_BURSTS", 1 << 20))
@@ -47,7 +48,7 @@ def pull(name, iq, params, stride=148, exact=False, kernel="burst_pull4_kernel<f
     return res, soft, dp
 
 
-iq, p, _ = synth.make_normal_bursts(N, dev, 4)
+iq, p, _ = make("normal", N, dev)
 res, soft, dp = pull("configs[1] NB max_toa 3, exact demodulator", iq, p, exact=True, kernel="burst_pull4_kernel<false, true, true>")
 
 # ---- TRXD packers on that launch's output
@@ -67,13 +68,13 @@ ms = timeit(lambda: trx.demod_va(x, dp))
 report("va_demod_kernel", "use_va demodulation, NB", N, "bursts", N * (625 * 8 + 8 + 156 * 4 + 4), ms)
 del x
 
-iq, p, _ = synth.make_access_bursts(N, dev)
+iq, p, _ = make("rach", N, dev)
 pull("configs[2] RACH max_toa 63", iq, p)
-iq, p, _ = synth.make_access_bursts(N, dev, ext=True)
+iq, p, _ = make("ext", N, dev)
 pull("configs[2] EXT_RACH (TS0/1/2) max_toa 63", iq, p)
-iq, p = synth.make_mixed_bursts(N, dev)
+iq, p, _ = make("mixed", N, dev)
 pull("configs[4] share: 7:1 NB:RACH", iq, p)
-iq, p, _ = synth.make_edge_bursts(N, dev)
+iq, p, _ = make("edge", N, dev)
 pull("EDGE 8-PSK, 444 soft bits", iq, p, stride=444, kernel="burst_pull4_kernel<false, false, false>")
 iq1, p1, _ = synth.make_normal_bursts(N, dev, 1, burst_len=156)
 pull("configs[0] geometry: NB 1 SPS, 156 samples", iq1, p1, kernel="burst_pull_kernel<1, false, 3>")
@@ -81,7 +82,7 @@ del iq, iq1
 
 # ---- front end (configs[3]): Channelizer(4, 192, 16) over 256k blocks, Resampler(65, 48) on the 4 channel streams
 nb = 1 << 18
-wide = synth.make_wideband_stream(nb, dev)
+wide, _, _ = make("frontend", nb, dev)
 ms = timeit(lambda: trx.channelize(wide, nb))
 report("channelize_kernel", "Channelizer::rotate, 768-sample blocks", nb, "blocks", nb * (768 * 4 + 4 * 192 * 8), ms)
 ch = trx.channelize(wide, nb)

@@ -9,25 +9,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from osmo_trx_amd import TrxHip, synth
+from workloads import make
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
 loads = sys.argv[2:] or ["nb", "nb63", "rach", "ext", "mixed"]
 trx = TrxHip(0)
 dev = "cuda:0"
 tot = {"bursts": 0, "reruns": 0}
+WL = {"nb": ("normal", 0), "rach": ("rach", 2), "ext": ("ext", 3), "mixed": ("mixed", 4)}   # workload, seed offset
 for wl in loads:
     for rep in range(4 if wl == "nb" else 1):
         seed = synth.SEED + 7919 * rep
-        if wl == "nb":
-            iq, p, _ = synth.make_normal_bursts(n, dev, 4, seed=seed)
-        elif wl == "nb63":
+        if wl == "nb63":
             iq, p, _ = synth.make_normal_bursts(n, dev, 4, seed=seed + 1, max_toa=33, delay_sym=(-2.0, 30.0))
-        elif wl == "rach":
-            iq, p, _ = synth.make_access_bursts(n, dev, seed=seed + 2)
-        elif wl == "ext":
-            iq, p, _ = synth.make_access_bursts(n, dev, seed=seed + 3, ext=True)
-        elif wl == "mixed":
-            iq, p = synth.make_mixed_bursts(n, dev, seed=seed + 4)
+        elif wl in WL:
+            iq, p, _ = make(WL[wl][0], n, dev, seed=seed + WL[wl][1])
         else:
             raise SystemExit(wl)
         dp = trx.params_tensor(p)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generator of the hand-placed instruction blocks of the normal-burst kernel (osmo_trx_amd/csrc/trx_kernel_nb.hip).
 
-    python tools/gen_nb_asm.py            # writes osmo_trx_amd/csrc/trx_nb_asm.inc (committed next to this script)
+    python tools/gen_nb_asm.py [OUT]      # writes osmo_trx_amd/csrc/trx_nb_asm.inc (committed), or OUT
 
 Why generated: hipcc treats an `asm` statement as one opaque instruction -- it pads neither the hazards nor the memory
 waits of what is inside, and it pads every boundary between two dependent asm statements with an s_nop of its own.  The
@@ -910,7 +910,7 @@ def c_string(lines):
     return "\n".join(out)
 
 
-def main():
+def main(out=OUT):
     sys.path.insert(0, ROOT)
     # LDS layout of the kernel's tables (must match trx_kernel_nb.hip; the kernel static_asserts these numbers)
     SINCV_LDS = 4096 + 32
@@ -953,9 +953,9 @@ def main():
     if errs:
         print("\n".join(errs))
         sys.exit(1)
-    open(OUT, "w").write("\n".join(hdr) + "\n")
-    print("wrote", os.path.relpath(OUT, ROOT), {k: len([t for t in b.text() if Block.parse(t)]) for k, b in blocks.items()})
+    open(out, "w").write("\n".join(hdr) + "\n")
+    print("wrote", os.path.relpath(out, ROOT), {k: len([t for t in b.text() if Block.parse(t)]) for k, b in blocks.items()})
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:2])

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction accounting of one kernel from `hipcc -S -gline-tables-only` output: per basic block, the
-instruction mix (VALU / SALU / LDS / VMEM / other) and the source lines it came from.
+instruction mix (VALU / SALU / LDS / VMEM / other) and the source lines it came from; --lines: totals per source line
+(branches, which count as SALU, also on their own) and over the kernel.
    hipcc --offload-arch=gfx950 --cuda-device-only -S -gline-tables-only -O3 -std=c++17 -ffp-contract=off -Iinclude \
          -o /tmp/k4.s osmo_trx_amd/csrc/trx_kernel4.hip
    python tools/isa_blocks.py /tmp/k4.s 'burst_pull4_kernelILb0ELb0E' [--lines]"""
@@ -58,6 +59,8 @@ def main():
         c = classify(op)
         cur[1][c] += 1
         cur[2][(loc[0], loc[1], c)] += 1
+        if op.startswith(("s_branch", "s_cbranch")):
+            cur[2][(loc[0], loc[1], "br")] += 1
     if by_line:
         tot = collections.Counter()
         for b in blocks:
@@ -68,14 +71,16 @@ def main():
             rows[(f, l)][c] += n
         for (f, l) in sorted(rows):
             r = rows[(f, l)]
-            print(f"{f}:{l:5d}  valu {r['valu']:5d} salu {r['salu']:5d} lds {r['lds']:4d} vmem {r['vmem']:3d} wait {r['wait']:4d}")
+            print(f"{f}:{l:5d}  valu {r['valu']:5d} salu {r['salu']:5d} lds {r['lds']:4d} vmem {r['vmem']:3d} wait {r['wait']:4d} br {r['br']:3d}")
+        print("total", dict(sum(rows.values(), collections.Counter())))
         return
     for lab, cnt, lines in blocks:
         if sum(cnt.values()) == 0:
             continue
         ls = collections.Counter()
         for (f, l, c), n in lines.items():
-            ls[(f, l)] += n
+            if c != "br":
+                ls[(f, l)] += n
         top = ", ".join(f"{f.replace('trx_', '').replace('.hip', '').replace('.h', '')}:{l}x{n}" for (f, l), n in ls.most_common(4))
         print(f"{lab:12s} valu {cnt['valu']:4d} salu {cnt['salu']:4d} lds {cnt['lds']:3d} vmem {cnt['vmem']:2d} wait {cnt['wait']:3d} | {top}")
 

@@ -4,17 +4,14 @@
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from osmo_trx_amd import TrxHip, synth, trxhip
+from osmo_trx_amd import TrxHip, trxhip
+from workloads import make
 n = int(os.environ.get('N_BURSTS', str(1 << 17)))
 trx = TrxHip(0)
 L = trxhip.load_library()
 L.trxhip_diag_read.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
 wl = os.environ.get('WORKLOAD', 'normal')
-if wl in ('rach', 'ext'):
-    iq, params, _ = synth.make_access_bursts(n, "cuda:0", ext=(wl == 'ext'))
-else:
-    iq, params, _ = synth.make_normal_bursts(n, "cuda:0", 4)
-kw = dict(soft_stride=148, slice_bits=True, exact=(wl == 'exact'))
+iq, params, kw = make(wl, n)
 dp = trx.params_tensor(params)
 trx.detect_demod(iq, dp, **kw); torch.cuda.synchronize()
 buf = (C.c_ulonglong * 32)()

@@ -4,12 +4,13 @@
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from osmo_trx_amd import TrxHip, synth, trxhip
+from osmo_trx_amd import TrxHip, trxhip
+from workloads import make
 n = int(os.environ.get('N_BURSTS', str(1 << 20)))
 trx = TrxHip(0)
 L = trxhip.load_library()
 L.trxhip_diag_read.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-iq, params, _ = synth.make_normal_bursts(n, "cuda:0", 4)
+iq, params, _ = make("normal", n)
 dp = trx.params_tensor(params)
 for _ in range(40):
     trx.detect_demod(iq, dp, sps=4)

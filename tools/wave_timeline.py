@@ -4,21 +4,16 @@
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
-from osmo_trx_amd import TrxHip, synth, trxhip
+from osmo_trx_amd import TrxHip, trxhip
+from workloads import make
 n = int(os.environ.get('N_BURSTS', str(1 << 20)))
 trx = TrxHip(0)
 L = trxhip.load_library()
 L.trxhip_diag_read_waves.argtypes = [C.c_void_p, C.c_int]
-wl = os.environ.get('WORKLOAD', 'normal')
-if wl == 'mixed':
-    iq, params = synth.make_mixed_bursts(n, "cuda:0")
-elif wl == 'rach':
-    iq, params, _ = synth.make_access_bursts(n, "cuda:0")
-else:
-    iq, params, _ = synth.make_normal_bursts(n, "cuda:0", 4)
+iq, params, kw = make(os.environ.get('WORKLOAD', 'normal'), n)
 dp = trx.params_tensor(params)
 for _ in range(3):
-    trx.detect_demod(iq, dp, soft_stride=148, slice_bits=True); torch.cuda.synchronize()
+    trx.detect_demod(iq, dp, **kw); torch.cuda.synchronize()
 W = 4096
 buf = np.zeros((W, 24), dtype=np.uint64)
 L.trxhip_diag_read_waves(buf.ctypes.data, W)
