@@ -184,6 +184,9 @@ uint64_t trxhip_tables_checksum(const void *h_blob, size_t size);     /* FNV-1a 
  *              truncated to soft_stride.  Unused tail and undetected bursts are zero-filled.
  *   flags    : TRXHIP_FLAG_* bits
  *   sps      : 1 or 4; burst_len: 625 @4 SPS (>= 624), 156/157 @1 SPS
+ * Asynchronous on `stream`, with two exceptions on the kernel split (trxhip_set_nb_kernel()): the call waits until the split
+ * launch four split launches back on this context has completed (its leftover list is reused), and when a batch is larger
+ * than that list has room for, the hipFree / hipMalloc that grow it can wait for the device.
  */
 int trxhip_detect_demod_batch(trxhip_ctx *ctx,
 			      const int16_t *d_iq, const trxhip_burst_params *d_params,

@@ -12,6 +12,7 @@
 
 #include "trx_tables.h"
 #include "../../include/trxhip.h"
+#include "trx_launch.h"
 
 typedef float2 c32;
 

@@ -11,49 +11,8 @@
 
 #include "../../include/trxhip.h"
 #include "trx_tables.h"
-
-// kernel launchers (trx_kernels.hip, trx_aux_kernels.hip)
-extern "C" int trx_launch_pull(unsigned *d_pool_ctr, const void *d_iq, int cf32, const trxhip_burst_params *d_params,
-			       trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, const float *d_ebp_in,
-			       size_t n_bursts, int L, int sps, float thresh, float full_scale,
-			       int soft_stride, int slice, int n_cu, hipStream_t stream);
-extern "C" int trx_launch_pull4_nb(unsigned *d_pool_ctr, const void *d_iq, const trxhip_burst_params *d_params,
-				   trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, size_t n_bursts,
-				   float thresh, float full_scale, int n_cu, unsigned *d_redo, unsigned *h_left, hipStream_t stream);
-extern "C" int trx_unit_masks_match(const trx_tables *t);       /* trx_kernel4.hip: compiled-in sign masks vs the tables */
-extern "C" int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride,
-				    uint8_t *d_pkt, size_t n_bursts, float rssi_offset, hipStream_t stream);
-extern "C" int trx_launch_convolve(const float *d_x, int x_len, const float *d_h, int h_len, int h_complex,
-				   float *d_y, int y_len, int start, int len, size_t n_vec, hipStream_t stream);
-extern "C" int trx_launch_convert_short_float(float *d_out, const int16_t *d_in, size_t len, hipStream_t stream);
-extern "C" int trx_launch_convert_float_short(int16_t *d_out, const float *d_in, float scale, size_t len, hipStream_t stream);
-extern "C" int trx_launch_dft_strided(const float *d_in, float *d_out, int m, size_t howmany, size_t istride, size_t ostride,
-				      int reverse, hipStream_t stream);
-extern "C" int trx_launch_frontend_fused(const int16_t *d_wide, float *d_out, size_t n_total, int p, int q, size_t out_stride,
-					 const float *parts, const trx_tables *d_tab, void *d_wide_hist_io, const void *d_chan_hist_in,
-					 void *d_chan_hist_out, hipStream_t stream);
-extern "C" int trx_launch_channelize(const int16_t *d_in, float *d_out, size_t n_total, size_t out_stride,
-				     const trx_tables *d_tab, void *d_hist_io, hipStream_t stream);
-extern "C" int trx_launch_resample(const float *d_in, float *d_out, size_t n_in, int p, int q, size_t n_chan,
-				   size_t in_stride, size_t out_stride, const float *d_parts, void *d_hist_io, hipStream_t stream);
-
-extern "C" int trx_launch_energy_detect(const float *d_x, size_t n_bursts, int burst_len, unsigned window, float *d_out,
-					hipStream_t stream);
-extern "C" int trx_launch_sch_detect(const float *d_iq, size_t buf_stride, trxhip_burst_result *d_results,
-				     const trx_tables *d_tab, size_t n_bufs, int len, int start, int toa_sub, float thresh,
-				     int unit_tables, hipStream_t stream);
-extern "C" int trx_unit_mask_sch_match(const trx_tables *t);   /* trx_sch.hip: the SCH sequence's compiled-in sign mask vs the tables */
-extern "C" int trx_launch_delay_vector(const float *d_in, float *d_out, const float *d_delays, const trx_tables *d_tab,
-				       size_t n_vec, int len, hipStream_t stream);
-extern "C" int trx_launch_scale_vector(float *d_x, size_t len, float sr, float si, hipStream_t stream);
-extern "C" int trx_launch_va_demod(const float *d_iq, const trxhip_burst_params *d_params,
-				   const trxhip_burst_result *d_detected, float *d_soft, int32_t *d_starts,
-				   size_t n_bursts, int L, float scale, int soft_stride, int flags, hipStream_t stream);
-extern "C" int trx_launch_vector_slicer(float *d_dst, const float *d_src, size_t len, hipStream_t stream);
-
 #include "trx_ctx.h"
-
-extern "C" int trx_fast_stats_read(unsigned long long *out4, int reset);   /* trx_kernel4.hip */
+#include "trx_launch.h"
 
 extern "C" {
 
@@ -133,30 +92,15 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 		return TRXHIP_ENOMEM;
 	ctx->device = device;
 	ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-	ctx->d_tables = nullptr;
 	ctx->no_unit = trx_unit_masks_match(t) ? 0 : 1;
 	ctx->sch_unit = trx_unit_mask_sch_match(t) ? 1 : 0;
-	ctx->d_pool = nullptr;
-	ctx->pool_next.store(0u);
 	ctx->pool_enabled = getenv("TRXHIP_NO_POOL") ? 0 : 1;          /* measurement switch, read once per context */
 	ctx->nb_enabled = getenv("TRXHIP_NO_NB_KERNEL") ? 0 : 1;       /* the same for the normal-burst kernel (A/B against the general one) */
-	ctx->redo_next = 0;
-	for (int i = 0; i < TRX_REDO_SLOTS; i++) {
-		ctx->redo[i].d = nullptr;
-		ctx->redo[i].cap = 0;
-		ctx->redo[i].ev = nullptr;
-		ctx->redo[i].busy = 0;
-		ctx->redo[i].h_left = nullptr;
-		ctx->redo[i].n_last = 0;
-	}
-	ctx->split_backoff = 0;
-	ctx->no_sym = 0;                                           /* the straight-line decimator reads taps 0..7 and mirrors them */
-	for (int k = 0; k < 8; k++)
+	for (int k = 0; k < 8; k++)                                    /* the straight-line decimator reads taps 0..7 and mirrors them */
 		if (memcmp(&t->dec_taps[k], &t->dec_taps[15 - k], sizeof(float)) != 0)
 			ctx->no_sym = 1;
 	/* the FAST detector's margin assumes sum_u |w_u| <= 2.6 for the 16 sinc weights of every fractional position
 	 * (trx_device.h, TRX_FAST_W): taps i <= fl use q = 512 k + f, taps i > fl use q = 512 k + (512 - f), k = 0 .. 7 */
-	ctx->no_fast = 0;
 	for (int f = 0; f < 512 && !ctx->no_fast; f++) {
 		double sum = 0.0;
 		for (int k = 0; k < 8; k++) {
@@ -168,14 +112,18 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 		if (!(sum <= 2.6))
 			ctx->no_fast = 1;
 	}
+	int rc = TRXHIP_OK;
 	if (hipMalloc(reinterpret_cast<void **>(&ctx->d_tables), sizeof(trx_tables)) != hipSuccess) {
-		delete ctx;
-		return TRXHIP_ENOMEM;
+		ctx->d_tables = nullptr;
+		rc = TRXHIP_ENOMEM;
+	} else if (hipMemcpy(ctx->d_tables, h_blob, sizeof(trx_tables), hipMemcpyHostToDevice) != hipSuccess) {
+		rc = TRXHIP_EIO;
+	} else if (!ctx->redo.create()) {
+		rc = TRXHIP_ENOMEM;
 	}
-	if (hipMemcpy(ctx->d_tables, h_blob, sizeof(trx_tables), hipMemcpyHostToDevice) != hipSuccess) {
-		(void)hipFree(ctx->d_tables);
-		delete ctx;
-		return TRXHIP_EIO;
+	if (rc != TRXHIP_OK) {
+		trxhip_destroy(ctx);
+		return rc;
 	}
 	if (hipMalloc(reinterpret_cast<void **>(&ctx->d_pool), TRX_POOL_SLOTS * 64) != hipSuccess ||
 	    hipMemset(ctx->d_pool, 0, TRX_POOL_SLOTS * 64) != hipSuccess) {
@@ -207,12 +155,7 @@ void trxhip_destroy(trxhip_ctx *ctx)
 	if (hipSetDevice(ctx->device) == hipSuccess) {
 		if (ctx->d_tables) (void)hipFree(ctx->d_tables);
 		if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-		for (int i = 0; i < TRX_REDO_SLOTS; i++) {
-			if (ctx->redo[i].busy) (void)hipEventSynchronize(ctx->redo[i].ev);
-			if (ctx->redo[i].ev) (void)hipEventDestroy(ctx->redo[i].ev);
-			if (ctx->redo[i].d) (void)hipFree(ctx->redo[i].d);
-			if (ctx->redo[i].h_left) (void)hipHostFree(ctx->redo[i].h_left);
-		}
+		ctx->redo.destroy();
 	}
 	delete ctx;
 }
@@ -286,79 +229,50 @@ static int pull_common(trxhip_ctx *ctx, const void *d_iq, int cf32, const trxhip
 		flags |= TRX_IFLAG_NO_SYM;
 	if (ctx->no_fast)
 		flags |= TRX_IFLAG_NO_FAST;
+	const hipStream_t st = static_cast<hipStream_t>(stream);
+
+	/* ---- the kernel choice ---- */
 	/* A launch that is being captured into a HIP graph keeps whatever it is handed for as long as the graph lives, and replays
 	 * may overlap later launches: it gets neither a pool counter pair (static split) nor a leftover list (general kernel only) --
 	 * both are recycled between launches. */
 	hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-	const bool capturing = stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cap) == hipSuccess &&
-			       cap != hipStreamCaptureStatusNone;
-	/* a counter pair for this launch (zero: the previous user's last workgroup re-armed it; trx_ctx.h) */
+	const bool capturing = st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+	const bool exact = (flags & TRXHIP_FLAG_EXACT_DEMOD) != 0;
+	/* the transceiver's 4-SPS burst size gets the production kernel (polyphase LDS layout, fused or exact demodulator) */
+	const bool k4 = sps == 4 && burst_len >= 624 && burst_len <= 628;
+	/* the launch pullRadioVector() makes: 625 samples, sliced rows of 148 soft bits, no flag but SLICE (and EXACT_DEMOD), none
+	 * of the internal TRX_IFLAG_* bits -- the 4-SPS kernel's COMMON instance folds these parameters, except with cf32 and exact
+	 * together */
+	const bool common = k4 && burst_len == 625 && d_soft && !d_ebp_in && soft_stride == 148 &&
+			    (flags & ~TRXHIP_FLAG_EXACT_DEMOD) == TRXHIP_FLAG_SLICE && !(cf32 && exact);
+	/* ... and with int16 input and the fused demodulator it is the split: the normal-burst kernel over the batch, then the
+	 * general kernel over whatever it left on its list */
+	const bool split = common && !cf32 && !exact && ctx->nb_enabled && !few_nb && !capturing;
+	/* a counter pair of the 4-SPS kernels' cross-die pool for this launch (zero: the previous user's last workgroup re-armed it;
+	 * trx_ctx.h).  The pool needs the persistent grid (one workgroup per CU) and >= 8 groups of 16 bursts per workgroup. */
 	unsigned *pool = nullptr;
-	if (ctx->d_pool && ctx->pool_enabled && !capturing && n_bursts >= (size_t)ctx->n_cu * 128)
+	if (k4 && ctx->d_pool && ctx->pool_enabled && !capturing && n_bursts >= (size_t)ctx->n_cu * 128)
 		pool = ctx->d_pool + (size_t)(ctx->pool_next.fetch_add(1u, std::memory_order_relaxed) % TRX_POOL_SLOTS) * 16;
-	/* The call pullRadioVector() makes for its traffic slots (int16 bursts of 625 samples at 4 SPS, fused demodulator, sliced rows
-	 * of 148 soft bits): the normal-burst kernel over the batch, then the general kernel over whatever it left on its list. */
-	if (ctx->nb_enabled && !few_nb && !capturing && !cf32 && !d_ebp_in && sps == 4 && burst_len == 625 && d_soft && soft_stride == 148 &&
-	    flags == TRXHIP_FLAG_SLICE) {
-		std::lock_guard<std::mutex> lk(ctx->redo_mu);
-		if (ctx->split_backoff) {
-			ctx->split_backoff--;                                   /* a recent batch left too much: the general kernel alone */
-			return trx_launch_pull(pool, d_iq, cf32, d_params, d_results, d_soft, ctx->d_tables, d_ebp_in, n_bursts, burst_len, sps,
-					       threshold, full_scale, soft_stride, flags, ctx->n_cu, static_cast<hipStream_t>(stream));
-		}
-		trxhip_ctx::redo_slot &sl = ctx->redo[ctx->redo_next++ % TRX_REDO_SLOTS];
-		bool ok = true;
-		if (sl.busy) {
-			ok = hipEventSynchronize(sl.ev) == hipSuccess;
-			sl.busy = 0;
-			if (ok && sl.h_left && sl.n_last && (size_t)*reinterpret_cast<volatile unsigned *>(sl.h_left) * 32 > sl.n_last)
-				ctx->split_backoff = 63;
-		}
-		if (ok && !sl.h_left)
-			ok = hipHostMalloc(reinterpret_cast<void **>(&sl.h_left), 64, hipHostMallocDefault) == hipSuccess;
-		if (ok) {
-			*sl.h_left = 0u;
-			sl.n_last = n_bursts;
-		}
-		if (ok && !sl.ev)
-			ok = hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) == hipSuccess;
-		if (ok && sl.cap < n_bursts) {
-			if (sl.d) (void)hipFree(sl.d);
-			sl.d = nullptr;
-			sl.cap = 0;
-			const size_t cap_new = n_bursts < 65536 ? 65536 : n_bursts;
-			/* header words + one flag byte per burst, padded to whole chunks of 256; all zero between launches */
-			const size_t bytes = TRX_REDO_HDR * sizeof(unsigned) + ((cap_new + 255) & ~(size_t)255);
-			/* (the memset runs on the null stream: drained before a kernel on the caller's -- possibly non-blocking -- stream
-			 * may touch the buffer; this is the allocation path, a handful of calls per context) */
-			ok = hipMalloc(reinterpret_cast<void **>(&sl.d), bytes) == hipSuccess && hipMemset(sl.d, 0, bytes) == hipSuccess &&
-			     hipDeviceSynchronize() == hipSuccess;
-			if (ok)
-				sl.cap = cap_new;
-			else if (sl.d) {
-				(void)hipFree(sl.d);
-				sl.d = nullptr;
-			}
-		}
-		if (ok) {
-			const int rc = trx_launch_pull4_nb(pool, d_iq, d_params, d_results, d_soft, ctx->d_tables, n_bursts, threshold, full_scale,
-							   ctx->n_cu, sl.d, sl.h_left, static_cast<hipStream_t>(stream));
-			if (rc == 0 && hipEventRecord(sl.ev, static_cast<hipStream_t>(stream)) == hipSuccess)
-				sl.busy = 1;
-			else if (rc == 0)
-				(void)hipStreamSynchronize(static_cast<hipStream_t>(stream));   /* no event: the slot is free once the stream has drained */
+
+	if (!k4) {
+		/* NLD: dword loads per lane held in registers for the prefetched burst (0: generic length, no prefetch) */
+		const int nld = sps == 1 ? 3 : burst_len <= 640 ? 10 : 0;
+		return trx_launch_pull(d_iq, cf32, nld, d_params, d_results, d_soft, ctx->d_tables, d_ebp_in, n_bursts, burst_len, sps,
+				       threshold, full_scale, soft_stride, flags, ctx->n_cu, st);
+	}
+	if (split) {
+		std::lock_guard<std::mutex> lk(ctx->redo.mu);
+		if (trx_redo_lists::slot *sl = ctx->redo.acquire(n_bursts, st)) {
+			const int rc = trx_launch_pull4_nb(pool, d_iq, d_params, d_results, d_soft, ctx->d_tables, n_bursts, threshold,
+							   full_scale, ctx->n_cu, sl->d, sl->h_left, st);
+			ctx->redo.launched(*sl, rc, st);
 			return rc;
 		}
-		/* (no list buffer: fall through to the general kernel) */
+		/* (back-off, or no list buffer: the general kernel alone) */
 	}
-	return trx_launch_pull(pool, d_iq, cf32, d_params, d_results, d_soft, ctx->d_tables, d_ebp_in, n_bursts, burst_len, sps,
-			       threshold, full_scale, soft_stride, flags, ctx->n_cu, static_cast<hipStream_t>(stream));
+	return trx_launch_pull4(pool, d_iq, cf32, exact, common, d_params, d_results, d_soft, ctx->d_tables, d_ebp_in, n_bursts,
+				burst_len, threshold, full_scale, soft_stride, flags, ctx->n_cu, st);
 }
-
-extern "C" int trx_launch_diversity_select(const int16_t *d_iq_paths, size_t n_bursts, int n_paths, int burst_len, int sps,
-					   int16_t *d_iq_sel, float *d_avg_energy, uint8_t *d_path, hipStream_t stream);
-extern "C" int trx_launch_diversity_power(trxhip_burst_result *d_res, const trxhip_burst_params *d_params, const float *d_avg_energy,
-					  size_t n_bursts, float full_scale, hipStream_t stream);
 
 int trxhip_select_diversity_batch(trxhip_ctx *ctx, const int16_t *d_iq_paths, size_t n_bursts, int n_paths, int burst_len, int sps,
 				  int16_t *d_iq_sel, float *d_avg_energy, uint8_t *d_path, void *stream)

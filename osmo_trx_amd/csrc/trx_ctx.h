@@ -7,14 +7,104 @@
 #include "../../include/trxhip.h"
 #include "trx_tables.h"
 
+#define TRX_POOL_SLOTS 1024
+#define TRX_REDO_SLOTS 4
+
+/* The lists of bursts the normal-burst kernel (trx_kernel_nb.hip) leaves to the general kernel: TRX_REDO_SLOTS device buffers of
+ * TRX_REDO_HDR words + one flag byte per burst, handed out round-robin per split launch under `mu` (held from acquire() to
+ * launched()).  A slot's header is zero between launches (the general kernel's last workgroup re-arms it); its event marks the
+ * end of the launch pair that used it last -- a slot is only handed out again (or re-allocated larger) once that event has
+ * completed.
+ * Feedback: the general kernel reports (into the slot's pinned word h_left) how many bursts the normal-burst kernel left it.
+ * Read when the slot comes round again: a batch that left more than 1/32 of its bursts -- slots of other types the caller gave
+ * no hint about -- makes the next 63 eligible launches run the general kernel alone (every left burst is read twice and stalls
+ * the first kernel's prefetch), then one launch probes again. */
+struct trx_redo_lists {
+	struct slot {
+		unsigned *d = nullptr;
+		size_t cap = 0;                /* bursts the buffer d has room for */
+		hipEvent_t ev = nullptr;
+		bool busy = false;             /* ev recorded after a launch that has not been waited for */
+		unsigned *h_left = nullptr;    /* pinned */
+		size_t n_last = 0;             /* bursts of the launch that used the slot last */
+	};
+	std::mutex mu;
+	slot s[TRX_REDO_SLOTS];
+	unsigned next = 0;
+	unsigned backoff = 0;
+
+	/* every slot's event and pinned word; false: out of memory (destroy() releases what was made) */
+	bool create()
+	{
+		for (slot &sl : s)
+			if (hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) != hipSuccess ||
+			    hipHostMalloc(reinterpret_cast<void **>(&sl.h_left), 64, hipHostMallocDefault) != hipSuccess)
+				return false;
+		return true;
+	}
+	/* the slot for a split launch of n bursts on `stream`, or NULL: back-off, or no list buffer (the general kernel alone) */
+	slot *acquire(size_t n, hipStream_t stream)
+	{
+		if (backoff) {
+			backoff--;
+			return nullptr;
+		}
+		slot &sl = s[next++ % TRX_REDO_SLOTS];
+		if (sl.busy) {
+			sl.busy = false;
+			if (hipEventSynchronize(sl.ev) != hipSuccess)
+				return nullptr;
+			if (sl.n_last && (size_t)*reinterpret_cast<volatile unsigned *>(sl.h_left) * 32 > sl.n_last)
+				backoff = 63;
+		}
+		*sl.h_left = 0u;
+		sl.n_last = n;
+		if (sl.cap < n) {
+			if (sl.d) (void)hipFree(sl.d);
+			sl.d = nullptr;
+			sl.cap = 0;
+			const size_t cap = n < 65536 ? 65536 : n;
+			/* header words + one flag byte per burst, padded to whole chunks of 256; all zero between launches.  The memset
+			 * goes on the caller's stream, ahead of the two kernels that use the buffer (the slot's last launch has completed) */
+			const size_t bytes = TRX_REDO_HDR * sizeof(unsigned) + ((cap + 255) & ~(size_t)255);
+			if (hipMalloc(reinterpret_cast<void **>(&sl.d), bytes) != hipSuccess || hipMemsetAsync(sl.d, 0, bytes, stream) != hipSuccess) {
+				if (sl.d) (void)hipFree(sl.d);
+				sl.d = nullptr;
+				return nullptr;
+			}
+			sl.cap = cap;
+		}
+		return &sl;
+	}
+	/* after the launch into sl (rc: its result) */
+	void launched(slot &sl, int rc, hipStream_t stream)
+	{
+		if (rc != 0)
+			return;
+		if (hipEventRecord(sl.ev, stream) == hipSuccess)
+			sl.busy = true;
+		else
+			(void)hipStreamSynchronize(stream);   /* no event: the slot is free once the stream has drained */
+	}
+	void destroy()
+	{
+		for (slot &sl : s) {
+			if (sl.busy) (void)hipEventSynchronize(sl.ev);
+			if (sl.ev) (void)hipEventDestroy(sl.ev);
+			if (sl.d) (void)hipFree(sl.d);
+			if (sl.h_left) (void)hipHostFree(sl.h_left);
+		}
+	}
+};
+
 struct trxhip_ctx {
-	int device;
-	int n_cu;
-	trx_tables *d_tables;
-	int no_unit;        /* tables do not have the compiled-in unit structure: keep the multiplying correlation */
-	int sch_unit;       /* the SCH sequence has the unit structure the kernel's compiled-in mask expects (trx_sch.hip) */
-	int no_sym;         /* decimator taps not bitwise symmetric: the kernels' straight-line paths (mirrored taps) are off */
-	int no_fast;        /* sinc LUT row sums above TRX_FAST_W: the fused kernels' FAST detector (proven margins) is off */
+	int device = 0;
+	int n_cu = 0;
+	trx_tables *d_tables = nullptr;
+	int no_unit = 0;    /* tables do not have the compiled-in unit structure: keep the multiplying correlation */
+	int sch_unit = 0;   /* the SCH sequence has the unit structure the kernel's compiled-in mask expects (trx_sch.hip) */
+	int no_sym = 0;     /* decimator taps not bitwise symmetric: the kernels' straight-line paths (mirrored taps) are off */
+	int no_fast = 0;    /* sinc LUT row sums above TRX_FAST_W: the fused kernels' FAST detector (proven margins) is off */
 	/* cross-die work pool of the 4-SPS kernel (trx_kernel4.hip): TRX_POOL_SLOTS counter pairs {drawn, workgroups done} of 64
 	 * bytes each, handed out round-robin PER LAUNCH.  The kernel re-arms its pair itself -- the last workgroup to finish
 	 * zeroes both words -- so there is no memset in front of a launch: nothing that two host threads launching on one stream
@@ -22,35 +112,12 @@ struct trxhip_ctx {
 	 * memset B, kernel A, kernel B left kernel B without a pool), no table of streams that fills up, and a launch
 	 * captured into a HIP graph is complete in itself (replays of one graph serialise).  Two launches share a pair only when
 	 * they are TRX_POOL_SLOTS pooled launches apart and still overlap -- 1024 outstanding batches of >= 32768 bursts. */
-	unsigned *d_pool;
-	int pool_enabled;                  /* trxhip_set_work_pool(); default 1, 0 when TRXHIP_NO_POOL is set at creation */
-	std::atomic<unsigned> pool_next;
-	/* The normal-burst kernel (trx_kernel_nb.hip) and the list of bursts it leaves to the general kernel: TRX_REDO_SLOTS device
-	 * buffers of TRX_REDO_HDR words + one flag byte per burst, handed out round-robin per launch under redo_mu.  A slot's header is zero
-	 * between launches (the general kernel's last workgroup re-arms it); its event marks the end of the launch pair that used
-	 * it last -- a slot is only handed out again (or re-allocated larger) once that event has completed. */
-	int nb_enabled;                    /* trxhip_set_nb_kernel(); default 1, 0 when TRXHIP_NO_NB_KERNEL is set at creation */
-	std::mutex redo_mu;
-	struct redo_slot { unsigned *d; size_t cap; hipEvent_t ev; int busy; unsigned *h_left; size_t n_last; } redo[4];
-	unsigned redo_next;
-	/* Feedback: the general kernel reports (into the slot's pinned word h_left) how many bursts the normal-burst kernel left it.
-	 * Read when the slot comes round again (its event has completed by then): a batch that left more than 1/32 of its bursts --
-	 * slots of other types the caller gave no hint about -- makes the next 63 eligible launches run the general kernel alone
-	 * (every left burst is read twice and stalls the first kernel's prefetch), then one launch probes again. */
-	unsigned split_backoff;
+	unsigned *d_pool = nullptr;
+	int pool_enabled = 1;              /* trxhip_set_work_pool(); 0 when TRXHIP_NO_POOL is set at creation */
+	std::atomic<unsigned> pool_next{0u};
+	int nb_enabled = 1;                /* trxhip_set_nb_kernel(); 0 when TRXHIP_NO_NB_KERNEL is set at creation */
+	trx_redo_lists redo;
 };
-#define TRX_POOL_SLOTS 1024
-#define TRX_REDO_SLOTS 4
-
-/* the TRXD wire packer's launcher (trx_aux_kernels.hip); d_results_copy (may be NULL): every result record is also written
- * there -- the host pipe points it at pinned memory and saves the download */
-extern "C" int trx_launch_pack_trxd_wire(const trxhip_burst_result *d_results, const trxhip_burst_params *d_params,
-					 const float *d_soft, int soft_stride, const trxhip_trxd_meta *d_meta, uint8_t *d_pkt,
-					 int pkt_stride, uint16_t *d_pkt_len, size_t n_bursts, float rssi_offset, hipStream_t stream,
-					 trxhip_burst_result *d_results_copy);
-
-/* bursts by reference (trx_aux_kernels.hip): n bursts of `dwords` 4-byte words each from the device-side addresses d_src[] */
-extern "C" int trx_launch_gather_bursts(const unsigned long long *d_src, void *d_dst, size_t n, unsigned dwords, hipStream_t stream);
 
 static inline int with_device(const trxhip_ctx *ctx)
 {

@@ -36,22 +36,33 @@
 
 typedef float2 c32;
 
-// The > 64 KB dynamic-LDS opt-in is a per-kernel, per-device attribute: arm it ONCE with the kernel's maximum (160 KB)
-// instead of the size of the current call -- concurrent callers with different sizes (the C ABI allows calls from
-// several host threads) would otherwise race between one thread's hipFuncSetAttribute and another's launch.
-#define TRX_ARM_DYNAMIC_LDS(kernel_ptr)                                                                          \
-	do {                                                                                                     \
-		static std::atomic<unsigned long long> armed_{0ull};                                             \
-		int dev_ = 0;                                                                                    \
-		if (hipGetDevice(&dev_) != hipSuccess) return TRXHIP_EIO;                                        \
-		const unsigned long long bit_ = 1ull << (dev_ & 63);                                             \
-		if (!(armed_.load(std::memory_order_acquire) & bit_)) {                                          \
-			if (hipFuncSetAttribute((const void *)(kernel_ptr), hipFuncAttributeMaxDynamicSharedMemorySize, \
-						160 * 1024) != hipSuccess)                                        \
-				return TRXHIP_EIO;                                                               \
-			armed_.fetch_or(bit_, std::memory_order_release);                                        \
-		}                                                                                                \
-	} while (0)
+// The > 64 KB dynamic-LDS opt-in is a per-kernel, per-device attribute: arm it ONCE per kernel and device with a fixed size
+// (the kernel's maximum, 160 KB unless the launcher knows better) instead of the size of the current call -- concurrent callers
+// with different sizes (the C ABI allows calls from several host threads) would otherwise race between one thread's
+// hipFuncSetAttribute and another's launch.  The kernel is a template argument, not a parameter: every kernel gets its own
+// flag word, including instances of one kernel template that share a function type.
+template <auto K>
+static int trx_arm_dynamic_lds(int bytes = 160 * 1024)
+{
+	static std::atomic<unsigned long long> armed{0ull};
+	int dev = 0;
+	if (hipGetDevice(&dev) != hipSuccess)
+		return TRXHIP_EIO;
+	const unsigned long long bit = 1ull << (dev & 63);
+	if (!(armed.load(std::memory_order_acquire) & bit)) {
+		if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+			return TRXHIP_EIO;
+		armed.fetch_or(bit, std::memory_order_release);
+	}
+	return 0;
+}
+
+// grid of the burst kernels: work is handed out in groups of 16 bursts, at most max_grid workgroups
+static inline size_t trx_burst_grid(size_t n_bursts, size_t max_grid)
+{
+	const size_t need = (n_bursts + 15) / 16;
+	return need < max_grid ? need : max_grid;
+}
 
 // Diagnostic build only (-DTRX_DIAG, libtrxhip_diag.so): per-phase cycle accounting (s_memtime deltas summed over all
 // bursts by lane 0 of every wave; tools/phase_cycles.py, tools/phase_cycles_nb.py).  The product library is built without it.

@@ -19,6 +19,7 @@
 #include <new>
 
 #include "trx_ctx.h"
+#include "trx_launch.h"
 
 struct trxhip_hostpipe {
 	trxhip_ctx *ctx;

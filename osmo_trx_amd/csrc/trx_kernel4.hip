@@ -28,6 +28,7 @@
 //     wave's timeline per burst, to which every issue slot -- vector, scalar, wait -- adds the same.
 #include <atomic>
 #include "trx_device.h"
+#include "trx_launch.h"
 
 #include "trx_k4_common.h"
 
@@ -1108,7 +1109,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 		}
 	}
 	// LIST: the last workgroup to finish re-arms the header for the next launch that is handed it and reports the number of bursts
-	// this launch worked through to the host (pool_ctr: in this form a word of pinned host memory; trx_ctx.h, split_backoff)
+	// this launch worked through to the host (pool_ctr: in this form a word of pinned host memory; trx_ctx.h, trx_redo_lists)
 	if (LIST) {
 		if (lane == 0 && l_done)
 			__hip_atomic_fetch_add(redo + 2, l_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1156,6 +1157,12 @@ extern "C" int trx_unit_masks_match(const trx_tables *t)
 
 #include "trx_kernel_nb.hip"
 
+// LDS of a burst_pull4_kernel<cf32, exact, ...> workgroup: tables, one slice per wave, work counter + pool ring
+static inline size_t k4_lds_bytes(bool cf32, bool exact)
+{
+	return K4_TABLES_BYTES + (size_t)K4_WPB(cf32, exact) * K4_SLICE * sizeof(c32) + K4_LDS_TAIL;
+}
+
 // The normal-burst kernel over the whole batch, then the general kernel (fused demodulator, common launch parameters) over the
 // bursts the first one left behind (d_redo: TRX_REDO_HDR words of header + one flag byte per burst, padded to a multiple of
 // 256: all zero on entry and all zero again when the second kernel has finished).  Preconditions (the caller checks them): int16 input of 625 samples,
@@ -1166,63 +1173,45 @@ extern "C" int trx_launch_pull4_nb(unsigned *d_pool_ctr, const void *d_iq, const
 {
 	if (n_bursts == 0)
 		return 0;
-	const size_t need = (n_bursts + 15) / 16;
-	size_t grid = (size_t)n_cu;
-	if (grid > need) grid = need;
-	unsigned *const pool = (d_pool_ctr && grid == (size_t)n_cu && need >= 8 * grid) ? d_pool_ctr : nullptr;
+	const size_t grid = trx_burst_grid(n_bursts, (size_t)n_cu);
 	{
-		auto k = nb_pull4_kernel;
-		TRX_ARM_DYNAMIC_LDS(k);
+		constexpr auto k = nb_pull4_kernel;
+		if (trx_arm_dynamic_lds<k>())
+			return TRXHIP_EIO;
 		hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NB_WPB * WAVE), NB_LDS_BYTES, stream, reinterpret_cast<const uint32_t *>(d_iq),
-				   d_params, d_results, d_soft, d_tab, (unsigned)n_bursts, thresh, full_scale, pool, d_redo,
+				   d_params, d_results, d_soft, d_tab, (unsigned)n_bursts, thresh, full_scale, d_pool_ctr, d_redo,
 				   thresh * thresh * 0.2f, thresh * thresh * (1.0f / 6.0f), thresh * thresh * (1.0f / 7.0f), thresh * thresh * 0.125f);
 	}
 	{
-		auto k = burst_pull4_kernel<false, false, true, true>;
-		TRX_ARM_DYNAMIC_LDS(k);
-		const size_t lds = K4_TABLES_BYTES + (size_t)K4_WPB(false, false) * K4_SLICE * sizeof(c32) + K4_LDS_TAIL;
-		hipLaunchKernelGGL(k, dim3((unsigned)n_cu), dim3(K4_WPB(false, false) * WAVE), lds, stream, d_iq, d_params, d_results, d_soft, d_tab,
-				   (const float4 *)nullptr, (unsigned)n_bursts, 625, thresh, full_scale, 148, TRXHIP_FLAG_SLICE, h_left, d_redo);
+		constexpr auto k = burst_pull4_kernel<false, false, true, true>;
+		if (trx_arm_dynamic_lds<k>())
+			return TRXHIP_EIO;
+		hipLaunchKernelGGL(k, dim3((unsigned)n_cu), dim3(K4_WPB(false, false) * WAVE), k4_lds_bytes(false, false), stream, d_iq, d_params,
+				   d_results, d_soft, d_tab, (const float4 *)nullptr, (unsigned)n_bursts, 625, thresh, full_scale, 148,
+				   TRXHIP_FLAG_SLICE, h_left, d_redo);
 	}
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
 
-extern "C" int trx_launch_pull4(unsigned *d_pool_ctr, const void *d_iq, int cf32, const trxhip_burst_params *d_params,
-				trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, const float *d_ebp_in,
-				size_t n_bursts, int L, float thresh, float full_scale, int soft_stride, int flags, int n_cu,
-				hipStream_t stream)
+// burst_pull4_kernel<cf32, exact, common>, armed with its exact LDS size (COMMON: the instance with the common launch parameters
+// folded, see the kernel; never with cf32 and exact together)
+extern "C" int trx_launch_pull4(unsigned *d_pool_ctr, const void *d_iq, int cf32, int exact, int common, const trxhip_burst_params *d_params,
+				trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, const float *d_ebp_in, size_t n_bursts,
+				int L, float thresh, float full_scale, int soft_stride, int flags, int n_cu, hipStream_t stream)
 {
 	if (n_bursts == 0)
 		return 0;
-	const bool exact = (flags & TRXHIP_FLAG_EXACT_DEMOD) != 0;      // two kernels: the demodulator is a compile-time choice
-	const int wpb = K4_WPB(cf32 != 0, exact);
-	const size_t lds = K4_TABLES_BYTES + (size_t)wpb * K4_SLICE * sizeof(c32) + K4_LDS_TAIL;   // + work counter + pool ring
-	size_t need = (n_bursts + 15) / 16;                             // work is handed out in groups of 16 bursts
-	size_t grid = (size_t)n_cu;
-	if (grid > need) grid = need;
-	/* the instantiation with the common launch parameters folded (see the kernel) */
-	const bool common = (!cf32 || !exact) && L == 625 && d_soft && !d_ebp_in && soft_stride == 148 &&
-			    (flags & ~TRXHIP_FLAG_EXACT_DEMOD) == TRXHIP_FLAG_SLICE;
+	const size_t grid = trx_burst_grid(n_bursts, (size_t)n_cu);
+	const size_t lds = k4_lds_bytes(cf32, exact);
 #define LAUNCH4(CF_, EX_, CM_)                                                                                  \
 	do {                                                                                                    \
-		auto k = burst_pull4_kernel<CF_, EX_, CM_>;                                                     \
-		/* the > 64 KB dynamic-LDS opt-in is per kernel and device: once, not per launch (small batches) */ \
-		static std::atomic<unsigned long long> armed{0ull};                                             \
-		int dev = 0;                                                                                    \
-		if (hipGetDevice(&dev) != hipSuccess) return TRXHIP_EIO;                                        \
-		const unsigned long long bit = 1ull << (dev & 63);                                              \
-		if (!(armed.load(std::memory_order_acquire) & bit)) {                                           \
-			if (hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-						(int)(K4_TABLES_BYTES + (size_t)K4_WPB(CF_, EX_) * K4_SLICE * sizeof(c32) + K4_LDS_TAIL)) != hipSuccess) \
-				return TRXHIP_EIO;                                                                  \
-			armed.fetch_or(bit, std::memory_order_release);                                             \
-		}                                                                                               \
-		hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(wpb * WAVE), lds, stream, d_iq, d_params, d_results, \
-				   d_soft, d_tab, reinterpret_cast<const float4 *>(d_ebp_in), (unsigned)n_bursts, L, thresh, \
-				   full_scale, soft_stride, flags, pool, (unsigned *)nullptr);                  \
+		constexpr auto k = burst_pull4_kernel<CF_, EX_, CM_>;                                           \
+		if (trx_arm_dynamic_lds<k>((int)lds))                                                           \
+			return TRXHIP_EIO;                                                                      \
+		hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(K4_WPB(CF_, EX_) * WAVE), lds, stream,         \
+				   d_iq, d_params, d_results, d_soft, d_tab, reinterpret_cast<const float4 *>(d_ebp_in), \
+				   (unsigned)n_bursts, L, thresh, full_scale, soft_stride, flags, d_pool_ctr, (unsigned *)nullptr); \
 	} while (0)
-	/* the cross-die pool needs every workgroup to own >= 7 static groups and the grid to be the persistent one */
-	unsigned *const pool = (d_pool_ctr && grid == (size_t)n_cu && need >= 8 * grid) ? d_pool_ctr : nullptr;   /* (TRXHIP_NO_POOL: trx_capi.cpp) */
 	if (cf32)        { if (exact) LAUNCH4(true, true, false); else if (common) LAUNCH4(true, false, true); else LAUNCH4(true, false, false); }
 	else if (common) { if (exact) LAUNCH4(false, true, true); else LAUNCH4(false, false, true); }
 	else             { if (exact) LAUNCH4(false, true, false); else LAUNCH4(false, false, false); }

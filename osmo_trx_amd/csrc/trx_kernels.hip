@@ -30,6 +30,7 @@
 // generic-C reference.  Only energyDetect (tree-summed), log2f (C/I) and log10f (RSSI) differ at the
 // 1e-6 level.
 #include "trx_device.h"
+#include "trx_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // the hot kernel
@@ -447,22 +448,13 @@ extern "C" size_t trx_pull_lds_bytes(int L, int waves_per_block)
 	return TRX_TABLES_LDS_BYTES + (size_t)waves_per_block * slice_c32 * sizeof(c32) + 16;   // + the workgroup's work counter
 }
 
-extern "C" int trx_launch_pull4(unsigned *d_pool_ctr, const void *d_iq, int cf32, const trxhip_burst_params *d_params,
-				trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, const float *d_ebp_in,
-				size_t n_bursts, int L, float thresh, float full_scale, int soft_stride, int flags, int n_cu,
-				hipStream_t stream);
-
-extern "C" int trx_launch_pull(unsigned *d_pool_ctr, const void *d_iq, int cf32, const trxhip_burst_params *d_params,
-			       trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, const float *d_ebp_in,
-			       size_t n_bursts, int L, int sps, float thresh, float full_scale,
-			       int soft_stride, int slice, int n_cu, hipStream_t stream)
+// burst_pull_kernel<sps, cf32, nld>
+extern "C" int trx_launch_pull(const void *d_iq, int cf32, int nld, const trxhip_burst_params *d_params, trxhip_burst_result *d_results,
+			       float *d_soft, const trx_tables *d_tab, const float *d_ebp_in, size_t n_bursts, int L, int sps, float thresh,
+			       float full_scale, int soft_stride, int flags, int n_cu, hipStream_t stream)
 {
 	if (n_bursts == 0)
 		return 0;
-	// the transceiver's 4-SPS burst size gets the production kernel (polyphase LDS layout, fused or exact demod)
-	if (sps == 4 && L >= 624 && L <= 628)
-		return trx_launch_pull4(d_pool_ctr, d_iq, cf32, d_params, d_results, d_soft, d_tab, d_ebp_in, n_bursts, L, thresh, full_scale,
-					soft_stride, slice, n_cu, stream);
 	// as many waves per workgroup as the 160 KB of LDS admit (12 at L = 625), one workgroup per CU
 	int wpb = TRX_WPB_OF(sps);
 	while (wpb > 1 && trx_pull_lds_bytes(L, wpb) > 160 * 1024)
@@ -470,23 +462,21 @@ extern "C" int trx_launch_pull(unsigned *d_pool_ctr, const void *d_iq, int cf32,
 	const size_t lds = trx_pull_lds_bytes(L, wpb);
 	if (lds > 160 * 1024)
 		return TRXHIP_EINVAL;
-	size_t need = (n_bursts + 15) / 16;                             // work is handed out in groups of 16 bursts
-	size_t grid = (size_t)n_cu * (size_t)((160 * 1024) / lds);
-	if (grid > need) grid = need;
+	const size_t grid = trx_burst_grid(n_bursts, (size_t)n_cu * (size_t)((160 * 1024) / lds));
 
 #define LAUNCH(SPS_, CF_, NLD_)                                                                                 \
 	do {                                                                                                    \
-		auto k = burst_pull_kernel<SPS_, CF_, NLD_>;                                                    \
-		TRX_ARM_DYNAMIC_LDS(k);                                                                         \
+		constexpr auto k = burst_pull_kernel<SPS_, CF_, NLD_>;                                          \
+		if (trx_arm_dynamic_lds<k>())                                                                   \
+			return TRXHIP_EIO;                                                                      \
 		hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(wpb * WAVE), lds, stream, d_iq, d_params, d_results, \
 				   d_soft, d_tab, reinterpret_cast<const float4 *>(d_ebp_in), (unsigned)n_bursts, L, thresh,     \
-				   full_scale, soft_stride, slice);                                             \
+				   full_scale, soft_stride, flags);                                             \
 	} while (0)
 
-	// NLD = dword loads per lane held in registers for the prefetched burst (0 = generic length, no prefetch)
 	if (sps == 4) {
-		if (L <= 640) { if (cf32) LAUNCH(4, true, 10); else LAUNCH(4, false, 10); }
-		else          { if (cf32) LAUNCH(4, true, 0);  else LAUNCH(4, false, 0); }
+		if (nld == 10) { if (cf32) LAUNCH(4, true, 10); else LAUNCH(4, false, 10); }
+		else           { if (cf32) LAUNCH(4, true, 0);  else LAUNCH(4, false, 0); }
 	} else {
 		if (cf32) LAUNCH(1, true, 3); else LAUNCH(1, false, 3);
 	}

@@ -1,0 +1,77 @@
+// trx_launch.h -- the launchers and other internals that one csrc/ translation unit defines and another calls.  They have C
+// linkage and are declared here only: every file that defines or calls one includes this header, so a definition whose
+// signature drifts from its declaration does not compile.  All return 0 or a TRXHIP_* error code.
+#ifndef TRX_LAUNCH_H
+#define TRX_LAUNCH_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/trxhip.h"
+#include "trx_tables.h"
+
+extern "C" {
+
+/* ---- trxhip_detect_demod_batch() and friends: trx_capi.cpp's pull_common() makes every choice, these only launch it ---- */
+
+/* trx_kernel4.hip: the 4-SPS kernel (L 624..628), instance burst_pull4_kernel<cf32, exact, common>.  d_pool_ctr (both 4-SPS
+ * launchers): the launch's counter pair of the cross-die work pool, or NULL; given only with n_bursts >= 128 * n_cu, so that
+ * the grid is the persistent one and every workgroup owns >= 8 groups of 16 bursts */
+int trx_launch_pull4(unsigned *d_pool_ctr, const void *d_iq, int cf32, int exact, int common, const trxhip_burst_params *d_params,
+		     trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, const float *d_ebp_in, size_t n_bursts,
+		     int L, float thresh, float full_scale, int soft_stride, int flags, int n_cu, hipStream_t stream);
+/* trx_kernel4.hip: the split -- the normal-burst kernel over the batch, then burst_pull4_kernel's common instance over the
+ * bursts it left on the list d_redo; h_left: pinned word that receives how many it left */
+int trx_launch_pull4_nb(unsigned *d_pool_ctr, const void *d_iq, const trxhip_burst_params *d_params, trxhip_burst_result *d_results,
+			float *d_soft, const trx_tables *d_tab, size_t n_bursts, float thresh, float full_scale, int n_cu,
+			unsigned *d_redo, unsigned *h_left, hipStream_t stream);
+/* trx_kernels.hip: the generic kernel, instance burst_pull_kernel<sps, cf32, nld> */
+int trx_launch_pull(const void *d_iq, int cf32, int nld, const trxhip_burst_params *d_params, trxhip_burst_result *d_results,
+		    float *d_soft, const trx_tables *d_tab, const float *d_ebp_in, size_t n_bursts, int L, int sps, float thresh,
+		    float full_scale, int soft_stride, int flags, int n_cu, hipStream_t stream);
+size_t trx_pull_lds_bytes(int L, int waves_per_block);                 /* trx_kernels.hip */
+
+int trx_fast_stats_read(unsigned long long *out4, int reset);          /* trx_kernel4.hip: the FAST detector's counters */
+int trx_unit_masks_match(const trx_tables *t);                        /* trx_kernel4.hip: compiled-in sign masks vs the tables */
+int trx_unit_mask_sch_match(const trx_tables *t);                     /* trx_sch.hip: the SCH sequence's sign mask vs the tables */
+
+/* ---- trx_sch.hip, trx_va.hip ---- */
+int trx_launch_sch_detect(const float *d_iq, size_t buf_stride, trxhip_burst_result *d_results, const trx_tables *d_tab,
+			  size_t n_bufs, int len, int start, int toa_sub, float thresh, int unit_tables, hipStream_t stream);
+size_t trx_va_lds_bytes(int L);
+int trx_launch_va_demod(const float *d_iq, const trxhip_burst_params *d_params, const trxhip_burst_result *d_detected, float *d_soft,
+			int32_t *d_starts, size_t n_bursts, int L, float scale, int soft_stride, int flags, hipStream_t stream);
+
+/* ---- trx_aux_kernels.hip ---- */
+int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,
+			 size_t n_bursts, float rssi_offset, hipStream_t stream);
+/* the TRXD wire packer; d_results_copy (may be NULL): every result record is also written there -- the host pipe points it at
+ * pinned memory and saves the download */
+int trx_launch_pack_trxd_wire(const trxhip_burst_result *d_results, const trxhip_burst_params *d_params, const float *d_soft,
+			      int soft_stride, const trxhip_trxd_meta *d_meta, uint8_t *d_pkt, int pkt_stride, uint16_t *d_pkt_len,
+			      size_t n_bursts, float rssi_offset, hipStream_t stream, trxhip_burst_result *d_results_copy);
+/* bursts by reference: n bursts of `dwords` 4-byte words each from the device-side addresses d_src[] */
+int trx_launch_gather_bursts(const unsigned long long *d_src, void *d_dst, size_t n, unsigned dwords, hipStream_t stream);
+int trx_launch_convolve(const float *d_x, int x_len, const float *d_h, int h_len, int h_complex, float *d_y, int y_len, int start,
+			int len, size_t n_vec, hipStream_t stream);
+int trx_launch_convert_short_float(float *d_out, const int16_t *d_in, size_t len, hipStream_t stream);
+int trx_launch_convert_float_short(int16_t *d_out, const float *d_in, float scale, size_t len, hipStream_t stream);
+int trx_launch_dft_strided(const float *d_in, float *d_out, int m, size_t howmany, size_t istride, size_t ostride, int reverse,
+			   hipStream_t stream);
+int trx_launch_frontend_fused(const int16_t *d_wide, float *d_out, size_t n_total, int p, int q, size_t out_stride,
+			      const float *parts, const trx_tables *d_tab, void *d_wide_hist_io, const void *d_chan_hist_in,
+			      void *d_chan_hist_out, hipStream_t stream);
+int trx_launch_channelize(const int16_t *d_in, float *d_out, size_t n_total, size_t out_stride, const trx_tables *d_tab,
+			  void *d_hist_io, hipStream_t stream);
+int trx_launch_resample(const float *d_in, float *d_out, size_t n_in, int p, int q, size_t n_chan, size_t in_stride,
+			size_t out_stride, const float *d_parts, void *d_hist_io, hipStream_t stream);
+int trx_launch_energy_detect(const float *d_x, size_t n_bursts, int burst_len, unsigned window, float *d_out, hipStream_t stream);
+int trx_launch_diversity_select(const int16_t *d_iq_paths, size_t n_bursts, int n_paths, int burst_len, int sps, int16_t *d_iq_sel,
+				float *d_avg_energy, uint8_t *d_path, hipStream_t stream);
+int trx_launch_diversity_power(trxhip_burst_result *d_res, const trxhip_burst_params *d_params, const float *d_avg_energy,
+			       size_t n_bursts, float full_scale, hipStream_t stream);
+int trx_launch_delay_vector(const float *d_in, float *d_out, const float *d_delays, const trx_tables *d_tab, size_t n_vec, int len,
+			    hipStream_t stream);
+int trx_launch_scale_vector(float *d_x, size_t len, float sr, float si, hipStream_t stream);
+int trx_launch_vector_slicer(float *d_dst, const float *d_src, size_t len, hipStream_t stream);
+
+}  // extern "C"
+#endif

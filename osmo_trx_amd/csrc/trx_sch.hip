@@ -20,6 +20,7 @@
 //     per tap.  A buffer with a sample that fails the guard, or tables without the structure, take the multiplying form.
 // Sums follow the reference's order (taps k ascending, -ffp-contract=off): rc and TOA are bit-exact.
 #include "trx_device.h"
+#include "trx_launch.h"
 
 #define SCH_MAX_THREADS 1024
 #define SCH_N 64                       // gSCHSequence length (sigProcLib.cpp:1467-1527)
@@ -196,7 +197,8 @@ extern "C" int trx_launch_sch_detect(const float *d_iq, size_t buf_stride, trxhi
 			   (size_t)(SCH_N + SCH_WIN + 1 + SCH_PAD_F + len + SCH_PAD_B) * sizeof(c32);
 	if (lds > 160 * 1024)
 		return TRXHIP_EINVAL;
-	TRX_ARM_DYNAMIC_LDS(sch_detect_kernel);
+	if (trx_arm_dynamic_lds<sch_detect_kernel>())
+		return TRXHIP_EIO;
 	/* persistent grid: as many workgroups as fit the chip at this LDS size (256 CUs), each walking its share of the buffers */
 	size_t per_cu = lds ? (160 * 1024) / lds : 1;
 	if (per_cu < 1) per_cu = 1;

@@ -20,6 +20,7 @@
 //     word; the traceback is the reference's serial walk on the scalar unit
 // Operand order follows the reference statement by statement (-ffp-contract=off): the +-127 outputs are bit-exact.
 #include "trx_device.h"
+#include "trx_launch.h"
 
 #define VA_WPB 2                       // waves per workgroup (11.4 KB of LDS per wave: 14 waves per CU)
 #define VA_BPW 4                       // bursts per wave: one per DPP row
@@ -457,7 +458,8 @@ extern "C" int trx_launch_va_demod(const float *d_iq, const trxhip_burst_params 
 	const size_t lds = trx_va_lds_bytes(L);
 	if (lds > 160 * 1024)
 		return TRXHIP_EINVAL;
-	TRX_ARM_DYNAMIC_LDS(va_demod_kernel);
+	if (trx_arm_dynamic_lds<va_demod_kernel>())
+		return TRXHIP_EIO;
 	const size_t per_block = VA_WPB * VA_BPW;
 	const size_t grid = (n_bursts + per_block - 1) / per_block;
 	hipLaunchKernelGGL(va_demod_kernel, dim3((unsigned)grid), dim3(VA_WPB * WAVE), lds, stream,

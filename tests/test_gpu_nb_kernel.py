@@ -19,13 +19,13 @@ def trx():
     t.close()
 
 
-def both(trx, iq, params):
+def both(trx, iq, params, **kw):
     d_iq, d_p = iq.to("cuda:0"), trx.params_tensor(params)
     trx.set_nb_kernel(True)
-    res_a, soft_a = trx.detect_demod(d_iq, d_p, sps=4)
+    res_a, soft_a = trx.detect_demod(d_iq, d_p, sps=4, **kw)
     torch.cuda.synchronize()
     trx.set_nb_kernel(False)
-    res_b, soft_b = trx.detect_demod(d_iq, d_p, sps=4)
+    res_b, soft_b = trx.detect_demod(d_iq, d_p, sps=4, **kw)
     torch.cuda.synchronize()
     trx.set_nb_kernel(True)
     return res_a, soft_a, res_b, soft_b
@@ -45,6 +45,20 @@ def assert_identical(trx, res_a, soft_a, res_b, soft_b):
 def test_normal_bursts_any_batch_size(trx, n):
     iq, params, _ = synth.make_normal_bursts(n, "cpu", 4, seed=101 + n)
     assert_identical(trx, *both(trx, iq, params))
+
+
+@pytest.mark.parametrize("threshold,full_scale", [(3.0, 32767.0), (5.0, 32767.0), (7.0, 65535.0), (4.0, 16384.0)])
+def test_threshold_and_full_scale(threshold, full_scale):
+    """the host computes the normal-burst kernel's detection gates from the threshold (threshold^2 x {0.2, 1/6, 1/7, 0.125}):
+    away from the defaults too the split gives the general kernel's bytes.  A fresh context: no back-off left by other tests."""
+    iq, params, _ = synth.make_normal_bursts(8192, "cpu", 4, seed=int(threshold * 10) + int(full_scale) % 97)
+    t = TrxHip(0)
+    try:
+        res_a, soft_a, res_b, soft_b = both(t, iq, params, threshold=threshold, full_scale=full_scale)
+        assert_identical(t, res_a, soft_a, res_b, soft_b)
+        assert (t.results_to_numpy(res_a)["rc"] > 0).any()
+    finally:
+        t.close()
 
 
 @pytest.mark.parametrize("max_toa", [0, 3, 17, 30, 32, 33, 63])
