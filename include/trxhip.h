@@ -1,5 +1,5 @@
 /*
- * trxhip.h -- C ABI of the MI355X (gfx950) receive-side burst DSP for osmo-trx.
+ * trxhip.h -- C ABI of the MI355X (gfx950) burst DSP for osmo-trx: the receive side and the burst modulators.
  *
  * This is the thin extern "C" HIP seam that sits where the reference calls its burst DSP:
  *
@@ -416,6 +416,81 @@ int trxhip_channelize_batch(trxhip_ctx *ctx, const int16_t *d_in, float *d_out,
 /* Resampler(p,q,16)::rotate over a continuous stream per channel: in n_in samples -> out n_in*p/q */
 int trxhip_resample_batch(trxhip_ctx *ctx, const float *d_in, float *d_out, size_t n_in, int p, int q,
 			  size_t n_chan, size_t in_stride, size_t out_stride, void *stream);
+
+/* ---- transmit side: the GMSK / 8-PSK burst modulators of sigProcLib.cpp, batched ----
+ * modulateBurst()       sigProcLib.cpp:970-979   (Transceiver.cpp:392-396, :107-120 through the burst generators)
+ *   modulateBurstLaurent  :595-670  GMSK at 4 SPS: c0 through the 16-tap pulse + c1 through the 8-tap pulse, 625 samples
+ *   modulateBurstBasic    :938-967  GMSK at 1 SPS: one 4-tap pulse, nbits + guard samples
+ *   rotateBurst           :558-580  empty pulse: rotation only, sps * (nbits + guard) samples
+ * modulateEdgeBurst()   sigProcLib.cpp:917-936
+ *   mapEdgeSymbols + shapeEdgeBurst :713-763  8-PSK at 4 SPS, delayed by one symbol, 625 samples
+ *   rotateEdgeBurst       :672-689  empty pulse: rotation only, sps * nbits / 3 samples
+ * Every sample is bit-identical to the reference's generic-C arithmetic.  Only bit 0 of each input byte
+ * counts (bits[i] & 0x01, as in the reference).
+ *
+ * Descriptor ranges; a burst outside them gets status TRXHIP_EINVAL and a zero row.  Some of these cases are undefined
+ * behaviour in the reference and are refused rather than reproduced:
+ *   GMSK, 4 SPS          2 <= nbits <= 155 (guard ignored, as in the reference).  nbits == 156 writes c0[4 * (nbits + 1)],
+ *                        past the reference's 625-sample buffer; nbits < 2 reads bits[-1] (:654-656)
+ *   GMSK, 1 SPS          1 <= nbits + guard <= 157 (GMSKRotation1 has 157 entries)
+ *   GMSK, empty pulse    1 <= sps * (nbits + guard) <= 625 at 4 SPS, <= 157 at 1 SPS.  At 4 SPS guard 9 (148 + 9 = 157
+ *                        symbols, 628 samples) reads GMSKRotation4[625..627], past the table
+ *   8-PSK, 4 SPS         nbits % 3 == 0, nbits <= 468 (156 symbols fill the 625 samples)
+ *   8-PSK, empty pulse   nbits % 3 == 0, 3 <= nbits <= 468, any sps of the call
+ *   8-PSK shaped at 1 SPS: refused (the reference returns NULL, :923-924)
+ *   always               nbits <= bits_stride, length <= out_stride, no unknown flag bits */
+#define TRXHIP_TX_8PSK         1   /* modulateEdgeBurst() instead of modulateBurst() */
+#define TRXHIP_TX_EMPTY_PULSE  2   /* emptyPulse = true: rotation only */
+typedef struct trxhip_tx_params {
+	uint16_t nbits;      /* bits of the burst (bytes at d_bits + b * bits_stride) */
+	uint8_t  guard;      /* guardPeriodLength (GMSK at 1 SPS and the empty pulse) */
+	uint8_t  flags;      /* TRXHIP_TX_* */
+	float    scale_re;   /* complex scale applied after modulation, as scaleVector() does (sigProcLib.cpp:1188-1213): */
+	float    scale_im;   /* (a.re*s.re - a.im*s.im, a.re*s.im + a.im*s.re).  Exactly (1, 0): the row is left unscaled */
+	uint32_t reserved;
+} trxhip_tx_params;
+/* n bursts, one launch:
+ *   d_bits     : n x bits_stride bytes
+ *   d_params   : n trxhip_tx_params
+ *   d_out_cf32 : n x out_stride complex64 (may be NULL); samples behind a burst's length are 0
+ *   d_out_s16  : n x out_stride x (I, Q) int16 (may be NULL): (int16_t)(int)(x * s16_scale) per component, the expression of
+ *                trxhip_convert_float_short().  4-SPS bursts in TN order at out_stride 625 are one TDMA frame's sample stream
+ *   d_out_len  : n int32 (may be NULL): the burst's length in samples, or TRXHIP_EINVAL for a refused descriptor
+ *   sps        : 1 or 4 (the reference's tx_sps)
+ * Asynchronous on `stream`.  TRXHIP_EINVAL without a context: there is no CPU path. */
+int trxhip_modulate_batch(trxhip_ctx *ctx, const uint8_t *d_bits, size_t bits_stride, const trxhip_tx_params *d_params,
+			  float *d_out_cf32, int16_t *d_out_s16, float s16_scale, size_t out_stride, int32_t *d_out_len,
+			  size_t n, int sps, void *stream);
+
+/* TRXD downlink datagrams to burst samples: Transceiver::driveTxPriorityQueue() + addRadioVector()
+ * (Transceiver.cpp:1087-1185, :373-399), parsed on the device.  Datagram b (struct trxd_hdr_v01_dl + bits, proto_trxd.h):
+ *   [0]     version << 4 | tn & 7 (version 0 or 1)   [1..4] fn, big endian   [5] tx_att (dB)   [6..] one bit per byte
+ *   length  6 + 148: GMSK, modulateBurst(bits, 8 + (tn % 4 == 0), sps)
+ *           6 + 444: 8-PSK, modulateEdgeBurst(bits, sps); only at 4 SPS (status TRXHIP_ENOTSUP otherwise, :1112-1116)
+ *   scale   (float)(full_scale * pow(10, (double)-tx_att / 20)), the expression of :396 with txFullScale = full_scale
+ * A datagram of any other length or version gets status TRXHIP_EINVAL; refused datagrams get a zero row (the reference
+ * drops them).  The FN-order bookkeeping (:1137-1171) and the filler table stay with the caller.
+ *   d_dgram     : n x dgram_stride bytes (dgram_stride >= 6; a datagram longer than dgram_stride is refused)
+ *   d_dgram_len : n uint16
+ *   d_info      : n trxhip_tx_info (may be NULL); outputs as trxhip_modulate_batch() */
+typedef struct trxhip_tx_info {
+	uint32_t fn;        /* TDMA frame number */
+	uint8_t  tn;        /* timeslot */
+	uint8_t  version;   /* TRXD header version */
+	uint8_t  tx_att;    /* attenuation, dB */
+	uint8_t  mod_8psk;  /* 1: 8-PSK burst */
+	uint16_t nbits;     /* 148, 444, or 0 when refused */
+	uint16_t length;    /* samples written, 0 when refused */
+	int32_t  status;    /* 0 or TRXHIP_E* */
+} trxhip_tx_info;
+int trxhip_modulate_trxd_batch(trxhip_ctx *ctx, const uint8_t *d_dgram, size_t dgram_stride, const uint16_t *d_dgram_len,
+			       double full_scale, int sps, float *d_out_cf32, int16_t *d_out_s16, float s16_scale,
+			       size_t out_stride, trxhip_tx_info *d_info, size_t n, void *stream);
+
+/* The transmit table struct (csrc/trx_tx_tables.h), host-only, no GPU needed: pulses, rotations, 8-PSK map and phasors, burst
+ * bit patterns */
+size_t trxhip_tx_tables_size(void);
+int  trxhip_tx_tables_generate_host(void *h_buf, size_t size);
 
 /* ---- streaming multi-ARFCN receive front end: RadioInterfaceMulti::pullBuffer(), radioInterfaceMulti.cpp:237-314 ----
  * Channelizer(4, block_len, 16)::rotate followed by Resampler(p, q, 16)::rotate on every filterbank channel, called

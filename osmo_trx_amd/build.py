@@ -25,7 +25,8 @@ HOSTCXX = [shutil.which("g++") or "g++", "-D__HIP_PLATFORM_AMD__", "-I", os.path
 HOSTLINK = ["-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-result"]
 
-LIB_SOURCES = ["trx_kernel4.hip", "trx_kernels.hip", "trx_aux_kernels.hip", "trx_sch.hip", "trx_va.hip", "trx_capi.cpp", "trx_hostpipe.cpp", "trx_tables.cpp"]
+LIB_SOURCES = ["trx_kernel4.hip", "trx_kernels.hip", "trx_aux_kernels.hip", "trx_sch.hip", "trx_va.hip", "trx_tx.hip", "trx_capi.cpp",
+               "trx_hostpipe.cpp", "trx_tables.cpp"]
 
 
 def _stale(target, sources):
@@ -79,13 +80,14 @@ def ref_include_dirs():
     return None
 
 
-SHIM_SOURCES = ["sigProcLib.cpp", "MultiArfcnRx.cpp", "BurstGatherer.cpp", "trxPullRadioVector.cpp"]
+SHIM_SOURCES = ["sigProcLib.cpp", "sigProcLibTx.cpp", "MultiArfcnRx.cpp", "BurstGatherer.cpp", "trxPullRadioVector.cpp"]
 
 
 def _build_shim(out, inc_dirs, force):
     srcs = [os.path.join(HOST, f) for f in SHIM_SOURCES]
     deps = srcs + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".h")] + \
-        [os.path.join(HOST, "compat", f) for f in os.listdir(os.path.join(HOST, "compat"))]
+        [os.path.join(HOST, "compat", f) for f in os.listdir(os.path.join(HOST, "compat"))] + \
+        [os.path.join(CSRC, "trx_tx_tables.h")]
     if force or _stale(out, deps + [LIB]):
         inc = []
         for d in inc_dirs + [HOST, os.path.join(ROOT, "include")]:

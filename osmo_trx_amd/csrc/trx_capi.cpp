@@ -120,6 +120,18 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 		rc = TRXHIP_EIO;
 	} else if (!ctx->redo.create()) {
 		rc = TRXHIP_ENOMEM;
+	} else {
+		/* the transmit tables (trx_tx_tables.h), next to the receive blob */
+		trx_tx_tables *tx = static_cast<trx_tx_tables *>(malloc(sizeof(trx_tx_tables)));
+		if (!tx || trx_tx_tables_generate(tx) != 0)
+			rc = TRXHIP_ENOMEM;
+		else if (hipMalloc(reinterpret_cast<void **>(&ctx->d_tx_tables), sizeof(trx_tx_tables)) != hipSuccess) {
+			ctx->d_tx_tables = nullptr;
+			rc = TRXHIP_ENOMEM;
+		} else if (hipMemcpy(ctx->d_tx_tables, tx, sizeof(trx_tx_tables), hipMemcpyHostToDevice) != hipSuccess) {
+			rc = TRXHIP_EIO;
+		}
+		free(tx);
 	}
 	if (rc != TRXHIP_OK) {
 		trxhip_destroy(ctx);
@@ -155,6 +167,7 @@ void trxhip_destroy(trxhip_ctx *ctx)
 	if (hipSetDevice(ctx->device) == hipSuccess) {
 		if (ctx->d_tables) (void)hipFree(ctx->d_tables);
 		if (ctx->d_pool) (void)hipFree(ctx->d_pool);
+		if (ctx->d_tx_tables) (void)hipFree(ctx->d_tx_tables);
 		ctx->redo.destroy();
 	}
 	delete ctx;
@@ -188,6 +201,65 @@ int trxhip_fast_stats(trxhip_ctx *ctx, uint64_t *out4, int reset)
 	for (int k = 0; k < 4; k++)
 		out4[k] = v[k];
 	return TRXHIP_OK;
+}
+
+size_t trxhip_tx_tables_size(void) { return sizeof(trx_tx_tables); }
+
+int trxhip_tx_tables_generate_host(void *h_buf, size_t size)
+{
+	if (!h_buf || size != sizeof(trx_tx_tables))
+		return TRXHIP_EINVAL;
+	return trx_tx_tables_generate(static_cast<trx_tx_tables *>(h_buf)) == 0 ? TRXHIP_OK : TRXHIP_EINVAL;
+}
+
+/* the row and stride limits both modulator entry points share: rows of at most 2^20 samples, 8-byte aligned cf32 rows and
+ * 4-byte aligned int16 rows (the kernel realigns each row to its 16- / 8-byte stores itself) */
+static int tx_check_outputs(const float *d_out_cf32, const int16_t *d_out_s16, size_t out_stride, int sps)
+{
+	if ((sps != 1 && sps != 4) || out_stride == 0 || out_stride > (1u << 20))
+		return TRXHIP_EINVAL;
+	if ((reinterpret_cast<uintptr_t>(d_out_cf32) & 7) || (reinterpret_cast<uintptr_t>(d_out_s16) & 3))
+		return TRXHIP_EINVAL;
+	return TRXHIP_OK;
+}
+
+int trxhip_modulate_batch(trxhip_ctx *ctx, const uint8_t *d_bits, size_t bits_stride, const trxhip_tx_params *d_params,
+			  float *d_out_cf32, int16_t *d_out_s16, float s16_scale, size_t out_stride, int32_t *d_out_len,
+			  size_t n, int sps, void *stream)
+{
+	if (!ctx || !ctx->d_tx_tables || (n && (!d_bits || !d_params)) || bits_stride == 0 ||
+	    tx_check_outputs(d_out_cf32, d_out_s16, out_stride, sps) != TRXHIP_OK)
+		return TRXHIP_EINVAL;
+	if (with_device(ctx))
+		return TRXHIP_EIO;
+	return trx_launch_tx_modulate(d_bits, bits_stride, d_params, nullptr, nullptr, ctx->d_tx_tables, d_out_cf32, d_out_s16,
+				      s16_scale, out_stride, d_out_len, nullptr, n, sps, static_cast<hipStream_t>(stream));
+}
+
+int trxhip_modulate_trxd_batch(trxhip_ctx *ctx, const uint8_t *d_dgram, size_t dgram_stride, const uint16_t *d_dgram_len,
+			       double full_scale, int sps, float *d_out_cf32, int16_t *d_out_s16, float s16_scale,
+			       size_t out_stride, trxhip_tx_info *d_info, size_t n, void *stream)
+{
+	if (!ctx || !ctx->d_tx_tables || (n && (!d_dgram || !d_dgram_len)) || dgram_stride < 6 ||
+	    tx_check_outputs(d_out_cf32, d_out_s16, out_stride, sps) != TRXHIP_OK)
+		return TRXHIP_EINVAL;
+	if (with_device(ctx))
+		return TRXHIP_EIO;
+	float att[256];
+	{
+		/* addRadioVector(), Transceiver.cpp:396: txFullScale * pow(10, (double) -RSSI / 20), narrowed to float by scaleVector()'s
+		 * complex argument.  Computed on the host in double once per full_scale; the kernel receives the 256 values by value */
+		std::lock_guard<std::mutex> lk(ctx->tx_mu);
+		if (!ctx->tx_att_valid || memcmp(&ctx->tx_full_scale, &full_scale, sizeof(double)) != 0) {
+			for (int a = 0; a < 256; a++)
+				ctx->tx_att_scale[a] = (float)(full_scale * pow(10, (double)-a / 20));
+			ctx->tx_full_scale = full_scale;
+			ctx->tx_att_valid = true;
+		}
+		memcpy(att, ctx->tx_att_scale, sizeof(att));
+	}
+	return trx_launch_tx_modulate(d_dgram, dgram_stride, nullptr, d_dgram_len, att, ctx->d_tx_tables, d_out_cf32, d_out_s16,
+				      s16_scale, out_stride, nullptr, d_info, n, sps, static_cast<hipStream_t>(stream));
 }
 
 int trxhip_tables_device_ptr(trxhip_ctx *ctx, void **d_blob)

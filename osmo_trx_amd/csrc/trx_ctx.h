@@ -6,6 +6,7 @@
 #include <mutex>
 #include "../../include/trxhip.h"
 #include "trx_tables.h"
+#include "trx_tx_tables.h"
 
 #define TRX_POOL_SLOTS 1024
 #define TRX_REDO_SLOTS 4
@@ -117,6 +118,12 @@ struct trxhip_ctx {
 	std::atomic<unsigned> pool_next{0u};
 	int nb_enabled = 1;                /* trxhip_set_nb_kernel(); 0 when TRXHIP_NO_NB_KERNEL is set at creation */
 	trx_redo_lists redo;
+	trx_tx_tables *d_tx_tables = nullptr;   /* transmit tables (trx_tx.hip), uploaded at creation */
+	/* trxhip_modulate_trxd_batch(): (float)(full_scale * pow(10, -att / 20.0)) for att = 0 .. 255, for the last full_scale */
+	std::mutex tx_mu;
+	double tx_full_scale = 0.0;
+	bool tx_att_valid = false;
+	float tx_att_scale[256];
 };
 
 static inline int with_device(const trxhip_ctx *ctx)

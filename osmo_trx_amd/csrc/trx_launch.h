@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include "../../include/trxhip.h"
 #include "trx_tables.h"
+#include "trx_tx_tables.h"
 
 extern "C" {
 
@@ -72,6 +73,16 @@ int trx_launch_delay_vector(const float *d_in, float *d_out, const float *d_dela
 			    hipStream_t stream);
 int trx_launch_scale_vector(float *d_x, size_t len, float sr, float si, hipStream_t stream);
 int trx_launch_vector_slicer(float *d_dst, const float *d_src, size_t len, hipStream_t stream);
+
+/* ---- trx_tx.hip: the burst modulators (trxhip_modulate_batch, trxhip_modulate_trxd_batch) ----
+ * d_dgram_len == NULL: d_in holds bits (in_stride bytes per burst) and d_params the descriptors; otherwise d_in holds TRXD
+ * datagrams (in_stride bytes each), d_dgram_len their lengths and h_att_scale the 256 scales by tx_att (host memory, passed
+ * by value) */
+int trx_launch_tx_modulate(const uint8_t *d_in, size_t in_stride, const trxhip_tx_params *d_params, const uint16_t *d_dgram_len,
+			   const float *h_att_scale, const trx_tx_tables *d_tab, float *d_out_cf32, int16_t *d_out_s16,
+			   float s16_scale, size_t out_stride, int32_t *d_out_len, trxhip_tx_info *d_info, size_t n, int sps,
+			   hipStream_t stream);
+int trx_tx_tables_generate(trx_tx_tables *t);                         /* host only */
 
 }  // extern "C"
 #endif

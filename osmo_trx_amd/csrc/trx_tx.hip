@@ -1,0 +1,476 @@
+// trx_tx.hip -- the transmit side: the GMSK / 8-PSK burst modulators of sigProcLib.cpp (modulateBurst :970-979,
+// modulateEdgeBurst :917-936) batched over N bursts, plus the TRXD downlink front (Transceiver.cpp:1087-1185, :373-399) and
+// the host generator of the transmit tables (trx_tx_tables.h).
+//
+// Kernel shape.  One wave per burst, four bursts per 256-thread workgroup.  The wave stages the burst's bits (bit 0 of each
+// byte) in LDS, then the symbol-rate values the reference places at every sps-th sample of its upsampled vectors (c0 and c1
+// of the Laurent modulator, the rotated 8-PSK symbols, the rotated 1-SPS symbols), then writes the row: every lane two samples
+// per round, 16-byte non-temporal stores for cf32 (8 bytes for int16), the row zero-filled behind the burst up to out_stride.
+// The kernel is store-bound: a 4-SPS burst is 5000 bytes of cf32 or 2500 of int16 against ~150 bytes of bits.
+//
+// Exactness.  The reference convolves (START_ONLY, sigProcLib.cpp:297-398 -> convolve_base.c:28-33, generic C) the upsampled
+// vector with the pulse: y[i] = sum_{k=0..H-1} x[i - (H-1) + k] * h[k], in ascending k, from 0.0f.  x is zero except at
+// multiples of sps, so here only the taps that meet a symbol position are summed, still in ascending k and still from 0.0f
+// (the argument is stated at sum_sparse4()).  All rotations and phasors come from the tables; the device computes no cos / sin / pow.  Built with
+// -ffp-contract=off (build.py): no multiply-add is fused.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "../../include/trxhip.h"
+#include "trx_tx_tables.h"
+#include "trx_launch.h"
+
+typedef float2 c32;
+typedef float f2v __attribute__((ext_vector_type(2)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef unsigned u2v __attribute__((ext_vector_type(2)));
+
+#define TX_WAVES 4                 /* bursts (waves) per workgroup */
+#define TX_SYMS 160                /* symbol slots per burst in LDS: 157 used (positions 0 .. 624 at 4 SPS, 0 .. 156 at 1 SPS) */
+#define TX_BITS 480                /* bit bytes per burst in LDS: 468 used */
+
+enum { TX_LAURENT = 0, TX_BASIC1 = 1, TX_ROTATE = 2, TX_EDGE4 = 3, TX_EDGE_ROTATE = 4 };
+
+struct trx_tx_desc {
+	int mode, nbits, len, status;
+	c32 scale;
+	bool scaled;
+};
+
+// The range checks of include/trxhip.h: the mode and the length of a burst, or status TRXHIP_EINVAL and length 0.
+__device__ static inline trx_tx_desc tx_describe(int nbits, int guard, int flags, int sps, size_t bits_stride, size_t out_stride)
+{
+	trx_tx_desc d;
+	d.nbits = nbits;
+	d.status = TRXHIP_EINVAL;
+	d.len = 0;
+	d.mode = TX_LAURENT;
+	d.scale = make_float2(1.0f, 0.0f);
+	d.scaled = false;
+	if (flags & ~(TRXHIP_TX_8PSK | TRXHIP_TX_EMPTY_PULSE) || (size_t)nbits > bits_stride)
+		return d;
+	int len = 0;
+	if (flags & TRXHIP_TX_8PSK) {
+		if (nbits % 3 != 0 || nbits > 3 * TRX_TX_EDGE_SYMS)
+			return d;
+		if (flags & TRXHIP_TX_EMPTY_PULSE) {
+			if (nbits < 3)
+				return d;
+			d.mode = TX_EDGE_ROTATE;
+			len = sps * (nbits / 3);
+		} else {
+			if (sps != 4)
+				return d;
+			d.mode = TX_EDGE4;
+			len = 625;
+		}
+	} else if (flags & TRXHIP_TX_EMPTY_PULSE) {
+		len = sps * (nbits + guard);
+		if (len < 1 || len > (sps == 4 ? 625 : 157))
+			return d;
+		d.mode = TX_ROTATE;
+	} else if (sps == 4) {
+		if (nbits < 2 || nbits > 155)
+			return d;
+		d.mode = TX_LAURENT;
+		len = 625;
+	} else {
+		len = nbits + guard;
+		if (len < 1 || len > 157)
+			return d;
+		d.mode = TX_BASIC1;
+	}
+	if ((size_t)len > out_stride)
+		return d;
+	d.len = len;
+	d.status = 0;
+	return d;
+}
+
+// Complex<float> operator* (Complex.h:73): (r*a.r - i*a.i, r*a.i + i*a.r)
+__device__ static inline c32 cmul(c32 x, c32 a) { return make_float2(x.x * a.x - x.y * a.y, x.x * a.y + x.y * a.x); }
+
+// y[i] of the 4-SPS START_ONLY convolution with an H-tap real pulse h (H = 16: c0, H = 8: c1) over a vector that is nonzero
+// only at positions 4m, whose values are sym[m] (m < TX_SYMS; the vector is 625 samples, so m <= 156).
+// The reference sums all H taps from 0.0f in ascending k: yr += x[j].re * h[k], j = i - (H-1) + k.  The skipped terms have
+// x[j] = (+-0, +-0), so each is a product +-0.  A sum that starts at +0.0f is never -0 in round-to-nearest (a + b is -0 only
+// if a and b are both -0), and s + (+-0) == s for every s that is not -0.  So adding the skipped terms would not change
+// one bit: summing only the contributing taps (at most 4 for c0, 2 for c1), in the same ascending order and from the same
+// 0.0f, gives the reference's float.
+template <int H>
+__device__ static inline c32 sum_sparse4(const c32 *sym, const float *h, int i)
+{
+	float yr = 0.0f, yi = 0.0f;
+	int m = (i - (H - 1) + 3) >> 2;            /* first symbol position 4m >= i - (H-1) */
+	if (m < 0)
+		m = 0;
+	for (; 4 * m <= i && m <= 156; m++) {
+		const c32 x = sym[m];
+		const float t = h[4 * m - i + (H - 1)];
+		yr += x.x * t;
+		yi += x.y * t;
+	}
+	return make_float2(yr, yi);
+}
+
+struct tx_lds {
+	c32 sym0[TX_WAVES][TX_SYMS];               /* c0 / 8-PSK / 1-SPS symbol values */
+	c32 sym1[TX_WAVES][TX_SYMS];               /* c1 of the Laurent modulator */
+	uint8_t bits[TX_WAVES][TX_BITS];
+	float p0[16], p1[8], q1[4];                /* pulse4_c0, pulse4_c1, pulse1_c0 */
+};
+
+struct tx_att_table { float s[256]; };
+
+// TRXD: the datagram's header decides the descriptor (driveTxPriorityQueue(), Transceiver.cpp:1099-1130; addRadioVector()
+// :388-396).  Returns the bits' address.
+__device__ static inline const uint8_t *trxd_describe(const uint8_t *dg, int dlen, size_t dgram_stride, int sps, const tx_att_table &att,
+						       size_t out_stride, trx_tx_desc &d, trxhip_tx_info &info)
+{
+	const uint8_t h0 = dg[0];
+	info.tn = h0 & 7;
+	info.version = h0 >> 4;
+	info.fn = ((uint32_t)dg[1] << 24) | ((uint32_t)dg[2] << 16) | ((uint32_t)dg[3] << 8) | (uint32_t)dg[4];
+	info.tx_att = dg[5];
+	info.mod_8psk = 0;
+	int nbits = 0, flags = 0, status = 0;
+	if (dlen == 6 + 148) {
+		nbits = 148;
+	} else if (dlen == 6 + 444) {
+		nbits = 444;
+		flags = TRXHIP_TX_8PSK;
+		info.mod_8psk = 1;
+		if (sps != 4)
+			status = TRXHIP_ENOTSUP;
+	} else {
+		status = TRXHIP_EINVAL;
+	}
+	if (info.version > 1 || (size_t)dlen > dgram_stride)
+		status = TRXHIP_EINVAL;
+	d = tx_describe(nbits, 8 + (info.tn % 4 == 0), flags, sps, dgram_stride - 6, out_stride);
+	if (status != 0) {
+		d.status = status;
+		d.len = 0;
+	}
+	if (d.status == 0) {
+		d.scale = make_float2(att.s[info.tx_att], 0.0f);        /* scaleVector(*burst, complex(scale)): imaginary part 0 */
+		d.scaled = true;
+	}
+	info.nbits = d.status == 0 ? (uint16_t)nbits : 0;
+	info.length = (uint16_t)d.len;
+	info.status = d.status;
+	return dg + 6;
+}
+
+template <bool TRXD>
+__global__ void __launch_bounds__(64 * TX_WAVES)
+tx_modulate_kernel(const uint8_t *__restrict__ in, size_t in_stride, const trxhip_tx_params *__restrict__ params,
+		   const uint16_t *__restrict__ dgram_len, tx_att_table att, const trx_tx_tables *__restrict__ tab,
+		   float *__restrict__ out_cf32, int16_t *__restrict__ out_s16, float s16_scale, size_t out_stride,
+		   int32_t *__restrict__ out_len, trxhip_tx_info *__restrict__ info_out, size_t n, int sps)
+{
+	__shared__ tx_lds L;
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const size_t b = (size_t)blockIdx.x * TX_WAVES + w;
+	const bool active = b < n;
+
+	if (threadIdx.x < 16)
+		L.p0[threadIdx.x] = tab->pulse4_c0[threadIdx.x];
+	else if (threadIdx.x < 24)
+		L.p1[threadIdx.x - 16] = tab->pulse4_c1[threadIdx.x - 16];
+	else if (threadIdx.x < 28)
+		L.q1[threadIdx.x - 24] = tab->pulse1_c0[threadIdx.x - 24];
+
+	// ---- descriptor (wave-uniform) ----
+	trx_tx_desc d;
+	d.status = TRXHIP_EINVAL;
+	d.len = 0;
+	d.nbits = 0;
+	d.mode = TX_LAURENT;
+	d.scaled = false;
+	const uint8_t *bits = nullptr;
+	if (active) {
+		if (TRXD) {
+			trxhip_tx_info info;
+			bits = trxd_describe(in + b * in_stride, dgram_len[b], in_stride, sps, att, out_stride, d, info);
+			if (info_out && lane == 0)
+				info_out[b] = info;
+		} else {
+			const trxhip_tx_params p = params[b];
+			d = tx_describe(p.nbits, p.guard, p.flags, sps, in_stride, out_stride);
+			d.scale = make_float2(p.scale_re, p.scale_im);
+			d.scaled = !(p.scale_re == 1.0f && p.scale_im == 0.0f && !signbit(p.scale_im));
+			bits = in + b * in_stride;
+		}
+		if (out_len && lane == 0)
+			out_len[b] = d.status == 0 ? d.len : d.status;
+	}
+	const bool ok = active && d.status == 0;
+	const int nbits = d.nbits, len = d.len;
+
+	// ---- stage the bits: only bit 0 counts (bits[i] & 0x01) ----
+	uint8_t *lb = L.bits[w];
+	if (ok)
+		for (int i = lane; i < nbits; i += 64)
+			lb[i] = bits[i] & 0x01;
+	__syncthreads();
+
+	// ---- symbol-rate values ----
+	c32 *s0 = L.sym0[w], *s1 = L.sym1[w];
+	if (ok) {
+		const c32 *rot4 = reinterpret_cast<const c32 *>(tab->rot4);
+		const c32 *rot1 = reinterpret_cast<const c32 *>(tab->rot1);
+		const c32 *psk8 = reinterpret_cast<const c32 *>(tab->psk8);
+		const c32 *erot = reinterpret_cast<const c32 *>(tab->edge_rot);
+		const c32 zero = make_float2(0.0f, 0.0f);
+		for (int m = lane; m < TX_SYMS; m += 64) {
+			c32 v0 = zero, v1 = zero;
+			if (d.mode == TX_LAURENT) {
+				// modulateBurstLaurent :615-656.  c0: padded tail (-1), the bits, padded tail (-1) at 4m, m = 0 .. nbits+1, then
+				// GMSKRotate's real branch (*rotPtr * x.real(), :247-251).  c1 = c0 * (0, phase) at m = 2 .. nbits+1, phase -1 at
+				// m = 2 (start magic) and 2 (b[m-2] ^ b[m-3]) - 1 after it (the loop and the end magic)
+				if (m <= nbits + 1) {
+					const float x = (m == 0 || m == nbits + 1) ? -1.0f : (lb[m - 1] ? 1.0f : -1.0f);   /* 2.0 * bit - 1.0 */
+					const c32 r = rot4[4 * m];
+					v0 = make_float2(r.x * x, r.y * x);
+					if (m >= 2) {
+						const float ph = (m == 2) ? -1.0f : ((lb[m - 2] ^ lb[m - 3]) ? 1.0f : -1.0f);
+						v1 = cmul(v0, make_float2(0.0f, ph));
+					}
+				}
+			} else if (d.mode == TX_BASIC1) {
+				// modulateBurstBasic :938-967 at 1 SPS: +-1 at m < nbits, 0 behind, GMSKRotate's real branch over all len samples
+				if (m < len) {
+					const float x = m < nbits ? (lb[m] ? 1.0f : -1.0f) : 0.0f;
+					const c32 r = rot1[m];
+					v0 = make_float2(r.x * x, r.y * x);
+				}
+			} else if (d.mode == TX_EDGE4 || d.mode == TX_EDGE_ROTATE) {
+				// mapEdgeSymbols :713-729 then symbol * rot (shapeEdgeBurst :750-756 one symbol late; rotateEdgeBurst :680-686)
+				const int k = d.mode == TX_EDGE4 ? m - 1 : m;
+				if (k >= 0 && k < nbits / 3) {
+					const unsigned idx = (unsigned)lb[3 * k] | ((unsigned)lb[3 * k + 1] << 1) | ((unsigned)lb[3 * k + 2] << 2);
+					v0 = cmul(psk8[idx], erot[k]);
+				}
+			}
+			s0[m] = v0;
+			s1[m] = v1;
+		}
+	}
+	__syncthreads();
+	if (!active)
+		return;
+
+	// ---- the row: samples [0, len) of the burst, zeros behind it up to out_stride ----
+	const c32 *rot = reinterpret_cast<const c32 *>(sps == 4 ? tab->rot4 : tab->rot1);
+	auto sample = [&](int i) -> c32 {
+		c32 y = make_float2(0.0f, 0.0f);
+		if (i >= len)
+			return y;
+		switch (d.mode) {
+		case TX_LAURENT: {
+			// c0_shaped + c1_shaped (:659-666): each convolution summed on its own, then added
+			const c32 a = sum_sparse4<16>(s0, L.p0, i), c = sum_sparse4<8>(s1, L.p1, i);
+			y = make_float2(a.x + c.x, a.y + c.y);
+			break;
+		}
+		case TX_EDGE4:
+			y = sum_sparse4<16>(s0, L.p0, i);
+			break;
+		case TX_BASIC1: {
+			// every sample is a symbol position at 1 SPS: the plain 4-tap START_ONLY sum, x[j] = 0 outside [0, len)
+			float yr = 0.0f, yi = 0.0f;
+			for (int k = 0; k < 4; k++) {
+				const int j = i - 3 + k;
+				if (j >= 0) {
+					yr += s0[j].x * L.q1[k];
+					yi += s0[j].y * L.q1[k];
+				}
+			}
+			y = make_float2(yr, yi);
+			break;
+		}
+		case TX_ROTATE: {
+			// rotateBurst :558-580: (+-1, 0) at every sps-th sample, GMSKRotate's complex branch, then the 1-tap empty pulse
+			// (real taps: 0.0f + x.re * 1.0f)
+			const int m = i / sps;
+			const float x = (i == m * sps && m < nbits) ? (lb[m] ? 1.0f : -1.0f) : 0.0f;
+			const c32 v = cmul(rot[i], make_float2(x, 0.0f));
+			y = make_float2(0.0f + v.x * 1.0f, 0.0f + v.y * 1.0f);
+			break;
+		}
+		default: {                             /* TX_EDGE_ROTATE: no filter, zeros between the symbols */
+			const int m = i / sps;
+			if (i == m * sps)
+				y = s0[m];
+			break;
+		}
+		}
+		if (d.scaled)                          /* scaleVector's complex branch, :1199-1203 */
+			y = make_float2(y.x * d.scale.x - y.y * d.scale.y, y.x * d.scale.y + y.y * d.scale.x);
+		return y;
+	};
+
+	const int stride = (int)out_stride;
+	if (out_cf32) {
+		float *row = out_cf32 + 2 * b * out_stride;
+		const int head = (reinterpret_cast<uintptr_t>(row) & 15) ? 1 : 0;     /* sample 0 alone when the row is 8-byte aligned */
+		if (head && lane == 0) {
+			const c32 y = sample(0);
+			__builtin_nontemporal_store((f2v){y.x, y.y}, reinterpret_cast<f2v *>(row));
+		}
+		for (int i0 = head + 2 * lane; i0 < stride; i0 += 128) {
+			const c32 y0 = sample(i0);
+			if (i0 + 1 < stride) {
+				const c32 y1 = sample(i0 + 1);
+				__builtin_nontemporal_store((f4v){y0.x, y0.y, y1.x, y1.y}, reinterpret_cast<f4v *>(row + 2 * i0));
+			} else {
+				__builtin_nontemporal_store((f2v){y0.x, y0.y}, reinterpret_cast<f2v *>(row + 2 * i0));
+			}
+		}
+	}
+	if (out_s16) {
+		// convert_float_short_kernel's expression (trx_aux_kernels.hip): (int16_t)(int)(x * scale)
+		int16_t *row = out_s16 + 2 * b * out_stride;
+		auto q = [&](float v) -> unsigned { return (unsigned)(uint16_t)(int16_t)(int)(v * s16_scale); };
+		const int head = (reinterpret_cast<uintptr_t>(row) & 7) ? 1 : 0;
+		if (head && lane == 0) {
+			const c32 y = sample(0);
+			__builtin_nontemporal_store(q(y.x) | (q(y.y) << 16), reinterpret_cast<unsigned *>(row));
+		}
+		for (int i0 = head + 2 * lane; i0 < stride; i0 += 128) {
+			const c32 y0 = sample(i0);
+			if (i0 + 1 < stride) {
+				const c32 y1 = sample(i0 + 1);
+				__builtin_nontemporal_store((u2v){q(y0.x) | (q(y0.y) << 16), q(y1.x) | (q(y1.y) << 16)},
+							    reinterpret_cast<u2v *>(row + 2 * i0));
+			} else {
+				__builtin_nontemporal_store(q(y0.x) | (q(y0.y) << 16), reinterpret_cast<unsigned *>(row + 2 * i0));
+			}
+		}
+	}
+}
+
+extern "C" int trx_launch_tx_modulate(const uint8_t *d_in, size_t in_stride, const trxhip_tx_params *d_params, const uint16_t *d_dgram_len,
+				      const float *h_att_scale, const trx_tx_tables *d_tab, float *d_out_cf32, int16_t *d_out_s16,
+				      float s16_scale, size_t out_stride, int32_t *d_out_len, trxhip_tx_info *d_info, size_t n, int sps,
+				      hipStream_t stream)
+{
+	if (n == 0)
+		return 0;
+	const size_t blocks = (n + TX_WAVES - 1) / TX_WAVES;
+	if (blocks > 0x7fffffffu)
+		return TRXHIP_EINVAL;
+	tx_att_table att;
+	if (h_att_scale)
+		memcpy(att.s, h_att_scale, sizeof(att.s));
+	else
+		memset(att.s, 0, sizeof(att.s));
+	if (d_dgram_len)
+		hipLaunchKernelGGL(tx_modulate_kernel<true>, dim3((unsigned)blocks), dim3(64 * TX_WAVES), 0, stream, d_in, in_stride,
+				   nullptr, d_dgram_len, att, d_tab, d_out_cf32, d_out_s16, s16_scale, out_stride, nullptr, d_info, n, sps);
+	else
+		hipLaunchKernelGGL(tx_modulate_kernel<false>, dim3((unsigned)blocks), dim3(64 * TX_WAVES), 0, stream, d_in, in_stride,
+				   d_params, nullptr, att, d_tab, d_out_cf32, d_out_s16, s16_scale, out_stride, d_out_len, nullptr, n, sps);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host: the transmit tables, built as sigProcLibSetup() builds the reference's (sigProcLib.cpp:2139-2172), with each
+// generator's operand order and float/double promotion points.
+// ------------------------------------------------------------------------------------------------
+static void tx_bits(uint8_t *dst, const char *s, size_t n)
+{
+	for (size_t i = 0; i < n; i++)
+		dst[i] = s[i] == '1';
+}
+
+extern "C" int trx_tx_tables_generate(trx_tx_tables *t)
+{
+	memset(t, 0, sizeof(*t));
+	t->magic = TRX_TX_TABLES_MAGIC;
+	t->version = TRX_TX_TABLES_VERSION;
+
+	// generateGSMPulse(4) :501-517 and generateC1Pulse :447-458: the Laurent pulses as tabulated doubles, stored as float
+	static const double c0_4[16] = {
+		0.0, 4.46348606e-03, 2.84385729e-02, 1.03184855e-01, 2.56065552e-01, 4.76375085e-01,
+		7.05961177e-01, 8.71291644e-01, 9.29453645e-01, 8.71291644e-01, 7.05961177e-01,
+		4.76375085e-01, 2.56065552e-01, 1.03184855e-01, 2.84385729e-02, 4.46348606e-03 };
+	static const double c1_4[8] = {
+		0.0, 8.16373112e-03, 2.84385729e-02, 5.64158904e-02, 7.05463553e-02, 5.64158904e-02,
+		2.84385729e-02, 8.16373112e-03 };
+	for (int i = 0; i < 16; i++) t->pulse4_c0[i] = (float)c0_4[i];
+	for (int i = 0; i < 8; i++) t->pulse4_c1[i] = (float)c1_4[i];
+
+	// generateGSMPulse(1) :519-533, normalised by sqrt(vectorNorm2) :535-543 (norm2 = i*i + r*r, Complex.h:113)
+	{
+		const int len = 4, sps = 1;
+		float center = (float)(len - 1.0) / 2.0;
+		float energy = 0.0f;
+		for (int i = 0; i < len; i++) {
+			float arg = ((float)i - center) / (float)sps;
+			t->pulse1_c0[i] = 0.96 * std::exp(-1.1380 * arg * arg - 0.527 * arg * arg * arg * arg);
+			energy += 0.0f * 0.0f + t->pulse1_c0[i] * t->pulse1_c0[i];
+		}
+		float avg = sqrtf(energy / sps);
+		for (int i = 0; i < len; i++)
+			t->pulse1_c0[i] /= avg;
+	}
+
+	// initGMSKRotationTables :191-216: phase accumulated in double, complex(cos(phase), sin(phase)) narrows to float
+	double phase = 0.0;
+	for (int i = 0; i < 625; i++) {
+		t->rot4[i].re = std::cos(phase);
+		t->rot4[i].im = std::sin(phase);
+		phase += M_PI / 2.0 / 4.0;
+	}
+	phase = 0.0;
+	for (int i = 0; i < 157; i++) {
+		t->rot1[i].re = std::cos(phase);
+		t->rot1[i].im = std::sin(phase);
+		phase += M_PI / 2.0;
+	}
+
+	// psk8_table :66-75: Complex<float> from double literals
+	static const double psk8[8][2] = {
+		{ -0.70710678, 0.70710678 }, { 0.0, -1.0 }, { 0.0, 1.0 }, { 0.70710678, -0.70710678 },
+		{ -1.0, 0.0 }, { -0.70710678, -0.70710678 }, { 0.70710678, 0.70710678 }, { 1.0, 0.0 } };
+	for (int i = 0; i < 8; i++) {
+		t->psk8[i].re = (float)psk8[i][0];
+		t->psk8[i].im = (float)psk8[i][1];
+	}
+
+	// shapeEdgeBurst :750-756 / rotateEdgeBurst :680-686: float phase = i * 3.0f * M_PI / 8.0f (size_t i: i * 3.0f is
+	// float, * M_PI double, / 8.0f double, narrowed to float), then cos / sin of that float (the float overloads)
+	for (size_t i = 0; i < TRX_TX_EDGE_SYMS; i++) {
+		float ph = i * 3.0f * M_PI / 8.0f;
+		t->edge_rot[i].re = std::cos(ph);
+		t->edge_rot[i].im = std::sin(ph);
+	}
+
+	// 3GPP TS 45.002 sections 5.2.3, 5.2.6, 5.2.7
+	tx_bits(t->dummy_burst,
+		"0001111101101110110000010100100111000001001000100000001111100011100010111000101110001010111010010100011001100111001111010011111000100101111101010000",
+		148);
+	tx_bits(t->rach_burst, "0011101001001011011111111001100110101010001111000", 49);
+	static const char *const tsc[8] = {
+		"00100101110000100010010111", "00101101110111100010110111", "01000011101110100100001110",
+		"01000111101101000100011110", "00011010111001000001101011", "01001110101100000100111010",
+		"10100111110110001010011111", "11101111000100101110111100" };
+	static const char *const edge_tsc[8] = {
+		"111111001111111001111001001001111111111111001111111111001111111001111001001001",
+		"111111001111001001111001001001111001001001001111111111001111001001111001001001",
+		"111001111111111111001001001111001001001111001111111001111111111111001001001111",
+		"111001111111111001001001001111001001111001111111111001111111111001001001001111",
+		"111111111001001111001111001001001111111001111111111111111001001111001111001001",
+		"111001111111001001001111001111001001111111111111111001111111001001001111001111",
+		"001111001111111001001001001001111001001111111111001111001111111001001001001001",
+		"001001001111001001001001111111111001111111001111001001001111001001001001111111" };
+	for (int k = 0; k < 8; k++) {
+		tx_bits(t->tsc[k], tsc[k], 26);
+		tx_bits(t->edge_tsc[k], edge_tsc[k], 78);
+	}
+	return 0;
+}

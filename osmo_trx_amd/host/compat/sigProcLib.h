@@ -1,6 +1,6 @@
 // compat/sigProcLib.h -- STAND-ALONE BUILD ONLY, see compat/Complex.h.
 //
-// The receive-side declarations of the reference's Transceiver52M/sigProcLib.h:27-152 (same names, argument
+// The declarations of the reference's Transceiver52M/sigProcLib.h:27-152 (same names, argument
 // meaning, return values and ownership rules) for building the shim where no osmo-trx checkout is at hand.
 // The product build does NOT use this file: it includes osmo-trx's own sigProcLib.h, so that
 // libtrxsigproc.so is link- and layout-compatible with reference-compiled callers (host/README in INTEGRATION.md).
@@ -77,6 +77,22 @@ SoftVector *demodAnyBurst(const signalVector &burst, CorrType detected, int sps,
 
 /* -1 .. +1 soft values to 0 .. 1 (sigProcLib.h:63) */
 void vectorSlicer(float *out, const float *in, size_t n);
+
+/* ---- the transmit side (sigProcLib.h:65-87): every call returns a new vector the caller deletes, or NULL */
+
+/* GMSK: 625 samples at 4 SPS, sps * (bits + guard) at 1 SPS or with the empty pulse */
+signalVector *modulateBurst(const BitVector &wBurst, int guardPeriodLength, int sps, bool emptyPulse = false);
+/* 8-PSK: 625 samples at 4 SPS, sps * bits / 3 with the empty pulse */
+signalVector *modulateEdgeBurst(const BitVector &bits, int sps, bool emptyPulse = false);
+/* random-payload 8-PSK burst, 4 SPS only (rand()) */
+signalVector *generateEdgeBurst(int tsc);
+/* zeros of a burst's length, 4 or 1 SPS */
+signalVector *generateEmptyBurst(int sps, int tn);
+/* random-payload GMSK normal / access burst, 4 or 1 SPS (rand()) */
+signalVector *genRandNormalBurst(int tsc, int sps, int tn);
+signalVector *genRandAccessBurst(int delay, int sps, int tn);
+/* the dummy burst, 4 or 1 SPS */
+signalVector *generateDummyBurst(int sps, int tn);
 
 /* ---- helpers that are entry points of their own */
 

@@ -144,6 +144,15 @@ extern "C" void trxsigproc_abi_layout(size_t out[8])
 	out[7] = sizeof(Vector<float>);
 }
 
+void *trxsigproc_thread_scratch(size_t bytes, void **stream)
+{
+	Scratch &t = tls;
+	if (!t.ensure(1, bytes, 1))
+		return nullptr;
+	*stream = t.stream;
+	return t.d_iq;
+}
+
 static void gpu_error(const char *where)
 {
 	/* the reference would LOG(ERR); the shim has no libosmocore logging context, stderr it is */

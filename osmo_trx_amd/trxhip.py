@@ -20,7 +20,15 @@ RESULT_DTYPE = np.dtype([
     ("energy", "<f4"), ("rssi", "<f4"), ("tsc", "u1"), ("clip", "u1"), ("idle", "u1"), ("nbits_div4", "u1"),
 ])
 TRXD_META_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("version", "u1"), ("tss", "u1"), ("reserved", "u1")])
+# trxhip_tx_params / trxhip_tx_info (include/trxhip.h, the transmit side)
+TX_PARAMS_DTYPE = np.dtype([("nbits", "<u2"), ("guard", "u1"), ("flags", "u1"), ("scale_re", "<f4"), ("scale_im", "<f4"),
+                            ("reserved", "<u4")])
+TX_INFO_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("version", "u1"), ("tx_att", "u1"), ("mod_8psk", "u1"),
+                          ("nbits", "<u2"), ("length", "<u2"), ("status", "<i4")])
 assert PARAMS_DTYPE.itemsize == 8 and RESULT_DTYPE.itemsize == 32 and TRXD_META_DTYPE.itemsize == 8
+assert TX_PARAMS_DTYPE.itemsize == 16 and TX_INFO_DTYPE.itemsize == 16
+TX_8PSK = 1             # TRXHIP_TX_8PSK
+TX_EMPTY_PULSE = 2      # TRXHIP_TX_EMPTY_PULSE
 
 TRXD_RECORD_BYTES = 156
 FLAG_SLICE = 1          # TRXHIP_FLAG_SLICE
@@ -98,6 +106,10 @@ SYMBOLS = {
     "trxhip_dft_batch": (_I, [_VP, _VP, _VP, _I, _SZ, _SZ, _SZ, _I, _VP]),
     "trxhip_channelize_batch": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _I, _VP]),
     "trxhip_resample_batch": (_I, [_VP, _VP, _VP, _SZ, _I, _I, _SZ, _SZ, _SZ, _VP]),
+    "trxhip_modulate_batch": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _F, _SZ, _VP, _SZ, _I, _VP]),
+    "trxhip_modulate_trxd_batch": (_I, [_VP, _VP, _SZ, _VP, C.c_double, _I, _VP, _VP, _F, _SZ, _VP, _SZ, _VP]),
+    "trxhip_tx_tables_size": (_SZ, []),
+    "trxhip_tx_tables_generate_host": (_I, [_VP, _SZ]),
     "trxhip_rx_frontend_create": (_I, [_VP, _I, _I, _I, C.POINTER(_VP)]),
     "trxhip_rx_frontend_destroy": (None, [_VP]),
     "trxhip_rx_frontend_reset": (_I, [_VP, _VP]),
@@ -141,6 +153,30 @@ def generate_tables_host():
     buf = (C.c_ubyte * n)()
     _check(L.trxhip_tables_generate_host(buf, n), "trxhip_tables_generate_host")
     return bytes(buf)
+
+
+def generate_tx_tables_host():
+    """The transmit table struct (csrc/trx_tx_tables.h) as bytes (host-only; works without a GPU)."""
+    L = load_library()
+    n = L.trxhip_tx_tables_size()
+    buf = (C.c_ubyte * n)()
+    _check(L.trxhip_tx_tables_generate_host(buf, n), "trxhip_tx_tables_generate_host")
+    return bytes(buf)
+
+
+def tx_params_host(nbits, guard=0, flags=0, scale=1.0, n=None):
+    """TX_PARAMS_DTYPE[n] from per-burst arrays or scalars (broadcast) of nbits, guard, flags and complex scale (1.0: unscaled).
+    n: the number of bursts when every argument is a scalar (default: the longest argument)."""
+    args = [np.atleast_1d(np.asarray(x)) for x in (nbits, guard, flags, scale)]
+    if n is None:
+        n = max(len(x) for x in args)
+    nbits, guard, flags, sc = (np.broadcast_to(x, (n,)) for x in args)
+    p = np.zeros(n, dtype=TX_PARAMS_DTYPE)
+    p["nbits"], p["guard"], p["flags"] = nbits, guard, flags
+    sc = sc.astype(np.complex128)
+    p["scale_re"] = sc.real.astype(np.float32)
+    p["scale_im"] = sc.imag.astype(np.float32)
+    return p
 
 
 def tables_checksum(blob):
@@ -220,6 +256,12 @@ class TrxHip:
         a = np.ascontiguousarray(params_np, dtype=PARAMS_DTYPE).view(np.uint8).reshape(-1, 8)
         return torch.from_numpy(a.copy()).to(f"cuda:{self.device}")
 
+    def tx_params_tensor(self, params_np):
+        """TX_PARAMS_DTYPE[n] numpy -> uint8[n, 16] device tensor."""
+        torch = self.torch
+        a = np.ascontiguousarray(params_np, dtype=TX_PARAMS_DTYPE).view(np.uint8).reshape(-1, 16)
+        return torch.from_numpy(a.copy()).to(f"cuda:{self.device}")
+
     def select_diversity(self, iq_paths, sps=4, stream=None):
         """Transceiver.cpp:723-741.  iq_paths: int16[n, n_paths, burst_len, 2] -> (iq_sel int16[n, burst_len, 2],
         avg_energy float32[n], path uint8[n])."""
@@ -275,6 +317,51 @@ class TrxHip:
                 self._stream(stream))
         _check(rc, "trxhip_detect_demod_batch")
         return results, soft
+
+    # ---- transmit side ------------------------------------------------------------------------------
+    def _tx_outputs(self, n, out_stride, cf32, s16_scale):
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        out = torch.empty((n, out_stride), dtype=torch.complex64, device=dev) if cf32 else None
+        s16 = torch.empty((n, out_stride, 2), dtype=torch.int16, device=dev) if s16_scale is not None else None
+        return out, s16
+
+    def modulate(self, bits, params, sps=4, cf32=True, s16_scale=None, out_stride=625, stream=None):
+        """modulateBurst() / modulateEdgeBurst() over a batch.  bits: uint8[n, bits_stride] (bit 0 of each byte counts),
+        params: uint8[n, 16] (tx_params_tensor).  Returns (complex64[n, out_stride] or None, int16[n, out_stride, 2] or None
+        -- only with s16_scale --, int32[n] lengths, TRXHIP_EINVAL where a descriptor was refused)."""
+        torch = self.torch
+        n, stride = bits.shape
+        assert params.shape == (n, 16) and params.dtype == torch.uint8
+        out, s16 = self._tx_outputs(n, out_stride, cf32, s16_scale)
+        lens = torch.empty(n, dtype=torch.int32, device=bits.device)
+        _check(self.L.trxhip_modulate_batch(self.h, self._dev(bits, torch.uint8), stride, self._dev(params),
+                                            self._dev(out) if out is not None else _VP(0),
+                                            self._dev(s16) if s16 is not None else _VP(0),
+                                            float(s16_scale or 0.0), out_stride, self._dev(lens), n, sps, self._stream(stream)),
+               "trxhip_modulate_batch")
+        return out, s16, lens
+
+    def modulate_trxd(self, dgrams, lengths, full_scale, sps=4, cf32=True, s16_scale=None, out_stride=625, stream=None):
+        """TRXD downlink datagrams -> burst samples (driveTxPriorityQueue + addRadioVector).  dgrams: uint8[n, dgram_stride],
+        lengths: uint16 as int16/int32 tensor of n.  Returns (complex64 rows or None, int16 rows or None, uint8[n, 16] info
+        records: TX_INFO_DTYPE)."""
+        torch = self.torch
+        n, stride = dgrams.shape
+        lens = lengths.to(torch.int32).to(torch.int16).contiguous()      # uint16 bit pattern
+        assert lens.shape == (n,)
+        out, s16 = self._tx_outputs(n, out_stride, cf32, s16_scale)
+        info = torch.empty((n, 16), dtype=torch.uint8, device=dgrams.device)
+        _check(self.L.trxhip_modulate_trxd_batch(self.h, self._dev(dgrams, torch.uint8), stride, self._dev(lens), float(full_scale),
+                                                 sps, self._dev(out) if out is not None else _VP(0),
+                                                 self._dev(s16) if s16 is not None else _VP(0), float(s16_scale or 0.0),
+                                                 out_stride, self._dev(info), n, self._stream(stream)),
+               "trxhip_modulate_trxd_batch")
+        return out, s16, info
+
+    @staticmethod
+    def tx_info_to_numpy(info):
+        return info.cpu().numpy().reshape(-1).view(TX_INFO_DTYPE)
 
     def demod_only(self, iq_cf32, params, ebp, sps=4, soft_stride=156, slice_bits=False, exact=False, stream=None):
         """demodAnyBurst() alone: iq complex64[n, L], params uint8[n, 8], ebp float32[n, 4] = {toa, amp_re, amp_im, 0}."""
