@@ -12,6 +12,9 @@
  *   convolve_real()/convolve_complex()        Transceiver52M/arch/common/convolve.h:6-14
  *   Channelizer::rotate()                     Transceiver52M/Channelizer.cpp:74-99
  *   Resampler::rotate()                       Transceiver52M/Resampler.cpp:131-150
+ *   Synthesis::rotate()                       Transceiver52M/Synthesis.cpp:66-104
+ *   RadioInterfaceMulti::pushBuffer()         Transceiver52M/radioInterfaceMulti.cpp:316-362
+ *   RadioInterfaceResamp::pushBuffer()        Transceiver52M/radioInterfaceResamp.cpp:196-230
  *
  * The reference runs these one burst at a time on one CPU thread per ARFCN; here they are batched:
  * one call processes N independent bursts that are resident in device memory (HBM).  The
@@ -417,6 +420,14 @@ int trxhip_channelize_batch(trxhip_ctx *ctx, const int16_t *d_in, float *d_out,
 int trxhip_resample_batch(trxhip_ctx *ctx, const float *d_in, float *d_out, size_t n_in, int p, int q,
 			  size_t n_chan, size_t in_stride, size_t out_stride, void *stream);
 
+/* Synthesis(m, block_len, h_len)::rotate batched over blocks: the counterpart of trxhip_channelize_batch (m = 4, h_len = 16,
+ * TRXHIP_ENOTSUP otherwise).  A forward, unnormalised 4-point DFT across the m rows at every time (cxvec_fft), the 16-tap
+ * path filters (convolve_real with ChannelizerBase's sub-filters), the interleave out[m*t + k] = y_k[t] (Synthesis.cpp:39-50).
+ * d_in : m rows x (n_blocks*block_len) complex64, row c at d_in + 2*c*in_stride (Synthesis::inputBuffer(c))
+ * d_out: n_blocks*block_len*m complex64, interleaved; zero history before block 0, carried between blocks */
+int trxhip_synthesize_batch(trxhip_ctx *ctx, const float *d_in, size_t in_stride, float *d_out,
+			    size_t n_blocks, int m, int block_len, int h_len, void *stream);
+
 /* ---- transmit side: the GMSK / 8-PSK burst modulators of sigProcLib.cpp, batched ----
  * modulateBurst()       sigProcLib.cpp:970-979   (Transceiver.cpp:392-396, :107-120 through the burst generators)
  *   modulateBurstLaurent  :595-670  GMSK at 4 SPS: c0 through the 16-tap pulse + c1 through the 8-tap pulse, 625 samples
@@ -514,6 +525,37 @@ int  trxhip_rx_frontend_seed(trxhip_rx_frontend *f, const int16_t *d_wide_prev, 
  * d_out : 4 channels x (n_blocks*block_len*p/q) complex64, channel c at d_out + 2*c*out_stride floats */
 int  trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t n_blocks, float *d_out,
 			     size_t out_stride, void *stream);
+
+/* ---- streaming transmit front end: RadioInterfaceMulti::pushBuffer() (radioInterfaceMulti.cpp:316-362) and
+ * RadioInterfaceResamp::pushBuffer() (radioInterfaceResamp.cpp:196-230) ----
+ * MULTI : chans 1..3 logical channels at the low rate; Resampler(p, q, 16) per active filterbank path (1 chan: path 0 <-
+ *         lchan 0; 2: 0 <- 0, 3 <- 1; 3: 0 <- 1, 1 <- 0, 3 <- 2: radioInterfaceMulti.cpp:92-124, :214-231), zero rows on the
+ *         others, then Synthesis(4, block_len*p/q, 16).  The reference: Resampler(48, 65) at block_len 260.
+ * RESAMP: chans == 1, Resampler(p, q, 16) alone: (96, 65) at 64 MHz clocking and block_len 260, (75, 52) at 100 MHz and 208.
+ * bw is Resampler::init's cutoff: 1.0 in RadioInterfaceMulti, 0.45 in RadioInterfaceResamp at tx_sps 4, 1.0 otherwise.
+ * The object carries what the reference carries between calls (the RadioBuffer headroom in front of every segment,
+ * radioBuffer.cpp:29-47, and Synthesis::hist), so any chunking of a stream gives the result of processing it in one
+ * piece; a fresh or reset object starts from zero history.
+ * Refused with TRXHIP_EINVAL: no context, an unknown mode, chans outside 1..3 (MULTI) or != 1 (RESAMP), p outside 1..128,
+ * q < 1, block_len % q != 0, q * ceil(256 / p) > 3072, bw not positive. */
+#define TRXHIP_TXFE_MULTI  0   /* RadioInterfaceMulti::pushBuffer: chans 1..3, per-path Resampler(p,q) + Synthesis(4) */
+#define TRXHIP_TXFE_RESAMP 1   /* RadioInterfaceResamp::pushBuffer: chans == 1, Resampler(p,q) only */
+typedef struct trxhip_tx_frontend trxhip_tx_frontend;
+int  trxhip_tx_frontend_create(trxhip_ctx *ctx, int mode, int chans, int block_len, int p, int q, float bw,
+			       trxhip_tx_frontend **out);   /* block_len = low-rate samples per block per channel */
+void trxhip_tx_frontend_destroy(trxhip_tx_frontend *f);
+int  trxhip_tx_frontend_reset(trxhip_tx_frontend *f, void *stream);   /* zero the carried history */
+/* Start mid-stream: the carried state of a stream processed up to here.  d_in_prev holds the n_blocks_prev blocks that
+ * immediately precede the shard, laid out as d_in of trxhip_tx_frontend_push(); one block suffices, because every filter
+ * is FIR with at most 15 + ceil(15 q / p) low-rate samples of memory.  n_blocks_prev = 0 is trxhip_tx_frontend_reset(). */
+int  trxhip_tx_frontend_seed(trxhip_tx_frontend *f, const float *d_in_prev, size_t in_stride, size_t n_blocks_prev,
+			     void *stream);
+/* d_in: chans logical channels, complex64, lchan l at d_in + 2*l*in_stride, n_blocks*block_len samples each.
+ * Output per block: MULTI 4*block_len*p/q wideband samples, RESAMP block_len*p/q.
+ * d_out_cf32 and/or d_out_s16 (at least one non-NULL); s16 = (int16_t)(int)(x * s16_scale), the expression of
+ * trxhip_convert_float_short().  RadioInterfaceMulti passes s16_scale = (float)(1.0 / chans). */
+int  trxhip_tx_frontend_push(trxhip_tx_frontend *f, const float *d_in, size_t in_stride, size_t n_blocks,
+			     float *d_out_cf32, int16_t *d_out_s16, float s16_scale, void *stream);
 
 #ifdef __cplusplus
 }

@@ -736,4 +736,196 @@ int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t
 	return trx_launch_resample(f->d_chan, d_out, n_total, f->p, f->q, 4, f->cap, out_stride, f->d_parts, hist_in, s);
 }
 
+
+int trxhip_synthesize_batch(trxhip_ctx *ctx, const float *d_in, size_t in_stride, float *d_out, size_t n_blocks, int m,
+			    int block_len, int h_len, void *stream)
+{
+	if (!ctx || !d_in || !d_out || block_len < 1)
+		return TRXHIP_EINVAL;
+	if (m != 4 || h_len != 16)
+		return TRXHIP_ENOTSUP;                 /* the reference instantiates Synthesis(4, 192, 16) only */
+	const size_t n_total = n_blocks * (size_t)block_len;
+	if (n_total == 0)
+		return TRXHIP_OK;
+	if (in_stride < n_total)
+		return TRXHIP_EINVAL;
+	if (with_device(ctx))
+		return TRXHIP_EIO;
+	return trx_launch_synthesize(d_in, in_stride, nullptr, d_out, nullptr, 0.0f, n_total, ctx->d_tables,
+				     static_cast<hipStream_t>(stream));
+}
+
+/* ---- streaming Tx front end: RadioInterfaceMulti::pushBuffer (radioInterfaceMulti.cpp:316-362) and
+ *      RadioInterfaceResamp::pushBuffer (radioInterfaceResamp.cpp:196-230) ---- */
+struct trxhip_tx_frontend {
+	trxhip_ctx *ctx;
+	int mode, chans, block_len, p, q;
+	bool fused;              /* MULTI whose geometry fits the fused kernel's tiles */
+	int hl;                  /* fused: low-rate samples of history per logical channel */
+	float *d_parts;          /* [p][16] resampler partitions, Resampler::initFilters(bw) */
+	void *d_hist;            /* fused: [chans][hl] complex64, the low-rate samples -hl .. -1 */
+	void *d_rs_hist;         /* otherwise: resample_kernel's [chans][16] (samples -15 .. -1 at 0 .. 14) */
+	void *d_row_hist;        /* MULTI unfused: [4][16], the channel-rate rows' samples -15 .. -1 */
+	float *d_scratch;        /* MULTI unfused: [4][cap] channel-rate rows; RESAMP: cap resampled samples (int16-only output) */
+	size_t cap;
+};
+
+static size_t txfe_out_per_block(const trxhip_tx_frontend *f)
+{
+	return (size_t)f->block_len / f->q * f->p * (f->mode == TRXHIP_TXFE_MULTI ? 4 : 1);
+}
+
+int trxhip_tx_frontend_create(trxhip_ctx *ctx, int mode, int chans, int block_len, int p, int q, float bw, trxhip_tx_frontend **out)
+{
+	if (!ctx || !out || (mode != TRXHIP_TXFE_MULTI && mode != TRXHIP_TXFE_RESAMP))
+		return TRXHIP_EINVAL;
+	if (mode == TRXHIP_TXFE_MULTI ? (chans < 1 || chans > 3) : chans != 1)
+		return TRXHIP_EINVAL;
+	if (p < 1 || p > 128 || q < 1 || block_len < 1 || (block_len % q) != 0 || !(bw > 0.0f) || !std::isfinite(bw))
+		return TRXHIP_EINVAL;                  /* Resampler::rotate needs whole q-sample groups per block (Resampler.cpp:100-112) */
+	if ((long long)q * ((256 + p - 1) / p) > 3072)
+		return TRXHIP_EINVAL;                  /* resample_kernel's tile */
+	if (with_device(ctx))
+		return TRXHIP_EIO;
+	trxhip_tx_frontend *f = new (std::nothrow) trxhip_tx_frontend();
+	if (!f)
+		return TRXHIP_ENOMEM;
+	f->ctx = ctx; f->mode = mode; f->chans = chans; f->block_len = block_len; f->p = p; f->q = q;
+	f->hl = 15 + (15 * q + p - 1) / p;
+	f->fused = mode == TRXHIP_TXFE_MULTI && trx_tx_fused_tm(p, q) > 0 && f->hl <= 256;
+	float *taps = static_cast<float *>(malloc((size_t)p * 16 * sizeof(float)));
+	if (!taps) { delete f; return TRXHIP_ENOMEM; }
+	trx_polyphase_taps((unsigned)p, (unsigned)q, 16, bw, taps);
+	bool ok = hipMalloc((void **)&f->d_parts, (size_t)p * 16 * sizeof(float)) == hipSuccess &&
+		  hipMemcpy(f->d_parts, taps, (size_t)p * 16 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+		  hipMalloc(&f->d_hist, (size_t)chans * f->hl * 8) == hipSuccess &&
+		  hipMalloc(&f->d_rs_hist, (size_t)chans * 16 * 8) == hipSuccess &&
+		  hipMalloc(&f->d_row_hist, 4 * 16 * 8) == hipSuccess;
+	free(taps);
+	if (!ok || trxhip_tx_frontend_reset(f, nullptr) != TRXHIP_OK || hipDeviceSynchronize() != hipSuccess) {
+		trxhip_tx_frontend_destroy(f);
+		return TRXHIP_ENOMEM;
+	}
+	*out = f;
+	return TRXHIP_OK;
+}
+
+void trxhip_tx_frontend_destroy(trxhip_tx_frontend *f)
+{
+	if (!f)
+		return;
+	if (with_device(f->ctx) == 0) {
+		if (f->d_parts) (void)hipFree(f->d_parts);
+		if (f->d_hist) (void)hipFree(f->d_hist);
+		if (f->d_rs_hist) (void)hipFree(f->d_rs_hist);
+		if (f->d_row_hist) (void)hipFree(f->d_row_hist);
+		if (f->d_scratch) (void)hipFree(f->d_scratch);
+	}
+	delete f;
+}
+
+int trxhip_tx_frontend_reset(trxhip_tx_frontend *f, void *stream)
+{
+	if (!f || with_device(f->ctx))
+		return TRXHIP_EINVAL;
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	if (hipMemsetAsync(f->d_hist, 0, (size_t)f->chans * f->hl * 8, s) != hipSuccess ||
+	    hipMemsetAsync(f->d_rs_hist, 0, (size_t)f->chans * 16 * 8, s) != hipSuccess ||
+	    hipMemsetAsync(f->d_row_hist, 0, 4 * 16 * 8, s) != hipSuccess)
+		return TRXHIP_EIO;
+	return TRXHIP_OK;
+}
+
+int trxhip_tx_frontend_seed(trxhip_tx_frontend *f, const float *d_in_prev, size_t in_stride, size_t n_blocks_prev, void *stream)
+{
+	if (!f)
+		return TRXHIP_EINVAL;
+	int rc = trxhip_tx_frontend_reset(f, stream);
+	if (rc || n_blocks_prev == 0)
+		return rc;
+	if (!d_in_prev)
+		return TRXHIP_EINVAL;
+	/* run the preceding blocks through the very same launches (their output is discarded): what they leave behind is the
+	 * state of a stream processed up to here */
+	float *scratch = nullptr;
+	if (hipMalloc((void **)&scratch, n_blocks_prev * txfe_out_per_block(f) * 8) != hipSuccess)
+		return TRXHIP_ENOMEM;
+	rc = trxhip_tx_frontend_push(f, d_in_prev, in_stride, n_blocks_prev, scratch, nullptr, 0.0f, stream);
+	if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess && rc == TRXHIP_OK)
+		rc = TRXHIP_EIO;
+	(void)hipFree(scratch);
+	return rc;
+}
+
+static int txfe_scratch(trxhip_tx_frontend *f, size_t n, hipStream_t s)
+{
+	if (n <= f->cap)
+		return TRXHIP_OK;
+	if (f->d_scratch) (void)hipFree(f->d_scratch);
+	f->d_scratch = nullptr;
+	f->cap = 0;
+	const size_t rows = f->mode == TRXHIP_TXFE_MULTI ? 4 : 1;
+	if (hipMalloc((void **)&f->d_scratch, rows * n * 8) != hipSuccess)
+		return TRXHIP_ENOMEM;
+	if (hipMemsetAsync(f->d_scratch, 0, rows * n * 8, s) != hipSuccess)      /* the rows of inactive paths stay zero */
+		return TRXHIP_EIO;
+	f->cap = n;
+	return TRXHIP_OK;
+}
+
+int trxhip_tx_frontend_push(trxhip_tx_frontend *f, const float *d_in, size_t in_stride, size_t n_blocks, float *d_out_cf32,
+			    int16_t *d_out_s16, float s16_scale, void *stream)
+{
+	if (!f || !d_in || (!d_out_cf32 && !d_out_s16))
+		return TRXHIP_EINVAL;
+	if ((reinterpret_cast<uintptr_t>(d_in) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_out_cf32) & 7) != 0 ||
+	    (reinterpret_cast<uintptr_t>(d_out_s16) & 3) != 0)
+		return TRXHIP_EINVAL;
+	if (n_blocks == 0)
+		return TRXHIP_OK;
+	const size_t n_in = n_blocks * (size_t)f->block_len;
+	if (f->chans > 1 && in_stride < n_in)
+		return TRXHIP_EINVAL;
+	if (with_device(f->ctx))
+		return TRXHIP_EIO;
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	const size_t n_times = n_in / f->q * f->p;                /* channel-rate samples per path */
+	int rc;
+	if (f->mode == TRXHIP_TXFE_RESAMP) {
+		float *cf = d_out_cf32;
+		if (!cf) {
+			if ((rc = txfe_scratch(f, n_times, s)) != TRXHIP_OK)
+				return rc;
+			cf = f->d_scratch;
+		}
+		rc = trx_launch_resample(d_in, cf, n_in, f->p, f->q, 1, in_stride, n_times, f->d_parts, f->d_rs_hist, s);
+		if (rc == TRXHIP_OK && d_out_s16)
+			rc = trx_launch_convert_float_short(d_out_s16, cf, s16_scale, 2 * n_times, s);
+		return rc;
+	}
+	if (f->fused) {
+		/* one pass, the channel-rate rows stay on the chip (trx_tx_frontend.hip, tx_frontend_fused_kernel) */
+		rc = trx_launch_tx_frontend_fused(d_in, in_stride, n_in, f->d_hist, f->hl, d_out_cf32, d_out_s16, s16_scale, f->chans, f->p,
+						  f->q, f->d_parts, f->ctx->d_tables, s);
+		if (rc != 1)
+			return rc ? rc : trx_launch_tx_save_hist(d_in, n_in, in_stride, f->chans, f->d_hist, f->hl, f->hl, s);
+	}
+	/* a geometry that does not fit the fused kernel's tiles: the resampler into channel-rate rows, then the synthesis bank */
+	if ((rc = txfe_scratch(f, n_times, s)) != TRXHIP_OK)
+		return rc;
+	static const int pchan_of[3][3] = { { 0, -1, -1 }, { 0, 3, -1 }, { 0, 1, 3 } };
+	static const int lchan_of[3][3] = { { 0, -1, -1 }, { 0, 1, -1 }, { 1, 0, 2 } };   /* radioInterfaceMulti.cpp:92-124 */
+	for (int c = 0; c < f->chans; c++) {
+		const int pc = pchan_of[f->chans - 1][c], l = lchan_of[f->chans - 1][c];
+		rc = trx_launch_resample(d_in + 2 * (size_t)l * in_stride, f->d_scratch + 2 * (size_t)pc * f->cap, n_in, f->p, f->q, 1,
+					 in_stride, f->cap, f->d_parts, static_cast<char *>(f->d_rs_hist) + (size_t)l * 16 * 8, s);
+		if (rc)
+			return rc;
+	}
+	rc = trx_launch_synthesize(f->d_scratch, f->cap, f->d_row_hist, d_out_cf32, d_out_s16, s16_scale, n_times, f->ctx->d_tables, s);
+	if (rc)
+		return rc;
+	return trx_launch_tx_save_hist(f->d_scratch, n_times, f->cap, 4, f->d_row_hist, 15, 16, s);
+}
+
 }  // extern "C"

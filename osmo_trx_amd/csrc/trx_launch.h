@@ -74,6 +74,16 @@ int trx_launch_delay_vector(const float *d_in, float *d_out, const float *d_dela
 int trx_launch_scale_vector(float *d_x, size_t len, float sr, float si, hipStream_t stream);
 int trx_launch_vector_slicer(float *d_dst, const float *d_src, size_t len, hipStream_t stream);
 
+/* ---- trx_tx_frontend.hip: Synthesis(4, ., 16) and the fused multi-ARFCN transmit front end ----
+ * d_hist of trx_launch_synthesize: NULL (zero history) or the 4 rows' samples -15 .. -1 at [c * 16 + 0 .. 14] */
+int trx_launch_synthesize(const float *d_in, size_t in_stride, const void *d_hist, float *d_out_cf32, int16_t *d_out_s16,
+			  float scale, size_t n_times, const trx_tables *d_tab, hipStream_t stream);
+int trx_launch_tx_save_hist(const float *d_x, size_t n, size_t stride, int n_chan, void *d_hist, int hn, int hs, hipStream_t stream);
+int trx_tx_fused_tm(int p, int q);
+int trx_launch_tx_frontend_fused(const float *d_in, size_t in_stride, size_t n_in, const void *d_hist, int hl, float *d_out_cf32,
+				 int16_t *d_out_s16, float scale, int chans, int p, int q, const float *d_parts, const trx_tables *d_tab,
+				 hipStream_t stream);
+
 /* ---- trx_tx.hip: the burst modulators (trxhip_modulate_batch, trxhip_modulate_trxd_batch) ----
  * d_dgram_len == NULL: d_in holds bits (in_stride bytes per burst) and d_params the descriptors; otherwise d_in holds TRXD
  * datagrams (in_stride bytes each), d_dgram_len their lengths and h_att_scale the 256 scales by tx_att (host memory, passed

@@ -21,6 +21,7 @@
 #include "trxBatch.h"
 #include "trxPullRadioVector.h"
 #include "MultiArfcnRx.h"
+#include "MultiArfcnTx.h"
 
 // "signalvector is owning despite claiming not to" (Transceiver.cpp:648-654): a vector built over memory it must not
 // delete[] gets a no-op deallocator, exactly as pullRadioVector() does for its shift buffer (:680)
@@ -469,6 +470,32 @@ int main(int argc, char **argv)
 			fwrite(out[l].data(), sizeof(complex), out[l].size(), f);
 			fclose(f);
 		}
+		sigProcLibDestroy();
+		return 0;
+	}
+	// multi_tx <in.cf32> <n_blocks> <chans> <out.s16>: MultiArfcnTx::pushBuffer in chunks of 1, 2, 3, ... blocks.  in.cf32 holds
+	// the chans logical channels one after the other, n_blocks * 260 complex samples each; out.s16 the wideband int16 IQ stream
+	if (!strcmp(argv[1], "multi_tx") && argc == 6) {
+		std::vector<char> raw = slurp(argv[2]);
+		const size_t n_blocks = atol(argv[3]), chans = atol(argv[4]), bl = 260;
+		MultiArfcnTx tx(chans);
+		if (!tx.init()) { fprintf(stderr, "MultiArfcnTx::init failed\n"); return 5; }
+		const complex *x = reinterpret_cast<const complex *>(raw.data());
+		const size_t per_block = bl / 65 * 48 * MultiArfcnTx::MCHANS;      /* wideband samples per block */
+		std::vector<int16_t> wide(n_blocks * per_block * 2);
+		std::vector<std::vector<complex> > in(chans);
+		size_t pos = 0, step = 1;
+		while (pos < n_blocks) {
+			const size_t nb = step < n_blocks - pos ? step : n_blocks - pos;
+			for (size_t l = 0; l < chans; l++)
+				in[l].assign(x + l * n_blocks * bl + pos * bl, x + l * n_blocks * bl + (pos + nb) * bl);
+			if (tx.pushBuffer(in, nb, wide.data() + pos * per_block * 2)) { fprintf(stderr, "pushBuffer failed\n"); return 6; }
+			pos += nb;
+			step++;
+		}
+		FILE *f = fopen(argv[5], "wb");
+		fwrite(wide.data(), sizeof(int16_t), wide.size(), f);
+		fclose(f);
 		sigProcLibDestroy();
 		return 0;
 	}

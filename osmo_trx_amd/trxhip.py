@@ -115,6 +115,12 @@ SYMBOLS = {
     "trxhip_rx_frontend_reset": (_I, [_VP, _VP]),
     "trxhip_rx_frontend_seed": (_I, [_VP, _VP, _SZ, _VP]),
     "trxhip_rx_frontend_pull": (_I, [_VP, _VP, _SZ, _VP, _SZ, _VP]),
+    "trxhip_synthesize_batch": (_I, [_VP, _VP, _SZ, _VP, _SZ, _I, _I, _I, _VP]),
+    "trxhip_tx_frontend_create": (_I, [_VP, _I, _I, _I, _I, _I, _F, C.POINTER(_VP)]),
+    "trxhip_tx_frontend_destroy": (None, [_VP]),
+    "trxhip_tx_frontend_reset": (_I, [_VP, _VP]),
+    "trxhip_tx_frontend_seed": (_I, [_VP, _VP, _SZ, _SZ, _VP]),
+    "trxhip_tx_frontend_push": (_I, [_VP, _VP, _SZ, _SZ, _VP, _VP, _F, _VP]),
 }
 
 
@@ -496,6 +502,15 @@ class TrxHip:
                                             self._stream(stream)), "trxhip_resample_batch")
         return out
 
+    def synthesize(self, rows, n_blocks, m=4, block_len=192, h_len=16, stream=None):
+        """Synthesis(m, block_len, h_len)::rotate over n_blocks blocks from zero history.  rows: complex64[m, >= n_blocks*block_len]
+        (Synthesis::inputBuffer(c) = rows[c]) -> complex64[n_blocks*block_len*m], interleaved"""
+        torch = self.torch
+        out = torch.empty(n_blocks * block_len * m, dtype=torch.complex64, device=rows.device)
+        _check(self.L.trxhip_synthesize_batch(self.h, self._dev(rows, torch.complex64), rows.shape[1], self._dev(out), n_blocks, m,
+                                              block_len, h_len, self._stream(stream)), "trxhip_synthesize_batch")
+        return out
+
 
 class RxFrontEnd:
     """Streaming Channelizer(4, block_len, 16) + Resampler(p, q, 16) with carried history (trxhip_rx_frontend_*)."""
@@ -530,6 +545,67 @@ class RxFrontEnd:
     def close(self):
         if getattr(self, "h", None):
             self.trx.L.trxhip_rx_frontend_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+TXFE_MULTI, TXFE_RESAMP = 0, 1
+
+
+class TxFrontEnd:
+    """Streaming transmit front end with carried history (trxhip_tx_frontend_*).  mode "multi": RadioInterfaceMulti::pushBuffer
+    (Resampler(p, q, 16, bw) per active filterbank path + Synthesis(4, block_len*p/q, 16)); mode "resamp":
+    RadioInterfaceResamp::pushBuffer (Resampler(p, q, 16, bw) alone, chans = 1)."""
+
+    def __init__(self, trx, chans=3, block_len=260, p=48, q=65, bw=1.0, mode="multi"):
+        self.trx = trx
+        self.mode = {"multi": TXFE_MULTI, "resamp": TXFE_RESAMP}[mode]
+        self.chans, self.block_len, self.p, self.q = chans, block_len, p, q
+        h = _VP()
+        _check(trx.L.trxhip_tx_frontend_create(trx.h, self.mode, chans, block_len, p, q, float(bw), C.byref(h)),
+               "trxhip_tx_frontend_create")
+        self.h = h
+
+    def out_len(self, n_blocks):
+        """output samples of n_blocks blocks"""
+        return n_blocks * self.block_len // self.q * self.p * (4 if self.mode == TXFE_MULTI else 1)
+
+    def _rows(self, x):
+        x = x if x.dim() == 2 else x.view(1, -1)
+        assert x.shape[0] == self.chans, (x.shape, self.chans)
+        return self.trx._dev(x, self.trx.torch.complex64), x.shape[1]
+
+    def reset(self, stream=None):
+        _check(self.trx.L.trxhip_tx_frontend_reset(self.h, self.trx._stream(stream)), "trxhip_tx_frontend_reset")
+
+    def seed(self, x_prev, n_blocks_prev, stream=None):
+        """Start mid-stream: x_prev = complex64[chans, >= n_blocks_prev*block_len], the blocks preceding the shard."""
+        ptr, stride = self._rows(x_prev) if n_blocks_prev else (None, 0)
+        _check(self.trx.L.trxhip_tx_frontend_seed(self.h, ptr, stride, n_blocks_prev, self.trx._stream(stream)),
+               "trxhip_tx_frontend_seed")
+
+    def push(self, x, n_blocks, cf32=True, s16_scale=None, stream=None):
+        """x: complex64[chans, >= n_blocks*block_len] (logical channel l in row l; 1-D for one channel).
+        Returns (complex64[out_len] or None, int16[out_len, 2] or None -- only with s16_scale)."""
+        torch = self.trx.torch
+        ptr, stride = self._rows(x)
+        n = self.out_len(n_blocks)
+        out = torch.empty(n, dtype=torch.complex64, device=x.device) if cf32 else None
+        s16 = torch.empty((n, 2), dtype=torch.int16, device=x.device) if s16_scale is not None else None
+        _check(self.trx.L.trxhip_tx_frontend_push(self.h, ptr, stride, n_blocks,
+                                                  self.trx._dev(out) if out is not None else None,
+                                                  self.trx._dev(s16) if s16 is not None else None,
+                                                  float(s16_scale or 0.0), self.trx._stream(stream)), "trxhip_tx_frontend_push")
+        return out, s16
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.trx.L.trxhip_tx_frontend_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -11,7 +11,8 @@ mixed (configs[4]: 7:1 normal / access), edge (8-PSK, 444 soft bits), 1sps (conf
 bursts as complex64), exact (normal, exact demodulator), va (normal, Viterbi alternative), nb_toa63 / nb_toa112 (normal
 bursts spread over 60 symbols of delay, max_toa 63 / 112: the windowed path), mixed_blocked (mixed, the access bursts moved
 to the end of the batch).  Others: sch_full (detectSCHBurst FULL, 16384 x 625 samples), sch_buffer (BUFFER search,
-256 x 60000 samples), frontend (configs[3]: channelizer, resampler and the fused front end over 256 Ki blocks)."""
+256 x 60000 samples), frontend (configs[3]: channelizer, resampler and the fused front end over 256 Ki blocks), tx_frontend
+(the transmit front end: 3 logical channels through trxhip_tx_frontend_push to int16, 256 Ki blocks of 260 samples)."""
 import argparse
 import json
 import os
@@ -23,8 +24,8 @@ import torch
 from osmo_trx_amd import TrxHip, synth, trxhip
 
 NAMES = ("normal", "rach", "ext", "mixed", "edge", "1sps", "cf32", "exact", "va", "nb_toa63", "nb_toa112", "mixed_blocked",
-         "sch_full", "sch_buffer", "frontend")
-DEFAULT_N = {"sch_full": 16384, "sch_buffer": 256, "frontend": 1 << 18}
+         "sch_full", "sch_buffer", "frontend", "tx_frontend")
+DEFAULT_N = {"sch_full": 16384, "sch_buffer": 256, "frontend": 1 << 18, "tx_frontend": 1 << 18}
 
 
 def make(name, n, device="cuda:0", seed=None):
@@ -61,6 +62,11 @@ def make(name, n, device="cuda:0", seed=None):
         kw = {"state": trxhip.SCH_DETECT_FULL if name == "sch_full" else trxhip.SCH_DETECT_BUFFER}
     elif name == "frontend":
         iq, p, kw = synth.make_wideband_stream(n, device, **s), None, {}
+    elif name == "tx_frontend":
+        g = torch.Generator(device=device)
+        g.manual_seed(5 if seed is None else seed)
+        x = torch.randn((3, n * 260, 2), generator=g, device=device) * 2000.0
+        iq, p, kw = torch.view_as_complex(x.contiguous()), None, {}
     else:
         raise ValueError(f"unknown workload {name!r} (one of {', '.join(NAMES)})")
     return iq, p, kw
@@ -81,6 +87,10 @@ def launcher(trx, name, iq, params, kw, hint=False):
             trx.resample(x, 65, 48)
             return fe.pull(iq, n)
         return run
+    if name == "tx_frontend":
+        n = iq.shape[1] // 260
+        fe = trxhip.TxFrontEnd(trx, chans=3)
+        return lambda: fe.push(iq, n, cf32=False, s16_scale=float(np.float32(1.0 / 3)))
     dp = trx.params_tensor(params)
     if name == "va":
         return lambda: trx.demod_va(iq, dp)
