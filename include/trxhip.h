@@ -557,6 +557,92 @@ int  trxhip_tx_frontend_seed(trxhip_tx_frontend *f, const float *d_in_prev, size
 int  trxhip_tx_frontend_push(trxhip_tx_frontend *f, const float *d_in, size_t in_stride, size_t n_blocks,
 			     float *d_out_cf32, int16_t *d_out_s16, float s16_scale, void *stream);
 
+/* ---- downlink burst scheduler: TRXD datagrams to each channel's transmit sample stream ----
+ * For batch callers ("datagrams in, radio samples out"); osmo-trx linked through the shims keeps its own Transceiver.
+ * Per logical channel (1..8) the object keeps what Transceiver keeps (Transceiver.cpp): the priority queue of bursts by
+ * GSM::Time (FN modulo the hyperframe 2715648 through FNDelta / FNCompare, then TN), the per-TN FN-order state of
+ * driveTxPriorityQueue() (:1137-1171), the filler table [102][8] (:95-135; channel 0 holds the configured filler, every
+ * other channel FILLER_ZERO, :255-256; retransmission into it on channel 0 exactly when the filler is FILLER_DUMMY,
+ * :218-219), the slot combinations with setModulus()'s moduli 26 / 51 / 102 / 52 (:483-512) and the RF mute flag.
+ * A render of n slots runs pushRadioVector()'s loop body (:416-481) for every slot from the clock, then advances the clock
+ * (incTN): stale bursts are dropped (the filler table updated first when retransmission is on), the current burst goes out
+ * (and into the filler table when retransmission is on), otherwise the filler entry fillerTable[FN % modulus[TN]][TN]; a slot
+ * whose combination is NONE or whose channel is muted is zeros and still consumes its burst.
+ * Duplicate times: of two queued bursts with the same (FN, TN) the earlier submission is transmitted and the later one is
+ * dropped as stale in the next slot (the reference's std::priority_queue leaves the order unspecified).
+ * Submit refuses, counting it in `refused` and queueing nothing: a length other than 6 + 148 (GMSK) or 6 + 444 (8-PSK; at
+ * 1 SPS refused too), a header version above 1.  A repeated FN of a TN is dropped (tx_trxd_fn_repeated); an earlier FN is
+ * counted (tx_trxd_fn_outoforder) and queued; a later FN past the next on channel 0 with FILLER_ZERO counts the FNs lost
+ * (tx_trxd_fn_skipped).  Random fillers (FILLER_NORM_RAND & co.) are not offered: they use rand().
+ * Samples: slot s of a render starts at s * 625 (4 SPS) or at its 1-SPS offset (slots of 157 / 156 / 156 / 156 / 157 / 156 /
+ * 156 / 156 samples from TN 0, a frame 1250) counted from the render's first slot.  A burst slot is the row
+ * trxhip_modulate_trxd_batch() gives its datagram; the dummy filler is modulateBurst(dummy, 8 + (tn % 4 == 0), sps) scaled by
+ * (full_scale, 0); other slots are zeros.
+ * Blocking: submit waits (hipEventSynchronize) only when all 2 * chans * queue_cap staging rows are taken, i.e. when renders
+ * still in flight hold more than chans * queue_cap consumed rows; render and render_frontend wait only for the render issued
+ * 4 calls earlier on the object (its slot buffer is reused).  render_frontend also allocates its remainder buffer (hipMalloc,
+ * which may wait for the device) on its first call and again, after hipStreamSynchronize on `stream`, when a front end with
+ * a longer block_len is attached; the buffer is sized for max_slots from any TN, so the clock never makes it grow.  Nothing
+ * calls hipDeviceSynchronize.  Issue every render of one object on one stream.  One object is not thread-safe.
+ * TRXHIP_EIO from a render (a failed copy or launch, after hipStreamSynchronize on `stream`): the queue and the filler
+ * table have moved on while the device's filler entries have not; the object is unusable and must be destroyed.
+ * ctx == NULL: a plan-only object (no device memory, no outputs); the queue logic and trxhip_tx_sched_plan() as on the GPU.
+ * Every refusal of an argument (config, channel, TN, combination, render before set_clock, more slots than max_slots, a
+ * front end whose chans differ, outputs too small) is TRXHIP_EINVAL and leaves the state untouched. */
+#define TRXHIP_FILLER_DUMMY 0     /* FillerType FILLER_DUMMY */
+#define TRXHIP_FILLER_ZERO  1     /* FillerType FILLER_ZERO */
+#define TRXHIP_COMB_FILL     0    /* Transceiver::ChannelCombination FILL, I .. XIII = 1 .. 13, NONE, LOOPBACK */
+#define TRXHIP_COMB_NONE     14
+#define TRXHIP_COMB_LOOPBACK 15
+typedef struct trxhip_tx_sched_cfg {
+	int32_t  chans;          /* logical channels, 1..8 */
+	int32_t  sps;            /* 1 or 4 */
+	int32_t  filler;         /* TRXHIP_FILLER_DUMMY or TRXHIP_FILLER_ZERO (channel 0) */
+	int32_t  queue_cap;      /* queued bursts per channel, 1 .. 2^20 (submit: TRXHIP_ENOMEM when full) */
+	uint64_t max_slots;      /* the largest render, slots per channel, 1 .. 2^26 */
+	double   full_scale;     /* txFullScale */
+} trxhip_tx_sched_cfg;
+#define TRXHIP_TXS_SRC_ZERO   0   /* zeros: slot combination NONE or RF muted */
+#define TRXHIP_TXS_SRC_BURST  1   /* a submitted burst, id = its submission id */
+#define TRXHIP_TXS_SRC_FILLER 2   /* the filler entry, id = the submission id of the burst that wrote it, -1: initial filler */
+typedef struct trxhip_tx_plan {
+	int64_t  id;
+	uint32_t fn;
+	uint8_t  tn;
+	uint8_t  src;            /* TRXHIP_TXS_SRC_* */
+	uint8_t  reserved[2];
+} trxhip_tx_plan;
+typedef struct trxhip_tx_sched_ctrs {
+	uint64_t tx_stale_bursts, tx_unavailable_bursts, tx_trxd_fn_repeated, tx_trxd_fn_outoforder, tx_trxd_fn_skipped;
+	uint64_t refused;        /* datagrams refused at submit (length, version, 8-PSK at 1 SPS) */
+} trxhip_tx_sched_ctrs;
+typedef struct trxhip_tx_sched trxhip_tx_sched;
+int  trxhip_tx_sched_create(trxhip_ctx *ctx, const trxhip_tx_sched_cfg *cfg, trxhip_tx_sched **out);
+void trxhip_tx_sched_destroy(trxhip_tx_sched *s);
+/* the transmit clock: the (FN, TN) of the next rendered slot; fn < 2715648.  Also drops render_frontend's remainder */
+int  trxhip_tx_sched_set_clock(trxhip_tx_sched *s, uint32_t fn, int tn);
+int  trxhip_tx_sched_clock(const trxhip_tx_sched *s, uint32_t *fn, int *tn);
+int  trxhip_tx_sched_set_slot(trxhip_tx_sched *s, int chan, int tn, int comb);   /* SETSLOT: comb = TRXHIP_COMB_* / 1..13 */
+int  trxhip_tx_sched_set_muted(trxhip_tx_sched *s, int chan, int muted);         /* RFMUTE */
+/* h_dgram: one TRXD downlink datagram of len bytes (the layout of trxhip_modulate_trxd_batch()), copied at once.
+ * *id = its submission id (0, 1, .. over the object's queued bursts) or -1 when refused or dropped */
+int  trxhip_tx_sched_submit(trxhip_tx_sched *s, int chan, const uint8_t *h_dgram, size_t len, int64_t *id);
+/* n_slots slots of every channel: channel c's stream at d_out_cf32 + 2*c*out_stride floats and / or d_out_s16 + 2*c*out_stride
+ * int16, (int16_t)(int)(x * s16_scales[c]) (RadioInterface::pushBuffer's convert_float_short per channel).  out_stride >= the
+ * samples of the render.  Plan-only objects take no outputs.  Asynchronous on `stream` */
+int  trxhip_tx_sched_render(trxhip_tx_sched *s, size_t n_slots, float *d_out_cf32, size_t out_stride, int16_t *d_out_s16,
+			    const float *s16_scales, void *stream);
+/* The same through a transmit front end of chans == the scheduler's (RadioInterface::driveTransmitRadio: append, then
+ * while (pushBuffer());): the rendered samples are appended to a remainder the object carries, every whole block_len block
+ * goes through trxhip_tx_frontend_push(fe, ..., d_out_cf32, d_out_s16, s16_scale), the rest stays.  *n_blocks = blocks
+ * written (out_cap: output samples the outputs hold, >= n_blocks * the front end's samples per block), *n_carried (may be
+ * NULL) = samples carried per channel.  A plain render or set_clock drops the remainder. */
+int  trxhip_tx_sched_render_frontend(trxhip_tx_sched *s, size_t n_slots, trxhip_tx_frontend *fe, float *d_out_cf32,
+				     int16_t *d_out_s16, float s16_scale, size_t out_cap, size_t *n_blocks, size_t *n_carried,
+				     void *stream);
+int  trxhip_tx_sched_plan(const trxhip_tx_sched *s, int chan, trxhip_tx_plan *h_out, size_t n);   /* the last render's first n slots */
+int  trxhip_tx_sched_counters(const trxhip_tx_sched *s, int chan, trxhip_tx_sched_ctrs *out);
+
 #ifdef __cplusplus
 }
 #endif

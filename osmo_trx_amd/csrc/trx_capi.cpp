@@ -775,6 +775,16 @@ static size_t txfe_out_per_block(const trxhip_tx_frontend *f)
 	return (size_t)f->block_len / f->q * f->p * (f->mode == TRXHIP_TXFE_MULTI ? 4 : 1);
 }
 
+int trx_tx_frontend_geometry(const trxhip_tx_frontend *f, int *chans, int *block_len, size_t *out_per_block)
+{
+	if (!f)
+		return TRXHIP_EINVAL;
+	*chans = f->chans;
+	*block_len = f->block_len;
+	*out_per_block = txfe_out_per_block(f);
+	return TRXHIP_OK;
+}
+
 int trxhip_tx_frontend_create(trxhip_ctx *ctx, int mode, int chans, int block_len, int p, int q, float bw, trxhip_tx_frontend **out)
 {
 	if (!ctx || !out || (mode != TRXHIP_TXFE_MULTI && mode != TRXHIP_TXFE_RESAMP))

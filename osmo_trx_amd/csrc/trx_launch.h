@@ -93,6 +93,18 @@ int trx_launch_tx_modulate(const uint8_t *d_in, size_t in_stride, const trxhip_t
 			   float s16_scale, size_t out_stride, int32_t *d_out_len, trxhip_tx_info *d_info, size_t n, int sps,
 			   hipStream_t stream);
 int trx_tx_tables_generate(trx_tx_tables *t);                         /* host only */
+/* the downlink burst scheduler's render (trx_tx.hip, tx_render_kernel; trx_tx_sched.h): n_slots slots of chans channels from
+ * the slot words d_slots[chan * n_slots + s] (a staged row holds its datagram's length, uint16, in its last two bytes), then
+ * the filler-table updates of the render */
+struct trx_tx_fill;
+struct trx_tx_fill_update;
+int trx_launch_tx_render(const uint32_t *d_slots, size_t n_slots, int chans, int tn0, int sps, const uint8_t *d_rows,
+			 const trx_tx_fill *d_fill, const float *h_att_scale, const trx_tx_tables *d_tab,
+			 float *d_out_cf32, int16_t *d_out_s16, const float *h_s16_scales, size_t out_stride, hipStream_t stream);
+int trx_launch_tx_fill_update(const trx_tx_fill_update *d_upd, size_t n, const uint8_t *d_rows, trx_tx_fill *d_fill,
+			      hipStream_t stream);
+/* trx_capi.cpp: a transmit front end's logical channels, block length and output samples per block */
+int trx_tx_frontend_geometry(const trxhip_tx_frontend *f, int *chans, int *block_len, size_t *out_per_block);
 
 }  // extern "C"
 #endif

@@ -20,6 +20,7 @@
 
 #include "../../include/trxhip.h"
 #include "trx_tx_tables.h"
+#include "trx_tx_sched.h"
 #include "trx_launch.h"
 
 typedef float2 c32;
@@ -374,6 +375,290 @@ extern "C" int trx_launch_tx_modulate(const uint8_t *d_in, size_t in_stride, con
 	else
 		hipLaunchKernelGGL(tx_modulate_kernel<false>, dim3((unsigned)blocks), dim3(64 * TX_WAVES), 0, stream, d_in, in_stride,
 				   d_params, nullptr, att, d_tab, d_out_cf32, d_out_s16, s16_scale, out_stride, d_out_len, nullptr, n, sps);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+// The symbol-rate values of one burst in LDS (wave-wide, lb = its staged bits): what the reference places at every sps-th
+// sample of its upsampled vectors.  tx_render_kernel's form of
+// tx_modulate_kernel's staging (that kernel keeps its own inline copy, so that its code object stays what it was).
+__device__ static inline void tx_stage_syms(const trx_tx_desc &d, const uint8_t *lb, c32 *s0, c32 *s1, int lane,
+					     const trx_tx_tables *__restrict__ tab)
+{
+	const int nbits = d.nbits, len = d.len;
+	const c32 *rot4 = reinterpret_cast<const c32 *>(tab->rot4);
+	const c32 *rot1 = reinterpret_cast<const c32 *>(tab->rot1);
+	const c32 *psk8 = reinterpret_cast<const c32 *>(tab->psk8);
+	const c32 *erot = reinterpret_cast<const c32 *>(tab->edge_rot);
+	const c32 zero = make_float2(0.0f, 0.0f);
+	for (int m = lane; m < TX_SYMS; m += 64) {
+		c32 v0 = zero, v1 = zero;
+		if (d.mode == TX_LAURENT) {
+			// modulateBurstLaurent :615-656.  c0: padded tail (-1), the bits, padded tail (-1) at 4m, m = 0 .. nbits+1, then
+			// GMSKRotate's real branch (*rotPtr * x.real(), :247-251).  c1 = c0 * (0, phase) at m = 2 .. nbits+1, phase -1 at
+			// m = 2 (start magic) and 2 (b[m-2] ^ b[m-3]) - 1 after it (the loop and the end magic)
+			if (m <= nbits + 1) {
+				const float x = (m == 0 || m == nbits + 1) ? -1.0f : (lb[m - 1] ? 1.0f : -1.0f);   /* 2.0 * bit - 1.0 */
+				const c32 r = rot4[4 * m];
+				v0 = make_float2(r.x * x, r.y * x);
+				if (m >= 2) {
+					const float ph = (m == 2) ? -1.0f : ((lb[m - 2] ^ lb[m - 3]) ? 1.0f : -1.0f);
+					v1 = cmul(v0, make_float2(0.0f, ph));
+				}
+			}
+		} else if (d.mode == TX_BASIC1) {
+			// modulateBurstBasic :938-967 at 1 SPS: +-1 at m < nbits, 0 behind, GMSKRotate's real branch over all len samples
+			if (m < len) {
+				const float x = m < nbits ? (lb[m] ? 1.0f : -1.0f) : 0.0f;
+				const c32 r = rot1[m];
+				v0 = make_float2(r.x * x, r.y * x);
+			}
+		} else if (d.mode == TX_EDGE4 || d.mode == TX_EDGE_ROTATE) {
+			// mapEdgeSymbols :713-729 then symbol * rot (shapeEdgeBurst :750-756 one symbol late; rotateEdgeBurst :680-686)
+			const int k = d.mode == TX_EDGE4 ? m - 1 : m;
+			if (k >= 0 && k < nbits / 3) {
+				const unsigned idx = (unsigned)lb[3 * k] | ((unsigned)lb[3 * k + 1] << 1) | ((unsigned)lb[3 * k + 2] << 2);
+				v0 = cmul(psk8[idx], erot[k]);
+			}
+		}
+		s0[m] = v0;
+		s1[m] = v1;
+	}
+}
+
+// Sample i of the burst described by d (0 at i >= d.len), from its symbol-rate values, then scaled as scaleVector() does
+// (tx_modulate_kernel's sample lambda).
+__device__ static inline c32 tx_sample(const trx_tx_desc &d, const c32 *s0, const c32 *s1, const uint8_t *lb, const tx_lds &L,
+				       const c32 *rot, int sps, int i)
+{
+	c32 y = make_float2(0.0f, 0.0f);
+	if (i >= d.len)
+		return y;
+	switch (d.mode) {
+	case TX_LAURENT: {
+		// c0_shaped + c1_shaped (:659-666): each convolution summed on its own, then added
+		const c32 a = sum_sparse4<16>(s0, L.p0, i), c = sum_sparse4<8>(s1, L.p1, i);
+		y = make_float2(a.x + c.x, a.y + c.y);
+		break;
+	}
+	case TX_EDGE4:
+		y = sum_sparse4<16>(s0, L.p0, i);
+		break;
+	case TX_BASIC1: {
+		// every sample is a symbol position at 1 SPS: the plain 4-tap START_ONLY sum, x[j] = 0 outside [0, len)
+		float yr = 0.0f, yi = 0.0f;
+		for (int k = 0; k < 4; k++) {
+			const int j = i - 3 + k;
+			if (j >= 0) {
+				yr += s0[j].x * L.q1[k];
+				yi += s0[j].y * L.q1[k];
+			}
+		}
+		y = make_float2(yr, yi);
+		break;
+	}
+	case TX_ROTATE: {
+		// rotateBurst :558-580: (+-1, 0) at every sps-th sample, GMSKRotate's complex branch, then the 1-tap empty pulse
+		// (real taps: 0.0f + x.re * 1.0f)
+		const int m = i / sps;
+		const float x = (i == m * sps && m < d.nbits) ? (lb[m] ? 1.0f : -1.0f) : 0.0f;
+		const c32 v = cmul(rot[i], make_float2(x, 0.0f));
+		y = make_float2(0.0f + v.x * 1.0f, 0.0f + v.y * 1.0f);
+		break;
+	}
+	default: {                             /* TX_EDGE_ROTATE: no filter, zeros between the symbols */
+		const int m = i / sps;
+		if (i == m * sps)
+			y = s0[m];
+		break;
+	}
+	}
+	if (d.scaled)                          /* scaleVector's complex branch, :1199-1203 */
+		y = make_float2(y.x * d.scale.x - y.y * d.scale.y, y.x * d.scale.y + y.y * d.scale.x);
+	return y;
+}
+
+// tx_modulate_kernel's store loop: samples [0, stride) of the row that starts `off` values (2 per sample) into out_cf32 and / or out_s16, every
+// lane two samples per round, 16-byte non-temporal stores for cf32 (8 bytes for int16) after a lone head sample when the row
+// is only 8- (4-) byte aligned.  Either output may be NULL.
+template <class F>
+__device__ static inline void tx_store_row(const F &sample, float *out_cf32, int16_t *out_s16, size_t off, float s16_scale, int stride,
+					    int lane)
+{
+	if (out_cf32) {
+		float *row = out_cf32 + off;
+		const int head = (reinterpret_cast<uintptr_t>(row) & 15) ? 1 : 0;     /* sample 0 alone when the row is 8-byte aligned */
+		if (head && lane == 0) {
+			const c32 y = sample(0);
+			__builtin_nontemporal_store((f2v){y.x, y.y}, reinterpret_cast<f2v *>(row));
+		}
+		for (int i0 = head + 2 * lane; i0 < stride; i0 += 128) {
+			const c32 y0 = sample(i0);
+			if (i0 + 1 < stride) {
+				const c32 y1 = sample(i0 + 1);
+				__builtin_nontemporal_store((f4v){y0.x, y0.y, y1.x, y1.y}, reinterpret_cast<f4v *>(row + 2 * i0));
+			} else {
+				__builtin_nontemporal_store((f2v){y0.x, y0.y}, reinterpret_cast<f2v *>(row + 2 * i0));
+			}
+		}
+	}
+	if (out_s16) {
+		// convert_float_short_kernel's expression (trx_aux_kernels.hip): (int16_t)(int)(x * scale)
+		int16_t *row = out_s16 + off;
+		auto q = [&](float v) -> unsigned { return (unsigned)(uint16_t)(int16_t)(int)(v * s16_scale); };
+		const int head = (reinterpret_cast<uintptr_t>(row) & 7) ? 1 : 0;
+		if (head && lane == 0) {
+			const c32 y = sample(0);
+			__builtin_nontemporal_store(q(y.x) | (q(y.y) << 16), reinterpret_cast<unsigned *>(row));
+		}
+		for (int i0 = head + 2 * lane; i0 < stride; i0 += 128) {
+			const c32 y0 = sample(i0);
+			if (i0 + 1 < stride) {
+				const c32 y1 = sample(i0 + 1);
+				__builtin_nontemporal_store((u2v){q(y0.x) | (q(y0.y) << 16), q(y1.x) | (q(y1.y) << 16)},
+							    reinterpret_cast<u2v *>(row + 2 * i0));
+			} else {
+				__builtin_nontemporal_store(q(y0.x) | (q(y0.y) << 16), reinterpret_cast<unsigned *>(row + 2 * i0));
+			}
+		}
+	}
+}
+
+// 1-SPS slot offsets in a frame: 157 / 156 / 156 / 156 / 157 / 156 / 156 / 156 samples (148 + 8 + (tn % 4 == 0))
+__device__ static inline size_t tx_slot1_start(int tn) { return (size_t)tn * 156 + (size_t)((tn + 3) >> 2); }
+
+// The downlink burst scheduler's render (trx_tx_sched.cpp plans, this kernel draws): one wave per (channel, slot), four per
+// workgroup, wave b = chan * n_slots + s.  The wave reads its slot word, describes the source (a staged TRXD datagram row, a
+// filler-table descriptor, or zeros), stages and modulates it as tx_modulate_kernel does and writes the samples straight
+// into the slot's place of the channel's stream: slot s of the render starts at s * 625 (4 SPS) or at its 1-SPS offset
+// counted from the render's first TN tn0.  Each output sample is written once; there are no burst rows in between.
+__global__ void __launch_bounds__(64 * TX_WAVES)
+tx_render_kernel(const uint32_t *__restrict__ slots, size_t n_slots, int chans, int tn0, int sps, const uint8_t *__restrict__ rows,
+		 const trx_tx_fill *__restrict__ fill, tx_att_table att,
+		 const trx_tx_tables *__restrict__ tab, float *__restrict__ out_cf32, int16_t *__restrict__ out_s16,
+		 trx_tx_s16_scales s16, size_t out_stride)
+{
+	__shared__ tx_lds L;
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const size_t b = (size_t)blockIdx.x * TX_WAVES + w;
+	const bool active = b < n_slots * (size_t)chans;
+
+	if (threadIdx.x < 16)
+		L.p0[threadIdx.x] = tab->pulse4_c0[threadIdx.x];
+	else if (threadIdx.x < 24)
+		L.p1[threadIdx.x - 16] = tab->pulse4_c1[threadIdx.x - 16];
+	else if (threadIdx.x < 28)
+		L.q1[threadIdx.x - 24] = tab->pulse1_c0[threadIdx.x - 24];
+
+	// ---- the slot and its source (wave-uniform) ----
+	trx_tx_desc d;
+	d.status = TRXHIP_EINVAL;
+	d.len = 0;
+	d.nbits = 0;
+	d.mode = TX_LAURENT;
+	d.scaled = false;
+	const uint8_t *bits = nullptr;
+	int chan = 0, len = 0;
+	size_t off = 0;
+	if (active) {
+		chan = (int)(b / n_slots);
+		const size_t s = b - (size_t)chan * n_slots, t = (size_t)tn0 + s;
+		const int tn = (int)(t & 7);
+		if (sps == 4) {
+			off = s * 625;
+			len = 625;
+		} else {
+			off = (t >> 3) * 1250 + tx_slot1_start(tn) - tx_slot1_start(tn0);
+			len = 156 + (tn % 4 == 0);
+		}
+		const uint32_t word = slots[b], idx = word & 0x3fffffffu;
+		if ((word >> 30) == TRX_TXS_ROW) {
+			trxhip_tx_info info;
+			const uint8_t *row = rows + (size_t)idx * TRX_TXS_ROW_STRIDE;
+			const int dlen = row[TRX_TXS_ROW_STRIDE - 2] | (row[TRX_TXS_ROW_STRIDE - 1] << 8);      /* the datagram's length */
+			bits = trxd_describe(row, dlen, TRX_TXS_ROW_STRIDE - 2, sps, att, (size_t)len, d, info);
+		} else if ((word >> 30) == TRX_TXS_ENTRY) {
+			const trx_tx_fill *f = fill + idx;
+			d = tx_describe(f->nbits, f->guard, f->flags, sps, TRX_TXS_FILL_BITS, (size_t)len);
+			d.scale = make_float2(f->scale_re, f->scale_im);
+			d.scaled = true;                   /* scaleVector() ran on every filler burst (Transceiver.cpp:123, :396) */
+			bits = f->bits;
+		}
+	}
+	const bool ok = active && d.status == 0;
+
+	// ---- stage the bits: only bit 0 counts (bits[i] & 0x01) ----
+	uint8_t *lb = L.bits[w];
+	if (ok)
+		for (int i = lane; i < d.nbits; i += 64)
+			lb[i] = bits[i] & 0x01;
+	__syncthreads();
+
+	c32 *s0 = L.sym0[w], *s1 = L.sym1[w];
+	if (ok)
+		tx_stage_syms(d, lb, s0, s1, lane, tab);
+	__syncthreads();
+	if (!active)
+		return;
+
+	// ---- the slot's samples: the burst, or zeros (d.len == 0: a zero slot, radioifyVector()'s zero(), radioInterface.cpp:132-141) ----
+	const c32 *rot = reinterpret_cast<const c32 *>(sps == 4 ? tab->rot4 : tab->rot1);
+	auto sample = [&](int i) -> c32 { return tx_sample(d, s0, s1, lb, L, rot, sps, i); };
+	tx_store_row(sample, out_cf32, out_s16, 2 * ((size_t)chan * out_stride + off), s16.s[chan], len, lane);
+}
+
+// End of a render: the filler-table entries the render's bursts wrote (updateFillerTable(), Transceiver.cpp:403-414) take
+// the bits of the staged row and the planner's parameters.  One wave per entry; at most one update per entry and render.
+__global__ void __launch_bounds__(64)
+tx_fill_update_kernel(const trx_tx_fill_update *__restrict__ upd, size_t n, const uint8_t *__restrict__ rows, trx_tx_fill *__restrict__ fill)
+{
+	const size_t k = blockIdx.x;
+	if (k >= n)
+		return;
+	const trx_tx_fill_update u = upd[k];
+	trx_tx_fill *f = fill + u.entry;
+	const uint8_t *src = rows + (size_t)u.row * TRX_TXS_ROW_STRIDE + 6;
+	for (int i = threadIdx.x; i < (int)TRX_TXS_FILL_BITS; i += 64)
+		f->bits[i] = i < (int)u.nbits ? src[i] : 0;
+	if (threadIdx.x == 0) {
+		f->nbits = u.nbits;
+		f->guard = u.guard;
+		f->flags = u.flags;
+		f->scale_re = u.scale_re;
+		f->scale_im = 0.0f;
+		f->reserved = 0;
+	}
+}
+
+extern "C" int trx_launch_tx_render(const uint32_t *d_slots, size_t n_slots, int chans, int tn0, int sps, const uint8_t *d_rows,
+				    const trx_tx_fill *d_fill, const float *h_att_scale, const trx_tx_tables *d_tab,
+				    float *d_out_cf32, int16_t *d_out_s16, const float *h_s16_scales, size_t out_stride, hipStream_t stream)
+{
+	if (n_slots == 0)
+		return 0;
+	if (chans < 1 || chans > TRX_TXS_MAX_CHANS || tn0 < 0 || tn0 > 7)
+		return TRXHIP_EINVAL;
+	const size_t blocks = (n_slots * (size_t)chans + TX_WAVES - 1) / TX_WAVES;
+	if (blocks > 0x7fffffffu)
+		return TRXHIP_EINVAL;
+	tx_att_table att;
+	memcpy(att.s, h_att_scale, sizeof(att.s));
+	trx_tx_s16_scales s16;
+	memset(&s16, 0, sizeof(s16));
+	if (h_s16_scales)
+		memcpy(s16.s, h_s16_scales, (size_t)chans * sizeof(float));
+	hipLaunchKernelGGL(tx_render_kernel, dim3((unsigned)blocks), dim3(64 * TX_WAVES), 0, stream, d_slots, n_slots, chans, tn0, sps,
+			   d_rows, d_fill, att, d_tab, d_out_cf32, d_out_s16, s16, out_stride);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+extern "C" int trx_launch_tx_fill_update(const trx_tx_fill_update *d_upd, size_t n, const uint8_t *d_rows, trx_tx_fill *d_fill,
+					 hipStream_t stream)
+{
+	if (n == 0)
+		return 0;
+	if (n > 0x7fffffffu)
+		return TRXHIP_EINVAL;
+	hipLaunchKernelGGL(tx_fill_update_kernel, dim3((unsigned)n), dim3(64), 0, stream, d_upd, n, d_rows, d_fill);
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
 

@@ -121,6 +121,17 @@ SYMBOLS = {
     "trxhip_tx_frontend_reset": (_I, [_VP, _VP]),
     "trxhip_tx_frontend_seed": (_I, [_VP, _VP, _SZ, _SZ, _VP]),
     "trxhip_tx_frontend_push": (_I, [_VP, _VP, _SZ, _SZ, _VP, _VP, _F, _VP]),
+    "trxhip_tx_sched_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
+    "trxhip_tx_sched_destroy": (None, [_VP]),
+    "trxhip_tx_sched_set_clock": (_I, [_VP, C.c_uint32, _I]),
+    "trxhip_tx_sched_clock": (_I, [_VP, C.POINTER(C.c_uint32), C.POINTER(_I)]),
+    "trxhip_tx_sched_set_slot": (_I, [_VP, _I, _I, _I]),
+    "trxhip_tx_sched_set_muted": (_I, [_VP, _I, _I]),
+    "trxhip_tx_sched_submit": (_I, [_VP, _I, _VP, _SZ, C.POINTER(C.c_int64)]),
+    "trxhip_tx_sched_render": (_I, [_VP, _SZ, _VP, _SZ, _VP, _VP, _VP]),
+    "trxhip_tx_sched_render_frontend": (_I, [_VP, _SZ, _VP, _VP, _VP, _F, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
+    "trxhip_tx_sched_plan": (_I, [_VP, _I, _VP, _SZ]),
+    "trxhip_tx_sched_counters": (_I, [_VP, _I, _VP]),
 }
 
 
@@ -606,6 +617,137 @@ class TxFrontEnd:
     def close(self):
         if getattr(self, "h", None):
             self.trx.L.trxhip_tx_frontend_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FILLER_DUMMY, FILLER_ZERO = 0, 1                    # TRXHIP_FILLER_* (FillerType)
+COMB_FILL, COMB_NONE, COMB_LOOPBACK = 0, 14, 15     # TRXHIP_COMB_* (Transceiver::ChannelCombination; I .. XIII = 1 .. 13)
+TXS_SRC_ZERO, TXS_SRC_BURST, TXS_SRC_FILLER = 0, 1, 2
+TX_PLAN_DTYPE = np.dtype([("id", "<i8"), ("fn", "<u4"), ("tn", "u1"), ("src", "u1"), ("reserved", "u1", 2)])
+TX_SCHED_COUNTERS = ("tx_stale_bursts", "tx_unavailable_bursts", "tx_trxd_fn_repeated", "tx_trxd_fn_outoforder",
+                     "tx_trxd_fn_skipped", "refused")
+
+
+class _TxSchedCfg(C.Structure):
+    _fields_ = [("chans", C.c_int32), ("sps", C.c_int32), ("filler", C.c_int32), ("queue_cap", C.c_int32),
+                ("max_slots", C.c_uint64), ("full_scale", C.c_double)]
+
+
+class TxScheduler:
+    """Downlink burst scheduler (trxhip_tx_sched_*): TRXD datagrams in, each channel's transmit stream out.
+    trx=None: a plan-only object (no GPU): render() only plans, plan() reads the plan back."""
+
+    def __init__(self, trx=None, chans=1, sps=4, filler=FILLER_DUMMY, full_scale=1.0, queue_cap=256, max_slots=8 * 1024):
+        self.trx = trx
+        self.L = trx.L if trx is not None else load_library()
+        self.chans, self.sps = chans, sps
+        cfg = _TxSchedCfg(chans, sps, filler, queue_cap, max_slots, float(full_scale))
+        h = _VP()
+        _check(self.L.trxhip_tx_sched_create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_tx_sched_create")
+        self.h = h
+        self._last = 0
+
+    def _stream(self, stream):
+        return self.trx._stream(stream) if self.trx is not None else None
+
+    def set_clock(self, fn, tn):
+        _check(self.L.trxhip_tx_sched_set_clock(self.h, fn, tn), "trxhip_tx_sched_set_clock")
+
+    def clock(self):
+        fn, tn = C.c_uint32(), _I()
+        _check(self.L.trxhip_tx_sched_clock(self.h, C.byref(fn), C.byref(tn)), "trxhip_tx_sched_clock")
+        return fn.value, tn.value
+
+    def set_slot(self, chan, tn, comb):
+        _check(self.L.trxhip_tx_sched_set_slot(self.h, chan, tn, comb), "trxhip_tx_sched_set_slot")
+
+    def set_muted(self, chan, muted):
+        _check(self.L.trxhip_tx_sched_set_muted(self.h, chan, int(bool(muted))), "trxhip_tx_sched_set_muted")
+
+    def submit(self, chan, dgram):
+        """dgram: bytes / uint8 array of one TRXD datagram.  Returns its submission id, or -1 when refused or dropped."""
+        b = bytes(bytearray(dgram))
+        buf = (C.c_ubyte * max(len(b), 1)).from_buffer_copy(b if b else b"\0")
+        i = C.c_int64()
+        _check(self.L.trxhip_tx_sched_submit(self.h, chan, buf, len(b), C.byref(i)), "trxhip_tx_sched_submit")
+        return i.value
+
+    def samples(self, n_slots, tn0=None):
+        """samples of n_slots slots rendered from TN tn0 (default: the clock's)"""
+        if self.sps == 4:
+            return 625 * n_slots
+        tn0 = self.clock()[1] if tn0 is None else tn0
+        pre = lambda t: t * 156 + (t + 3) // 4      # noqa: E731
+        t = tn0 + n_slots
+        return (t // 8) * 1250 + pre(t % 8) - pre(tn0)
+
+    def render(self, n_slots, cf32=True, s16_scales=None, stream=None, out=None):
+        """Plan-only: plans n_slots slots, returns None.  Otherwise (complex64[chans, n] or None, int16[chans, n, 2] or None),
+        n = the render's samples; out = a preallocated complex64[chans, >= n] row buffer (cf32 only)."""
+        if self.trx is None:
+            _check(self.L.trxhip_tx_sched_render(self.h, n_slots, None, 0, None, None, None), "trxhip_tx_sched_render")
+            self._last = n_slots
+            return None
+        if not cf32 and out is None and s16_scales is None:
+            raise TrxHipError("TxScheduler.render: no output (cf32=False and no s16_scales)")
+        torch = self.trx.torch
+        n = self.samples(n_slots)
+        dev = f"cuda:{self.trx.device}"
+        if out is None and cf32:
+            out = torch.empty((self.chans, max(n, 1)), dtype=torch.complex64, device=dev)
+        s16 = sc = None
+        if s16_scales is not None:
+            s16 = torch.empty((self.chans, max(n, 1), 2), dtype=torch.int16, device=dev)
+            sc = (C.c_float * self.chans)(*[float(x) for x in s16_scales])
+        stride = out.shape[1] if out is not None else s16.shape[1]
+        _check(self.L.trxhip_tx_sched_render(self.h, n_slots, self.trx._dev(out) if out is not None else None, stride,
+                                             self.trx._dev(s16) if s16 is not None else None, sc, self._stream(stream)),
+               "trxhip_tx_sched_render")
+        self._last = n_slots
+        return (out[:, :n] if out is not None else None), (s16[:, :n] if s16 is not None else None)
+
+    def render_frontend(self, n_slots, fe, cf32=True, s16_scale=None, stream=None):
+        """Render through a TxFrontEnd: returns (n_blocks, n_carried, complex64[fe.out_len(n_blocks)] or None,
+        int16[.., 2] or None)."""
+        torch = self.trx.torch
+        cap = fe.out_len((self.block_bound(n_slots, fe)))
+        dev = f"cuda:{self.trx.device}"
+        out = torch.empty(max(cap, 1), dtype=torch.complex64, device=dev) if cf32 else None
+        s16 = torch.empty((max(cap, 1), 2), dtype=torch.int16, device=dev) if s16_scale is not None else None
+        nb, nc = _SZ(), _SZ()
+        _check(self.L.trxhip_tx_sched_render_frontend(self.h, n_slots, fe.h, self.trx._dev(out) if out is not None else None,
+                                                      self.trx._dev(s16) if s16 is not None else None, float(s16_scale or 0.0),
+                                                      cap, C.byref(nb), C.byref(nc), self._stream(stream)),
+               "trxhip_tx_sched_render_frontend")
+        self._last = n_slots
+        n = fe.out_len(nb.value)
+        return nb.value, nc.value, (out[:n] if out is not None else None), (s16[:n] if s16 is not None else None)
+
+    def block_bound(self, n_slots, fe):
+        """blocks a render_frontend of n_slots can write at most (the carried remainder is < block_len)"""
+        return (fe.block_len - 1 + self.samples(n_slots)) // fe.block_len
+
+    def plan(self, chan, n=None):
+        """TX_PLAN_DTYPE[n] of the last render (default: all its slots)"""
+        n = self._last if n is None else n
+        a = np.zeros(n, dtype=TX_PLAN_DTYPE)
+        _check(self.L.trxhip_tx_sched_plan(self.h, chan, a.ctypes.data_as(_VP), n), "trxhip_tx_sched_plan")
+        return a
+
+    def counters(self, chan):
+        a = np.zeros(6, dtype=np.uint64)
+        _check(self.L.trxhip_tx_sched_counters(self.h, chan, a.ctypes.data_as(_VP)), "trxhip_tx_sched_counters")
+        return dict(zip(TX_SCHED_COUNTERS, (int(x) for x in a)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.trxhip_tx_sched_destroy(self.h)
             self.h = None
 
     def __del__(self):

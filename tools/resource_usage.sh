@@ -17,5 +17,5 @@ hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-mat
 	awk -v pat="$PAT" '/Function Name/{on = ($0 ~ pat)} on{print}'
 echo
 echo "# code size (llvm-readelf -s, bytes):"
-/opt/rocm/lib/llvm/bin/llvm-readelf -s $T/k.o | awk -v pat="$PAT" '$4 == "FUNC" && $8 ~ pat {print $3, $8}'
+/opt/rocm/lib/llvm/bin/llvm-readelf -s $T/k.o | awk -v pat="$PAT" '$4 == "FUNC" && $8 ~ pat && !seen[$8]++ {print $3, $8}'
 rm -rf $T
