@@ -62,6 +62,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	static_assert(NB_TABLES_BYTES % 16 == 0 && (NB_SLICE * 8) % 16 == 0 && (K4_XS * 8) % 16 == 0 && (NB_D_LEN * 8) % 16 == 0, "16-byte LDS accesses");
 	static_assert(NB_LDS_BYTES <= 160 * 1024, "LDS");
 	static_assert(NB_ASM_GDEC_OFF == (TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36) * 4, "tools/gen_nb_asm.py: LDS offset of the decimator taps");
+	static_assert(NB_ASM_DEC_MAX_NACT == 15 + NB_ASM_CORR_MAX_LEN, "tools/gen_nb_asm.py: DEC and CORR change form at the same window");
 	static_assert(NB_ASM_LSEQ_OFF == (NB_TABLES_FLOATS - 2 * 8 * 16) * 4, "tools/gen_nb_asm.py: LDS offset of the training-sequence taps");
 	constexpr int NLD = 10;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -452,19 +453,25 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			__builtin_assume(len >= 16 && len <= 16 + NB_MAX_TOA);
 			// (hand-placed blocks: tools/gen_nb_asm.py)  decimator of the window + the addition-only correlation's guard
 			const unsigned vd_addr = lds_addr(D) + 8u * (unsigned)lane, vcz_addr = lds_addr(cz) + 8u * (unsigned)lane;
+			// (windows of up to NB_ASM_CORR_MAX_LEN lags: the accumulators of DEC and CORR move across the lanes -- decimated sample i
+			// ends in lane i + 4, lag k in lane k + NB_ASM_CORR_LANE0; wider windows: lane = sample / lag, the samples through LDS)
 			unsigned long long bad;
+			float dr, di;
 			asm volatile(NB_ASM_DEC
-				     : [bad] "=s"(bad)
-				     : [pd] "v"(lds_addr(P + PH_M0 + 52) + 8u * (unsigned)lane), [vd] "v"(vd_addr), [zero] "v"(0), [nact] "s"(15 + len)
+				     : [bad] "=s"(bad), [dr] "=&v"(dr), [di] "=&v"(di)
+				     : [pd] "v"(lds_addr(P + PH_M0 + 52) + 8u * (unsigned)lane), [vd] "v"(vd_addr), [vd4] "v"(vd_addr - 32u), [zero] "v"(0),
+				       [nact] "s"(15 + len)
 				     : NB_ASM_CLOBBERS);
 			DIAG_MARK(2);
 			{
-				// ---- correlation (lane = lag; the twelve lanes behind the window store the right zero pad), arg-max and the
-				// energyDetect sum (:1573-1585); the lane constants of the TOA search are fetched in the reductions' wait states
+				// ---- correlation (lag k in lane k + lag0; the right zero pad of cz[] is stored too), arg-max and the energyDetect
+				// sum (:1573-1585); the lane constants of the TOA search are fetched in the reductions' wait states
 				float v;
+				const int lag0 = (len <= NB_ASM_CORR_MAX_LEN) ? NB_ASM_CORR_LANE0 : 0;   // lane of lag 0
 				asm volatile(NB_ASM_CORR
 					     : [nrm] "=&v"(v)
-					     : [vd] "v"(vd_addr), [vcz] "v"(vcz_addr), [len] "s"(len), [tsc] "s"(tsc), [bad] "s"(bad)
+					     : [vd] "v"(vd_addr), [vcz] "v"(vcz_addr), [vdm] "v"(vd_addr - 8u * NB_ASM_CORR_LANE0),
+					       [vczm] "v"(vcz_addr - 8u * NB_ASM_CORR_LANE0), [dr] "v"(dr), [di] "v"(di), [len] "s"(len), [tsc] "s"(tsc), [bad] "s"(bad)
 					     : NB_ASM_CLOBBERS);
 				DIAG_MARK(3);
 				int m_bits, es_bits, bidx;
@@ -472,10 +479,11 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				asm volatile(NB_ASM_AMAX("ds_read_b32 %[kr], %[l4] offset:%c[lc]", "ds_read_b32 %[ka], %[l4] offset:%c[lc]+256",
 							 "ds_read_b32 %[kb], %[l4] offset:%c[lc]+512", "ds_read_b32 %[kic], %[l4] offset:%c[lc]+768",
 							 "ds_read_b32 %[ktp], %[l4] offset:%c[lc]+1024", "s_nop 0", "s_nop 0", "s_nop 0")
+					     "s_sub_u32 %[bidx], %[bidx], %[lag0]\n\t"                 // arg-max lane -> lag (no maximum: bidx is not read)
 					     "s_waitcnt lgkmcnt(0)"
-					     : [m] "=s"(m_bits), [es] "=s"(es_bits), [bidx] "=s"(bidx), [kr] "=&v"(kr), [ka] "=&v"(ka), [kb] "=&v"(kb),
+					     : [m] "=&s"(m_bits), [es] "=&s"(es_bits), [bidx] "=&s"(bidx), [kr] "=&v"(kr), [ka] "=&v"(ka), [kb] "=&v"(kb),
 					       [kic] "=&v"(kic), [ktp] "=&v"(ktp)
-					     : [nrm] "v"(v), [ep] "v"(epart), [l4] "v"(4 * lane),
+					     : [nrm] "v"(v), [ep] "v"(epart), [l4] "v"(4 * lane), [lag0] "s"(lag0),
 					       [lc] "n"((TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 64 + 5 * WAVE) * 4)
 					     : NB_ASM_CLOBBERS);
 				DIAG_MARK(4);

@@ -9,7 +9,8 @@ blocks below are therefore whole phases of a burst, and this script CHECKS what 
   * wait states (gfx950 rules as the compiler's own code shows them): packed-fp32 result -> VALU reader 1; VALU-written
     VGPR -> DPP source 2; VALU-written SGPR / VCC -> VALU reader 2; transcendental result -> VALU reader 1; VALU-written
     VGPR -> v_readlane 1; VALU-written SGPR -> v_readlane lane select 4, -> VMEM address 5; x3 / x4 store data 2;
-  * every register loaded from LDS is covered by an s_waitcnt lgkmcnt(n) before its first use (LDS returns in order).
+  * every register loaded from LDS is covered by an s_waitcnt lgkmcnt(n) before its first use (LDS returns in order);
+  * a DPP source lane that EXEC disables is invalid: the mask of a wave_shr:1 instruction is a run of lanes from lane 0.
 Registers: operands the compiler allocates are %[name]; the blocks' temporaries are the fixed VGPRs v64..v127 and SGPRs
 s87..s99, declared as clobbers of every statement (NB_ASM_CLOBBERS)."""
 import os
@@ -155,6 +156,10 @@ class Block:
                 for r in rd:
                     if r in w_exec and w_exec[r] != "full" and w_exec[r] != exec_tok and r not in getattr(self, "exec_ok", ()):
                         errs.append(f"{self.name}: `{text.strip()}` under EXEC {exec_tok!r} reads {r}, written under {w_exec[r]!r}")
+            # ---- a DPP source lane that EXEC disables is invalid (the write is dropped, or reads 0 with bound_ctrl): under wave_shr:1
+            # lane l reads lane l - 1, so the mask must be full or a run of lanes that starts at lane 0
+            if is_dpp and "wave_shr:1" in mods and exec_tok != "full" and not re.match(r"^(s_bfm_b64 exec, \S+, 0|s_lshr_b64 exec, -1, \S+)$", exec_tok):
+                errs.append(f"{self.name}: `{text.strip()}` under EXEC {exec_tok!r}: the mask does not cover every DPP source lane")
             # ---- LDS data must have arrived
             for r in rd:
                 if r in pending:
@@ -226,29 +231,102 @@ def sreg(i, n=1):
 # block DEC: the /4 decimator of the detection window (downsampleBurst restricted to what the correlation and computeCI
 # read, sigProcLib.cpp:1587-1601) + the addition-only correlation's guard (unit_unsafe, trx_device.h).
 #   %[pd]   VGPR  LDS byte address of P + PH_M0 + (56 + lane) - 4     (polyphase burst, trx_k4_common.h)
-#   %[vd]   VGPR  LDS byte address of D[lane]
+#   %[vd]   VGPR  LDS byte address of D[lane]          %[vd4] VGPR  LDS byte address of D[lane - 4]
 #   %[zero] VGPR  0 (address of the wave-uniform tap reads)
-#   %[nact] SGPR  15 + len: active lanes
+#   %[nact] SGPR  15 + len: decimated samples
 #   %[bad]  SGPR pair out: lanes whose decimated sample fails the guard
+#   %[dr] %[di] VGPR out: the decimated sample, re / im (lane l + 4: sample l; undefined for the wide form)
 # y = sum_k x[4i-15+k] * g[k], product then sum, k ascending, first sum = first product (decimate16_sym<true>); taps 0..7
-# only (bitwise symmetric filter).  The sixteen samples arrive in order: four waits, each covering the next four.
+# only (bitwise symmetric filter).  Tap k of output l is polyphase entry P[(k+1)&3][m0 + l + ((k+1)>>2)]: for one phase the
+# entry output l takes at row offset j+1 is the one output l+1 takes at offset j.
+#   * windows of up to 60 samples (max_toa <= 29): every lane loads ITS OWN four entries X_r = P[r][m0 + lane] and forms all
+#     sixteen products with them; the accumulator of output l starts in lane l and MOVES one lane up (wave_shr:1 on the
+#     accumulator operand of the add) whenever the next tap's sample lives one row further -- in front of taps 3, 7, 11, 15.
+#     The same products, summed in the same order; output l ends in lane l + 4.  4 sample reads instead of 16.
+#   * wider windows (15 + len + 4 > 64 lanes): lane = output, sixteen reads per lane (.Lnb_dec_wide).
 # ------------------------------------------------------------------------------------------------------------------
-def block_dec(gdec_off):
-    b = Block("DEC", ("nact", "bad"))
+DEC_SHIFT = 4                    # lanes the moving accumulator travels
+DEC_MAX_NACT = 64 - DEC_SHIFT    # widest window of the moving form
+DPP_SHR = "wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+
+
+def dec_guard(b, re, im, t0, t1):
+    b(f"v_min_f32_e64 {t0}, |{re}|, |{im}|")
+    b(f"v_max_f32_e64 {t1}, |{re}|, |{im}|")
+    b(f"v_ldexp_f32 {t0}, {t0}, 17")
+    b(f"v_cmp_lt_f32_e32 vcc, {t0}, {t1}")
+    b("s_mov_b64 exec, -1")
+    b("s_mov_b64 %[bad], vcc")
+    b("s_waitcnt lgkmcnt(0)")          # (the store: nothing of this block may be outstanding for the checker; costs nothing behind the guard)
+
+
+def dec_tap(kk):
+    base = (124 if (kk >> 2) else 120) + (2 if (kk & 2) else 0)
+    sel = "op_sel:[0,1] op_sel_hi:[1,1]" if (kk & 1) else "op_sel:[0,0] op_sel_hi:[1,0]"
+    return f"{vreg(base, 2)} {sel}"
+
+
+def dec_moving(gdec_off):
+    b = Block("DEC[moving]", ("nact", "bad"))
+    PR = lambda k: 64 + 2 * k                  # product of tap k: v[64+2k : 65+2k]
+    XR = lambda r: vreg(96 + 2 * r, 2)         # this lane's entry of phase r
+    ACC = 104
+    b(f"s_sub_u32 s88, {DEC_MAX_NACT}, %[nact]")
+    b("s_lshr_b64 exec, -1, s88")             # lanes 0 .. nact + 3 (all 64 at the widest window, which s_bfm_b64 cannot express):
+                                              # every lane an accumulator passes through (a DPP source lane must be enabled)
+    b(f"ds_read_b128 {vreg(120, 4)}, %[zero] offset:{gdec_off}")
+    b(f"ds_read_b128 {vreg(124, 4)}, %[zero] offset:{gdec_off + 16}")
+    for r in (1, 2, 3, 0):
+        b(f"ds_read_b64 {XR(r)}, %[pd] offset:{r * PH_A * 8}")
+
+    def mul(k):
+        b(f"v_pk_mul_f32 {vreg(PR(k), 2)}, {XR((k + 1) & 3)}, {dec_tap(k if k < 8 else 15 - k)}")
+
+    def add(k):
+        src0 = vreg(PR(0), 2) if k == 1 else vreg(ACC, 2)
+        b(f"v_pk_add_f32 {vreg(ACC, 2)}, {src0}, {vreg(PR(k), 2)}")
+
+    def add_moving(k, dst=(f"v{ACC}", f"v{ACC + 1}")):
+        for c in range(2):
+            b(f"v_add_f32_dpp {dst[c]}, v{ACC + c}, v{PR(k) + c} {DPP_SHR}")
+
+    b("s_waitcnt lgkmcnt(3)")
+    mul(0)
+    b("s_waitcnt lgkmcnt(2)")
+    mul(1)
+    b("s_waitcnt lgkmcnt(1)")
+    mul(2); add(1)
+    b("s_waitcnt lgkmcnt(0)")
+    mul(3); add(2); mul(4); mul(5); add_moving(3)
+    mul(6); add(4); mul(7); add(5); mul(8); add(6); mul(9); mul(10); add_moving(7)
+    mul(11); add(8); mul(12); add(9); mul(13); add(10); mul(14); mul(15); add_moving(11)
+    add(12)
+    b("s_nop 0")
+    add(13)
+    b("s_nop 0")
+    add(14)
+    b("s_nop 1")
+    out = ("%[dr]", "%[di]")
+    add_moving(15, out)
+    b(f"s_bfm_b64 exec, %[nact], {DEC_SHIFT}")                     # output l sits in lane l + 4
+    b("ds_write2_b32 %[vd4], %[dr], %[di] offset1:1")          # D[] stays: computeCI's samples (TAIL), the multiplying correlation
+    dec_guard(b, out[0], out[1], "v106", "v107")
+    b.exec_ok = {f"v{ACC}", f"v{ACC + 1}", "%[dr]", "%[di]"}       # (lanes 4 .. nact + 3 are inside the mask they were written under)
+    return b
+
+
+def dec_wide(gdec_off):
+    b = Block("DEC[wide]", ("nact", "bad"))
     X = lambda k: vreg(88 + 2 * k, 2)
-    GA, GB = 120, 124
-    b(f"s_bfm_b64 exec, %[nact], 0")
-    b(f"ds_read_b128 {vreg(GA, 4)}, %[zero] offset:{gdec_off}")
-    b(f"ds_read_b128 {vreg(GB, 4)}, %[zero] offset:{gdec_off + 16}")
+    b("s_bfm_b64 exec, %[nact], 0")
+    b(f"ds_read_b128 {vreg(120, 4)}, %[zero] offset:{gdec_off}")
+    b(f"ds_read_b128 {vreg(124, 4)}, %[zero] offset:{gdec_off + 16}")
     for k in range(16):
         off = (((k + 1) & 3) * PH_A + ((k + 1) >> 2)) * 8
         b(f"ds_read_b64 {X(k)}, %[pd] offset:{off}")
 
     def mul(k):
-        kk = k if k < 8 else 15 - k
-        base = (GB if (kk >> 2) else GA) + (2 if (kk & 2) else 0)
-        sel = "op_sel:[0,1] op_sel_hi:[1,1]" if (kk & 1) else "op_sel:[0,0] op_sel_hi:[1,0]"
-        b(f"v_pk_mul_f32 {X(k)}, {X(k)}, {vreg(base, 2)} {sel}")
+        b(f"v_pk_mul_f32 {X(k)}, {X(k)}, {dec_tap(k if k < 8 else 15 - k)}")
 
     def add(k):            # y (in X(0)) += product k
         b(f"v_pk_add_f32 {X(0)}, {X(0)}, {X(k)}")
@@ -264,71 +342,54 @@ def block_dec(gdec_off):
     b("s_nop 0")
     add(15)
     b(f"ds_write_b64 %[vd], {X(0)}")
-    b("v_min_f32_e64 v90, |v88|, |v89|")
-    b("v_max_f32_e64 v91, |v88|, |v89|")
-    b("v_ldexp_f32 v90, v90, 17")
-    b("v_cmp_lt_f32_e32 vcc, v90, v91")
-    b("s_mov_b64 exec, -1")
-    b("s_mov_b64 %[bad], vcc")
-    b("s_waitcnt lgkmcnt(0)")          # (the store: nothing of this block may be outstanding for the checker; costs nothing behind the guard)
+    dec_guard(b, "v88", "v89", "v90", "v91")
     return b
+
+
+def block_dec(gdec_off):
+    """-> (block, [straight-line paths to check])"""
+    mv, wd = dec_moving(gdec_off), dec_wide(gdec_off)
+    b = Block("DEC", ("nact", "bad"))
+    b.ins = [f"s_cmp_gt_u32 %[nact], {DEC_MAX_NACT}", "s_cbranch_scc1 .Lnb_dec_wide"] + mv.ins + ["s_branch .Lnb_dec_end", ".Lnb_dec_wide:"] + \
+        wd.ins + [".Lnb_dec_end:"]
+    return b, [mv, wd]
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # block CORR: correlation of the window against the slot's training sequence without multiplications (corr_unit,
-# trx_device.h: every tap is +-1 rotated by k pi/2 under the guard), lane = lag; arg-max input.
+# trx_device.h: every tap is +-1 rotated by k pi/2 under the guard); arg-max input.
 #   %[vd]  VGPR  LDS byte address of D[lane]      %[vcz] VGPR  LDS byte address of cz[lane]
 #   %[len] SGPR  window length                    %[tsc] SGPR  training sequence 0..7
-#   %[nrm] VGPR out: |corr|^2 (0 for lanes >= len)
-# The sum is one chain by definition (the reference's order) and a dependent v_pk_add_f32 needs a wait state: the waits
-# for the next sample ARE those wait states.  Eight variants (sign / swap patterns are instruction modifiers), entered by
-# a computed jump.
+#   %[nrm] VGPR out: |corr|^2 (0 for lanes that hold no lag)
+#   %[dr] %[di] VGPR the decimated sample of lane - 4 (block DEC); %[vdm] %[vczm] VGPR LDS byte addresses of D[lane - 19]
+#   and cz[lane - 19]
+# The sum is one chain by definition (the reference's order: k ascending from +0, convolve_base.c:28-54).  Eight variants
+# (the sign / component pattern of a training sequence), entered by a computed jump.
+#   * wide windows (more than 45 lags): lane = lag; D[lag + k] from LDS, one v_pk_add_f32 per tap (sign / swap are
+#     instruction modifiers); a dependent v_pk_add_f32 needs a wait state: the waits for the next sample ARE those.
+#   * windows of up to 45 lags: decimated sample i sits in lane i + 4 (block DEC), and the accumulator moves:
+#     acc[l] = acc[l - 1] +- d_c[l] (wave_shr:1 on the accumulator, re and im chains interleaved: a VALU-written DPP source
+#     needs two wait states, the other chain's add is one of them).  After tap k lane l holds sum_{k' <= k} s_k' d[l - 4 - k + k']:
+#     lag lam ends in lane lam + 19.  No LDS read.  Lanes below 19 hold partial sums: |corr|^2 = 0 there.
 # ------------------------------------------------------------------------------------------------------------------
-def block_corr(lseq_off):
-    b = Block("CORR", ("len", "tsc", "bad"))
-    X = lambda k: vreg(88 + 2 * k, 2)
-    ACC = vreg(120, 2)
-    b(f"v_mov_b64_e32 {ACC}, 0")
-    b("s_bfm_b64 exec, %[len], 0")
-    for k in range(16):
-        b(f"ds_read_b64 {X(k)}, %[vd] offset:{8 * k}")
-    b("s_cmp_lg_u64 %[bad], 0")                                    # a sample failed the guard: the multiplying form (below)
-    b("s_cbranch_scc1 .Lnb_corr_mul")
+CORR_LANE0 = DEC_SHIFT + 15      # lane of lag 0 in the moving form
+CORR_MAX_LEN = 64 - CORR_LANE0
+
+
+def corr_jump(b, sfx):
     b("s_getpc_b64 s[88:89]")
-    b(".Lnb_corr_pc:")
-    b("s_mul_i32 s90, %[tsc], .Lnb_corr_v1-.Lnb_corr_v0")
+    b(f".Lnb_corr{sfx}_pc:")
+    b(f"s_mul_i32 s90, %[tsc], .Lnb_corr{sfx}_v1-.Lnb_corr{sfx}_v0")
     b("s_add_u32 s88, s88, s90")
     b("s_addc_u32 s89, s89, 0")
-    b("s_add_u32 s88, s88, .Lnb_corr_v0-.Lnb_corr_pc")
+    b(f"s_add_u32 s88, s88, .Lnb_corr{sfx}_v0-.Lnb_corr{sfx}_pc")
     b("s_addc_u32 s89, s89, 0")
     b("s_setpc_b64 s[88:89]")
-    for t in range(8):
-        b(f".Lnb_corr_v{t}:")
-        for k in range(16):
-            odd, neg = (k & 1), (NEG_MASKS[t] >> k) & 1
-            if not odd and not neg:
-                mod = ""
-            elif not odd and neg:
-                mod = " neg_lo:[0,1] neg_hi:[0,1]"
-            elif odd and not neg:
-                mod = " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,0]"
-            else:
-                mod = " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,0] neg_hi:[0,1]"
-            b(f"s_waitcnt lgkmcnt({15 - k})")
-            b(f"v_pk_add_f32 {ACC}, {ACC}, {X(k)}{mod}")
-        b("s_branch .Lnb_corr_join")
-    b(".Lnb_corr_join:")
-    b("s_add_u32 s90, %[len], 12")
-    b("s_bfm_b64 exec, s90, 0")
-    b(f"ds_write_b64 %[vcz], {ACC}")
-    b("s_mov_b64 exec, -1")                         # (lanes >= len hold the 0 they were initialised with: |corr|^2 = 0 there)
-    b(f"v_pk_mul_f32 v[122:123], {ACC}, {ACC}")
-    b("s_waitcnt lgkmcnt(0)")
-    b("v_add_f32_e32 %[nrm], v123, v122")
-    b("s_branch .Lnb_corr_end")
-    # ---- cold (about one burst in 3000): convolve_complex() as written (convolve_base.c:28-40, :72-85), taps from LDS:
-    # (yr, yi) += (xr hr - xi hi, xr hi + xi hr) as two packed multiplies, one packed add with the low half negated, one accumulate
-    b(".Lnb_corr_mul:")
+
+
+def corr_mul(b, sfx, lseq_off, X, ACC):
+    """cold (about one burst in 3000): convolve_complex() as written (convolve_base.c:28-40, :72-85), taps from LDS:
+    (yr, yi) += (xr hr - xi hi, xr hi + xi hr) as two packed multiplies, one packed add with the low half negated, one accumulate"""
     b("s_lshl_b32 s90, %[tsc], 7")
     b("v_mov_b32_e32 v64, s90")
     H = lambda k: vreg(66 + 2 * (k & 7), 2)
@@ -343,9 +404,143 @@ def block_corr(lseq_off):
             b("v_pk_add_f32 v[86:87], v[82:83], v[84:85] neg_lo:[0,1] neg_hi:[0,0]")
             b("s_nop 0")
             b(f"v_pk_add_f32 {ACC}, {ACC}, v[86:87]")
-    b("s_branch .Lnb_corr_join")
-    b(".Lnb_corr_end:")
-    return b
+    b(f"s_branch .Lnb_corr{sfx}_join")
+
+
+def corr_lanes(lseq_off, sfx):
+    """lane = lag, samples from D[] -> (head, [variant t], join, mul): lists of lines"""
+    X = lambda k: vreg(88 + 2 * k, 2)
+    ACC = vreg(120, 2)
+    h = Block("h")
+    h(f"v_mov_b64_e32 {ACC}, 0")
+    h("s_bfm_b64 exec, %[len], 0")
+    for k in range(16):
+        h(f"ds_read_b64 {X(k)}, %[vd] offset:{8 * k}")
+    h("s_cmp_lg_u64 %[bad], 0")                                    # a sample failed the guard: the multiplying form
+    h(f"s_cbranch_scc1 .Lnb_corr{sfx}_mul")
+    corr_jump(h, sfx)
+    vs = []
+    for t in range(8):
+        v = Block("v")
+        v(f".Lnb_corr{sfx}_v{t}:")
+        for k in range(16):
+            odd, neg = (k & 1), (NEG_MASKS[t] >> k) & 1
+            if not odd and not neg:
+                mod = ""
+            elif not odd and neg:
+                mod = " neg_lo:[0,1] neg_hi:[0,1]"
+            elif odd and not neg:
+                mod = " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,0]"
+            else:
+                mod = " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,0] neg_hi:[0,1]"
+            v(f"s_waitcnt lgkmcnt({15 - k})")
+            v(f"v_pk_add_f32 {ACC}, {ACC}, {X(k)}{mod}")
+        v(f"s_branch .Lnb_corr{sfx}_join")
+        vs.append(v.ins)
+    j = Block("j")
+    j(f".Lnb_corr{sfx}_join:")
+    j("s_add_u32 s90, %[len], 12")
+    j("s_bfm_b64 exec, s90, 0")
+    j(f"ds_write_b64 %[vcz], {ACC}")
+    j("s_mov_b64 exec, -1")                         # (lanes >= len hold the 0 they were initialised with: |corr|^2 = 0 there)
+    j(f"v_pk_mul_f32 v[122:123], {ACC}, {ACC}")
+    j("s_waitcnt lgkmcnt(0)")
+    j("v_add_f32_e32 %[nrm], v123, v122")
+    j("s_branch .Lnb_corr_end")
+    m = Block("m")
+    m(f".Lnb_corr{sfx}_mul:")
+    corr_mul(m, sfx, lseq_off, X, ACC)
+    return h.ins, vs, j.ins, m.ins
+
+
+def corr_moving(lseq_off):
+    """lane = lag + 19, samples from block DEC's registers"""
+    sfx = "r"
+    X = lambda k: vreg(88 + 2 * k, 2)
+    ACC = vreg(120, 2)
+    D = ("%[dr]", "%[di]")
+    h = Block("h")
+    h(f"v_mov_b64_e32 {ACC}, 0")
+    h("v_mov_b64_e32 v[122:123], 0")
+    h("v_mov_b32_e32 %[nrm], 0")
+    h("s_lshl_b32 s90, %[len], 3")
+    h(f"s_sub_u32 s91, {CORR_MAX_LEN}, %[len]")
+    h("v_add_u32_e32 v64, s90, %[vcz]")                             # &cz[len + lane]: the right zero pad, stored by lanes 0..11
+    h("s_lshr_b64 exec, -1, s91")                                  # lanes 0 .. len + 18: every lane that holds a sample or passes an accumulator on
+    h("s_cmp_lg_u64 %[bad], 0")
+    h(f"s_cbranch_scc1 .Lnb_corr{sfx}_mul")
+    corr_jump(h, sfx)
+    vs = []
+    for t in range(8):
+        v = Block("v")
+        v(f".Lnb_corr{sfx}_v{t}:")
+        for k in range(16):
+            odd, neg = (k & 1), (NEG_MASKS[t] >> k) & 1
+            # tap k = (+-1) (j)^k... as the packed form has it: even: (re, im) +- (d.re, d.im); odd: (re -+ d.im, im +- d.re)
+            if not odd:
+                ops = [("sub" if neg else "add", D[0]), ("sub" if neg else "add", D[1])]
+            else:
+                ops = [("add" if neg else "sub", D[1]), ("sub" if neg else "add", D[0])]
+            for c in range(2):
+                if k == 0:
+                    v(f"v_{ops[c][0]}_f32_e32 v{120 + c}, 0, {ops[c][1]}")
+                else:
+                    v(f"v_{ops[c][0]}_f32_dpp v{120 + c}, v{120 + c}, {ops[c][1]} {DPP_SHR}")
+            if k < 15:
+                v("s_nop 0")
+        v(f"s_branch .Lnb_corr{sfx}_join")
+        vs.append(v.ins)
+    j = Block("j")
+    j(f".Lnb_corr{sfx}_join:")
+    j("s_bfm_b64 exec, 12, 0")
+    j("ds_write_b64 v64, v[122:123]")
+    j(f"s_bfm_b64 exec, %[len], {CORR_LANE0}")
+    j(f"ds_write_b64 %[vczm], {ACC}")
+    j(f"v_pk_mul_f32 v[124:125], {ACC}, {ACC}")
+    j("s_nop 0")
+    j("v_add_f32_e32 %[nrm], v125, v124")
+    j("s_mov_b64 exec, -1")
+    j("s_waitcnt lgkmcnt(0)")
+    j("s_branch .Lnb_corr_end")
+    m = Block("m")
+    m(f".Lnb_corr{sfx}_mul:")
+    m(f"s_bfm_b64 exec, %[len], {CORR_LANE0}")
+    for k in range(16):
+        m(f"ds_read_b64 {X(k)}, %[vdm] offset:{8 * k}")
+    corr_mul(m, sfx, lseq_off, X, ACC)
+    return h.ins, vs, j.ins, m.ins
+
+
+def block_corr(lseq_off):
+    """-> (block, [straight-line paths to check])"""
+    ops = ("len", "tsc", "bad")
+    b = Block("CORR", ops)
+    paths = []
+
+    def add_form(name, parts, pre):
+        h, vs, j, m = parts
+        b.ins += h
+        for v in vs:
+            b.ins += v
+        b.ins += j + m
+        ibr = next(i for i, t in enumerate(h) if t.startswith("s_cbranch_scc1"))
+        for t, v in enumerate(vs):
+            p = Block(f"CORR[{name}, tsc {t}]", ops)
+            p.ins = pre + h + v + j
+            paths.append(p)
+        p = Block(f"CORR[{name}, mul]", ops)
+        p.ins = pre + h[:ibr] + m + j
+        paths.append(p)
+
+    pre = [f"s_cmp_gt_u32 %[len], {CORR_MAX_LEN}", "s_cbranch_scc1 .Lnb_corr_wide"]
+    b.ins += pre
+    add_form("moving", corr_moving(lseq_off), pre)
+    b.ins += [".Lnb_corr_wide:"]
+    add_form("lanes", corr_lanes(lseq_off, "w"), pre)
+    b.ins += [".Lnb_corr_end:"]
+    for p in paths:
+        p.exec_ok = {"v120", "v121"}                               # (the lanes read are inside the mask they were written under)
+    return b, paths
 
 
 def check_paths(b):
@@ -368,28 +563,6 @@ def check_paths(b):
         for e in v.check():
             if e.split(": ", 1)[1] not in [x.split(": ", 1)[1] for x in errs]:
                 errs.append(e)
-    return errs
-
-
-def check_variants(b):
-    """CORR: check each variant as its own straight line (prefix + variant t + suffix)"""
-    errs = []
-    lines = b.ins
-    # the multiplying form: prefix up to the branch, the cold block, then the join
-    im, ie = lines.index(".Lnb_corr_mul:"), lines.index(".Lnb_corr_end:")
-    ibr = lines.index("s_cbranch_scc1 .Lnb_corr_mul")
-    jj = lines.index(".Lnb_corr_join:")
-    v = Block("CORR[mul]", ("len", "tsc", "bad"))
-    v.ins = lines[:ibr] + lines[im:ie - 0] + lines[jj:im - 0]
-    errs += v.check()
-    lines = lines[:im] + lines[ie:]
-    i0 = lines.index(".Lnb_corr_v0:")
-    j = lines.index(".Lnb_corr_join:")
-    per = (j - i0) // 8
-    for t in range(8):
-        v = Block(f"CORR[tsc {t}]", ("len", "tsc"))
-        v.ins = lines[:i0] + lines[i0 + t * per: i0 + (t + 1) * per] + lines[j:]
-        errs += v.check()
     return errs
 
 
@@ -917,19 +1090,22 @@ def main(out=OUT):
     gdec_off = (SINCV_LDS + 16 * 64 + 65 * 36) * 4
     NB_TABLES_END_OLD = SINCV_LDS + 16 * 64 + 65 * 36 + 16 + 64 + 5 * 64 + 5 * 64      # floats in front of the training-sequence taps
     blocks = {}
-    blocks["DEC"] = block_dec(gdec_off)
+    blocks["DEC"], dec_paths = block_dec(gdec_off)
     lseq_off = NB_TABLES_END_OLD * 4
-    blocks["CORR"] = block_corr(lseq_off)
+    blocks["CORR"], corr_paths = block_corr(lseq_off)
     wa4_off = SINCV_LDS * 4
     blocks["DETA"] = block_deta(wa4_off)
     blocks["DETB"] = block_detb()
     blocks["TAIL"] = block_tail()
     blocks["FIRG"] = block_firg()
-    errs = blocks["DEC"].check() + check_variants(blocks["CORR"]) + check_paths(blocks["DETA"]) + check_paths(blocks["DETB"]) + \
+    errs = [e for p in dec_paths + corr_paths for e in p.check()] + check_paths(blocks["DETA"]) + check_paths(blocks["DETB"]) + \
         check_paths(blocks["TAIL"]) + check_paths(blocks["FIRG"])
     hdr = ["// trx_nb_asm.inc -- GENERATED by tools/gen_nb_asm.py (hazards and LDS waits checked there); do not edit.",
            f"#define NB_ASM_GDEC_OFF {gdec_off}",
            f"#define NB_ASM_LSEQ_OFF {lseq_off}",
+           f"#define NB_ASM_DEC_MAX_NACT {DEC_MAX_NACT}",
+           f"#define NB_ASM_CORR_LANE0 {CORR_LANE0}",
+           f"#define NB_ASM_CORR_MAX_LEN {CORR_MAX_LEN}",
            "#define NB_ASM_CLOBBERS " + ", ".join(f'"v{i}"' for i in range(64, 128)) + ", " +
            ", ".join(f'"s{i}"' for i in range(87, 100)) + ', "vcc", "scc", "memory"']
     for name, b in blocks.items():
