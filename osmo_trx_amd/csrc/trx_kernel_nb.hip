@@ -12,8 +12,8 @@
 //   * the peak-ratio gate is too close to call for the estimate (about one in 1e5);
 //   * the detected TOA is outside the straight-line demodulator's geometry (toa < -0.25 or > 9 symbols).
 // What is different from the general kernel, beside what is absent:
-//   * soft bits never go through LDS: the three outputs of a lane (symbols 4 + 3 lane + j; symbols 0..3 come from the
-//     low-edge lanes) are rotated, scaled and sliced in registers -- the (-j)^i rotation is a quad permutation of ONE
+//   * soft bits never go through LDS: the three outputs of a lane (lanes 2..49: symbols 3 lane - 2 + j, the sums the demodulator's
+//     moving accumulators end in; symbols 0..3 come from the low-edge lanes 54, 57, 60, 63) are rotated, scaled and sliced in registers -- the (-j)^i rotation is a quad permutation of ONE
 //     per-lane multiplier, applied by the DPP operand of the multiply -- and stored as one 12-byte store per lane (a
 //     contiguous 576-byte run per burst), one burst late like the general kernel's (the stores must be older than the
 //     prefetch loads: vmcnt retires in order);
@@ -117,12 +117,14 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		lcn[0 * WAVE + threadIdx.x] = pc0.ratio_off * 8;
 		lcn[1 * WAVE + threadIdx.x] = (pc0.flA - 8) * 8;
 		lcn[2 * WAVE + threadIdx.x] = pc0.offB;
-		// the demodulator's lanes: 0..47 symbols 4 + 3 lane .. with the composite row; 52..55 symbol e = (-lane) & 3, main part of its
-		// truncated row (row e of the parked block); 56..59 the same symbols' taps u < 8 (row 4 + e, window two symbols earlier)
-		const int l = threadIdx.x, e = (-l) & 3;
-		const bool sp = l >= 52 && l < 60;
-		lcn[3 * WAVE + l] = 8 * (sp ? (l < 56 ? e : e - 2) : (l < 48 ? 4 + 3 * l : 148));   // first symbol, bytes
-		lcn[4 * WAVE + l] = sp ? (e + (l >= 56 ? 4 : 0)) * K4_NTP * 4 : -1;                 // tap row inside the parked block, bytes
+		// the demodulator's lanes (tools/gen_nb_asm.py, fir_moving: every lane holds twelve samples = three symbols, the sums move
+		// two lanes up): 0..49 samples from symbol 4 + 3 lane on, composite row (50, 51: idle, as 49); 52 + 3 e + t, low-edge symbol
+		// e: t = 0, 1 main part -- samples from symbol e / e + 3, row e of the parked block; t = 2 its taps u < 8 -- samples from
+		// symbol e - 3, row 4 + e
+		const int l = threadIdx.x, e = (l - 52) / 3, t = (l - 52) % 3;
+		const bool sp = l >= 52;
+		lcn[3 * WAVE + l] = 8 * (sp ? (t == 0 ? e : t == 1 ? e + 3 : e - 3) : 4 + 3 * (l < 49 ? l : 49));   // first symbol, bytes
+		lcn[4 * WAVE + l] = sp ? (e + (t == 2 ? 4 : 0)) * K4_NTP * 4 : -1;                 // tap row inside the parked block, bytes
 	}
 	for (int i = lane0; i < NB_SLICE; i += WAVE)
 		wbase[i] = make_float2(0.0f, 0.0f);
@@ -357,16 +359,17 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				dec[hi_i] = cmul(make_float2(sr, si), scale);
 		}
 		wave_sync();
-		// this kernel's lanes: 0..47 symbols 4 + 3 lane + j, 52..55 symbol (-lane) & 3; real((-j)^i x) and the slicer as the general
-		// kernel's flush() has them (component i & 1, sign by i & 2)
+		// this kernel's lanes: 2..49 symbols 3 lane - 2 + j, 54 + 3 e symbol e (the other lanes' values are never stored: any valid
+		// index); real((-j)^i x) and the slicer as the general kernel's flush() has them (component i & 1, sign by i & 2)
 		auto pick = [&](int i) {
 			const float d = reinterpret_cast<const float *>(dec + i)[i & 1];
 			return __builtin_amdgcn_fmed3f(fmaf((i & 2) ? -0.5f : 0.5f, d, 0.5f), 0.0f, 1.0f);
 		};
-		const int i0 = (lane < 48) ? 4 + 3 * lane : ((-lane) & 3);
+		const bool reg = lane >= 2 && lane < 50;
+		const int i0 = reg ? 3 * lane - 2 : ((((lane - 54) * 11) >> 5) & 3);
 		o.x = pick(i0);
-		o.y = pick(lane < 48 ? i0 + 1 : 0);
-		o.z = pick(lane < 48 ? i0 + 2 : 0);
+		o.y = pick(reg ? i0 + 1 : 0);
+		o.z = pick(reg ? i0 + 2 : 0);
 		wave_sync();
 		return true;
 	};
@@ -411,21 +414,22 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				asm volatile("" :: "v"(pre_i[r]));
 		}
 		DIAG_MARK(14);
-		// ---- the previous burst's output: 148 soft bits (lanes 0..47: symbols 4 + 3 lane + j as one 12-byte store, lanes
-		// 52..55: symbols 0..3) and the result record (lanes 0..7)
+		// ---- the previous burst's output: 148 soft bits (lanes 2..49: symbols 3 lane - 2 + j as one 12-byte store, lanes
+		// 54, 57, 60, 63: symbols 0..3) and the result record (lanes 0..7)
 		if (pend_any) {
 			float *const so = soft + (size_t)pend_b * 148;
 			int *const rp = reinterpret_cast<int *>(results + pend_b);
 			const float oe = o.x;
-			asm volatile("s_bfm_b64 exec, 48, 0\n\t"
+			asm volatile("s_bfm_b64 exec, 48, 2\n\t"
 				     "global_store_dwordx3 %0, %1, %2 offset:16\n\t"
-				     "s_bfm_b64 exec, 4, 52\n\t"
+				     "s_mov_b32 exec_lo, 0\n\t"
+			     "s_mov_b32 exec_hi, 0x92400000\n\t"
 				     "global_store_dword %3, %4, %2\n\t"
 				     "s_mov_b64 exec, %8\n\t"
 				     "global_store_dword %5, %6, %7\n\t"
 				     "s_mov_b64 exec, -1\n\t"
 				     "s_nop 0"
-				     :: "v"(lane * 12), "v"(o), "s"(so), "v"(((-lane) & 3) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
+				     :: "v"((lane - 2) * 12), "v"(o), "s"(so), "v"((((lane - 54) * 11) >> 5) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
 				        "s"(pend_rec ? 0xffull : 0ull)
 				     : "memory");
 		}
@@ -619,15 +623,16 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		float *const so = soft + (size_t)pend_b * 148;
 		int *const rp = reinterpret_cast<int *>(results + pend_b);
 		const float oe = o.x;
-		asm volatile("s_bfm_b64 exec, 48, 0\n\t"
+		asm volatile("s_bfm_b64 exec, 48, 2\n\t"
 			     "global_store_dwordx3 %0, %1, %2 offset:16\n\t"
-			     "s_bfm_b64 exec, 4, 52\n\t"
+		     "s_mov_b32 exec_lo, 0\n\t"
+		     "s_mov_b32 exec_hi, 0x92400000\n\t"
 			     "global_store_dword %3, %4, %2\n\t"
 			     "s_mov_b64 exec, %8\n\t"
 			     "global_store_dword %5, %6, %7\n\t"
 			     "s_mov_b64 exec, -1\n\t"
 			     "s_nop 0"
-			     :: "v"(lane * 12), "v"(o), "s"(so), "v"(((-lane) & 3) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
+			     :: "v"((lane - 2) * 12), "v"(o), "s"(so), "v"((((lane - 54) * 11) >> 5) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
 			        "s"(pend_rec ? 0xffull : 0ull)
 			     : "memory");
 	}

@@ -925,20 +925,23 @@ def block_tail():
 # ------------------------------------------------------------------------------------------------------------------
 # block DEMOD: demodGmskBurst (:2055-2072) of the usual geometry, fused: delay o decimate as one 24-tap filter at the
 # symbol instants (fir24x3, trx_k4_common.h -- the same sums in the same order), rotation / 1/amp / slicer input in
-# registers.
-#   lanes 0..47: symbols 4 + 3 lane + j with the burst's composite row; lanes 52..55: symbol e = (-lane) & 3, main part of
-#   its truncated row (parked in D); lanes 56..59: the same symbols' taps u < 8 (window two symbols earlier)
+# registers.  The filter is a MOVING accumulator (fir_moving, below): every lane reads only its own twelve samples.
+#   lane m < 50: samples x[12 m + c + 16 + r], composite row; the sums of symbols 4 + 3 l + j (l < 48) start in lane l and
+#   end in lane l + 2.  Lanes 52 + 3 e + t carry low-edge symbol e = 0..3 (truncated rows, parked in D): t = 0, 1 the main
+#   part (row e) in slot 0 -- it ends in slot 0 of lane 54 + 3 e; t = 2 the taps u < 8 (row 4 + e) as a sum that stays in
+#   slot 1 of that lane; the two are joined by one add there.
+#   CONSUMED (lane, slot) pairs: lanes 2..49, slots 0..2; lanes 54, 57, 60, 63, slot 0.  Everything else (lanes 0, 1, 50, 51, the
+#   other slots of lanes 52..63) holds partial sums of no symbol and is never stored.
 #   in : SGPR nk, pb (LDS byte address of P[0] of this wave), cb (LDS byte address of comp + 32: tap U0 of row 0), db (LDS
-#        byte address of D); VGPR rows (4), vp, l16, kic (lane constant: 8 * first symbol), ktp (lane constant: byte offset
-#        of the lane's tap row inside D, -1 for the lanes on the composite row)
-#   out: VGPR d0 d1 d2: real((-j)^i z / amp) of the lane's three symbols (the slicer's input)
+#        byte address of D); VGPR rows (4), vp, l16, kic (lane constant: 8 * first symbol of the lane's twelve samples), ktp
+#        (lane constant: byte offset of the lane's tap row inside D, -1 for the lanes on the composite row)
+#   out: VGPR d0 d1 d2: real((-j)^i z / amp) of the three symbols that END in the lane (the slicer's input)
 # ------------------------------------------------------------------------------------------------------------------
 def block_demod(b):
     # the straight-line geometry: shift w = nk >> 7 in -36 .. 0 (0 <= TOA <= 9 symbols); other bursts leave with ok = 0 -- 1 / amp
     # and S are done -- and take the general form of the demodulator (trx_kernel_nb.hip, cold)
-    ACC = [vreg(64 + 2 * j, 2) for j in range(3)]
-    RING = lambda v: vreg(72 + 2 * (v & 15), 2)
-    CQ = [104, 108]
+    ACC = [64, 66, 68]
+    X = lambda r: vreg(72 + 2 * r, 2)
     P = [112, 113, 114, 115]
     # S = mean |sample|^2 of computeCI's sixteen samples (lanes 0..15: a tree sum), in the wait states of the address arithmetic
     b("s_bfm_b64 exec, 16, 0")
@@ -977,34 +980,34 @@ def block_demod(b):
         b(f"s_mul_i32 s96, s96, {(1 - 4 * PH_A) * 8}")
         b(f"s_add_u32 s96, s96, {k * PH_A * 8}")
         b(f"v_add_u32_e32 {vreg(P[k])}, s96, {vreg(P[0])}")
-    D, NT, NV = 4, 24, 32
     PH0 = 96                                                       # byte offset of PH_M0 entries
-    b("s_mov_b32 exec_hi, 0x0ff0ffff")                             # lanes 48..51 and 60..63 have no symbol: off for the filter
-    # the first twelve samples do not depend on the tap rows: requested in front of the wait for those (L2 latency)
-    for v in range(8 + D):
-        b(f"ds_read_b64 {RING(v)}, {vreg(P[v & 3])} offset:{PH0 + 8 * (v >> 2)}")
+    # (all 64 lanes run the filter: an accumulator passes through every lane below the one it ends in)
+    # the lane's twelve samples do not depend on the tap rows: requested in front of the wait for those (L2 latency)
+    for r in range(12):
+        b(f"ds_read_b64 {X(r)}, {vreg(P[r & 3])} offset:{PH0 + 8 * (r >> 2)}")
     b("v_add_u32_e32 v116, %[db], %[l16]")
     b("v_cmp_lt_i32_e32 vcc, -1, %[ktp]")
     b("v_add_u32_e32 v117, %[db], %[ktp]")
     b("v_mov_b32_e32 v118, s95")
     for j_ in range(3):
-        b(f"v_mov_b64_e32 {ACC[j_]}, 0")
+        b(f"v_mov_b64_e32 {vreg(ACC[j_], 2)}, 0")
     b("v_cndmask_b32_e32 v117, v118, v117, vcc")                   # this lane's tap row
     b("s_waitcnt vmcnt(0)")
     b("ds_write_b128 v116, v[120:123]")                            # park the low-edge rows: lane l < 48 holds floats 4l .. 4l+3 of the 8 x 24 block
-    fir_core(b, ACC, RING, CQ, P, preload=False)
-    # output stage: low-edge symbols = main part (lane 52 + c) + taps u < 8 (lane 56 + c); symbol i wants real((-j)^i z / amp) =
-    # z.x * VP[k] + z.y * VP[k - 1], k = i & 3 = (j - lane) & 3: a quad permutation of VP, applied by the DPP operand
-    b("s_nop 0")
-    b("v_add_f32_dpp v64, v64, v64 row_shl:4 row_mask:0x8 bank_mask:0xf")
-    b("v_add_f32_dpp v65, v65, v65 row_shl:4 row_mask:0x8 bank_mask:0xf")
-    b(f"v_mul_f32_dpp %[d1], v119, v66 quad_perm:[1,0,3,2] {D_ALL}")
-    b(f"v_mul_f32_dpp %[d2], v119, v68 quad_perm:[2,1,0,3] {D_ALL}")
-    b(f"v_mul_f32_dpp %[d0], v119, v64 quad_perm:[0,3,2,1] {D_ALL}")
-    b(f"v_fmac_f32_dpp %[d1], v119, v67 quad_perm:[0,3,2,1] {D_ALL}")
-    b(f"v_fmac_f32_dpp %[d2], v119, v69 quad_perm:[1,0,3,2] {D_ALL}")
-    b(f"v_fmac_f32_dpp %[d0], v119, v65 quad_perm:[3,2,1,0] {D_ALL}")
+    fir_moving(b, ACC, X)
+    # output stage: low-edge symbol e = main part (slot 0, arrived in lane 54 + 3 e) + taps u < 8 (slot 1 of that lane); symbol i
+    # wants real((-j)^i z / amp) = z.x * VP[k] + z.y * VP[k - 1], k = i & 3: a quad permutation of VP, applied by the DPP operand.
+    # The sums of lane L are those of symbols 3 L - 2 + j (lanes 54 + 3 e: 160 + 9 e = e mod 4, slot 0): k = (2 + j - L) & 3
+    b("s_mov_b32 exec_lo, 0")
+    b("s_mov_b32 exec_hi, 0xfff00000")
+    b("v_pk_add_f32 v[64:65], v[64:65], v[66:67]")                 # main + low (lanes 52..63; consumed: 54, 57, 60, 63)
     b("s_mov_b64 exec, -1")
+    b(f"v_mul_f32_dpp %[d1], v119, v66 quad_perm:[3,2,1,0] {D_ALL}")
+    b(f"v_mul_f32_dpp %[d2], v119, v68 quad_perm:[0,3,2,1] {D_ALL}")
+    b(f"v_mul_f32_dpp %[d0], v119, v64 quad_perm:[2,1,0,3] {D_ALL}")
+    b(f"v_fmac_f32_dpp %[d1], v119, v67 quad_perm:[2,1,0,3] {D_ALL}")
+    b(f"v_fmac_f32_dpp %[d2], v119, v69 quad_perm:[3,2,1,0] {D_ALL}")
+    b(f"v_fmac_f32_dpp %[d0], v119, v65 quad_perm:[1,0,3,2] {D_ALL}")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1046,6 +1049,115 @@ def block_firg():
     fir_core(b, ACC, RING, CQ, P, preload=True)
     b("s_mov_b64 exec, -1")
     return b
+
+
+FIRM_LOW_LANE0 = 52              # first lane of the low-edge symbols (three lanes per symbol)
+
+
+def fir_moving(b, ACC, X):
+    """The composite filter as a moving accumulator.  Today's sum of lane l, slot j: ACC[j] = sum_{u = 0..23} x[12 l + c + 4 j + u] h[u],
+    u ascending from +0.  With 4 j + u = 12 s + r (stage s = 0, 1, 2; r = 0..11) the sample is X_{l + s}[r], one of the twelve that
+    lane l + s holds: in stage s lane m adds X_m[r] h[12 s + r - 4 j] into slot j for the r with 0 <= 12 s + r - 4 j < 24, r
+    ascending, and between two stages the slot's accumulator moves one lane up (v_mov_b32_dpp wave_shr:1).  Every output is the
+    same 24 FMAs in the same order from the same +0 -- the same bits -- and ends in lane l + 2 (slot 0 has no stage 2: it is
+    carried there by a second move, so that the three sums of a lane belong to adjacent symbols).
+        terms (stage, slot):   slot 0: 12 12 0    slot 1: 8 12 4    slot 2: 4 12 8           = 72 FMAs per lane
+    A slot is one dependent chain (packed FMA -> reader: 1 wait state, -> DPP source: 2); the three chains are interleaved so
+    that every wait state is another chain's instruction.
+    Low-edge symbols (lanes 52 + 3 e + t, rows of the parked block -- trx_tables.h edge8, unchanged):
+      t = 0, 1: row e, samples [W, W + 12) and [W + 12, W + 24), W = 4 e + c: slot 0 is the main part, 24 FMAs from +0 like
+                any other, and ends in lane 54 + 3 e;
+      t = 2:    row 4 + e = [0, 0, six low taps, sixteen zeros], samples [W - 12, W): stage 0 of slot 1 is
+                sum_{r = 4..11} x[W - 12 + r] row[r - 4] = sum_{u = 0..7} x[W - 8 + u] row[u] -- the low part, u ascending from +0.
+                Slot 1's moves are masked off for lanes 52..63 (EXEC = lanes 0..51 around them), so the sum stays in its lane,
+                and its stages 1 and 2 multiply the zero taps 8..23.
+      Zero taps are bit-safe: the samples are converted int16, hence finite, so x * 0 = +-0; a round-to-nearest sum that starts
+      at +0 is never -0 (+0 + -0 = +0, and a non-zero sum stays non-zero), so fma(x, 0, acc) = acc for every acc that occurs and
+      fma(x, T, acc) behind leading zero taps sees acc = +0, as if it were the first.  The low part is thereby the same FMAs
+      on the same operands as before for u < 8 and no-ops behind; main + low is one add, as before.
+    Registers: six tap quads v96..v111, v124..v127, v120..v123 (the last one behind the first LDS wait: v120..v123 hold the
+    parked rows until the ds_write in front has read them); v117 = the lane's tap row."""
+    Q = [96, 100, 104, 108, 124, 120]
+    for q in range(5):
+        b(f"ds_read_b128 {vreg(Q[q], 4)}, v117 offset:{16 * q}")
+    lds_q = list(range(5))                                         # tap quads outstanding, oldest first (everything older: in front)
+    arrived = set()
+    # per-slot programs
+    prog = []
+    for j in range(3):
+        pj = []
+        for s_ in range(3):
+            for r in range(12):
+                t = 12 * s_ + r - 4 * j
+                if 0 <= t < 24:
+                    pj.append(("fma", r, t))
+            if s_ < 2:
+                pj.append(("mov",))
+        if j == 0:
+            assert pj[-1] == ("mov",)                              # (slot 0: the carry to lane l + 2)
+        else:
+            assert pj[-1][0] == "fma"
+        prog.append(pj)
+    assert sum(1 for pj in prog for i in pj if i[0] == "fma") == 72
+    pos = 0
+    last = [(-10, "mov")] * 3                                      # (position, kind) of the slot's last writer
+    ip = [0, 0, 0]
+    q5_issued = False
+
+    def ready(j):
+        ins = prog[j][ip[j]]
+        gap = pos - last[j][0] - 1
+        if ins[0] == "fma":
+            return gap >= (1 if last[j][1] == "fma" else 0)
+        return gap >= 2
+
+    while any(ip[j] < len(prog[j]) for j in range(3)):
+        cand = [j for j in range(3) if ip[j] < len(prog[j]) and ready(j)]
+        if not cand:
+            b("s_nop 0")
+            pos += 1
+            continue
+        # the chain with the most left first; among equals one whose taps have arrived
+        def key(j):
+            ins = prog[j][ip[j]]
+            there = ins[0] == "mov" or (ins[2] >> 2) in arrived
+            return (there, len(prog[j]) - ip[j])
+        j = max(cand, key=key)
+        ins = prog[j][ip[j]]
+        ip[j] += 1
+        if ins[0] == "fma":
+            _, r, t = ins
+            q = t >> 2
+            if q not in arrived:
+                n = len(lds_q) - 1 - lds_q.index(q)
+                b(f"s_waitcnt lgkmcnt({n})")
+                pos += 1
+                for qq in lds_q[:lds_q.index(q) + 1]:
+                    arrived.add(qq)
+                del lds_q[:len(lds_q) - n]
+                if not q5_issued:
+                    b(f"ds_read_b128 {vreg(Q[5], 4)}, v117 offset:{16 * 5}")
+                    lds_q.append(5)
+                    q5_issued = True
+                    pos += 1
+            hp = vreg(Q[q] + (2 if (t & 2) else 0), 2)
+            sel = "op_sel:[0,1,0] op_sel_hi:[1,1,1]" if (t & 1) else "op_sel:[0,0,0] op_sel_hi:[1,0,1]"
+            a = vreg(ACC[j], 2)
+            b(f"v_pk_fma_f32 {a}, {X(r)}, {hp}, {a} {sel}")
+            last[j] = (pos, "fma")
+            pos += 1
+        else:
+            if j == 1:
+                b(f"s_bfm_b64 exec, {FIRM_LOW_LANE0}, 0")          # the low parts (slot 1 of lanes 52..63) stay where they are
+                pos += 1
+            for c in range(2):
+                b(f"v_mov_b32_dpp v{ACC[j] + c}, v{ACC[j] + c} {DPP_SHR}")
+            pos += 2
+            last[j] = (pos - 1, "mov")
+            if j == 1:
+                b("s_mov_b64 exec, -1")
+                pos += 1
+    b.firm_nops = sum(1 for t in b.ins if t == "s_nop 0")
 
 
 def fir_core(b, ACC, RING, CQ, P, preload):
