@@ -416,7 +416,8 @@ int trxhip_dft_batch(trxhip_ctx *ctx, const float *d_in, float *d_out, int m, si
  * d_out: m * (n_blocks * block_len) complex64, channel-major (outputBuffer(chan), Channelizer.cpp:60-66) */
 int trxhip_channelize_batch(trxhip_ctx *ctx, const int16_t *d_in, float *d_out,
 			    size_t n_blocks, int m, int block_len, int h_len, void *stream);
-/* Resampler(p,q,16)::rotate over a continuous stream per channel: in n_in samples -> out n_in*p/q */
+/* Resampler(p,q,16)::rotate over a continuous stream per channel: in n_in samples -> out n_in*p/q.  (p,q) = (65,48), (1,4) and
+ * RadioInterfaceResamp's receive ratios (65,96) and (52,75) with cutoff 1.0; TRXHIP_ENOTSUP otherwise. */
 int trxhip_resample_batch(trxhip_ctx *ctx, const float *d_in, float *d_out, size_t n_in, int p, int q,
 			  size_t n_chan, size_t in_stride, size_t out_stride, void *stream);
 
@@ -522,9 +523,31 @@ int  trxhip_rx_frontend_reset(trxhip_rx_frontend *f, void *stream);           /*
  * run.  n_blocks_prev = 0 (stream start) is trxhip_rx_frontend_reset(). */
 int  trxhip_rx_frontend_seed(trxhip_rx_frontend *f, const int16_t *d_wide_prev, size_t n_blocks_prev, void *stream);
 /* d_wide: n_blocks * block_len * 4 wideband int16 IQ samples (16-byte aligned);
- * d_out : 4 channels x (n_blocks*block_len*p/q) complex64, channel c at d_out + 2*c*out_stride floats */
+ * d_out : 4 channels x (n_blocks*block_len*p/q) complex64, channel c at d_out + 2*c*out_stride floats.
+ * Objects of trxhip_rx_frontend_create_chans(): d_wide and the rows of d_out as described there. */
 int  trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t n_blocks, float *d_out,
 			     size_t out_stride, void *stream);
+
+/* The receive front end per logical channel: what RadioInterfaceMulti::pullBuffer() and RadioInterfaceResamp::pullBuffer()
+ * (radioInterfaceResamp.cpp:156-193) compute, and nothing else.  trxhip_rx_frontend_create() and every object it makes keep
+ * their behaviour (four rows, physical order); _destroy, _reset, _seed and _pull accept both kinds of object.
+ * MULTI : chans 1..3 logical channels.  pullBuffer() skips the inactive filterbank paths and writes recvBuffer[lchan]
+ *         (:237-314); the active paths and their order are radioInterfaceMulti.cpp:92-124, :214-231 -- 1 chan: lchan 0 <- path 0;
+ *         2: 0 <- 0, 1 <- 3; 3: 0 <- 1, 1 <- 0, 2 <- 3.  d_wide as above; _pull writes chans rows, logical channel l at
+ *         d_out + 2*l*out_stride floats.  Nothing is computed or stored for an inactive path; row l is bit-identical to row
+ *         pchan(l) of a four-row object fed the same stream, under any chunking.
+ * RESAMP: chans == 1.  d_wide is n_blocks*block_len int16 IQ samples of the one channel (4-byte aligned), block_len the
+ *         device-side chunk (1536 for (65,96), 1200 for (52,75) at 4 SPS); convert_short_float, then Resampler(p, q, 16) with
+ *         Resampler::init()'s default cutoff 1.0 (Resampler.h:44); one row of n_blocks*block_len/q*p samples.  The object carries
+ *         dnsampler->len() = 16 input samples between calls (:146-147, :191), zero at a fresh or reset object; _seed takes the
+ *         preceding blocks in this layout.
+ * Refused with TRXHIP_EINVAL: no context or no `out`, an unknown mode, chans outside 1..3 (MULTI) or != 1 (RESAMP),
+ * block_len < 16, p outside 1..128, q outside 1..3072, block_len % q != 0, q * ceil(256 / p) > 3072. */
+#define TRXHIP_RXFE_MULTI  0   /* RadioInterfaceMulti::pullBuffer: Channelizer(4) + Resampler(p,q) on the active paths */
+#define TRXHIP_RXFE_RESAMP 1   /* RadioInterfaceResamp::pullBuffer: convert_short_float + Resampler(p,q), chans == 1 */
+int trxhip_rx_frontend_create_chans(trxhip_ctx *ctx, int mode, int chans, int block_len, int p, int q,
+                                    trxhip_rx_frontend **out);
+int trxhip_rx_frontend_rows(const trxhip_rx_frontend *f);   /* rows pull() writes: 4 for trxhip_rx_frontend_create() objects */
 
 /* ---- streaming transmit front end: RadioInterfaceMulti::pushBuffer() (radioInterfaceMulti.cpp:316-362) and
  * RadioInterfaceResamp::pushBuffer() (radioInterfaceResamp.cpp:196-230) ----

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "../../include/trxhip.h"
 #include "trx_tables.h"
@@ -168,6 +169,8 @@ void trxhip_destroy(trxhip_ctx *ctx)
 		if (ctx->d_tables) (void)hipFree(ctx->d_tables);
 		if (ctx->d_pool) (void)hipFree(ctx->d_pool);
 		if (ctx->d_tx_tables) (void)hipFree(ctx->d_tx_tables);
+		for (float *t : ctx->d_rs_resamp)
+			if (t) (void)hipFree(t);
 		ctx->redo.destroy();
 	}
 	delete ctx;
@@ -609,31 +612,53 @@ int trxhip_resample_batch(trxhip_ctx *ctx, const float *d_in, float *d_out, size
 {
 	if (!ctx || !d_in || !d_out)
 		return TRXHIP_EINVAL;
-	if (!((p == 65 && q == 48) || (p == 1 && q == 4)))
-		return TRXHIP_ENOTSUP;                 /* Resampler(65,48) radioInterfaceMulti.cpp:35-36; (1,4) sigProcLib.cpp:2161 */
+	const int resamp = (p == 65 && q == 96) ? 0 : ((p == 52 && q == 75) ? 1 : -1);
+	if (!((p == 65 && q == 48) || (p == 1 && q == 4) || resamp >= 0))
+		return TRXHIP_ENOTSUP;                 /* Resampler(65,48) radioInterfaceMulti.cpp:35-36; (1,4) sigProcLib.cpp:2161;
+		                                        * (65,96) and (52,75) radioInterfaceResamp.cpp:36-41 */
 	if (n_in % q)
 		return TRXHIP_EINVAL;                  /* Resampler.cpp:100-104 */
 	if (with_device(ctx))
 		return TRXHIP_EIO;
-	const float *parts = (p == 65) ? &ctx->d_tables->rs6548_taps[0][0] : &ctx->d_tables->dec_taps[0];
+	const float *parts = (p == 65 && q == 48) ? &ctx->d_tables->rs6548_taps[0][0] : &ctx->d_tables->dec_taps[0];
+	if (resamp >= 0) {
+		std::lock_guard<std::mutex> lock(ctx->rs_mu);
+		if (!ctx->d_rs_resamp[resamp]) {
+			std::vector<float> taps((size_t)p * 16);
+			trx_polyphase_taps((unsigned)p, (unsigned)q, 16, 1.0f, taps.data());
+			float *d = nullptr;
+			if (hipMalloc((void **)&d, taps.size() * sizeof(float)) != hipSuccess)
+				return TRXHIP_ENOMEM;
+			if (hipMemcpy(d, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+				(void)hipFree(d);
+				return TRXHIP_EIO;
+			}
+			ctx->d_rs_resamp[resamp] = d;
+		}
+		parts = ctx->d_rs_resamp[resamp];
+	}
 	return trx_launch_resample(d_in, d_out, n_in, p, q, n_chan, in_stride, out_stride, parts, nullptr,
 				   static_cast<hipStream_t>(stream));
 }
 
-/* ---- streaming Rx front end: RadioInterfaceMulti::pullBuffer (radioInterfaceMulti.cpp:237-314) ---- */
+/* ---- streaming Rx front end: RadioInterfaceMulti::pullBuffer (radioInterfaceMulti.cpp:237-314) and
+ *      RadioInterfaceResamp::pullBuffer (radioInterfaceResamp.cpp:156-193) ---- */
+enum { RXFE_FOUR_ROWS = -1 };    /* trxhip_rx_frontend_create(): all four filterbank channels in physical order */
 struct trxhip_rx_frontend {
 	trxhip_ctx *ctx;
+	int mode;                /* RXFE_FOUR_ROWS, TRXHIP_RXFE_MULTI or TRXHIP_RXFE_RESAMP */
+	int rows;                /* rows pull() writes: 4, chans, 1 */
 	int block_len, p, q;
 	float *d_parts;          /* [p][16] resampler partitions */
-	void *d_wide_hist;       /* 15 time steps x 4 int16 IQ samples */
-	void *d_chan_hist;       /* [2][4][16] complex64: the fused kernel reads one half and leaves the other (its first and its
-	                          * last workgroup run at the same time) */
+	void *d_wide_hist;       /* 15 time steps x 4 int16 IQ samples; RESAMP: [2][16] int16 IQ samples, halves as d_chan_hist's */
+	void *d_chan_hist;       /* [2][4][16] complex64 ([2][rows][16] by logical channel in a MULTI object): the fused kernel reads
+	                          * one half and leaves the other (its first and its last workgroup run at the same time) */
 	int hist_cur;
 	float *d_chan;           /* [4][cap] channelizer output scratch */
 	size_t cap;
 };
 
-int trxhip_rx_frontend_create(trxhip_ctx *ctx, int block_len, int p, int q, trxhip_rx_frontend **out)
+static int rxfe_create(trxhip_ctx *ctx, int mode, int rows, int block_len, int p, int q, trxhip_rx_frontend **out)
 {
 	if (!ctx || !out || block_len < 16 || p < 1 || q < 1 || p > 128 || q > 3072 || (block_len % q) != 0)
 		return TRXHIP_EINVAL;                  /* Resampler::rotate needs whole q-sample groups per block (Resampler.cpp:100-112) */
@@ -642,7 +667,8 @@ int trxhip_rx_frontend_create(trxhip_ctx *ctx, int block_len, int p, int q, trxh
 	trxhip_rx_frontend *f = new (std::nothrow) trxhip_rx_frontend();
 	if (!f)
 		return TRXHIP_ENOMEM;
-	f->ctx = ctx; f->block_len = block_len; f->p = p; f->q = q; f->d_chan = nullptr; f->cap = 0; f->hist_cur = 0;
+	f->ctx = ctx; f->mode = mode; f->rows = rows;
+	f->block_len = block_len; f->p = p; f->q = q; f->d_chan = nullptr; f->cap = 0; f->hist_cur = 0;
 	float *taps = static_cast<float *>(malloc((size_t)p * 16 * sizeof(float)));
 	if (!taps) { delete f; return TRXHIP_ENOMEM; }
 	trx_polyphase_taps((unsigned)p, (unsigned)q, 16, 1.0f, taps);
@@ -654,6 +680,27 @@ int trxhip_rx_frontend_create(trxhip_ctx *ctx, int block_len, int p, int q, trxh
 	if (!ok) { trxhip_rx_frontend_destroy(f); return TRXHIP_ENOMEM; }
 	*out = f;
 	return TRXHIP_OK;
+}
+
+int trxhip_rx_frontend_create(trxhip_ctx *ctx, int block_len, int p, int q, trxhip_rx_frontend **out)
+{
+	return rxfe_create(ctx, RXFE_FOUR_ROWS, 4, block_len, p, q, out);
+}
+
+int trxhip_rx_frontend_create_chans(trxhip_ctx *ctx, int mode, int chans, int block_len, int p, int q, trxhip_rx_frontend **out)
+{
+	if (!ctx || !out || (mode != TRXHIP_RXFE_MULTI && mode != TRXHIP_RXFE_RESAMP))
+		return TRXHIP_EINVAL;
+	if (mode == TRXHIP_RXFE_MULTI ? (chans < 1 || chans > 3) : chans != 1)
+		return TRXHIP_EINVAL;
+	if (p >= 1 && p <= 128 && (long long)q * ((256 + p - 1) / p) > 3072)
+		return TRXHIP_EINVAL;                  /* the resampler kernels' tile */
+	return rxfe_create(ctx, mode, chans, block_len, p, q, out);
+}
+
+int trxhip_rx_frontend_rows(const trxhip_rx_frontend *f)
+{
+	return f ? f->rows : TRXHIP_EINVAL;
 }
 
 void trxhip_rx_frontend_destroy(trxhip_rx_frontend *f)
@@ -692,7 +739,7 @@ int trxhip_rx_frontend_seed(trxhip_rx_frontend *f, const int16_t *d_wide_prev, s
 	 * d_wide_hist / d_chan_hist is the state of a stream processed up to here */
 	const size_t n_out = n_blocks_prev * (size_t)f->block_len / f->q * f->p;
 	float *scratch = nullptr;
-	if (hipMalloc((void **)&scratch, 4 * n_out * 8) != hipSuccess)
+	if (hipMalloc((void **)&scratch, (size_t)f->rows * n_out * 8) != hipSuccess)
 		return TRXHIP_ENOMEM;
 	rc = trxhip_rx_frontend_pull(f, d_wide_prev, n_blocks_prev, scratch, n_out, stream);
 	if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess && rc == TRXHIP_OK)
@@ -701,11 +748,48 @@ int trxhip_rx_frontend_seed(trxhip_rx_frontend *f, const int16_t *d_wide_prev, s
 	return rc;
 }
 
+static int rxfe_scratch(trxhip_rx_frontend *f, size_t n_total)
+{
+	if (n_total <= f->cap)
+		return TRXHIP_OK;
+	if (f->d_chan) (void)hipFree(f->d_chan);
+	f->d_chan = nullptr;
+	if (hipMalloc((void **)&f->d_chan, 4 * n_total * 8) != hipSuccess) { f->cap = 0; return TRXHIP_ENOMEM; }
+	f->cap = n_total;
+	return TRXHIP_OK;
+}
+
+/* a MULTI object: the active filterbank paths only, row l = logical channel l (radioInterfaceMulti.cpp:92-124, :214-231) */
+static int rxfe_pull_chans(trxhip_rx_frontend *f, const int16_t *d_wide, size_t n_total, float *d_out, size_t out_stride, hipStream_t s)
+{
+	const size_t half = (size_t)f->rows * 16 * 8;
+	char *const hist = static_cast<char *>(f->d_chan_hist);
+	char *const hist_in = hist + (size_t)f->hist_cur * half, *const hist_out = hist + (size_t)(f->hist_cur ^ 1) * half;
+	/* one pass (trx_rx_frontend.hip, rx_frontend_chans_kernel) ... */
+	int rc = trx_launch_rx_frontend_chans(d_wide, d_out, n_total, f->rows, f->p, f->q, out_stride, f->d_parts, f->ctx->d_tables,
+					      f->d_wide_hist, hist_in, hist_out, s);
+	if (rc == 0)
+		f->hist_cur ^= 1;
+	if (rc != 1)
+		return rc;
+	/* ... or, for a geometry that fits no tile, the channelizer into scratch and the resampler on the active rows */
+	if ((rc = rxfe_scratch(f, n_total)) != TRXHIP_OK)
+		return rc;
+	rc = trx_launch_channelize(d_wide, f->d_chan, n_total, f->cap, f->ctx->d_tables, f->d_wide_hist, s);
+	static const int pchan_of[3][3] = { { 0, -1, -1 }, { 0, 3, -1 }, { 1, 0, 3 } };
+	for (int l = 0; l < f->rows && rc == TRXHIP_OK; l++)
+		rc = trx_launch_resample(f->d_chan + 2 * (size_t)pchan_of[f->rows - 1][l] * f->cap, d_out + 2 * (size_t)l * out_stride, n_total,
+					 f->p, f->q, 1, f->cap, out_stride, f->d_parts, hist_in + (size_t)l * 16 * 8, s);
+	return rc;
+}
+
 int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t n_blocks, float *d_out,
 			    size_t out_stride, void *stream)
 {
-	if (!f || !d_wide || !d_out || (reinterpret_cast<uintptr_t>(d_wide) & 15) != 0)
+	if (!f || !d_wide || !d_out)
 		return TRXHIP_EINVAL;
+	if ((reinterpret_cast<uintptr_t>(d_wide) & (f->mode == TRXHIP_RXFE_RESAMP ? 3 : 15)) != 0)
+		return TRXHIP_EINVAL;                  /* one 16-byte load per wideband time step; RESAMP: one 4-byte sample */
 	if (n_blocks == 0)
 		return TRXHIP_OK;
 	if (with_device(f->ctx))
@@ -714,6 +798,18 @@ int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t
 	if (out_stride < n_total / f->q * f->p)
 		return TRXHIP_EINVAL;
 	hipStream_t s = static_cast<hipStream_t>(stream);
+	if (f->mode == TRXHIP_RXFE_RESAMP) {
+		/* int16 in, one row out (trx_rx_frontend.hip, rx_resamp_s16_kernel); the kernel reads one half of the carried samples
+		 * and leaves the other */
+		char *const sh = static_cast<char *>(f->d_wide_hist);
+		const int rc = trx_launch_rx_resamp_s16(d_wide, d_out, n_total, f->p, f->q, f->d_parts, sh + (size_t)f->hist_cur * 64,
+							sh + (size_t)(f->hist_cur ^ 1) * 64, s);
+		if (rc == 0)
+			f->hist_cur ^= 1;
+		return rc;
+	}
+	if (f->mode == TRXHIP_RXFE_MULTI)
+		return rxfe_pull_chans(f, d_wide, n_total, d_out, out_stride, s);
 	char *const hist = static_cast<char *>(f->d_chan_hist);
 	void *const hist_in = hist + (size_t)f->hist_cur * 4 * 16 * 8, *const hist_out = hist + (size_t)(f->hist_cur ^ 1) * 4 * 16 * 8;
 	/* one pass, the channel-rate streams stay on the chip (trx_aux_kernels.hip, frontend_fused_kernel) ... */

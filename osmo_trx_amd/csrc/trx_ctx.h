@@ -124,6 +124,10 @@ struct trxhip_ctx {
 	double tx_full_scale = 0.0;
 	bool tx_att_valid = false;
 	float tx_att_scale[256];
+	/* trxhip_resample_batch(): the partitions [p][16] of RadioInterfaceResamp's receive ratios (65, 96) and (52, 75), cutoff 1.0,
+	 * uploaded on first use */
+	std::mutex rs_mu;
+	float *d_rs_resamp[2] = { nullptr, nullptr };
 };
 
 static inline int with_device(const trxhip_ctx *ctx)

@@ -74,6 +74,17 @@ int trx_launch_delay_vector(const float *d_in, float *d_out, const float *d_dela
 int trx_launch_scale_vector(float *d_x, size_t len, float sr, float si, hipStream_t stream);
 int trx_launch_vector_slicer(float *d_dst, const float *d_src, size_t len, hipStream_t stream);
 
+/* ---- trx_rx_frontend.hip: the receive front end per logical channel ----
+ * trx_launch_rx_frontend_chans: trx_launch_frontend_fused for chans = 1..3 logical channels (row l of d_out = logical channel
+ * l; the channel histories are [chans][16]); returns 1 when the geometry fits no tile.
+ * trx_launch_rx_resamp_s16: convert_short_float + Resampler(p, q, 16)::rotate of one int16 channel; d_hist_in / d_hist_out:
+ * 16 int16 IQ samples each, the samples -16 .. -1 of this call and of the next */
+int trx_launch_rx_frontend_chans(const int16_t *d_wide, float *d_out, size_t n_total, int chans, int p, int q, size_t out_stride,
+				 const float *parts, const trx_tables *d_tab, void *d_wide_hist_io, const void *d_chan_hist_in,
+				 void *d_chan_hist_out, hipStream_t stream);
+int trx_launch_rx_resamp_s16(const int16_t *d_in, float *d_out, size_t n_in, int p, int q, const float *parts,
+			     const void *d_hist_in, void *d_hist_out, hipStream_t stream);
+
 /* ---- trx_tx_frontend.hip: Synthesis(4, ., 16) and the fused multi-ARFCN transmit front end ----
  * d_hist of trx_launch_synthesize: NULL (zero history) or the 4 rows' samples -15 .. -1 at [c * 16 + 0 .. 14] */
 int trx_launch_synthesize(const float *d_in, size_t in_stride, const void *d_hist, float *d_out_cf32, int16_t *d_out_s16,

@@ -41,7 +41,9 @@ bool MultiArfcnRx::init()
 	if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
 		return false;
 	stream_ = s;
-	return trxhip_rx_frontend_create(trxsigproc_context(), (int)block_len_, p_, q_, &fe_) == TRXHIP_OK;
+	/* the active filterbank paths only, rows by logical channel (radioInterfaceMulti.cpp:237-314) */
+	return trxhip_rx_frontend_create_chans(trxsigproc_context(), TRXHIP_RXFE_MULTI, (int)chans_, (int)block_len_, p_, q_, &fe_) ==
+	       TRXHIP_OK;
 }
 
 int MultiArfcnRx::pullBuffer(const int16_t *wide, size_t n_blocks, std::vector<std::vector<complex> > &out)
@@ -57,7 +59,7 @@ int MultiArfcnRx::pullBuffer(const int16_t *wide, size_t n_blocks, std::vector<s
 		if (d_wide_) hipFree(d_wide_);
 		if (d_out_) hipFree(d_out_);
 		d_wide_ = d_out_ = nullptr;
-		if (hipMalloc(&d_wide_, n_wide * 4) != hipSuccess || hipMalloc(&d_out_, MCHANS * n_out * 8) != hipSuccess) {
+		if (hipMalloc(&d_wide_, n_wide * 4) != hipSuccess || hipMalloc(&d_out_, chans_ * n_out * 8) != hipSuccess) {
 			cap_blocks_ = 0;
 			return -EIO;
 		}
@@ -67,14 +69,11 @@ int MultiArfcnRx::pullBuffer(const int16_t *wide, size_t n_blocks, std::vector<s
 	    trxhip_rx_frontend_pull(fe_, static_cast<const int16_t *>(d_wide_), n_blocks, static_cast<float *>(d_out_), n_out, s) != TRXHIP_OK)
 		return -EIO;
 	out.resize(chans_);
-	for (size_t pchan = 0; pchan < MCHANS; pchan++) {
-		const int lchan = getLogicalChan(pchan, chans_);
-		if (lchan < 0)
-			continue;
+	for (size_t lchan = 0; lchan < chans_; lchan++) {
 		std::vector<complex> &dst = out[lchan];
 		const size_t old = dst.size();
 		dst.resize(old + n_out);
-		if (hipMemcpyAsync(&dst[old], static_cast<const char *>(d_out_) + pchan * n_out * 8, n_out * 8,
+		if (hipMemcpyAsync(&dst[old], static_cast<const char *>(d_out_) + lchan * n_out * 8, n_out * 8,
 				   hipMemcpyDeviceToHost, s) != hipSuccess)
 			return -EIO;
 	}

@@ -7,6 +7,7 @@
 //   sigproc_selftest va <cfile> <tsc> <out.f32>
 //   sigproc_selftest sch <cfile> <0 full | 1 narrow | 2 buffer> <out.txt>
 //   sigproc_selftest batch <iq.s16> <params.bin> <n> <sps> <burst_len> <out_results.bin> <out_soft.bin>
+//   sigproc_selftest resamp_rx <in.s16> <n_chunks> <chunk_len> <p> <q> <out.cf32>
 //   sigproc_selftest pullrv <iq.s16> <params.bin> <n> <chans> <muted_chan | -1> <exact 0|1> <out.bin>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +22,7 @@
 #include "trxBatch.h"
 #include "trxPullRadioVector.h"
 #include "MultiArfcnRx.h"
+#include "ResampRx.h"
 #include "MultiArfcnTx.h"
 
 // "signalvector is owning despite claiming not to" (Transceiver.cpp:648-654): a vector built over memory it must not
@@ -470,6 +472,27 @@ int main(int argc, char **argv)
 			fwrite(out[l].data(), sizeof(complex), out[l].size(), f);
 			fclose(f);
 		}
+		sigProcLibDestroy();
+		return 0;
+	}
+	// resamp_rx <in.s16> <n_chunks> <chunk_len> <p> <q> <out.cf32>: ResampRx::pullBuffer in runs of 1, 2, 3, ... chunks
+	if (!strcmp(argv[1], "resamp_rx") && argc == 8) {
+		std::vector<char> raw = slurp(argv[2]);
+		const size_t n_chunks = atol(argv[3]), chunk_len = atol(argv[4]);
+		ResampRx rx(chunk_len, atoi(argv[5]), atoi(argv[6]));
+		if (!rx.init()) { fprintf(stderr, "ResampRx::init failed\n"); return 5; }
+		std::vector<complex> out;
+		const int16_t *w = reinterpret_cast<const int16_t *>(raw.data());
+		size_t pos = 0, step = 1;
+		while (pos < n_chunks) {
+			const size_t nc = step < n_chunks - pos ? step : n_chunks - pos;
+			if (rx.pullBuffer(w + pos * chunk_len * 2, nc, out)) { fprintf(stderr, "pullBuffer failed\n"); return 6; }
+			pos += nc;
+			step++;
+		}
+		FILE *f = fopen(argv[7], "wb");
+		fwrite(out.data(), sizeof(complex), out.size(), f);
+		fclose(f);
 		sigProcLibDestroy();
 		return 0;
 	}

@@ -111,6 +111,8 @@ SYMBOLS = {
     "trxhip_tx_tables_size": (_SZ, []),
     "trxhip_tx_tables_generate_host": (_I, [_VP, _SZ]),
     "trxhip_rx_frontend_create": (_I, [_VP, _I, _I, _I, C.POINTER(_VP)]),
+    "trxhip_rx_frontend_create_chans": (_I, [_VP, _I, _I, _I, _I, _I, C.POINTER(_VP)]),
+    "trxhip_rx_frontend_rows": (_I, [_VP]),
     "trxhip_rx_frontend_destroy": (None, [_VP]),
     "trxhip_rx_frontend_reset": (_I, [_VP, _VP]),
     "trxhip_rx_frontend_seed": (_I, [_VP, _VP, _SZ, _VP]),
@@ -523,15 +525,31 @@ class TrxHip:
         return out
 
 
-class RxFrontEnd:
-    """Streaming Channelizer(4, block_len, 16) + Resampler(p, q, 16) with carried history (trxhip_rx_frontend_*)."""
+RXFE_MULTI, RXFE_RESAMP = 0, 1                      # TRXHIP_RXFE_*
+RXFE_PCHAN = {1: (0,), 2: (0, 3), 3: (1, 0, 3)}     # filterbank path of logical channel l (radioInterfaceMulti.cpp:92-124)
 
-    def __init__(self, trx, block_len=192, p=65, q=48):
+
+class RxFrontEnd:
+    """Streaming receive front end with carried history (trxhip_rx_frontend_*).  chans=None: Channelizer(4, block_len, 16) +
+    Resampler(p, q, 16) on all four filterbank channels, rows in physical order.  chans=1..3, mode "multi":
+    RadioInterfaceMulti::pullBuffer, the active paths only, row l = logical channel l.  chans=1, mode "resamp":
+    RadioInterfaceResamp::pullBuffer, int16 samples of one channel -> convert_short_float + Resampler(p, q, 16)."""
+
+    def __init__(self, trx, block_len=192, p=65, q=48, chans=None, mode="multi"):
         self.trx = trx
         self.block_len, self.p, self.q = block_len, p, q
+        self.chans = chans
+        self.mode = {"multi": RXFE_MULTI, "resamp": RXFE_RESAMP}[mode]
         h = _VP()
-        _check(trx.L.trxhip_rx_frontend_create(trx.h, block_len, p, q, C.byref(h)), "trxhip_rx_frontend_create")
+        if chans is None:
+            if self.mode != RXFE_MULTI:
+                raise ValueError('mode "resamp" needs chans=1')
+            _check(trx.L.trxhip_rx_frontend_create(trx.h, block_len, p, q, C.byref(h)), "trxhip_rx_frontend_create")
+        else:
+            _check(trx.L.trxhip_rx_frontend_create_chans(trx.h, self.mode, chans, block_len, p, q, C.byref(h)),
+                   "trxhip_rx_frontend_create_chans")
         self.h = h
+        self.rows = trx.L.trxhip_rx_frontend_rows(h)
 
     def reset(self, stream=None):
         _check(self.trx.L.trxhip_rx_frontend_reset(self.h, self.trx._stream(stream)), "trxhip_rx_frontend_reset")
@@ -542,13 +560,14 @@ class RxFrontEnd:
         _check(self.trx.L.trxhip_rx_frontend_seed(self.h, ptr, n_blocks_prev, self.trx._stream(stream)), "trxhip_rx_frontend_seed")
 
     def pull(self, wide_iq, n_blocks, stream=None, out=None):
-        """wide_iq: int16[n_blocks*block_len*4, 2] -> complex64[4, n_blocks*block_len*p/q] (written into `out` when given)"""
+        """wide_iq: int16[n_blocks*block_len*4, 2] (mode "resamp": int16[n_blocks*block_len, 2]) -> complex64[rows,
+        n_blocks*block_len*p/q] (written into `out` when given)"""
         torch = self.trx.torch
         n_out = n_blocks * self.block_len // self.q * self.p
         if out is None:
-            out = torch.empty((4, n_out), dtype=torch.complex64, device=wide_iq.device)
-        elif tuple(out.shape) != (4, n_out) or out.dtype != torch.complex64 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous complex64[4, n_out] tensor")
+            out = torch.empty((self.rows, n_out), dtype=torch.complex64, device=wide_iq.device)
+        elif tuple(out.shape) != (self.rows, n_out) or out.dtype != torch.complex64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous complex64[%d, n_out] tensor" % self.rows)
         _check(self.trx.L.trxhip_rx_frontend_pull(self.h, self.trx._dev(wide_iq, torch.int16), n_blocks, self.trx._dev(out),
                                                   n_out, self.trx._stream(stream)), "trxhip_rx_frontend_pull")
         return out
