@@ -1,7 +1,7 @@
 """osmo_trx_amd -- MI355X (gfx950) receive-side burst DSP for osmo-trx.
 
 The product is the HIP library osmo_trx_amd/lib/libtrxhip.so behind the C ABI of include/trxhip.h
-(kernels: csrc/trx_kernels.hip, csrc/trx_aux_kernels.hip) plus the C++ host shim that keeps the
+(kernels: csrc/trx_kernels.hip, csrc/trx_aux_kernels.hip, csrc/trx_rx_frontend.hip, ...) plus the C++ host shim that keeps the
 reference's sigProcLib.h signatures (host/).  This Python package is plumbing only: a ctypes
 binding that hands torch device pointers to the C ABI (trxhip.py), the synthetic workload
 generator (synth.py), batch sharding + RCCL table broadcast (shard.py) and the build driver

@@ -759,30 +759,6 @@ static int rxfe_scratch(trxhip_rx_frontend *f, size_t n_total)
 	return TRXHIP_OK;
 }
 
-/* a MULTI object: the active filterbank paths only, row l = logical channel l (radioInterfaceMulti.cpp:92-124, :214-231) */
-static int rxfe_pull_chans(trxhip_rx_frontend *f, const int16_t *d_wide, size_t n_total, float *d_out, size_t out_stride, hipStream_t s)
-{
-	const size_t half = (size_t)f->rows * 16 * 8;
-	char *const hist = static_cast<char *>(f->d_chan_hist);
-	char *const hist_in = hist + (size_t)f->hist_cur * half, *const hist_out = hist + (size_t)(f->hist_cur ^ 1) * half;
-	/* one pass (trx_rx_frontend.hip, rx_frontend_chans_kernel) ... */
-	int rc = trx_launch_rx_frontend_chans(d_wide, d_out, n_total, f->rows, f->p, f->q, out_stride, f->d_parts, f->ctx->d_tables,
-					      f->d_wide_hist, hist_in, hist_out, s);
-	if (rc == 0)
-		f->hist_cur ^= 1;
-	if (rc != 1)
-		return rc;
-	/* ... or, for a geometry that fits no tile, the channelizer into scratch and the resampler on the active rows */
-	if ((rc = rxfe_scratch(f, n_total)) != TRXHIP_OK)
-		return rc;
-	rc = trx_launch_channelize(d_wide, f->d_chan, n_total, f->cap, f->ctx->d_tables, f->d_wide_hist, s);
-	static const int pchan_of[3][3] = { { 0, -1, -1 }, { 0, 3, -1 }, { 1, 0, 3 } };
-	for (int l = 0; l < f->rows && rc == TRXHIP_OK; l++)
-		rc = trx_launch_resample(f->d_chan + 2 * (size_t)pchan_of[f->rows - 1][l] * f->cap, d_out + 2 * (size_t)l * out_stride, n_total,
-					 f->p, f->q, 1, f->cap, out_stride, f->d_parts, hist_in + (size_t)l * 16 * 8, s);
-	return rc;
-}
-
 int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t n_blocks, float *d_out,
 			    size_t out_stride, void *stream)
 {
@@ -808,28 +784,27 @@ int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t
 			f->hist_cur ^= 1;
 		return rc;
 	}
-	if (f->mode == TRXHIP_RXFE_MULTI)
-		return rxfe_pull_chans(f, d_wide, n_total, d_out, out_stride, s);
+	/* the four-row object: rows = the filterbank paths; a MULTI object: the active paths only, row l = logical channel l */
+	const size_t half = (size_t)f->rows * 16 * 8;
 	char *const hist = static_cast<char *>(f->d_chan_hist);
-	void *const hist_in = hist + (size_t)f->hist_cur * 4 * 16 * 8, *const hist_out = hist + (size_t)(f->hist_cur ^ 1) * 4 * 16 * 8;
-	/* one pass, the channel-rate streams stay on the chip (trx_aux_kernels.hip, frontend_fused_kernel) ... */
-	int rc = trx_launch_frontend_fused(d_wide, d_out, n_total, f->p, f->q, out_stride, f->d_parts, f->ctx->d_tables,
+	char *const hist_in = hist + (size_t)f->hist_cur * half, *const hist_out = hist + (size_t)(f->hist_cur ^ 1) * half;
+	/* one pass, the channel-rate streams stay on the chip (trx_rx_frontend.hip, frontend_fused_kernel<rows>) ... */
+	int rc = trx_launch_frontend_fused(d_wide, d_out, n_total, f->rows, f->p, f->q, out_stride, f->d_parts, f->ctx->d_tables,
 					   f->d_wide_hist, hist_in, hist_out, s);
 	if (rc == 0)
 		f->hist_cur ^= 1;
 	if (rc != 1)
 		return rc;
-	/* ... or, for a geometry that does not fit its tiles, the two kernels with the channel streams in a scratch buffer */
-	if (n_total > f->cap) {
-		if (f->d_chan) (void)hipFree(f->d_chan);
-		f->d_chan = nullptr;
-		if (hipMalloc((void **)&f->d_chan, 4 * n_total * 8) != hipSuccess) { f->cap = 0; return TRXHIP_ENOMEM; }
-		f->cap = n_total;
-	}
-	rc = trx_launch_channelize(d_wide, f->d_chan, n_total, f->cap, f->ctx->d_tables, f->d_wide_hist, s);
-	if (rc)
+	/* ... or, for a geometry that fits no tile, the two kernels with the channel streams in a scratch buffer */
+	if ((rc = rxfe_scratch(f, n_total)) != TRXHIP_OK)
 		return rc;
-	return trx_launch_resample(f->d_chan, d_out, n_total, f->p, f->q, 4, f->cap, out_stride, f->d_parts, hist_in, s);
+	rc = trx_launch_channelize(d_wide, f->d_chan, n_total, f->cap, f->ctx->d_tables, f->d_wide_hist, s);
+	if (f->mode == RXFE_FOUR_ROWS)
+		return rc ? rc : trx_launch_resample(f->d_chan, d_out, n_total, f->p, f->q, 4, f->cap, out_stride, f->d_parts, hist_in, s);
+	for (int l = 0; l < f->rows && rc == TRXHIP_OK; l++)
+		rc = trx_launch_resample(f->d_chan + 2 * (size_t)trx_arfcn_pchan(f->rows, l) * f->cap, d_out + 2 * (size_t)l * out_stride,
+					 n_total, f->p, f->q, 1, f->cap, out_stride, f->d_parts, hist_in + (size_t)l * 16 * 8, s);
+	return rc;
 }
 
 
@@ -1019,10 +994,8 @@ int trxhip_tx_frontend_push(trxhip_tx_frontend *f, const float *d_in, size_t in_
 	/* a geometry that does not fit the fused kernel's tiles: the resampler into channel-rate rows, then the synthesis bank */
 	if ((rc = txfe_scratch(f, n_times, s)) != TRXHIP_OK)
 		return rc;
-	static const int pchan_of[3][3] = { { 0, -1, -1 }, { 0, 3, -1 }, { 0, 1, 3 } };
-	static const int lchan_of[3][3] = { { 0, -1, -1 }, { 0, 1, -1 }, { 1, 0, 2 } };   /* radioInterfaceMulti.cpp:92-124 */
-	for (int c = 0; c < f->chans; c++) {
-		const int pc = pchan_of[f->chans - 1][c], l = lchan_of[f->chans - 1][c];
+	for (int l = 0; l < f->chans; l++) {
+		const int pc = trx_arfcn_pchan(f->chans, l);
 		rc = trx_launch_resample(d_in + 2 * (size_t)l * in_stride, f->d_scratch + 2 * (size_t)pc * f->cap, n_in, f->p, f->q, 1,
 					 in_stride, f->cap, f->d_parts, static_cast<char *>(f->d_rs_hist) + (size_t)l * 16 * 8, s);
 		if (rc)

@@ -9,6 +9,13 @@
 #include "trx_tables.h"
 #include "trx_tx_tables.h"
 
+/* RadioInterfaceMulti's ARFCN map (radioInterfaceMulti.cpp:92-124, :214-231): the filterbank path (0..3) of logical channel l
+ * with `rows` = 1..3 logical channels; rows = 4 names the four paths themselves (the four-row receive object) */
+constexpr int trx_arfcn_pchan(int rows, int l)
+{
+	return rows == 4 ? l : (rows == 1 ? 0 : (rows == 2 ? (l == 0 ? 0 : 3) : (l == 0 ? 1 : (l == 1 ? 0 : 3))));
+}
+
 extern "C" {
 
 /* ---- trxhip_detect_demod_batch() and friends: trx_capi.cpp's pull_common() makes every choice, these only launch it ---- */
@@ -57,13 +64,6 @@ int trx_launch_convert_short_float(float *d_out, const int16_t *d_in, size_t len
 int trx_launch_convert_float_short(int16_t *d_out, const float *d_in, float scale, size_t len, hipStream_t stream);
 int trx_launch_dft_strided(const float *d_in, float *d_out, int m, size_t howmany, size_t istride, size_t ostride, int reverse,
 			   hipStream_t stream);
-int trx_launch_frontend_fused(const int16_t *d_wide, float *d_out, size_t n_total, int p, int q, size_t out_stride,
-			      const float *parts, const trx_tables *d_tab, void *d_wide_hist_io, const void *d_chan_hist_in,
-			      void *d_chan_hist_out, hipStream_t stream);
-int trx_launch_channelize(const int16_t *d_in, float *d_out, size_t n_total, size_t out_stride, const trx_tables *d_tab,
-			  void *d_hist_io, hipStream_t stream);
-int trx_launch_resample(const float *d_in, float *d_out, size_t n_in, int p, int q, size_t n_chan, size_t in_stride,
-			size_t out_stride, const float *d_parts, void *d_hist_io, hipStream_t stream);
 int trx_launch_energy_detect(const float *d_x, size_t n_bursts, int burst_len, unsigned window, float *d_out, hipStream_t stream);
 int trx_launch_diversity_select(const int16_t *d_iq_paths, size_t n_bursts, int n_paths, int burst_len, int sps, int16_t *d_iq_sel,
 				float *d_avg_energy, uint8_t *d_path, hipStream_t stream);
@@ -74,14 +74,21 @@ int trx_launch_delay_vector(const float *d_in, float *d_out, const float *d_dela
 int trx_launch_scale_vector(float *d_x, size_t len, float sr, float si, hipStream_t stream);
 int trx_launch_vector_slicer(float *d_dst, const float *d_src, size_t len, hipStream_t stream);
 
-/* ---- trx_rx_frontend.hip: the receive front end per logical channel ----
- * trx_launch_rx_frontend_chans: trx_launch_frontend_fused for chans = 1..3 logical channels (row l of d_out = logical channel
- * l; the channel histories are [chans][16]); returns 1 when the geometry fits no tile.
+/* ---- trx_rx_frontend.hip: the receive front end ----
+ * trx_launch_channelize / trx_launch_resample: Channelizer(4, ., 16)::rotate and Resampler(p, q, 16)::rotate over a continuous
+ * stream; d_hist_io (may be NULL): the carried samples -15 .. -1, read and then replaced by the call's last 15.
+ * trx_launch_frontend_fused: the two in one pass (frontend_fused_kernel<rows>).  rows = 4: the four filterbank paths in physical
+ * order; rows = 1..3: row l of d_out = logical channel l = path trx_arfcn_pchan(rows, l).  The channel histories are
+ * [rows][16].  Returns 1 when the geometry fits no tile: the caller then runs the two launchers above.
  * trx_launch_rx_resamp_s16: convert_short_float + Resampler(p, q, 16)::rotate of one int16 channel; d_hist_in / d_hist_out:
  * 16 int16 IQ samples each, the samples -16 .. -1 of this call and of the next */
-int trx_launch_rx_frontend_chans(const int16_t *d_wide, float *d_out, size_t n_total, int chans, int p, int q, size_t out_stride,
-				 const float *parts, const trx_tables *d_tab, void *d_wide_hist_io, const void *d_chan_hist_in,
-				 void *d_chan_hist_out, hipStream_t stream);
+int trx_launch_channelize(const int16_t *d_in, float *d_out, size_t n_total, size_t out_stride, const trx_tables *d_tab,
+			  void *d_hist_io, hipStream_t stream);
+int trx_launch_resample(const float *d_in, float *d_out, size_t n_in, int p, int q, size_t n_chan, size_t in_stride,
+			size_t out_stride, const float *d_parts, void *d_hist_io, hipStream_t stream);
+int trx_launch_frontend_fused(const int16_t *d_wide, float *d_out, size_t n_total, int rows, int p, int q, size_t out_stride,
+			      const float *parts, const trx_tables *d_tab, void *d_wide_hist_io, const void *d_chan_hist_in,
+			      void *d_chan_hist_out, hipStream_t stream);
 int trx_launch_rx_resamp_s16(const int16_t *d_in, float *d_out, size_t n_in, int p, int q, const float *parts,
 			     const void *d_hist_in, void *d_hist_out, hipStream_t stream);
 

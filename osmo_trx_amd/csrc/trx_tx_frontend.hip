@@ -1,5 +1,5 @@
 // trx_tx_frontend.hip -- the multi-ARFCN transmit front end (gfx950, wave64), the mirror image of the receive front end
-// in trx_aux_kernels.hip:
+// in trx_rx_frontend.hip:
 //   * Synthesis(4, blockLen, 16)::rotate       Synthesis.cpp:66-104: forward 4-point DFT across the 4 paths, 16-tap path
 //                                              filters with carried history, interleave out[4t + k] = y_k[t] (:39-50)
 //   * RadioInterfaceMulti::pushBuffer()        radioInterfaceMulti.cpp:316-362: Resampler(p, q, 16)::rotate of every active
@@ -28,7 +28,7 @@ __device__ __forceinline__ tx_v2f tx_lds(const c32 *p)
 	return *(lds_ptr)(p);
 }
 
-// Workgroup barrier for LDS hand-offs only (as fe_lds_barrier, trx_aux_kernels.hip): waits for this wave's LDS operations,
+// Workgroup barrier for LDS hand-offs only (as fe_lds_barrier, trx_rx_frontend.hip): waits for this wave's LDS operations,
 // not for its global loads and stores, so the next tile's prefetch and this tile's output stores stay in flight.
 __device__ __forceinline__ void tx_lds_barrier()
 {

@@ -15,7 +15,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "gpurun_out")
-OURS = ("burst_pull", "pack_trxd", "va_demod", "channelize_kernel", "resample_kernel", "convolve_kernel", "convert_short_float",
+OURS = ("burst_pull", "pack_trxd", "va_demod", "channelize_kernel", "resample_kernel", "frontend_fused_kernel", "convolve_kernel", "convert_short_float",
         "delay_vector", "energy_detect", "vector_slicer", "sch_detect", "save_")
 PEAK = 8000.0
 

@@ -98,17 +98,21 @@ def test_rows_equal_the_four_row_objects(trx, chans, p, q, block_len):
     four.close(); fe.close()
 
 
-@pytest.mark.parametrize("p,q,block_len", GEOMETRIES)
+@pytest.mark.parametrize("p,q,block_len", GEOMETRIES + [UNFUSED])
 def test_rows_against_the_oracle_directly(trx, p, q, block_len):
-    """Not through the four-row object: orc_channelizer_rotate block by block, orc_resampler_rotate on the active paths."""
+    """Every instance of the one fused kernel (and, for UNFUSED, the one fallback) against orc_channelizer_rotate block by block
+    and orc_resampler_rotate on the rows' paths: the four-row object (chans=None) on paths 0..3, chans = 1..3 on the active
+    ones.  At 65/48 the 60 blocks are a first tile fed from history, interior tiles and a partial last tile (5 blocks a tile)."""
     from osmo_trx_amd import synth
     n_blocks = 60
     wide = synth.make_wideband_stream(n_blocks, "cuda:0", block_len=block_len)
     ref = dict(zip(range(4), oracle_rows(wide.cpu().numpy(), block_len, p, q, range(4))))
-    for chans in (1, 2, 3):
+    for chans in (None, 1, 2, 3):
         fe = front_end(trx, block_len=block_len, p=p, q=q, chans=chans)
         got = fe.pull(wide, n_blocks).cpu().numpy()
-        for l, pc in enumerate(PCHAN[chans]):
+        pchans = range(4) if chans is None else PCHAN[chans]
+        assert got.shape[0] == len(pchans)
+        for l, pc in enumerate(pchans):
             assert bits_equal(got[l], ref[pc]), (chans, l, pc)
         fe.close()
 

@@ -92,7 +92,7 @@ ms = timeit(lambda: trx.resample(xch, 65, 48))
 report("resample_kernel", "Resampler(65,48)::rotate, 4 channels", nb, "blocks", 4 * n_in * 8 + 4 * (n_in // 48 * 65) * 8, ms)
 fe = trxhip.RxFrontEnd(trx)
 ms = timeit(lambda: fe.pull(wide, nb))
-report("frontend_fused_kernel", "rx_frontend_pull: channelizer + resampler in one pass (streaming, carried history)", nb, "blocks",
+report("frontend_fused_kernel<4>", "rx_frontend_pull: channelizer + resampler in one pass (streaming, carried history)", nb, "blocks",
        nb * 768 * 4 + 4 * (n_in // 48 * 65) * 8, ms)
 del wide, ch, xch
 
