@@ -152,6 +152,11 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		t5pk |= (v & 15) << (4 * t);
 	}
 	t5pk = uni(t5pk);
+	// (the burst loop's conditions are kept as wave-uniform integers in scalar registers: a bool that depends on LDS contents, or
+	// that is carried round the loop as a phi of constants, is a 64-bit lane mask to the compiler, and every test of it an
+	// s_and_b64 vcc, exec, mask + s_cbranch_vcc pair in a structurised flow graph)
+	// a slot's word (max_toa << 16 | tsc << 8 | type) is below this for the windows the kernel takes; 0: it takes none
+	const unsigned toa_lim = (unsigned)uni(t5_ok ? (int)((NB_MAX_TOA + 1u) << 16) : 0);
 	const unsigned long long e8_addr = reinterpret_cast<unsigned long long>(&tab->edge8[0][0][0]);
 	// ---- work distribution: groups of 16 consecutive bursts.  Static part: workgroup w owns ONE contiguous range of groups
 	// (7/8 of the batch when the cross-die pool is on, everything otherwise); the rest is drawn group by group from a
@@ -168,7 +173,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	if (base16 + items > n_bursts)
 		items = (base16 < n_bursts) ? n_bursts - base16 : 0u;       // the batch's last group may be short
 	auto burst_of = [&](unsigned jj) -> unsigned {
-		if (jj < items)
+		if (__builtin_expect(jj < items, 1))
 			return base16 + jj;
 		if (!pooled)
 			return NB_NO_BURST;
@@ -223,10 +228,32 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	// ---- deferred output (registers): o = the lane's three sliced soft bits, recw = the result record (lanes 0..7)
 	v3f o = { 0.0f, 0.0f, 0.0f };
 	int recw = 0;
-	bool pend_any = false;
-	bool pend_rec = false;                                         // recw holds the pending burst's record (a slot without a burst)
+	int pend_m = 0;                                                // 0 / -1: o holds the soft bits of burst pend_b, not yet stored
+	int pend_rm = 0;                                               // 0 / 0xff: and recw its record (a slot without a burst)
 	unsigned pend_b = 0;
-	bool left_any = false;
+	int left_any = 0;
+	// the three stores carry their own EXEC masks, ANDed with pend_m / taken from pend_rm: with nothing pending they store nothing,
+	// and no branch goes round them
+	auto store_pending = [&](const int lane) {
+		float *const so = soft + (size_t)pend_b * 148;
+		int *const rp = reinterpret_cast<int *>(results + pend_b);
+		const float oe = o.x;
+		asm volatile("s_bfm_b64 exec, 48, 2\n\t"
+			     "s_and_b32 exec_lo, exec_lo, %8\n\t"
+			     "s_and_b32 exec_hi, exec_hi, %8\n\t"
+			     "global_store_dwordx3 %0, %1, %2 offset:16\n\t"
+			     "s_mov_b32 exec_lo, 0\n\t"
+			     "s_and_b32 exec_hi, %8, 0x92400000\n\t"
+			     "global_store_dword %3, %4, %2\n\t"
+			     "s_mov_b32 exec_lo, %9\n\t"
+			     "s_mov_b32 exec_hi, 0\n\t"
+			     "global_store_dword %5, %6, %7\n\t"
+			     "s_mov_b64 exec, -1\n\t"
+			     "s_nop 0"
+			     :: "v"((lane - 2) * 12), "v"(o), "s"(so), "v"((((lane - 54) * 11) >> 5) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
+			        "s"(pend_m), "s"(pend_rm)
+			     : "memory", "scc");
+	};
 	// ---- the records of detected bursts are made 64 at a time: what computeCI / amp / toa / RSSI need of burst k of the batch
 	// goes into lane k of these registers (seven moves under a one-lane mask), flush_records() does the arithmetic once per lane -- the same
 	// operations in the same order as block TAIL did per burst on a wave-uniform value (two logarithms and two reciprocals
@@ -255,6 +282,9 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				     "s_nop 1"
 				     :: "v"(results + (unsigned)q_b), "v"(r0), "v"(r1) : "memory");
 		}
+		// (the lanes rejoin HERE, in a block of its own: folded into the loop's latch, the join would make every value the loop
+		// carries -- q_n, the pending masks -- a phi behind a divergent branch, that is a vector register or a lane mask)
+		asm volatile("");
 		q_n = 0;
 	};
 
@@ -269,8 +299,10 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	auto demod_general = [&](const int nk, const c32 ampv, const int lane) -> bool {
 		constexpr int L = 625, nwrite = 148;
 		c32 *const dec = D;
-		const trx_tables *tabc = tab;                               // (opaque copy: the table addresses of this cold path are formed here,
-		asm volatile("" : "+s"(tabc));                              //  not kept in scalar registers across the burst loop)
+		// (the table addresses of this cold path are formed here, from the one address the loop keeps for block TAIL, behind an
+		// opaque copy: none of them is kept in scalar registers across the burst loop)
+		const trx_tables *tabc = reinterpret_cast<const trx_tables *>(e8_addr - offsetof(trx_tables, edge8));
+		asm volatile("" : "+s"(tabc));
 		const int w = nk >> 7, fr = nk & 127;
 		const int fidx = (fr >= 2) ? (fr >> 1) : TRX_DELAY_FILTS;
 		const float ian = __builtin_amdgcn_rcpf(norm2(ampv));
@@ -281,7 +313,9 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		const int i0l = cdiv4(n_lo), i0h = i_full_hi + 1;
 		const bool need_lo = (n_hi >= n_lo) && (i0l < i_full_lo) && (i0l < nwrite);
 		const bool need_hi = (n_hi >= n_lo) && (i0h <= fdiv4(n_hi + 15)) && (i0h < nwrite);
-		const bool lo_tab = need_lo && (n_hi >= 4 * (i_full_lo - 1));
+		// (the wave-uniform conditions of this path as integers read from lane 0, the per-lane ones formed again where they are
+		// used: as bools they are lane masks, two scalar registers each, live across the filter -- more than the burst loop has left)
+		const int lo_tab = uni(need_lo && (n_hi >= 4 * (i_full_lo - 1)));
 		float ct0 = 0.0f, ct1 = 0.0f, ct2 = 0.0f;
 		const int le = lane >> 4, lt = lane & 15;
 		const int li = i0l + le;
@@ -293,7 +327,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			ct1 = row[16];
 			ct2 = (lt < 4) ? row[32] : 0.0f;
 		}
-		const bool hi_tab = need_hi && (w <= -2) && (n_lo <= 4 * i0h - 15);
+		const int hi_tab = uni(need_hi && (w <= -2) && (n_lo <= 4 * i0h - 15));
 		if ((need_lo && !lo_tab) || (need_hi && !hi_tab))
 			return false;
 		float ch0 = 0.0f, ch1 = 0.0f, ch2 = 0.0f;
@@ -306,6 +340,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			ch1 = row[16];
 			ch2 = (lt < 4) ? row[32] : 0.0f;
 		}
+		int tabv = lo_tab | (hi_tab << 1);                          // (across the filter in one vector register, not as two masks)
+		asm volatile("" : "+v"(tabv));
 		{
 			const int c_full = -24 - w;
 			const int i_min = cdiv4(-36 - c_full), i_max = fdiv4(L + 1 - c_full);
@@ -336,7 +372,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				}
 			}
 		}
-		if (lo_tab) {
+		const int tab2 = uni(tabv), lo_tab2 = tab2 & 1, hi_tab2 = tab2 & 2;
+		if (lo_tab2) {
 			const int s0 = 4 * li - 24 - w + lt;
 			const c32 *pp = P + ((s0 & 3) * PH_A + PH_M0 + (s0 >> 2));
 			const c32 x0 = lds_c32(pp), x1 = lds_c32(pp + 4), x2 = lds_c32(pp + 8);
@@ -344,10 +381,12 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			ar = fmaf(x1.x, ct1, ar); ai = fmaf(x1.y, ct1, ai);
 			ar = fmaf(x2.x, ct2, ar); ai = fmaf(x2.y, ct2, ai);
 			const float sr = row_sum(ar), si = row_sum(ai);
-			if (lt == 0 && lact)
+			int lt0s = lt0;
+			asm volatile("" : "+v"(lt0s));
+			if (lt == 0 && lt0s >= 1)
 				dec[li] = cmul(make_float2(sr, si), scale);
 		}
-		if (hi_tab) {
+		if (hi_tab2) {
 			const int s0 = 4 * hi_i - 24 - w + lt;
 			const c32 *pp = P + ((s0 & 3) * PH_A + PH_M0 + (s0 >> 2));
 			const c32 x0 = lds_c32(pp), x1 = lds_c32(pp + 4), x2 = lds_c32(pp + 8);
@@ -355,7 +394,9 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			ar = fmaf(x1.x, ch1, ar); ai = fmaf(x1.y, ch1, ai);
 			ar = fmaf(x2.x, ch2, ar); ai = fmaf(x2.y, ch2, ai);
 			const float sr = row_sum(ar), si = row_sum(ai);
-			if (lt == 0 && hact && hi_i < 156)
+			int htms = htm;
+			asm volatile("" : "+v"(htms));
+			if (lt == 0 && htms >= 0 && hi_i < 156)
 				dec[hi_i] = cmul(make_float2(sr, si), scale);
 		}
 		wave_sync();
@@ -376,6 +417,40 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 
 	DIAG_DECL;
 	unsigned j_next = 0, b_next = NB_NO_BURST;
+	// the next burst of this wave from the ticket just taken: its number, the pool's draw at a group boundary, its prefetch
+	// (items below j_plain are in the static range and off the pool's group boundaries: one scalar compare and one add give the
+	// burst; the compiler joins the two branches in front of ONE copy of the prefetch loads, behind a flag -- kept apart, the
+	// pool branch's copy waited for vmcnt(0), the stores just issued, in front of its loads: tools/isa_guard_nb.py checks every copy)
+	const unsigned j_plain = (unsigned)uni((int)(!pooled ? items : items >= 16u ? items - 16u : 0u));
+	auto advance = [&](const int taken, const int lane) {
+		j_next = (unsigned)taken;
+		if (__builtin_expect(j_next < j_plain, 1)) {
+			b_next = base16 + j_next;
+			DIAG_MARK(17);
+			prefetch(b_next, lane);
+		} else {
+			b_next = burst_of(j_next);
+			if (pooled && (j_next & 15u) == 0u && j_next + 16u >= items)
+				pool_draw(j_next, b_next == NB_NO_BURST && j_next >= items, lane);
+			DIAG_MARK(17);
+			if (b_next != NB_NO_BURST)
+				prefetch(b_next, lane);
+		}
+	};
+	// left to the general kernel: the burst's flag byte, and "something was left" (plain stores: a type-mixed batch leaves a
+	// million bursts, and a million atomics on one counter cost ten times the batch)
+	// ("something was left" once per wave: a million stores to one address serialise in the L2 like a million atomics)
+	auto mark_left = [&](const unsigned bb, const int lane) {
+		pend_m = 0;                                                 // nothing of this burst is stored
+		pend_rm = 0;
+		if (lane == 0) {
+			reinterpret_cast<uint8_t *>(redo + TRX_REDO_HDR)[bb] = 1;
+			if (!left_any)
+				__hip_atomic_store(redo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+		asm volatile("");                                           // (the lanes rejoin here, not in the loop's latch: see flush_records)
+		left_any = 1;
+	};
 	for (unsigned b = b_first; b != NB_NO_BURST; b = b_next) {
 		int lane;                                                  // re-materialised per burst (see burst_pull4_kernel)
 		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
@@ -384,72 +459,55 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		// ---- is this a slot the kernel handles?  (a slot of another type is flagged before anything is spent on its samples)
 		const unsigned max_toa = prm0 >> 16;
 		const int tsc = (prm0 >> 8) & 0xff;
-		bool leave = ((prm0 & 0xf8ffu) != (unsigned)TRXHIP_TSC) || (max_toa > NB_MAX_TOA) || !t5_ok;
-
-		// ---- phase 0: registers -> fp32 polyphase LDS; clip scan and energyDetect partial sums on the fly
-		c32 *const pload = P + (lane & 3) * PH_A + PH_M0 + (lane >> 2);
-		float amax = 0.0f, epart = 0.0f;
 #ifdef TRX_DIAG
 		DIAG_MARK(12);                                              // (loop top: mbcnt, ticket issue, slot type)
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		DIAG_MARK(13);                                              // the prefetched samples' arrival, apart from their conversion
 #endif
-		if (!leave) {
-#pragma unroll
-			for (int r = 0; r < NLD; r++) {
-				const int i = r * WAVE + lane;
-				if (r < NLD - 1 || i < 625) {
-					const c32 v = make_float2((float)(int16_t)(pre_i[r] & 0xffffu), (float)(int16_t)(pre_i[r] >> 16));
-					pload[16 * r] = v;
-					asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v.x), "v"(v.y));
-					if (r < 5)
-						epart = fmaf(v.x, v.x, fmaf(v.y, v.y, epart));
-				}
-			}
-		} else {
+		// (one compare: a type or TSC that does not fit sets the high bits of the word whose upper half is max_toa)
+		const unsigned slot_key = prm0 | (0u - ((prm0 & 0xf8ffu) ^ (unsigned)TRXHIP_TSC));
+		if (__builtin_expect(slot_key >= toa_lim, 0)) {
 			// the prefetched samples are dropped, but they must be "used": a path that reaches the next prefetch with loads
 			// the compiler still counts as outstanding makes it wait for vmcnt(0) right behind the new loads (measured: -4 %)
 #pragma unroll
 			for (int r = 0; r < NLD; r++)
 				asm volatile("" :: "v"(pre_i[r]));
+			store_pending(lane);
+			advance(claim_take(ticket), lane);
+			mark_left(b, lane);
+			continue;
+		}
+
+		// ---- phase 0: registers -> fp32 polyphase LDS; clip scan and energyDetect partial sums on the fly
+		c32 *const pload = P + (lane & 3) * PH_A + PH_M0 + (lane >> 2);
+		float amax = 0.0f, epart = 0.0f;
+#pragma unroll
+		for (int r = 0; r < NLD; r++) {
+			const int i = r * WAVE + lane;
+			if (r < NLD - 1 || i < 625) {
+				const c32 v = make_float2((float)(int16_t)(pre_i[r] & 0xffffu), (float)(int16_t)(pre_i[r] >> 16));
+				pload[16 * r] = v;
+				asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v.x), "v"(v.y));
+				if (r < 5)
+					epart = fmaf(v.x, v.x, fmaf(v.y, v.y, epart));
+			}
 		}
 		DIAG_MARK(14);
 		// ---- the previous burst's output: 148 soft bits (lanes 2..49: symbols 3 lane - 2 + j as one 12-byte store, lanes
 		// 54, 57, 60, 63: symbols 0..3) and the result record (lanes 0..7)
-		if (pend_any) {
-			float *const so = soft + (size_t)pend_b * 148;
-			int *const rp = reinterpret_cast<int *>(results + pend_b);
-			const float oe = o.x;
-			asm volatile("s_bfm_b64 exec, 48, 2\n\t"
-				     "global_store_dwordx3 %0, %1, %2 offset:16\n\t"
-				     "s_mov_b32 exec_lo, 0\n\t"
-			     "s_mov_b32 exec_hi, 0x92400000\n\t"
-				     "global_store_dword %3, %4, %2\n\t"
-				     "s_mov_b64 exec, %8\n\t"
-				     "global_store_dword %5, %6, %7\n\t"
-				     "s_mov_b64 exec, -1\n\t"
-				     "s_nop 0"
-				     :: "v"((lane - 2) * 12), "v"(o), "s"(so), "v"((((lane - 54) * 11) >> 5) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
-				        "s"(pend_rec ? 0xffull : 0ull)
-				     : "memory");
-		}
-		pend_any = false;
+		store_pending(lane);
 		DIAG_MARK(16);
 		// (a converted burst has at least five LDS writes behind the ticket's request -- ten rows, at most two per instruction --
 		// and nothing else on lgkmcnt: the ticket is there when five are outstanding, the writes drain under the next block)
-		j_next = (unsigned)(leave ? claim_take(ticket) : claim_take_behind<5>(ticket));
-		b_next = burst_of(j_next);
-		if (pooled && (j_next & 15u) == 0u && j_next + 16u >= items)
-			pool_draw(j_next, b_next == NB_NO_BURST && j_next >= items, lane);
-		DIAG_MARK(17);
-		if (b_next != NB_NO_BURST)
-			prefetch(b_next, lane);
+		advance(claim_take_behind<5>(ticket), lane);
 		DIAG_MARK(15);
 
-		int clip = 0;
-		if (!leave) {
+		pend_m = 0;
+		pend_rm = 0xff;                                             // (a slot without a burst, until one is detected)
+		int leave = 0;
+		{
 			// maxAmplitude() > 30000 (:1711-1722, :1746)
-			clip = __ballot(amax > TRX_CLIP_THRESH) != 0ull;
+			const int clip = __ballot(amax > TRX_CLIP_THRESH) != 0ull;
 
 			// ---- detectGeneralBurst window of a normal burst (:1887-1904: target 82, head 10, tail 6 + max_toa -> start 71,
 			// len 16 + max_toa): decimated samples 56 .. 70 + len, one per lane
@@ -491,9 +549,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					       [lc] "n"((TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 64 + 5 * WAVE) * 4)
 					     : NB_ASM_CLOBBERS);
 				DIAG_MARK(4);
-				int hit = 0;
 				int toa512 = 0;
-				if (m_bits != 0) {                                          // fastPeakDetect: a maximum above zero exists (:1120-1139)
+				if (__builtin_expect(m_bits != 0, 1)) {                                          // fastPeakDetect: a maximum above zero exists (:1120-1139)
 					// edge gate, peak-ratio gate, round A of the TOA bisection and its walk (DETA); round B, walk, peak value (DETB)
 					int st, e512;
 					float km;
@@ -504,14 +561,14 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						     : NB_ASM_CLOBBERS);
 					DIAG_MARK(5);
 					int xr_bits = 0, xi_bits = 0;
-					if (st == 1) {
+					if (__builtin_expect(st == 1, 1)) {
 						asm volatile(NB_ASM_DETB
 							     : [st] "=&s"(st), [toa] "=&s"(toa512), [xr] "=&s"(xr_bits), [xi] "=&s"(xi_bits)
 							     : [e] "s"(e512), [kb] "v"(kb), [czb] "s"(lds_addr(cz)), [km] "v"(km)
 							     : NB_ASM_CLOBBERS);
 						DIAG_MARK(6);
 					}
-					if (st == 3) {
+					if (__builtin_expect(st == 3, 0)) {
 						// an uncertified early / late decision on the path: the search again in the reference's operand order
 						if (lane == 0)
 							atomicAdd(&g_trx_fast_stats[0], 1ull);
@@ -525,13 +582,12 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						xi_bits = uni(__float_as_int(xcorr.y));
 						st = 1;
 					}
-					if (st == 2) {
-						leave = true;                                          // the gate is too close to call for the estimate
+					if (__builtin_expect(st == 2, 0)) {
+						leave = 1;                                          // the gate is too close to call for the estimate
 						if (lane == 0) atomicAdd(&g_trx_fast_stats[2], 1ull);
 					}
-					if (st == 1) {
+					if (__builtin_expect(st == 1, 1)) {
 						// computeCI, amp, toa, the result record, 1 / amp; then demodGmskBurst of the usual geometry (TAIL)
-						hit = 1;
 						int ok, s_bits;
 						float d0, d1, d2;
 						const int t5 = (t5pk << (28 - 4 * tsc)) >> 28;
@@ -545,7 +601,11 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 							     : NB_ASM_CLOBBERS);
 						DIAG_MARK(10);
 						asm volatile("s_setprio 2");
-						if (!ok) {
+						// vectorSlicer: 0.5 * (x + 1), clamped (:546-556); the cold demodulator below writes its own over them
+						o.x = __builtin_amdgcn_fmed3f(fmaf(0.5f, d0, 0.5f), 0.0f, 1.0f);
+						o.y = __builtin_amdgcn_fmed3f(fmaf(0.5f, d1, 0.5f), 0.0f, 1.0f);
+						o.z = __builtin_amdgcn_fmed3f(fmaf(0.5f, d2, 0.5f), 0.0f, 1.0f);
+						if (__builtin_expect(!ok, 0)) {
 							// TOA outside the straight-line geometry (an early burst, or one later than 9 symbols): the general form
 							if (lane == 0) atomicAdd(&g_trx_fast_stats[3], 1ull);
 							const float *const h = lhdr + 8 * tsc;
@@ -553,9 +613,10 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 							const float a0 = xr * h[2], a1 = xr * h[3], a2 = xi * h[3], a3 = xi * h[2];
 							const c32 ampv = make_float2(unif(a0 - a2), unif(a1 + a3));     // amp = peak / gain, as block TAIL has it
 							if (!demod_general(t5 + 10 * 512 - toa512, ampv, lane))
-								leave = true;
+								leave = 1;
 						}
-						if (!leave) {
+						pend_rm = 0;
+						if (__builtin_expect(!leave, 1)) {
 							// the record's inputs: lane q_n of the seven registers (toa in 1/512 symbol: position - sync->toa - head)
 							asm("s_lshl_b64 exec, 1, %[n]\n\t"
 						    "v_mov_b32_e32 %[qxr], %[xr]\n\t"
@@ -572,14 +633,9 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						      [ss] "s"(s_bits), [fl] "s"((int)((uint32_t)tsc | ((uint32_t)clip << 8) | (37u << 24))), [b] "s"((int)b));
 						q_n++;
 						}
-						if (ok) {
-							o.x = __builtin_amdgcn_fmed3f(fmaf(0.5f, d0, 0.5f), 0.0f, 1.0f);     // vectorSlicer: 0.5 * (x + 1), clamped (:546-556)
-							o.y = __builtin_amdgcn_fmed3f(fmaf(0.5f, d1, 0.5f), 0.0f, 1.0f);
-							o.z = __builtin_amdgcn_fmed3f(fmaf(0.5f, d2, 0.5f), 0.0f, 1.0f);
-						}
 					}
 				}
-				if (!hit && !leave) {
+				if (__builtin_expect(pend_rm & ~leave & 1, 0)) {
 					// nothing found: rc (:1764), energy and RSSI (Transceiver.cpp:741,751), zero soft bits
 					const float energy = __int_as_float(es_bits) * 0.0125f;
 					const float rssi = fs_db - 3.01029996f * __log2f(energy);
@@ -595,46 +651,23 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					recw = word;
 					o = (v3f){ 0.0f, 0.0f, 0.0f };
 				}
-				pend_rec = !hit;
 			}
 		}
-		if (leave) {
-			// left to the general kernel: the burst's flag byte, and "something was left" (plain stores: a type-mixed batch leaves a
-			// million bursts, and a million atomics on one counter cost ten times the batch)
-			// ("something was left" once per wave: a million stores to one address serialise in the L2 like a million atomics)
-			if (lane == 0) {
-				reinterpret_cast<uint8_t *>(redo + TRX_REDO_HDR)[b] = 1;
-				if (!left_any)
-					__hip_atomic_store(redo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			}
-			left_any = true;
+		if (__builtin_expect(leave, 0)) {
+			mark_left(b, lane);
 			continue;
 		}
 		pend_b = b;
-		pend_any = true;
-		if (q_n == WAVE)
+		pend_m = -1;
+		if (__builtin_expect(q_n == WAVE, 0))
 			flush_records(lane);
 		DIAG_MARK(11);
 	}
 	// ---- the last burst's output
-	if (pend_any) {
+	{
 		int lane;
 		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-		float *const so = soft + (size_t)pend_b * 148;
-		int *const rp = reinterpret_cast<int *>(results + pend_b);
-		const float oe = o.x;
-		asm volatile("s_bfm_b64 exec, 48, 2\n\t"
-			     "global_store_dwordx3 %0, %1, %2 offset:16\n\t"
-		     "s_mov_b32 exec_lo, 0\n\t"
-		     "s_mov_b32 exec_hi, 0x92400000\n\t"
-			     "global_store_dword %3, %4, %2\n\t"
-			     "s_mov_b64 exec, %8\n\t"
-			     "global_store_dword %5, %6, %7\n\t"
-			     "s_mov_b64 exec, -1\n\t"
-			     "s_nop 0"
-			     :: "v"((lane - 2) * 12), "v"(o), "s"(so), "v"((((lane - 54) * 11) >> 5) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
-			        "s"(pend_rec ? 0xffull : 0ull)
-			     : "memory");
+		store_pending(lane);
 	}
 	{
 		int lane;

@@ -7,9 +7,12 @@ The loop is C++ around hand-placed blocks, and twice in round 6 a harmless-looki
 `s_waitcnt vmcnt(0)` between the next burst's prefetch loads (an exec-masked tenth load; a 64-bit vector address built in
 one of the destination registers) -- 3-4 % of the headline each time, invisible to every test.  Checked here (and by
 tests/test_isa_guard_cpu.py on every CPU run):
-  * the ten prefetch loads of the loop are issued back to back: no s_waitcnt between the first and the last of them;
+  * the ten prefetch loads of the loop (and of every copy on its out-of-line paths) are issued back to back: no s_waitcnt between
+    the first and the last of them; one group lies on the loop's main path;
   * the work ticket is taken with a partial wait (lgkmcnt(5)), not a drain of the converted samples' LDS writes;
   * no spills, no scratch, 128 VGPRs (4 waves per SIMD), and the code size.
+  * the stores of flush_records() do not lie on the loop's main path (they belong behind it: once per 64 bursts).
+Reported, not checked: the static instruction and branch counts of the main path outside the hand-placed blocks.
 Prints a JSON summary; exit status 1 on a violation."""
 import json
 import os
@@ -49,19 +52,22 @@ def check(text):
         cur.append(i)
     if cur:
         groups.append(cur)
-    if not groups or len(groups[-1]) != 10:
-        errs.append(f"expected a last group of 10 non-temporal prefetch loads, found groups of {[len(g) for g in groups]}")
-    else:
-        g = groups[-1]
+    # (every group behind the first: the loop's own prefetch and the copies on its out-of-line paths -- the foreign slot, the
+    # pool boundary -- wherever the layout puts them)
+    if len(groups) < 2 or any(len(g) != 10 for g in groups[1:]):
+        errs.append(f"expected groups of 10 non-temporal prefetch loads behind the first, found groups of {[len(g) for g in groups]}")
+    for g in groups[1:] if len(groups) >= 2 else []:
+        if len(g) != 10:
+            continue
         between = [body[i].strip() for i in range(g[0], g[-1]) if "s_waitcnt" in body[i]]
         # and in front of the group, behind the address arithmetic: a wait for vmcnt(0) there stalls on the stores just issued
         before = [body[i].strip() for i in range(max(0, g[0] - 12), g[0]) if re.search(r"s_waitcnt.*vmcnt\(0\)", body[i])]
         if between:
-            errs.append(f"s_waitcnt between the loop's prefetch loads: {between}")
+            errs.append(f"s_waitcnt between the loop's prefetch loads (line {g[0]}): {between}")
         if before:
-            errs.append(f"s_waitcnt vmcnt(0) right in front of the loop's prefetch loads: {before}")
+            errs.append(f"s_waitcnt vmcnt(0) right in front of the loop's prefetch loads (line {g[0]}): {before}")
         if any(re.search(r"v\[\d+:\d+\], off", body[i]) for i in g):
-            errs.append("prefetch loads with a 64-bit vector address (expected the scalar-base form)")
+            errs.append(f"prefetch loads with a 64-bit vector address (line {g[0]}; expected the scalar-base form)")
     if not any(re.search(r"s_waitcnt lgkmcnt\(5\)", t) for t in body):
         errs.append("no `s_waitcnt lgkmcnt(5)`: the work ticket is taken behind a full drain of the LDS")
     # ---- resources (the kernel's metadata record)
@@ -74,8 +80,42 @@ def check(text):
     if res["vgpr_count"] > 128:
         errs.append(f"{res['vgpr_count']} VGPRs: fewer than 4 waves per SIMD")
     n_ins = sum(1 for t in body if re.match(r"\s+[a-z_0-9]+(\s|$)", t) and not t.strip().startswith((".", ";")))
+    rep = loop_report(body)
+    main = rep["loop_main_path"]
+    if main is None:
+        errs.append("the burst loop's main path was not found (first v_mbcnt_lo .. back edge behind the last `s_setprio 2`)")
+    else:
+        # the join blocks that keep the loop's carried state in scalar registers are empty asm statements: a compiler that folds
+        # them away brings flush_records() back into the loop, and with it the masks
+        if main["flush_records_stores_on_it"]:
+            errs.append("flush_records' stores lie on the loop's main path")
+        if not any(g[0] > main["first"] and g[-1] < main["last"] for g in groups[1:]):
+            errs.append("no prefetch group on the loop's main path")
     return errs, {"kernel": "nb_pull4_kernel", **res, "instructions": n_ins,
-                  "prefetch_groups": [len(g) for g in groups]}
+                  "prefetch_groups": [len(g) for g in groups], **rep}
+
+
+def loop_report(body):
+    """Reporting only: the burst loop's main path as laid out -- from the loop's lane id (the first v_mbcnt_lo of the kernel) to
+    the first branch behind block TAIL (the last `s_setprio 2`) that goes back to a label at the loop's head -- its branches
+    outside the hand-placed blocks, and whether flush_records' 16-byte stores lie on it."""
+    try:
+        head = next(i for i, t in enumerate(body) if "v_mbcnt_lo_u32_b32" in t)
+        labels = {m.group(1) for t in body[max(0, head - 24):head] for m in [re.match(r"(\.LBB\d+_\d+):", t)] if m}
+        tail = max(i for i, t in enumerate(body) if re.match(r"\s*s_setprio 2", t))
+        back = next(i for i in range(tail, len(body))
+                    if (m := re.match(r"\s*s_c?branch\w*\s+(\.LBB\d+_\d+)", body[i])) and m.group(1) in labels)
+    except (StopIteration, ValueError):
+        return {"loop_main_path": None}
+    in_asm, branches, ins = False, 0, 0
+    for t in body[head:back + 1]:
+        if "#ASMSTART" in t or "#ASMEND" in t:
+            in_asm = "#ASMSTART" in t
+        elif not in_asm and re.match(r"\s+[a-z_0-9]+(\s|$)", t) and not t.strip().startswith((".", ";")):
+            ins += 1
+            branches += bool(re.match(r"\s*s_c?branch", t))
+    return {"loop_main_path": {"first": head, "last": back, "instructions_outside_blocks": ins, "branches_outside_blocks": branches,
+                               "flush_records_stores_on_it": any("global_store_dwordx4" in t for t in body[head:back + 1])}}
 
 
 def main():
