@@ -186,7 +186,10 @@ uint64_t trxhip_tables_checksum(const void *h_blob, size_t size);     /* FNV-1a 
  *              bits (nbits_div4 = 111): give soft_stride >= 444 when EDGE slots are possible, otherwise the row is
  *              truncated to soft_stride.  Unused tail and undetected bursts are zero-filled.
  *   flags    : TRXHIP_FLAG_* bits
- *   sps      : 1 or 4; burst_len: 625 @4 SPS (>= 624), 156/157 @1 SPS
+ *   sps      : 1 or 4; burst_len: 625 @4 SPS (>= 624), 156/157 @1 SPS (148..192 is accepted at 1 SPS)
+ *              1 SPS with TRXHIP_FLAG_SLICE clear: the reference's GMSKReverseRotation1 table has 157 entries
+ *              (sigProcLib.cpp:207), so raw soft values exist for i < min(burst_len, 157); the rest of the row is 0.
+ *              Sliced rows (148 values) are not affected.
  * Asynchronous on `stream`, with two exceptions on the kernel split (trxhip_set_nb_kernel()): the call waits until the split
  * launch four split launches back on this context has completed (its leftover list is reused), and when a batch is larger
  * than that list has room for, the hipFree / hipMalloc that grow it can wait for the device.

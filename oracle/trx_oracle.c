@@ -1120,7 +1120,14 @@ static int demod_gmsk_burst(const orc_cf *burst, int n, int sps, const orc_ebp *
 	orc_cf *dec = malloc((size_t)(n > 160 ? n : 160) * sizeof(orc_cf));
 	int olen = demod_common(burst, n, sps, ebp, dec);
 	if (olen < 0) { free(dec); return -1; }
+	/* GMSKReverseRotation1 has 157 entries (sigProcLib.cpp:207, :2066): a longer 1-SPS burst would index past it there.  The
+	 * rows the reference leaves undefined are defined here (and in the kernels) as 0.0; no read goes past the table. */
+	const int nrot = (int)(sizeof(T.rrot1) / sizeof(T.rrot1[0]));
 	for (int i = 0; i < olen; i++) {
+		if (i >= nrot) {
+			soft[i] = 0.0f;
+			continue;
+		}
 		orc_cf v = cmul(T.rrot1[i], dec[i]);              /* GMSKReverseRotate(*dec, 1) */
 		soft[i] = v.re;                                     /* signalToSoftVector */
 	}
@@ -1199,13 +1206,59 @@ int orc_demod_any_burst(const orc_cf *burst, int n, int type, int sps, orc_ebp *
  * Batched DSP core of Transceiver::pullRadioVector, Transceiver.cpp:665-815
  * (FIFO, clock, noise history and counters stay with the caller)
  * ---------------------------------------------------------------------------------------- */
-void orc_pull_batch(const int16_t *iq, size_t n_bursts, int burst_len, int sps,
-		    const orc_burst_params *params, float threshold, double full_scale,
-		    orc_burst_result *res, float *soft, int soft_stride, int slice)
+/* one burst of the batch, already fp32 (behind convert_short_float): energyDetect -> rssi -> clip -> detectAnyBurst ->
+ * demodAnyBurst -> vectorSlicer.  flags: ORC_PULL_SLICE | ORC_PULL_IDLE_DUMMY */
+static void pull_one(const orc_cf *burst, int burst_len, int sps, const orc_burst_params *p, float threshold,
+		     double full_scale, orc_burst_result *r, float *so, int soft_stride, int flags)
+{
+	float raw[448];
+
+	/* :724-746 (one diversity path) */
+	float pow = orc_energy_detect(burst, burst_len, 20 * sps);
+	float avg = 0.0f;
+	avg += pow;
+	avg = sqrtf(avg / 1);
+	r->energy = pow;
+	r->rssi = (float)(20.0 * log10(full_scale / avg));      /* :751 without rssi_offset */
+	r->clip = max_amplitude(burst, burst_len) > CLIP_THRESH;
+
+	/* :754-755; with ORC_PULL_IDLE_DUMMY the slot is searched as detectAnyBurst(IDLE) would (detectDummyBurst, :1945-1947) */
+	if (p->type == ORC_IDLE && !(flags & ORC_PULL_IDLE_DUMMY))
+		return;
+
+	orc_ebp ebp;
+	memset(&ebp, 0, sizeof(ebp));
+	int rc = orc_detect_any_burst(burst, burst_len, p->tsc, threshold, sps, p->type, p->max_toa, &ebp);
+	r->rc = rc;
+	if (rc <= 0)                                  /* :769-782 */
+		return;
+
+	int nsoft = orc_demod_any_burst(burst, burst_len, rc, sps, &ebp, raw);
+	r->toa = ebp.toa;
+	r->amp_re = ebp.amp.re;
+	r->amp_im = ebp.amp.im;
+	r->ci = ebp.ci;
+	r->tsc = ebp.tsc;
+	r->idle = 0;
+	int nbits = (nsoft == 444) ? 444 : 148;       /* :793-800 */
+	r->nbits_div4 = (uint8_t)(nbits / 4);
+	if (so) {
+		if (flags & ORC_PULL_SLICE) {
+			int m = nbits < soft_stride ? nbits : soft_stride;
+			orc_vector_slicer(so, raw, (size_t)m);      /* :803 */
+		} else {
+			int m = nsoft < soft_stride ? nsoft : soft_stride;
+			memcpy(so, raw, (size_t)m * sizeof(float));
+		}
+	}
+}
+
+static void pull_batch_any(const int16_t *iq16, const orc_cf *iqf, size_t n_bursts, int burst_len, int sps,
+			   const orc_burst_params *params, float threshold, double full_scale,
+			   orc_burst_result *res, float *soft, int soft_stride, int flags)
 {
 	if (!T_ready) orc_setup();
-	orc_cf *burst = malloc((size_t)burst_len * sizeof(orc_cf));
-	float raw[448];
+	orc_cf *burst = iq16 ? malloc((size_t)burst_len * sizeof(orc_cf)) : NULL;
 
 	for (size_t b = 0; b < n_bursts; b++) {
 		const orc_burst_params *p = &params[b];
@@ -1218,48 +1271,30 @@ void orc_pull_batch(const int16_t *iq, size_t n_bursts, int burst_len, int sps,
 		if (p->type == ORC_OFF)                       /* :704-707 */
 			continue;
 
-		/* radioInterface.cpp:344-348 convert_short_float, no scaling */
-		orc_convert_short_float((float *)burst, &iq[b * (size_t)burst_len * 2], burst_len * 2);
-
-		/* :724-746 (one diversity path) */
-		float pow = orc_energy_detect(burst, burst_len, 20 * sps);
-		float avg = 0.0f;
-		avg += pow;
-		avg = sqrtf(avg / 1);
-		r->energy = pow;
-		r->rssi = (float)(20.0 * log10(full_scale / avg));      /* :751 without rssi_offset */
-		r->clip = max_amplitude(burst, burst_len) > CLIP_THRESH;
-
-		if (p->type == ORC_IDLE)                      /* :754-755 */
-			continue;
-
-		orc_ebp ebp;
-		memset(&ebp, 0, sizeof(ebp));
-		int rc = orc_detect_any_burst(burst, burst_len, p->tsc, threshold, sps, p->type, p->max_toa, &ebp);
-		r->rc = rc;
-		if (rc <= 0)                                  /* :769-782 */
-			continue;
-
-		int nsoft = orc_demod_any_burst(burst, burst_len, rc, sps, &ebp, raw);
-		r->toa = ebp.toa;
-		r->amp_re = ebp.amp.re;
-		r->amp_im = ebp.amp.im;
-		r->ci = ebp.ci;
-		r->tsc = ebp.tsc;
-		r->idle = 0;
-		int nbits = (nsoft == 444) ? 444 : 148;       /* :793-800 */
-		r->nbits_div4 = (uint8_t)(nbits / 4);
-		if (so) {
-			if (slice) {
-				int m = nbits < soft_stride ? nbits : soft_stride;
-				orc_vector_slicer(so, raw, (size_t)m);      /* :803 */
-			} else {
-				int m = nsoft < soft_stride ? nsoft : soft_stride;
-				memcpy(so, raw, (size_t)m * sizeof(float));
-			}
+		if (iq16) {
+			/* radioInterface.cpp:344-348 convert_short_float, no scaling */
+			orc_convert_short_float((float *)burst, &iq16[b * (size_t)burst_len * 2], burst_len * 2);
+			pull_one(burst, burst_len, sps, p, threshold, full_scale, r, so, soft_stride, flags);
+		} else {
+			pull_one(&iqf[b * (size_t)burst_len], burst_len, sps, p, threshold, full_scale, r, so, soft_stride, flags);
 		}
 	}
 	free(burst);
+}
+
+void orc_pull_batch(const int16_t *iq, size_t n_bursts, int burst_len, int sps,
+		    const orc_burst_params *params, float threshold, double full_scale,
+		    orc_burst_result *res, float *soft, int soft_stride, int flags)
+{
+	pull_batch_any(iq, NULL, n_bursts, burst_len, sps, params, threshold, full_scale, res, soft, soft_stride, flags);
+}
+
+/* the same for bursts that are fp32 already (the sigProcLib-signature callers: samples as the radio interface scaled them) */
+void orc_pull_batch_cf32(const orc_cf *iq, size_t n_bursts, int burst_len, int sps,
+			 const orc_burst_params *params, float threshold, double full_scale,
+			 orc_burst_result *res, float *soft, int soft_stride, int flags)
+{
+	pull_batch_any(NULL, iq, n_bursts, burst_len, sps, params, threshold, full_scale, res, soft, soft_stride, flags);
 }
 
 /* ----------------------------------------------------------------------------------------

@@ -140,10 +140,20 @@ typedef struct {
 } orc_burst_result;
 
 /* iq: n_bursts x burst_len x (I,Q) int16.  soft: n_bursts x soft_stride floats
- * (sliced 0..1 rx_burst when slice!=0, else raw demodAnyBurst output). */
+ * (sliced 0..1 rx_burst with ORC_PULL_SLICE, else raw demodAnyBurst output).
+ * flags: ORC_PULL_* bits, nothing else (0 = raw rows, ORC_PULL_SLICE = 1 = sliced rows, as the former `slice` argument).
+ * ORC_PULL_IDLE_DUMMY searches IDLE slots with detectDummyBurst (sigProcLib.cpp:1863-1877), as
+ * detectAnyBurst(IDLE) does, instead of skipping them the way pullRadioVector does (rc = IDLE on a hit).
+ * 1 SPS, raw rows: GMSKReverseRotation1 ends at 157 entries (sigProcLib.cpp:207); positions >= 157 of a longer burst are 0. */
+#define ORC_PULL_SLICE      1
+#define ORC_PULL_IDLE_DUMMY 4
 void orc_pull_batch(const int16_t *iq, size_t n_bursts, int burst_len, int sps,
 		    const orc_burst_params *params, float threshold, double full_scale,
-		    orc_burst_result *res, float *soft, int soft_stride, int slice);
+		    orc_burst_result *res, float *soft, int soft_stride, int flags);
+/* the same over fp32 bursts (n_bursts x burst_len complex): no convert_short_float in front */
+void orc_pull_batch_cf32(const orc_cf *iq, size_t n_bursts, int burst_len, int sps,
+			 const orc_burst_params *params, float threshold, double full_scale,
+			 orc_burst_result *res, float *soft, int soft_stride, int flags);
 /* the same with n_paths diversity paths per burst (Transceiver.cpp:723-751): iq is n_bursts x n_paths x burst_len x 2 */
 void orc_pull_batch_div(const int16_t *iq, size_t n_bursts, int n_paths, int burst_len, int sps,
 			const orc_burst_params *params, float threshold, double full_scale,

@@ -552,7 +552,7 @@ diversity_power_kernel(trxhip_burst_result *__restrict__ res, const trxhip_burst
 			continue;
 		const float e = avg_energy[b];
 		res[b].energy = e;
-		res[b].rssi = 6.02059991f * __log2f(full_scale) - 3.01029996f * __log2f(e);
+		res[b].rssi = 6.02059991f * __log2f(full_scale * __builtin_amdgcn_rsqf(e));   // as rssi_db() (trx_device.h)
 	}
 }
 

@@ -306,6 +306,15 @@ __device__ __forceinline__ trx_v2f pk_mul_tap(trx_v2f x, trx_v2f hpair)
 
 // Complex.h:113 norm2(): i*i + r*r
 __device__ __forceinline__ float norm2(c32 v) { return v.y * v.y + v.x * v.x; }
+// 20*log10(full_scale / sqrt(energy)) (Transceiver.cpp:741,751) as ONE logarithm, of the ratio the reference forms.  Assumption:
+// the caller's full_scale belongs to the scale of its samples (complex64 callers choose both), so that the RSSI itself is a few
+// tens of dB and |log2| of the ratio stays below ~10; then the hardware logarithm's error and the product's rounding stay below
+// 1e-5 dB at any such scale.  (20 log10(fs) - 10 log10(e) loses that: two terms of ~200 dB
+// at samples of 1e10 are each rounded to 1.5e-5 dB.)  energy = 0 gives +inf as in the reference.
+__device__ __forceinline__ float rssi_db(float full_scale, float energy)
+{
+	return 6.02059991f * __log2f(full_scale * __builtin_amdgcn_rsqf(energy));
+}
 
 // ------------------------------------------------------------------------------------------------
 // Correlation against a GMSK training sequence without multiplications -- and still bit-identical to

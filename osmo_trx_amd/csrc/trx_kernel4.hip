@@ -291,7 +291,6 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 		pool_g[threadIdx.x] = K4_POOL_UNSET;
 	__syncthreads();
 
-	const float fs_db = 6.02059991f * __log2f(full_scale);          // 20*log10(full_scale)
 	// Work distribution.  The workgroup owns every gridDim.x-th group of 16 bursts ("items" j = 0, 1, ... in that order) and its
 	// waves CLAIM them one at a time from an LDS counter, one burst ahead (at prefetch time).  A static split -- the same number
 	// of bursts for every wave -- leaves the CU under-occupied for the last third of the kernel: the SIMD's issue arbitration
@@ -555,7 +554,7 @@ burst_pull4_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__re
 			clip = __ballot(amax > TRX_CLIP_THRESH) != 0ull;
 			epart = wave_sum_quad0(epart);                          // energyDetect partial sums (lanes = 0 mod 4 hold them)
 			energy = epart * 0.0125f;                               // energyDetect(burst, 20*sps): / 80
-			rssi = fs_db - 3.01029996f * __log2f(energy);       // 20*log10(fs/sqrt(e)), Transceiver.cpp:741,751
+			rssi = rssi_db(full_scale, energy);
 			wave_sync();
 			DIAG_MARK(1);
 

@@ -136,7 +136,6 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		pool_g[threadIdx.x] = NB_POOL_UNSET;
 	__syncthreads();
 
-	const float fs_db = 6.02059991f * __log2f(full_scale);          // 20*log10(full_scale)
 	// the peak-ratio gate's estimate (tools/gen_nb_asm.py, DETA): thresh^2 / num for the four possible term counts, and the
 	// constant term of its certain-pass bound
 	const float thr2 = thresh * thresh;
@@ -268,7 +267,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			const float amp_re = a0 - a2, amp_im = a1 + a3;         // amp = peak / gain (:1701): peak * (1 / gain), Complex.h:74
 			const float toa = (float)q_toa * 0.001953125f;          // position - sync->toa (:1704) - head (:1768): exact in 1/512
 			const float energy = __int_as_float(q_es) * 0.0125f;    // energyDetect(burst, 20 * sps): / 80
-			const float rssi = fs_db - 3.01029996f * __log2f(energy);
+			const float rssi = rssi_db(full_scale, energy);
 			const float p2 = xi * xi + xr * xr;
 			const float C = p2 * h[7];                              // |peak|^2 / ci_den (:1633), table: RN(1 / ci_den)
 			const float S = __int_as_float(q_s);
@@ -638,7 +637,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				if (__builtin_expect(pend_rm & ~leave & 1, 0)) {
 					// nothing found: rc (:1764), energy and RSSI (Transceiver.cpp:741,751), zero soft bits
 					const float energy = __int_as_float(es_bits) * 0.0125f;
-					const float rssi = fs_db - 3.01029996f * __log2f(energy);
+					const float rssi = rssi_db(full_scale, energy);
 					const uint32_t flags = ((uint32_t)clip << 8) | (1u << 16);
 					int word = clip ? -TRXHIP_SIGERR_CLIP : 0;
 					word = put_lane<1>(word, 0.0f);

@@ -95,7 +95,6 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 		*wg_next = waves_per_block;
 	__syncthreads();
 
-	const float fs_db = 6.02059991f * __log2f(full_scale);          // 20*log10(full_scale)
 	const PeakConst pkc = peak_const(threadIdx.x & (WAVE - 1));      // lane constants of the TOA bisection
 	// the workgroup's bursts are blockIdx.x, blockIdx.x + gridDim.x, ...; its waves claim them one ahead from an LDS counter
 	// (a static split leaves the CU under-occupied for the last third of the kernel, see burst_pull4_kernel)
@@ -198,7 +197,7 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 			clip = __ballot(amax > TRX_CLIP_THRESH) != 0ull;        // maxAmplitude() > 30000 (:1711-1722, :1746): some lane saw a larger component
 			// energyDetect(burst, 20*sps) (:1573-1585), tree-summed; RSSI (Transceiver.cpp:741,751) in fp32
 			energy = wave_sum(epart) / (float)win;
-			rssi = fs_db - 3.01029996f * __log2f(energy);           // 20*log10(fs/sqrt(e)), Transceiver.cpp:741,751
+			rssi = rssi_db(full_scale, energy);
 			wave_sync();
 
 			if (ebp_in) {
@@ -384,7 +383,9 @@ burst_pull_kernel(const void *__restrict__ iq_, const trxhip_burst_params *__res
 			} else {
 			nbits = 148;
 			if (so) {
-				const int nwrite = (slice & 1) ? nbits : nsoft;
+				// GMSKReverseRotation1 has 157 entries (sigProcLib.cpp:207): a 1-SPS burst longer than that has no rotation
+				// for its last samples in the reference; those raw values are 0 here (include/trxhip.h), rrot is read below 157
+				const int nwrite = (slice & 1) ? nbits : (nsoft < 157 ? nsoft : 157);
 				for (int i = lane; i < soft_stride; i += WAVE) {
 					float sv = 0.0f;
 					if (i < nwrite) {

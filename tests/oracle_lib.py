@@ -117,6 +117,7 @@ def lib():
     L.orc_modulate_edge_burst.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.orc_pull_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_double,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    L.orc_pull_batch_cf32.argtypes = L.orc_pull_batch.argtypes
     L.orc_pull_batch_div.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.orc_trxd_toa256.restype = C.c_int
@@ -249,15 +250,31 @@ def demod_any_burst(burst, ctype, sps, ebp):
     return soft[:max(n, 0)].copy()
 
 
-def pull_batch(iq, sps, params, threshold=4.0, full_scale=32767.0, soft_stride=148, slice_bits=True):
-    """iq: int16[n, burst_len, 2]; params: PARAMS_DTYPE[n]. Returns (RESULT_DTYPE[n], float32[n, soft_stride])."""
+PULL_SLICE, PULL_IDLE_DUMMY = 1, 4                      # ORC_PULL_* (oracle/trx_oracle.h)
+
+
+def pull_batch(iq, sps, params, threshold=4.0, full_scale=32767.0, soft_stride=148, slice_bits=True, idle_dummy=False):
+    """iq: int16[n, burst_len, 2]; params: PARAMS_DTYPE[n]. Returns (RESULT_DTYPE[n], float32[n, soft_stride]).
+    idle_dummy: IDLE slots are searched with detectDummyBurst (rc = IDLE on a hit), as under TRXHIP_FLAG_IDLE_DUMMY."""
     iq = np.ascontiguousarray(iq, dtype=np.int16)
     n, burst_len = iq.shape[0], iq.shape[1]
     params = np.ascontiguousarray(params, dtype=PARAMS_DTYPE)
     res = np.zeros(n, dtype=RESULT_DTYPE)
     soft = np.zeros((n, soft_stride), dtype=np.float32)
     lib().orc_pull_batch(_ptr(iq), n, burst_len, sps, _ptr(params), threshold, full_scale,
-                         _ptr(res), _ptr(soft), soft_stride, 1 if slice_bits else 0)
+                         _ptr(res), _ptr(soft), soft_stride, (PULL_SLICE if slice_bits else 0) | (PULL_IDLE_DUMMY if idle_dummy else 0))
+    return res, soft
+
+
+def pull_batch_cf32(x, sps, params, threshold=4.0, full_scale=32767.0, soft_stride=148, slice_bits=True, idle_dummy=False):
+    """pull_batch for bursts that are fp32 already: x complex64[n, burst_len] (no convert_short_float in front)."""
+    x = np.ascontiguousarray(x, dtype=np.complex64)
+    n, burst_len = x.shape[0], x.shape[1]
+    params = np.ascontiguousarray(params, dtype=PARAMS_DTYPE)
+    res = np.zeros(n, dtype=RESULT_DTYPE)
+    soft = np.zeros((n, soft_stride), dtype=np.float32)
+    lib().orc_pull_batch_cf32(_ptr(x), n, burst_len, sps, _ptr(params), threshold, full_scale,
+                              _ptr(res), _ptr(soft), soft_stride, (PULL_SLICE if slice_bits else 0) | (PULL_IDLE_DUMMY if idle_dummy else 0))
     return res, soft
 
 

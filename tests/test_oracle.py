@@ -424,3 +424,31 @@ def test_stage_vectors_of_the_reference_kernels(golden_dir):
         assert np.array_equal(got.view(np.float32), v["delay"][k]), k
     L.orc_resampler_free(r)
     assert i_nb == 33 and i_ab == 32
+
+
+def test_pull_batch_cf32_idle_dummy_and_rows_past_the_rotation_table():
+    """orc_pull_batch_cf32 shares orc_pull_batch's per-burst body: integer-valued complex64 gives the int16 entry's bytes.
+    ORC_PULL_IDLE_DUMMY searches IDLE slots with detectDummyBurst (rc = IDLE, bi->idle cleared on a hit) and is off by
+    default.  At 1 SPS a raw row has values for i < 157 (GMSKReverseRotation1, sigProcLib.cpp:207) and zeros behind."""
+    import instance_inputs as I
+    from osmo_trx_amd import synth
+    for sps, L in ((4, 625), (1, 192)):
+        iq, params, _ = synth.make_normal_bursts(64, "cpu", sps, seed=21, burst_len=L)
+        kw = dict(soft_stride=200, slice_bits=False)
+        r16, s16 = O.pull_batch(iq.numpy(), sps, params, **kw)
+        r32, s32 = O.pull_batch_cf32(I.as_cf32(iq).numpy(), sps, params, **kw)
+        assert r16.tobytes() == r32.tobytes() and s16.tobytes() == s32.tobytes() and (r16["rc"] > 0).sum() > 50
+        det = r16["rc"] > 0
+        n_raw = 156 if sps == 4 else 157
+        assert s16[det][:, n_raw - 1].any() and not s16[:, n_raw:].any()
+    iq, params = I.dummy_bursts_1sps(64, 156, seed=22)
+    r0, _ = O.pull_batch(iq.numpy(), 1, params, threshold=1.5)
+    assert (r0["rc"] == 0).all() and (r0["idle"] == 1).all() and (r0["energy"] > 0).all()
+    r1, s1 = O.pull_batch(iq.numpy(), 1, params, threshold=1.5, idle_dummy=True)
+    hit = r1["rc"] == O.IDLE
+    assert hit.sum() > 48 and (r1["idle"][hit] == 0).all() and (r1["tsc"] == 0).all() and (r1["nbits_div4"][hit] == 37).all()
+    for b in np.where(hit)[0][:8]:
+        x = iq[b].numpy().astype(np.float32).view(np.complex64).reshape(-1)
+        rc, e = O.detect_any_burst(x, 0, 1.5, 1, O.IDLE, int(params["max_toa"][b]))
+        assert rc == O.IDLE and r1["toa"][b] == np.float32(e.toa)
+        assert np.array_equal(s1[b], np.clip(0.5 * (O.demod_any_burst(x, rc, 1, e)[:148] + 1.0), 0.0, 1.0).astype(np.float32))

@@ -63,6 +63,36 @@ def test_oracle_and_table_generator_under_asan_ubsan(tmp_path):
                 std::vector<orc_burst_result> res(16);
                 std::vector<float> so(16 * 148);
                 orc_pull_batch(iq.data(), 16, L, sps, prm.data(), 4.0f, 32767.0, res.data(), so.data(), 148, 1);
+                if (sps != 1) continue;
+                // 1 SPS, every accepted kind of length, raw rows: a detected normal burst (TSC 0) so that the demodulator's
+                // reverse rotation runs over the whole burst -- its table has 157 entries -- through both batch entries
+                uint8_t bits[148] = {0};
+                const char *tsc0 = "00100101110000100010010111";
+                for (int i = 3; i < 145; i++) { s = s * 1103515245u + 12345u; bits[i] = (s >> 20) & 1; }
+                for (int i = 0; i < 26; i++) bits[61 + i] = (uint8_t)(tsc0[i] - '0');
+                orc_cf wave[160];
+                if (orc_modulate_burst(bits, 148, 8, 1, 0, wave) != 156) return 4;
+                const int lens[4] = {148, 156, 157, 192};
+                for (int L1 : lens) {
+                    std::vector<int16_t> iq1(4 * L1 * 2, 0);
+                    std::vector<orc_cf> cf1(4 * L1);
+                    for (int b = 0; b < 4; b++)
+                        for (int i = 0; i < L1; i++) {
+                            const float re = i < 156 ? 8000.0f * wave[i].re : 0.0f, im = i < 156 ? 8000.0f * wave[i].im : 0.0f;
+                            iq1[(b * L1 + i) * 2] = (int16_t)re; iq1[(b * L1 + i) * 2 + 1] = (int16_t)im;
+                            cf1[b * L1 + i].re = re / 32768.0f; cf1[b * L1 + i].im = im / 32768.0f;
+                        }
+                    for (int i = 0; i < 4; i++) { prm[i].type = ORC_TSC; prm[i].tsc = 0; prm[i].max_toa = 3 + 30 * (i & 1); prm[i].reserved = 0; }
+                    const int strides[2] = {L1, 200};
+                    for (int stride : strides) {
+                        std::vector<float> raw(4 * stride);                   // exactly the rows: a write past a row is caught too
+                        orc_pull_batch(iq1.data(), 4, L1, 1, prm.data(), 4.0f, 32767.0, res.data(), raw.data(), stride, 0);
+                        if (res[0].rc != ORC_TSC) return 5;
+                        orc_pull_batch_cf32(cf1.data(), 4, L1, 1, prm.data(), 4.0f, 1.0, res.data(), raw.data(), stride, 0);
+                        if (res[0].rc != ORC_TSC) return 6;
+                        for (int i = 157; i < stride; i++) if (raw[i] != 0.0f) return 7;
+                    }
+                }
             }
             float soft[444];
             for (int i = 0; i < 444; i++) soft[i] = (float)(i % 7) / 6.0f;
