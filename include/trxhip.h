@@ -669,6 +669,112 @@ int  trxhip_tx_sched_render_frontend(trxhip_tx_sched *s, size_t n_slots, trxhip_
 int  trxhip_tx_sched_plan(const trxhip_tx_sched *s, int chan, trxhip_tx_plan *h_out, size_t n);   /* the last render's first n slots */
 int  trxhip_tx_sched_counters(const trxhip_tx_sched *s, int chan, trxhip_tx_sched_ctrs *out);
 
+/* ---- uplink burst scheduler: each channel's receive sample stream to TRXD uplink indications ----
+ * The counterpart of the downlink scheduler, for batch callers ("radio samples in, datagrams out"): what lies between
+ * trxhip_rx_frontend_pull() and the wire in the reference --
+ *   RadioInterface::driveReceiveRadio()        radioInterface.cpp:240-294   (cut the stream into slots, keep the receive clock)
+ *   Transceiver::pullRadioVector(), its head   Transceiver.cpp:665-815      (burstTime, OFF, mute, power, noise ring, counters)
+ *   Transceiver::expectedCorrType()            Transceiver.cpp:513-601      (SETSLOT / HANDOVER state to the slot's CorrType)
+ *   Transceiver::driveReceiveFIFO()            Transceiver.cpp:1187-1224    (one TRXD v0 / v1 datagram per indication)
+ * Slot cutter: 4 SPS only, burstSize = 625 (a config with sps = 1 is TRXHIP_EINVAL; the 157 / 156 / 156 / 156 pattern stays
+ * out).  A pull appends its n_samples per channel to a remainder the object carries on the device and cuts slots
+ * `while (recvSz > burstSize)` -- strictly greater, as in the reference, so the remainder may hold exactly 625 samples.  All
+ * channels advance together.  Each cut slot takes the receive clock's (FN, TN), then incTN().  There is no FIFO between the
+ * cutter and the DSP, so the reference's "drop when 32 are queued" (radioInterface.cpp:277-280) has no counterpart.
+ * Slot time and type: burstTime = time + ul_fn_offset (GSM::Time::operator+=(int): FN modulo 2715648, the offset may be
+ * negative); type = expectedCorrType(burstTime, chan) over the combinations TRXHIP_COMB_*; mHandover[tn][ss] belongs to the
+ * object, not to a channel; tsc = mTSC; max_toa = mMaxExpectedDelayAB for RACH / EXT_RACH, else mMaxExpectedDelayNB (:757-758;
+ * 63 and 30 until set_max_toa).  Settings changed between pulls apply to the slots cut by later pulls.
+ * Per slot, in pullRadioVector()'s order: OFF -- nothing (no datagram, no power, no noise update; the record carries fn, tn and
+ * the OFF flag).  Muted channel -- an idle indication with rssi 0, noise ring untouched, no DSP: v1 sends an idle datagram with
+ * rssi byte 0, v0 nothing.  Otherwise avg = sqrt(energy) (float, correctly rounded; one diversity path).  IDLE --
+ * mNoises.insert(avg), mNoiseLev = mNoises.avg() (20 entries summed in float in index order, / 20.0f), an idle indication.
+ * Any other type -- trxhip_detect_demod_batch[_cf32] with TRXHIP_FLAG_SLICE (and cfg.flags): rc <= 0 is an idle indication,
+ * rc == -TRXHIP_SIGERR_CLIP counts in rx_clipping, any other negative rc in rx_no_burst_detected; rx_empty_burst stays 0.
+ * Outputs of a pull that cuts n slots, device buffers indexed [chan * n + slot]:
+ *   d_pkt, d_pkt_len : datagram rows of pkt_stride bytes and their lengths, exactly trxhip_pack_trxd_wire_batch()'s (one call
+ *                      per channel with its version and rssi_offset over the slot's result record)
+ *   d_ind            : trxhip_ul_ind records; rc, toa, ci, tsc, rssi, nbits as trxhip_burst_result has them (rssi in dBFS without
+ *                      rssi_offset); noise_lev = mNoiseLev after this slot.  The reference's bi->noise,
+ *                      20 log10(rxFullScale / mNoiseLev) + rssi_offset in double, is the caller's to take from noise_lev
+ *   d_soft (or NULL) : sliced soft bits, 148 floats per slot, 444 with cfg.egprs.  The wire packer reads these rows, so the first
+ *                      pull without d_soft allocates the object's own chans * max_slots rows (592 or 1776 bytes each: 155 MB at
+ *                      one channel and 2^18 slots, 14.9 GB at the limits of the config) with hipMalloc, which may wait for the
+ *                      device (TRXHIP_ENOMEM, state untouched, when it fails); a caller that always passes d_soft never pays it
+ * Alignment: d_pkt, d_ind and d_soft 4 bytes, d_pkt_len 2.  Besides the rows every object holds 64 bytes per slot of
+ * chans * max_slots for parameters, meta, result records and ring positions.
+ * Waiting: trxhip_rx_sched_counters() and _noise_state() wait for the pulls issued so far; create waits for its own
+ * initialisation; nothing else in the scheduler waits and nothing calls hipDeviceSynchronize (the detect entry point keeps its own rule, see trxhip_detect_demod_batch).
+ * Issue every pull of one object on one stream; one object is not thread-safe.  TRXHIP_EIO from a pull: destroy the object.
+ * ctx == NULL: a plan-only object (no device memory, inputs and outputs NULL): cutter, clock and trxhip_rx_sched_plan() as on
+ * the GPU.  Every refused argument (config, chan, tn, ss, comb, version, sps != 4, a pull before set_clock, more slots than
+ * max_slots or out_slots, a missing or misaligned buffer, int16 and complex64 pulls mixed over a carried remainder) is
+ * TRXHIP_EINVAL and leaves the state untouched. */
+#define TRXHIP_ULIND_OFF    1   /* type OFF: nothing is sent (pullRadioVector() returns -ENOENT) */
+#define TRXHIP_ULIND_MUTED  2   /* the channel was muted */
+#define TRXHIP_ULIND_IDLE   4   /* bi->idle */
+typedef struct trxhip_ul_ind {
+	uint32_t fn;             /* burstTime */
+	uint8_t  tn;
+	uint8_t  type;           /* enum trxhip_corr_type the slot was searched for */
+	uint8_t  flags;          /* TRXHIP_ULIND_* */
+	uint8_t  tsc;
+	int32_t  rc;
+	float    toa, ci, rssi;
+	float    noise_lev;      /* mNoiseLev after this slot */
+	uint16_t nbits;          /* 148, 444, or 0 */
+	uint16_t reserved;
+} trxhip_ul_ind;
+typedef struct trxhip_rx_plan {
+	uint32_t fn;             /* burstTime */
+	uint8_t  tn;
+	uint8_t  type;           /* expectedCorrType() */
+	uint16_t max_toa;
+} trxhip_rx_plan;
+typedef struct trxhip_rx_sched_ctrs {
+	uint64_t rx_empty_burst, rx_clipping, rx_no_burst_detected;
+} trxhip_rx_sched_ctrs;
+typedef struct trxhip_rx_sched_cfg {
+	int32_t  chans;          /* logical channels, 1..8 */
+	int32_t  sps;            /* 4 */
+	int32_t  tsc;            /* mTSC, 0..7 */
+	int32_t  ul_fn_offset;   /* cfg->ul_fn_offset, |offset| < 2715648 */
+	int32_t  ext_rach;       /* cfg->ext_rach */
+	int32_t  egprs;          /* cfg->egprs: soft rows of 444 */
+	int32_t  flags;          /* 0 or TRXHIP_FLAG_EXACT_DEMOD */
+	float    threshold;      /* TRXHIP_BURST_THRESH */
+	float    full_scale;     /* rxFullScale */
+	uint32_t reserved;
+	uint64_t max_slots;      /* the largest pull, slots per channel, 1 .. 2^20 */
+} trxhip_rx_sched_cfg;
+typedef struct trxhip_rx_sched trxhip_rx_sched;
+int  trxhip_rx_sched_create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out);
+void trxhip_rx_sched_destroy(trxhip_rx_sched *s);
+/* the receive clock: the (FN, TN) the next cut slot takes; fn < 2715648.  set_clock also drops the carried remainder */
+int  trxhip_rx_sched_set_clock(trxhip_rx_sched *s, uint32_t fn, int tn);
+int  trxhip_rx_sched_clock(const trxhip_rx_sched *s, uint32_t *fn, int *tn);
+int  trxhip_rx_sched_set_slot(trxhip_rx_sched *s, int chan, int tn, int comb);       /* SETSLOT */
+int  trxhip_rx_sched_set_handover(trxhip_rx_sched *s, int tn, int ss, int on);       /* HANDOVER / NOHANDOVER, ss 0..7 */
+int  trxhip_rx_sched_set_muted(trxhip_rx_sched *s, int chan, int muted);             /* RFMUTE */
+int  trxhip_rx_sched_set_trxd_version(trxhip_rx_sched *s, int chan, int version);    /* SETFORMAT: 0 or 1 */
+int  trxhip_rx_sched_set_rssi_offset(trxhip_rx_sched *s, int chan, float rssi_offset_db);
+int  trxhip_rx_sched_set_max_toa(trxhip_rx_sched *s, int max_toa_nb, int max_toa_ab);   /* SETMAXDLYNB / SETMAXDLY, 0..65535 */
+/* slots the next pull of n_samples will cut (it depends only on the carried count), or TRXHIP_EINVAL */
+int64_t trxhip_rx_sched_slots(const trxhip_rx_sched *s, size_t n_samples);
+/* n_samples samples of every channel: channel c's chunk at d_in + 2*c*in_stride (int16 I, Q / floats; 4- / 8-byte aligned;
+ * in_stride >= n_samples).  Slots that lie inside the chunk are read where they are.  out_slots: slots per channel the outputs
+ * hold; *n_slots (may be NULL) = slots cut; *n_carried (may be NULL) = samples carried per channel.  Asynchronous on `stream` */
+int  trxhip_rx_sched_pull_s16(trxhip_rx_sched *s, const int16_t *d_in, size_t in_stride, size_t n_samples, uint8_t *d_pkt,
+			      int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots,
+			      size_t *n_slots, size_t *n_carried, void *stream);
+int  trxhip_rx_sched_pull_cf32(trxhip_rx_sched *s, const float *d_in, size_t in_stride, size_t n_samples, uint8_t *d_pkt,
+			       int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots,
+			       size_t *n_slots, size_t *n_carried, void *stream);
+int  trxhip_rx_sched_plan(const trxhip_rx_sched *s, int chan, trxhip_rx_plan *h_out, size_t n);   /* the last pull's first n slots */
+int  trxhip_rx_sched_counters(trxhip_rx_sched *s, int chan, trxhip_rx_sched_ctrs *out);
+/* the channel's noise ring as the reference holds it: ring[20], the insert position (0..20) and mNoiseLev */
+int  trxhip_rx_sched_noise_state(trxhip_rx_sched *s, int chan, float *ring20, uint32_t *itr, float *lev);
+
 #ifdef __cplusplus
 }
 #endif

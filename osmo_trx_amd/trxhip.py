@@ -134,6 +134,22 @@ SYMBOLS = {
     "trxhip_tx_sched_render_frontend": (_I, [_VP, _SZ, _VP, _VP, _VP, _F, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
     "trxhip_tx_sched_plan": (_I, [_VP, _I, _VP, _SZ]),
     "trxhip_tx_sched_counters": (_I, [_VP, _I, _VP]),
+    "trxhip_rx_sched_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
+    "trxhip_rx_sched_destroy": (None, [_VP]),
+    "trxhip_rx_sched_set_clock": (_I, [_VP, C.c_uint32, _I]),
+    "trxhip_rx_sched_clock": (_I, [_VP, C.POINTER(C.c_uint32), C.POINTER(_I)]),
+    "trxhip_rx_sched_set_slot": (_I, [_VP, _I, _I, _I]),
+    "trxhip_rx_sched_set_handover": (_I, [_VP, _I, _I, _I]),
+    "trxhip_rx_sched_set_muted": (_I, [_VP, _I, _I]),
+    "trxhip_rx_sched_set_trxd_version": (_I, [_VP, _I, _I]),
+    "trxhip_rx_sched_set_rssi_offset": (_I, [_VP, _I, _F]),
+    "trxhip_rx_sched_set_max_toa": (_I, [_VP, _I, _I]),
+    "trxhip_rx_sched_slots": (C.c_int64, [_VP, _SZ]),
+    "trxhip_rx_sched_pull_s16": (_I, [_VP, _VP, _SZ, _SZ, _VP, _I, _VP, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
+    "trxhip_rx_sched_pull_cf32": (_I, [_VP, _VP, _SZ, _SZ, _VP, _I, _VP, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
+    "trxhip_rx_sched_plan": (_I, [_VP, _I, _VP, _SZ]),
+    "trxhip_rx_sched_counters": (_I, [_VP, _I, _VP]),
+    "trxhip_rx_sched_noise_state": (_I, [_VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(_F)]),
 }
 
 
@@ -767,6 +783,156 @@ class TxScheduler:
     def close(self):
         if getattr(self, "h", None):
             self.L.trxhip_tx_sched_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ULIND_OFF, ULIND_MUTED, ULIND_IDLE = 1, 2, 4         # TRXHIP_ULIND_*
+UL_IND_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("type", "u1"), ("flags", "u1"), ("tsc", "u1"), ("rc", "<i4"), ("toa", "<f4"),
+                         ("ci", "<f4"), ("rssi", "<f4"), ("noise_lev", "<f4"), ("nbits", "<u2"), ("reserved", "<u2")])
+RX_PLAN_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("type", "u1"), ("max_toa", "<u2")])
+RX_SCHED_COUNTERS = ("rx_empty_burst", "rx_clipping", "rx_no_burst_detected")
+assert UL_IND_DTYPE.itemsize == 32 and RX_PLAN_DTYPE.itemsize == 8
+
+
+class _RxSchedCfg(C.Structure):
+    _fields_ = [("chans", C.c_int32), ("sps", C.c_int32), ("tsc", C.c_int32), ("ul_fn_offset", C.c_int32), ("ext_rach", C.c_int32),
+                ("egprs", C.c_int32), ("flags", C.c_int32), ("threshold", C.c_float), ("full_scale", C.c_float),
+                ("reserved", C.c_uint32), ("max_slots", C.c_uint64)]
+
+
+class RxScheduler:
+    """Uplink burst scheduler (trxhip_rx_sched_*): each channel's receive stream in, TRXD uplink datagrams and indication
+    records out.  trx=None: a plan-only object (no GPU): pull(n_samples=...) only cuts and plans, plan() reads the plan back."""
+
+    def __init__(self, trx=None, chans=1, sps=4, tsc=0, ul_fn_offset=0, ext_rach=False, egprs=False, exact=False, threshold=4.0,
+                 full_scale=32767.0, max_slots=8 * 1024):
+        self.trx = trx
+        self.L = trx.L if trx is not None else load_library()
+        self.chans, self.full_scale = chans, float(full_scale)
+        self.soft_stride = 444 if egprs else 148
+        self.rssi_offset = [0.0] * chans
+        cfg = _RxSchedCfg(chans, sps, tsc, ul_fn_offset, int(bool(ext_rach)), int(bool(egprs)), FLAG_EXACT_DEMOD if exact else 0,
+                          threshold, full_scale, 0, max_slots)
+        h = _VP()
+        _check(self.L.trxhip_rx_sched_create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_rx_sched_create")
+        self.h = h
+        self._last = 0
+
+    def set_clock(self, fn, tn):
+        _check(self.L.trxhip_rx_sched_set_clock(self.h, fn, tn), "trxhip_rx_sched_set_clock")
+
+    def clock(self):
+        fn, tn = C.c_uint32(), _I()
+        _check(self.L.trxhip_rx_sched_clock(self.h, C.byref(fn), C.byref(tn)), "trxhip_rx_sched_clock")
+        return fn.value, tn.value
+
+    def set_slot(self, chan, tn, comb):
+        _check(self.L.trxhip_rx_sched_set_slot(self.h, chan, tn, comb), "trxhip_rx_sched_set_slot")
+
+    def set_handover(self, tn, ss, on=True):
+        _check(self.L.trxhip_rx_sched_set_handover(self.h, tn, ss, int(bool(on))), "trxhip_rx_sched_set_handover")
+
+    def set_muted(self, chan, muted):
+        _check(self.L.trxhip_rx_sched_set_muted(self.h, chan, int(bool(muted))), "trxhip_rx_sched_set_muted")
+
+    def set_trxd_version(self, chan, version):
+        _check(self.L.trxhip_rx_sched_set_trxd_version(self.h, chan, version), "trxhip_rx_sched_set_trxd_version")
+
+    def set_rssi_offset(self, chan, db):
+        _check(self.L.trxhip_rx_sched_set_rssi_offset(self.h, chan, db), "trxhip_rx_sched_set_rssi_offset")
+        self.rssi_offset[chan] = float(np.float32(db))
+
+    def set_max_toa(self, nb=30, ab=63):
+        _check(self.L.trxhip_rx_sched_set_max_toa(self.h, nb, ab), "trxhip_rx_sched_set_max_toa")
+
+    def slots(self, n_samples):
+        n = self.L.trxhip_rx_sched_slots(self.h, n_samples)
+        if n < 0:
+            _check(int(n), "trxhip_rx_sched_slots")
+        return int(n)
+
+    def pull(self, x=None, n_samples=None, pkt_stride=None, want_soft=False, stream=None):
+        """x: int16[chans, n, 2] or complex64[chans, n] device tensor (one chunk of every channel; a 1-channel object also takes
+        int16[n, 2] / complex64[n]); plan-only: n_samples.  Returns (n_slots, n_carried) for a plan-only object, otherwise
+        (pkt uint8[chans, n_slots, pkt_stride], pkt_len int16[chans, n_slots], ind uint8[chans, n_slots, 32] (UL_IND_DTYPE),
+        soft float32[chans, n_slots, 148 | 444] or None) device tensors."""
+        ns, nc = _SZ(), _SZ()
+        if self.trx is None:
+            _check(self.L.trxhip_rx_sched_pull_s16(self.h, None, 0, n_samples, None, 0, None, None, None, 0, C.byref(ns), C.byref(nc),
+                                                   None), "trxhip_rx_sched_pull_s16")
+            self._last = ns.value
+            return ns.value, nc.value
+        torch = self.trx.torch
+        s16 = x.dtype == torch.int16
+        if x.dim() == (2 if s16 else 1):
+            x = x.unsqueeze(0)
+        assert x.shape[0] == self.chans and (x.dtype == torch.complex64 or (s16 and x.shape[2] == 2)), (x.shape, x.dtype)
+        n_in = x.shape[1]
+        n = self.slots(n_in)
+        if pkt_stride is None:
+            pkt_stride = 160 if self.soft_stride == 148 else 456
+        dev = f"cuda:{self.trx.device}"
+        pkt = torch.empty((self.chans, n, pkt_stride), dtype=torch.uint8, device=dev)
+        plen = torch.empty((self.chans, n), dtype=torch.int16, device=dev)
+        ind = torch.empty((self.chans, n, 32), dtype=torch.uint8, device=dev)
+        soft = torch.empty((self.chans, n, self.soft_stride), dtype=torch.float32, device=dev) if want_soft else None
+        fn = self.L.trxhip_rx_sched_pull_s16 if s16 else self.L.trxhip_rx_sched_pull_cf32
+        _check(fn(self.h, self.trx._dev(x) if n_in else None, n_in, n_in, self.trx._dev(pkt), pkt_stride, self.trx._dev(plen),
+                  self.trx._dev(ind), self.trx._dev(soft) if soft is not None else None, n, C.byref(ns), C.byref(nc),
+                  self.trx._stream(stream)), "trxhip_rx_sched_pull")
+        assert ns.value == n
+        self._last = n
+        return pkt, plen, ind, soft
+
+    def plan(self, chan, n=None):
+        """RX_PLAN_DTYPE[n] of the last pull (default: all its slots)"""
+        n = self._last if n is None else n
+        a = np.zeros(n, dtype=RX_PLAN_DTYPE)
+        _check(self.L.trxhip_rx_sched_plan(self.h, chan, a.ctypes.data_as(_VP), n), "trxhip_rx_sched_plan")
+        return a
+
+    def counters(self, chan):
+        """waits for the pulls issued so far"""
+        a = np.zeros(3, dtype=np.uint64)
+        _check(self.L.trxhip_rx_sched_counters(self.h, chan, a.ctypes.data_as(_VP)), "trxhip_rx_sched_counters")
+        return dict(zip(RX_SCHED_COUNTERS, (int(x) for x in a)))
+
+    def noise_state(self, chan):
+        """(ring float32[20], itr, mNoiseLev float32); waits for the pulls issued so far"""
+        ring = np.zeros(20, dtype=np.float32)
+        itr, lev = C.c_uint32(), C.c_float()
+        _check(self.L.trxhip_rx_sched_noise_state(self.h, chan, ring.ctypes.data_as(_VP), C.byref(itr), C.byref(lev)),
+               "trxhip_rx_sched_noise_state")
+        return ring, itr.value, np.float32(lev.value)
+
+    @staticmethod
+    def ind_to_numpy(ind):
+        """uint8[chans, n, 32] device tensor -> UL_IND_DTYPE[chans, n]"""
+        a = ind.cpu().numpy()
+        return a.view(UL_IND_DTYPE).reshape(a.shape[:-1])
+
+    def ind_db(self, ind, chan):
+        """bi->rssi and bi->noise (Transceiver.cpp:750-752) of UL_IND_DTYPE records of channel chan, as float64 arrays: the record's
+        rssi (dBFS, the device's float, what the datagram's rssi byte is made from) + rssi_offset, and
+        20 log10(rxFullScale / mNoiseLev) + rssi_offset in double from the record's noise_lev.  OFF and muted slots give 0 (bi is
+        left as initialised, :697-699)."""
+        ind = np.asarray(ind)
+        sent = (ind["flags"] & (ULIND_OFF | ULIND_MUTED)) == 0
+        off = self.rssi_offset[chan]
+        with np.errstate(divide="ignore"):
+            rssi = np.where(sent, ind["rssi"].astype(np.float64) + off, 0.0)
+            noise = np.where(sent, 20.0 * np.log10(self.full_scale / ind["noise_lev"].astype(np.float64)) + off, 0.0)
+        return rssi, noise
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.trxhip_rx_sched_destroy(self.h)
             self.h = None
 
     def __del__(self):
