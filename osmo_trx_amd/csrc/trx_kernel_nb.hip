@@ -45,12 +45,22 @@
 // waves fill what is left: +0.5 % same box (5 rounds, three alternatives within +-0.3 % of it: profiles/r06_ab_runs.txt).
 typedef float v3f __attribute__((ext_vector_type(3)));
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) v2f lds_v2f;
 
 // byte address of an LDS object (what the ds_* instructions of the asm blocks take)
 template <typename T>
 __device__ __forceinline__ unsigned lds_addr(const T *p)
 {
 	return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) T *)p;
+}
+
+// the lane's number, for the cold paths of the burst loop: each derives its own where it starts (the loop's main path carries
+// none -- what it needs of the lane are the addresses made once in front of the loop)
+__device__ __forceinline__ int nb_lane_id()
+{
+	int lane;
+	asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+	return lane;
 }
 
 __global__ void __launch_bounds__(NB_WPB * WAVE)
@@ -64,6 +74,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	static_assert(NB_ASM_GDEC_OFF == (TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36) * 4, "tools/gen_nb_asm.py: LDS offset of the decimator taps");
 	static_assert(NB_ASM_DEC_MAX_NACT == 15 + NB_ASM_CORR_MAX_LEN, "tools/gen_nb_asm.py: DEC and CORR change form at the same window");
 	static_assert(NB_ASM_LSEQ_OFF == (NB_TABLES_FLOATS - 2 * 8 * 16) * 4, "tools/gen_nb_asm.py: LDS offset of the training-sequence taps");
+	static_assert(NB_ASM_AW_PD == (PH_M0 + 52) * 8 && NB_ASM_AW_D == K4_XS * 8 && NB_ASM_AW_CZ == (K4_XS + NB_D_LEN + TRX_CZ_PAD) * 8,
+		      "tools/gen_nb_asm.py: offsets of P, D[] and cz[] inside a wave's slice");
 	constexpr int NLD = 10;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	const int lane0 = threadIdx.x & (WAVE - 1);
@@ -187,7 +199,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		const unsigned bb = ((n_static_groups + (unsigned)g) << 4) + (jj & 15u);
 		return bb < n_bursts ? bb : NB_NO_BURST;
 	};
-	auto pool_draw = [&](unsigned jj, bool ended, int lane) {
+	auto pool_draw = [&](unsigned jj, bool ended) {
+		const int lane = nb_lane_id();
 		const unsigned k = (jj + 16u - items) >> 4;
 		int g = NB_POOL_END;
 		if (!ended) {
@@ -203,26 +216,50 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		}
 	};
 
+	// ---- what the burst loop needs of the lane and the wave, made ONCE and carried in registers: left to the compiler, each is
+	// rebuilt from the lane id wherever it is used -- 28 vector instructions per burst, two 32-bit multiplies among them, at the
+	// head of the chains the first LDS write and DEC's first read wait for.  Opaque copies: a value the compiler cannot see
+	// through is kept, not rematerialised.
+	//   a_p    byte address of the conversion's first row: P + (lane & 3) * PH_A + PH_M0 + (lane >> 2) of this wave's slice;
+	//          row r is offset 128 r of it
+	//   a_w    slice base + 8 * lane: P + PH_M0 + 52 + lane, D[lane], D[lane - 4 / - 19], cz[lane], cz[lane - 19] are
+	//          compile-time offsets of it in the blocks DEC, CORR and TAIL (tools/gen_nb_asm.py: NB_ASM_AW_*)
+	//   a_l4   4 * lane (prefetch rows 0..8, the lane constants' fetch in AMAX, the record's store), a_l4c 4 * min(lane, 48) (the
+	//          tenth prefetch row: no load goes behind word 624 of its burst), a_l16 16 * lane (DETA, TAIL)
+	//   a_st   byte offset of the lane's soft bits inside a burst's 148: lanes 2..49 (lane - 2) * 12 + 16, lanes 54 + 3 e: 4 e
+	unsigned a_p = lds_addr(wbase) + 8u * (unsigned)((lane0 & 3) * PH_A + PH_M0 + (lane0 >> 2));
+	unsigned a_w = lds_addr(wbase) + 8u * (unsigned)lane0;
+	unsigned a_l4 = 4u * (unsigned)lane0;
+	unsigned a_l4c = 4u * min((unsigned)lane0, 48u);
+	unsigned a_l16 = 16u * (unsigned)lane0;
+	unsigned a_st = (lane0 >= 54) ? 4u * (unsigned)((lane0 - 54) / 3) : (unsigned)(lane0 - 2) * 12u + 16u;
+	asm volatile("" : "+v"(a_p));
+	asm volatile("" : "+v"(a_w));
+	asm volatile("" : "+v"(a_l4));
+	asm volatile("" : "+v"(a_l4c));
+	asm volatile("" : "+v"(a_l16));
+	asm volatile("" : "+v"(a_st));
+
 	// ---- software prefetch of the next burst: ten dwords per lane + the slot's parameters
 	uint32_t pre_i[NLD];
 	uint32_t pre_prm = 0u;
-	auto prefetch = [&](unsigned bb, int lane) {
+	auto prefetch = [&](unsigned bb) {
 		pre_prm = reinterpret_cast<const uint32_t *>(params)[2 * (size_t)bb];
-		const uint32_t *src = iq + (size_t)bb * 625;
-		// (unsigned lane: the offset zero-extends, the loads take the scalar-base form -- no 64-bit vector address whose
+		const char *src = reinterpret_cast<const char *>(iq + (size_t)bb * 625);
+		// (an unsigned 32-bit byte offset: it zero-extends, the loads take the scalar-base form -- no 64-bit vector address whose
 		// high half the compiler would build in one of the destination registers, with a wait for vmcnt(0) in front)
-		const unsigned ul = (unsigned)lane & 63u;
+		const uint32_t *const row = reinterpret_cast<const uint32_t *>(src + a_l4);
 #pragma unroll
 		for (int r = 0; r < NLD - 1; r++)
-			pre_i[r] = __builtin_nontemporal_load(src + (unsigned)(r * WAVE) + ul);        // read once: streaming
+			pre_i[r] = __builtin_nontemporal_load(row + r * WAVE);                         // read once: streaming
 		// the tenth row has 49 words: lanes 49..63 re-read word 624 (never stored to the LDS).  An exec-masked load behind a
 		// "v_mov 0" made the compiler wait for vmcnt(0) -- the nine loads just issued -- in front of the v_mov (measured: -4 %)
-		pre_i[NLD - 1] = __builtin_nontemporal_load(src + (unsigned)((NLD - 1) * WAVE) + min(ul, 48u));
+		pre_i[NLD - 1] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(src + a_l4c) + (NLD - 1) * WAVE);
 	};
 	// items j < 16 * my_groups of the static range exist for every workgroup of a launch the launcher sizes (>= 1 group each)
 	const unsigned b_first = burst_of((unsigned)wave);
 	if (b_first != NB_NO_BURST)
-		prefetch(b_first, lane0);
+		prefetch(b_first);
 
 	// ---- deferred output (registers): o = the lane's three sliced soft bits, recw = the result record (lanes 0..7)
 	v3f o = { 0.0f, 0.0f, 0.0f };
@@ -233,24 +270,24 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	int left_any = 0;
 	// the three stores carry their own EXEC masks, ANDed with pend_m / taken from pend_rm: with nothing pending they store nothing,
 	// and no branch goes round them
-	auto store_pending = [&](const int lane) {
+	// (one offset register for both soft-bit stores: a lane is in at most one of their masks)
+	auto store_pending = [&]() {
 		float *const so = soft + (size_t)pend_b * 148;
 		int *const rp = reinterpret_cast<int *>(results + pend_b);
 		const float oe = o.x;
 		asm volatile("s_bfm_b64 exec, 48, 2\n\t"
-			     "s_and_b32 exec_lo, exec_lo, %8\n\t"
-			     "s_and_b32 exec_hi, exec_hi, %8\n\t"
-			     "global_store_dwordx3 %0, %1, %2 offset:16\n\t"
+			     "s_and_b32 exec_lo, exec_lo, %7\n\t"
+			     "s_and_b32 exec_hi, exec_hi, %7\n\t"
+			     "global_store_dwordx3 %0, %1, %2\n\t"
 			     "s_mov_b32 exec_lo, 0\n\t"
-			     "s_and_b32 exec_hi, %8, 0x92400000\n\t"
-			     "global_store_dword %3, %4, %2\n\t"
-			     "s_mov_b32 exec_lo, %9\n\t"
+			     "s_and_b32 exec_hi, %7, 0x92400000\n\t"
+			     "global_store_dword %0, %3, %2\n\t"
+			     "s_mov_b32 exec_lo, %8\n\t"
 			     "s_mov_b32 exec_hi, 0\n\t"
-			     "global_store_dword %5, %6, %7\n\t"
+			     "global_store_dword %4, %5, %6\n\t"
 			     "s_mov_b64 exec, -1\n\t"
 			     "s_nop 0"
-			     :: "v"((lane - 2) * 12), "v"(o), "s"(so), "v"((((lane - 54) * 11) >> 5) * 4), "v"(oe), "v"(lane * 4), "v"(recw), "s"(rp),
-			        "s"(pend_m), "s"(pend_rm)
+			     :: "v"(a_st), "v"(o), "s"(so), "v"(oe), "v"(a_l4), "v"(recw), "s"(rp), "s"(pend_m), "s"(pend_rm)
 			     : "memory", "scc");
 	};
 	// ---- the records of detected bursts are made 64 at a time: what computeCI / amp / toa / RSSI need of burst k of the batch
@@ -259,7 +296,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	// at a quarter of the rate among them), and one 32-byte store per record
 	int q_xr = 0, q_xi = 0, q_es = 0, q_toa = 0, q_s = 0, q_fl = 0, q_b = 0;
 	int q_n = 0;
-	auto flush_records = [&](const int lane) {
+	auto flush_records = [&]() {
+		const int lane = nb_lane_id();
 		if (lane < q_n) {
 			const float *const h = lhdr + 8 * (q_fl & 0xff);        // {gain, 1 / gain, ci_den, toa, n, 1 / ci_den} of the slot's sequence
 			const float xr = __int_as_float(q_xr), xi = __int_as_float(q_xi);
@@ -421,28 +459,28 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	// burst; the compiler joins the two branches in front of ONE copy of the prefetch loads, behind a flag -- kept apart, the
 	// pool branch's copy waited for vmcnt(0), the stores just issued, in front of its loads: tools/isa_guard_nb.py checks every copy)
 	const unsigned j_plain = (unsigned)uni((int)(!pooled ? items : items >= 16u ? items - 16u : 0u));
-	auto advance = [&](const int taken, const int lane) {
+	auto advance = [&](const int taken) {
 		j_next = (unsigned)taken;
 		if (__builtin_expect(j_next < j_plain, 1)) {
 			b_next = base16 + j_next;
 			DIAG_MARK(17);
-			prefetch(b_next, lane);
+			prefetch(b_next);
 		} else {
 			b_next = burst_of(j_next);
 			if (pooled && (j_next & 15u) == 0u && j_next + 16u >= items)
-				pool_draw(j_next, b_next == NB_NO_BURST && j_next >= items, lane);
+				pool_draw(j_next, b_next == NB_NO_BURST && j_next >= items);
 			DIAG_MARK(17);
 			if (b_next != NB_NO_BURST)
-				prefetch(b_next, lane);
+				prefetch(b_next);
 		}
 	};
 	// left to the general kernel: the burst's flag byte, and "something was left" (plain stores: a type-mixed batch leaves a
 	// million bursts, and a million atomics on one counter cost ten times the batch)
 	// ("something was left" once per wave: a million stores to one address serialise in the L2 like a million atomics)
-	auto mark_left = [&](const unsigned bb, const int lane) {
+	auto mark_left = [&](const unsigned bb) {
 		pend_m = 0;                                                 // nothing of this burst is stored
 		pend_rm = 0;
-		if (lane == 0) {
+		if (nb_lane_id() == 0) {
 			reinterpret_cast<uint8_t *>(redo + TRX_REDO_HDR)[bb] = 1;
 			if (!left_any)
 				__hip_atomic_store(redo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -451,15 +489,18 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		left_any = 1;
 	};
 	for (unsigned b = b_first; b != NB_NO_BURST; b = b_next) {
-		int lane;                                                  // re-materialised per burst (see burst_pull4_kernel)
-		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+		// (the prefetch offsets pass through an empty statement once per burst: the zero-extension of a value defined in front of
+		// the loop is hoisted there as a register pair, and the prefetch loads then take the 64-bit vector address after all.  No
+		// instruction, the same register.)
+		asm volatile("" : "+v"(a_l4));
+		asm volatile("" : "+v"(a_l4c));
 		const int ticket = claim_issue(wg_next);
 		const unsigned prm0 = (unsigned)uni((int)pre_prm);
 		// ---- is this a slot the kernel handles?  (a slot of another type is flagged before anything is spent on its samples)
 		const unsigned max_toa = prm0 >> 16;
 		const int tsc = (prm0 >> 8) & 0xff;
 #ifdef TRX_DIAG
-		DIAG_MARK(12);                                              // (loop top: mbcnt, ticket issue, slot type)
+		DIAG_MARK(12);                                              // (loop top: ticket issue, slot type)
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		DIAG_MARK(13);                                              // the prefetched samples' arrival, apart from their conversion
 #endif
@@ -471,34 +512,40 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 #pragma unroll
 			for (int r = 0; r < NLD; r++)
 				asm volatile("" :: "v"(pre_i[r]));
-			store_pending(lane);
-			advance(claim_take(ticket), lane);
-			mark_left(b, lane);
+			store_pending();
+			advance(claim_take(ticket));
+			mark_left(b);
 			continue;
 		}
 
 		// ---- phase 0: registers -> fp32 polyphase LDS; clip scan and energyDetect partial sums on the fly
-		c32 *const pload = P + (lane & 3) * PH_A + PH_M0 + (lane >> 2);
+		// (row r of the ten is offset 128 r of a_p: one address register, the offsets fit the 8-bit fields of ds_write2_b64)
+		lds_v2f *const pload = reinterpret_cast<lds_v2f *>(a_p);
 		float amax = 0.0f, epart = 0.0f;
 #pragma unroll
 		for (int r = 0; r < NLD; r++) {
-			const int i = r * WAVE + lane;
-			if (r < NLD - 1 || i < 625) {
-				const c32 v = make_float2((float)(int16_t)(pre_i[r] & 0xffffu), (float)(int16_t)(pre_i[r] >> 16));
+			const v2f v = { (float)(int16_t)(pre_i[r] & 0xffffu), (float)(int16_t)(pre_i[r] >> 16) };
+			// the tenth row has 49 samples: lanes 49..63 hold sample 624 once more (prefetch) -- the maximum may take it again,
+			// the LDS may not: the row is written under a constant mask, with no compare and no branch round it
+			if (r < NLD - 1)
 				pload[16 * r] = v;
-				asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v.x), "v"(v.y));
-				if (r < 5)
-					epart = fmaf(v.x, v.x, fmaf(v.y, v.y, epart));
-			}
+			else
+				asm volatile("s_bfm_b64 exec, 49, 0\n\t"
+					     "ds_write_b64 %0, %1 offset:%c2\n\t"
+					     "s_mov_b64 exec, -1"
+					     :: "v"(a_p), "v"(v), "n"(128 * (NLD - 1)) : "memory");
+			asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v.x), "v"(v.y));
+			if (r < 5)
+				epart = fmaf(v.x, v.x, fmaf(v.y, v.y, epart));
 		}
 		DIAG_MARK(14);
 		// ---- the previous burst's output: 148 soft bits (lanes 2..49: symbols 3 lane - 2 + j as one 12-byte store, lanes
 		// 54, 57, 60, 63: symbols 0..3) and the result record (lanes 0..7)
-		store_pending(lane);
+		store_pending();
 		DIAG_MARK(16);
 		// (a converted burst has at least five LDS writes behind the ticket's request -- ten rows, at most two per instruction --
 		// and nothing else on lgkmcnt: the ticket is there when five are outstanding, the writes drain under the next block)
-		advance(claim_take_behind<5>(ticket), lane);
+		advance(claim_take_behind<5>(ticket));
 		DIAG_MARK(15);
 
 		pend_m = 0;
@@ -513,15 +560,14 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			const int len = 16 + (int)max_toa;
 			__builtin_assume(len >= 16 && len <= 16 + NB_MAX_TOA);
 			// (hand-placed blocks: tools/gen_nb_asm.py)  decimator of the window + the addition-only correlation's guard
-			const unsigned vd_addr = lds_addr(D) + 8u * (unsigned)lane, vcz_addr = lds_addr(cz) + 8u * (unsigned)lane;
+			// (P, D[] and cz[] of this lane: compile-time offsets of a_w inside the blocks)
 			// (windows of up to NB_ASM_CORR_MAX_LEN lags: the accumulators of DEC and CORR move across the lanes -- decimated sample i
 			// ends in lane i + 4, lag k in lane k + NB_ASM_CORR_LANE0; wider windows: lane = sample / lag, the samples through LDS)
 			unsigned long long bad;
 			float dr, di;
 			asm volatile(NB_ASM_DEC
 				     : [bad] "=s"(bad), [dr] "=&v"(dr), [di] "=&v"(di)
-				     : [pd] "v"(lds_addr(P + PH_M0 + 52) + 8u * (unsigned)lane), [vd] "v"(vd_addr), [vd4] "v"(vd_addr - 32u), [zero] "v"(0),
-				       [nact] "s"(15 + len)
+				     : [aw] "v"(a_w), [zero] "v"(0), [nact] "s"(15 + len)
 				     : NB_ASM_CLOBBERS);
 			DIAG_MARK(2);
 			{
@@ -531,8 +577,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				const int lag0 = (len <= NB_ASM_CORR_MAX_LEN) ? NB_ASM_CORR_LANE0 : 0;   // lane of lag 0
 				asm volatile(NB_ASM_CORR
 					     : [nrm] "=&v"(v)
-					     : [vd] "v"(vd_addr), [vcz] "v"(vcz_addr), [vdm] "v"(vd_addr - 8u * NB_ASM_CORR_LANE0),
-					       [vczm] "v"(vcz_addr - 8u * NB_ASM_CORR_LANE0), [dr] "v"(dr), [di] "v"(di), [len] "s"(len), [tsc] "s"(tsc), [bad] "s"(bad)
+					     : [aw] "v"(a_w), [dr] "v"(dr), [di] "v"(di), [len] "s"(len), [tsc] "s"(tsc), [bad] "s"(bad)
 					     : NB_ASM_CLOBBERS);
 				DIAG_MARK(3);
 				int m_bits, es_bits, bidx;
@@ -544,7 +589,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					     "s_waitcnt lgkmcnt(0)"
 					     : [m] "=&s"(m_bits), [es] "=&s"(es_bits), [bidx] "=&s"(bidx), [kr] "=&v"(kr), [ka] "=&v"(ka), [kb] "=&v"(kb),
 					       [kic] "=&v"(kic), [ktp] "=&v"(ktp)
-					     : [nrm] "v"(v), [ep] "v"(epart), [l4] "v"(4 * lane), [lag0] "s"(lag0),
+					     : [nrm] "v"(v), [ep] "v"(epart), [l4] "v"(a_l4), [lag0] "s"(lag0),
 					       [lc] "n"((TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 64 + 5 * WAVE) * 4)
 					     : NB_ASM_CLOBBERS);
 				DIAG_MARK(4);
@@ -555,7 +600,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					float km;
 					asm volatile(NB_ASM_DETA
 						     : [st] "=&s"(st), [e] "=&s"(e512), [km] "=&v"(km)
-						     : [bidx] "s"(bidx), [len] "s"(len), [czb] "s"(lds_addr(cz)), [kr] "v"(kr), [ka] "v"(ka), [l16] "v"(16 * lane),
+						     : [bidx] "s"(bidx), [len] "s"(len), [czb] "s"(lds_addr(cz)), [kr] "v"(kr), [ka] "v"(ka), [l16] "v"(a_l16),
 						       [k5] "s"(gk5), [k6] "s"(gk6), [k7] "s"(gk7), [k8] "s"(gk8), [c0] "v"(gc0)
 						     : NB_ASM_CLOBBERS);
 					DIAG_MARK(5);
@@ -569,6 +614,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					}
 					if (__builtin_expect(st == 3, 0)) {
 						// an uncertified early / late decision on the path: the search again in the reference's operand order
+						const int lane = nb_lane_id();
 						if (lane == 0)
 							atomicAdd(&g_trx_fast_stats[0], 1ull);
 						PeakConst pkc;
@@ -583,7 +629,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					}
 					if (__builtin_expect(st == 2, 0)) {
 						leave = 1;                                          // the gate is too close to call for the estimate
-						if (lane == 0) atomicAdd(&g_trx_fast_stats[2], 1ull);
+						if (nb_lane_id() == 0) atomicAdd(&g_trx_fast_stats[2], 1ull);
 					}
 					if (__builtin_expect(st == 1, 1)) {
 						// computeCI, amp, toa, the result record, 1 / amp; then demodGmskBurst of the usual geometry (TAIL)
@@ -594,8 +640,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						asm volatile(NB_ASM_TAIL
 							     : [ok] "=&s"(ok), [ssum] "=&s"(s_bits), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2)
 							     : [toa] "s"(toa512), [xr] "s"(xr_bits), [xi] "s"(xi_bits), [t5] "s"(t5), [hdrb] "s"(lds_addr(lhdr) + 32u * (unsigned)tsc),
-							       [e8lo] "s"((unsigned)e8_addr), [e8hi] "s"((unsigned)(e8_addr >> 32)), [l16] "v"(16 * lane),
-							       [vd] "v"(vd_addr), [pb] "s"(lds_addr(P)), [cb] "s"(lds_addr(comp) + 4u * (K4_U0 + TRX_FUSED_SH)), [db] "s"(lds_addr(D)),
+							       [e8lo] "s"((unsigned)e8_addr), [e8hi] "s"((unsigned)(e8_addr >> 32)), [l16] "v"(a_l16),
+							       [aw] "v"(a_w), [pb] "s"(lds_addr(P)), [cb] "s"(lds_addr(comp) + 4u * (K4_U0 + TRX_FUSED_SH)), [db] "s"(lds_addr(D)),
 							       [kic] "v"(kic), [ktp] "v"(ktp)
 							     : NB_ASM_CLOBBERS);
 						DIAG_MARK(10);
@@ -606,6 +652,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						o.z = __builtin_amdgcn_fmed3f(fmaf(0.5f, d2, 0.5f), 0.0f, 1.0f);
 						if (__builtin_expect(!ok, 0)) {
 							// TOA outside the straight-line geometry (an early burst, or one later than 9 symbols): the general form
+							const int lane = nb_lane_id();
 							if (lane == 0) atomicAdd(&g_trx_fast_stats[3], 1ull);
 							const float *const h = lhdr + 8 * tsc;
 							const float xr = __int_as_float(xr_bits), xi = __int_as_float(xi_bits);
@@ -653,26 +700,18 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			}
 		}
 		if (__builtin_expect(leave, 0)) {
-			mark_left(b, lane);
+			mark_left(b);
 			continue;
 		}
 		pend_b = b;
 		pend_m = -1;
 		if (__builtin_expect(q_n == WAVE, 0))
-			flush_records(lane);
+			flush_records();
 		DIAG_MARK(11);
 	}
 	// ---- the last burst's output
-	{
-		int lane;
-		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-		store_pending(lane);
-	}
-	{
-		int lane;
-		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-		flush_records(lane);                                       // the records still in the registers
-	}
+	store_pending();
+	flush_records();                                               // the records still in the registers
 	DIAG_FLUSH();
 	if (pooled) {
 		__syncthreads();

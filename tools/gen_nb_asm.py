@@ -21,6 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "osmo_trx_amd", "csrc", "trx_nb_asm.inc")
 
 PH_A, PH_M0 = 180, 12
+# %[aw]: the one per-lane LDS address the blocks DEC, CORR and TAIL take -- the wave's slice base + 8 * lane, computed once in
+# front of the burst loop (trx_kernel_nb.hip: a_w).  What the blocks address is a compile-time byte offset of it in the ds_*
+# offset field (16 bits; a slice is 7.7 KB): the kernel static_asserts these against its LDS carve.
+NB_D_LEN, CZ_PAD = 160, 12
+AW_PD = (PH_M0 + 52) * 8                         # P + PH_M0 + (56 + lane) - 4
+AW_D = 4 * PH_A * 8                              # D[lane]
+AW_CZ = (4 * PH_A + NB_D_LEN + CZ_PAD) * 8       # cz[lane]
 TRANS = ("v_rcp_", "v_sqrt_", "v_log_", "v_exp_", "v_rsq_", "v_sin_", "v_cos_")
 NEG_MASKS = [0x447b, 0xc5bb, 0x7488, 0x7709, 0xa75c, 0xf60d, 0x4eb9, 0xdc21]   # TRX_UNIT_NEG_TSC0..7 (trx_device.h)
 
@@ -230,8 +237,9 @@ def sreg(i, n=1):
 # ------------------------------------------------------------------------------------------------------------------
 # block DEC: the /4 decimator of the detection window (downsampleBurst restricted to what the correlation and computeCI
 # read, sigProcLib.cpp:1587-1601) + the addition-only correlation's guard (unit_unsafe, trx_device.h).
-#   %[pd]   VGPR  LDS byte address of P + PH_M0 + (56 + lane) - 4     (polyphase burst, trx_k4_common.h)
-#   %[vd]   VGPR  LDS byte address of D[lane]          %[vd4] VGPR  LDS byte address of D[lane - 4]
+#   %[aw]   VGPR  slice base + 8 * lane: P + PH_M0 + (56 + lane) - 4 (polyphase burst, trx_k4_common.h) is offset AW_PD of it,
+#                 D[lane] offset AW_D, D[lane - 4] offset AW_D - 32 (ds_write2_b32's offsets have 8 bits: that one address is formed
+#                 in a wait state of the sum's last adds)
 #   %[zero] VGPR  0 (address of the wave-uniform tap reads)
 #   %[nact] SGPR  15 + len: decimated samples
 #   %[bad]  SGPR pair out: lanes whose decimated sample fails the guard
@@ -277,7 +285,7 @@ def dec_moving(gdec_off):
     b(f"ds_read_b128 {vreg(120, 4)}, %[zero] offset:{gdec_off}")
     b(f"ds_read_b128 {vreg(124, 4)}, %[zero] offset:{gdec_off + 16}")
     for r in (1, 2, 3, 0):
-        b(f"ds_read_b64 {XR(r)}, %[pd] offset:{r * PH_A * 8}")
+        b(f"ds_read_b64 {XR(r)}, %[aw] offset:{AW_PD + r * PH_A * 8}")
 
     def mul(k):
         b(f"v_pk_mul_f32 {vreg(PR(k), 2)}, {XR((k + 1) & 3)}, {dec_tap(k if k < 8 else 15 - k)}")
@@ -305,13 +313,14 @@ def dec_moving(gdec_off):
     add(13)
     b("s_nop 0")
     add(14)
-    b("s_nop 1")
+    b(f"v_add_u32_e32 v108, {AW_D - 8 * DEC_SHIFT}, %[aw]")        # &D[lane - 4] (one of the two wait states in front of the DPP source)
+    b("s_nop 0")
     out = ("%[dr]", "%[di]")
     add_moving(15, out)
     b(f"s_bfm_b64 exec, %[nact], {DEC_SHIFT}")                     # output l sits in lane l + 4
-    b("ds_write2_b32 %[vd4], %[dr], %[di] offset1:1")          # D[] stays: computeCI's samples (TAIL), the multiplying correlation
+    b("ds_write2_b32 v108, %[dr], %[di] offset1:1")          # D[] stays: computeCI's samples (TAIL), the multiplying correlation
     dec_guard(b, out[0], out[1], "v106", "v107")
-    b.exec_ok = {f"v{ACC}", f"v{ACC + 1}", "%[dr]", "%[di]"}       # (lanes 4 .. nact + 3 are inside the mask they were written under)
+    b.exec_ok = {f"v{ACC}", f"v{ACC + 1}", "%[dr]", "%[di]", "v108"}       # (lanes 4 .. nact + 3 are inside the mask they were written under)
     return b
 
 
@@ -323,7 +332,7 @@ def dec_wide(gdec_off):
     b(f"ds_read_b128 {vreg(124, 4)}, %[zero] offset:{gdec_off + 16}")
     for k in range(16):
         off = (((k + 1) & 3) * PH_A + ((k + 1) >> 2)) * 8
-        b(f"ds_read_b64 {X(k)}, %[pd] offset:{off}")
+        b(f"ds_read_b64 {X(k)}, %[aw] offset:{AW_PD + off}")
 
     def mul(k):
         b(f"v_pk_mul_f32 {X(k)}, {X(k)}, {dec_tap(k if k < 8 else 15 - k)}")
@@ -341,7 +350,7 @@ def dec_wide(gdec_off):
     mul(12); add(11); mul(13); add(12); mul(14); add(13); mul(15); add(14)
     b("s_nop 0")
     add(15)
-    b(f"ds_write_b64 %[vd], {X(0)}")
+    b(f"ds_write_b64 %[aw], {X(0)} offset:{AW_D}")
     dec_guard(b, "v88", "v89", "v90", "v91")
     return b
 
@@ -358,11 +367,11 @@ def block_dec(gdec_off):
 # ------------------------------------------------------------------------------------------------------------------
 # block CORR: correlation of the window against the slot's training sequence without multiplications (corr_unit,
 # trx_device.h: every tap is +-1 rotated by k pi/2 under the guard); arg-max input.
-#   %[vd]  VGPR  LDS byte address of D[lane]      %[vcz] VGPR  LDS byte address of cz[lane]
+#   %[aw]  VGPR  slice base + 8 * lane: D[lane] is offset AW_D of it, cz[lane] offset AW_CZ; the moving form's D[lane - 19] and
+#                cz[lane - 19] are 152 bytes below those
 #   %[len] SGPR  window length                    %[tsc] SGPR  training sequence 0..7
 #   %[nrm] VGPR out: |corr|^2 (0 for lanes that hold no lag)
-#   %[dr] %[di] VGPR the decimated sample of lane - 4 (block DEC); %[vdm] %[vczm] VGPR LDS byte addresses of D[lane - 19]
-#   and cz[lane - 19]
+#   %[dr] %[di] VGPR the decimated sample of lane - 4 (block DEC)
 # The sum is one chain by definition (the reference's order: k ascending from +0, convolve_base.c:28-54).  Eight variants
 # (the sign / component pattern of a training sequence), entered by a computed jump.
 #   * wide windows (more than 45 lags): lane = lag; D[lag + k] from LDS, one v_pk_add_f32 per tap (sign / swap are
@@ -415,7 +424,7 @@ def corr_lanes(lseq_off, sfx):
     h(f"v_mov_b64_e32 {ACC}, 0")
     h("s_bfm_b64 exec, %[len], 0")
     for k in range(16):
-        h(f"ds_read_b64 {X(k)}, %[vd] offset:{8 * k}")
+        h(f"ds_read_b64 {X(k)}, %[aw] offset:{AW_D + 8 * k}")
     h("s_cmp_lg_u64 %[bad], 0")                                    # a sample failed the guard: the multiplying form
     h(f"s_cbranch_scc1 .Lnb_corr{sfx}_mul")
     corr_jump(h, sfx)
@@ -441,7 +450,7 @@ def corr_lanes(lseq_off, sfx):
     j(f".Lnb_corr{sfx}_join:")
     j("s_add_u32 s90, %[len], 12")
     j("s_bfm_b64 exec, s90, 0")
-    j(f"ds_write_b64 %[vcz], {ACC}")
+    j(f"ds_write_b64 %[aw], {ACC} offset:{AW_CZ}")
     j("s_mov_b64 exec, -1")                         # (lanes >= len hold the 0 they were initialised with: |corr|^2 = 0 there)
     j(f"v_pk_mul_f32 v[122:123], {ACC}, {ACC}")
     j("s_waitcnt lgkmcnt(0)")
@@ -465,7 +474,7 @@ def corr_moving(lseq_off):
     h("v_mov_b32_e32 %[nrm], 0")
     h("s_lshl_b32 s90, %[len], 3")
     h(f"s_sub_u32 s91, {CORR_MAX_LEN}, %[len]")
-    h("v_add_u32_e32 v64, s90, %[vcz]")                             # &cz[len + lane]: the right zero pad, stored by lanes 0..11
+    h("v_add_u32_e32 v64, s90, %[aw]")                              # &cz[len + lane]: the right zero pad, stored by lanes 0..11
     h("s_lshr_b64 exec, -1, s91")                                  # lanes 0 .. len + 18: every lane that holds a sample or passes an accumulator on
     h("s_cmp_lg_u64 %[bad], 0")
     h(f"s_cbranch_scc1 .Lnb_corr{sfx}_mul")
@@ -493,9 +502,9 @@ def corr_moving(lseq_off):
     j = Block("j")
     j(f".Lnb_corr{sfx}_join:")
     j("s_bfm_b64 exec, 12, 0")
-    j("ds_write_b64 v64, v[122:123]")
+    j(f"ds_write_b64 v64, v[122:123] offset:{AW_CZ}")
     j(f"s_bfm_b64 exec, %[len], {CORR_LANE0}")
-    j(f"ds_write_b64 %[vczm], {ACC}")
+    j(f"ds_write_b64 %[aw], {ACC} offset:{AW_CZ - 8 * CORR_LANE0}")
     j(f"v_pk_mul_f32 v[124:125], {ACC}, {ACC}")
     j("s_nop 0")
     j("v_add_f32_e32 %[nrm], v125, v124")
@@ -506,7 +515,7 @@ def corr_moving(lseq_off):
     m(f".Lnb_corr{sfx}_mul:")
     m(f"s_bfm_b64 exec, %[len], {CORR_LANE0}")
     for k in range(16):
-        m(f"ds_read_b64 {X(k)}, %[vdm] offset:{8 * k}")
+        m(f"ds_read_b64 {X(k)}, %[aw] offset:{AW_D - 8 * CORR_LANE0 + 8 * k}")
     corr_mul(m, sfx, lseq_off, X, ACC)
     return h.ins, vs, j.ins, m.ins
 
@@ -863,7 +872,7 @@ def block_detb():
 #   * the result record: field k in lane k of one register (rc, toa, amp.re, amp.im, ci, energy, rssi, flags)
 #   in : SGPR toa (position * 512), xr / xi (peak value), t5 ((int)(sync->toa * 512)), hdrb (LDS byte address of the
 #        sequence header), e8lo / e8hi (address of tab->edge8), es (energy sum), fsdb (20 log10 full_scale), flags;
-#        VGPR l16 (16 * lane), vd (LDS byte address of D[lane]); SGPR pairs modd = 0xaaaa.., m23 = 0xcccc..
+#        VGPR l16 (16 * lane), aw (slice base + 8 * lane: D[lane] is offset AW_D of it); SGPR pairs modd = 0xaaaa.., m23 = 0xcccc..
 #   out: SGPR ok (0: TOA outside the straight-line geometry), nk; VGPR rows (4 registers), vp, rec
 # ------------------------------------------------------------------------------------------------------------------
 def block_tail():
@@ -888,9 +897,9 @@ def block_tail():
     b("s_cmp_lt_i32 %[toa], 0")
     b("s_cselect_b32 s96, s97, s96")
     b("s_lshl_b32 s96, s96, 3")
-    b("v_add_u32_e32 v64, s96, %[vd]")                             # &D[rt + lane]: sample ps + lane, ps = start + 1 - N + rt
+    b("v_add_u32_e32 v64, s96, %[aw]")                             # &D[rt + lane] - AW_D: sample ps + lane, ps = start + 1 - N + rt
     b("s_bfm_b64 exec, 16, 0")
-    b("ds_read_b64 v[66:67], v64")                                 # computeCI's sixteen samples (:1608-1639)
+    b(f"ds_read_b64 v[66:67], v64 offset:{AW_D}")                              # computeCI's sixteen samples (:1608-1639)
     b("s_mov_b64 exec, -1")
     b("s_waitcnt lgkmcnt(1)")
     # ---- every lane: amp = peak / gain (:1701), 1 / amp, the output stage's multiplier VP
@@ -1218,6 +1227,9 @@ def main(out=OUT):
            f"#define NB_ASM_DEC_MAX_NACT {DEC_MAX_NACT}",
            f"#define NB_ASM_CORR_LANE0 {CORR_LANE0}",
            f"#define NB_ASM_CORR_MAX_LEN {CORR_MAX_LEN}",
+           f"#define NB_ASM_AW_PD {AW_PD}",
+           f"#define NB_ASM_AW_D {AW_D}",
+           f"#define NB_ASM_AW_CZ {AW_CZ}",
            "#define NB_ASM_CLOBBERS " + ", ".join(f'"v{i}"' for i in range(64, 128)) + ", " +
            ", ".join(f'"s{i}"' for i in range(87, 100)) + ', "vcc", "scc", "memory"']
     for name, b in blocks.items():

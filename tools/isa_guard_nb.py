@@ -12,7 +12,11 @@ tests/test_isa_guard_cpu.py on every CPU run):
   * the work ticket is taken with a partial wait (lgkmcnt(5)), not a drain of the converted samples' LDS writes;
   * no spills, no scratch, 128 VGPRs (4 waves per SIMD), and the code size.
   * the stores of flush_records() do not lie on the loop's main path (they belong behind it: once per 64 bursts).
-Reported, not checked: the static instruction and branch counts of the main path outside the hand-placed blocks.
+  * what depends only on the lane and the wave is made once in front of the loop (the kernel's a_p, a_w, a_l4, ...): the main path
+    outside the hand-placed blocks holds no lane id (v_mbcnt_*) and none of the integer multiplies that addresses were built
+    with per burst (v_mul_lo_u32, v_mad_u64_u32, v_mul_u32_u24).
+Reported, not checked: the static instruction, vector-instruction and branch counts of the main path outside the hand-placed
+blocks.
 Prints a JSON summary; exit status 1 on a violation."""
 import json
 import os
@@ -26,6 +30,8 @@ sys.path.insert(0, ROOT)
 from osmo_trx_amd import build as B   # noqa: E402
 
 KERNEL = "_Z15nb_pull4_kernel"
+# per-lane work that belongs in front of the loop: the lane id and the slow integer multiplies of address arithmetic
+LANE_ONLY = re.compile(r"\s*(v_mbcnt_\w+|v_mul_lo_u32|v_mad_u64_u32|v_mul_u32_u24)\w*\s")
 
 
 def assembly(keep=None):
@@ -83,7 +89,7 @@ def check(text):
     rep = loop_report(body)
     main = rep["loop_main_path"]
     if main is None:
-        errs.append("the burst loop's main path was not found (first v_mbcnt_lo .. back edge behind the last `s_setprio 2`)")
+        errs.append("the burst loop's main path was not found (the ticket's ds_add_rtn_u32 .. back edge behind the last `s_setprio 2`)")
     else:
         # the join blocks that keep the loop's carried state in scalar registers are empty asm statements: a compiler that folds
         # them away brings flush_records() back into the loop, and with it the masks
@@ -91,30 +97,51 @@ def check(text):
             errs.append("flush_records' stores lie on the loop's main path")
         if not any(g[0] > main["first"] and g[-1] < main["last"] for g in groups[1:]):
             errs.append("no prefetch group on the loop's main path")
+        if main["lane_only_work_on_it"]:
+            errs.append(f"per-lane constants are rebuilt on the loop's main path: {main['lane_only_work_on_it']}")
     return errs, {"kernel": "nb_pull4_kernel", **res, "instructions": n_ins,
                   "prefetch_groups": [len(g) for g in groups], **rep}
 
 
 def loop_report(body):
-    """Reporting only: the burst loop's main path as laid out -- from the loop's lane id (the first v_mbcnt_lo of the kernel) to
-    the first branch behind block TAIL (the last `s_setprio 2`) that goes back to a label at the loop's head -- its branches
-    outside the hand-placed blocks, and whether flush_records' 16-byte stores lie on it."""
+    """The burst loop's main path as laid out -- from the loop header's label (the last one in front of the work ticket's
+    request, the kernel's first ds_add_rtn_u32) to the first branch behind block TAIL (the last `s_setprio 2`) that goes back to a label at the loop's head --
+    its instructions and branches outside every `asm` statement of the source, its vector instructions outside the generated
+    blocks (valu_outside_blocks: the short asm statements of the source -- the clip scan's v_max3, the record's moves -- count,
+    a statement that names one of the blocks' fixed registers v64..v127 does not), whether flush_records' 16-byte stores lie
+    on it, and what it holds of per-lane work that belongs in front of the loop."""
     try:
-        head = next(i for i, t in enumerate(body) if "v_mbcnt_lo_u32_b32" in t)
-        labels = {m.group(1) for t in body[max(0, head - 24):head] for m in [re.match(r"(\.LBB\d+_\d+):", t)] if m}
+        ticket = next(i for i, t in enumerate(body) if "ds_add_rtn_u32" in t)
+        head = max(i for i in range(ticket) if re.match(r"\.LBB\d+_\d+:", body[i]))
+        labels = {m.group(1) for t in body[max(0, head - 24):head + 1] for m in [re.match(r"(\.LBB\d+_\d+):", t)] if m}
         tail = max(i for i, t in enumerate(body) if re.match(r"\s*s_setprio 2", t))
         back = next(i for i in range(tail, len(body))
                     if (m := re.match(r"\s*s_c?branch\w*\s+(\.LBB\d+_\d+)", body[i])) and m.group(1) in labels)
     except (StopIteration, ValueError):
         return {"loop_main_path": None}
-    in_asm, branches, ins = False, 0, 0
+    in_asm, branches, ins, valu, lane_only, stmt = False, 0, 0, 0, [], []
+
+    def short_stmt():
+        nonlocal valu
+        if not any(re.search(r"\bv(6[4-9]|[7-9]\d|1[01]\d|12[0-7])\b|\bv\[(6[4-9]|[7-9]\d|1[01]\d|12[0-7]):", t) for t in stmt):
+            valu += sum(1 for t in stmt if re.match(r"\s*v_", t))
+            lane_only.extend(t.strip() for t in stmt if LANE_ONLY.match(t))
+
     for t in body[head:back + 1]:
         if "#ASMSTART" in t or "#ASMEND" in t:
-            in_asm = "#ASMSTART" in t
-        elif not in_asm and re.match(r"\s+[a-z_0-9]+(\s|$)", t) and not t.strip().startswith((".", ";")):
+            if in_asm and "#ASMEND" in t:
+                short_stmt()
+            in_asm, stmt = "#ASMSTART" in t, []
+        elif in_asm:
+            stmt.append(t)
+        elif re.match(r"\s+[a-z_0-9]+(\s|$)", t) and not t.strip().startswith((".", ";")):
             ins += 1
             branches += bool(re.match(r"\s*s_c?branch", t))
-    return {"loop_main_path": {"first": head, "last": back, "instructions_outside_blocks": ins, "branches_outside_blocks": branches,
+            valu += bool(re.match(r"\s*v_", t))
+            if LANE_ONLY.match(t):
+                lane_only.append(t.strip())
+    return {"loop_main_path": {"first": head, "last": back, "instructions_outside_blocks": ins, "valu_outside_blocks": valu,
+                               "branches_outside_blocks": branches, "lane_only_work_on_it": lane_only,
                                "flush_records_stores_on_it": any("global_store_dwordx4" in t for t in body[head:back + 1])}}
 
 
