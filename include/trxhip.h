@@ -676,11 +676,18 @@ int  trxhip_tx_sched_counters(const trxhip_tx_sched *s, int chan, trxhip_tx_sche
  *   Transceiver::pullRadioVector(), its head   Transceiver.cpp:665-815      (burstTime, OFF, mute, power, noise ring, counters)
  *   Transceiver::expectedCorrType()            Transceiver.cpp:513-601      (SETSLOT / HANDOVER state to the slot's CorrType)
  *   Transceiver::driveReceiveFIFO()            Transceiver.cpp:1187-1224    (one TRXD v0 / v1 datagram per indication)
- * Slot cutter: 4 SPS only, burstSize = 625 (a config with sps = 1 is TRXHIP_EINVAL; the 157 / 156 / 156 / 156 pattern stays
- * out).  A pull appends its n_samples per channel to a remainder the object carries on the device and cuts slots
- * `while (recvSz > burstSize)` -- strictly greater, as in the reference, so the remainder may hold exactly 625 samples.  All
+ * Slot cutter: at 4 SPS burstSize = 625; at 1 SPS -- the reference's default receive rate (DEFAULT_RX_SPS,
+ * CommonLibs/trx_vty.h:29), an object from trxhip_rx_sched_create_sps() -- burstSize = 156 + (tN % 4 == 0), recomputed after
+ * every incTN() (radioInterface.cpp:257-258, :283-288): slots of 157 / 156 / 156 / 156 samples from a TN that is a multiple of 4,
+ * 625 samples to four slots.  A pull appends its n_samples per channel to a remainder the object carries on the device and cuts
+ * slots `while (recvSz > burstSize)` -- strictly greater than the size of the slot that would be cut next, as in the reference,
+ * so the remainder may hold exactly 625 samples (1 SPS: 156 in front of a slot of 156, 157 in front of one of 157).  All
  * channels advance together.  Each cut slot takes the receive clock's (FN, TN), then incTN().  There is no FIFO between the
  * cutter and the DSP, so the reference's "drop when 32 are queued" (radioInterface.cpp:277-280) has no counterpart.
+ * At 1 SPS the slots inside a pull's chunk are read where they lie, like the 625-sample slots at 4 SPS, by an instance of the
+ * 1-SPS burst kernel that knows where slot k starts and how long it is; a slot's record and soft row are bit for bit those of
+ * trxhip_detect_demod_batch[_cf32](burst_len = 156 or 157, sps = 1) over that slot as a row.  energyDetect's window is 20 * sps
+ * samples (Transceiver.cpp:725).  Not at 1 SPS: EDGE (cfg.egprs; the reference forces 4 SPS for it, osmo-trx.cpp:485-490).
  * Slot time and type: burstTime = time + ul_fn_offset (GSM::Time::operator+=(int): FN modulo 2715648, the offset may be
  * negative); type = expectedCorrType(burstTime, chan) over the combinations TRXHIP_COMB_*; mHandover[tn][ss] belongs to the
  * object, not to a channel; tsc = mTSC; max_toa = mMaxExpectedDelayAB for RACH / EXT_RACH, else mMaxExpectedDelayNB (:757-758;
@@ -707,8 +714,10 @@ int  trxhip_tx_sched_counters(const trxhip_tx_sched *s, int chan, trxhip_tx_sche
  * initialisation; nothing else in the scheduler waits and nothing calls hipDeviceSynchronize (the detect entry point keeps its own rule, see trxhip_detect_demod_batch).
  * Issue every pull of one object on one stream; one object is not thread-safe.  TRXHIP_EIO from a pull: destroy the object.
  * ctx == NULL: a plan-only object (no device memory, inputs and outputs NULL): cutter, clock and trxhip_rx_sched_plan() as on
- * the GPU.  Every refused argument (config, chan, tn, ss, comb, version, sps != 4, a pull before set_clock, more slots than
- * max_slots or out_slots, a missing or misaligned buffer, int16 and complex64 pulls mixed over a carried remainder) is
+ * the GPU.  Every refused argument (config, chan, tn, ss, comb, version, sps other than 4 -- or 1 through
+ * trxhip_rx_sched_create_sps() --, egprs with sps = 1, a pull before set_clock, more slots than
+ * max_slots or out_slots, a missing or misaligned buffer, int16 and complex64 pulls mixed over a carried remainder -- by a
+ * device object, and by a plan-only one of sps = 1, where the entry point called names the format --) is
  * TRXHIP_EINVAL and leaves the state untouched. */
 #define TRXHIP_ULIND_OFF    1   /* type OFF: nothing is sent (pullRadioVector() returns -ENOENT) */
 #define TRXHIP_ULIND_MUTED  2   /* the channel was muted */
@@ -736,19 +745,22 @@ typedef struct trxhip_rx_sched_ctrs {
 } trxhip_rx_sched_ctrs;
 typedef struct trxhip_rx_sched_cfg {
 	int32_t  chans;          /* logical channels, 1..8 */
-	int32_t  sps;            /* 4 */
+	int32_t  sps;            /* 4; trxhip_rx_sched_create_sps() also takes 1 */
 	int32_t  tsc;            /* mTSC, 0..7 */
 	int32_t  ul_fn_offset;   /* cfg->ul_fn_offset, |offset| < 2715648 */
 	int32_t  ext_rach;       /* cfg->ext_rach */
-	int32_t  egprs;          /* cfg->egprs: soft rows of 444 */
-	int32_t  flags;          /* 0 or TRXHIP_FLAG_EXACT_DEMOD */
+	int32_t  egprs;          /* cfg->egprs: soft rows of 444; 0 with sps = 1 */
+	int32_t  flags;          /* 0 or TRXHIP_FLAG_EXACT_DEMOD (sps = 1: accepted, the 1-SPS kernels are exact already) */
 	float    threshold;      /* TRXHIP_BURST_THRESH */
 	float    full_scale;     /* rxFullScale */
 	uint32_t reserved;
 	uint64_t max_slots;      /* the largest pull, slots per channel, 1 .. 2^20 */
 } trxhip_rx_sched_cfg;
 typedef struct trxhip_rx_sched trxhip_rx_sched;
-int  trxhip_rx_sched_create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out);
+int  trxhip_rx_sched_create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out);   /* cfg->sps = 4 */
+/* the same with cfg->sps = 1 or 4: at 4 it is trxhip_rx_sched_create(); at 1 the object cuts 157 / 156 / 156 / 156 slots, its
+ * soft rows are 148 floats and cfg->egprs != 0 is TRXHIP_EINVAL.  Every other call takes either object */
+int  trxhip_rx_sched_create_sps(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out);
 void trxhip_rx_sched_destroy(trxhip_rx_sched *s);
 /* the receive clock: the (FN, TN) the next cut slot takes; fn < 2715648.  set_clock also drops the carried remainder */
 int  trxhip_rx_sched_set_clock(trxhip_rx_sched *s, uint32_t fn, int tn);
@@ -759,7 +771,8 @@ int  trxhip_rx_sched_set_muted(trxhip_rx_sched *s, int chan, int muted);        
 int  trxhip_rx_sched_set_trxd_version(trxhip_rx_sched *s, int chan, int version);    /* SETFORMAT: 0 or 1 */
 int  trxhip_rx_sched_set_rssi_offset(trxhip_rx_sched *s, int chan, float rssi_offset_db);
 int  trxhip_rx_sched_set_max_toa(trxhip_rx_sched *s, int max_toa_nb, int max_toa_ab);   /* SETMAXDLYNB / SETMAXDLY, 0..65535 */
-/* slots the next pull of n_samples will cut (it depends only on the carried count), or TRXHIP_EINVAL */
+/* slots the next pull of n_samples will cut (it depends only on the carried count and, at 1 SPS, on the clock's TN), or
+ * TRXHIP_EINVAL */
 int64_t trxhip_rx_sched_slots(const trxhip_rx_sched *s, size_t n_samples);
 /* n_samples samples of every channel: channel c's chunk at d_in + 2*c*in_stride (int16 I, Q / floats; 4- / 8-byte aligned;
  * in_stride >= n_samples).  Slots that lie inside the chunk are read where they are.  out_slots: slots per channel the outputs

@@ -36,6 +36,14 @@ int trx_launch_pull(const void *d_iq, int cf32, int nld, const trxhip_burst_para
 		    float *d_soft, const trx_tables *d_tab, const float *d_ebp_in, size_t n_bursts, int L, int sps, float thresh,
 		    float full_scale, int soft_stride, int flags, int n_cu, hipStream_t stream);
 size_t trx_pull_lds_bytes(int L, int waves_per_block);                 /* trx_kernels.hip */
+/* trx_kernels.hip: the stream form of the 1-SPS kernel, instance burst_pull_stream_kernel<cf32>, for the uplink scheduler.  d_iq:
+ * the first of n_slots slots of a 1-SPS receive stream that lie back to back, 157 samples where the slot's TN is a multiple of
+ * 4 and 156 elsewhere; tn_phase: that first slot's TN & 3.  Slot k is read where it lies, trx_rxs_slot_start() samples behind
+ * d_iq, and nothing outside the slots is read.  Slot k's record and soft row are those of burst_pull_kernel<1, cf32, 3> over a
+ * row of that slot's length, bit for bit.  flags: TRXHIP_FLAG_SLICE and the TRX_IFLAG_* bits */
+int trx_launch_pull_stream(const void *d_iq, int cf32, unsigned tn_phase, const trxhip_burst_params *d_params,
+			   trxhip_burst_result *d_results, float *d_soft, const trx_tables *d_tab, size_t n_slots, float thresh,
+			   float full_scale, int soft_stride, int flags, int n_cu, hipStream_t stream);
 
 int trx_fast_stats_read(unsigned long long *out4, int reset);          /* trx_kernel4.hip: the FAST detector's counters */
 int trx_unit_masks_match(const trx_tables *t);                        /* trx_kernel4.hip: compiled-in sign masks vs the tables */

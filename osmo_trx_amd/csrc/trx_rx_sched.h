@@ -3,6 +3,7 @@
 //   GSM::Time::operator+=(int)            GSM/GSMCommon.h:152-159     burstTime = time + ul_fn_offset (Transceiver.cpp:690)
 //   Transceiver::expectedCorrType()       Transceiver.cpp:513-601     with its three subslot tables
 //   max_toa                               Transceiver.cpp:757-758
+//   RadioInterface::driveReceiveRadio()   radioInterface.cpp:252-291   the slot cutter at 4 SPS (625) and at 1 SPS (157/156/156/156)
 // and the per-pull device state the kernels share.
 #pragma once
 #include <stddef.h>
@@ -18,6 +19,7 @@
 
 #define TRX_RXS_MAX_CHANS  8
 #define TRX_RXS_SLOT       625u            /* burstSize at 4 SPS, radioInterface.cpp:257-258 */
+#define TRX_RXS_SLOT1_MAX  157u            /* the longer burstSize at 1 SPS, radioInterface.cpp:257-258 */
 #define TRX_RXS_REM_STRIDE 640u            /* samples per channel of one half of the remainder area (it holds <= 625) */
 #define TRX_RXS_NOISE_CNT  20              /* mNoises(NOISE_CNT), Transceiver.h:48, Transceiver.cpp:64 */
 #define TRX_RXS_HYPERFRAME 2715648u        /* GSM::gHyperframe = 2048 * 26 * 51: a multiple of 26, 51, 52 and 102 */
@@ -184,4 +186,38 @@ TRX_RXS_HD inline uint64_t trx_rxs_slots(uint64_t carried, uint64_t n_samples)
 {
 	const uint64_t total = carried + n_samples;
 	return total ? (total - 1) / TRX_RXS_SLOT : 0;
+}
+
+/* ---- 1 SPS: burstSize = 156 + (tN % 4 == 0), recomputed after every incTN() (radioInterface.cpp:257-258, :283-288) ----
+ * tn0: the TN of slot 0 (the receive clock when the pull starts).  j0 = (4 - tn0) & 3 is the first slot of 157 samples; four
+ * consecutive slots are always 625 samples, eight 1250. */
+
+/* samples of slot k */
+TRX_RXS_HD inline uint32_t trx_rxs_slot_len(int tn0, uint64_t k)
+{
+	return 156u + (uint32_t)((((uint64_t)tn0 + k) & 3u) == 0u);
+}
+
+/* where slot k starts, in samples behind the start of slot 0: 156 k + the slots of 157 among 0 .. k - 1 */
+TRX_RXS_HD inline uint64_t trx_rxs_slot_start(int tn0, uint64_t k)
+{
+	const uint64_t j0 = (uint64_t)((4 - tn0) & 3);
+	return 156u * k + ((k + 3u - j0) >> 2);
+}
+
+/* `while (recvSz > burstSize)` over carried + n_samples samples with the clock at tn0: slot k is cut when more than its own
+ * length is left behind its start, i.e. when slot k + 1 starts before the stream's last sample -- the count is the largest m
+ * with trx_rxs_slot_start(m) <= total - 1.  The starts repeat every 4 slots, 625 samples on: whole groups by division, the rest
+ * by at most three compares.  Strict against the size of the slot that would be cut next: 156 samples stay in front of a slot
+ * of 156, 157 in front of one of 157. */
+TRX_RXS_HD inline uint64_t trx_rxs_slots1(int tn0, uint64_t carried, uint64_t n_samples)
+{
+	const uint64_t total = carried + n_samples;
+	if (!total)
+		return 0;
+	const uint64_t q = (total - 1) / TRX_RXS_SLOT, r = (total - 1) % TRX_RXS_SLOT;
+	uint64_t m = 0;
+	for (uint64_t i = 1; i < 4; i++)
+		m += trx_rxs_slot_start(tn0, i) <= r;
+	return 4 * q + m;
 }

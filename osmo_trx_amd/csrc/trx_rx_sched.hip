@@ -1,7 +1,8 @@
 // trx_rx_sched.hip -- the uplink burst scheduler: each channel's receive sample stream in, TRXD uplink indications out.
 //
 // The counterpart of trx_tx_sched.cpp.  It restates what the reference does between the radio's receive buffer and the wire:
-//   RadioInterface::driveReceiveRadio()        radioInterface.cpp:240-294   cut slots `while (recvSz > burstSize)`, incTN
+//   RadioInterface::driveReceiveRadio()        radioInterface.cpp:240-294   cut slots `while (recvSz > burstSize)`, incTN;
+//                                                                           burstSize 625 at 4 SPS, 157/156/156/156 at 1 SPS
 //   Transceiver::pullRadioVector()             Transceiver.cpp:665-815      burstTime, OFF, mute, power, noise ring, counters
 //   Transceiver::expectedCorrType()            Transceiver.cpp:513-601      (trx_rx_sched.h)
 //   noiseVector::insert() / avg()              radioVector.cpp:84-108
@@ -10,6 +11,8 @@
 // settings alone), rx_edge_kernel (the one slot per channel that straddles the carried remainder and the chunk; the new
 // remainder), trxhip_detect_demod_batch[_cf32] over the straddling rows and, per channel, over the slots that lie inside the
 // caller's chunk -- read where they are --, rx_ind_kernel (records, counters, noise ring), trx_launch_pack_trxd_wire per channel.
+// At 1 SPS the slots in the chunk are not one length apart: they go to burst_pull_stream_kernel (trx_launch_pull_stream), which
+// finds slot k from the run's first slot and its TN; the straddling rows, all of slot 0's length, take the batch entry point.
 // With ctx == NULL the object is plan-only: cutter, clock and plan, no device memory.
 #include <hip/hip_runtime.h>
 
@@ -90,22 +93,23 @@ rx_plan_kernel(const trx_rxs_settings st, uint32_t fn0, int tn0, uint32_t n_slot
 
 // ------------------------------------------------------------------------------------------------
 // rx_edge_kernel: one block per channel.  The stream of this pull is the carried remainder followed by the chunk.  Its first
-// 625 samples, when some of them are carried, are the one slot that does not lie in the caller's chunk: it is assembled into
-// edge_row.  The samples behind the last cut slot go to the OTHER half of the remainder area (the scheme of
-// rx_resamp_s16_kernel): nothing a pull reads is overwritten by it.  T: one IQ sample (uint32_t: int16 pair; float2).
+// slot0 samples (625; at 1 SPS slot 0's 157 or 156), when some of them are carried, are the one slot that does not lie in the
+// caller's chunk: it is assembled into edge_row, rows slot0 apart.  The samples from `cut` on, behind the last cut slot, go to the
+// OTHER half of the remainder area (the scheme of rx_resamp_s16_kernel): nothing a pull reads is overwritten by it.
+// T: one IQ sample (uint32_t: int16 pair; float2).
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
 rx_edge_kernel(const T *__restrict__ in, size_t in_stride, const T *__restrict__ rem_in, T *__restrict__ rem_out, uint32_t carried,
-	       uint32_t n_slots, uint32_t n_rem, T *__restrict__ edge_row)
+	       uint32_t n_slots, uint32_t slot0, size_t cut, uint32_t n_rem, T *__restrict__ edge_row)
 {
 	const int chan = blockIdx.x;
 	const T *x = in + (size_t)chan * in_stride;
 	const T *r = rem_in + (size_t)chan * TRX_RXS_REM_STRIDE;
 	if (n_slots && carried)
-		for (uint32_t i = threadIdx.x; i < TRX_RXS_SLOT; i += kThreads)
-			edge_row[(size_t)chan * TRX_RXS_SLOT + i] = i < carried ? r[i] : x[i - carried];
-	const size_t cut = (size_t)n_slots * TRX_RXS_SLOT;           /* < carried + n_samples; n_rem = the difference, <= 625 */
+		for (uint32_t i = threadIdx.x; i < slot0; i += kThreads)
+			edge_row[(size_t)chan * slot0 + i] = i < carried ? r[i] : x[i - carried];
+	/* cut < carried + n_samples; n_rem = the difference, <= the next slot's length */
 	for (uint32_t i = threadIdx.x; i < n_rem; i += kThreads) {
 		const size_t j = cut + i;
 		rem_out[(size_t)chan * TRX_RXS_REM_STRIDE + i] = j < carried ? r[j] : x[j - carried];
@@ -260,7 +264,7 @@ struct trxhip_rx_sched {
 	trxhip_burst_result *d_res = nullptr, *d_edge_res = nullptr;
 	uint32_t *d_rank = nullptr, *d_idle_slot = nullptr;
 	float *d_soft = nullptr, *d_edge_soft = nullptr;
-	void *d_edge_row = nullptr;            /* [chans][625] samples of either format */
+	void *d_edge_row = nullptr;            /* [chans][625] samples of either format (1 SPS: rows of slot 0's 157 or 156) */
 	void *d_rem = nullptr;                 /* [2][chans][TRX_RXS_REM_STRIDE] samples of either format */
 	trx_rxs_noise *d_noise = nullptr;      /* [2][chans] */
 	unsigned long long *d_ctrs = nullptr;  /* [chans][2]: rx_clipping, rx_no_burst_detected */
@@ -286,16 +290,26 @@ int wait_pulls(trxhip_rx_sched *s)
 
 int launched() { return hipGetLastError() == hipSuccess ? TRXHIP_OK : TRXHIP_EIO; }
 
+// radioInterface.cpp:272-291: the slots a pull of n_samples cuts.  At 1 SPS the count depends on the clock's TN as well
+uint64_t slots_of(const trxhip_rx_sched *s, size_t n_samples)
+{
+	return s->cfg.sps == 1 ? trx_rxs_slots1(s->tn, s->carried, n_samples) : trx_rxs_slots(s->carried, n_samples);
+}
+
 int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_t n_samples, uint8_t *d_pkt, int pkt_stride,
 	 uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
 {
 	if (!s || !s->clock_set)
 		return TRXHIP_EINVAL;
-	const uint64_t n64 = trx_rxs_slots(s->carried, n_samples);
+	const uint64_t n64 = slots_of(s, n_samples);
 	if (n64 > s->cfg.max_slots)
 		return TRXHIP_EINVAL;
 	const uint32_t n = (uint32_t)n64;
 	const int chans = s->cfg.chans;
+	const bool sps1 = s->cfg.sps == 1;
+	/* a 1-SPS object refuses mixed formats without a context too: its plan-only form refuses what the device form refuses */
+	if (!s->ctx && sps1 && n_samples && s->carried && cf32 != s->carried_cf32)
+		return TRXHIP_EINVAL;
 	if (s->ctx) {
 		const uintptr_t align = cf32 ? 7 : 3;
 		if (n_samples && (!d_in || (reinterpret_cast<uintptr_t>(d_in) & align) || in_stride < n_samples))
@@ -309,7 +323,10 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 	} else if (d_in || d_pkt || d_pkt_len || d_ind || d_soft) {
 		return TRXHIP_EINVAL;                                  /* a plan-only object takes no buffers */
 	}
-	const uint32_t n_rem = (uint32_t)(s->carried + n_samples - (uint64_t)n * TRX_RXS_SLOT);
+	/* where the remainder begins in this pull's stream, and the length of slot 0 (the straddling one, the same for all channels) */
+	const uint64_t cut = sps1 ? trx_rxs_slot_start(s->tn, n) : (uint64_t)n * TRX_RXS_SLOT;
+	const uint32_t slot0 = sps1 ? trx_rxs_slot_len(s->tn, 0) : TRX_RXS_SLOT;
+	const uint32_t n_rem = (uint32_t)(s->carried + n_samples - cut);
 	if (s->ctx && n_samples) {
 		if (with_device(s->ctx))
 			return TRXHIP_EIO;
@@ -339,28 +356,39 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 			if (cf32)
 				hipLaunchKernelGGL(rx_edge_kernel<float2>, dim3(chans), dim3(kThreads), 0, st, static_cast<const float2 *>(d_in),
 						   in_stride, reinterpret_cast<const float2 *>(rem_in), reinterpret_cast<float2 *>(rem_out),
-						   s->carried, n, n_rem, static_cast<float2 *>(s->d_edge_row));
+						   s->carried, n, slot0, (size_t)cut, n_rem, static_cast<float2 *>(s->d_edge_row));
 			else
 				hipLaunchKernelGGL(rx_edge_kernel<uint32_t>, dim3(chans), dim3(kThreads), 0, st, static_cast<const uint32_t *>(d_in),
 						   in_stride, reinterpret_cast<const uint32_t *>(rem_in), reinterpret_cast<uint32_t *>(rem_out),
-						   s->carried, n, n_rem, static_cast<uint32_t *>(s->d_edge_row));
+						   s->carried, n, slot0, (size_t)cut, n_rem, static_cast<uint32_t *>(s->d_edge_row));
 			rc = launched();
 		}
 		const int flags = TRXHIP_FLAG_SLICE | (s->cfg.flags & TRXHIP_FLAG_EXACT_DEMOD);
 		auto detect = [&](const void *iq, const trxhip_burst_params *p, trxhip_burst_result *r, float *so, size_t cnt) {
-			return cf32 ? trxhip_detect_demod_batch_cf32(s->ctx, static_cast<const float *>(iq), p, r, so, cnt, TRX_RXS_SLOT, 4,
+			return cf32 ? trxhip_detect_demod_batch_cf32(s->ctx, static_cast<const float *>(iq), p, r, so, cnt, (int)slot0, s->cfg.sps,
 								     s->cfg.threshold, s->cfg.full_scale, ss, flags, stream)
-				    : trxhip_detect_demod_batch(s->ctx, static_cast<const int16_t *>(iq), p, r, so, cnt, TRX_RXS_SLOT, 4,
+				    : trxhip_detect_demod_batch(s->ctx, static_cast<const int16_t *>(iq), p, r, so, cnt, (int)slot0, s->cfg.sps,
 								s->cfg.threshold, s->cfg.full_scale, ss, flags, stream);
+		};
+		/* 1 SPS, the slots from k0 on: back to back from slot k0's start, 157 or 156 samples each.  The flags are those the
+		 * batch entry point hands the row kernel (trx_capi.cpp, pull_common()) */
+		auto detect_stream = [&](const void *iq, size_t k0, const trxhip_burst_params *p, trxhip_burst_result *r, float *so, size_t cnt) {
+			const int kf = flags | (s->ctx->no_unit ? TRX_IFLAG_NO_UNIT : 0) | (s->ctx->no_sym ? TRX_IFLAG_NO_SYM : 0) |
+				       (s->ctx->no_fast ? TRX_IFLAG_NO_FAST : 0);
+			return trx_launch_pull_stream(iq, cf32, (unsigned)(((size_t)s->tn + k0) & 3u), p, r, so, s->ctx->d_tables, cnt,
+						      s->cfg.threshold, s->cfg.full_scale, ss, kf, s->ctx->n_cu, st);
 		};
 		if (rc == TRXHIP_OK && straddle)
 			rc = detect(s->d_edge_row, s->d_edge_params, s->d_edge_res, s->d_edge_soft, (size_t)chans);
-		// the slots inside the chunk, where they are: slot k starts k * 625 - carried samples into it
+		// the slots inside the chunk, where they are: slot k starts k * 625 - carried samples into it (1 SPS:
+		// trx_rxs_slot_start(tn, k) - carried); the last of them ends before the chunk does
 		const size_t k0 = straddle ? 1 : 0;
+		const size_t first = (size_t)(sps1 ? trx_rxs_slot_start(s->tn, k0) : k0 * TRX_RXS_SLOT) - s->carried;
 		for (int c = 0; rc == TRXHIP_OK && c < chans && n > k0; c++) {
 			const size_t o = (size_t)c * n + k0;
-			const char *iq = static_cast<const char *>(d_in) + ((size_t)c * in_stride + k0 * TRX_RXS_SLOT - s->carried) * esz;
-			rc = detect(iq, s->d_params + o, s->d_res + o, soft + o * (size_t)ss, n - k0);
+			const char *iq = static_cast<const char *>(d_in) + ((size_t)c * in_stride + first) * esz;
+			rc = sps1 ? detect_stream(iq, k0, s->d_params + o, s->d_res + o, soft + o * (size_t)ss, n - k0)
+				  : detect(iq, s->d_params + o, s->d_res + o, soft + o * (size_t)ss, n - k0);
 		}
 		if (rc == TRXHIP_OK && n) {
 			RssiOffsets offs;
@@ -384,8 +412,9 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 		s->rem_half ^= 1;
 		if (n)
 			s->noise_half ^= 1;
-		s->carried_cf32 = cf32;
 	}
+	if (n_samples)
+		s->carried_cf32 = cf32;
 	if (n) {
 		s->last_st = s->st;
 		s->last_fn = s->fn;
@@ -404,16 +433,16 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 	return TRXHIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int trxhip_rx_sched_create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out)
+// create: sps is 4, or 1 where the caller admits it (trxhip_rx_sched_create_sps)
+int create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out, bool admit_sps1)
 {
 	if (!cfg || !out)
 		return TRXHIP_EINVAL;
 	const trxhip_rx_sched_cfg c = *cfg;
-	if (c.chans < 1 || c.chans > TRX_RXS_MAX_CHANS || c.sps != 4 || c.tsc < 0 || c.tsc > 7 ||
+	/* EDGE needs 4 SPS on receive (osmo-trx.cpp:485-490) */
+	if (c.sps != 4 && !(admit_sps1 && c.sps == 1 && !c.egprs))
+		return TRXHIP_EINVAL;
+	if (c.chans < 1 || c.chans > TRX_RXS_MAX_CHANS || c.tsc < 0 || c.tsc > 7 ||
 	    c.ul_fn_offset <= -(int32_t)TRX_RXS_HYPERFRAME || c.ul_fn_offset >= (int32_t)TRX_RXS_HYPERFRAME ||
 	    (c.flags & ~TRXHIP_FLAG_EXACT_DEMOD) || !(c.full_scale > 0.0f) || !std::isfinite(c.full_scale) || !std::isfinite(c.threshold) ||
 	    c.max_slots < 1 || c.max_slots > ((uint64_t)1 << 20))
@@ -465,6 +494,20 @@ int trxhip_rx_sched_create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxh
 	}
 	*out = s;
 	return TRXHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trxhip_rx_sched_create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out)
+{
+	return create(ctx, cfg, out, false);
+}
+
+int trxhip_rx_sched_create_sps(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **out)
+{
+	return create(ctx, cfg, out, true);
 }
 
 void trxhip_rx_sched_destroy(trxhip_rx_sched *s)
@@ -559,7 +602,7 @@ int64_t trxhip_rx_sched_slots(const trxhip_rx_sched *s, size_t n_samples)
 {
 	if (!s)
 		return TRXHIP_EINVAL;
-	return (int64_t)trx_rxs_slots(s->carried, n_samples);
+	return (int64_t)slots_of(s, n_samples);
 }
 
 int trxhip_rx_sched_pull_s16(trxhip_rx_sched *s, const int16_t *d_in, size_t in_stride, size_t n_samples, uint8_t *d_pkt,

@@ -135,6 +135,7 @@ SYMBOLS = {
     "trxhip_tx_sched_plan": (_I, [_VP, _I, _VP, _SZ]),
     "trxhip_tx_sched_counters": (_I, [_VP, _I, _VP]),
     "trxhip_rx_sched_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
+    "trxhip_rx_sched_create_sps": (_I, [_VP, _VP, C.POINTER(_VP)]),
     "trxhip_rx_sched_destroy": (None, [_VP]),
     "trxhip_rx_sched_set_clock": (_I, [_VP, C.c_uint32, _I]),
     "trxhip_rx_sched_clock": (_I, [_VP, C.POINTER(C.c_uint32), C.POINTER(_I)]),
@@ -808,7 +809,8 @@ class _RxSchedCfg(C.Structure):
 
 class RxScheduler:
     """Uplink burst scheduler (trxhip_rx_sched_*): each channel's receive stream in, TRXD uplink datagrams and indication
-    records out.  trx=None: a plan-only object (no GPU): pull(n_samples=...) only cuts and plans, plan() reads the plan back."""
+    records out.  trx=None: a plan-only object (no GPU): pull(n_samples=...) only cuts and plans, plan() reads the plan back.
+    sps=1: the reference's default receive rate, slots of 157 / 156 / 156 / 156 samples (trxhip_rx_sched_create_sps)."""
 
     def __init__(self, trx=None, chans=1, sps=4, tsc=0, ul_fn_offset=0, ext_rach=False, egprs=False, exact=False, threshold=4.0,
                  full_scale=32767.0, max_slots=8 * 1024):
@@ -820,7 +822,8 @@ class RxScheduler:
         cfg = _RxSchedCfg(chans, sps, tsc, ul_fn_offset, int(bool(ext_rach)), int(bool(egprs)), FLAG_EXACT_DEMOD if exact else 0,
                           threshold, full_scale, 0, max_slots)
         h = _VP()
-        _check(self.L.trxhip_rx_sched_create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_rx_sched_create")
+        create = self.L.trxhip_rx_sched_create_sps if sps == 1 else self.L.trxhip_rx_sched_create
+        _check(create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_rx_sched_create")
         self.h = h
         self._last = 0
 
