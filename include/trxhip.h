@@ -551,6 +551,8 @@ int  trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_
 int trxhip_rx_frontend_create_chans(trxhip_ctx *ctx, int mode, int chans, int block_len, int p, int q,
                                     trxhip_rx_frontend **out);
 int trxhip_rx_frontend_rows(const trxhip_rx_frontend *f);   /* rows pull() writes: 4 for trxhip_rx_frontend_create() objects */
+/* samples per row a pull of n_blocks writes: n_blocks*block_len/q*p (0 for NULL); host arithmetic only */
+size_t trxhip_rx_frontend_out_samples(const trxhip_rx_frontend *f, size_t n_blocks);
 
 /* ---- streaming transmit front end: RadioInterfaceMulti::pushBuffer() (radioInterfaceMulti.cpp:316-362) and
  * RadioInterfaceResamp::pushBuffer() (radioInterfaceResamp.cpp:196-230) ----
@@ -676,6 +678,7 @@ int  trxhip_tx_sched_counters(const trxhip_tx_sched *s, int chan, trxhip_tx_sche
  *   Transceiver::pullRadioVector(), its head   Transceiver.cpp:665-815      (burstTime, OFF, mute, power, noise ring, counters)
  *   Transceiver::expectedCorrType()            Transceiver.cpp:513-601      (SETSLOT / HANDOVER state to the slot's CorrType)
  *   Transceiver::driveReceiveFIFO()            Transceiver.cpp:1187-1224    (one TRXD v0 / v1 datagram per indication)
+ * trxhip_rx_sched_pull_frontend() joins the two: the radio's samples through the front end and the cutter in one call.
  * Slot cutter: at 4 SPS burstSize = 625; at 1 SPS -- the reference's default receive rate (DEFAULT_RX_SPS,
  * CommonLibs/trx_vty.h:29), an object from trxhip_rx_sched_create_sps() -- burstSize = 156 + (tN % 4 == 0), recomputed after
  * every incTN() (radioInterface.cpp:257-258, :283-288): slots of 157 / 156 / 156 / 156 samples from a TN that is a multiple of 4,
@@ -783,6 +786,31 @@ int  trxhip_rx_sched_pull_s16(trxhip_rx_sched *s, const int16_t *d_in, size_t in
 int  trxhip_rx_sched_pull_cf32(trxhip_rx_sched *s, const float *d_in, size_t in_stride, size_t n_samples, uint8_t *d_pkt,
 			       int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots,
 			       size_t *n_slots, size_t *n_carried, void *stream);
+/* Through the receive front end -- RadioInterface::driveReceiveRadio() as one step, pullBuffer() and then the cutter: the
+ * radio's int16 samples in, indications out.  fe: an object of trxhip_rx_frontend_create_chans() on the scheduler's context
+ * whose trxhip_rx_frontend_rows() equals the scheduler's chans -- MULTI with 1..3 logical channels, or RESAMP with one; d_wide
+ * and n_blocks as trxhip_rx_frontend_pull() takes them.  The scheduler's sps states the front end's output rate: 4, or 1 (a
+ * RESAMP object at 1 SPS has block_len 384 at (65, 96): resamp_inchunk = inrate * 4 * sps, radioInterfaceResamp.cpp).
+ * The effect on every output and on the carried state of both objects -- the front end's histories; the scheduler's remainder,
+ * clock, noise rings, counters and last plan -- is that of
+ *   trxhip_rx_frontend_pull(fe, d_wide, n_blocks, rows, stride, stream);
+ *   trxhip_rx_sched_pull_cf32(s, rows, stride, trxhip_rx_frontend_out_samples(fe, n_blocks), ...the same outputs..., stream);
+ * byte for byte, and the remainder is kept where pull_cf32 keeps it: the two forms may alternate on one object (an int16 pull
+ * over the complex64 remainder, or this call over an int16 one, stays refused).  n_blocks == 0 cuts nothing and launches nothing.
+ * d_work: caller-owned, 16-byte aligned, chans rows of work_stride complex64 samples, work_stride even and >=
+ * TRXHIP_RX_SCHED_WORK_HEAD + out_samples; its content matters only during the call's work on `stream`.  The front end stores
+ * channel l at d_work + 2*(l*work_stride + TRXHIP_RX_SCHED_WORK_HEAD), the carried remainder is put in front of it, and every
+ * slot, the one that begins in the remainder too, is detected where it lies: no slot is assembled and no second detect launch
+ * runs.  Refused with TRXHIP_EINVAL before anything is launched, both objects untouched: a NULL, plan-only or foreign-context
+ * object, rows != chans, the four-row object of trxhip_rx_frontend_create(), d_wide NULL or misaligned, d_work NULL or
+ * misaligned, work_stride odd or too small, and whatever trxhip_rx_sched_pull_cf32() refuses.
+ * trxhip_rx_sched_slots_frontend(): trxhip_rx_sched_slots(s, out_samples), or TRXHIP_EINVAL for a pair the pull refuses */
+#define TRXHIP_RX_SCHED_WORK_HEAD 640   /* samples in front of the front end's output in a work row */
+int64_t trxhip_rx_sched_slots_frontend(const trxhip_rx_sched *s, const trxhip_rx_frontend *fe, size_t n_blocks);
+int  trxhip_rx_sched_pull_frontend(trxhip_rx_sched *s, trxhip_rx_frontend *fe, const int16_t *d_wide, size_t n_blocks,
+				   float *d_work, size_t work_stride, uint8_t *d_pkt, int pkt_stride, uint16_t *d_pkt_len,
+				   trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots, size_t *n_slots, size_t *n_carried,
+				   void *stream);
 int  trxhip_rx_sched_plan(const trxhip_rx_sched *s, int chan, trxhip_rx_plan *h_out, size_t n);   /* the last pull's first n slots */
 int  trxhip_rx_sched_counters(trxhip_rx_sched *s, int chan, trxhip_rx_sched_ctrs *out);
 /* the channel's noise ring as the reference holds it: ring[20], the insert position (0..20) and mNoiseLev */

@@ -703,6 +703,24 @@ int trxhip_rx_frontend_rows(const trxhip_rx_frontend *f)
 	return f ? f->rows : TRXHIP_EINVAL;
 }
 
+size_t trxhip_rx_frontend_out_samples(const trxhip_rx_frontend *f, size_t n_blocks)
+{
+	return f ? n_blocks * (size_t)f->block_len / f->q * f->p : 0;
+}
+
+int trx_rx_frontend_geometry(const trxhip_rx_frontend *f, trxhip_ctx **ctx, int *rows, int *resamp, int *block_len, int *p, int *q)
+{
+	if (!f || f->mode == RXFE_FOUR_ROWS)
+		return TRXHIP_EINVAL;
+	*ctx = f->ctx;
+	*rows = f->rows;
+	*resamp = f->mode == TRXHIP_RXFE_RESAMP;
+	*block_len = f->block_len;
+	*p = f->p;
+	*q = f->q;
+	return TRXHIP_OK;
+}
+
 void trxhip_rx_frontend_destroy(trxhip_rx_frontend *f)
 {
 	if (!f)

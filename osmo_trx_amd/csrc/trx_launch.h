@@ -132,5 +132,9 @@ int trx_launch_tx_fill_update(const trx_tx_fill_update *d_upd, size_t n, const u
 /* trx_capi.cpp: a transmit front end's logical channels, block length and output samples per block */
 int trx_tx_frontend_geometry(const trxhip_tx_frontend *f, int *chans, int *block_len, size_t *out_per_block);
 
+/* trx_capi.cpp: a receive front end of trxhip_rx_frontend_create_chans() -- its context, rows, whether it is a RESAMP object,
+ * block length and ratio; TRXHIP_EINVAL for NULL and for the four-row object of trxhip_rx_frontend_create() */
+int trx_rx_frontend_geometry(const trxhip_rx_frontend *f, trxhip_ctx **ctx, int *rows, int *resamp, int *block_len, int *p, int *q);
+
 }  // extern "C"
 #endif

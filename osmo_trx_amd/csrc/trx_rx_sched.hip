@@ -13,6 +13,10 @@
 // caller's chunk -- read where they are --, rx_ind_kernel (records, counters, noise ring), trx_launch_pack_trxd_wire per channel.
 // At 1 SPS the slots in the chunk are not one length apart: they go to burst_pull_stream_kernel (trx_launch_pull_stream), which
 // finds slot k from the run's first slot and its TN; the straddling rows, all of slot 0's length, take the batch entry point.
+// trxhip_rx_sched_pull_frontend() is driveReceiveRadio()'s one step, pullBuffer() then the cutter: the receive front end stores its
+// rows into the caller's work rows behind TRX_RXS_REM_STRIDE samples of room, rx_join_kernel puts the carried remainder in front
+// of them and saves the new one, and every slot of the pull -- the one that begins in the remainder too -- is detected where it
+// lies: no slot is assembled, no launch over straddling rows runs, and the plan, the epilogue and the packer are the same.
 // With ctx == NULL the object is plan-only: cutter, clock and plan, no device memory.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +28,8 @@
 #include "trx_ctx.h"
 #include "trx_launch.h"
 #include "trx_rx_sched.h"
+
+static_assert(TRXHIP_RX_SCHED_WORK_HEAD == TRX_RXS_REM_STRIDE, "the work row's head holds one carried remainder");
 
 namespace {
 
@@ -110,6 +116,31 @@ rx_edge_kernel(const T *__restrict__ in, size_t in_stride, const T *__restrict__
 		for (uint32_t i = threadIdx.x; i < slot0; i += kThreads)
 			edge_row[(size_t)chan * slot0 + i] = i < carried ? r[i] : x[i - carried];
 	/* cut < carried + n_samples; n_rem = the difference, <= the next slot's length */
+	for (uint32_t i = threadIdx.x; i < n_rem; i += kThreads) {
+		const size_t j = cut + i;
+		rem_out[(size_t)chan * TRX_RXS_REM_STRIDE + i] = j < carried ? r[j] : x[j - carried];
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// rx_join_kernel: one block per channel, behind the front end's kernels of a trxhip_rx_sched_pull_frontend().  The front end has
+// stored this pull's samples of channel `chan` from work[chan * work_stride + TRX_RXS_REM_STRIDE] on, the same aligned place
+// every pull.  The `carried` samples of the remainder go in front of them, to [TRX_RXS_REM_STRIDE - carried, TRX_RXS_REM_STRIDE),
+// so that the pull's stream lies in one piece and all its slots are read where they lie (nothing to do when no slot is cut).
+// The samples from `cut` on go to the OTHER half of the remainder area, in rx_edge_kernel's format and place: a pull_cf32 may
+// follow.  What is read (rem_in, the front end's samples) and what is written (the row's head, rem_out) never overlap.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads)
+rx_join_kernel(float2 *work, size_t work_stride, const float2 *__restrict__ rem_in, float2 *__restrict__ rem_out, uint32_t carried,
+	       uint32_t n_slots, size_t cut, uint32_t n_rem)
+{
+	const int chan = blockIdx.x;
+	float2 *x = work + (size_t)chan * work_stride + TRX_RXS_REM_STRIDE;         /* the front end's first sample */
+	const float2 *r = rem_in + (size_t)chan * TRX_RXS_REM_STRIDE;
+	if (n_slots)
+		for (uint32_t i = threadIdx.x; i < carried; i += kThreads)
+			(x - carried)[i] = r[i];                                   /* carried <= 625 < TRX_RXS_REM_STRIDE */
+	/* cut < carried + the front end's samples; n_rem = the difference, <= the next slot's length */
 	for (uint32_t i = threadIdx.x; i < n_rem; i += kThreads) {
 		const size_t j = cut + i;
 		rem_out[(size_t)chan * TRX_RXS_REM_STRIDE + i] = j < carried ? r[j] : x[j - carried];
@@ -296,8 +327,16 @@ uint64_t slots_of(const trxhip_rx_sched *s, size_t n_samples)
 	return s->cfg.sps == 1 ? trx_rxs_slots1(s->tn, s->carried, n_samples) : trx_rxs_slots(s->carried, n_samples);
 }
 
+// a pull through the receive front end: d_in is then the place in the work rows where the front end stores (complex64)
+struct FrontEndPull {
+	trxhip_rx_frontend *fe;
+	const int16_t *d_wide;
+	size_t n_blocks;
+};
+
 int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_t n_samples, uint8_t *d_pkt, int pkt_stride,
-	 uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
+	 uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream,
+	 const FrontEndPull *fep = nullptr)
 {
 	if (!s || !s->clock_set)
 		return TRXHIP_EINVAL;
@@ -331,7 +370,7 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 		if (with_device(s->ctx))
 			return TRXHIP_EIO;
 		const hipStream_t st = static_cast<hipStream_t>(stream);
-		const bool straddle = n && s->carried;
+		const bool straddle = n && s->carried && !fep;         /* through the front end the stream lies in one piece */
 		const size_t esz = cf32 ? 8 : 4;
 		const char *rem_in = static_cast<const char *>(s->d_rem) + (size_t)s->rem_half * chans * TRX_RXS_REM_STRIDE * esz;
 		char *rem_out = static_cast<char *>(s->d_rem) + (size_t)(s->rem_half ^ 1) * chans * TRX_RXS_REM_STRIDE * esz;
@@ -352,7 +391,17 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 					   s->d_meta, s->d_rank, s->d_idle_slot, s->d_edge_params);
 			rc = launched();
 		}
-		if (rc == TRXHIP_OK) {
+		if (rc == TRXHIP_OK && fep) {
+			float *rows = const_cast<float *>(static_cast<const float *>(d_in));
+			rc = trxhip_rx_frontend_pull(fep->fe, fep->d_wide, fep->n_blocks, rows, in_stride, stream);
+			if (rc == TRXHIP_OK) {
+				hipLaunchKernelGGL(rx_join_kernel, dim3(chans), dim3(kThreads), 0, st,
+						   reinterpret_cast<float2 *>(rows) - TRX_RXS_REM_STRIDE, in_stride,
+						   reinterpret_cast<const float2 *>(rem_in), reinterpret_cast<float2 *>(rem_out), s->carried, n,
+						   (size_t)cut, n_rem);
+				rc = launched();
+			}
+		} else if (rc == TRXHIP_OK) {
 			if (cf32)
 				hipLaunchKernelGGL(rx_edge_kernel<float2>, dim3(chans), dim3(kThreads), 0, st, static_cast<const float2 *>(d_in),
 						   in_stride, reinterpret_cast<const float2 *>(rem_in), reinterpret_cast<float2 *>(rem_out),
@@ -381,12 +430,13 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 		if (rc == TRXHIP_OK && straddle)
 			rc = detect(s->d_edge_row, s->d_edge_params, s->d_edge_res, s->d_edge_soft, (size_t)chans);
 		// the slots inside the chunk, where they are: slot k starts k * 625 - carried samples into it (1 SPS:
-		// trx_rxs_slot_start(tn, k) - carried); the last of them ends before the chunk does
+		// trx_rxs_slot_start(tn, k) - carried); the last of them ends before the chunk does.  Through the front end slot 0 is
+		// one of them: it starts `carried` samples in front of the chunk, in the work row's head
 		const size_t k0 = straddle ? 1 : 0;
-		const size_t first = (size_t)(sps1 ? trx_rxs_slot_start(s->tn, k0) : k0 * TRX_RXS_SLOT) - s->carried;
+		const ptrdiff_t first = (ptrdiff_t)(sps1 ? trx_rxs_slot_start(s->tn, k0) : k0 * TRX_RXS_SLOT) - (ptrdiff_t)s->carried;
 		for (int c = 0; rc == TRXHIP_OK && c < chans && n > k0; c++) {
 			const size_t o = (size_t)c * n + k0;
-			const char *iq = static_cast<const char *>(d_in) + ((size_t)c * in_stride + first) * esz;
+			const char *iq = static_cast<const char *>(d_in) + ((ptrdiff_t)((size_t)c * in_stride) + first) * (ptrdiff_t)esz;
 			rc = sps1 ? detect_stream(iq, k0, s->d_params + o, s->d_res + o, soft + o * (size_t)ss, n - k0)
 				  : detect(iq, s->d_params + o, s->d_res + o, soft + o * (size_t)ss, n - k0);
 		}
@@ -431,6 +481,23 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 	if (n_carried)
 		*n_carried = n_rem;
 	return TRXHIP_OK;
+}
+
+// the pair trxhip_rx_sched_pull_frontend() takes: a device scheduler and a per-channel front end (1..3 ARFCNs, or RESAMP) on its
+// context with one row per scheduler channel.  *n_out: the samples per channel n_blocks blocks give
+bool frontend_ok(const trxhip_rx_sched *s, const trxhip_rx_frontend *fe, size_t n_blocks, int *resamp, size_t *n_out)
+{
+	trxhip_ctx *ctx = nullptr;
+	int rows = 0, block_len = 0, p = 0, q = 0;
+	if (!s || !s->ctx || trx_rx_frontend_geometry(fe, &ctx, &rows, resamp, &block_len, &p, &q) != TRXHIP_OK)
+		return false;
+	if (ctx != s->ctx || rows != s->cfg.chans)
+		return false;
+	/* max_slots <= 2^20: a pull that could be accepted is far below this */
+	if (n_blocks > ((size_t)1 << 40) / (size_t)block_len)
+		return false;
+	*n_out = trxhip_rx_frontend_out_samples(fe, n_blocks);
+	return true;
 }
 
 // create: sps is 4, or 1 where the caller admits it (trxhip_rx_sched_create_sps)
@@ -617,6 +684,34 @@ int trxhip_rx_sched_pull_cf32(trxhip_rx_sched *s, const float *d_in, size_t in_s
 			      size_t *n_carried, void *stream)
 {
 	return pull(s, d_in, 1, in_stride, n_samples, d_pkt, pkt_stride, d_pkt_len, d_ind, d_soft, out_slots, n_slots, n_carried, stream);
+}
+
+int64_t trxhip_rx_sched_slots_frontend(const trxhip_rx_sched *s, const trxhip_rx_frontend *fe, size_t n_blocks)
+{
+	int resamp;
+	size_t n_out;
+	if (!frontend_ok(s, fe, n_blocks, &resamp, &n_out))
+		return TRXHIP_EINVAL;
+	return (int64_t)slots_of(s, n_out);
+}
+
+int trxhip_rx_sched_pull_frontend(trxhip_rx_sched *s, trxhip_rx_frontend *fe, const int16_t *d_wide, size_t n_blocks, float *d_work,
+				  size_t work_stride, uint8_t *d_pkt, int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind,
+				  float *d_soft, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
+{
+	int resamp;
+	size_t n_out;
+	if (!frontend_ok(s, fe, n_blocks, &resamp, &n_out))
+		return TRXHIP_EINVAL;
+	if (!d_wide || (reinterpret_cast<uintptr_t>(d_wide) & (resamp ? 3 : 15)))     /* trxhip_rx_frontend_pull()'s rule */
+		return TRXHIP_EINVAL;
+	if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15) || (work_stride & 1) || work_stride < TRXHIP_RX_SCHED_WORK_HEAD + n_out)
+		return TRXHIP_EINVAL;
+	/* the front end's kernels store single complex64 samples (8 bytes) at d_out: every row's place behind the head, a multiple of
+	 * 16 bytes from d_work, is more than they need.  From here on it is a complex64 pull of the chunk that will lie there */
+	const FrontEndPull fep = { fe, d_wide, n_blocks };
+	return pull(s, d_work + 2 * (size_t)TRXHIP_RX_SCHED_WORK_HEAD, 1, work_stride, n_out, d_pkt, pkt_stride, d_pkt_len, d_ind, d_soft,
+		    out_slots, n_slots, n_carried, stream, &fep);
 }
 
 int trxhip_rx_sched_plan(const trxhip_rx_sched *s, int chan, trxhip_rx_plan *h_out, size_t n)

@@ -79,3 +79,11 @@ int MultiArfcnRx::pullBuffer(const int16_t *wide, size_t n_blocks, std::vector<s
 	}
 	return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;
 }
+
+int MultiArfcnRx::pullScheduled(trxhip_rx_sched *sched, const int16_t *d_wide, size_t n_blocks, float *d_work, size_t work_stride,
+				uint8_t *d_pkt, int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots,
+				size_t *n_slots, size_t *n_carried)
+{
+	return trxhip_rx_sched_pull_frontend(sched, fe_, d_wide, n_blocks, d_work, work_stride, d_pkt, pkt_stride, d_pkt_len, d_ind, d_soft,
+					     out_slots, n_slots, n_carried, stream_);
+}

@@ -61,3 +61,11 @@ int ResampRx::pullBuffer(const int16_t *in, size_t n_chunks, std::vector<complex
 		return -EIO;
 	return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;
 }
+
+int ResampRx::pullScheduled(trxhip_rx_sched *sched, const int16_t *d_in, size_t n_chunks, float *d_work, size_t work_stride,
+				uint8_t *d_pkt, int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots,
+				size_t *n_slots, size_t *n_carried)
+{
+	return trxhip_rx_sched_pull_frontend(sched, fe_, d_in, n_chunks, d_work, work_stride, d_pkt, pkt_stride, d_pkt_len, d_ind, d_soft,
+					     out_slots, n_slots, n_carried, stream_);
+}

@@ -10,6 +10,8 @@
 #include "signalVector.h"
 
 struct trxhip_rx_frontend;
+struct trxhip_rx_sched;
+struct trxhip_ul_ind;
 
 class ResampRx {
 public:
@@ -19,6 +21,15 @@ public:
 	/* One or more pullBuffer() calls' worth of work: in = n_chunks * chunk_len int16 IQ samples as read from the device.
 	 * Appends n_chunks * chunk_len * p / q samples to out.  0 or -EIO. */
 	int pullBuffer(const int16_t *in, size_t n_chunks, std::vector<complex> &out);
+	/* RadioInterface::driveReceiveRadio() as one step, on the device: the same chunks through this object's front end and the
+	 * one-channel uplink scheduler sched (on sigProcLibSetup()'s context; its sps states this object's output rate) to TRXD
+	 * indications -- trxhip_rx_sched_pull_frontend() (include/trxhip.h) with this object's front-end handle and stream.  Every
+	 * pointer is device memory: d_in as `in` above, d_work the call's work row, the rest the scheduler's outputs.
+	 * Asynchronous; returns the call's TRXHIP_* code. */
+	int pullScheduled(trxhip_rx_sched *sched, const int16_t *d_in, size_t n_chunks, float *d_work, size_t work_stride,
+			  uint8_t *d_pkt, int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots,
+			  size_t *n_slots, size_t *n_carried);
+	void *stream() const { return stream_; }        /* the stream pullBuffer() and pullScheduled() work on */
 private:
 	size_t chunk_len_;
 	int p_, q_;

@@ -8,6 +8,7 @@
 //   sigproc_selftest sch <cfile> <0 full | 1 narrow | 2 buffer> <out.txt>
 //   sigproc_selftest batch <iq.s16> <params.bin> <n> <sps> <burst_len> <out_results.bin> <out_soft.bin>
 //   sigproc_selftest resamp_rx <in.s16> <n_chunks> <chunk_len> <p> <q> <out.cf32>
+//   sigproc_selftest rx_join <wide.s16> <n_blocks> <chans>
 //   sigproc_selftest pullrv <iq.s16> <params.bin> <n> <chans> <muted_chan | -1> <exact 0|1> <out.bin>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +19,9 @@
 #include <atomic>
 #include <chrono>
 #include <thread>
+
+#include <hip/hip_runtime_api.h>
+#include "trxhip.h"
 
 #include "trxBatch.h"
 #include "trxPullRadioVector.h"
@@ -36,6 +40,7 @@ static_assert(sizeof(signalVector) == 48, "signalVector layout");
 static_assert(sizeof(SoftVector) == 40 && sizeof(complex) == 8, "SoftVector / complex layout");
 
 extern "C" const char *trxsigproc_abi(void);
+extern "C" trxhip_ctx *trxsigproc_context(void);      /* sigProcLib.cpp: the context sigProcLibSetup() created */
 extern "C" void trxsigproc_abi_layout(size_t out[8]);
 
 static std::vector<char> slurp(const char *path)
@@ -474,6 +479,99 @@ int main(int argc, char **argv)
 		}
 		sigProcLibDestroy();
 		return 0;
+	}
+	// rx_join <wide.s16> <n_blocks> <chans>: MultiArfcnRx::pullScheduled (trxhip_rx_sched_pull_frontend) in runs of 1, 2, 3, ...
+	// blocks against trxhip_rx_frontend_pull + trxhip_rx_sched_pull_cf32 on a second pair of objects: outputs, slot counts and
+	// the state left behind must be the same bytes.  Prints "rx_join identical <slots>"
+	if (!strcmp(argv[1], "rx_join") && argc == 5) {
+		std::vector<char> raw = slurp(argv[2]);
+		const size_t n_blocks = atol(argv[3]), chans = atol(argv[4]), cap = 256;
+		if (chans < 1 || chans > 3 || raw.size() < n_blocks * 192 * 4 * 4) return 2;
+		MultiArfcnRx rx(chans);
+		if (!rx.init()) { fprintf(stderr, "MultiArfcnRx::init failed\n"); return 5; }
+		trxhip_ctx *ctx = trxsigproc_context();
+		trxhip_rx_frontend *fe = nullptr;
+		trxhip_rx_sched *sc[2] = { nullptr, nullptr };
+		trxhip_rx_sched_cfg cfg;
+		memset(&cfg, 0, sizeof(cfg));
+		cfg.chans = (int32_t)chans; cfg.sps = 4; cfg.tsc = 5; cfg.threshold = 4.0f; cfg.full_scale = 32767.0f; cfg.max_slots = cap;
+		bool ok = trxhip_rx_frontend_create_chans(ctx, TRXHIP_RXFE_MULTI, (int)chans, 192, 65, 48, &fe) == TRXHIP_OK;
+		for (int i = 0; i < 2 && ok; i++) {
+			ok = trxhip_rx_sched_create(ctx, &cfg, &sc[i]) == TRXHIP_OK && trxhip_rx_sched_set_clock(sc[i], 0, 0) == TRXHIP_OK;
+			for (size_t c = 0; c < chans && ok; c++) {
+				static const int comb[8] = { 1, 1, TRXHIP_COMB_FILL, 1, 4, TRXHIP_COMB_NONE, 1, 1 };
+				for (int tn = 0; tn < 8 && ok; tn++)
+					ok = trxhip_rx_sched_set_slot(sc[i], (int)c, tn, comb[(tn + c) % 8]) == TRXHIP_OK;
+				ok = ok && trxhip_rx_sched_set_trxd_version(sc[i], (int)c, (int)(c & 1)) == TRXHIP_OK;
+			}
+		}
+		if (!ok) { fprintf(stderr, "rx_join: create failed\n"); return 5; }
+		const size_t n_max = n_blocks * 260, stride = TRXHIP_RX_SCHED_WORK_HEAD + n_max;
+		const size_t sz[4] = { chans * cap * 160, chans * cap * 2, chans * cap * sizeof(trxhip_ul_ind), chans * cap * 148 * 4 };
+		void *d_wide = nullptr, *d_work = nullptr, *d_rows = nullptr, *d_out[2][4];
+		ok = hipMalloc(&d_wide, raw.size()) == hipSuccess && hipMalloc(&d_work, chans * stride * 8) == hipSuccess &&
+		     hipMalloc(&d_rows, chans * n_max * 8) == hipSuccess &&
+		     hipMemcpy(d_wide, raw.data(), raw.size(), hipMemcpyHostToDevice) == hipSuccess;
+		for (int i = 0; i < 2; i++)
+			for (int k = 0; k < 4; k++)
+				ok = ok && hipMalloc(&d_out[i][k], sz[k]) == hipSuccess;
+		if (!ok) { fprintf(stderr, "rx_join: no memory\n"); return 5; }
+		hipStream_t st = static_cast<hipStream_t>(rx.stream());
+		size_t pos = 0, step = 1, slots = 0;
+		int bad = 0;
+		while (pos < n_blocks && !bad) {
+			const size_t nb = step < n_blocks - pos ? step : n_blocks - pos;
+			const int16_t *w = static_cast<const int16_t *>(d_wide) + pos * 192 * 4 * 2;
+			size_t ns[2] = { 0, 0 }, nc[2] = { 0, 0 };
+			for (int i = 0; i < 2; i++)
+				for (int k = 0; k < 4; k++)
+					ok = ok && hipMemsetAsync(d_out[i][k], 0, sz[k], st) == hipSuccess;
+			int rc = rx.pullScheduled(sc[0], w, nb, static_cast<float *>(d_work), stride, static_cast<uint8_t *>(d_out[0][0]), 160,
+						  static_cast<uint16_t *>(d_out[0][1]), static_cast<trxhip_ul_ind *>(d_out[0][2]),
+						  static_cast<float *>(d_out[0][3]), cap, &ns[0], &nc[0]);
+			if (rc == TRXHIP_OK)
+				rc = trxhip_rx_frontend_pull(fe, w, nb, static_cast<float *>(d_rows), n_max, st);
+			if (rc == TRXHIP_OK)
+				rc = trxhip_rx_sched_pull_cf32(sc[1], static_cast<const float *>(d_rows), n_max, nb * 260, static_cast<uint8_t *>(d_out[1][0]),
+							       160, static_cast<uint16_t *>(d_out[1][1]), static_cast<trxhip_ul_ind *>(d_out[1][2]),
+							       static_cast<float *>(d_out[1][3]), cap, &ns[1], &nc[1], st);
+			if (rc != TRXHIP_OK || !ok) { fprintf(stderr, "rx_join: pull failed (%d)\n", rc); return 6; }
+			if (ns[0] != ns[1] || nc[0] != nc[1]) bad = 1;
+			for (int k = 0; k < 4 && !bad; k++) {
+				std::vector<char> a(sz[k]), b(sz[k]);
+				if (hipMemcpyAsync(a.data(), d_out[0][k], sz[k], hipMemcpyDeviceToHost, st) != hipSuccess ||
+				    hipMemcpyAsync(b.data(), d_out[1][k], sz[k], hipMemcpyDeviceToHost, st) != hipSuccess ||
+				    hipStreamSynchronize(st) != hipSuccess)
+					return 6;
+				/* rows [chan * n + slot]: the first chans * n rows of each buffer are the pull's */
+				bad = memcmp(a.data(), b.data(), sz[k] / cap * ns[0]) != 0;
+			}
+			slots += ns[0];
+			pos += nb;
+			step++;
+		}
+		for (size_t c = 0; c < chans && !bad; c++) {
+			float ring[2][20], lev[2];
+			uint32_t itr[2], fn[2];
+			int tn[2];
+			trxhip_rx_sched_ctrs ct[2];
+			for (int i = 0; i < 2; i++)
+				if (trxhip_rx_sched_noise_state(sc[i], (int)c, ring[i], &itr[i], &lev[i]) || trxhip_rx_sched_counters(sc[i], (int)c, &ct[i]) ||
+				    trxhip_rx_sched_clock(sc[i], &fn[i], &tn[i]))
+					return 6;
+			bad = memcmp(ring[0], ring[1], sizeof(ring[0])) || memcmp(&lev[0], &lev[1], 4) || itr[0] != itr[1] ||
+			      memcmp(&ct[0], &ct[1], sizeof(ct[0])) || fn[0] != fn[1] || tn[0] != tn[1];
+		}
+		printf("rx_join %s %zu\n", bad ? "DIFFERENT" : "identical", slots);
+		for (int i = 0; i < 2; i++) {
+			trxhip_rx_sched_destroy(sc[i]);
+			for (int k = 0; k < 4; k++)
+				hipFree(d_out[i][k]);
+		}
+		trxhip_rx_frontend_destroy(fe);
+		hipFree(d_wide); hipFree(d_work); hipFree(d_rows);
+		sigProcLibDestroy();
+		return bad ? 7 : 0;
 	}
 	// resamp_rx <in.s16> <n_chunks> <chunk_len> <p> <q> <out.cf32>: ResampRx::pullBuffer in runs of 1, 2, 3, ... chunks
 	if (!strcmp(argv[1], "resamp_rx") && argc == 8) {

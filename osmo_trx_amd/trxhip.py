@@ -113,6 +113,7 @@ SYMBOLS = {
     "trxhip_rx_frontend_create": (_I, [_VP, _I, _I, _I, C.POINTER(_VP)]),
     "trxhip_rx_frontend_create_chans": (_I, [_VP, _I, _I, _I, _I, _I, C.POINTER(_VP)]),
     "trxhip_rx_frontend_rows": (_I, [_VP]),
+    "trxhip_rx_frontend_out_samples": (_SZ, [_VP, _SZ]),
     "trxhip_rx_frontend_destroy": (None, [_VP]),
     "trxhip_rx_frontend_reset": (_I, [_VP, _VP]),
     "trxhip_rx_frontend_seed": (_I, [_VP, _VP, _SZ, _VP]),
@@ -148,6 +149,9 @@ SYMBOLS = {
     "trxhip_rx_sched_slots": (C.c_int64, [_VP, _SZ]),
     "trxhip_rx_sched_pull_s16": (_I, [_VP, _VP, _SZ, _SZ, _VP, _I, _VP, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
     "trxhip_rx_sched_pull_cf32": (_I, [_VP, _VP, _SZ, _SZ, _VP, _I, _VP, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
+    "trxhip_rx_sched_slots_frontend": (C.c_int64, [_VP, _VP, _SZ]),
+    "trxhip_rx_sched_pull_frontend": (_I, [_VP, _VP, _VP, _SZ, _VP, _SZ, _VP, _I, _VP, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
+                                           _VP]),
     "trxhip_rx_sched_plan": (_I, [_VP, _I, _VP, _SZ]),
     "trxhip_rx_sched_counters": (_I, [_VP, _I, _VP]),
     "trxhip_rx_sched_noise_state": (_I, [_VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(_F)]),
@@ -794,6 +798,7 @@ class TxScheduler:
 
 
 ULIND_OFF, ULIND_MUTED, ULIND_IDLE = 1, 2, 4         # TRXHIP_ULIND_*
+RX_SCHED_WORK_HEAD = 640                             # TRXHIP_RX_SCHED_WORK_HEAD
 UL_IND_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("type", "u1"), ("flags", "u1"), ("tsc", "u1"), ("rc", "<i4"), ("toa", "<f4"),
                          ("ci", "<f4"), ("rssi", "<f4"), ("noise_lev", "<f4"), ("nbits", "<u2"), ("reserved", "<u2")])
 RX_PLAN_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("type", "u1"), ("max_toa", "<u2")])
@@ -826,9 +831,11 @@ class RxScheduler:
         _check(create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_rx_sched_create")
         self.h = h
         self._last = 0
+        self.carried = 0             # samples per channel the last pull left in the remainder
 
     def set_clock(self, fn, tn):
         _check(self.L.trxhip_rx_sched_set_clock(self.h, fn, tn), "trxhip_rx_sched_set_clock")
+        self.carried = 0
 
     def clock(self):
         fn, tn = C.c_uint32(), _I()
@@ -869,7 +876,7 @@ class RxScheduler:
         if self.trx is None:
             _check(self.L.trxhip_rx_sched_pull_s16(self.h, None, 0, n_samples, None, 0, None, None, None, 0, C.byref(ns), C.byref(nc),
                                                    None), "trxhip_rx_sched_pull_s16")
-            self._last = ns.value
+            self._last, self.carried = ns.value, nc.value
             return ns.value, nc.value
         torch = self.trx.torch
         s16 = x.dtype == torch.int16
@@ -890,7 +897,44 @@ class RxScheduler:
                   self.trx._dev(ind), self.trx._dev(soft) if soft is not None else None, n, C.byref(ns), C.byref(nc),
                   self.trx._stream(stream)), "trxhip_rx_sched_pull")
         assert ns.value == n
-        self._last = n
+        self._last, self.carried = n, nc.value
+        return pkt, plen, ind, soft
+
+    def slots_frontend(self, fe, n_blocks):
+        """slots the next pull_frontend of n_blocks through fe will cut"""
+        n = self.L.trxhip_rx_sched_slots_frontend(self.h, fe.h, n_blocks)
+        if n < 0:
+            _check(int(n), "trxhip_rx_sched_slots_frontend")
+        return int(n)
+
+    def pull_frontend(self, fe, wide_iq, n_blocks, pkt_stride=None, want_soft=False, stream=None, work=None):
+        """The radio's samples through the RxFrontEnd fe (chans=1..3 "multi", or "resamp") and the cutter in one call
+        (trxhip_rx_sched_pull_frontend): wide_iq as RxFrontEnd.pull takes it; returns what pull() returns.  work: a contiguous
+        complex64[chans, >= RX_SCHED_WORK_HEAD + n_out] device tensor with an even row length (allocated when None)."""
+        torch = self.trx.torch
+        n_out = self.L.trxhip_rx_frontend_out_samples(fe.h, n_blocks)
+        n = self.slots_frontend(fe, n_blocks)
+        dev = f"cuda:{self.trx.device}"
+        if work is None:
+            work = torch.empty((self.chans, RX_SCHED_WORK_HEAD + n_out + (n_out & 1)), dtype=torch.complex64, device=dev)
+        elif (work.dim() != 2 or work.shape[0] != self.chans or work.shape[1] < RX_SCHED_WORK_HEAD + n_out or work.shape[1] % 2 or
+              work.dtype != torch.complex64 or not work.is_contiguous()):
+            raise ValueError("work must be a contiguous complex64[%d, >= %d] tensor with an even row length"
+                             % (self.chans, RX_SCHED_WORK_HEAD + n_out))
+        if pkt_stride is None:
+            pkt_stride = 160 if self.soft_stride == 148 else 456
+        pkt = torch.empty((self.chans, n, pkt_stride), dtype=torch.uint8, device=dev)
+        plen = torch.empty((self.chans, n), dtype=torch.int16, device=dev)
+        ind = torch.empty((self.chans, n, 32), dtype=torch.uint8, device=dev)
+        soft = torch.empty((self.chans, n, self.soft_stride), dtype=torch.float32, device=dev) if want_soft else None
+        ns, nc = _SZ(), _SZ()
+        _check(self.L.trxhip_rx_sched_pull_frontend(self.h, fe.h, self.trx._dev(wide_iq, torch.int16), n_blocks, self.trx._dev(work),
+                                                    work.shape[1], self.trx._dev(pkt), pkt_stride, self.trx._dev(plen),
+                                                    self.trx._dev(ind), self.trx._dev(soft) if soft is not None else None, n,
+                                                    C.byref(ns), C.byref(nc), self.trx._stream(stream)),
+               "trxhip_rx_sched_pull_frontend")
+        assert ns.value == n
+        self._last, self.carried = n, nc.value
         return pkt, plen, ind, soft
 
     def plan(self, chan, n=None):
