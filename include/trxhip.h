@@ -242,6 +242,38 @@ enum { TRXHIP_SCH_DETECT_FULL = 0, TRXHIP_SCH_DETECT_NARROW = 1, TRXHIP_SCH_DETE
 int trxhip_detect_sch_batch_cf32(trxhip_ctx *ctx, const float *d_iq_cf32, trxhip_burst_result *d_results,
 				 size_t n_bufs, size_t buf_len, int sps, int state, float threshold, void *stream);
 
+/* The MS-side synchronisation-burst receiver, the live branch of ms_trx::handle_sch() (ms/ms_rx_lower.cpp:157-205) with
+ * decode_sch() (:59-100): convert_and_scale by `scale` (the reference: 1 / rxFullScale), gr-gsm's channel estimate on the 64-bit
+ * extended training sequence at 4 samples per symbol, detect_burst_nb() and gsm_sch_decode / gsm_sch_parse / gsm_sch_to_fn
+ * (ms/sch.c:141-204), for n_bufs independent buffers of buf_len samples that lie buf_stride >= buf_len samples apart.
+ *   TRXHIP_SCH_SYNC_TRACK  get_sch_chan_imp_resp(): one slot.  At most the first 625 samples of a buffer are used, everything
+ *                          outside them reads as zero; 160 lags, start clamped to [-39, 39] (buf_len >= 1)
+ *   TRXHIP_SCH_SYNC_ACQ    get_sch_buffer_chan_imp_resp(): the lags 0 .. buf_len - 513 of the whole buffer, start not clamped;
+ *                          532 <= buf_len <= TRXHIP_SCH_SYNC_MAX_LEN (the reference's buffer: 12 frames = 60000 samples).  Where the
+ *                          burst would start in front of the buffer (start < 0; the reference reads in front of its array) the
+ *                          missing samples are zeros.  Uses a scratch of the context, n_bufs * (buf_len - 512) floats: ACQ calls
+ *                          on one context run one behind the other
+ * d_results[b]: see below.  d_bits (may be NULL): int8 [n_bufs][148], detect_burst_nb()'s output (+-127, -127 = a one).
+ * -TRXHIP_EINVAL (nothing launched, nothing written): unknown mode, n_bufs == 0, a NULL pointer, buf_stride < buf_len, buf_len
+ * outside the mode's range. */
+enum { TRXHIP_SCH_SYNC_TRACK = 0, TRXHIP_SCH_SYNC_ACQ = 1 };
+#define TRXHIP_SCH_SYNC_MAX_LEN (1 << 20)
+typedef struct {             /* 24 bytes */
+	int32_t rc;          /* 0: 1 = parity good (and fn >= 0); 0 = not decoded */
+	int32_t start;       /* 4: burst start in samples as the reference's function returns it (TRACK: after the clamp) */
+	float corr_max;      /* 8: largest |correlation| of the 20-tap channel estimate */
+	int32_t fn;          /* 12: gsm_sch_to_fn(); -1 when rc == 0 */
+	uint16_t t1;         /* 16: the decoded fields; 0 when rc == 0 */
+	uint8_t bsic;        /* 18 */
+	uint8_t t2;          /* 19 */
+	uint8_t t3p;         /* 20 */
+	uint8_t reserved[3]; /* 21: zero */
+} trxhip_sch_sync_result;
+int trxhip_sch_sync_batch_cf32(trxhip_ctx *ctx, const float *d_iq_cf32, size_t buf_stride, trxhip_sch_sync_result *d_results,
+			       int8_t *d_bits, size_t n_bufs, size_t buf_len, int mode, float scale, void *stream);
+int trxhip_sch_sync_batch_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t buf_stride, trxhip_sch_sync_result *d_results,
+			      int8_t *d_bits, size_t n_bufs, size_t buf_len, int mode, float scale, void *stream);
+
 /* delayVector() (sigProcLib.h:97, sigProcLib.cpp:1046-1098) for n_vec complex64 vectors of `len` samples, one delay
  * (in samples) per vector in d_delays: 64-phase 20-tap fractional filter when |frac| > 0.01, then the integer shift
  * with zero fill.  d_out must not alias d_in. */

@@ -172,6 +172,7 @@ void trxhip_destroy(trxhip_ctx *ctx)
 		for (float *t : ctx->d_rs_resamp)
 			if (t) (void)hipFree(t);
 		ctx->redo.destroy();
+		ctx->sch_sync.destroy();
 	}
 	delete ctx;
 }
@@ -542,6 +543,48 @@ int trxhip_detect_sch_batch_cf32(trxhip_ctx *ctx, const float *d_iq, trxhip_burs
 	const int toa_sub = (state == TRXHIP_SCH_DETECT_BUFFER) ? 3 + 39 + 64 : head;      /* :1853-1858 */
 	return trx_launch_sch_detect(d_iq, buf_len, d_results, ctx->d_tables, n_bufs, len, start, toa_sub, threshold,
 				     ctx->sch_unit, static_cast<hipStream_t>(stream));
+}
+
+static int sch_sync_common(trxhip_ctx *ctx, const void *d_iq, int i16, size_t buf_stride, trxhip_sch_sync_result *d_results,
+			   int8_t *d_bits, size_t n_bufs, size_t buf_len, int mode, float scale, void *stream)
+{
+	if (!ctx || !d_iq || !d_results || n_bufs == 0 || n_bufs > 0x7fffffffull || buf_stride < buf_len)
+		return TRXHIP_EINVAL;
+	if (mode == TRXHIP_SCH_SYNC_TRACK) {
+		if (buf_len < 1 || buf_len > 0x7fffffffull)
+			return TRXHIP_EINVAL;
+	} else if (mode == TRXHIP_SCH_SYNC_ACQ) {
+		/* search_stop_pos = len - 512 lags (grgsm_vitac.cpp:304), of which 20 make the first window */
+		if (buf_len < 512 + 20 || buf_len > TRXHIP_SCH_SYNC_MAX_LEN)
+			return TRXHIP_EINVAL;
+	} else {
+		return TRXHIP_EINVAL;
+	}
+	if (with_device(ctx))
+		return TRXHIP_EIO;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (mode == TRXHIP_SCH_SYNC_TRACK)
+		return trx_launch_sch_sync(d_iq, i16, buf_stride, d_results, d_bits, n_bufs, (int)buf_len, 0, scale, nullptr, nullptr, st);
+	trx_sch_scratch &sc = ctx->sch_sync;
+	std::lock_guard<std::mutex> lock(sc.mu);
+	if (!sc.acquire(n_bufs, buf_len - 512))
+		return TRXHIP_ENOMEM;
+	const int rc = trx_launch_sch_sync(d_iq, i16, buf_stride, d_results, d_bits, n_bufs, (int)buf_len, 1, scale, sc.d_power,
+					   sc.d_best, st);
+	sc.launched(st);
+	return rc;
+}
+
+int trxhip_sch_sync_batch_cf32(trxhip_ctx *ctx, const float *d_iq, size_t buf_stride, trxhip_sch_sync_result *d_results,
+			       int8_t *d_bits, size_t n_bufs, size_t buf_len, int mode, float scale, void *stream)
+{
+	return sch_sync_common(ctx, d_iq, 0, buf_stride, d_results, d_bits, n_bufs, buf_len, mode, scale, stream);
+}
+
+int trxhip_sch_sync_batch_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t buf_stride, trxhip_sch_sync_result *d_results,
+			      int8_t *d_bits, size_t n_bufs, size_t buf_len, int mode, float scale, void *stream)
+{
+	return sch_sync_common(ctx, d_iq, 1, buf_stride, d_results, d_bits, n_bufs, buf_len, mode, scale, stream);
 }
 
 int trxhip_delay_vector_batch_cf32(trxhip_ctx *ctx, const float *d_in, float *d_out, const float *d_delays, size_t n_vec,

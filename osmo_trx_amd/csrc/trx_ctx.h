@@ -98,6 +98,67 @@ struct trx_redo_lists {
 	}
 };
 
+/* Scratch of trxhip_sch_sync_batch_*() in ACQ mode (trx_sch_sync.hip): the correlation powers of every lag, n_bufs x (len - 512)
+ * floats, and the chosen window per buffer.  One pair per context, grown on demand and reused from call to call: `mu` is held
+ * from acquire() to launched(), and the buffers are handed out again only once the launches that used them last have completed
+ * (the event), so ACQ calls on one context from several threads or streams run one behind the other. */
+struct trx_sch_scratch {
+	std::mutex mu;
+	float *d_power = nullptr;
+	size_t power_cap = 0;              /* floats */
+	int32_t *d_best = nullptr;
+	size_t best_cap = 0;               /* buffers */
+	hipEvent_t ev = nullptr;
+	bool busy = false;
+
+	/* room for n_bufs buffers of n_lags lags; false: out of memory */
+	bool acquire(size_t n_bufs, size_t n_lags)
+	{
+		if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+			ev = nullptr;
+			return false;
+		}
+		if (busy) {
+			busy = false;
+			if (hipEventSynchronize(ev) != hipSuccess)
+				return false;
+		}
+		if (power_cap < n_bufs * n_lags) {
+			if (d_power) (void)hipFree(d_power);
+			power_cap = 0;
+			if (hipMalloc(reinterpret_cast<void **>(&d_power), n_bufs * n_lags * sizeof(float)) != hipSuccess) {
+				d_power = nullptr;
+				return false;
+			}
+			power_cap = n_bufs * n_lags;
+		}
+		if (best_cap < n_bufs) {
+			if (d_best) (void)hipFree(d_best);
+			best_cap = 0;
+			if (hipMalloc(reinterpret_cast<void **>(&d_best), n_bufs * sizeof(int32_t)) != hipSuccess) {
+				d_best = nullptr;
+				return false;
+			}
+			best_cap = n_bufs;
+		}
+		return true;
+	}
+	void launched(hipStream_t stream)
+	{
+		if (hipEventRecord(ev, stream) == hipSuccess)
+			busy = true;
+		else
+			(void)hipStreamSynchronize(stream);
+	}
+	void destroy()
+	{
+		if (busy) (void)hipEventSynchronize(ev);
+		if (ev) (void)hipEventDestroy(ev);
+		if (d_power) (void)hipFree(d_power);
+		if (d_best) (void)hipFree(d_best);
+	}
+};
+
 struct trxhip_ctx {
 	int device = 0;
 	int n_cu = 0;
@@ -128,6 +189,7 @@ struct trxhip_ctx {
 	 * uploaded on first use */
 	std::mutex rs_mu;
 	float *d_rs_resamp[2] = { nullptr, nullptr };
+	trx_sch_scratch sch_sync;
 };
 
 static inline int with_device(const trxhip_ctx *ctx)

@@ -56,6 +56,12 @@ size_t trx_va_lds_bytes(int L);
 int trx_launch_va_demod(const float *d_iq, const trxhip_burst_params *d_params, const trxhip_burst_result *d_detected, float *d_soft,
 			int32_t *d_starts, size_t n_bursts, int L, float scale, int soft_stride, int flags, hipStream_t stream);
 
+/* trx_sch_sync.hip: the MS-side SCH receiver.  d_iq: int16 IQ (i16) or complex64 buffers, buf_stride samples apart; acq: the
+ * buffer search over the lags 0 .. len - 513 through d_power (n_bufs x (len - 512) floats) and d_best (n_bufs), else the
+ * one-slot search (both NULL) */
+int trx_launch_sch_sync(const void *d_iq, int i16, size_t buf_stride, trxhip_sch_sync_result *d_results, int8_t *d_bits,
+			size_t n_bufs, int len, int acq, float scale, float *d_power, int32_t *d_best, hipStream_t stream);
+
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,
 			 size_t n_bursts, float rssi_offset, hipStream_t stream);

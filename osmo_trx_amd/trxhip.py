@@ -36,6 +36,12 @@ FLAG_EXACT_DEMOD = 2    # TRXHIP_FLAG_EXACT_DEMOD
 FLAG_IDLE_DUMMY = 4     # TRXHIP_FLAG_IDLE_DUMMY
 FLAG_FEW_NB_SLOTS = 16  # TRXHIP_FLAG_FEW_NB_SLOTS (a hint: see include/trxhip.h)
 SCH_DETECT_FULL, SCH_DETECT_NARROW, SCH_DETECT_BUFFER = 0, 1, 2   # sch_detect_type (sigProcLib.h:139-143)
+SCH_SYNC_TRACK, SCH_SYNC_ACQ = 0, 1                               # TRXHIP_SCH_SYNC_*
+SCH_SYNC_MAX_LEN = 1 << 20                                        # TRXHIP_SCH_SYNC_MAX_LEN
+# trxhip_sch_sync_result
+SCH_SYNC_DTYPE = np.dtype([("rc", "<i4"), ("start", "<i4"), ("corr_max", "<f4"), ("fn", "<i4"), ("t1", "<u2"), ("bsic", "u1"),
+                           ("t2", "u1"), ("t3p", "u1"), ("reserved", "u1", (3,))])
+assert SCH_SYNC_DTYPE.itemsize == 24
 
 
 def few_nb_hint(host_params):
@@ -82,6 +88,8 @@ SYMBOLS = {
     "trxhip_scale_vector_cf32": (_I, [_VP, _VP, _SZ, C.c_float, C.c_float, _VP]),
     "trxhip_demod_va_batch_cf32": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _SZ, _I, C.c_float, _I, _I, _VP]),
     "trxhip_detect_sch_batch_cf32": (_I, [_VP, _VP, _VP, _SZ, _SZ, _I, _I, C.c_float, _VP]),
+    "trxhip_sch_sync_batch_cf32": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _SZ, _I, _F, _VP]),
+    "trxhip_sch_sync_batch_i16": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _SZ, _I, _F, _VP]),
     "trxhip_vector_slicer": (_I, [_VP, _VP, _VP, _SZ, _VP]),
     "trxhip_pack_trxd_batch": (_I, [_VP, _VP, _VP, _I, _VP, _SZ, _F, _VP]),
     "trxhip_pack_trxd_wire_batch": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _SZ, _F, _VP]),
@@ -457,6 +465,27 @@ class TrxHip:
         _check(self.L.trxhip_detect_sch_batch_cf32(self.h, self._dev(iq_cf32), self._dev(results), n, buf_len, sps, state,
                                                    threshold, self._stream(stream)), "trxhip_detect_sch_batch_cf32")
         return results
+
+    def sch_sync(self, iq, mode, scale=1.0 / 2047.0, want_bits=False, buf_len=None, stream=None):
+        """The MS-side SCH receiver (ms_trx::handle_sch + decode_sch): iq complex64[n, stride] or int16[n, stride, 2] buffers of
+        which the first buf_len samples (default: all) are used; mode SCH_SYNC_TRACK (one slot) or SCH_SYNC_ACQ (buffer search);
+        scale: convert_and_scale's factor, 1 / rxFullScale in the reference.  Returns SCH_SYNC_DTYPE[n] (numpy; synchronises),
+        and with want_bits also the demodulated sbits int8[n, 148]."""
+        torch = self.torch
+        n, stride = iq.shape[0], iq.shape[1]
+        if iq.dtype == torch.int16:
+            assert iq.dim() == 3 and iq.shape[2] == 2
+            fn, name = self.L.trxhip_sch_sync_batch_i16, "trxhip_sch_sync_batch_i16"
+        elif iq.dtype == torch.complex64:
+            fn, name = self.L.trxhip_sch_sync_batch_cf32, "trxhip_sch_sync_batch_cf32"
+        else:
+            raise TrxHipError(f"unsupported IQ dtype {iq.dtype}")
+        results = torch.empty((n, SCH_SYNC_DTYPE.itemsize), dtype=torch.uint8, device=iq.device)
+        bits = torch.empty((n, 148), dtype=torch.int8, device=iq.device) if want_bits else None
+        _check(fn(self.h, self._dev(iq), stride, self._dev(results), self._dev(bits) if want_bits else _VP(0), n,
+                  stride if buf_len is None else buf_len, mode, scale, self._stream(stream)), name)
+        rec = results.cpu().numpy().reshape(-1).view(SCH_SYNC_DTYPE)
+        return (rec, bits.cpu().numpy()) if want_bits else rec
 
     @staticmethod
     def results_to_numpy(results):
