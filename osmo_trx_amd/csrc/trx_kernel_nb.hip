@@ -72,7 +72,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	static_assert(NB_TABLES_BYTES % 16 == 0 && (NB_SLICE * 8) % 16 == 0 && (K4_XS * 8) % 16 == 0 && (NB_D_LEN * 8) % 16 == 0, "16-byte LDS accesses");
 	static_assert(NB_LDS_BYTES <= 160 * 1024, "LDS");
 	static_assert(NB_ASM_GDEC_OFF == (TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36) * 4, "tools/gen_nb_asm.py: LDS offset of the decimator taps");
-	static_assert(NB_ASM_DEC_MAX_NACT == 15 + NB_ASM_CORR_MAX_LEN, "tools/gen_nb_asm.py: DEC and CORR change form at the same window");
+	static_assert(NB_ASM_DEC_MAX_NACT == 15 + NB_ASM_CORR_MAX_LEN, "tools/gen_nb_asm.py: DEC and CORR change form at the same window (one test)");
 	static_assert(NB_ASM_LSEQ_OFF == (NB_TABLES_FLOATS - 2 * 8 * 16) * 4, "tools/gen_nb_asm.py: LDS offset of the training-sequence taps");
 	static_assert(NB_ASM_AW_PD == (PH_M0 + 52) * 8 && NB_ASM_AW_D == K4_XS * 8 && NB_ASM_AW_CZ == (K4_XS + NB_D_LEN + TRX_CZ_PAD) * 8,
 		      "tools/gen_nb_asm.py: offsets of P, D[] and cz[] inside a wave's slice");
@@ -151,7 +151,10 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	// the peak-ratio gate's estimate (tools/gen_nb_asm.py, DETA): thresh^2 / num for the four possible term counts, and the
 	// constant term of its certain-pass bound
 	const float thr2 = thresh * thresh;
-	// (gk5 .. gk8 = thresh^2 / 5 .. thresh^2 / 8 come as kernel arguments: scalar registers)
+	// (gk5 .. gk8 = thresh^2 / 5 .. thresh^2 / 8 come as kernel arguments; the loop keeps them in lanes 5 .. 8 of ONE vector
+	// register, from which the gate reads the one it needs by lane number: four scalar registers less across the loop)
+	float gkv = lane0 == 5 ? gk5 : lane0 == 6 ? gk6 : lane0 == 7 ? gk7 : gk8;
+	asm volatile("" : "+v"(gkv));
 	const float gc0 = thr2 * 1.0001e-5f;
 	// (int)(sync->toa * 512) of the eight training sequences, 4 bits each (+-1 for the reference's tables); a table set whose
 	// offsets do not fit leaves every burst to the general kernel
@@ -325,6 +328,25 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		q_n = 0;
 	};
 
+	// the record's inputs of a detected burst: lane q_n of the seven registers (toa in 1/512 symbol: position - sync->toa - head)
+	auto queue_record = [&](const int xr_bits, const int xi_bits, const int es_bits, const int toa, const int s_bits, const int fl, const unsigned bb) {
+		asm("s_lshl_b64 exec, 1, %[n]\n\t"
+		    "v_mov_b32_e32 %[qxr], %[xr]\n\t"
+		    "v_mov_b32_e32 %[qxi], %[xi]\n\t"
+		    "v_mov_b32_e32 %[qes], %[es]\n\t"
+		    "v_mov_b32_e32 %[qtoa], %[toa]\n\t"
+		    "v_mov_b32_e32 %[qs], %[ss]\n\t"
+		    "v_mov_b32_e32 %[qfl], %[fl]\n\t"
+		    "v_mov_b32_e32 %[qb], %[b]\n\t"
+		    "s_mov_b64 exec, -1"
+		    : [qxr] "+v"(q_xr), [qxi] "+v"(q_xi), [qes] "+v"(q_es), [qtoa] "+v"(q_toa), [qs] "+v"(q_s), [qfl] "+v"(q_fl),
+		      [qb] "+v"(q_b)
+		    : [n] "s"(uni(q_n)), [xr] "s"(xr_bits), [xi] "s"(xi_bits), [es] "s"(es_bits), [toa] "s"(toa),
+		      [ss] "s"(s_bits), [fl] "s"(fl), [b] "s"((int)bb)
+		    : "scc");                                              // (s_lshl_b64 writes SCC: the geometry's compare may not be carried across it)
+		q_n++;
+	};
+
 	// ---- cold: demodGmskBurst for a TOA outside the straight-line geometry (shift w = nk >> 7 above 0: an early burst; below -36:
 	// later than 9 symbols).  The general kernel's fused demodulator (trx_kernel4.hip, "FUSED": same sums, same order -- the
 	// results are bit-identical to its) on this kernel's buffers: full outputs from the composite filter, the partial ones at the
@@ -352,7 +374,11 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		const bool need_hi = (n_hi >= n_lo) && (i0h <= fdiv4(n_hi + 15)) && (i0h < nwrite);
 		// (the wave-uniform conditions of this path as integers read from lane 0, the per-lane ones formed again where they are
 		// used: as bools they are lane masks, two scalar registers each, live across the filter -- more than the burst loop has left)
-		const int lo_tab = uni(need_lo && (n_hi >= 4 * (i_full_lo - 1)));
+		// (a partial output the tables do not cover is known from the shift alone: the burst leaves here, in front of the table
+		// reads, and behind this the tables cover whatever is needed -- no condition of it stays live as a mask)
+		if (uni((need_lo && !(n_hi >= 4 * (i_full_lo - 1))) || (need_hi && !((w <= -2) && (n_lo <= 4 * i0h - 15)))))
+			return false;
+		const int lo_tab = uni(need_lo);
 		float ct0 = 0.0f, ct1 = 0.0f, ct2 = 0.0f;
 		const int le = lane >> 4, lt = lane & 15;
 		const int li = i0l + le;
@@ -364,9 +390,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			ct1 = row[16];
 			ct2 = (lt < 4) ? row[32] : 0.0f;
 		}
-		const int hi_tab = uni(need_hi && (w <= -2) && (n_lo <= 4 * i0h - 15));
-		if ((need_lo && !lo_tab) || (need_hi && !hi_tab))
-			return false;
+		const int hi_tab = uni(need_hi);
 		float ch0 = 0.0f, ch1 = 0.0f, ch2 = 0.0f;
 		const int hi_i = i0h + le;
 		const int htm = n_hi + 15 - 4 * hi_i;
@@ -478,8 +502,6 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	// million bursts, and a million atomics on one counter cost ten times the batch)
 	// ("something was left" once per wave: a million stores to one address serialise in the L2 like a million atomics)
 	auto mark_left = [&](const unsigned bb) {
-		pend_m = 0;                                                 // nothing of this burst is stored
-		pend_rm = 0;
 		if (nb_lane_id() == 0) {
 			reinterpret_cast<uint8_t *>(redo + TRX_REDO_HDR)[bb] = 1;
 			if (!left_any)
@@ -488,7 +510,9 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		asm volatile("");                                           // (the lanes rejoin here, not in the loop's latch: see flush_records)
 		left_any = 1;
 	};
-	for (unsigned b = b_first; b != NB_NO_BURST; b = b_next) {
+	// (the back edge is the likely one: the copies of the carried burst number and slot word are laid out behind the loop's last
+	// test, not out of line with a jump of their own there and back)
+	for (unsigned b = b_first; __builtin_expect(b != NB_NO_BURST, 1); b = b_next) {
 		// (the prefetch offsets pass through an empty statement once per burst: the zero-extension of a value defined in front of
 		// the loop is hoisted there as a register pair, and the prefetch loads then take the 64-bit vector address after all.  No
 		// instruction, the same register.)
@@ -506,6 +530,9 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 #endif
 		// (one compare: a type or TSC that does not fit sets the high bits of the word whose upper half is max_toa)
 		const unsigned slot_key = prm0 | (0u - ((prm0 & 0xf8ffu) ^ (unsigned)TRXHIP_TSC));
+		// (a burst that is left to the general kernel is flagged where that is decided, on a rare side, and stores nothing:
+		// pend_m = 0.  A value carried to the loop's end, not a test on the main path)
+		int keep = -1;
 		if (__builtin_expect(slot_key >= toa_lim, 0)) {
 			// the prefetched samples are dropped, but they must be "used": a path that reaches the next prefetch with loads
 			// the compiler still counts as outstanding makes it wait for vmcnt(0) right behind the new loads (measured: -4 %)
@@ -514,125 +541,149 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 				asm volatile("" :: "v"(pre_i[r]));
 			store_pending();
 			advance(claim_take(ticket));
+			pend_rm = 0;
 			mark_left(b);
-			continue;
-		}
-
-		// ---- phase 0: registers -> fp32 polyphase LDS; clip scan and energyDetect partial sums on the fly
-		// (row r of the ten is offset 128 r of a_p: one address register, the offsets fit the 8-bit fields of ds_write2_b64)
-		lds_v2f *const pload = reinterpret_cast<lds_v2f *>(a_p);
-		float amax = 0.0f, epart = 0.0f;
+			keep = 0;                                               // nothing of this burst is stored
+		} else {
+			// ---- phase 0: registers -> fp32 polyphase LDS; clip scan and energyDetect partial sums on the fly
+			// (row r of the ten is offset 128 r of a_p: one address register, the offsets fit the 8-bit fields of ds_write2_b64)
+			lds_v2f *const pload = reinterpret_cast<lds_v2f *>(a_p);
+			float amax = 0.0f, epart = 0.0f;
 #pragma unroll
-		for (int r = 0; r < NLD; r++) {
-			const v2f v = { (float)(int16_t)(pre_i[r] & 0xffffu), (float)(int16_t)(pre_i[r] >> 16) };
-			// the tenth row has 49 samples: lanes 49..63 hold sample 624 once more (prefetch) -- the maximum may take it again,
-			// the LDS may not: the row is written under a constant mask, with no compare and no branch round it
-			if (r < NLD - 1)
-				pload[16 * r] = v;
-			else
-				asm volatile("s_bfm_b64 exec, 49, 0\n\t"
-					     "ds_write_b64 %0, %1 offset:%c2\n\t"
-					     "s_mov_b64 exec, -1"
-					     :: "v"(a_p), "v"(v), "n"(128 * (NLD - 1)) : "memory");
-			asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v.x), "v"(v.y));
-			if (r < 5)
-				epart = fmaf(v.x, v.x, fmaf(v.y, v.y, epart));
-		}
-		DIAG_MARK(14);
-		// ---- the previous burst's output: 148 soft bits (lanes 2..49: symbols 3 lane - 2 + j as one 12-byte store, lanes
-		// 54, 57, 60, 63: symbols 0..3) and the result record (lanes 0..7)
-		store_pending();
-		DIAG_MARK(16);
-		// (a converted burst has at least five LDS writes behind the ticket's request -- ten rows, at most two per instruction --
-		// and nothing else on lgkmcnt: the ticket is there when five are outstanding, the writes drain under the next block)
-		advance(claim_take_behind<5>(ticket));
-		DIAG_MARK(15);
+			for (int r = 0; r < NLD; r++) {
+				const v2f v = { (float)(int16_t)(pre_i[r] & 0xffffu), (float)(int16_t)(pre_i[r] >> 16) };
+				// the tenth row has 49 samples: lanes 49..63 hold sample 624 once more (prefetch) -- the maximum may take it again,
+				// the LDS may not: the row is written under a constant mask, with no compare and no branch round it
+				if (r < NLD - 1)
+					pload[16 * r] = v;
+				else
+					asm volatile("s_bfm_b64 exec, 49, 0\n\t"
+						     "ds_write_b64 %0, %1 offset:%c2\n\t"
+						     "s_mov_b64 exec, -1"
+						     :: "v"(a_p), "v"(v), "n"(128 * (NLD - 1)) : "memory");
+				asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v.x), "v"(v.y));
+				if (r < 5)
+					epart = fmaf(v.x, v.x, fmaf(v.y, v.y, epart));
+			}
+			DIAG_MARK(14);
+			// ---- the previous burst's output: 148 soft bits (lanes 2..49: symbols 3 lane - 2 + j as one 12-byte store, lanes
+			// 54, 57, 60, 63: symbols 0..3) and the result record (lanes 0..7)
+			store_pending();
+			DIAG_MARK(16);
+			// (a converted burst has at least five LDS writes behind the ticket's request -- ten rows, at most two per instruction --
+			// and nothing else on lgkmcnt: the ticket is there when five are outstanding, the writes drain under the next block)
+			advance(claim_take_behind<5>(ticket));
+			DIAG_MARK(15);
 
-		pend_m = 0;
-		pend_rm = 0xff;                                             // (a slot without a burst, until one is detected)
-		int leave = 0;
-		{
-			// maxAmplitude() > 30000 (:1711-1722, :1746)
-			const int clip = __ballot(amax > TRX_CLIP_THRESH) != 0ull;
-
-			// ---- detectGeneralBurst window of a normal burst (:1887-1904: target 82, head 10, tail 6 + max_toa -> start 71,
-			// len 16 + max_toa): decimated samples 56 .. 70 + len, one per lane
-			const int len = 16 + (int)max_toa;
-			__builtin_assume(len >= 16 && len <= 16 + NB_MAX_TOA);
-			// (hand-placed blocks: tools/gen_nb_asm.py)  decimator of the window + the addition-only correlation's guard
-			// (P, D[] and cz[] of this lane: compile-time offsets of a_w inside the blocks)
-			// (windows of up to NB_ASM_CORR_MAX_LEN lags: the accumulators of DEC and CORR move across the lanes -- decimated sample i
-			// ends in lane i + 4, lag k in lane k + NB_ASM_CORR_LANE0; wider windows: lane = sample / lag, the samples through LDS)
-			unsigned long long bad;
-			float dr, di;
-			asm volatile(NB_ASM_DEC
-				     : [bad] "=s"(bad), [dr] "=&v"(dr), [di] "=&v"(di)
-				     : [aw] "v"(a_w), [zero] "v"(0), [nact] "s"(15 + len)
-				     : NB_ASM_CLOBBERS);
-			DIAG_MARK(2);
+			pend_rm = 0;                                                // (0xff: a slot without a burst -- the rare side below)
 			{
-				// ---- correlation (lag k in lane k + lag0; the right zero pad of cz[] is stored too), arg-max and the energyDetect
-				// sum (:1573-1585); the lane constants of the TOA search are fetched in the reductions' wait states
-				float v;
+				// maxAmplitude() > 30000 (:1711-1722, :1746)
+				// (an integer in ONE scalar register: as a bool it is a lane mask, a register pair, from here to the record)
+				int clip;
+				asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, 1, 0" : "=s"(clip) : "s"(__ballot(amax > TRX_CLIP_THRESH)) : "scc");
+
+				// ---- detectGeneralBurst window of a normal burst (:1887-1904: target 82, head 10, tail 6 + max_toa -> start 71,
+				// len 16 + max_toa): decimated samples 56 .. 70 + len, one per lane
+				const int len = 16 + (int)max_toa;
+				__builtin_assume(len >= 16 && len <= 16 + NB_MAX_TOA);
+				// (hand-placed blocks: tools/gen_nb_asm.py)  decimator of the window + the addition-only correlation's guard
+				// (P, D[] and cz[] of this lane: compile-time offsets of a_w inside the blocks)
+				// (windows of up to NB_ASM_CORR_MAX_LEN lags: the accumulators of DEC and CORR move across the lanes -- decimated sample i
+				// ends in lane i + 4, lag k in lane k + NB_ASM_CORR_LANE0; wider windows: lane = sample / lag, the samples through LDS)
+				// (DEC and CORR are ONE statement: their rare forms -- the wide window, a sample that fails the guard -- lie in the shadow
+				// of CORR's computed jump, and the main path falls through to it)
+				// ---- correlation (lag k in lane k + lag0; the right zero pad of cz[] is stored too)
+				float v;                                                    // |corr|^2 by lane
 				const int lag0 = (len <= NB_ASM_CORR_MAX_LEN) ? NB_ASM_CORR_LANE0 : 0;   // lane of lag 0
-				asm volatile(NB_ASM_CORR
+				asm volatile(NB_ASM_DECCORR
 					     : [nrm] "=&v"(v)
-					     : [aw] "v"(a_w), [dr] "v"(dr), [di] "v"(di), [len] "s"(len), [tsc] "s"(tsc), [bad] "s"(bad)
+					     : [aw] "v"(a_w), [zero] "v"(0), [len] "s"(len), [tsc] "s"(tsc)
 					     : NB_ASM_CLOBBERS);
-				DIAG_MARK(3);
-				int m_bits, es_bits, bidx;
-				int kr, ka, kb, kic, ktp;                                   // lane constants (lcn[])
-				asm volatile(NB_ASM_AMAX("ds_read_b32 %[kr], %[l4] offset:%c[lc]", "ds_read_b32 %[ka], %[l4] offset:%c[lc]+256",
-							 "ds_read_b32 %[kb], %[l4] offset:%c[lc]+512", "ds_read_b32 %[kic], %[l4] offset:%c[lc]+768",
-							 "ds_read_b32 %[ktp], %[l4] offset:%c[lc]+1024", "s_nop 0", "s_nop 0", "s_nop 0")
-					     "s_sub_u32 %[bidx], %[bidx], %[lag0]\n\t"                 // arg-max lane -> lag (no maximum: bidx is not read)
-					     "s_waitcnt lgkmcnt(0)"
-					     : [m] "=&s"(m_bits), [es] "=&s"(es_bits), [bidx] "=&s"(bidx), [kr] "=&v"(kr), [ka] "=&v"(ka), [kb] "=&v"(kb),
-					       [kic] "=&v"(kic), [ktp] "=&v"(ktp)
-					     : [nrm] "v"(v), [ep] "v"(epart), [l4] "v"(a_l4), [lag0] "s"(lag0),
-					       [lc] "n"((TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 64 + 5 * WAVE) * 4)
-					     : NB_ASM_CLOBBERS);
-				DIAG_MARK(4);
-				int toa512 = 0;
-				if (__builtin_expect(m_bits != 0, 1)) {                                          // fastPeakDetect: a maximum above zero exists (:1120-1139)
-					// edge gate, peak-ratio gate, round A of the TOA bisection and its walk (DETA); round B, walk, peak value (DETB)
+				{
+					// ---- arg-max and the energyDetect sum (:1573-1585); the lane constants of the TOA search are fetched in the
+					// reductions' wait states
+					DIAG_MARK(3);
+					int m_bits, es_bits, bidx;
+					int kr, ka, kb, kic, ktp;                                   // lane constants (lcn[])
+					asm volatile(NB_ASM_AMAX("ds_read_b32 %[kr], %[l4] offset:%c[lc]", "ds_read_b32 %[ka], %[l4] offset:%c[lc]+256",
+								 "ds_read_b32 %[kb], %[l4] offset:%c[lc]+512", "ds_read_b32 %[kic], %[l4] offset:%c[lc]+768",
+								 "ds_read_b32 %[ktp], %[l4] offset:%c[lc]+1024", "s_nop 0", "s_nop 0", "s_nop 0")
+						     "s_sub_u32 %[bidx], %[bidx], %[lag0]\n\t"                 // arg-max lane -> lag (no maximum: -lag0)
+						     "s_waitcnt lgkmcnt(0)"
+						     : [m] "=&s"(m_bits), [es] "=&s"(es_bits), [bidx] "=&s"(bidx), [kr] "=&v"(kr), [ka] "=&v"(ka), [kb] "=&v"(kb),
+						       [kic] "=&v"(kic), [ktp] "=&v"(ktp)
+						     : [nrm] "v"(v), [ep] "v"(epart), [l4] "v"(a_l4), [lag0] "s"(lag0),
+						       [lc] "n"((TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 64 + 5 * WAVE) * 4)
+						     : NB_ASM_CLOBBERS);
+					DIAG_MARK(4);
+					// edge gate, peak-ratio gate, round A of the TOA bisection and its walk (DETA); round B, walk, peak value (DETB).
+					// fastPeakDetect's "a maximum above zero exists" (:1120-1139) is DETA's edge gate: without one every |corr|^2 is +0,
+					// the arg-max is the first lane and bidx = -lag0 <= 0 -- status 0, like any peak at the window's edge.
+					// (the status lives in the blocks' fixed register NB_ASM_ST: their rare sides, behind the loop, write it too)
+					// INVARIANT of NB_ASM_COLD (control flow the compiler does not see: it is entered from and left for labels inside DETA,
+					// DETB and TAIL): the cold code reads and writes only registers that are in the clobber list of all three statements, and
+					// NB_ASM_ST, which must stay the bound output of DETA and DETB.  No %[operand] of these statements may be named there (the
+					// generator asserts it), and none of the statements may be duplicated (their labels would be, too: the assembler refuses).
 					int st, e512;
 					float km;
 					asm volatile(NB_ASM_DETA
-						     : [st] "=&s"(st), [e] "=&s"(e512), [km] "=&v"(km)
+						     : [st] "=&" NB_ASM_ST(st), [e] "=&s"(e512), [km] "=&v"(km)
 						     : [bidx] "s"(bidx), [len] "s"(len), [czb] "s"(lds_addr(cz)), [kr] "v"(kr), [ka] "v"(ka), [l16] "v"(a_l16),
-						       [k5] "s"(gk5), [k6] "s"(gk6), [k7] "s"(gk7), [k8] "s"(gk8), [c0] "v"(gc0)
-						     : NB_ASM_CLOBBERS);
+						       [gkv] "v"(gkv), [c0] "v"(gc0)
+						     : NB_ASM_CLOBBERS_ST);
 					DIAG_MARK(5);
-					int xr_bits = 0, xi_bits = 0;
+					int toa512 = 0, xr_bits = 0, xi_bits = 0;
 					if (__builtin_expect(st == 1, 1)) {
 						asm volatile(NB_ASM_DETB
-							     : [st] "=&s"(st), [toa] "=&s"(toa512), [xr] "=&s"(xr_bits), [xi] "=&s"(xi_bits)
+							     : [st] "=&" NB_ASM_ST(st), [toa] "=&s"(toa512), [xr] "=&s"(xr_bits), [xi] "=&s"(xi_bits)
 							     : [e] "s"(e512), [kb] "v"(kb), [czb] "s"(lds_addr(cz)), [km] "v"(km)
-							     : NB_ASM_CLOBBERS);
+							     : NB_ASM_CLOBBERS_ST);
 						DIAG_MARK(6);
 					}
-					if (__builtin_expect(st == 3, 0)) {
-						// an uncertified early / late decision on the path: the search again in the reference's operand order
-						const int lane = nb_lane_id();
-						if (lane == 0)
-							atomicAdd(&g_trx_fast_stats[0], 1ull);
-						PeakConst pkc;
-						pkc.flA = pkcl[0 * WAVE + lane]; pkc.loA = pkcl[1 * WAVE + lane]; pkc.hiA = pkcl[2 * WAVE + lane];
-						pkc.offB = pkcl[3 * WAVE + lane]; pkc.ratio_off = pkcl[4 * WAVE + lane];
-						c32 xcorr;
-						peak_detect_spec(cz, bidx, sincv, pkc, lane, &toa512, &xcorr, wa4);
-						toa512 = uni(toa512);
-						xr_bits = uni(__float_as_int(xcorr.x));
-						xi_bits = uni(__float_as_int(xcorr.y));
-						st = 1;
-					}
-					if (__builtin_expect(st == 2, 0)) {
-						leave = 1;                                          // the gate is too close to call for the estimate
-						if (nb_lane_id() == 0) atomicAdd(&g_trx_fast_stats[2], 1ull);
+					// ---- everything but "detected, every decision certified": ONE test on the main path, the rare side tells them apart
+					if (__builtin_expect(st != 1, 0)) {
+						// (an opaque copy: the three values are told apart HERE, not by a comparison tree in front of the main path's test)
+						int stc = st;
+						asm volatile("" : "+s"(stc));
+						if (stc == 3) {
+							// an uncertified early / late decision on the path: the search again in the reference's operand order
+							const int lane = nb_lane_id();
+							if (lane == 0)
+								atomicAdd(&g_trx_fast_stats[0], 1ull);
+							PeakConst pkc;
+							pkc.flA = pkcl[0 * WAVE + lane]; pkc.loA = pkcl[1 * WAVE + lane]; pkc.hiA = pkcl[2 * WAVE + lane];
+							pkc.offB = pkcl[3 * WAVE + lane]; pkc.ratio_off = pkcl[4 * WAVE + lane];
+							c32 xcorr;
+							peak_detect_spec(cz, bidx, sincv, pkc, lane, &toa512, &xcorr, wa4);
+							toa512 = uni(toa512);
+							xr_bits = uni(__float_as_int(xcorr.x));
+							xi_bits = uni(__float_as_int(xcorr.y));
+							st = 1;
+						} else if (stc == 2) {
+							// the gate is too close to call for the estimate
+							if (nb_lane_id() == 0) atomicAdd(&g_trx_fast_stats[2], 1ull);
+							mark_left(b);
+							keep = 0;
+						} else {
+							// nothing found: rc (:1764), energy and RSSI (Transceiver.cpp:741,751), zero soft bits
+							const float energy = __int_as_float(es_bits) * 0.0125f;
+							const float rssi = rssi_db(full_scale, energy);
+							const uint32_t flags = ((uint32_t)clip << 8) | (1u << 16);
+							int word = clip ? -TRXHIP_SIGERR_CLIP : 0;
+							word = put_lane<1>(word, 0.0f);
+							word = put_lane<2>(word, 0.0f);
+							word = put_lane<3>(word, 0.0f);
+							word = put_lane<4>(word, 0.0f);
+							word = put_lane<5>(word, energy);
+							word = put_lane<6>(word, rssi);
+							word = write_lane<7>(word, (int)flags);
+							recw = word;
+							o = (v3f){ 0.0f, 0.0f, 0.0f };
+							pend_rm = 0xff;                                 // (a slot without a burst: the record goes with the soft bits)
+						}
 					}
 					if (__builtin_expect(st == 1, 1)) {
-						// computeCI, amp, toa, the result record, 1 / amp; then demodGmskBurst of the usual geometry (TAIL)
+						// ---- computeCI, amp, toa, the result record, 1 / amp; then demodGmskBurst of the usual geometry (TAIL)
 						int ok, s_bits;
 						float d0, d1, d2;
 						const int t5 = (t5pk << (28 - 4 * tsc)) >> 28;
@@ -650,6 +701,11 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						o.x = __builtin_amdgcn_fmed3f(fmaf(0.5f, d0, 0.5f), 0.0f, 1.0f);
 						o.y = __builtin_amdgcn_fmed3f(fmaf(0.5f, d1, 0.5f), 0.0f, 1.0f);
 						o.z = __builtin_amdgcn_fmed3f(fmaf(0.5f, d2, 0.5f), 0.0f, 1.0f);
+						// the record's inputs are queued in front of the geometry test -- no test of "left" behind it, and none of them is
+						// carried across the rare side's filter in a scalar register; a burst left to the general kernel there gives its
+						// place in the queue back
+						queue_record(xr_bits, xi_bits, es_bits, toa512 - t5 - 10 * 512, s_bits,
+							     (int)((uint32_t)tsc | ((uint32_t)clip << 8) | (37u << 24)), b);
 						if (__builtin_expect(!ok, 0)) {
 							// TOA outside the straight-line geometry (an early burst, or one later than 9 symbols): the general form
 							const int lane = nb_lane_id();
@@ -658,57 +714,25 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 							const float xr = __int_as_float(xr_bits), xi = __int_as_float(xi_bits);
 							const float a0 = xr * h[2], a1 = xr * h[3], a2 = xi * h[3], a3 = xi * h[2];
 							const c32 ampv = make_float2(unif(a0 - a2), unif(a1 + a3));     // amp = peak / gain, as block TAIL has it
-							if (!demod_general(t5 + 10 * 512 - toa512, ampv, lane))
-								leave = 1;
-						}
-						pend_rm = 0;
-						if (__builtin_expect(!leave, 1)) {
-							// the record's inputs: lane q_n of the seven registers (toa in 1/512 symbol: position - sync->toa - head)
-							asm("s_lshl_b64 exec, 1, %[n]\n\t"
-						    "v_mov_b32_e32 %[qxr], %[xr]\n\t"
-						    "v_mov_b32_e32 %[qxi], %[xi]\n\t"
-						    "v_mov_b32_e32 %[qes], %[es]\n\t"
-						    "v_mov_b32_e32 %[qtoa], %[toa]\n\t"
-						    "v_mov_b32_e32 %[qs], %[ss]\n\t"
-						    "v_mov_b32_e32 %[qfl], %[fl]\n\t"
-						    "v_mov_b32_e32 %[qb], %[b]\n\t"
-						    "s_mov_b64 exec, -1"
-						    : [qxr] "+v"(q_xr), [qxi] "+v"(q_xi), [qes] "+v"(q_es), [qtoa] "+v"(q_toa), [qs] "+v"(q_s), [qfl] "+v"(q_fl),
-						      [qb] "+v"(q_b)
-						    : [n] "s"(uni(q_n)), [xr] "s"(xr_bits), [xi] "s"(xi_bits), [es] "s"(es_bits), [toa] "s"(toa512 - t5 - 10 * 512),
-						      [ss] "s"(s_bits), [fl] "s"((int)((uint32_t)tsc | ((uint32_t)clip << 8) | (37u << 24))), [b] "s"((int)b));
-						q_n++;
+							if (!demod_general(t5 + 10 * 512 - toa512, ampv, lane)) {
+								q_n--;
+								mark_left(b);
+								keep = 0;
+							}
 						}
 					}
 				}
-				if (__builtin_expect(pend_rm & ~leave & 1, 0)) {
-					// nothing found: rc (:1764), energy and RSSI (Transceiver.cpp:741,751), zero soft bits
-					const float energy = __int_as_float(es_bits) * 0.0125f;
-					const float rssi = rssi_db(full_scale, energy);
-					const uint32_t flags = ((uint32_t)clip << 8) | (1u << 16);
-					int word = clip ? -TRXHIP_SIGERR_CLIP : 0;
-					word = put_lane<1>(word, 0.0f);
-					word = put_lane<2>(word, 0.0f);
-					word = put_lane<3>(word, 0.0f);
-					word = put_lane<4>(word, 0.0f);
-					word = put_lane<5>(word, energy);
-					word = put_lane<6>(word, rssi);
-					word = write_lane<7>(word, (int)flags);
-					recw = word;
-					o = (v3f){ 0.0f, 0.0f, 0.0f };
-				}
 			}
 		}
-		if (__builtin_expect(leave, 0)) {
-			mark_left(b);
-			continue;
-		}
 		pend_b = b;
-		pend_m = -1;
+		pend_m = keep;
 		if (__builtin_expect(q_n == WAVE, 0))
 			flush_records();
 		DIAG_MARK(11);
 	}
+	// ---- the rare sides of the blocks DETA, DETB and TAIL (tools/gen_nb_asm.py: NB_ASM_COLD), entered from and left for labels
+	// inside those blocks; here it is jumped over
+	asm volatile(NB_ASM_COLD ::: NB_ASM_CLOBBERS);
 	// ---- the last burst's output
 	store_pending();
 	flush_records();                                               // the records still in the registers

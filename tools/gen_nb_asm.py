@@ -12,7 +12,13 @@ blocks below are therefore whole phases of a burst, and this script CHECKS what 
   * every register loaded from LDS is covered by an s_waitcnt lgkmcnt(n) before its first use (LDS returns in order);
   * a DPP source lane that EXEC disables is invalid: the mask of a wave_shr:1 instruction is a run of lanes from lane 0.
 Registers: operands the compiler allocates are %[name]; the blocks' temporaries are the fixed VGPRs v64..v127 and SGPRs
-s87..s99, declared as clobbers of every statement (NB_ASM_CLOBBERS)."""
+s87..s99, declared as clobbers of every statement (NB_ASM_CLOBBERS).
+Jumps: the burst loop's main path FALLS THROUGH every block -- no jump over cold code.  A block's rare side lies either in
+the shadow of a taken jump the main path cannot avoid (DEC and CORR are one statement: the wide and the multiplying forms sit
+between CORR's computed jump and its first variant), or in NB_ASM_COLD, one statement behind the loop that names fixed
+registers only (DETA's gate exit and careful walk, DETB's careful walk, TAIL's geometry exit), which is why the detection status
+has a fixed register (NB_ASM_ST).  Cold labels carry the prefix .Lnbc_; where they may lie is checked here, and on the compiled
+kernel by tools/isa_guard_nb.py."""
 import os
 import re
 import sys
@@ -241,9 +247,9 @@ def sreg(i, n=1):
 #                 D[lane] offset AW_D, D[lane - 4] offset AW_D - 32 (ds_write2_b32's offsets have 8 bits: that one address is formed
 #                 in a wait state of the sum's last adds)
 #   %[zero] VGPR  0 (address of the wave-uniform tap reads)
-#   %[nact] SGPR  15 + len: decimated samples
-#   %[bad]  SGPR pair out: lanes whose decimated sample fails the guard
-#   %[dr] %[di] VGPR out: the decimated sample, re / im (lane l + 4: sample l; undefined for the wide form)
+#   %[len]  SGPR  window length; 15 + len decimated samples (NACT, a fixed register)
+#   out: VCC lanes whose decimated sample fails the guard; DRI (fixed registers) the decimated sample, re / im (lane l + 4:
+#        sample l; moving form only)
 # y = sum_k x[4i-15+k] * g[k], product then sum, k ascending, first sum = first product (decimate16_sym<true>); taps 0..7
 # only (bitwise symmetric filter).  Tap k of output l is polyphase entry P[(k+1)&3][m0 + l + ((k+1)>>2)]: for one phase the
 # entry output l takes at row offset j+1 is the one output l+1 takes at offset j.
@@ -251,9 +257,11 @@ def sreg(i, n=1):
 #     sixteen products with them; the accumulator of output l starts in lane l and MOVES one lane up (wave_shr:1 on the
 #     accumulator operand of the add) whenever the next tap's sample lives one row further -- in front of taps 3, 7, 11, 15.
 #     The same products, summed in the same order; output l ends in lane l + 4.  4 sample reads instead of 16.
-#   * wider windows (15 + len + 4 > 64 lanes): lane = output, sixteen reads per lane (.Lnb_dec_wide).
+#   * wider windows (15 + len + 4 > 64 lanes): lane = output, sixteen reads per lane (cold: .Lnbc_dc_wide).
 # ------------------------------------------------------------------------------------------------------------------
 DEC_SHIFT = 4                    # lanes the moving accumulator travels
+NACT = "s92"                     # 15 + len, decimated samples: made at the head of the statement (DEC and CORR are ONE statement)
+DRI = ("v110", "v111")           # the decimated sample of lane - 4, re / im: from DEC's moving form to CORR's
 DEC_MAX_NACT = 64 - DEC_SHIFT    # widest window of the moving form
 DPP_SHR = "wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
 
@@ -262,9 +270,8 @@ def dec_guard(b, re, im, t0, t1):
     b(f"v_min_f32_e64 {t0}, |{re}|, |{im}|")
     b(f"v_max_f32_e64 {t1}, |{re}|, |{im}|")
     b(f"v_ldexp_f32 {t0}, {t0}, 17")
-    b(f"v_cmp_lt_f32_e32 vcc, {t0}, {t1}")
+    b(f"v_cmp_lt_f32_e32 vcc, {t0}, {t1}")                          # VCC: lanes whose decimated sample fails the guard
     b("s_mov_b64 exec, -1")
-    b("s_mov_b64 %[bad], vcc")
     b("s_waitcnt lgkmcnt(0)")          # (the store: nothing of this block may be outstanding for the checker; costs nothing behind the guard)
 
 
@@ -275,11 +282,11 @@ def dec_tap(kk):
 
 
 def dec_moving(gdec_off):
-    b = Block("DEC[moving]", ("nact", "bad"))
+    b = Block("DEC", ("len",))
     PR = lambda k: 64 + 2 * k                  # product of tap k: v[64+2k : 65+2k]
     XR = lambda r: vreg(96 + 2 * r, 2)         # this lane's entry of phase r
     ACC = 104
-    b(f"s_sub_u32 s88, {DEC_MAX_NACT}, %[nact]")
+    b(f"s_sub_u32 s88, {DEC_MAX_NACT}, {NACT}")
     b("s_lshr_b64 exec, -1, s88")             # lanes 0 .. nact + 3 (all 64 at the widest window, which s_bfm_b64 cannot express):
                                               # every lane an accumulator passes through (a DPP source lane must be enabled)
     b(f"ds_read_b128 {vreg(120, 4)}, %[zero] offset:{gdec_off}")
@@ -315,19 +322,19 @@ def dec_moving(gdec_off):
     add(14)
     b(f"v_add_u32_e32 v108, {AW_D - 8 * DEC_SHIFT}, %[aw]")        # &D[lane - 4] (one of the two wait states in front of the DPP source)
     b("s_nop 0")
-    out = ("%[dr]", "%[di]")
+    out = DRI
     add_moving(15, out)
-    b(f"s_bfm_b64 exec, %[nact], {DEC_SHIFT}")                     # output l sits in lane l + 4
-    b("ds_write2_b32 v108, %[dr], %[di] offset1:1")          # D[] stays: computeCI's samples (TAIL), the multiplying correlation
+    b(f"s_bfm_b64 exec, {NACT}, {DEC_SHIFT}")                      # output l sits in lane l + 4
+    b(f"ds_write2_b32 v108, {out[0]}, {out[1]} offset1:1")         # D[] stays: computeCI's samples (TAIL), the multiplying correlation
     dec_guard(b, out[0], out[1], "v106", "v107")
-    b.exec_ok = {f"v{ACC}", f"v{ACC + 1}", "%[dr]", "%[di]", "v108"}       # (lanes 4 .. nact + 3 are inside the mask they were written under)
+    b.exec_ok = {f"v{ACC}", f"v{ACC + 1}", out[0], out[1], "v108"}       # (lanes 4 .. nact + 3 are inside the mask they were written under)
     return b
 
 
 def dec_wide(gdec_off):
-    b = Block("DEC[wide]", ("nact", "bad"))
+    b = Block("DEC_WIDE", ("len",))
     X = lambda k: vreg(88 + 2 * k, 2)
-    b("s_bfm_b64 exec, %[nact], 0")
+    b(f"s_bfm_b64 exec, {NACT}, 0")
     b(f"ds_read_b128 {vreg(120, 4)}, %[zero] offset:{gdec_off}")
     b(f"ds_read_b128 {vreg(124, 4)}, %[zero] offset:{gdec_off + 16}")
     for k in range(16):
@@ -355,15 +362,6 @@ def dec_wide(gdec_off):
     return b
 
 
-def block_dec(gdec_off):
-    """-> (block, [straight-line paths to check])"""
-    mv, wd = dec_moving(gdec_off), dec_wide(gdec_off)
-    b = Block("DEC", ("nact", "bad"))
-    b.ins = [f"s_cmp_gt_u32 %[nact], {DEC_MAX_NACT}", "s_cbranch_scc1 .Lnb_dec_wide"] + mv.ins + ["s_branch .Lnb_dec_end", ".Lnb_dec_wide:"] + \
-        wd.ins + [".Lnb_dec_end:"]
-    return b, [mv, wd]
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # block CORR: correlation of the window against the slot's training sequence without multiplications (corr_unit,
 # trx_device.h: every tap is +-1 rotated by k pi/2 under the guard); arg-max input.
@@ -371,7 +369,11 @@ def block_dec(gdec_off):
 #                cz[lane - 19] are 152 bytes below those
 #   %[len] SGPR  window length                    %[tsc] SGPR  training sequence 0..7
 #   %[nrm] VGPR out: |corr|^2 (0 for lanes that hold no lag)
-#   %[dr] %[di] VGPR the decimated sample of lane - 4 (block DEC)
+#   DRI (fixed registers) the decimated sample of lane - 4 (block DEC, moving form)
+# DEC and CORR are ONE statement (NB_ASM_DECCORR): the main path -- the moving forms, a guard that holds -- falls through DEC, tests
+# the window's width and the guard once each, and leaves CORR by two taken jumps, the computed one into a variant and the variant's
+# own to the end (every variant carries the short tail: the stores of cz[], |corr|^2; the last one falls through).  The rare forms
+# lie in the computed jump's shadow, between it and the first variant.
 # The sum is one chain by definition (the reference's order: k ascending from +0, convolve_base.c:28-54).  Eight variants
 # (the sign / component pattern of a training sequence), entered by a computed jump.
 #   * wide windows (more than 45 lags): lane = lag; D[lag + k] from LDS, one v_pk_add_f32 per tap (sign / swap are
@@ -385,18 +387,18 @@ CORR_LANE0 = DEC_SHIFT + 15      # lane of lag 0 in the moving form
 CORR_MAX_LEN = 64 - CORR_LANE0
 
 
-def corr_jump(b, sfx):
+def corr_jump(b, sfx, pfx=".Lnb_corr"):
     b("s_getpc_b64 s[88:89]")
-    b(f".Lnb_corr{sfx}_pc:")
-    b(f"s_mul_i32 s90, %[tsc], .Lnb_corr{sfx}_v1-.Lnb_corr{sfx}_v0")
+    b(f"{pfx}{sfx}_pc:")
+    b(f"s_mul_i32 s90, %[tsc], {pfx}{sfx}_v1-{pfx}{sfx}_v0")
     b("s_add_u32 s88, s88, s90")
     b("s_addc_u32 s89, s89, 0")
-    b(f"s_add_u32 s88, s88, .Lnb_corr{sfx}_v0-.Lnb_corr{sfx}_pc")
+    b(f"s_add_u32 s88, s88, {pfx}{sfx}_v0-{pfx}{sfx}_pc")
     b("s_addc_u32 s89, s89, 0")
     b("s_setpc_b64 s[88:89]")
 
 
-def corr_mul(b, sfx, lseq_off, X, ACC):
+def corr_mul(b, sfx, lseq_off, X, ACC, join=True):
     """cold (about one burst in 3000): convolve_complex() as written (convolve_base.c:28-40, :72-85), taps from LDS:
     (yr, yi) += (xr hr - xi hi, xr hi + xi hr) as two packed multiplies, one packed add with the low half negated, one accumulate"""
     b("s_lshl_b32 s90, %[tsc], 7")
@@ -413,7 +415,8 @@ def corr_mul(b, sfx, lseq_off, X, ACC):
             b("v_pk_add_f32 v[86:87], v[82:83], v[84:85] neg_lo:[0,1] neg_hi:[0,0]")
             b("s_nop 0")
             b(f"v_pk_add_f32 {ACC}, {ACC}, v[86:87]")
-    b(f"s_branch .Lnb_corr{sfx}_join")
+    if join:
+        b(f"s_branch .Lnbc_corr{sfx}_join")
 
 
 def corr_lanes(lseq_off, sfx):
@@ -425,13 +428,12 @@ def corr_lanes(lseq_off, sfx):
     h("s_bfm_b64 exec, %[len], 0")
     for k in range(16):
         h(f"ds_read_b64 {X(k)}, %[aw] offset:{AW_D + 8 * k}")
-    h("s_cmp_lg_u64 %[bad], 0")                                    # a sample failed the guard: the multiplying form
-    h(f"s_cbranch_scc1 .Lnb_corr{sfx}_mul")
-    corr_jump(h, sfx)
+    h(f"s_cbranch_vccnz .Lnbc_corr{sfx}_mul")                      # a sample failed the guard (VCC: block DEC): the multiplying form
+    corr_jump(h, sfx, ".Lnbc_corr")
     vs = []
     for t in range(8):
         v = Block("v")
-        v(f".Lnb_corr{sfx}_v{t}:")
+        v(f".Lnbc_corr{sfx}_v{t}:")
         for k in range(16):
             odd, neg = (k & 1), (NEG_MASKS[t] >> k) & 1
             if not odd and not neg:
@@ -444,10 +446,10 @@ def corr_lanes(lseq_off, sfx):
                 mod = " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,0] neg_hi:[0,1]"
             v(f"s_waitcnt lgkmcnt({15 - k})")
             v(f"v_pk_add_f32 {ACC}, {ACC}, {X(k)}{mod}")
-        v(f"s_branch .Lnb_corr{sfx}_join")
+        v(f"s_branch .Lnbc_corr{sfx}_join")
         vs.append(v.ins)
     j = Block("j")
-    j(f".Lnb_corr{sfx}_join:")
+    j(f".Lnbc_corr{sfx}_join:")
     j("s_add_u32 s90, %[len], 12")
     j("s_bfm_b64 exec, s90, 0")
     j(f"ds_write_b64 %[aw], {ACC} offset:{AW_CZ}")
@@ -455,19 +457,19 @@ def corr_lanes(lseq_off, sfx):
     j(f"v_pk_mul_f32 v[122:123], {ACC}, {ACC}")
     j("s_waitcnt lgkmcnt(0)")
     j("v_add_f32_e32 %[nrm], v123, v122")
-    j("s_branch .Lnb_corr_end")
     m = Block("m")
-    m(f".Lnb_corr{sfx}_mul:")
+    m(f".Lnbc_corr{sfx}_mul:")
     corr_mul(m, sfx, lseq_off, X, ACC)
     return h.ins, vs, j.ins, m.ins
 
 
 def corr_moving(lseq_off):
-    """lane = lag + 19, samples from block DEC's registers"""
+    """lane = lag + 19, samples from block DEC's registers -> (head, [variant t], tail, mul): lists of lines.  The tail (the
+    stores of cz[], |corr|^2) closes EVERY variant: a variant leaves for the block's end itself, the last one by falling through"""
     sfx = "r"
     X = lambda k: vreg(88 + 2 * k, 2)
     ACC = vreg(120, 2)
-    D = ("%[dr]", "%[di]")
+    D = DRI
     h = Block("h")
     h(f"v_mov_b64_e32 {ACC}, 0")
     h("v_mov_b64_e32 v[122:123], 0")
@@ -476,9 +478,16 @@ def corr_moving(lseq_off):
     h(f"s_sub_u32 s91, {CORR_MAX_LEN}, %[len]")
     h("v_add_u32_e32 v64, s90, %[aw]")                              # &cz[len + lane]: the right zero pad, stored by lanes 0..11
     h("s_lshr_b64 exec, -1, s91")                                  # lanes 0 .. len + 18: every lane that holds a sample or passes an accumulator on
-    h("s_cmp_lg_u64 %[bad], 0")
-    h(f"s_cbranch_scc1 .Lnb_corr{sfx}_mul")
-    corr_jump(h, sfx)
+    j = Block("j")
+    j("s_bfm_b64 exec, 12, 0")
+    j(f"ds_write_b64 v64, v[122:123] offset:{AW_CZ}")
+    j(f"s_bfm_b64 exec, %[len], {CORR_LANE0}")
+    j(f"ds_write_b64 %[aw], {ACC} offset:{AW_CZ - 8 * CORR_LANE0}")
+    j(f"v_pk_mul_f32 v[124:125], {ACC}, {ACC}")
+    j("s_nop 0")
+    j("v_add_f32_e32 %[nrm], v125, v124")
+    j("s_mov_b64 exec, -1")
+    j("s_waitcnt lgkmcnt(0)")
     vs = []
     for t in range(8):
         v = Block("v")
@@ -497,58 +506,57 @@ def corr_moving(lseq_off):
                     v(f"v_{ops[c][0]}_f32_dpp v{120 + c}, v{120 + c}, {ops[c][1]} {DPP_SHR}")
             if k < 15:
                 v("s_nop 0")
-        v(f"s_branch .Lnb_corr{sfx}_join")
+        v.ins += j.ins
+        if t < 7:
+            v("s_branch .Lnb_corr_end")
         vs.append(v.ins)
-    j = Block("j")
-    j(f".Lnb_corr{sfx}_join:")
-    j("s_bfm_b64 exec, 12, 0")
-    j(f"ds_write_b64 v64, v[122:123] offset:{AW_CZ}")
-    j(f"s_bfm_b64 exec, %[len], {CORR_LANE0}")
-    j(f"ds_write_b64 %[aw], {ACC} offset:{AW_CZ - 8 * CORR_LANE0}")
-    j(f"v_pk_mul_f32 v[124:125], {ACC}, {ACC}")
-    j("s_nop 0")
-    j("v_add_f32_e32 %[nrm], v125, v124")
-    j("s_mov_b64 exec, -1")
-    j("s_waitcnt lgkmcnt(0)")
-    j("s_branch .Lnb_corr_end")
     m = Block("m")
-    m(f".Lnb_corr{sfx}_mul:")
     m(f"s_bfm_b64 exec, %[len], {CORR_LANE0}")
     for k in range(16):
         m(f"ds_read_b64 {X(k)}, %[aw] offset:{AW_D - 8 * CORR_LANE0 + 8 * k}")
-    corr_mul(m, sfx, lseq_off, X, ACC)
+    corr_mul(m, sfx, lseq_off, X, ACC, join=False)
     return h.ins, vs, j.ins, m.ins
 
 
-def block_corr(lseq_off):
+def block_deccorr(gdec_off, lseq_off):
     """-> (block, [straight-line paths to check])"""
-    ops = ("len", "tsc", "bad")
-    b = Block("CORR", ops)
-    paths = []
-
-    def add_form(name, parts, pre):
-        h, vs, j, m = parts
-        b.ins += h
-        for v in vs:
-            b.ins += v
-        b.ins += j + m
-        ibr = next(i for i, t in enumerate(h) if t.startswith("s_cbranch_scc1"))
-        for t, v in enumerate(vs):
-            p = Block(f"CORR[{name}, tsc {t}]", ops)
-            p.ins = pre + h + v + j
-            paths.append(p)
-        p = Block(f"CORR[{name}, mul]", ops)
-        p.ins = pre + h[:ibr] + m + j
-        paths.append(p)
-
-    pre = [f"s_cmp_gt_u32 %[len], {CORR_MAX_LEN}", "s_cbranch_scc1 .Lnb_corr_wide"]
-    b.ins += pre
-    add_form("moving", corr_moving(lseq_off), pre)
-    b.ins += [".Lnb_corr_wide:"]
-    add_form("lanes", corr_lanes(lseq_off, "w"), pre)
+    ops = ("len", "tsc")
+    pre = [f"s_add_u32 {NACT}, %[len], 15", f"s_cmp_gt_u32 %[len], {CORR_MAX_LEN}", "s_cbranch_scc1 .Lnbc_dc_wide"]
+    mv, wd = dec_moving(gdec_off), dec_wide(gdec_off)
+    h, vs, j, m = corr_moving(lseq_off)
+    wh, wvs, wj, wm = corr_lanes(lseq_off, "w")
+    hj = Block("hj")
+    corr_jump(hj, "r")
+    b = Block("DECCORR", ops)
+    b.ins = pre + mv.ins + ["s_cbranch_vccnz .Lnbc_dc_mul"] + h + hj.ins
+    # ---- in the computed jump's shadow: the wide window's forms; the moving form's multiplying variant
+    b.ins += [".Lnbc_dc_wide:"] + wd.ins + wh
+    for v in wvs:
+        b.ins += v
+    b.ins += wj + ["s_branch .Lnb_corr_end"] + wm
+    b.ins += [".Lnbc_dc_mul:"] + h + m + j + ["s_branch .Lnb_corr_end"]
+    for v in vs:
+        b.ins += v
     b.ins += [".Lnb_corr_end:"]
+    paths = []
+    for t, v in enumerate(vs):
+        p = Block(f"DECCORR[moving, tsc {t}]", ops)
+        p.ins = pre + mv.ins + h + hj.ins + v
+        paths.append(p)
+    p = Block("DECCORR[moving, mul]", ops)
+    p.ins = pre + mv.ins + h + m + j
+    paths.append(p)
+    ibr = next(i for i, t in enumerate(wh) if t.startswith("s_cbranch_vccnz"))
+    for t, v in enumerate(wvs):
+        p = Block(f"DECCORR[lanes, tsc {t}]", ops)
+        p.ins = pre + wd.ins + wh + v + wj
+        paths.append(p)
+    p = Block("DECCORR[lanes, mul]", ops)
+    p.ins = pre + wd.ins + wh[:ibr] + wm + wj
+    paths.append(p)
     for p in paths:
-        p.exec_ok = {"v120", "v121"}                               # (the lanes read are inside the mask they were written under)
+        # (the lanes read are inside the mask they were written under: DEC's outputs in lanes 4 .. nact + 3, the accumulators)
+        p.exec_ok = set(mv.exec_ok) | {"v120", "v121"}
     return b, paths
 
 
@@ -622,6 +630,7 @@ def fhex(x):
     return "0x%08x" % struct.unpack("<I", struct.pack("<f", x))[0]
 
 
+ST = "s98"                       # the detection status of DETA / DETB: a fixed register, written by the cold code too
 KAPPA = 6e-6                     # TRX_FAST_KAPPA (trx_device.h): certified-comparison margin of the FAST detector
 D_ALL = "row_mask:0xf bank_mask:0xf"
 
@@ -651,24 +660,30 @@ def careful_walk(b, c, cd, p, pos, levels, unsure_label, w="b64"):
 # on an estimate with a proven margin, round A of peakDetect()'s bisection (levels 0..4, trx_device.h peak_detect_fast) and
 # its certified tree walk.
 #   in : %[bidx] %[len] %[czb] SGPR (czb = LDS byte address of cz[0]); %[kr] %[ka] VGPR lane constants (byte offsets of the
-#        lane's peak-ratio term and of round A's first tap, relative to &cz[bidx]); %[l16] VGPR 16 * lane; %[k5]..%[k8] SGPR
-#        thresh^2 / n; %[c0] VGPR thresh^2 * 1.0001e-5; %[nodes] SGPR pair 0x1555555555555555
-#   out: %[st] SGPR 0 miss / 1 found / 2 gate too close to call / 3 an uncertified decision on the path; %[e] SGPR earlyIndex
-#        * 512 after round A; %[km] VGPR KAPPA * |corr[bidx]|^2 (round B's margin term)
+#        lane's peak-ratio term and of round A's first tap, relative to &cz[bidx]); %[l16] VGPR 16 * lane; %[gkv] VGPR lane n =
+#        thresh^2 / n (n = 5..8); %[c0] VGPR thresh^2 * 1.0001e-5
+#   out: status in the FIXED register NB_ASM_ST (the kernel binds its operand to it: "={s98}"), 0 miss / 1 found / 2 gate too
+#        close to call / 3 an uncertified decision on the path; %[e] SGPR earlyIndex * 512 after round A; %[km] VGPR KAPPA *
+#        |corr[bidx]|^2 (round B's margin term)
+# The main path falls through the block: its rare sides -- the gate's exit, the careful walk -- are in NB_ASM_COLD, a statement
+# behind the burst loop that names fixed registers only (which is why the status has one), and come back to .Lnb_da_walked /
+# .Lnb_da_end; the edge gate leaves for .Lnb_da_end directly.
 # The gate: reference |amp| / (sqrtf(avg / num) + 1e-5) < thresh.  Estimate t2 = avg * thresh^2 / num (avg tree-summed: within
 # 6e-7; t2 within 1.2e-6 of the reference's squared threshold without its 1e-5).  (rms + 1e-5)^2 >= rms^2, so amp2 < t2 (1 -
 # 1.2e-5) is a certain miss; (rms + 1e-5)^2 <= rms^2 (1 + 1e-5) + 1.0001e-5 (2ab <= a^2 + b^2), so amp2 > t2 * 1.000024 + c0 is
 # a certain pass; in between (one burst in ~5e4) the burst is left to the general kernel, which rounds as the reference does.
 # ------------------------------------------------------------------------------------------------------------------
 def block_deta(wa4_off):
-    b = Block("DETA", ("bidx", "len", "czb", "k5", "k6", "k7", "k8", "st", "e"))
+    b = Block("DETA", ("bidx", "len", "czb", "e"))
+    cold = Block("DETA_COLD")
     X = lambda k: vreg(88 + 2 * k, 2)            # round A samples 0..7
     Y = lambda k: vreg(112 + 2 * k, 2)           # samples 8..15
-    b("s_mov_b32 %[st], 0")
-    b("s_cmp_lt_i32 %[bidx], 3")                                   # :1683
-    b("s_cbranch_scc1 .Lnb_da_end")
-    b("s_sub_u32 s88, %[len], 3")
-    b("s_cmp_gt_i32 %[bidx], s88")
+    # the edge gate (:1683): 3 <= bidx <= len - 3 as ONE unsigned range compare (len >= 16).  A window without a maximum above
+    # zero (fastPeakDetect, :1120-1139: every |corr|^2 is +0, so the first lane holds "the maximum" and bidx = -lag0 <= 0) leaves here, too
+    b(f"s_mov_b32 {ST}, 0")
+    b("s_sub_u32 s88, %[bidx], 3")
+    b("s_sub_u32 s89, %[len], 6")
+    b("s_cmp_gt_u32 s88, s89")
     b("s_cbranch_scc1 .Lnb_da_end")
     b("s_lshl3_add_u32 s89, %[bidx], %[czb]")                      # &cz[bidx]
     b("s_add_u32 s90, %[len], -1")
@@ -692,9 +707,10 @@ def block_deta(wa4_off):
     b("v_mov_b64_e32 v[84:85], 0")                                 # p0, p1 of the two-chain sums
     b("v_mov_b64_e32 v[86:87], 0")
     # number of in-range terms (:1555-1562) -> thresh^2 / num: scalar instructions, placed in the wait states of the vector ones
+    # (thresh^2 / num, num = 5..8: lane num of %[gkv], made in front of the burst loop -- one v_readlane in place of three
+    # compare / select pairs, and no scalar register is held for the four constants across the loop)
     sc = ["s_add_u32 s91, %[bidx], -1", "s_sub_u32 s92, %[len], %[bidx]", "s_min_u32 s91, s91, 4", "s_add_u32 s92, s92, -2",
-          "s_min_u32 s92, s92, 4", "s_add_u32 s91, s91, s92", "s_cmp_eq_u32 s91, 8", "s_cselect_b32 s92, %[k8], %[k7]",
-          "s_cmp_eq_u32 s91, 6", "s_cselect_b32 s93, %[k6], %[k5]", "s_cmp_ge_u32 s91, 7", "s_cselect_b32 s92, s92, s93"]
+          "s_min_u32 s92, s92, 4", "s_add_u32 s91, s91, s92", "v_readlane_b32 s92, %[gkv], s91"]
     for t in sc[:3]:
         b(t)
     b("s_waitcnt lgkmcnt(11)")
@@ -710,21 +726,16 @@ def block_deta(wa4_off):
     b(sc[5])
     b(sc[6])
     b(f"v_add_f32_dpp v75, v75, v75 quad_perm:[1,0,3,2] {D_ALL}")
-    b(sc[7])
-    b(sc[8])
+    b("s_nop 1")
     b(f"v_add_f32_dpp v75, v75, v75 quad_perm:[2,3,0,1] {D_ALL}")
-    b(sc[9])
-    b(sc[10])
+    b("s_nop 1")
     b(f"v_add_f32_dpp v75, v75, v75 row_half_mirror {D_ALL}")     # lanes 0..7: sum of the eight terms
-    b(sc[11])
     b("v_mul_f32_e32 v112, s92, v75")                              # t2
     b(f"v_mul_f32_e32 v113, {fhex(1.0 - 1.2e-5)}, v112")
     b(f"v_fmamk_f32 v114, v112, {fhex(1.000024)}, %[c0]")
-    b("v_cmp_lt_f32_e32 vcc, v74, v113")
-    b("s_cbranch_vccnz .Lnb_da_wait_end")                          # certain miss
+    # (v113 <= v112 <= v114: what is no certain pass leaves, and the cold exit tells the certain miss from the too-close-to-call)
     b("v_cmp_gt_f32_e32 vcc, v74, v114")
-    b("s_mov_b32 %[st], 2")
-    b("s_cbranch_vccz .Lnb_da_wait_end")                           # too close to call
+    b("s_cbranch_vccz .Lnbc_da_gate")
     b("s_mov_b64 exec, -1")
     # ---- round A: interp over taps fl-7 .. fl+8 with this lane's weights, two FMA chains (even / odd taps)
     b(f"ds_read_b128 v[104:107], %[l16] offset:{wa4_off + 2048}")
@@ -755,43 +766,49 @@ def block_deta(wa4_off):
     b("s_lshl_b32 s94, %[bidx], 9")
     b(f"v_mov_b32_dpp v90, v90 quad_perm:[1,0,3,2] {D_ALL}")
     b("v_cmp_lt_f32_e64 s[88:89], v91, v90")
-    b("s_mov_b32 %[st], 1")
+    b(f"s_mov_b32 {ST}, 1")
     b("s_lshr_b64 s[90:91], s[88:89], 1")
     b("s_or_b64 s[90:91], s[90:91], s[88:89]")
     b("s_mov_b32 s96, 0x55555555")
     b("s_mov_b32 s97, 0x15555555")
     b("s_and_b64 s[92:93], s[90:91], s[96:97]")
     b("s_cmp_eq_u64 s[92:93], s[96:97]")
-    b("s_cbranch_scc0 .Lnb_da_careful")
+    b("s_cbranch_scc0 .Lnbc_da_careful")
     fast_walk(b, "s[88:89]", "s95", "s96", 5)
     b(".Lnb_da_walked:")
     b("s_lshl_b32 s95, s95, 5")                                    # off = 32 p - 496; E = (bidx - 1) * 512 + off
     b("s_add_u32 s94, s94, s95")
     b("s_add_u32 %[e], s94, -1008")
-    b("s_branch .Lnb_da_end")
-    b(".Lnb_da_careful:")
-    careful_walk(b, "s[88:89]", "s[90:91]", "s95", "s96", 5, ".Lnb_da_unsure")
-    b("s_branch .Lnb_da_walked")
-    b(".Lnb_da_unsure:")
-    b("s_mov_b32 %[st], 3")
-    b("s_branch .Lnb_da_end")
-    b(".Lnb_da_wait_end:")
-    b("s_mov_b64 exec, -1")
-    b("s_waitcnt lgkmcnt(0)")
     b(".Lnb_da_end:")
-    return b
+    # ---- cold (NB_ASM_COLD, behind the burst loop): fixed registers only
+    cold(".Lnbc_da_careful:")
+    careful_walk(cold, "s[88:89]", "s[90:91]", "s95", "s96", 5, ".Lnbc_da_unsure")
+    cold("s_branch .Lnb_da_walked")
+    cold(".Lnbc_da_unsure:")
+    cold(f"s_mov_b32 {ST}, 3")
+    cold("s_branch .Lnb_da_end")
+    cold(".Lnbc_da_gate:")                                         # (EXEC: lanes 0..7, as the gate's compare left it)
+    cold("v_cmp_lt_f32_e32 vcc, v74, v113")                        # certain miss: status 0; else too close to call
+    cold("s_cmp_eq_u64 vcc, 0")
+    cold(f"s_cselect_b32 {ST}, 2, 0")
+    cold("s_mov_b64 exec, -1")
+    cold("s_waitcnt lgkmcnt(0)")
+    cold("s_branch .Lnb_da_end")
+    return b, cold
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # block DETB: round B of the bisection (levels 5..8 on lanes 0..29, the sixteen possible final positions on lanes 32..47),
 # its certified walk, and the interpolated peak value at the final position (peakDetect(), :1141-1186).
 #   in : %[e] SGPR earlyIndex * 512; %[kb] VGPR lane constant offB; %[czb] SGPR; %[km] VGPR
-#   out: %[st] SGPR 1 / 3; %[toa] SGPR final position * 512; %[xr] %[xi] SGPR interpolated value
+#   out: status 1 / 3 in the fixed register NB_ASM_ST; %[toa] SGPR final position * 512; %[xr] %[xi] SGPR interpolated value
+#        (status 3: undefined).  The careful walk is in NB_ASM_COLD (see DETA).
 # sinc LUT index of a fraction f: taps i <= fl use q = 512 k + f, taps i > fl use q = 512 k + (512 - f), XOR-swizzled
 # (trx_tables.h: q ^ ((q >> 4) & 31); swz(512) = 512, so f = 0 needs no special case).  sincv[] sits at LDS offset 0.
 # ------------------------------------------------------------------------------------------------------------------
 def block_detb():
-    b = Block("DETB", ("e", "czb", "st", "toa", "xr", "xi"))
+    b = Block("DETB", ("e", "czb", "toa", "xr", "xi"))
+    cold = Block("DETB_COLD")
     X = lambda k: vreg(80 + 2 * k, 2)
     W = lambda k: 96 + k
     Y = lambda k: vreg(104 + 2 * k, 2)
@@ -833,7 +850,7 @@ def block_detb():
     b("v_pk_add_f32 v[74:75], v[64:65], v[66:67]")                 # interpolated value at this lane's position
     b("s_add_u32 s92, %[e], 497")
     b("v_pk_mul_f32 v[76:77], v[74:75], v[74:75]")
-    b("s_mov_b32 %[st], 1")
+    b(f"s_mov_b32 {ST}, 1")
     b("v_add_f32_e32 v78, v77, v76")
     b(f"v_fmamk_f32 v79, v78, {fhex(KAPPA)}, %[km]")
     b("v_sub_f32_e32 v96, v78, v79")
@@ -845,21 +862,22 @@ def block_detb():
     b("s_or_b32 s90, s90, s88")
     b("s_and_b32 s91, s90, 0x15555555")
     b("s_cmp_eq_u32 s91, 0x15555555")
-    b("s_cbranch_scc0 .Lnb_db_careful")
+    b("s_cbranch_scc0 .Lnbc_db_careful")
     fast_walk(b, "s88", "s94", "s95", 4, "b32")
     b(".Lnb_db_walked:")
     b("s_add_u32 s93, s94, 32")                                    # lane that evaluated the final position
     b("s_lshl1_add_u32 %[toa], s94, s92")                          # E + offB + 512, offB = 2 p - 15
     b("v_readlane_b32 %[xr], v74, s93")
     b("v_readlane_b32 %[xi], v75, s93")
-    b("s_branch .Lnb_db_end")
-    b(".Lnb_db_careful:")
-    careful_walk(b, "s88", "s90", "s94", "s95", 4, ".Lnb_db_unsure", "b32")
-    b("s_branch .Lnb_db_walked")
-    b(".Lnb_db_unsure:")
-    b("s_mov_b32 %[st], 3")
     b(".Lnb_db_end:")
-    return b
+    # ---- cold (NB_ASM_COLD): fixed registers only
+    cold(".Lnbc_db_careful:")
+    careful_walk(cold, "s88", "s90", "s94", "s95", 4, ".Lnbc_db_unsure", "b32")
+    cold("s_branch .Lnb_db_walked")
+    cold(".Lnbc_db_unsure:")
+    cold(f"s_mov_b32 {ST}, 3")
+    cold("s_branch .Lnb_db_end")
+    return b, cold
 
 # ------------------------------------------------------------------------------------------------------------------
 # block TAIL: what detectBurst() does behind peakDetect (:1695-1708) for a found burst, the demodulator's set-up and the
@@ -873,10 +891,11 @@ def block_detb():
 #   in : SGPR toa (position * 512), xr / xi (peak value), t5 ((int)(sync->toa * 512)), hdrb (LDS byte address of the
 #        sequence header), e8lo / e8hi (address of tab->edge8), es (energy sum), fsdb (20 log10 full_scale), flags;
 #        VGPR l16 (16 * lane), aw (slice base + 8 * lane: D[lane] is offset AW_D of it); SGPR pairs modd = 0xaaaa.., m23 = 0xcccc..
-#   out: SGPR ok (0: TOA outside the straight-line geometry), nk; VGPR rows (4 registers), vp, rec
+#   out: SGPR ok (0: TOA outside the straight-line geometry -- left through NB_ASM_COLD, S done), ssum (S); VGPR d0 d1 d2 (block DEMOD)
 # ------------------------------------------------------------------------------------------------------------------
 def block_tail():
     b = Block("TAIL", ("toa", "xr", "xi", "t5", "hdrb", "e8lo", "e8hi", "ok", "ssum", "pb", "cb", "db"))
+    cold = Block("TAIL_COLD")
     b("v_mov_b32_e32 v65, %[hdrb]")
     b("ds_read_b128 v[68:71], v65")                                # gain, 1 / gain
     b("s_sub_u32 s88, %[t5], %[toa]")
@@ -924,11 +943,12 @@ def block_tail():
     # (the burst's record -- C/I, RSSI, amp, toa -- is not made here: its inputs go into lane `slot` of seven registers and 64
     # records are made at once, trx_kernel_nb.hip flush_records; what is per burst is S, computeCI's mean sample power)
     block_demod(b)
-    b("s_branch .Lnb_tl_end")
-    b(".Lnb_tl_wait_end:")
-    b("s_waitcnt vmcnt(0)")                                        # (the tap rows were requested: their registers are free again behind this)
     b(".Lnb_tl_end:")
-    return b
+    # ---- cold (NB_ASM_COLD): the geometry's exit
+    cold(".Lnbc_tl_wait:")
+    cold("s_waitcnt vmcnt(0)")                                     # (the tap rows were requested: their registers are free again behind this)
+    cold("s_branch .Lnb_tl_end")
+    return b, cold
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -979,7 +999,7 @@ def block_demod(b):
     b("s_mov_b64 exec, -1")
     b("s_sub_u32 s96, 0, s88")
     b("s_cmp_gt_u32 s96, 36")
-    b("s_cbranch_scc1 .Lnb_tl_wait_end")
+    b("s_cbranch_scc1 .Lnbc_tl_wait")
     b("s_mov_b32 %[ok], 1")
     b(f"v_add_u32_e32 {vreg(P[0])}, s94, %[kic]")
     for k in range(1, 4):
@@ -1211,16 +1231,37 @@ def main(out=OUT):
     gdec_off = (SINCV_LDS + 16 * 64 + 65 * 36) * 4
     NB_TABLES_END_OLD = SINCV_LDS + 16 * 64 + 65 * 36 + 16 + 64 + 5 * 64 + 5 * 64      # floats in front of the training-sequence taps
     blocks = {}
-    blocks["DEC"], dec_paths = block_dec(gdec_off)
     lseq_off = NB_TABLES_END_OLD * 4
-    blocks["CORR"], corr_paths = block_corr(lseq_off)
+    blocks["DECCORR"], dc_paths = block_deccorr(gdec_off, lseq_off)
     wa4_off = SINCV_LDS * 4
-    blocks["DETA"] = block_deta(wa4_off)
-    blocks["DETB"] = block_detb()
-    blocks["TAIL"] = block_tail()
+    blocks["DETA"], da_cold = block_deta(wa4_off)
+    blocks["DETB"], db_cold = block_detb()
+    blocks["TAIL"], tl_cold = block_tail()
     blocks["FIRG"] = block_firg()
-    errs = [e for p in dec_paths + corr_paths for e in p.check()] + check_paths(blocks["DETA"]) + check_paths(blocks["DETB"]) + \
-        check_paths(blocks["TAIL"]) + check_paths(blocks["FIRG"])
+    # the rare sides of DETA, DETB and TAIL: one statement behind the burst loop, jumped over where it lies.  It is entered from
+    # and left for labels inside those blocks, so it may name fixed registers only -- no %[operand]
+    cold = Block("COLD")
+    cold.ins = ["s_branch .Lnbc_end"] + da_cold.ins + db_cold.ins + tl_cold.ins + [".Lnbc_end:"]
+    assert not any("%[" in t for t in cold.ins)
+    blocks["COLD"] = cold
+
+    def with_cold(b, c):
+        """the hazard checker's view of a block and its cold part: the cold code in front of the block's last label, jumped over
+        (the order the two had as one statement; check_paths() then follows every branch into it)"""
+        v = Block(b.name, [n[2:-1] for n in b.sgpr_ops])
+        assert b.ins[-1].endswith("_end:")
+        v.ins = b.ins[:-1] + ["s_branch " + b.ins[-1][:-1]] + c.ins + [b.ins[-1]]
+        return v
+    errs = [e for p in dc_paths for e in p.check()] + \
+        check_paths(with_cold(blocks["DETA"], da_cold)) + check_paths(with_cold(blocks["DETB"], db_cold)) + \
+        check_paths(with_cold(blocks["TAIL"], tl_cold)) + check_paths(blocks["FIRG"])
+    # no jump over cold code: cold labels (.Lnbc_*) lie behind the loop or in the shadow of DECCORR's computed jump only
+    for name in ("DETA", "DETB", "TAIL"):
+        errs += [f"{name}: cold label {t} inside a block of the main path" for t in blocks[name].ins if t.startswith(".Lnbc_")]
+    dc = blocks["DECCORR"].ins
+    i_pc, i_v0 = min(i for i, t in enumerate(dc) if t.startswith("s_setpc_b64")), dc.index(".Lnb_corrr_v0:")
+    errs += [f"DECCORR: cold label {t} outside the computed jump's shadow" for i, t in enumerate(dc)
+             if t.startswith(".Lnbc_") and not i_pc < i < i_v0]
     hdr = ["// trx_nb_asm.inc -- GENERATED by tools/gen_nb_asm.py (hazards and LDS waits checked there); do not edit.",
            f"#define NB_ASM_GDEC_OFF {gdec_off}",
            f"#define NB_ASM_LSEQ_OFF {lseq_off}",
@@ -1230,8 +1271,12 @@ def main(out=OUT):
            f"#define NB_ASM_AW_PD {AW_PD}",
            f"#define NB_ASM_AW_D {AW_D}",
            f"#define NB_ASM_AW_CZ {AW_CZ}",
+           f'#define NB_ASM_ST "{{{ST}}}"',
            "#define NB_ASM_CLOBBERS " + ", ".join(f'"v{i}"' for i in range(64, 128)) + ", " +
-           ", ".join(f'"s{i}"' for i in range(87, 100)) + ', "vcc", "scc", "memory"']
+           ", ".join(f'"s{i}"' for i in range(87, 100)) + ', "vcc", "scc", "memory"',
+           # (DETA, DETB: the status register is an output there)
+           "#define NB_ASM_CLOBBERS_ST " + ", ".join(f'"v{i}"' for i in range(64, 128)) + ", " +
+           ", ".join(f'"s{i}"' for i in range(87, 100) if f"s{i}" != ST) + ', "vcc", "scc", "memory"']
     for name, b in blocks.items():
         hdr.append(f"#define NB_ASM_{name} \\")
         lines = b.text()

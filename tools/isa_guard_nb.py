@@ -15,8 +15,11 @@ tests/test_isa_guard_cpu.py on every CPU run):
   * what depends only on the lane and the wave is made once in front of the loop (the kernel's a_p, a_w, a_l4, ...): the main path
     outside the hand-placed blocks holds no lane id (v_mbcnt_*) and none of the integer multiplies that addresses were built
     with per burst (v_mul_lo_u32, v_mad_u64_u32, v_mul_u32_u24).
-Reported, not checked: the static instruction, vector-instruction and branch counts of the main path outside the hand-placed
-blocks.
+  * the common burst's path through the loop, blocks included, executes at most 22 branch instructions, at most 3 of them taken
+    (block CORR's computed jump, its variant's exit, the back edge), and no cold code lies on it between a block's entry and
+    its exit (tools/gen_nb_asm.py: labels .Lnbc_*): the main path falls through every block.
+Reported, not checked: the static instruction and vector-instruction counts of the main path outside the hand-placed blocks,
+its branches outside and inside them (branches_outside_blocks, branches_inside_blocks), the taken ones (taken_on_main_path).
 Prints a JSON summary; exit status 1 on a violation."""
 import json
 import os
@@ -89,37 +92,68 @@ def check(text):
     rep = loop_report(body)
     main = rep["loop_main_path"]
     if main is None:
-        errs.append("the burst loop's main path was not found (the ticket's ds_add_rtn_u32 .. back edge behind the last `s_setprio 2`)")
+        errs.append("the burst loop's main path was not found (the ticket's ds_add_rtn_u32 .. a branch back to the loop's head)")
     else:
         # the join blocks that keep the loop's carried state in scalar registers are empty asm statements: a compiler that folds
         # them away brings flush_records() back into the loop, and with it the masks
         if main["flush_records_stores_on_it"]:
             errs.append("flush_records' stores lie on the loop's main path")
-        if not any(g[0] > main["first"] and g[-1] < main["last"] for g in groups[1:]):
+        if not any(all(i in main["lines"] for i in g) for g in groups[1:]):
             errs.append("no prefetch group on the loop's main path")
+        # jumps and tests: the common burst executes at most MAX_BRANCHES branch instructions, MAX_TAKEN of them taken (block CORR's
+        # computed jump, its variant's exit, the back edge), and falls through every block -- no cold code inside one to jump over
+        if main["branches"] > MAX_BRANCHES:
+            errs.append(f"{main['branches']} branch instructions on the loop's main path (at most {MAX_BRANCHES})")
+        if main["taken_on_main_path"] > MAX_TAKEN:
+            errs.append(f"{main['taken_on_main_path']} taken branches on the loop's main path (at most {MAX_TAKEN}): {main['taken']}")
+        if main["cold_labels_inside_blocks"]:
+            errs.append(f"cold code on the loop's main path, between a block's entry and its exit: {main['cold_labels_inside_blocks']}")
+        main["lines"] = len(main["lines"])
         if main["lane_only_work_on_it"]:
             errs.append(f"per-lane constants are rebuilt on the loop's main path: {main['lane_only_work_on_it']}")
     return errs, {"kernel": "nb_pull4_kernel", **res, "instructions": n_ins,
                   "prefetch_groups": [len(g) for g in groups], **rep}
 
 
+COLD_LABEL = re.compile(r"(\.Lnbc_\w+|\.Lnb_(dec_wide|corr_wide|corr\w_mul|corr\w_join|da_careful|da_unsure|da_wait_end|db_careful|db_unsure|"
+                        r"tl_wait_end)):")
+MAX_BRANCHES, MAX_TAKEN = 22, 3
+
+
 def loop_report(body):
-    """The burst loop's main path as laid out -- from the loop header's label (the last one in front of the work ticket's
-    request, the kernel's first ds_add_rtn_u32) to the first branch behind block TAIL (the last `s_setprio 2`) that goes back to a label at the loop's head --
-    its instructions and branches outside every `asm` statement of the source, its vector instructions outside the generated
-    blocks (valu_outside_blocks: the short asm statements of the source -- the clip scan's v_max3, the record's moves -- count,
-    a statement that names one of the blocks' fixed registers v64..v127 does not), whether flush_records' 16-byte stores lie
-    on it, and what it holds of per-lane work that belongs in front of the loop."""
+    """The burst loop's main path AS EXECUTED by the common burst -- a normal-burst slot, detected, every decision certified,
+    straight-line geometry, a narrow window, training sequence 0 -- walked from the loop header's label (the last one in front of
+    the work ticket's request, the kernel's first ds_add_rtn_u32): a conditional branch falls through, the jumps whose target is
+    known statically are followed (s_branch; block CORR's s_setpc_b64, to its first variant), and the walk ends at the first branch
+    to a label at the loop's head, the back edge.  Reported: the path's instructions, vector instructions and branches outside every
+    `asm` statement of the source (valu_outside_blocks: the short asm statements of the source -- the clip scan's v_max3, the
+    record's moves -- count, a statement that names one of the blocks' fixed registers v64..v127 does not), its branches inside
+    the statements, how many of all its branches are taken, the cold labels the path falls into (tools/gen_nb_asm.py: .Lnbc_*; those in the shadow of block CORR's computed jump are not
+    on it),
+    whether flush_records' 16-byte stores lie on it, and what it holds of per-lane work that belongs in front of the loop."""
     try:
         ticket = next(i for i, t in enumerate(body) if "ds_add_rtn_u32" in t)
         head = max(i for i in range(ticket) if re.match(r"\.LBB\d+_\d+:", body[i]))
-        labels = {m.group(1) for t in body[max(0, head - 24):head + 1] for m in [re.match(r"(\.LBB\d+_\d+):", t)] if m}
-        tail = max(i for i, t in enumerate(body) if re.match(r"\s*s_setprio 2", t))
-        back = next(i for i in range(tail, len(body))
-                    if (m := re.match(r"\s*s_c?branch\w*\s+(\.LBB\d+_\d+)", body[i])) and m.group(1) in labels)
     except (StopIteration, ValueError):
         return {"loop_main_path": None}
-    in_asm, branches, ins, valu, lane_only, stmt = False, 0, 0, 0, [], []
+    where = {m.group(1): i for i, t in enumerate(body) for m in [re.match(r"(\.\w+):", t.strip())] if m}
+
+    def reaches_head(i):
+        """a label of the loop's head: from it the header is reached by a few scalar moves and waits (the copies of the carried
+        state), wherever the layout put them -- in front of the header, or out of line with a jump to it"""
+        for _ in range(32):
+            if i is None or i >= len(body):
+                return 0
+            if i == head:
+                return 1
+            m = re.match(r"\s*(s_c?branch\w*|s_setpc_b64|s_endpgm)\s*(\S*)", body[i])
+            if m and m.group(1) != "s_branch":
+                return 0
+            i = where.get(m.group(2)) if m else i + 1
+        return 0
+    labels = {l for l, i in where.items() if re.match(r"\.LBB\d+_\d+$", l) and reaches_head(i)}
+    in_asm, ins, valu, lane_only, stmt = False, 0, 0, [], []
+    br_out, br_in, taken, cold, visited, back = 0, 0, [], [], set(), None
 
     def short_stmt():
         nonlocal valu
@@ -127,22 +161,58 @@ def loop_report(body):
             valu += sum(1 for t in stmt if re.match(r"\s*v_", t))
             lane_only.extend(t.strip() for t in stmt if LANE_ONLY.match(t))
 
-    for t in body[head:back + 1]:
-        if "#ASMSTART" in t or "#ASMEND" in t:
-            if in_asm and "#ASMEND" in t:
-                short_stmt()
-            in_asm, stmt = "#ASMSTART" in t, []
-        elif in_asm:
-            stmt.append(t)
+    i = head
+    while back is None and i < len(body) and i not in visited:
+        t = body[i]
+        visited.add(i)
+        nxt = i + 1
+        if "#ASMSTART" in t:
+            in_asm, stmt = True, []
+        elif "#ASMEND" in t:
+            short_stmt()
+            in_asm = False
+        elif COLD_LABEL.match(t.strip()):                          # the path falls into (or through) cold code
+            cold.append(t.strip()[:-1])
         elif re.match(r"\s+[a-z_0-9]+(\s|$)", t) and not t.strip().startswith((".", ";")):
-            ins += 1
-            branches += bool(re.match(r"\s*s_c?branch", t))
-            valu += bool(re.match(r"\s*v_", t))
-            if LANE_ONLY.match(t):
-                lane_only.append(t.strip())
+            m = re.match(r"\s*(s_cbranch_\w+|s_branch|s_setpc_b64)\s+(\S+)", t)
+            if in_asm:
+                stmt.append(t)
+            else:
+                ins += 1
+                valu += bool(re.match(r"\s*v_", t))
+                if LANE_ONLY.match(t):
+                    lane_only.append(t.strip())
+            if m:
+                br_in += in_asm
+                br_out += not in_asm
+                if m.group(1) == "s_setpc_b64":                   # the computed jump of block CORR: its first variant
+                    nxt = next((k for k in range(i, len(body)) if re.match(r"\.Lnb_corr\w*_v0:", body[k].strip())), None)
+                    taken.append(t.strip())
+                elif m.group(2) in labels:
+                    back = i
+                    taken.append(t.strip())
+                    # (copies of the carried state that the layout put out of line reach the header by a jump of their own)
+                    k = where[m.group(2)]
+                    while k != head:
+                        mm = re.match(r"\s*s_branch\s+(\S+)", body[k])
+                        if mm:
+                            br_out += 1
+                            taken.append(body[k].strip())
+                        k = where[mm.group(1)] if mm else k + 1
+                elif m.group(1) == "s_branch":
+                    nxt = where.get(m.group(2))
+                    taken.append(t.strip())
+                if nxt is None:
+                    break
+        i = nxt
+    if back is None:
+        return {"loop_main_path": None}
     return {"loop_main_path": {"first": head, "last": back, "instructions_outside_blocks": ins, "valu_outside_blocks": valu,
-                               "branches_outside_blocks": branches, "lane_only_work_on_it": lane_only,
-                               "flush_records_stores_on_it": any("global_store_dwordx4" in t for t in body[head:back + 1])}}
+                               "branches_outside_blocks": br_out, "branches_inside_blocks": br_in, "branches": br_out + br_in,
+                               "taken_on_main_path": len(taken), "taken": taken, "cold_labels_inside_blocks": cold,
+                               "lane_only_work_on_it": lane_only,
+                               "flush_records_stores_on_it": any("global_store_dwordx4" in body[k] for k in visited),
+                               "lines": sorted(visited)}}
 
 
 def main():

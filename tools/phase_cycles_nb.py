@@ -20,9 +20,9 @@ L.trxhip_diag_read(buf, 1)
 trx.detect_demod(iq, dp, sps=4); torch.cuda.synchronize()
 L.trxhip_diag_read(buf, 1)
 names = {12: "loop top", 13: "wait for the prefetched samples", 14: "convert + LDS writes", 16: "flush previous burst's stores", 17: "take the work ticket (+ pool)",
-         15: "issue next prefetch", 2: "DEC", 3: "CORR", 4: "AMAX", 5: "DETA", 6: "DETB", 10: "TAIL (record + demod)", 11: "slicer / loop end"}
+         15: "issue next prefetch", 3: "DEC + CORR (one statement)", 4: "AMAX", 5: "DETA", 6: "DETB", 10: "TAIL (record + demod)", 11: "slicer / loop end"}
 tot = sum(buf[:20])
-for k in (12, 13, 14, 16, 17, 15, 2, 3, 4, 5, 6, 10, 11):
+for k in (12, 13, 14, 16, 17, 15, 3, 4, 5, 6, 10, 11):
     print(f"{names[k]:48s} {buf[k] / n:8.0f} cycles/burst  {100.0 * buf[k] / tot:5.1f} %")
 print(f"{'total':48s} {tot / n:8.0f}")
 import time
