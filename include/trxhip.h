@@ -274,6 +274,60 @@ int trxhip_sch_sync_batch_cf32(trxhip_ctx *ctx, const float *d_iq_cf32, size_t b
 int trxhip_sch_sync_batch_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t buf_stride, trxhip_sch_sync_result *d_results,
 			      int8_t *d_bits, size_t n_bufs, size_t buf_len, int mode, float scale, void *stream);
 
+/* The MS-side downlink burst receiver: upper_trx::pullRadioVector() and the burst indication of driveReceiveFIFO()
+ * (ms/ms_upper.cpp:161-304) for n_slots slots of 625 samples at 4 samples per symbol.  Slot b is the 625 samples at
+ * d_iq + b * slot_stride (slot_stride in complex samples, >= 625; a stream cut at a constant 625 is slot_stride = 625); nothing
+ * outside them is read, and where the receiver reaches outside (the reference's zeroed workbuf, 40 samples either side) it reads
+ * zeros.  convert_and_scale's factor is 1.f / rx_full_scale (the reference: 1.f / float(rxFullScale)).
+ * d_slots[b] says where the slot lies in the frame structure and what trxcon answered; its kind follows from (fn, tn) alone, on
+ * the device.  d_ind[b] is always written (fn, tn copied through, reserved bytes zero, sch_fn = -1 where no SCH was decoded):
+ *   SCH      demodulated whether or not ACTIVE is set (the lower layer does, ms_rx_lower.cpp:130-153): start, corr_max, sch_rc,
+ *            sch_fn, sch_bsic and the 148 bits are those of trxhip_sch_sync_batch_*(TRXHIP_SCH_SYNC_TRACK) on the same samples, bit
+ *            for bit; rssi = 10, toa256 = 0 (:194-200); sent = ACTIVE
+ *   FCCH     nothing is computed; with ACTIVE sent = 1 and flags = TRXHIP_MS_IND_TRASH (:189-192), bits zero
+ *   traffic  with ACTIVE: pow = energyDetect(x, 80), gr-gsm's channel estimate on training sequence tsc (59 lags), start clamped to
+ *            [-39, 39], detect_burst_nb; sent = 1, toa256 = 0, rssi = (int)floor(20.0 * log10(rx_full_scale / sqrtf(pow))).  An
+ *            all-zero slot (pow == 0, where the reference divides by zero): rssi = 0, flags = TRXHIP_MS_IND_SILENT, bits and start
+ *            as the receiver gives them.  Without ACTIVE: sent = 0, nothing computed, zeros
+ *   BAD      tn > 7, or a traffic slot with tsc > 7: sent = 0, nothing computed, zeros
+ * d_bits (may be NULL): int8 [n_slots][148], +-127 with -127 a one; zeros where nothing was demodulated.
+ * -TRXHIP_EINVAL (nothing launched, nothing written): a NULL ctx, d_iq, d_slots or d_ind, n_slots == 0, slot_stride < 625,
+ * rx_full_scale not finite or <= 0. */
+#define TRXHIP_MS_KIND_BAD 0    /* tn > 7, or a traffic slot with tsc > 7 */
+#define TRXHIP_MS_KIND_FCCH 1   /* gsm_fcch_check_ts(): tn == 0 && fn % 51 in {0, 10, 20, 30, 40} (ms/sch.c:100-135) */
+#define TRXHIP_MS_KIND_SCH 2    /* gsm_sch_check_ts(): tn == 0 && fn % 51 in {1, 11, 21, 31, 41} */
+#define TRXHIP_MS_KIND_NB 3     /* every other slot */
+#define TRXHIP_MS_SLOT_ACTIVE 1 /* trxcon answered the RTR indication with TRXCON_PHYIF_RTR_F_ACTIVE (ms_upper.cpp:183-187) */
+#define TRXHIP_MS_IND_TRASH 1   /* FCCH slot: the reference returns true without writing anything (:189-192) */
+#define TRXHIP_MS_IND_SILENT 2  /* traffic slot whose energyDetect() is 0: the reference's RSSI is undefined there */
+typedef struct {             /* 8 bytes */
+	uint32_t fn;         /* 0 */
+	uint8_t tn;          /* 4 */
+	uint8_t tsc;         /* 5: the cell's training sequence (traffic slots) */
+	uint8_t flags;       /* 6: TRXHIP_MS_SLOT_* */
+	uint8_t reserved;    /* 7 */
+} trxhip_ms_slot;
+typedef struct {             /* 32 bytes */
+	uint32_t fn;         /* 0 */
+	uint8_t tn;          /* 4 */
+	uint8_t kind;        /* 5: TRXHIP_MS_KIND_* */
+	uint8_t sent;        /* 6: 1 where driveReceiveFIFO() would call trxcon_phyif_handle_burst_ind */
+	uint8_t flags;       /* 7: TRXHIP_MS_IND_* */
+	int16_t rssi;        /* 8 */
+	int16_t toa256;      /* 10 */
+	int32_t start;       /* 12: burst start in samples, after the +-39 clamp (SCH, traffic); else 0 */
+	float corr_max;      /* 16: largest |correlation| of the 20-tap channel estimate */
+	float pow;           /* 20: energyDetect()'s return (traffic); else 0 */
+	int32_t sch_fn;      /* 24: SCH with good parity: gsm_sch_to_fn(); else -1 */
+	uint8_t sch_rc;      /* 28: 1 = SCH decoded */
+	uint8_t sch_bsic;    /* 29 */
+	uint8_t reserved[2]; /* 30: zero */
+} trxhip_ms_burst_ind;
+int trxhip_ms_rx_batch_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t slot_stride, const trxhip_ms_slot *d_slots,
+			   trxhip_ms_burst_ind *d_ind, int8_t *d_bits, size_t n_slots, float rx_full_scale, void *stream);
+int trxhip_ms_rx_batch_cf32(trxhip_ctx *ctx, const float *d_iq_cf32, size_t slot_stride, const trxhip_ms_slot *d_slots,
+			    trxhip_ms_burst_ind *d_ind, int8_t *d_bits, size_t n_slots, float rx_full_scale, void *stream);
+
 /* delayVector() (sigProcLib.h:97, sigProcLib.cpp:1046-1098) for n_vec complex64 vectors of `len` samples, one delay
  * (in samples) per vector in d_delays: 64-phase 20-tap fractional filter when |frac| > 0.01, then the integer shift
  * with zero fill.  d_out must not alias d_in. */

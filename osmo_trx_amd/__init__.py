@@ -9,7 +9,11 @@ generator (synth.py), batch sharding + RCCL table broadcast (shard.py) and the b
 compute entry point raises.
 """
 from .trxhip import (TrxHip, TrxHipError, PARAMS_DTYPE, RESULT_DTYPE, lib_path, load_library,  # noqa: F401
-                     OFF, TSC, EXT_RACH, RACH, SCH, EDGE, IDLE)
+                     OFF, TSC, EXT_RACH, RACH, SCH, EDGE, IDLE,
+                     MS_SLOT_DTYPE, MS_IND_DTYPE, MS_KIND_BAD, MS_KIND_FCCH, MS_KIND_SCH, MS_KIND_NB, MS_SLOT_ACTIVE,
+                     MS_IND_TRASH, MS_IND_SILENT, ms_slot_kind)
 
 __all__ = ["TrxHip", "TrxHipError", "PARAMS_DTYPE", "RESULT_DTYPE", "lib_path", "load_library",
-           "OFF", "TSC", "EXT_RACH", "RACH", "SCH", "EDGE", "IDLE"]
+           "OFF", "TSC", "EXT_RACH", "RACH", "SCH", "EDGE", "IDLE",
+           "MS_SLOT_DTYPE", "MS_IND_DTYPE", "MS_KIND_BAD", "MS_KIND_FCCH", "MS_KIND_SCH", "MS_KIND_NB", "MS_SLOT_ACTIVE",
+           "MS_IND_TRASH", "MS_IND_SILENT", "ms_slot_kind"]

@@ -587,6 +587,32 @@ int trxhip_sch_sync_batch_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t buf_s
 	return sch_sync_common(ctx, d_iq, 1, buf_stride, d_results, d_bits, n_bufs, buf_len, mode, scale, stream);
 }
 
+static int ms_rx_common(trxhip_ctx *ctx, const void *d_iq, int i16, size_t slot_stride, const trxhip_ms_slot *d_slots,
+			trxhip_ms_burst_ind *d_ind, int8_t *d_bits, size_t n_slots, float rx_full_scale, void *stream)
+{
+	if (!ctx || !d_iq || !d_slots || !d_ind || n_slots == 0 || n_slots > 0x7fffffffull || slot_stride < 625)
+		return TRXHIP_EINVAL;
+	if (!std::isfinite(rx_full_scale) || rx_full_scale <= 0.0f)
+		return TRXHIP_EINVAL;
+	if (with_device(ctx))
+		return TRXHIP_EIO;
+	/* 1.f / float(rxFullScale) (ms_upper.cpp:203) */
+	return trx_launch_ms_rx(d_iq, i16, slot_stride, d_slots, d_ind, d_bits, n_slots, 1.0f / rx_full_scale, rx_full_scale,
+				static_cast<hipStream_t>(stream));
+}
+
+int trxhip_ms_rx_batch_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t slot_stride, const trxhip_ms_slot *d_slots,
+			   trxhip_ms_burst_ind *d_ind, int8_t *d_bits, size_t n_slots, float rx_full_scale, void *stream)
+{
+	return ms_rx_common(ctx, d_iq, 1, slot_stride, d_slots, d_ind, d_bits, n_slots, rx_full_scale, stream);
+}
+
+int trxhip_ms_rx_batch_cf32(trxhip_ctx *ctx, const float *d_iq, size_t slot_stride, const trxhip_ms_slot *d_slots,
+			    trxhip_ms_burst_ind *d_ind, int8_t *d_bits, size_t n_slots, float rx_full_scale, void *stream)
+{
+	return ms_rx_common(ctx, d_iq, 0, slot_stride, d_slots, d_ind, d_bits, n_slots, rx_full_scale, stream);
+}
+
 int trxhip_delay_vector_batch_cf32(trxhip_ctx *ctx, const float *d_in, float *d_out, const float *d_delays, size_t n_vec,
 				   int len, void *stream)
 {

@@ -62,6 +62,10 @@ int trx_launch_va_demod(const float *d_iq, const trxhip_burst_params *d_params, 
 int trx_launch_sch_sync(const void *d_iq, int i16, size_t buf_stride, trxhip_sch_sync_result *d_results, int8_t *d_bits,
 			size_t n_bufs, int len, int acq, float scale, float *d_power, int32_t *d_best, hipStream_t stream);
 
+/* trx_ms_rx.hip: the MS-side downlink burst receiver, n_slots slots of 625 samples slot_stride samples apart; scale: 1 / rx_full_scale */
+int trx_launch_ms_rx(const void *d_iq, int i16, size_t slot_stride, const trxhip_ms_slot *d_slots, trxhip_ms_burst_ind *d_ind,
+		     int8_t *d_bits, size_t n_slots, float scale, float rx_full_scale, hipStream_t stream);
+
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,
 			 size_t n_bursts, float rssi_offset, hipStream_t stream);

@@ -32,21 +32,7 @@
 #define VA_SLICE_BYTES(L) ((size_t)(4 * VA_XA(L) + 64 + VA_FL + 32) * sizeof(c32) + 64 * sizeof(float) +                  \
 			   (size_t)VA_BPW * (VA_FSTRIDE * sizeof(float) + 8 * sizeof(c32)) + VA_BPW * 16)
 
-// The training sequences after gmsk_mapper() and conj() (grgsm_vitac.cpp:57-79, :122-145) are walks over
-// {1, j, -1, -j}: out[i] = (+-j) * out[i-1] from the start point 1 / -1 (normal burst, first bit 0 / 1) or -j (access),
-// then conjugated.  Stored as 2-bit quarter-turn codes (0: 1, 1: j, 2: -1, 3: -j) of the elements the channel
-// estimate uses, i = 5 .. 20 of the 26 TSC bits and i = 5 .. 35 of the 41 access bits (TRAIN_BEGINNING = 5), element
-// k at bits 2k, 2k+1 -- computed from the 3GPP TS 45.002 bit strings by the same walk (tests compare with the oracle,
-// which maps the bits at run time).
-#define VA_TSC_CODES0 0x131319b9ull
-#define VA_TSC_CODES1 0x9311b9b9ull
-#define VA_TSC_CODES2 0x1913b3b3ull
-#define VA_TSC_CODES3 0x191933b1ull
-#define VA_TSC_CODES4 0xbb191193ull
-#define VA_TSC_CODES5 0x991b3391ull
-#define VA_TSC_CODES6 0x139bb9b1ull
-#define VA_TSC_CODES7 0x91933b31ull
-#define VA_ACC_CODES 0x464e4ccccc6c644ull
+// the training sequences' quarter-turn codes (VA_TSC_CODES0 .. 7, VA_ACC_CODES): trx_va_common.h
 
 __global__ void __launch_bounds__(VA_WPB * WAVE)
 va_demod_kernel(const c32 *__restrict__ iq, const trxhip_burst_params *__restrict__ params,

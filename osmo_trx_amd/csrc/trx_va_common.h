@@ -22,6 +22,22 @@
 // any stage can touch (start + 4 * 147 + 19 + 4 < 640) whatever L is.
 #define VA_XA(L) (((((L) > 640 ? (L) : 640) + 3) / 4 + 31) / 32 * 32 + 8)
 
+// The training sequences after gmsk_mapper() and conj() (grgsm_vitac.cpp:57-79, :122-145) are walks over
+// {1, j, -1, -j}: out[i] = (+-j) * out[i-1] from the start point 1 / -1 (normal burst, first bit 0 / 1) or -j (access),
+// then conjugated.  Stored as 2-bit quarter-turn codes (0: 1, 1: j, 2: -1, 3: -j) of the elements the channel
+// estimate uses, i = 5 .. 20 of the 26 TSC bits and i = 5 .. 35 of the 41 access bits (TRAIN_BEGINNING = 5), element
+// k at bits 2k, 2k+1 -- computed from the 3GPP TS 45.002 bit strings by the same walk (tests compare with the oracle,
+// which maps the bits at run time).
+#define VA_TSC_CODES0 0x131319b9ull
+#define VA_TSC_CODES1 0x9311b9b9ull
+#define VA_TSC_CODES2 0x1913b3b3ull
+#define VA_TSC_CODES3 0x191933b1ull
+#define VA_TSC_CODES4 0xbb191193ull
+#define VA_TSC_CODES5 0x991b3391ull
+#define VA_TSC_CODES6 0x139bb9b1ull
+#define VA_TSC_CODES7 0x91933b31ull
+#define VA_ACC_CODES 0x464e4ccccc6c644ull
+
 // correlate_sequence() (grgsm_vitac.cpp:147-155) for one lag: sum_ii seq[ii] * x[j0 + 4 ii], seq[ii] a quarter turn.
 // std::complex's a * b with a in {1, j, -1, -j} is b with its parts swapped / negated exactly (the products with 0 only
 // contribute +-0), so every term of the reference's sum is ONE v_pk_add_f32 whose op_sel / neg modifiers carry the

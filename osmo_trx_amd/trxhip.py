@@ -42,6 +42,29 @@ SCH_SYNC_MAX_LEN = 1 << 20                                        # TRXHIP_SCH_S
 SCH_SYNC_DTYPE = np.dtype([("rc", "<i4"), ("start", "<i4"), ("corr_max", "<f4"), ("fn", "<i4"), ("t1", "<u2"), ("bsic", "u1"),
                            ("t2", "u1"), ("t3p", "u1"), ("reserved", "u1", (3,))])
 assert SCH_SYNC_DTYPE.itemsize == 24
+# the MS-side downlink burst receiver: trxhip_ms_slot / trxhip_ms_burst_ind, TRXHIP_MS_*
+MS_KIND_BAD, MS_KIND_FCCH, MS_KIND_SCH, MS_KIND_NB = 0, 1, 2, 3
+MS_SLOT_ACTIVE = 1
+MS_IND_TRASH, MS_IND_SILENT = 1, 2
+MS_SLOT_LEN = 625
+MS_SLOT_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("tsc", "u1"), ("flags", "u1"), ("reserved", "u1")])
+MS_IND_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("kind", "u1"), ("sent", "u1"), ("flags", "u1"), ("rssi", "<i2"), ("toa256", "<i2"),
+                         ("start", "<i4"), ("corr_max", "<f4"), ("pow", "<f4"), ("sch_fn", "<i4"), ("sch_rc", "u1"), ("sch_bsic", "u1"),
+                         ("reserved", "u1", (2,))])
+assert MS_SLOT_DTYPE.itemsize == 8 and MS_IND_DTYPE.itemsize == 32
+
+
+def ms_slot_kind(fn, tn, tsc=0):
+    """TRXHIP_MS_KIND_* of slot (fn, tn): gsm_fcch_check_ts / gsm_sch_check_ts (ms/sch.c:100-139); BAD for tn > 7 and for a traffic
+    slot with tsc > 7.  The receiver computes the same on the device."""
+    if tn > 7:
+        return MS_KIND_BAD
+    fn51 = fn % 51
+    if tn == 0 and fn51 in (0, 10, 20, 30, 40):
+        return MS_KIND_FCCH
+    if tn == 0 and fn51 in (1, 11, 21, 31, 41):
+        return MS_KIND_SCH
+    return MS_KIND_NB if tsc <= 7 else MS_KIND_BAD
 
 
 def few_nb_hint(host_params):
@@ -90,6 +113,8 @@ SYMBOLS = {
     "trxhip_detect_sch_batch_cf32": (_I, [_VP, _VP, _VP, _SZ, _SZ, _I, _I, C.c_float, _VP]),
     "trxhip_sch_sync_batch_cf32": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _SZ, _I, _F, _VP]),
     "trxhip_sch_sync_batch_i16": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _SZ, _I, _F, _VP]),
+    "trxhip_ms_rx_batch_i16": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _SZ, _F, _VP]),
+    "trxhip_ms_rx_batch_cf32": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _SZ, _F, _VP]),
     "trxhip_vector_slicer": (_I, [_VP, _VP, _VP, _SZ, _VP]),
     "trxhip_pack_trxd_batch": (_I, [_VP, _VP, _VP, _I, _VP, _SZ, _F, _VP]),
     "trxhip_pack_trxd_wire_batch": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _SZ, _F, _VP]),
@@ -486,6 +511,52 @@ class TrxHip:
                   stride if buf_len is None else buf_len, mode, scale, self._stream(stream)), name)
         rec = results.cpu().numpy().reshape(-1).view(SCH_SYNC_DTYPE)
         return (rec, bits.cpu().numpy()) if want_bits else rec
+
+    @staticmethod
+    def ms_rx_geometry(iq, slots, rx_full_scale):
+        """What ms_rx() checks before it touches the GPU: (n slots, slot stride in samples, whether iq is int16)."""
+        import math
+        import torch
+        if iq.dtype == torch.int16 and iq.dim() == 3 and iq.shape[2] == 2:
+            i16 = True
+        elif iq.dtype == torch.complex64 and iq.dim() == 2:
+            i16 = False
+        else:
+            raise TrxHipError(f"iq must be int16[n, stride, 2] or complex64[n, stride], not {iq.dtype}{list(iq.shape)}")
+        n, stride = int(iq.shape[0]), int(iq.shape[1])
+        if n == 0 or stride < MS_SLOT_LEN:
+            raise TrxHipError(f"need at least one slot of {MS_SLOT_LEN} samples, got {n} x {stride}")
+        if isinstance(slots, np.ndarray):
+            ok = slots.dtype == MS_SLOT_DTYPE and slots.shape == (n,)
+        else:
+            ok = slots.dtype == torch.uint8 and tuple(slots.shape) == (n, MS_SLOT_DTYPE.itemsize)
+        if not ok:
+            raise TrxHipError(f"slots must be MS_SLOT_DTYPE[{n}] or a device uint8[{n}, {MS_SLOT_DTYPE.itemsize}] tensor")
+        if not (math.isfinite(rx_full_scale) and rx_full_scale > 0):
+            raise TrxHipError(f"rx_full_scale must be finite and positive, not {rx_full_scale}")
+        return n, stride, i16
+
+    def ms_slots_tensor(self, slots_np):
+        """MS_SLOT_DTYPE[n] numpy -> uint8[n, 8] device tensor."""
+        a = np.ascontiguousarray(slots_np, dtype=MS_SLOT_DTYPE).view(np.uint8).reshape(-1, MS_SLOT_DTYPE.itemsize)
+        return self.torch.from_numpy(a.copy()).to(f"cuda:{self.device}")
+
+    def ms_rx(self, iq, slots, rx_full_scale=2047.0, want_bits=True, stream=None):
+        """The MS-side downlink burst receiver (upper_trx::pullRadioVector + the burst indication of driveReceiveFIFO): iq
+        int16[n, stride, 2] or complex64[n, stride] slots of which the first 625 samples are used; slots MS_SLOT_DTYPE[n] (numpy) or a
+        device uint8[n, 8] tensor; rx_full_scale: the reference's rxFullScale.  Returns (MS_IND_DTYPE[n] numpy, sbits int8[n, 148]
+        numpy or None); synchronises."""
+        torch = self.torch
+        n, stride, i16 = self.ms_rx_geometry(iq, slots, rx_full_scale)
+        fn, name = (self.L.trxhip_ms_rx_batch_i16, "trxhip_ms_rx_batch_i16") if i16 else \
+            (self.L.trxhip_ms_rx_batch_cf32, "trxhip_ms_rx_batch_cf32")
+        d_slots = self.ms_slots_tensor(slots) if isinstance(slots, np.ndarray) else slots
+        ind = torch.empty((n, MS_IND_DTYPE.itemsize), dtype=torch.uint8, device=iq.device)
+        bits = torch.empty((n, 148), dtype=torch.int8, device=iq.device) if want_bits else None
+        _check(fn(self.h, self._dev(iq), stride, self._dev(d_slots, torch.uint8), self._dev(ind), self._dev(bits) if want_bits else _VP(0),
+                  n, rx_full_scale, self._stream(stream)), name)
+        rec = ind.cpu().numpy().reshape(-1).view(MS_IND_DTYPE)
+        return rec, (bits.cpu().numpy() if want_bits else None)
 
     @staticmethod
     def results_to_numpy(results):
