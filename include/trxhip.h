@@ -902,6 +902,103 @@ int  trxhip_rx_sched_counters(trxhip_rx_sched *s, int chan, trxhip_rx_sched_ctrs
 /* the channel's noise ring as the reference holds it: ring[20], the insert position (0..20) and mNoiseLev */
 int  trxhip_rx_sched_noise_state(trxhip_rx_sched *s, int chan, float *ring20, uint32_t *itr, float *lev);
 
+/* ---- The MS-side downlink slot scheduler: the radio's sample stream in, burst indications out -----------------------------
+ * What the reference does between the radio's receive buffers and upper_trx::pullRadioVector(): ms_trx::search_for_sch() /
+ * handle_sch(true) (first acquisition), ms_trx::grab_bursts() / handle_sch_or_nb() (ms/ms_rx_lower.cpp:130-153, :157-205,
+ * :310-422) and time_keeper (ms/ms.h:160-221), for one downlink stream at 4 samples per symbol.  The object carries the
+ * partial slot between chunks, keeps the GSM clock with its sample timestamp, and moves the cut by what the SCH bursts
+ * measure (temp_ts_corr_offset).  Per cut slot the kind, ACTIVE, the indication record and the 148 sbits are those of
+ * trxhip_ms_rx_batch_*() on the same 625 samples with {fn, tn, tsc, ACTIVE = bit tn of active_tns}, byte for byte.
+ *
+ * acquire: handle_sch(true) on a buffer the caller has filled (the reference: 60000 samples; 532 .. TRXHIP_SCH_SYNC_MAX_LEN):
+ *   trxhip_sch_sync_batch_*(TRXHIP_SCH_SYNC_ACQ) with scale 1 / rx_full_scale, WAITS for the 24-byte result, copies it to h_res
+ *   (may be NULL) and returns 1 (burst found) or 0 (not found, state untouched).  On 1: the clock becomes (fn, 0) with ts 0
+ *   (timekeeper.set(fn, 0), :91), mTSC = bsic & 7 (:90), first_sch_ts_start = first_ts + start - 16 - 1 (:198); the carried
+ *   partial slot and any pending correction are dropped, and the next pull is grab_bursts()' first call.  The level gate and
+ *   the gain steps around it (:333-347) stay with the caller.  A plan-only object READS *h_res as the receiver's answer.
+ * pull: one call of grab_bursts() with the chunk as `rcd` (n_samples samples from timestamp first_ts), literally:
+ *   first call after an acquire (:362-383): next_burst_start = first_ts - first_sch_ts_start in int64; fullts, fracts by C's
+ *     division; to_skip = 625 - fracts (a whole slot when fracts == 0); the clock fullts incTN() later, one more when fracts,
+ *     one back (dec_by_one), and ts = first_ts - 625 + to_skip
+ *   carried partial slot (:385-396): a chunk shorter than the missing part only extends it and cuts nothing (the correction
+ *     stays pending); else the completed slot is cut first, with ts = first_ts - carried, and to_skip = the missing part
+ *   correction (:399-406): to_skip -= pending; negative: to_skip = 0 and the pending value is kept whole; else pending = 0
+ *   full = (n_samples - to_skip) / 625 slots at to_skip + i * 625, the rest is the new partial slot (:408-421)
+ *   each cut slot FIRST does incTN(1) with ts = its first sample's timestamp (inc_and_update_safe) and THEN takes the clock --
+ *     the clock an object reports is that of the last slot cut; the asserts of inc_and_update_safe (0.5 < diff / 625 < 1.5)
+ *     count in clock_jumps
+ *   with tracking on, every SCH slot with sch_rc == 1 && abs(start) > 1 adds -start to the pending correction (:199-203);
+ *     several SCH slots of one pull add up, as in one reference buffer (an integer atomic: no ordering effect)
+ *   d_ind[k], d_bits[k * 148] (d_bits may be NULL): slot k of the pull, k < *n_slots <= out_slots
+ * Waits: a pull with tracking on that follows a pull which cut an SCH slot waits for that pull's correction (4 bytes, pinned,
+ *   one event) before it plans; when the completed partial slot is itself an SCH slot, the pull demodulates that slot alone,
+ *   waits for it, and plans the rest (the reference handles it before :399).  Nothing else waits, nothing calls
+ *   hipDeviceSynchronize, and with tracking off no pull waits.  trxhip_ms_sched_state() waits for a correction in flight.
+ * trxhip_ms_sched_slots(): slots the next pull of n_samples cuts -- exact when it is not the first pull after an acquire and
+ *   tracking is off or no correction can be pending; else the upper bound (carried + n_samples) / 625 + 1.
+ * Defined where the reference is not: where the literal arithmetic leaves the chunk (to_skip > n_samples; the reference calls
+ *   read_n with a negative count) the pull is TRXHIP_EINVAL -- a longer chunk is accepted.  (Where such a pull, or one refused
+ *   for out_slots, had to demodulate a straddling SCH slot first, d_ind[0] and the first row of d_bits may have been written;
+ *   the object's state is untouched all the same.)
+ * TRXHIP_EINVAL, state untouched: n_samples == 0, a pull before set_clock or a successful acquire, out_slots too small, a
+ *   NULL or misaligned buffer (int16: 4 bytes, complex64: 8, d_ind: 4), int16 and complex64 pulls mixed over a carried partial
+ *   slot, tsc > 7, fn >= 2715648, tn > 7, rx_full_scale not finite or not positive; a plan-only object takes no buffers.
+ * ctx == NULL: a plan-only object -- cutter, clock, plan and state as on the GPU; the SCH results come from the queue of
+ *   trxhip_ms_sched_feed_starts() (it replaces the queue; one entry per SCH slot cut with tracking on,
+ *   TRXHIP_MS_SCHED_NO_SCH or an empty queue: not decoded; a refused pull consumes none).  Issue every call of one object on one stream; one object is not thread-safe. */
+#define TRXHIP_MS_SCHED_NO_SCH INT32_MIN
+typedef struct trxhip_ms_sched_cfg {
+	float    rx_full_scale;  /* rxFullScale */
+	uint8_t  tsc;            /* mTSC, 0..7 */
+	uint8_t  active_tns;     /* bit tn: trxcon answers TRXCON_PHYIF_RTR_F_ACTIVE on that TN */
+	uint8_t  tracking;       /* 0: SCH starts are reported but never move the cut */
+	uint8_t  reserved;
+} trxhip_ms_sched_cfg;
+typedef struct trxhip_ms_plan {  /* 24 bytes */
+	uint32_t fn;
+	uint8_t  tn;
+	uint8_t  kind;           /* TRXHIP_MS_KIND_* */
+	uint8_t  flags;          /* TRXHIP_MS_SLOT_* */
+	uint8_t  reserved;
+	int64_t  ts;             /* timestamp of the slot's first sample */
+	int32_t  src_off;        /* ts - first_ts: where the slot begins in the chunk (< 0: in the carried partial slot) */
+	uint32_t reserved2;
+} trxhip_ms_plan;
+typedef struct trxhip_ms_sched_status {  /* 72 bytes */
+	int64_t  to_skip;            /* applied by the last pull that reached the correction (:399-406) */
+	int64_t  pending;            /* temp_ts_corr_offset */
+	int64_t  first_sch_ts_start;
+	uint32_t carried;            /* partial_rdofs */
+	uint8_t  carried_cf32, first_call, tracking, tsc;
+	uint8_t  active_tns, clock_set, reserved[6];
+	uint64_t clock_jumps;        /* inc_and_update_safe()'s asserts that would have fired */
+	uint64_t pulls, slots, sch_slots;
+} trxhip_ms_sched_status;
+typedef struct trxhip_ms_sched trxhip_ms_sched;
+int  trxhip_ms_sched_create(trxhip_ctx *ctx, const trxhip_ms_sched_cfg *cfg, trxhip_ms_sched **out);
+void trxhip_ms_sched_destroy(trxhip_ms_sched *s);
+/* timekeeper.set(): the clock of the last slot cut and its timestamp; drops the carried partial slot and any pending
+ * correction; the next pull is not a first call */
+int  trxhip_ms_sched_set_clock(trxhip_ms_sched *s, uint32_t fn, int tn, int64_t ts);
+int  trxhip_ms_sched_clock(const trxhip_ms_sched *s, uint32_t *fn, int *tn, int64_t *ts);
+int  trxhip_ms_sched_set_tsc(trxhip_ms_sched *s, int tsc);
+int  trxhip_ms_sched_set_active(trxhip_ms_sched *s, uint8_t tn_mask);
+int  trxhip_ms_sched_set_tracking(trxhip_ms_sched *s, int on);
+int  trxhip_ms_sched_feed_starts(trxhip_ms_sched *s, const int32_t *starts, size_t n);   /* plan-only objects */
+int  trxhip_ms_sched_acquire_s16(trxhip_ms_sched *s, const int16_t *d_buf, size_t n_samples, int64_t first_ts,
+				 trxhip_sch_sync_result *h_res, void *stream);
+int  trxhip_ms_sched_acquire_cf32(trxhip_ms_sched *s, const float *d_buf, size_t n_samples, int64_t first_ts,
+				  trxhip_sch_sync_result *h_res, void *stream);
+int64_t trxhip_ms_sched_slots(const trxhip_ms_sched *s, size_t n_samples);
+int  trxhip_ms_sched_pull_s16(trxhip_ms_sched *s, const int16_t *d_in, size_t n_samples, int64_t first_ts,
+			      trxhip_ms_burst_ind *d_ind, int8_t *d_bits, size_t out_slots, size_t *n_slots, size_t *n_carried,
+			      void *stream);
+int  trxhip_ms_sched_pull_cf32(trxhip_ms_sched *s, const float *d_in, size_t n_samples, int64_t first_ts,
+			       trxhip_ms_burst_ind *d_ind, int8_t *d_bits, size_t out_slots, size_t *n_slots, size_t *n_carried,
+			       void *stream);
+int  trxhip_ms_sched_plan(const trxhip_ms_sched *s, trxhip_ms_plan *h_out, size_t n);   /* the last pull's first n slots */
+int  trxhip_ms_sched_state(trxhip_ms_sched *s, trxhip_ms_sched_status *out);
+
 #ifdef __cplusplus
 }
 #endif

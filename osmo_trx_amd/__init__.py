@@ -11,9 +11,11 @@ compute entry point raises.
 from .trxhip import (TrxHip, TrxHipError, PARAMS_DTYPE, RESULT_DTYPE, lib_path, load_library,  # noqa: F401
                      OFF, TSC, EXT_RACH, RACH, SCH, EDGE, IDLE,
                      MS_SLOT_DTYPE, MS_IND_DTYPE, MS_KIND_BAD, MS_KIND_FCCH, MS_KIND_SCH, MS_KIND_NB, MS_SLOT_ACTIVE,
-                     MS_IND_TRASH, MS_IND_SILENT, ms_slot_kind)
+                     MS_IND_TRASH, MS_IND_SILENT, ms_slot_kind, MsRxScheduler, MS_PLAN_DTYPE, MS_SCHED_STATE_DTYPE,
+                     MS_SCHED_NO_SCH)
 
 __all__ = ["TrxHip", "TrxHipError", "PARAMS_DTYPE", "RESULT_DTYPE", "lib_path", "load_library",
            "OFF", "TSC", "EXT_RACH", "RACH", "SCH", "EDGE", "IDLE",
            "MS_SLOT_DTYPE", "MS_IND_DTYPE", "MS_KIND_BAD", "MS_KIND_FCCH", "MS_KIND_SCH", "MS_KIND_NB", "MS_SLOT_ACTIVE",
-           "MS_IND_TRASH", "MS_IND_SILENT", "ms_slot_kind"]
+           "MS_IND_TRASH", "MS_IND_SILENT", "ms_slot_kind", "MsRxScheduler", "MS_PLAN_DTYPE", "MS_SCHED_STATE_DTYPE",
+           "MS_SCHED_NO_SCH"]

@@ -65,6 +65,10 @@ int trx_launch_sch_sync(const void *d_iq, int i16, size_t buf_stride, trxhip_sch
 /* trx_ms_rx.hip: the MS-side downlink burst receiver, n_slots slots of 625 samples slot_stride samples apart; scale: 1 / rx_full_scale */
 int trx_launch_ms_rx(const void *d_iq, int i16, size_t slot_stride, const trxhip_ms_slot *d_slots, trxhip_ms_burst_ind *d_ind,
 		     int8_t *d_bits, size_t n_slots, float scale, float rx_full_scale, hipStream_t stream);
+/* its stream form (trx_ms_sched.h): the slots of one pull of the MS-side slot scheduler, read where they lie in d_chunk */
+struct trx_mss_stream;
+int trx_launch_ms_rx_stream(const void *d_chunk, int i16, const struct trx_mss_stream *sa, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+			    size_t n_slots, float scale, float rx_full_scale, hipStream_t stream);
 
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,

@@ -12,8 +12,12 @@
 // demodulate is an idle row, like the batch tail), and the channel decoder only in waves that hold an SCH slot.
 // Both of the reference's serial float sums keep their order: the window recurrence (sch_scan_round) and energyDetect's 80 terms
 // (the same DPP shift-add chain: 64 steps and 16).
+// THE STREAM FORM (trx_ms_sched.hip) is a second instantiation of the same body: a slot's record is computed from the pull's base
+// clock and the slot index, the slot is read where it lies in the caller's chunk (or from the row that holds the straddling
+// slot), and a decoded SCH slot with abs(start) > 1 adds -start to the pull's correction word.
 #include "trx_sch_common.h"
 #include "trx_launch.h"
+#include "trx_ms_sched.h"
 
 #define MS_SLOT 625                      // ONE_TS_BURST_LEN (ms.h:50)
 // get_norm_chan_imp_resp: search_center = TRAIN_POS = 3 + 57 + 1 + 5; lags (66 - 5) * 4 + 1 .. (66 + 5 + 5) * 4 - 1 of the slot, which
@@ -62,10 +66,38 @@ __device__ __forceinline__ float ms_energy_detect(const c32 *x0, int lane)
 	return lane_val(acc, MS_EN_TERMS - WAVE - 1) / (float)MS_EN_TERMS;
 }
 
-template <bool I16>
+// The two words of slot b's record {fn | tn, tsc, flags}: read from the slot records, or (STREAM) made from the pull's base clock
+template <bool STREAM>
+__device__ __forceinline__ void ms_slot_words(const trxhip_ms_slot *slots, const trx_mss_stream &sa, unsigned b, uint32_t &w0, uint32_t &w1)
+{
+	if (STREAM) {
+		int tn;
+		trx_mss_clock_add(sa.fn0, sa.tn0, b, &w0, &tn);
+		w1 = (uint32_t)tn | (uint32_t)sa.tsc << 8 | (((sa.active >> tn) & 1u) ? (uint32_t)TRXHIP_MS_SLOT_ACTIVE << 16 : 0u);
+	} else {
+		w0 = reinterpret_cast<const uint32_t *>(slots)[2 * (size_t)b];
+		w1 = reinterpret_cast<const uint32_t *>(slots)[2 * (size_t)b + 1];
+	}
+}
+
+// Where slot b's 625 samples lie: row b of the batch, or (STREAM) in the chunk / in the straddling slot's row
+template <bool I16, bool STREAM>
+__device__ __forceinline__ const char *ms_slot_src(const void *iq, size_t slot_stride, const trx_mss_stream &sa, unsigned b)
+{
+	if (STREAM) {
+		if (sa.edge_row && b == 0)
+			return reinterpret_cast<const char *>(sa.edge_row);
+		const int64_t at = sa.first + (int64_t)(b - (sa.edge_row ? 1u : 0u)) * MS_SLOT;
+		return reinterpret_cast<const char *>(iq) + at * (I16 ? 4 : 8);
+	}
+	return reinterpret_cast<const char *>(iq) + (size_t)b * slot_stride * (I16 ? 4 : 8);
+}
+
+template <bool I16, bool STREAM>
 __global__ void __launch_bounds__(SS_WPB * WAVE)
 ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_slot *__restrict__ slots,
-	     trxhip_ms_burst_ind *__restrict__ ind, int8_t *__restrict__ bits, unsigned n_slots, float scale, float rx_full_scale)
+	     trxhip_ms_burst_ind *__restrict__ ind, int8_t *__restrict__ bits, unsigned n_slots, float scale, float rx_full_scale,
+	     const trx_mss_stream sa)
 {
 	__shared__ __attribute__((aligned(16))) char smem[SS_WPB * MS_SLICE_BYTES];
 	const int lane = threadIdx.x & (WAVE - 1);
@@ -98,8 +130,10 @@ ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_sl
 			continue;
 		}
 		// the slot's kind (ms_upper.cpp:180-181 over sch.c:100-139) and what the reference does with it
-		const unsigned w1 = (unsigned)uni((int)reinterpret_cast<const uint32_t *>(slots)[2 * (size_t)b + 1]);
-		const unsigned fn51 = (unsigned)uni((int)reinterpret_cast<const uint32_t *>(slots)[2 * (size_t)b]) % 51u;
+		uint32_t sw0, sw1;
+		ms_slot_words<STREAM>(slots, sa, b, sw0, sw1);
+		const unsigned w1 = (unsigned)uni((int)sw1);
+		const unsigned fn51 = (unsigned)uni((int)sw0) % 51u;
 		const unsigned tn = w1 & 0xffu, tsc = (w1 >> 8) & 0xffu;
 		const bool active = ((w1 >> 16) & TRXHIP_MS_SLOT_ACTIVE) != 0;
 		int kind = TRXHIP_MS_KIND_NB;
@@ -119,7 +153,7 @@ ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_sl
 			continue;
 		}
 		// the slot 40 samples into the zeroed array (ms_upper.cpp:164-171, ms_rx_lower.cpp:162-164), scaled on the way in
-		const char *src = reinterpret_cast<const char *>(iq) + (size_t)b * slot_stride * (I16 ? 4 : 8);
+		const char *src = ms_slot_src<I16, STREAM>(iq, slot_stride, sa, b);
 		for (int j = lane; j < SS_WIN; j += WAVE) {
 			const int g = j - 40;
 			xs[(j & 3) * SS_XA + (j >> 2)] = (g >= 0 && g < MS_SLOT) ? ss_load<I16>(src, (size_t)g, scale) : make_float2(0.0f, 0.0f);
@@ -224,11 +258,12 @@ ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_sl
 
 	// =================== the indication record (ms_upper.cpp:194-200, :272-274, :288-297) ===================
 	if (live && l4 == 0) {
-		const uint32_t w1 = reinterpret_cast<const uint32_t *>(slots)[2 * (size_t)bme + 1];
+		uint32_t w0, w1;
+		ms_slot_words<STREAM>(slots, sa, bme, w0, w1);
 		const float pow = __int_as_float(nf.y);
 		const int fl = (nf.x >> 16) & 0xff;
 		trxhip_ms_burst_ind r;
-		r.fn = reinterpret_cast<const uint32_t *>(slots)[2 * (size_t)bme];
+		r.fn = w0;
 		r.tn = (uint8_t)(w1 & 0xffu);
 		r.kind = (uint8_t)kind;
 		r.sent = (uint8_t)((nf.x >> 8) & 1);
@@ -249,6 +284,9 @@ ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_sl
 		r.sch_bsic = ok ? (uint8_t)bsic : 0;
 		r.reserved[0] = r.reserved[1] = 0;
 		ind[bme] = r;
+		// continuous sch tracking, only update if off too much (ms_rx_lower.cpp:199-203): temp_ts_corr_offset += -start
+		if (STREAM && sa.corr && ok && (mt.z > 1 || mt.z < -1))
+			atomicAdd(sa.corr, -mt.z);
 	}
 }
 
@@ -259,11 +297,29 @@ extern "C" int trx_launch_ms_rx(const void *d_iq, int i16, size_t slot_stride, c
 		return 0;
 	const size_t per_block = SS_WPB * VA_BPW;
 	const size_t grid = (n_slots + per_block - 1) / per_block;
+	const trx_mss_stream none = {};
 	if (i16)
-		hipLaunchKernelGGL(ms_rx_kernel<true>, dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_iq, slot_stride, d_slots, d_ind,
-				   d_bits, (unsigned)n_slots, scale, rx_full_scale);
+		hipLaunchKernelGGL((ms_rx_kernel<true, false>), dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_iq, slot_stride, d_slots,
+				   d_ind, d_bits, (unsigned)n_slots, scale, rx_full_scale, none);
 	else
-		hipLaunchKernelGGL(ms_rx_kernel<false>, dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_iq, slot_stride, d_slots, d_ind,
-				   d_bits, (unsigned)n_slots, scale, rx_full_scale);
+		hipLaunchKernelGGL((ms_rx_kernel<false, false>), dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_iq, slot_stride, d_slots,
+				   d_ind, d_bits, (unsigned)n_slots, scale, rx_full_scale, none);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+// the stream form: n_slots slots of one pull, described by sa (trx_ms_sched.h); d_chunk: the caller's chunk
+extern "C" int trx_launch_ms_rx_stream(const void *d_chunk, int i16, const trx_mss_stream *sa, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+				       size_t n_slots, float scale, float rx_full_scale, hipStream_t stream)
+{
+	if (n_slots == 0)
+		return 0;
+	const size_t per_block = SS_WPB * VA_BPW;
+	const size_t grid = (n_slots + per_block - 1) / per_block;
+	if (i16)
+		hipLaunchKernelGGL((ms_rx_kernel<true, true>), dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_chunk, (size_t)MS_SLOT,
+				   nullptr, d_ind, d_bits, (unsigned)n_slots, scale, rx_full_scale, *sa);
+	else
+		hipLaunchKernelGGL((ms_rx_kernel<false, true>), dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_chunk, (size_t)MS_SLOT,
+				   nullptr, d_ind, d_bits, (unsigned)n_slots, scale, rx_full_scale, *sa);
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }

@@ -188,6 +188,21 @@ SYMBOLS = {
     "trxhip_rx_sched_plan": (_I, [_VP, _I, _VP, _SZ]),
     "trxhip_rx_sched_counters": (_I, [_VP, _I, _VP]),
     "trxhip_rx_sched_noise_state": (_I, [_VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(_F)]),
+    "trxhip_ms_sched_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
+    "trxhip_ms_sched_destroy": (None, [_VP]),
+    "trxhip_ms_sched_set_clock": (_I, [_VP, C.c_uint32, _I, C.c_int64]),
+    "trxhip_ms_sched_clock": (_I, [_VP, C.POINTER(C.c_uint32), C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "trxhip_ms_sched_set_tsc": (_I, [_VP, _I]),
+    "trxhip_ms_sched_set_active": (_I, [_VP, C.c_uint8]),
+    "trxhip_ms_sched_set_tracking": (_I, [_VP, _I]),
+    "trxhip_ms_sched_feed_starts": (_I, [_VP, _VP, _SZ]),
+    "trxhip_ms_sched_acquire_s16": (_I, [_VP, _VP, _SZ, C.c_int64, _VP, _VP]),
+    "trxhip_ms_sched_acquire_cf32": (_I, [_VP, _VP, _SZ, C.c_int64, _VP, _VP]),
+    "trxhip_ms_sched_slots": (C.c_int64, [_VP, _SZ]),
+    "trxhip_ms_sched_pull_s16": (_I, [_VP, _VP, _SZ, C.c_int64, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
+    "trxhip_ms_sched_pull_cf32": (_I, [_VP, _VP, _SZ, C.c_int64, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
+    "trxhip_ms_sched_plan": (_I, [_VP, _VP, _SZ]),
+    "trxhip_ms_sched_state": (_I, [_VP, _VP]),
 }
 
 
@@ -1080,6 +1095,137 @@ class RxScheduler:
     def close(self):
         if getattr(self, "h", None):
             self.L.trxhip_rx_sched_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MS_SCHED_NO_SCH = -(1 << 31)                         # TRXHIP_MS_SCHED_NO_SCH
+MS_PLAN_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("kind", "u1"), ("flags", "u1"), ("reserved", "u1"), ("ts", "<i8"),
+                          ("src_off", "<i4"), ("reserved2", "<u4")])
+MS_SCHED_STATE_DTYPE = np.dtype([("to_skip", "<i8"), ("pending", "<i8"), ("first_sch_ts_start", "<i8"), ("carried", "<u4"),
+                                 ("carried_cf32", "u1"), ("first_call", "u1"), ("tracking", "u1"), ("tsc", "u1"), ("active_tns", "u1"),
+                                 ("clock_set", "u1"), ("reserved", "u1", (6,)), ("clock_jumps", "<u8"), ("pulls", "<u8"),
+                                 ("slots", "<u8"), ("sch_slots", "<u8")])
+assert MS_PLAN_DTYPE.itemsize == 24 and MS_SCHED_STATE_DTYPE.itemsize == 72
+
+
+class _MsSchedCfg(C.Structure):
+    _fields_ = [("rx_full_scale", C.c_float), ("tsc", C.c_uint8), ("active_tns", C.c_uint8), ("tracking", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+class MsRxScheduler:
+    """MS-side downlink slot scheduler (trxhip_ms_sched_*): the radio's sample stream in, burst indications and sbits out --
+    ms_trx::grab_bursts() with its time_keeper and the SCH feedback on the cut.  trx=None: a plan-only object (no GPU):
+    pull(n_samples=..., first_ts=...) only cuts and plans, the SCH starts come from feed_starts()."""
+
+    def __init__(self, trx=None, rx_full_scale=2047.0, tsc=0, active_tns=0xFF, tracking=True):
+        self.trx = trx
+        self.L = trx.L if trx is not None else load_library()
+        cfg = _MsSchedCfg(rx_full_scale, tsc, active_tns, int(bool(tracking)), 0)
+        h = _VP()
+        _check(self.L.trxhip_ms_sched_create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_ms_sched_create")
+        self.h = h
+        self._last = 0
+        self.carried = 0
+
+    def set_clock(self, fn, tn, ts=0):
+        _check(self.L.trxhip_ms_sched_set_clock(self.h, fn, tn, ts), "trxhip_ms_sched_set_clock")
+        self.carried = 0
+
+    def clock(self):
+        """(fn, tn, ts) of the last slot cut"""
+        fn, tn, ts = C.c_uint32(), _I(), C.c_int64()
+        _check(self.L.trxhip_ms_sched_clock(self.h, C.byref(fn), C.byref(tn), C.byref(ts)), "trxhip_ms_sched_clock")
+        return fn.value, tn.value, ts.value
+
+    def set_tsc(self, tsc):
+        _check(self.L.trxhip_ms_sched_set_tsc(self.h, tsc), "trxhip_ms_sched_set_tsc")
+
+    def set_active(self, tn_mask):
+        _check(self.L.trxhip_ms_sched_set_active(self.h, tn_mask), "trxhip_ms_sched_set_active")
+
+    def set_tracking(self, on):
+        _check(self.L.trxhip_ms_sched_set_tracking(self.h, int(bool(on))), "trxhip_ms_sched_set_tracking")
+
+    def feed_starts(self, starts):
+        """plan-only: the `start` of the next SCH slots cut with tracking on (MS_SCHED_NO_SCH: not decoded)"""
+        a = np.ascontiguousarray(starts, dtype=np.int32)
+        _check(self.L.trxhip_ms_sched_feed_starts(self.h, a.ctypes.data_as(_VP), len(a)), "trxhip_ms_sched_feed_starts")
+
+    def acquire(self, x=None, first_ts=0, result=None, stream=None):
+        """handle_sch(true) on the buffer x (int16[n, 2] or complex64[n] device tensor).  Returns (found, SCH_SYNC_DTYPE record);
+        waits for the result.  Plan-only: result is the record the receiver would have given, n the buffer's length."""
+        rec = np.zeros(1, dtype=SCH_SYNC_DTYPE)
+        if self.trx is None:
+            rec[0] = result
+            rc = self.L.trxhip_ms_sched_acquire_s16(self.h, None, 60000, first_ts, rec.ctypes.data_as(_VP), None)
+        else:
+            s16 = x.dtype == self.trx.torch.int16
+            fn = self.L.trxhip_ms_sched_acquire_s16 if s16 else self.L.trxhip_ms_sched_acquire_cf32
+            rc = fn(self.h, self.trx._dev(x), x.shape[0], first_ts, rec.ctypes.data_as(_VP), self.trx._stream(stream))
+        if rc < 0:
+            _check(rc, "trxhip_ms_sched_acquire")
+        if rc == 1:
+            self.carried = 0
+        return bool(rc), rec[0]
+
+    def slots(self, n_samples):
+        n = self.L.trxhip_ms_sched_slots(self.h, n_samples)
+        if n < 0:
+            _check(int(n), "trxhip_ms_sched_slots")
+        return int(n)
+
+    def pull(self, x=None, first_ts=0, n_samples=None, want_bits=True, stream=None):
+        """x: int16[n, 2] or complex64[n] device tensor, the chunk whose first sample has timestamp first_ts; plan-only:
+        n_samples.  Returns (n_slots, n_carried) for a plan-only object, otherwise (ind uint8[n_slots, 32] (MS_IND_DTYPE),
+        sbits int8[n_slots, 148] or None) device tensors."""
+        ns, nc = _SZ(), _SZ()
+        if self.trx is None:
+            _check(self.L.trxhip_ms_sched_pull_s16(self.h, None, n_samples, first_ts, None, None, 0, C.byref(ns), C.byref(nc), None),
+                   "trxhip_ms_sched_pull_s16")
+            self._last, self.carried = ns.value, nc.value
+            return ns.value, nc.value
+        torch = self.trx.torch
+        s16 = x.dtype == torch.int16
+        assert x.dtype == torch.complex64 and x.dim() == 1 or (s16 and x.dim() == 2 and x.shape[1] == 2), (x.shape, x.dtype)
+        n_in = x.shape[0]
+        cap = self.slots(n_in)
+        dev = f"cuda:{self.trx.device}"
+        ind = torch.empty((max(cap, 1), MS_IND_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        bits = torch.empty((max(cap, 1), 148), dtype=torch.int8, device=dev) if want_bits else None
+        fn = self.L.trxhip_ms_sched_pull_s16 if s16 else self.L.trxhip_ms_sched_pull_cf32
+        _check(fn(self.h, self.trx._dev(x), n_in, first_ts, self.trx._dev(ind), self.trx._dev(bits) if want_bits else None, cap,
+                  C.byref(ns), C.byref(nc), self.trx._stream(stream)), "trxhip_ms_sched_pull")
+        self._last, self.carried = ns.value, nc.value
+        return ind[:ns.value], (bits[:ns.value] if want_bits else None)
+
+    def plan(self, n=None):
+        """MS_PLAN_DTYPE[n] of the last pull (default: all its slots)"""
+        n = self._last if n is None else n
+        a = np.zeros(n, dtype=MS_PLAN_DTYPE)
+        _check(self.L.trxhip_ms_sched_plan(self.h, a.ctypes.data_as(_VP), n), "trxhip_ms_sched_plan")
+        return a
+
+    def state(self):
+        """MS_SCHED_STATE_DTYPE record; waits for a correction in flight"""
+        a = np.zeros(1, dtype=MS_SCHED_STATE_DTYPE)
+        _check(self.L.trxhip_ms_sched_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_sched_state")
+        return a[0]
+
+    @staticmethod
+    def ind_to_numpy(ind):
+        """uint8[n, 32] device tensor -> MS_IND_DTYPE[n]"""
+        return ind.cpu().numpy().reshape(-1).view(MS_IND_DTYPE)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.trxhip_ms_sched_destroy(self.h)
             self.h = None
 
     def __del__(self):
