@@ -999,6 +999,96 @@ int  trxhip_ms_sched_pull_cf32(trxhip_ms_sched *s, const float *d_in, size_t n_s
 int  trxhip_ms_sched_plan(const trxhip_ms_sched *s, trxhip_ms_plan *h_out, size_t n);   /* the last pull's first n slots */
 int  trxhip_ms_sched_state(trxhip_ms_sched *s, trxhip_ms_sched_status *out);
 
+/* ---- The MS-side uplink burst scheduler: burst requests in, the radio's transmit sample stream out --------------------------
+ * What the reference does between trxcon's burst request and the radio: upper_trx::driveTx() (ms/ms_upper.cpp:306-355),
+ * ms_trx::submit_burst() (ms/ms.cpp:114-160), set_ta() (ms/ms.h:299-303) and submit_burst_ts() (ms/uhd_specific.h:260-269,
+ * ms/bladerf_specific.h:461-478), for one MS at 4 samples per symbol, int16 out.
+ * A request is what trxcon_phyif_handle_burst_req() queues (ms/ms_trxcon_if.cpp:36-46): {fn, tn, pwr, 148 bits}; a request
+ * with burst_len == 0 never reaches the queue there, and is not submitted here.
+ * submit, per request, with the timekeeper's pair (now_fn, now_tn, now_ts) the caller passes (trxhip_ms_sched_clock()):
+ *   target = (fn, tn).incTN(3); diff_fn = FNDelta(target.fn, now_fn); diff_tn = (target.tn - (int)now_tn) % 8 (C remainder);
+ *   tosend = Time(diff_fn, 0).incTN(diff_tn) when diff_tn > 0, else .decTN(-diff_tn) (FN borrow, below 0 to the hyperframe)
+ *   "TX too late": diff_fn < 0 || (diff_fn == 0 && (target.tn - now.TN() < 3)) with TN() unsigned -> TRXHIP_MS_TX_LATE
+ *   send_ts = now_ts + tosend.FN * 8 * 625 + tosend.TN * 625 - timing_advance: ONE_TS_BURST_LEN is an unsigned int (ms/ms.h:50),
+ *     so the two products are formed modulo 2^32 before they widen to the int64 sum, and so they are here (they differ from
+ *     the int64 products from tosend.FN = 858994 on, 66 minutes ahead); radio_ts = send_ts + rxtx_delay
+ *   scale = (float)((double)tx_full_scale * pow(10, -RSSI / 10)), RSSI = (int)pwr, -RSSI / 10 an INTEGER division (:336):
+ *     pwr 0..9 is full scale, 10..19 a tenth, ...
+ *   The unsigned TN: with diff_fn == 0 and target.tn < now_tn the difference wraps, the burst is not "too late", and tosend is
+ *     Time(0, 0).decTN(k) = (2715647, 8 - k).  The plan reports that literal send_ts with TRXHIP_MS_TX_WRAPPED and stages nothing.
+ * The burst's int16 samples are row b of trxhip_modulate_batch({148, 8 + (tn % 4 == 0), 0, scale, 0}, sps 4, s16_scale 1):
+ *   modulateBurst(bits, guard, 4), scaleVector(complex(scale)), static_cast<int16_t>(x * 1) (ms/ms.h:74-78).
+ * Defined where the reference is not (its radio decides, or its behaviour is undefined):
+ *   tx_full_scale > 21477 is refused: a Laurent modulator sample is at most 1.52568 (the largest per-phase sum of |taps|, c0 plus
+ *     c1) and the largest scale is tx_full_scale, so above 21477 the product can reach 32768, where the reference's cast is
+ *     undefined.  2047 (bladeRF) and 9830 = (unsigned)(32767 * 0.3) (UHD) pass.
+ *   EXPIRED: radio_ts lies before the end of the last rendered window.  OVERLAP: the 625 samples intersect those of a queued
+ *     burst; the later request loses.  FULL: max_pending bursts are queued.  Checked in this order, after LATE and WRAPPED.
+ *   LATE requests report send_ts = radio_ts = 0 (the reference returns before it forms them).
+ * Only QUEUED bursts are staged: bits and scale into a ring of max_pending rows on the device, one asynchronous copy per run of
+ * consecutive ring rows (one per call while the free rows are not fragmented).
+ * render: samples [first_ts, first_ts + n_samples) of the uplink stream as (I, Q) int16.  Queued bursts lie where their
+ *   radio_ts puts them, clipped to the window; every other sample is 0; every sample is written exactly once.  A burst that
+ *   ends inside the window is retired; one that crosses the window's end stays queued and the next render draws the rest from
+ *   its bits (no sample state is carried: the modulator is deterministic).  Windows must not go backwards; a gap between
+ *   windows is allowed.  A retired burst counts in `drawn` when at least one of its samples lay in a window, in `missed` when
+ *   none did (it lay wholly in a gap); *n_drawn (may be NULL) = bursts this render retired as drawn.
+ * Waits: submit waits for the copy issued 4 submit calls earlier, render for the render issued 4 render calls earlier (their
+ *   pinned buffers are reused), and either may call hipHostMalloc / hipMalloc when a call is larger than any before.  Nothing
+ *   calls hipDeviceSynchronize.  Issue every call of one object on one stream; one object is not thread-safe.  TRXHIP_EIO from
+ *   submit or render (a failed copy or launch): destroy the object.
+ * ctx == NULL: a plan-only object -- submit, plan, render's window and retire logic, counters as on the GPU; nothing is drawn
+ *   and render takes d_out == NULL.
+ * TRXHIP_EINVAL, state untouched: tx_full_scale > 21477, max_pending outside 1 .. 2^22, set_ta outside -126 .. 127, a request
+ *   with tn > 7 or fn >= 2715648 (the whole call fails), now_fn >= 2715648, now_tn > 7, |now_ts| or |first_ts| > 2^62, h_reqs NULL
+ *   with n > 0, first_ts before the end of the previous window, n_samples > 2^31, d_out NULL or not 4-byte aligned on a device
+ *   object, d_out given to a plan-only one. */
+#define TRXHIP_MS_TX_QUEUED  0
+#define TRXHIP_MS_TX_LATE    1
+#define TRXHIP_MS_TX_WRAPPED 2
+#define TRXHIP_MS_TX_EXPIRED 3
+#define TRXHIP_MS_TX_OVERLAP 4
+#define TRXHIP_MS_TX_FULL    5
+typedef struct trxhip_ms_tx_cfg {
+	uint32_t tx_full_scale;  /* txFullScale: 2047 (bladeRF), 9830 (UHD); <= 21477 */
+	int32_t  rxtx_delay;     /* rxtxdelay: -60 (bladeRF), -67 (UHD) */
+	uint32_t max_pending;    /* queued bursts, 1 .. 2^22 */
+	uint32_t reserved;
+} trxhip_ms_tx_cfg;
+typedef struct trxhip_ms_tx_req {  /* 156 bytes */
+	uint32_t fn;
+	uint8_t  tn;
+	uint8_t  pwr;
+	uint8_t  reserved[2];
+	uint8_t  bits[148];      /* one bit per byte; bit 0 counts */
+} trxhip_ms_tx_req;
+typedef struct trxhip_ms_tx_plan {  /* 32 bytes */
+	int64_t  send_ts;
+	int64_t  radio_ts;       /* send_ts + rxtx_delay: the timestamp of the burst's first sample */
+	int32_t  diff_fn, diff_tn;
+	float    scale;
+	int32_t  status;         /* TRXHIP_MS_TX_* */
+} trxhip_ms_tx_plan;
+typedef struct trxhip_ms_tx_status {  /* 96 bytes */
+	uint64_t submitted, queued, late, wrapped, expired, overlap, full;   /* requests, by plan status */
+	uint64_t drawn, missed;  /* retired bursts */
+	uint64_t pending;        /* queued and not retired */
+	int64_t  rendered_end;   /* the end of the last window; 0 before the first */
+	int32_t  timing_advance; /* set_ta's val * 4 */
+	uint8_t  window_set;     /* a window has been rendered */
+	uint8_t  reserved[3];
+} trxhip_ms_tx_status;
+typedef struct trxhip_ms_tx trxhip_ms_tx;
+int  trxhip_ms_tx_create(trxhip_ctx *ctx, const trxhip_ms_tx_cfg *cfg, trxhip_ms_tx **out);
+void trxhip_ms_tx_destroy(trxhip_ms_tx *s);
+/* set_ta(): timing_advance = val * 4, -126 <= val <= 127; applies to bursts submitted afterwards */
+int  trxhip_ms_tx_set_ta(trxhip_ms_tx *s, int val);
+/* n requests in host memory, in order; h_plan (may be NULL): one record per request */
+int  trxhip_ms_tx_submit(trxhip_ms_tx *s, const trxhip_ms_tx_req *h_reqs, size_t n, uint32_t now_fn, int now_tn, int64_t now_ts,
+			 trxhip_ms_tx_plan *h_plan, void *stream);
+int  trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, int64_t first_ts, size_t *n_drawn, void *stream);
+int  trxhip_ms_tx_state(const trxhip_ms_tx *s, trxhip_ms_tx_status *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,12 @@ int trx_launch_tx_render(const uint32_t *d_slots, size_t n_slots, int chans, int
 			 float *d_out_cf32, int16_t *d_out_s16, const float *h_s16_scales, size_t out_stride, hipStream_t stream);
 int trx_launch_tx_fill_update(const trx_tx_fill_update *d_upd, size_t n, const uint8_t *d_rows, trx_tx_fill *d_fill,
 			      hipStream_t stream);
+/* the MS-side uplink burst scheduler's render (trx_tx.hip, ms_tx_render_kernel; trx_ms_tx.h): the n_segs segments that tile a
+ * window of d_out (int16 I, Q; 4-byte aligned), one wave each, from the staged bursts d_rows */
+struct trx_mstx_seg;
+struct trx_mstx_row;
+int trx_launch_ms_tx_render(const trx_mstx_seg *d_segs, size_t n_segs, const trx_mstx_row *d_rows, const trx_tx_tables *d_tab,
+			    int16_t *d_out, hipStream_t stream);
 /* trx_capi.cpp: a transmit front end's logical channels, block length and output samples per block */
 int trx_tx_frontend_geometry(const trxhip_tx_frontend *f, int *chans, int *block_len, size_t *out_per_block);
 

@@ -21,6 +21,7 @@
 #include "../../include/trxhip.h"
 #include "trx_tx_tables.h"
 #include "trx_tx_sched.h"
+#include "trx_ms_tx.h"
 #include "trx_launch.h"
 
 typedef float2 c32;
@@ -659,6 +660,82 @@ extern "C" int trx_launch_tx_fill_update(const trx_tx_fill_update *d_upd, size_t
 	if (n > 0x7fffffffu)
 		return TRXHIP_EINVAL;
 	hipLaunchKernelGGL(tx_fill_update_kernel, dim3((unsigned)n), dim3(64), 0, stream, d_upd, n, d_rows, d_fill);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+// The MS-side uplink burst scheduler's render (trx_ms_tx.cpp plans, this kernel draws): one wave per segment, four per
+// workgroup.  Uplink bursts lie at any sample offset of the window (send_ts - timing_advance + rxtxdelay) and may begin or end
+// outside it, so the planner tiles the window with segments of at most 625 samples: a stretch of a staged burst, from its
+// sample `first` on, or zeros.  A burst segment stages the burst's bits and symbols as tx_render_kernel does and evaluates
+// tx_sample at i + first: a burst drawn in two windows gives the samples of one drawn whole.  The int16 are those of
+// tx_modulate_kernel with s16_scale 1 -- driveTx()'s static_cast<int16_t>(x * 1) -- through tx_store_row: a lone head sample when
+// the segment starts 4 bytes off an 8-byte boundary, 8-byte stores, a lone tail.  Every sample of the window is written once.
+__global__ void __launch_bounds__(64 * TX_WAVES)
+ms_tx_render_kernel(const trx_mstx_seg *__restrict__ segs, size_t n_segs, const trx_mstx_row *__restrict__ rows,
+		    const trx_tx_tables *__restrict__ tab, int16_t *__restrict__ out)
+{
+	__shared__ tx_lds L;
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const size_t b = (size_t)blockIdx.x * TX_WAVES + w;
+	const bool active = b < n_segs;
+
+	if (threadIdx.x < 16)
+		L.p0[threadIdx.x] = tab->pulse4_c0[threadIdx.x];
+	else if (threadIdx.x < 24)
+		L.p1[threadIdx.x - 16] = tab->pulse4_c1[threadIdx.x - 16];
+
+	// ---- the segment and its source (wave-uniform) ----
+	trx_tx_desc d;
+	d.status = 0;
+	d.mode = TX_LAURENT;                       /* modulateBurst(bits, 8 + (tn % 4 == 0), 4), ms_upper.cpp:335 */
+	d.nbits = 148;
+	d.len = 0;                                 /* zeros until a burst is found */
+	d.scale = make_float2(1.0f, 0.0f);
+	d.scaled = true;                           /* scaleVector() runs on every burst, :336 */
+	const uint8_t *bits = nullptr;
+	int first = 0, len = 0;
+	size_t off = 0;
+	if (active) {
+		const trx_mstx_seg g = segs[b];
+		off = g.out_off;
+		len = g.len;
+		first = g.first;
+		if (g.src != TRX_MSTX_ZERO) {
+			const trx_mstx_row *r = rows + g.src;
+			bits = r->bits;
+			d.len = (int)TRX_MSTX_BURST;
+			d.scale = make_float2(r->scale, 0.0f);
+		}
+	}
+	const bool ok = bits != nullptr;
+
+	uint8_t *lb = L.bits[w];
+	if (ok)
+		for (int i = lane; i < d.nbits; i += 64)
+			lb[i] = bits[i] & 0x01;
+	__syncthreads();
+
+	c32 *s0 = L.sym0[w], *s1 = L.sym1[w];
+	if (ok)
+		tx_stage_syms(d, lb, s0, s1, lane, tab);
+	__syncthreads();
+	if (!active)
+		return;
+
+	const c32 *rot = reinterpret_cast<const c32 *>(tab->rot4);
+	auto sample = [&](int i) -> c32 { return tx_sample(d, s0, s1, lb, L, rot, 4, i + first); };
+	tx_store_row(sample, nullptr, out, 2 * off, 1.0f, len, lane);
+}
+
+extern "C" int trx_launch_ms_tx_render(const trx_mstx_seg *d_segs, size_t n_segs, const trx_mstx_row *d_rows, const trx_tx_tables *d_tab,
+				       int16_t *d_out, hipStream_t stream)
+{
+	if (n_segs == 0)
+		return 0;
+	const size_t blocks = (n_segs + TX_WAVES - 1) / TX_WAVES;
+	if (blocks > 0x7fffffffu)
+		return TRXHIP_EINVAL;
+	hipLaunchKernelGGL(ms_tx_render_kernel, dim3((unsigned)blocks), dim3(64 * TX_WAVES), 0, stream, d_segs, n_segs, d_rows, d_tab, d_out);
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
 

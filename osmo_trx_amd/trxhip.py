@@ -203,6 +203,12 @@ SYMBOLS = {
     "trxhip_ms_sched_pull_cf32": (_I, [_VP, _VP, _SZ, C.c_int64, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
     "trxhip_ms_sched_plan": (_I, [_VP, _VP, _SZ]),
     "trxhip_ms_sched_state": (_I, [_VP, _VP]),
+    "trxhip_ms_tx_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
+    "trxhip_ms_tx_destroy": (None, [_VP]),
+    "trxhip_ms_tx_set_ta": (_I, [_VP, _I]),
+    "trxhip_ms_tx_submit": (_I, [_VP, _VP, _SZ, C.c_uint32, _I, C.c_int64, _VP, _VP]),
+    "trxhip_ms_tx_render_s16": (_I, [_VP, _VP, _SZ, C.c_int64, C.POINTER(_SZ), _VP]),
+    "trxhip_ms_tx_state": (_I, [_VP, _VP]),
 }
 
 
@@ -1226,6 +1232,88 @@ class MsRxScheduler:
     def close(self):
         if getattr(self, "h", None):
             self.L.trxhip_ms_sched_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# the MS-side uplink burst scheduler: trxhip_ms_tx_req / _plan / _status, TRXHIP_MS_TX_*
+MS_TX_QUEUED, MS_TX_LATE, MS_TX_WRAPPED, MS_TX_EXPIRED, MS_TX_OVERLAP, MS_TX_FULL = range(6)
+MS_TX_REQ_DTYPE = np.dtype([("fn", "<u4"), ("tn", "u1"), ("pwr", "u1"), ("reserved", "u1", (2,)), ("bits", "u1", (148,))])
+MS_TX_PLAN_DTYPE = np.dtype([("send_ts", "<i8"), ("radio_ts", "<i8"), ("diff_fn", "<i4"), ("diff_tn", "<i4"), ("scale", "<f4"),
+                             ("status", "<i4")])
+MS_TX_STATE_DTYPE = np.dtype([("submitted", "<u8"), ("queued", "<u8"), ("late", "<u8"), ("wrapped", "<u8"), ("expired", "<u8"),
+                              ("overlap", "<u8"), ("full", "<u8"), ("drawn", "<u8"), ("missed", "<u8"), ("pending", "<u8"),
+                              ("rendered_end", "<i8"), ("timing_advance", "<i4"), ("window_set", "u1"), ("reserved", "u1", (3,))])
+assert MS_TX_REQ_DTYPE.itemsize == 156 and MS_TX_PLAN_DTYPE.itemsize == 32 and MS_TX_STATE_DTYPE.itemsize == 96
+
+
+def ms_tx_requests(fn, tn, pwr, bits):
+    """MS_TX_REQ_DTYPE[n] from fn, tn, pwr (scalars or n values each) and bits uint8[n, 148] (or [148]: one request)"""
+    bits = np.asarray(bits, dtype=np.uint8).reshape(-1, 148)
+    r = np.zeros(len(bits), dtype=MS_TX_REQ_DTYPE)
+    r["fn"], r["tn"], r["pwr"], r["bits"] = fn, tn, pwr, bits
+    return r
+
+
+class _MsTxCfg(C.Structure):
+    _fields_ = [("tx_full_scale", C.c_uint32), ("rxtx_delay", C.c_int32), ("max_pending", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MsTxScheduler:
+    """MS-side uplink burst scheduler (trxhip_ms_tx_*): burst requests in, the radio's int16 transmit stream out --
+    driveTx()'s scale and ms_trx::submit_burst()'s timestamp arithmetic, then a render of any window of the stream.
+    trx=None: a plan-only object (no GPU): submit, plan, window and counters; render draws nothing."""
+
+    def __init__(self, trx=None, tx_full_scale=2047, rxtx_delay=0, max_pending=1024):
+        self.trx = trx
+        self.L = trx.L if trx is not None else load_library()
+        cfg = _MsTxCfg(tx_full_scale, rxtx_delay, max_pending, 0)
+        h = _VP()
+        _check(self.L.trxhip_ms_tx_create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_ms_tx_create")
+        self.h = h
+
+    def set_ta(self, val):
+        _check(self.L.trxhip_ms_tx_set_ta(self.h, val), "trxhip_ms_tx_set_ta")
+
+    def submit(self, reqs, clock, stream=None):
+        """reqs: MS_TX_REQ_DTYPE[n] (ms_tx_requests()); clock: the timekeeper's (fn, tn, ts), MsRxScheduler.clock().
+        Returns the plan, MS_TX_PLAN_DTYPE[n]."""
+        reqs = np.ascontiguousarray(reqs, dtype=MS_TX_REQ_DTYPE).reshape(-1)
+        plan = np.zeros(len(reqs), dtype=MS_TX_PLAN_DTYPE)
+        fn, tn, ts = clock
+        _check(self.L.trxhip_ms_tx_submit(self.h, reqs.ctypes.data_as(_VP), len(reqs), fn, tn, ts, plan.ctypes.data_as(_VP),
+                                          self.trx._stream(stream) if self.trx is not None else None), "trxhip_ms_tx_submit")
+        return plan
+
+    def render(self, n_samples, first_ts, out=None, stream=None):
+        """samples [first_ts, first_ts + n_samples) of the uplink stream.  Returns (int16[n_samples, 2] device tensor, n_drawn);
+        out: an int16 device tensor of at least n_samples (I, Q) pairs to write instead.  Plan-only: (None, n_drawn)."""
+        nd = _SZ()
+        if self.trx is None:
+            _check(self.L.trxhip_ms_tx_render_s16(self.h, None, n_samples, first_ts, C.byref(nd), None), "trxhip_ms_tx_render_s16")
+            return None, nd.value
+        torch = self.trx.torch
+        if out is None:
+            out = torch.empty((max(n_samples, 1), 2), dtype=torch.int16, device=f"cuda:{self.trx.device}")
+        assert out.dtype == torch.int16 and out.is_contiguous() and out.numel() >= 2 * n_samples, (out.shape, out.dtype)
+        _check(self.L.trxhip_ms_tx_render_s16(self.h, out.data_ptr(), n_samples, first_ts, C.byref(nd), self.trx._stream(stream)),
+               "trxhip_ms_tx_render_s16")
+        return out, nd.value
+
+    def state(self):
+        """MS_TX_STATE_DTYPE record: the counters and the window state"""
+        a = np.zeros(1, dtype=MS_TX_STATE_DTYPE)
+        _check(self.L.trxhip_ms_tx_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_tx_state")
+        return a[0]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.trxhip_ms_tx_destroy(self.h)
             self.h = None
 
     def __del__(self):
