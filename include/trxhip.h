@@ -78,7 +78,7 @@ enum trxhip_signal_error {
 #define TRXHIP_FLAG_IDLE_DUMMY   4  /* search IDLE slots for the dummy burst, as detectAnyBurst(IDLE) does (detectDummyBurst,
                                      * sigProcLib.cpp:1863-1877, :1945-1947; rc = IDLE on a hit) instead of skipping them as
                                      * pullRadioVector does (Transceiver.cpp:754-755) */
-#define TRXHIP_FLAG_USE_VA       8  /* trxhip_hostpipe_cfg.flags only: see there */
+#define TRXHIP_FLAG_USE_VA       8  /* trxhip_hostpipe_cfg.flags and trxhip_rx_sched_cfg.flags only: cfg->use_va, see there */
 #define TRXHIP_FLAG_FEW_NB_SLOTS 16 /* a HINT from a caller that knows its slot types (expectedCorrType() runs on the host,
                                      * Transceiver.cpp:513-601): more than 1/32 of the batch's slots are not normal-burst slots
                                      * (type TSC, tsc < 8, max_toa <= 32).  Results never depend on it; the call then runs the
@@ -421,8 +421,8 @@ typedef struct trxhip_hostpipe_cfg {
 	int32_t  sps;
 	int32_t  soft_stride;  /* floats per burst downloaded (148 / 156 / 444); 0 = no float soft output */
 	int32_t  pkt_stride;   /* bytes per burst of TRXD datagrams downloaded (multiple of 4, >= 160); 0 = no TRXD packing */
-	int32_t  flags;        /* TRXHIP_FLAG_*; TRXD packing implies TRXHIP_FLAG_SLICE.  TRXHIP_FLAG_USE_VA (host pipe only): the
-	                        * cfg->use_va flow of pullRadioVector (Transceiver.cpp:760-787) -- the slot's bursts are what the radio
+	int32_t  flags;        /* TRXHIP_FLAG_*; TRXD packing implies TRXHIP_FLAG_SLICE.  TRXHIP_FLAG_USE_VA (here and in the uplink
+	                        * burst scheduler's config): the cfg->use_va flow of pullRadioVector (Transceiver.cpp:760-787) -- the slot's bursts are what the radio
 	                        * read 20 samples early; power / rssi come from them as read, detection runs on the copy shifted by 20
 	                        * samples (zeros behind), the soft bits from scaleVector(1 / 16383) + demodAnyBurst_va() on the unshifted
 	                        * burst (trxhip_demod_va_batch_cf32 chained behind the detection records): hard 0 / 1 rows of 148 */
@@ -787,6 +787,21 @@ int  trxhip_tx_sched_counters(const trxhip_tx_sched *s, int chan, trxhip_tx_sche
  * mNoises.insert(avg), mNoiseLev = mNoises.avg() (20 entries summed in float in index order, / 20.0f), an idle indication.
  * Any other type -- trxhip_detect_demod_batch[_cf32] with TRXHIP_FLAG_SLICE (and cfg.flags): rc <= 0 is an idle indication,
  * rc == -TRXHIP_SIGERR_CLIP counts in rx_clipping, any other negative rc in rx_no_burst_detected; rx_empty_burst stays 0.
+ * cfg.flags & TRXHIP_FLAG_USE_VA: cfg->use_va ("viterbi-eq", Transceiver.cpp:760-787).  The stream handed to such an object is
+ * what the radio read with readTimestamp -= 20 (rif_va_wrapper, osmo-trx.cpp:84-99) -- the early read is the caller's -- so
+ * every slot begins 20 samples before the burst the detector expects.  OFF, mute and the noise ring are as above.  Power, rssi
+ * and the ring's avg come from energyDetect over the slot as read; detection runs on shift_vec, the slot's samples 20 .. 604
+ * with 40 zeros behind, and gives rc, toa, tsc and ci; rc <= 0 is the idle indication with the counters as above; otherwise the
+ * soft row is vectorSlicer over scaleVector(burst, 1 / 16383) + demodAnyBurst_va() on the unshifted slot
+ * (trxhip_demod_va_batch_cf32's bits: hard 0 / 1 for 148 bits, or for 88 on the access branch with 0.5 behind them).  Every slot
+ * is read where it lies: one kernel writes the detector's rows and the slots' power, the detect entry point runs over those
+ * rows, one kernel runs the Viterbi receiver over the slots in the stream (int16 streams are converted and scaled as they
+ * are loaded; no complex64 copy is made).  The detector's rows are the object's: chans * max_slots * 625 samples of the pull's
+ * format (2500 bytes a slot for int16, 5000 for complex64: 655 MB / 1.31 GB at one channel and 2^18 slots), allocated with
+ * hipMalloc on the first such pull and again when a pull's format differs from the last one's (possible only with nothing
+ * carried); TRXHIP_ENOMEM, state untouched, when that fails.  As the reference does (osmo-trx.cpp:492-496), create refuses the
+ * flag with sps = 1 or egprs, and with TRXHIP_FLAG_EXACT_DEMOD (no filter demodulator runs); trxhip_rx_sched_pull_frontend()
+ * takes a RESAMP front end and refuses a MULTI one.  A plan-only object accepts the flag and cuts and plans as without it.
  * Outputs of a pull that cuts n slots, device buffers indexed [chan * n + slot]:
  *   d_pkt, d_pkt_len : datagram rows of pkt_stride bytes and their lengths, exactly trxhip_pack_trxd_wire_batch()'s (one call
  *                      per channel with its version and rssi_offset over the slot's result record)
@@ -839,7 +854,8 @@ typedef struct trxhip_rx_sched_cfg {
 	int32_t  ul_fn_offset;   /* cfg->ul_fn_offset, |offset| < 2715648 */
 	int32_t  ext_rach;       /* cfg->ext_rach */
 	int32_t  egprs;          /* cfg->egprs: soft rows of 444; 0 with sps = 1 */
-	int32_t  flags;          /* 0 or TRXHIP_FLAG_EXACT_DEMOD (sps = 1: accepted, the 1-SPS kernels are exact already) */
+	int32_t  flags;          /* 0, TRXHIP_FLAG_EXACT_DEMOD (sps = 1: accepted, the 1-SPS kernels are exact already) or
+	                          * TRXHIP_FLAG_USE_VA (sps = 4, egprs = 0) */
 	float    threshold;      /* TRXHIP_BURST_THRESH */
 	float    full_scale;     /* rxFullScale */
 	uint32_t reserved;
@@ -889,7 +905,8 @@ int  trxhip_rx_sched_pull_cf32(trxhip_rx_sched *s, const float *d_in, size_t in_
  * slot, the one that begins in the remainder too, is detected where it lies: no slot is assembled and no second detect launch
  * runs.  Refused with TRXHIP_EINVAL before anything is launched, both objects untouched: a NULL, plan-only or foreign-context
  * object, rows != chans, the four-row object of trxhip_rx_frontend_create(), d_wide NULL or misaligned, d_work NULL or
- * misaligned, work_stride odd or too small, and whatever trxhip_rx_sched_pull_cf32() refuses.
+ * misaligned, work_stride odd or too small, a MULTI front end with a TRXHIP_FLAG_USE_VA scheduler (the reference refuses
+ * use_va with multi-ARFCN), and whatever trxhip_rx_sched_pull_cf32() refuses.
  * trxhip_rx_sched_slots_frontend(): trxhip_rx_sched_slots(s, out_samples), or TRXHIP_EINVAL for a pair the pull refuses */
 #define TRXHIP_RX_SCHED_WORK_HEAD 640   /* samples in front of the front end's output in a work row */
 int64_t trxhip_rx_sched_slots_frontend(const trxhip_rx_sched *s, const trxhip_rx_frontend *fe, size_t n_blocks);

@@ -56,6 +56,17 @@ size_t trx_va_lds_bytes(int L);
 int trx_launch_va_demod(const float *d_iq, const trxhip_burst_params *d_params, const trxhip_burst_result *d_detected, float *d_soft,
 			int32_t *d_starts, size_t n_bursts, int L, float scale, int soft_stride, int flags, hipStream_t stream);
 
+/* trx_rx_sched_va.hip: the uplink scheduler's use_va flow over the chans * n_slots slots of one pull, slot chan * n_slots + k at
+ * d_in + chan * in_stride + k * 625 - carried samples (int16 pairs, or complex64 with cf32), slot 0 of every channel at
+ * d_edge + chan * 625 instead when d_edge is given.  _prep: the detector's rows (samples 20 .. 604, then 40 zeros) into d_shift
+ * in the input's format, and energyDetect(slot, 80) of the slots as read.  _slots: va_demod_kernel's work with slicing for the
+ * slots whose record in d_detected has rc > 0, a zero soft row for the others */
+int trx_launch_rx_va_prep(const void *d_in, int cf32, size_t in_stride, const void *d_edge, uint32_t carried, size_t n_slots, int chans,
+			  void *d_shift, float *d_energy, hipStream_t stream);
+int trx_launch_rx_va_slots(const void *d_in, int cf32, size_t in_stride, const void *d_edge, uint32_t carried, size_t n_slots,
+			   int chans, const trxhip_burst_params *d_params, const trxhip_burst_result *d_detected, float *d_soft,
+			   float scale, int soft_stride, hipStream_t stream);
+
 /* trx_sch_sync.hip: the MS-side SCH receiver.  d_iq: int16 IQ (i16) or complex64 buffers, buf_stride samples apart; acq: the
  * buffer search over the lags 0 .. len - 513 through d_power (n_bufs x (len - 512) floats) and d_best (n_bufs), else the
  * one-slot search (both NULL) */

@@ -17,6 +17,11 @@
 // rows into the caller's work rows behind TRX_RXS_REM_STRIDE samples of room, rx_join_kernel puts the carried remainder in front
 // of them and saves the new one, and every slot of the pull -- the one that begins in the remainder too -- is detected where it
 // lies: no slot is assembled, no launch over straddling rows runs, and the plan, the epilogue and the packer are the same.
+// With TRXHIP_FLAG_USE_VA (cfg->use_va, Transceiver.cpp:760-787; the stream is what the radio read 20 samples early) the detect
+// launches above give way to one detect launch between trx_rx_sched_va.hip's two kernels: rx_va_prep_kernel (the detector's rows -- every slot's
+// samples 20 .. 604, zeros behind -- and the power of the slots as read), trxhip_detect_demod_batch[_cf32] over those rows
+// without soft output, rx_va_slot_kernel (the Viterbi receiver over the unshifted slots it found, read where they lie, sliced)
+// and trxhip_apply_diversity_power (energy and rssi from the slots as read); the straddling row is one of the slots.
 // With ctx == NULL the object is plan-only: cutter, clock and plan, no device memory.
 #include <hip/hip_runtime.h>
 
@@ -295,6 +300,9 @@ struct trxhip_rx_sched {
 	trxhip_burst_result *d_res = nullptr, *d_edge_res = nullptr;
 	uint32_t *d_rank = nullptr, *d_idle_slot = nullptr;
 	float *d_soft = nullptr, *d_edge_soft = nullptr;
+	void *d_shift = nullptr;               /* TRXHIP_FLAG_USE_VA: [chans][max_slots][625] samples of shift_cf32's format, the detector's rows */
+	int shift_cf32 = 0;
+	float *d_energy = nullptr;             /* TRXHIP_FLAG_USE_VA: [chans][max_slots], energyDetect of the slots as read */
 	void *d_edge_row = nullptr;            /* [chans][625] samples of either format (1 SPS: rows of slot 0's 157 or 156) */
 	void *d_rem = nullptr;                 /* [2][chans][TRX_RXS_REM_STRIDE] samples of either format */
 	trx_rxs_noise *d_noise = nullptr;      /* [2][chans] */
@@ -371,6 +379,8 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 			return TRXHIP_EIO;
 		const hipStream_t st = static_cast<hipStream_t>(stream);
 		const bool straddle = n && s->carried && !fep;         /* through the front end the stream lies in one piece */
+		const bool va = (s->cfg.flags & TRXHIP_FLAG_USE_VA) != 0;
+		const bool edge_rec = straddle && !va;                 /* the straddling row has a record and a soft row of its own */
 		const size_t esz = cf32 ? 8 : 4;
 		const char *rem_in = static_cast<const char *>(s->d_rem) + (size_t)s->rem_half * chans * TRX_RXS_REM_STRIDE * esz;
 		char *rem_out = static_cast<char *>(s->d_rem) + (size_t)(s->rem_half ^ 1) * chans * TRX_RXS_REM_STRIDE * esz;
@@ -382,6 +392,18 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 				s->d_soft = nullptr;
 				return TRXHIP_ENOMEM;
 			}
+		}
+		if (va && n && (!s->d_shift || s->shift_cf32 != cf32)) {
+			/* the detector's rows, in the stream's format: allocated on the first use_va pull, and again when the format changes
+			 * (only with nothing carried, see above); hipFree waits for the pulls that read the old rows.  Nothing has changed
+			 * yet if it fails */
+			if (s->d_shift)
+				(void)hipFree(s->d_shift);
+			if (hipMalloc(&s->d_shift, (size_t)chans * s->cfg.max_slots * TRX_RXS_SLOT * esz) != hipSuccess) {
+				s->d_shift = nullptr;
+				return TRXHIP_ENOMEM;
+			}
+			s->shift_cf32 = cf32;
 		}
 		float *soft = d_soft ? d_soft : s->d_soft;
 		const int ss = s->soft_stride;
@@ -412,7 +434,8 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 						   s->carried, n, slot0, (size_t)cut, n_rem, static_cast<uint32_t *>(s->d_edge_row));
 			rc = launched();
 		}
-		const int flags = TRXHIP_FLAG_SLICE | (s->cfg.flags & TRXHIP_FLAG_EXACT_DEMOD);
+		/* use_va: detection alone, no soft bits from it (Transceiver.cpp:762-768) */
+		const int flags = va ? 0 : TRXHIP_FLAG_SLICE | (s->cfg.flags & TRXHIP_FLAG_EXACT_DEMOD);
 		auto detect = [&](const void *iq, const trxhip_burst_params *p, trxhip_burst_result *r, float *so, size_t cnt) {
 			return cf32 ? trxhip_detect_demod_batch_cf32(s->ctx, static_cast<const float *>(iq), p, r, so, cnt, (int)slot0, s->cfg.sps,
 								     s->cfg.threshold, s->cfg.full_scale, ss, flags, stream)
@@ -427,14 +450,30 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 			return trx_launch_pull_stream(iq, cf32, (unsigned)(((size_t)s->tn + k0) & 3u), p, r, so, s->ctx->d_tables, cnt,
 						      s->cfg.threshold, s->cfg.full_scale, ss, kf, s->ctx->n_cu, st);
 		};
-		if (rc == TRXHIP_OK && straddle)
+		if (va && n) {
+			/* cfg->use_va (Transceiver.cpp:760-787): every slot of the pull, the assembled straddling row among them, in one
+			 * launch each -- the detector's rows and the power of the slots as read; detection over those rows; the Viterbi
+			 * receiver over the unshifted slots it found, sliced; energy and rssi of the records from the slots as read */
+			const void *edge = straddle ? s->d_edge_row : nullptr;
+			const size_t all = (size_t)chans * n;
+			if (rc == TRXHIP_OK)
+				rc = trx_launch_rx_va_prep(d_in, cf32, in_stride, edge, s->carried, n, chans, s->d_shift, s->d_energy, st);
+			if (rc == TRXHIP_OK)
+				rc = detect(s->d_shift, s->d_params, s->d_res, nullptr, all);
+			if (rc == TRXHIP_OK)
+				rc = trx_launch_rx_va_slots(d_in, cf32, in_stride, edge, s->carried, n, chans, s->d_params, s->d_res, soft,
+							    1.0f / (float)((1 << 14) - 1), ss, st);
+			if (rc == TRXHIP_OK)
+				rc = trxhip_apply_diversity_power(s->ctx, s->d_res, s->d_params, s->d_energy, all, s->cfg.full_scale, stream);
+		}
+		if (rc == TRXHIP_OK && edge_rec)
 			rc = detect(s->d_edge_row, s->d_edge_params, s->d_edge_res, s->d_edge_soft, (size_t)chans);
 		// the slots inside the chunk, where they are: slot k starts k * 625 - carried samples into it (1 SPS:
 		// trx_rxs_slot_start(tn, k) - carried); the last of them ends before the chunk does.  Through the front end slot 0 is
 		// one of them: it starts `carried` samples in front of the chunk, in the work row's head
 		const size_t k0 = straddle ? 1 : 0;
 		const ptrdiff_t first = (ptrdiff_t)(sps1 ? trx_rxs_slot_start(s->tn, k0) : k0 * TRX_RXS_SLOT) - (ptrdiff_t)s->carried;
-		for (int c = 0; rc == TRXHIP_OK && c < chans && n > k0; c++) {
+		for (int c = 0; rc == TRXHIP_OK && !va && c < chans && n > k0; c++) {
 			const size_t o = (size_t)c * n + k0;
 			const char *iq = static_cast<const char *>(d_in) + ((ptrdiff_t)((size_t)c * in_stride) + first) * (ptrdiff_t)esz;
 			rc = sps1 ? detect_stream(iq, k0, s->d_params + o, s->d_res + o, soft + o * (size_t)ss, n - k0)
@@ -443,8 +482,8 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 		if (rc == TRXHIP_OK && n) {
 			RssiOffsets offs;
 			memcpy(offs.v, s->rssi_offset, sizeof(offs.v));
-			hipLaunchKernelGGL(rx_ind_kernel, dim3(bpc + (straddle ? 1u : 0u), chans), dim3(kThreads), 0, st, n, s->d_plan, s->d_params,
-					   s->d_meta, s->d_res, straddle ? s->d_edge_res : nullptr, s->d_rank, s->d_idle_slot,
+			hipLaunchKernelGGL(rx_ind_kernel, dim3(bpc + (edge_rec ? 1u : 0u), chans), dim3(kThreads), 0, st, n, s->d_plan, s->d_params,
+					   s->d_meta, s->d_res, edge_rec ? s->d_edge_res : nullptr, s->d_rank, s->d_idle_slot,
 					   s->d_noise + (size_t)s->noise_half * chans, s->d_noise + (size_t)(s->noise_half ^ 1) * chans, s->d_ctrs,
 					   d_ind, s->d_edge_soft, soft, ss, offs);
 			rc = launched();
@@ -493,6 +532,9 @@ bool frontend_ok(const trxhip_rx_sched *s, const trxhip_rx_frontend *fe, size_t 
 		return false;
 	if (ctx != s->ctx || rows != s->cfg.chans)
 		return false;
+	/* the reference refuses use_va with multi-ARFCN (osmo-trx.cpp:492-496) */
+	if ((s->cfg.flags & TRXHIP_FLAG_USE_VA) && !*resamp)
+		return false;
 	/* max_slots <= 2^20: a pull that could be accepted is far below this */
 	if (n_blocks > ((size_t)1 << 40) / (size_t)block_len)
 		return false;
@@ -511,8 +553,12 @@ int create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **ou
 		return TRXHIP_EINVAL;
 	if (c.chans < 1 || c.chans > TRX_RXS_MAX_CHANS || c.tsc < 0 || c.tsc > 7 ||
 	    c.ul_fn_offset <= -(int32_t)TRX_RXS_HYPERFRAME || c.ul_fn_offset >= (int32_t)TRX_RXS_HYPERFRAME ||
-	    (c.flags & ~TRXHIP_FLAG_EXACT_DEMOD) || !(c.full_scale > 0.0f) || !std::isfinite(c.full_scale) || !std::isfinite(c.threshold) ||
+	    (c.flags & ~(TRXHIP_FLAG_EXACT_DEMOD | TRXHIP_FLAG_USE_VA)) || !(c.full_scale > 0.0f) || !std::isfinite(c.full_scale) || !std::isfinite(c.threshold) ||
 	    c.max_slots < 1 || c.max_slots > ((uint64_t)1 << 20))
+		return TRXHIP_EINVAL;
+	/* use_va: 4 SPS, no EDGE (osmo-trx.cpp:492-496), and no filter demodulator whose operand order could be chosen */
+	const bool va = (c.flags & TRXHIP_FLAG_USE_VA) != 0;
+	if (va && (c.sps != 4 || c.egprs || (c.flags & TRXHIP_FLAG_EXACT_DEMOD)))
 		return TRXHIP_EINVAL;
 	if (ctx && with_device(ctx))
 		return TRXHIP_EINVAL;
@@ -550,6 +596,7 @@ int create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **ou
 		  hipMalloc((void **)&s->d_edge_row, ch * TRX_RXS_SLOT * 8) == hipSuccess &&
 		  hipMalloc((void **)&s->d_rem, rem_bytes) == hipSuccess && hipMalloc((void **)&s->d_noise, noise_bytes) == hipSuccess &&
 		  hipMalloc((void **)&s->d_ctrs, ch * 2 * sizeof(unsigned long long)) == hipSuccess &&
+		  (!va || hipMalloc((void **)&s->d_energy, slots * sizeof(float)) == hipSuccess) &&
 		  hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) == hipSuccess;
 	/* the ring starts as std::vector<float>(20): zeros, itr 0, mNoiseLev 0 (Transceiver.cpp:64) */
 	ok = ok && hipMemset(s->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(s->d_noise, 0, noise_bytes) == hipSuccess &&
@@ -586,7 +633,7 @@ void trxhip_rx_sched_destroy(trxhip_rx_sched *s)
 			(void)hipEventSynchronize(s->ev);
 		if (s->ev) (void)hipEventDestroy(s->ev);
 		void *bufs[] = { s->d_plan, s->d_params, s->d_meta, s->d_res, s->d_rank, s->d_idle_slot, s->d_soft, s->d_edge_params,
-				 s->d_edge_res, s->d_edge_soft, s->d_edge_row, s->d_rem, s->d_noise, s->d_ctrs };
+				 s->d_edge_res, s->d_edge_soft, s->d_edge_row, s->d_rem, s->d_noise, s->d_ctrs, s->d_shift, s->d_energy };
 		for (void *p : bufs)
 			if (p) (void)hipFree(p);
 	}

@@ -25,7 +25,8 @@ public:
 	 * one-channel uplink scheduler sched (on sigProcLibSetup()'s context; its sps states this object's output rate) to TRXD
 	 * indications -- trxhip_rx_sched_pull_frontend() (include/trxhip.h) with this object's front-end handle and stream.  Every
 	 * pointer is device memory: d_in as `in` above, d_work the call's work row, the rest the scheduler's outputs.
-	 * Asynchronous; returns the call's TRXHIP_* code. */
+	 * A scheduler created with TRXHIP_FLAG_USE_VA (cfg->use_va; d_in is then what the radio read 20 samples early) is taken
+	 * as any other: the handle is passed through.  Asynchronous; returns the call's TRXHIP_* code. */
 	int pullScheduled(trxhip_rx_sched *sched, const int16_t *d_in, size_t n_chunks, float *d_work, size_t work_stride,
 			  uint8_t *d_pkt, int pkt_stride, uint16_t *d_pkt_len, trxhip_ul_ind *d_ind, float *d_soft, size_t out_slots,
 			  size_t *n_slots, size_t *n_carried);

@@ -34,7 +34,8 @@ TRXD_RECORD_BYTES = 156
 FLAG_SLICE = 1          # TRXHIP_FLAG_SLICE
 FLAG_EXACT_DEMOD = 2    # TRXHIP_FLAG_EXACT_DEMOD
 FLAG_IDLE_DUMMY = 4     # TRXHIP_FLAG_IDLE_DUMMY
-FLAG_FEW_NB_SLOTS = 16  # TRXHIP_FLAG_FEW_NB_SLOTS (a hint: see include/trxhip.h)
+FLAG_USE_VA = 8         # TRXHIP_FLAG_USE_VA (host pipe, uplink scheduler)
+FLAG_FEW_NB_SLOTS = 16 # TRXHIP_FLAG_FEW_NB_SLOTS (a hint: see include/trxhip.h)
 SCH_DETECT_FULL, SCH_DETECT_NARROW, SCH_DETECT_BUFFER = 0, 1, 2   # sch_detect_type (sigProcLib.h:139-143)
 SCH_SYNC_TRACK, SCH_SYNC_ACQ = 0, 1                               # TRXHIP_SCH_SYNC_*
 SCH_SYNC_MAX_LEN = 1 << 20                                        # TRXHIP_SCH_SYNC_MAX_LEN
@@ -939,14 +940,14 @@ class RxScheduler:
     sps=1: the reference's default receive rate, slots of 157 / 156 / 156 / 156 samples (trxhip_rx_sched_create_sps)."""
 
     def __init__(self, trx=None, chans=1, sps=4, tsc=0, ul_fn_offset=0, ext_rach=False, egprs=False, exact=False, threshold=4.0,
-                 full_scale=32767.0, max_slots=8 * 1024):
+                 full_scale=32767.0, max_slots=8 * 1024, use_va=False):
         self.trx = trx
         self.L = trx.L if trx is not None else load_library()
         self.chans, self.full_scale = chans, float(full_scale)
         self.soft_stride = 444 if egprs else 148
         self.rssi_offset = [0.0] * chans
-        cfg = _RxSchedCfg(chans, sps, tsc, ul_fn_offset, int(bool(ext_rach)), int(bool(egprs)), FLAG_EXACT_DEMOD if exact else 0,
-                          threshold, full_scale, 0, max_slots)
+        cfg = _RxSchedCfg(chans, sps, tsc, ul_fn_offset, int(bool(ext_rach)), int(bool(egprs)),
+                          (FLAG_EXACT_DEMOD if exact else 0) | (FLAG_USE_VA if use_va else 0), threshold, full_scale, 0, max_slots)
         h = _VP()
         create = self.L.trxhip_rx_sched_create_sps if sps == 1 else self.L.trxhip_rx_sched_create
         _check(create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_rx_sched_create")
