@@ -1016,6 +1016,67 @@ int  trxhip_ms_sched_pull_cf32(trxhip_ms_sched *s, const float *d_in, size_t n_s
 int  trxhip_ms_sched_plan(const trxhip_ms_sched *s, trxhip_ms_plan *h_out, size_t n);   /* the last pull's first n slots */
 int  trxhip_ms_sched_state(trxhip_ms_sched *s, trxhip_ms_sched_status *out);
 
+/* ---- A group of MS-side downlink streams: the pulls of all members cut and received as one step ---------------------------
+ * n_members (1 .. TRXHIP_MS_GROUP_MAX_MEMBERS) streams, each what one trxhip_ms_sched is -- its own tsc, active_tns, tracking,
+ * clock, carried partial slot, pending correction, counters and last plan --, behind one radio type: rx_full_scale belongs to
+ * the group, and every cfgs[i].rx_full_scale must equal it.  Every call that names a member has the semantics of the
+ * trxhip_ms_sched_* call of the same name on that member; a member index >= n_members is TRXHIP_EINVAL.
+ * pull: h_chunks[m] = {d_in, n_samples, first_ts} is member m's chunk; n_samples == 0: the member has no chunk in this pull --
+ *   nothing of it changes, h_n_slots[m] = 0, its last plan is kept.  The sample format is that of the call; the carried-format
+ *   rule holds per member.  Member m's slot k goes to d_ind[m * out_stride + k] and d_bits[(m * out_stride + k) * 148] (d_bits
+ *   may be NULL), k < h_n_slots[m] <= out_stride; nothing else of the outputs is written.  h_n_slots, h_n_carried (each may be
+ *   NULL): n_members values.
+ *   All or nothing: where any member's pull is one the single object refuses (above, per member, with out_stride as out_slots),
+ *   the call returns that member's code, *bad_member (may be NULL; -1 otherwise) is the lowest such index, and no member's state
+ *   moves (rows of straddling SCH slots may already have been written, as above).  What a refused pull may have done all the
+ *   same, none of it visible in any member's state: waited for and folded the corrections in flight (wait (1) below; state()
+ *   folds them too), waited for a pinned table area, and run the launch set of wait (2) -- its table copy, its join, a clear and
+ *   a copy of all n_members correction words.  A pull in which no member has a chunk, or whose slots need more than 2^31 - 1
+ *   wavefronts, is TRXHIP_EINVAL.
+ *   Issued per pull, whatever n_members is: one copy of a table (64 bytes per member with slots, 64 per member with a join) from
+ *   one of four pinned areas taken in turn, one join launch, one clear and one copy of the n_members correction words where a
+ *   tracking member cuts an SCH slot, one receiver launch, one event record behind all of it.
+ * Waits: (1) once for the group, for the corrections of an earlier pull, when a tracking member plans and any member's
+ *   correction is in flight; (2) once for the group, where the straddling slot of one or more tracking members is an SCH slot:
+ *   those slots are demodulated together in a launch set of their own (table, join, clear, receiver, copy, event) first.  A
+ *   pinned table area is written again only behind the event of the launch set that read it, four launch sets earlier: a host
+ *   that runs further ahead of the device than that waits there.  With tracking off everywhere a pull waits for nothing else.
+ * acquire: one trxhip_sch_sync_batch_*(TRXHIP_SCH_SYNC_ACQ) over n buffers of buf_len samples, buf_stride samples apart (buffer i
+ *   is members[i]'s, first_ts[i] its first sample's timestamp), one wait; h_res (may be NULL), h_found (may be NULL): n values.
+ *   Per found member the assignments of trxhip_ms_sched_acquire_*; members not found are untouched.  Returns the number found.
+ *   TRXHIP_EINVAL, nothing changed: a member listed twice, n == 0, a found record with fn outside the hyperframe.
+ * ctx == NULL: a plan-only group -- no buffers, starts from per-member queues, acquire READS h_res[i]; out_stride == 0 leaves
+ *   the counts unbounded, as the plan-only single object does, any other value bounds them as on the GPU.
+ * Issue every call of one group on one stream; one group is not thread-safe. */
+#define TRXHIP_MS_GROUP_MAX_MEMBERS 4096
+typedef struct trxhip_ms_group_chunk {  /* 24 bytes */
+	const void *d_in;        /* int16 I, Q pairs or complex64, as the call says; 4- / 8-byte aligned */
+	size_t      n_samples;   /* 0: no chunk for this member */
+	int64_t     first_ts;
+} trxhip_ms_group_chunk;
+typedef struct trxhip_ms_group trxhip_ms_group;
+int  trxhip_ms_group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const trxhip_ms_sched_cfg *cfgs,
+			    trxhip_ms_group **out);
+void trxhip_ms_group_destroy(trxhip_ms_group *g);
+int  trxhip_ms_group_members(const trxhip_ms_group *g);
+int  trxhip_ms_group_set_clock(trxhip_ms_group *g, uint32_t member, uint32_t fn, int tn, int64_t ts);
+int  trxhip_ms_group_clock(const trxhip_ms_group *g, uint32_t member, uint32_t *fn, int *tn, int64_t *ts);
+int  trxhip_ms_group_set_tsc(trxhip_ms_group *g, uint32_t member, int tsc);
+int  trxhip_ms_group_set_active(trxhip_ms_group *g, uint32_t member, uint8_t tn_mask);
+int  trxhip_ms_group_set_tracking(trxhip_ms_group *g, uint32_t member, int on);
+int  trxhip_ms_group_feed_starts(trxhip_ms_group *g, uint32_t member, const int32_t *starts, size_t n);   /* plan-only groups */
+int64_t trxhip_ms_group_slots(const trxhip_ms_group *g, uint32_t member, size_t n_samples);
+int  trxhip_ms_group_plan(const trxhip_ms_group *g, uint32_t member, trxhip_ms_plan *h_out, size_t n);
+int  trxhip_ms_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_sched_status *out);
+int  trxhip_ms_group_acquire_s16(trxhip_ms_group *g, const uint32_t *members, size_t n, const int16_t *d_bufs, size_t buf_stride,
+				 size_t buf_len, const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream);
+int  trxhip_ms_group_acquire_cf32(trxhip_ms_group *g, const uint32_t *members, size_t n, const float *d_bufs, size_t buf_stride,
+				  size_t buf_len, const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream);
+int  trxhip_ms_group_pull_s16(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+			      size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream);
+int  trxhip_ms_group_pull_cf32(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+			       size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream);
+
 /* ---- The MS-side uplink burst scheduler: burst requests in, the radio's transmit sample stream out --------------------------
  * What the reference does between trxcon's burst request and the radio: upper_trx::driveTx() (ms/ms_upper.cpp:306-355),
  * ms_trx::submit_burst() (ms/ms.cpp:114-160), set_ta() (ms/ms.h:299-303) and submit_burst_ts() (ms/uhd_specific.h:260-269,

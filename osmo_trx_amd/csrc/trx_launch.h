@@ -80,6 +80,12 @@ int trx_launch_ms_rx(const void *d_iq, int i16, size_t slot_stride, const trxhip
 struct trx_mss_stream;
 int trx_launch_ms_rx_stream(const void *d_chunk, int i16, const struct trx_mss_stream *sa, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
 			    size_t n_slots, float scale, float rx_full_scale, hipStream_t stream);
+/* its group form (trx_ms_sched.h): n_waves waves over the n_entries members of the table d_tab, each wave's slots those of one
+ * member */
+struct trx_mss_member;
+int trx_launch_ms_rx_group(const struct trx_mss_member *d_tab, int i16, size_t n_entries, size_t n_waves, float scale, float rx_full_scale,
+			   hipStream_t stream);
+#define TRX_MS_RX_SLOTS_PER_WAVE 4      /* VA_BPW: slots per wave in all three forms */
 
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,

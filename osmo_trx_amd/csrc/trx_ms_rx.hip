@@ -15,6 +15,8 @@
 // THE STREAM FORM (trx_ms_sched.hip) is a second instantiation of the same body: a slot's record is computed from the pull's base
 // clock and the slot index, the slot is read where it lies in the caller's chunk (or from the row that holds the straddling
 // slot), and a decoded SCH slot with abs(start) > 1 adds -start to the pull's correction word.
+// THE GROUP FORM (trxhip_ms_group_*) is the stream form behind a table: a wave's four slots belong to one member of a group of
+// streams, and the wave takes chunk, descriptor and outputs from that member's table entry.
 #include "trx_sch_common.h"
 #include "trx_launch.h"
 #include "trx_ms_sched.h"
@@ -93,15 +95,14 @@ __device__ __forceinline__ const char *ms_slot_src(const void *iq, size_t slot_s
 	return reinterpret_cast<const char *>(iq) + (size_t)b * slot_stride * (I16 ? 4 : 8);
 }
 
+// The receiver of one wave: the VA_BPW slots from q0 on, of n_slots.  wave: the wave's index in its block (its LDS slice)
 template <bool I16, bool STREAM>
-__global__ void __launch_bounds__(SS_WPB * WAVE)
-ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_slot *__restrict__ slots,
-	     trxhip_ms_burst_ind *__restrict__ ind, int8_t *__restrict__ bits, unsigned n_slots, float scale, float rx_full_scale,
-	     const trx_mss_stream sa)
+__device__ __forceinline__ void ms_rx_wave(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_slot *__restrict__ slots,
+					   trxhip_ms_burst_ind *__restrict__ ind, int8_t *__restrict__ bits, unsigned n_slots, float scale,
+					   float rx_full_scale, const trx_mss_stream &sa, const int wave, const unsigned q0)
 {
 	__shared__ __attribute__((aligned(16))) char smem[SS_WPB * MS_SLICE_BYTES];
 	const int lane = threadIdx.x & (WAVE - 1);
-	const int wave = uni((int)(threadIdx.x >> 6));
 	char *base = smem + wave * MS_SLICE_BYTES;
 	c32 *xs = reinterpret_cast<c32 *>(base);                       // polyphase: local sample j at xs[(j & 3) * SS_XA + (j >> 2)]
 	c32 *corr = xs + 4 * SS_XA;
@@ -115,7 +116,6 @@ ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_sl
 	int4 *info = reinterpret_cast<int4 *>(base + SS_SLICE_BYTES);
 	uint4 *words = reinterpret_cast<uint4 *>(xs);                  // 148 x 16 bytes over the head of xs[]
 
-	const unsigned q0 = (blockIdx.x * SS_WPB + wave) * VA_BPW;     // first slot of this wave
 	if (q0 >= n_slots)
 		return;
 
@@ -290,6 +290,43 @@ ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_sl
 	}
 }
 
+template <bool I16, bool STREAM>
+__global__ void __launch_bounds__(SS_WPB * WAVE)
+ms_rx_kernel(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_slot *__restrict__ slots,
+	     trxhip_ms_burst_ind *__restrict__ ind, int8_t *__restrict__ bits, unsigned n_slots, float scale, float rx_full_scale,
+	     const trx_mss_stream sa)
+{
+	const int wave = uni((int)(threadIdx.x >> 6));
+	const unsigned q0 = (blockIdx.x * SS_WPB + wave) * VA_BPW;     // first slot of this wave
+	ms_rx_wave<I16, STREAM>(iq, slot_stride, slots, ind, bits, n_slots, scale, rx_full_scale, sa, wave, q0);
+}
+
+// THE GROUP FORM (trxhip_ms_group_*): the pulls of many streams in one launch.  A wave's four slots belong to one member: the wave
+// finds its entry in the table by its first wave (wave-uniform loads), and from there on it is the stream form on that member's
+// chunk, descriptor and outputs.  A member's last wave has idle rows, as the batch tail has.
+template <bool I16>
+__global__ void __launch_bounds__(SS_WPB * WAVE)
+ms_rx_group_kernel(const trx_mss_member *__restrict__ tab, unsigned n_entries, unsigned n_waves, float scale, float rx_full_scale)
+{
+	const int wave = uni((int)(threadIdx.x >> 6));
+	const unsigned gw = blockIdx.x * SS_WPB + wave;
+	if (gw >= n_waves)
+		return;
+	unsigned lo = 0, hi = n_entries;                               // tab[lo].first_wave <= gw < tab[hi].first_wave
+	while (hi - lo > 1) {
+		const unsigned mid = (lo + hi) >> 1;
+		if (tab[mid].first_wave <= gw)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	const trx_mss_member *e = tab + lo;
+	const trx_mss_stream sa = e->sa;
+	const unsigned n_slots = e->n_slots;
+	const unsigned q0 = (gw - e->first_wave) * VA_BPW;
+	ms_rx_wave<I16, true>(e->chunk, (size_t)MS_SLOT, nullptr, e->ind, e->bits, n_slots, scale, rx_full_scale, sa, wave, q0);
+}
+
 extern "C" int trx_launch_ms_rx(const void *d_iq, int i16, size_t slot_stride, const trxhip_ms_slot *d_slots, trxhip_ms_burst_ind *d_ind,
 				int8_t *d_bits, size_t n_slots, float scale, float rx_full_scale, hipStream_t stream)
 {
@@ -323,3 +360,23 @@ extern "C" int trx_launch_ms_rx_stream(const void *d_chunk, int i16, const trx_m
 				   nullptr, d_ind, d_bits, (unsigned)n_slots, scale, rx_full_scale, *sa);
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
+
+// the group form: n_waves waves over the n_entries members of d_tab (trx_ms_sched.h)
+extern "C" int trx_launch_ms_rx_group(const trx_mss_member *d_tab, int i16, size_t n_entries, size_t n_waves, float scale, float rx_full_scale,
+				      hipStream_t stream)
+{
+	if (n_entries == 0 || n_waves == 0)
+		return 0;
+	if (n_entries > n_waves || n_waves > 0x7fffffffu)
+		return TRXHIP_EINVAL;
+	const size_t grid = (n_waves + SS_WPB - 1) / SS_WPB;
+	if (i16)
+		hipLaunchKernelGGL((ms_rx_group_kernel<true>), dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_tab, (unsigned)n_entries,
+				   (unsigned)n_waves, scale, rx_full_scale);
+	else
+		hipLaunchKernelGGL((ms_rx_group_kernel<false>), dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_tab, (unsigned)n_entries,
+				   (unsigned)n_waves, scale, rx_full_scale);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+static_assert(TRX_MS_RX_SLOTS_PER_WAVE == VA_BPW, "slots per wave");
+static_assert(sizeof(trx_mss_member) == 64, "table entry");

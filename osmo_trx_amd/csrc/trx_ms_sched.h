@@ -70,3 +70,26 @@ struct trx_mss_stream {
 	uint32_t    fn0;
 	uint8_t     tn0, tsc, active, reserved;
 };
+
+/* The group form of ms_rx_kernel (trxhip_ms_group_*): a table of the members that have receiver work in this launch, in the order
+ * of their waves.  A wave's VA_BPW slots belong to one member: wave w serves the entry with the largest first_wave <= w, whose
+ * slots (w - first_wave) * VA_BPW .. are the stream form's with this entry's chunk, descriptor and outputs.  first_wave rises
+ * strictly from 0; an entry has n_slots >= 1.  64 bytes */
+struct trx_mss_member {
+	const void            *chunk;      /* the member's chunk of this pull */
+	trx_mss_stream         sa;         /* sa.corr: the member's own word of the group's correction words, or NULL */
+	trxhip_ms_burst_ind   *ind;        /* where the entry's slot 0 goes */
+	int8_t                *bits;       /* the same for the sbits, or NULL */
+	uint32_t               n_slots;
+	uint32_t               first_wave;
+};
+
+/* One block of ms_join_group_kernel: ms_join_kernel's arguments for one member.  64 bytes */
+struct trx_mss_join {
+	const void *in, *rem_in;
+	void       *rem_out, *edge_row;
+	uint64_t    tail_at;
+	uint32_t    carried, keep, n_tail;
+	int32_t     do_edge;
+	uint64_t    reserved;
+};

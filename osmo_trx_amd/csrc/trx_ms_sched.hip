@@ -13,6 +13,11 @@
 // is summed on the device into one word that starts at zero and is copied to a pinned mailbox behind the launch; the host adds
 // it to temp_ts_corr_offset when the next pull plans.
 // With ctx == NULL the object is plan-only: cutter, clock and plan, no device memory; SCH starts come from a queue.
+// A pull is written in two steps that the single object and the group (trxhip_ms_group_*) share: the plan of one member
+// (plan_begin / plan_finish: integers only, nothing moves) and the issue; commit() then moves the member's state.  The group
+// issues the pulls of all its members as one table (trx_ms_sched.h), one ms_join_group_kernel, one clear of the correction
+// words, one group launch of the receiver (trx_ms_rx.hip), one copy of the correction words, one event -- and at most the same
+// two waits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -29,6 +34,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr size_t kMaxSamples = (size_t)1 << 40;
+constexpr int kTabSlots = 4;                   /* pinned table areas of a group: the host runs at most this many launch sets ahead */
 
 // ------------------------------------------------------------------------------------------------
 // ms_join_kernel: one block.  The stream of a pull is the carried partial slot (rem_in, `carried` samples) followed by the chunk.
@@ -38,9 +44,8 @@ constexpr size_t kMaxSamples = (size_t)1 << 40;
 // T: one IQ sample (uint32_t: int16 pair; float2).  carried + (625 - carried) <= 625, keep + n_tail < 625.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ void __launch_bounds__(kThreads)
-ms_join_kernel(const T *__restrict__ in, const T *__restrict__ rem_in, T *__restrict__ rem_out, T *__restrict__ edge_row,
-	       uint32_t carried, int do_edge, uint32_t keep, size_t tail_at, uint32_t n_tail)
+__device__ __forceinline__ void ms_join(const T *__restrict__ in, const T *__restrict__ rem_in, T *__restrict__ rem_out, T *__restrict__ edge_row,
+					uint32_t carried, int do_edge, uint32_t keep, size_t tail_at, uint32_t n_tail)
 {
 	if (do_edge)
 		for (uint32_t i = threadIdx.x; i < TRX_MSS_SLOT; i += kThreads)
@@ -51,10 +56,28 @@ ms_join_kernel(const T *__restrict__ in, const T *__restrict__ rem_in, T *__rest
 		rem_out[keep + i] = in[tail_at + i];
 }
 
-}  // namespace
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+ms_join_kernel(const T *__restrict__ in, const T *__restrict__ rem_in, T *__restrict__ rem_out, T *__restrict__ edge_row,
+	       uint32_t carried, int do_edge, uint32_t keep, size_t tail_at, uint32_t n_tail)
+{
+	ms_join<T>(in, rem_in, rem_out, edge_row, carried, do_edge, keep, tail_at, n_tail);
+}
 
-struct trxhip_ms_sched {
-	trxhip_ctx *ctx = nullptr;
+// ms_join_group_kernel: one block per member of a group pull that needs a join, its arguments from the table
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+ms_join_group_kernel(const trx_mss_join *__restrict__ tab)
+{
+	const trx_mss_join j = tab[blockIdx.x];
+	ms_join<T>(static_cast<const T *>(j.in), static_cast<const T *>(j.rem_in), static_cast<T *>(j.rem_out), static_cast<T *>(j.edge_row),
+		   j.carried, j.do_edge, j.keep, (size_t)j.tail_at, j.n_tail);
+}
+
+static_assert(sizeof(trx_mss_join) == 64 && sizeof(trx_mss_member) == 64, "table entries");
+
+// One downlink stream on the host: what a single object is apart from its device memory, and what a group holds per member
+struct ms_member {
 	float rx_full_scale = 0.0f;
 	uint8_t tsc = 0, active = 0;
 	bool tracking = false;
@@ -67,7 +90,7 @@ struct trxhip_ms_sched {
 	uint32_t carried = 0;                  /* partial_rdofs */
 	int carried_cf32 = 0;                  /* its format */
 	int64_t pending = 0;                   /* temp_ts_corr_offset, without what `unread` says is still on its way */
-	bool unread = false;                   /* a launch with SCH slots was issued: its sum arrives in *h_corr behind ev_corr */
+	bool unread = false;                   /* a launch with SCH slots was issued: its sum arrives in the mailbox behind ev_corr */
 	int64_t to_skip_last = 0;
 	uint64_t clock_jumps = 0, pulls = 0, slots = 0, sch_slots = 0;
 	// the last pull, for trxhip_ms_sched_plan()
@@ -83,14 +106,64 @@ struct trxhip_ms_sched {
 	// plan-only: the SCH starts fed from outside
 	std::vector<int32_t> feed;
 	size_t feed_at = 0;
+	int rem_half = 0;                      /* device: the half of the partial-slot area the next pull reads */
+};
+
+// The plan of one member's pull.  plan_begin() fills the first part, plan_finish() the second; neither moves the member.
+struct ms_plan {
+	int cf32 = 0;
+	size_t n_samples = 0;
+	int64_t first_ts = 0;
+	bool extend = false;                   /* the chunk only extends the partial slot (:385-391): nothing else is planned */
+	bool straddle = false;
+	bool prelim = false;                   /* the straddling slot is an SCH slot the cutter follows: it is demodulated first */
+	uint32_t carried = 0;
+	uint32_t fn = 0, fnb = 0;              /* (fn, tn): the clock behind the first call's steps and the straddling slot; */
+	int tn = 0, tnb = 0;                   /* (fnb, tnb): in front of the straddling slot */
+	int64_t ts = 0, to_skip = 0;
+	uint64_t jumps = 0;
+	// plan_finish()
+	bool waited = false;                   /* the straddling slot's indication is written already */
+	int64_t pending = 0, full = 0, frac = 0, cnt = 0;
+	uint32_t fn0 = 0;                      /* the clock of slot 0 */
+	int tn0 = 0;
+	uint64_t sch_full = 0, sch_all = 0;
+	size_t feed_at = 0;
+};
+
+}  // namespace
+
+struct trxhip_ms_sched : ms_member {
+	trxhip_ctx *ctx = nullptr;
 	// device state (ctx != NULL)
 	void *d_rem = nullptr;                 /* [2][TRX_MSS_REM_STRIDE] samples of either format */
 	void *d_edge_row = nullptr;            /* 625 samples of either format */
 	int32_t *d_corr = nullptr, *h_corr = nullptr;
 	trxhip_sch_sync_result *d_acq = nullptr, *h_acq = nullptr;
-	int rem_half = 0;                      /* the half the next pull reads */
 	hipEvent_t ev_corr = nullptr, ev = nullptr;
 	bool ev_used = false;
+};
+
+struct trxhip_ms_group {
+	trxhip_ctx *ctx = nullptr;
+	float rx_full_scale = 0.0f;
+	std::vector<ms_member> m;
+	std::vector<ms_plan> plan;             /* scratch of a pull */
+	std::vector<int> rc;
+	// device state (ctx != NULL)
+	char *d_rem = nullptr;                 /* [n][2][TRX_MSS_REM_STRIDE] samples of either format */
+	char *d_edge = nullptr;                /* [n][625] samples of either format */
+	int32_t *d_corr = nullptr, *h_corr = nullptr;      /* [n] correction words and their pinned mailbox */
+	trxhip_sch_sync_result *d_acq = nullptr, *h_acq = nullptr;   /* [n] */
+	// the table of a launch set: up to n receiver entries followed by up to n join entries, 64 bytes each.  It is staged in one of
+	// kTabSlots pinned areas taken in turn.  A launch set records ONE event, its area's, behind everything it issues: the area is
+	// written again only behind that event, and where the set sums corrections the same event says that the mailbox holds them
+	char *d_tab = nullptr, *h_tab = nullptr;
+	hipEvent_t ev_tab[kTabSlots] = {};
+	bool tab_used[kTabSlots] = {};
+	int tab_at = 0;                        /* the area the next launch set takes */
+	int corr_at = 0;                       /* the area of the last launch set that summed corrections */
+	hipEvent_t ev = nullptr;               /* acquire's */
 };
 
 namespace {
@@ -106,6 +179,24 @@ int fold_correction(trxhip_ms_sched *s)
 		return TRXHIP_EIO;
 	s->pending += *s->h_corr;
 	s->unread = false;
+	return TRXHIP_OK;
+}
+
+// the same for a group: one wait, and every member's word
+int fold_correction(trxhip_ms_group *g)
+{
+	bool any = false;
+	for (const ms_member &m : g->m)
+		any = any || m.unread;
+	if (!any)
+		return TRXHIP_OK;
+	if (with_device(g->ctx) || hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess)
+		return TRXHIP_EIO;
+	for (size_t i = 0; i < g->m.size(); i++)
+		if (g->m[i].unread) {
+			g->m[i].pending += g->h_corr[i];
+			g->m[i].unread = false;
+		}
 	return TRXHIP_OK;
 }
 
@@ -155,109 +246,97 @@ int launch_rx(trxhip_ms_sched *s, const void *d_in, int cf32, bool edge, int64_t
 }
 
 // plan-only: the next fed start as handle_sch(false) would add it (:199-203)
-int64_t fed_correction(const trxhip_ms_sched *s, size_t &at)
+int64_t fed_correction(const ms_member &m, size_t &at)
 {
-	if (at >= s->feed.size())
+	if (at >= m.feed.size())
 		return 0;
-	const int32_t start = s->feed[at++];
+	const int32_t start = m.feed[at++];
 	if (start == TRXHIP_MS_SCHED_NO_SCH || (start <= 1 && start >= -1))
 		return 0;
 	return -(int64_t)start;
 }
 
-int pull(trxhip_ms_sched *s, const void *d_in, int cf32, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
-	 size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
+// ------------------------------------------------------------------------------------------------
+// The plan of one member's pull, in two steps around the second of the two waits.
+// plan_begin: what the single object refuses before it launches anything; the chunk that only extends the partial slot; the
+//   first call after an acquire (:362-383); the straddling slot's clock (:385-396), and whether that slot has to be demodulated
+//   before the rest can be planned.  device: the object has buffers (else it takes none); bounded: out_slots limits the count
+// ------------------------------------------------------------------------------------------------
+int plan_begin(const ms_member &m, bool device, bool bounded, int cf32, size_t n_samples, int64_t first_ts, const void *d_in, const void *d_ind,
+	       const void *d_bits, size_t out_slots, ms_plan &p)
 {
-	if (!s || !s->clock_set || n_samples == 0 || n_samples > kMaxSamples)
+	if (!m.clock_set || n_samples == 0 || n_samples > kMaxSamples)
 		return TRXHIP_EINVAL;
-	if (s->carried && cf32 != s->carried_cf32)
+	if (m.carried && cf32 != m.carried_cf32)
 		return TRXHIP_EINVAL;
-	if (s->ctx) {
+	if (device) {
 		if (!d_in || (reinterpret_cast<uintptr_t>(d_in) & (cf32 ? 7 : 3)) || !d_ind || (reinterpret_cast<uintptr_t>(d_ind) & 3))
 			return TRXHIP_EINVAL;
-		if (with_device(s->ctx))
-			return TRXHIP_EIO;
 	} else if (d_in || d_ind || d_bits) {
 		return TRXHIP_EINVAL;                                  /* a plan-only object takes no buffers */
 	}
-	const hipStream_t st = static_cast<hipStream_t>(stream);
-	const int64_t n = (int64_t)n_samples;
-	uint32_t fn = s->fn;
-	int tn = s->tn;
-	int64_t ts = s->ts;
-	size_t feed_at = s->feed_at;
-	uint64_t jumps = 0;
-
+	p = ms_plan();
+	p.cf32 = cf32;
+	p.n_samples = n_samples;
+	p.first_ts = first_ts;
+	p.fn = m.fn;
+	p.tn = m.tn;
+	p.ts = m.ts;
 	// partial burst samples read from the last buffer: a chunk shorter than the missing part only extends them (:385-391)
-	if (!s->first_call && s->carried && n_samples < TRX_MSS_SLOT - s->carried) {
-		if (s->ctx) {
-			if (launch_join(s, d_in, cf32, 0, s->carried, 0, (uint32_t)n_samples, st) != TRXHIP_OK ||
-			    hipEventRecord(s->ev, st) != hipSuccess)
-				return TRXHIP_EIO;
-			s->ev_used = true;
-			s->rem_half ^= 1;
-		}
-		s->carried += (uint32_t)n_samples;
-		s->carried_cf32 = cf32;
-		s->last.n = 0;
-		s->pulls++;
-		if (n_slots)
-			*n_slots = 0;
-		if (n_carried)
-			*n_carried = s->carried;
+	if (!m.first_call && m.carried && n_samples < TRX_MSS_SLOT - m.carried) {
+		p.extend = true;
 		return TRXHIP_OK;
 	}
-
-	// the correction of the pull before: the first of the two waits
-	if (s->tracking && fold_correction(s) != TRXHIP_OK)
-		return TRXHIP_EIO;
-	int64_t pending = s->pending;
-	int64_t to_skip = 0;
-
 	// round up to next burst by calculating the time between sch detection and now (:362-383)
-	if (s->first_call) {
-		const int64_t next_burst_start = first_ts - s->first_sch_ts_start;
+	if (m.first_call) {
+		const int64_t next_burst_start = first_ts - m.first_sch_ts_start;
 		const int64_t fullts = next_burst_start / TRX_MSS_SLOT, fracts = next_burst_start % TRX_MSS_SLOT;
-		to_skip = TRX_MSS_SLOT - fracts;
+		p.to_skip = TRX_MSS_SLOT - fracts;
 		/* fullts inc_and_update() (none when fullts <= 0), inc_both() when fracts, dec_by_one(): TNs on the clock; the final
 		 * set() keeps the clock and overwrites every timestamp the steps left */
 		int64_t steps = (fullts > 0 ? fullts : 0) + (fracts ? 1 : 0) - 1;
 		const int64_t period = (int64_t)TRX_MSS_HYPERFRAME * 8;
 		steps = ((steps % period) + period) % period;
-		trx_mss_clock_add(fn, tn, (uint64_t)steps, &fn, &tn);
-		ts = first_ts - TRX_MSS_SLOT + to_skip;
+		trx_mss_clock_add(p.fn, p.tn, (uint64_t)steps, &p.fn, &p.tn);
+		p.ts = first_ts - TRX_MSS_SLOT + p.to_skip;
 	}
-
-	const uint32_t carried = s->first_call ? 0u : s->carried;      /* (an acquire drops the partial slot) */
-	const bool straddle = carried != 0;
-	const uint32_t fnb = fn;                                       /* slot k of the pull: k + 1 incTN() behind (fnb, tnb) */
-	const int tnb = tn;
-	bool waited = false;
-	if (straddle) {
-		if (s->ctx && out_slots < 1)
+	p.carried = m.first_call ? 0u : m.carried;                     /* (an acquire drops the partial slot) */
+	p.straddle = p.carried != 0;
+	p.fnb = p.fn;                                                  /* slot k of the pull: k + 1 incTN() behind (fnb, tnb) */
+	p.tnb = p.tn;
+	if (p.straddle) {
+		if (bounded && out_slots < 1)
 			return TRXHIP_EINVAL;
-		jumps += jump(first_ts - carried - ts);                    /* inc_and_update_safe(first_ts - partial_rdofs), :393 */
-		trx_mss_clock_add(fn, tn, 1, &fn, &tn);
-		ts = first_ts - carried;
+		p.jumps += jump(first_ts - p.carried - p.ts);              /* inc_and_update_safe(first_ts - partial_rdofs), :393 */
+		trx_mss_clock_add(p.fn, p.tn, 1, &p.fn, &p.tn);
+		p.ts = first_ts - p.carried;
 		// handle_sch_or_nb() on the completed slot comes before the correction is applied (:394, :399): where it is an SCH slot
 		// the cutter follows, this slot alone is demodulated first -- the second of the two waits
-		if (s->tracking && trx_mss_is_sch(fn, tn)) {
-			if (s->ctx) {
-				if (launch_join(s, d_in, cf32, 1, 0, 0, 0, st) != TRXHIP_OK ||
-				    launch_rx(s, d_in, cf32, true, 0, fn, tn, d_ind, d_bits, 1, true, st) != TRXHIP_OK ||
-				    hipEventSynchronize(s->ev_corr) != hipSuccess)
-					return TRXHIP_EIO;
-				pending += *s->h_corr;
-				waited = true;
-			} else {
-				pending += fed_correction(s, feed_at);
-			}
-		}
-		to_skip = TRX_MSS_SLOT - carried;
+		p.prelim = m.tracking && trx_mss_is_sch(p.fn, p.tn);
+		p.to_skip = TRX_MSS_SLOT - p.carried;
 	}
+	return TRXHIP_OK;
+}
 
+// plan_finish: the correction (:398-406), the slots in the chunk (:408-421), the counts, the clocks.  The member's correction in
+// flight has been folded.  prelim_corr: what the straddling SCH slot summed (device objects with p.prelim); a plan-only object
+// takes it, and those of the slots in the chunk, from its queue
+int plan_finish(const ms_member &m, bool device, bool bounded, size_t out_slots, int64_t prelim_corr, ms_plan &p)
+{
+	const int64_t n = (int64_t)p.n_samples;
+	int64_t pending = m.pending;
+	size_t feed_at = m.feed_at;
+	if (p.prelim) {
+		if (device) {
+			pending += prelim_corr;
+			p.waited = true;
+		} else {
+			pending += fed_correction(m, feed_at);
+		}
+	}
 	// apply sample rate slippage compensation (:398-406); with tracking off nothing moves the cut and the value stays
-	if (s->tracking) {
+	int64_t to_skip = p.to_skip;
+	if (m.tracking) {
 		to_skip -= pending;
 		if (to_skip < 0)
 			to_skip = 0;
@@ -268,78 +347,160 @@ int pull(trxhip_ms_sched *s, const void *d_in, int cf32, size_t n_samples, int64
 		return TRXHIP_EINVAL;
 	const int64_t left_after_burst = n - to_skip;
 	const int64_t full = left_after_burst / TRX_MSS_SLOT, frac = left_after_burst % TRX_MSS_SLOT;
-	const int64_t cnt = full + (straddle ? 1 : 0);
-	if (cnt > 0x7fffffff || (s->ctx && (uint64_t)cnt > out_slots))
+	const int64_t cnt = full + (p.straddle ? 1 : 0);
+	if (cnt > 0x7fffffff || (bounded && (uint64_t)cnt > out_slots))
 		return TRXHIP_EINVAL;
 
-	uint32_t fn_full, fn0;                                         /* the clocks of the first slot in the chunk and of slot 0 */
-	int tn_full, tn0;
-	trx_mss_clock_add(fn, tn, 1, &fn_full, &tn_full);
-	trx_mss_clock_add(fnb, tnb, 1, &fn0, &tn0);
-	const uint64_t sch_full = full ? trx_mss_count_sch(fn_full, tn_full, (uint64_t)full) : 0;
-	const uint64_t sch_all = cnt ? trx_mss_count_sch(fn0, tn0, (uint64_t)cnt) : 0;
+	uint32_t fn_full;                                              /* the clock of the first slot in the chunk */
+	int tn_full;
+	trx_mss_clock_add(p.fn, p.tn, 1, &fn_full, &tn_full);
+	trx_mss_clock_add(p.fnb, p.tnb, 1, &p.fn0, &p.tn0);
+	p.sch_full = full ? trx_mss_count_sch(fn_full, tn_full, (uint64_t)full) : 0;
+	p.sch_all = cnt ? trx_mss_count_sch(p.fn0, p.tn0, (uint64_t)cnt) : 0;
+	if (!device && m.tracking)
+		for (uint64_t i = 0; i < p.sch_full; i++)
+			pending += fed_correction(m, feed_at);
 
-	if (s->ctx) {
-		int rc = TRXHIP_OK;
-		const bool edge = straddle && !waited;
-		if (edge || frac)
-			rc = launch_join(s, d_in, cf32, edge, 0, (size_t)(to_skip + full * TRX_MSS_SLOT), (uint32_t)frac, st);
-		const size_t k0 = waited ? 1 : 0;
-		const bool sum = s->tracking && sch_full != 0;
-		if (rc == TRXHIP_OK && (size_t)cnt > k0) {
+	// the slots in the chunk: inc_and_update_safe(first_ts + to_skip + i * 625), :413-417
+	if (full) {
+		p.jumps += jump(p.first_ts + to_skip - p.ts);
+		trx_mss_clock_add(p.fn, p.tn, (uint64_t)full, &p.fn, &p.tn);
+		p.ts = p.first_ts + to_skip + (full - 1) * TRX_MSS_SLOT;
+	}
+	p.to_skip = to_skip;
+	p.pending = pending;
+	p.full = full;
+	p.frac = frac;
+	p.cnt = cnt;
+	p.feed_at = feed_at;
+	return TRXHIP_OK;
+}
+
+// the issued pull becomes the member's state
+void commit(ms_member &m, const ms_plan &p)
+{
+	if (p.extend) {
+		m.carried += (uint32_t)p.n_samples;
+		m.carried_cf32 = p.cf32;
+		m.last.n = 0;
+		m.pulls++;
+		return;
+	}
+	m.last.fn0 = p.fn0;
+	m.last.tn0 = p.tn0;
+	m.last.n = (size_t)p.cnt;
+	m.last.straddle = p.straddle;
+	m.last.carried = p.carried;
+	m.last.to_skip = p.to_skip;
+	m.last.first_ts = p.first_ts;
+	m.last.tsc = m.tsc;
+	m.last.active = m.active;
+	m.fn = p.fn;
+	m.tn = p.tn;
+	m.ts = p.ts;
+	m.first_call = false;
+	m.carried = (uint32_t)p.frac;
+	m.carried_cf32 = p.cf32;
+	m.pending = p.pending;
+	m.feed_at = p.feed_at;
+	m.to_skip_last = p.to_skip;
+	m.clock_jumps += p.jumps;
+	m.pulls++;
+	m.slots += (uint64_t)p.cnt;
+	m.sch_slots += p.sch_all;
+}
+
+int pull(trxhip_ms_sched *s, const void *d_in, int cf32, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+	 size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
+{
+	if (!s)
+		return TRXHIP_EINVAL;
+	const bool device = s->ctx != nullptr;
+	ms_plan p;
+	int rc = plan_begin(*s, device, device, cf32, n_samples, first_ts, d_in, d_ind, d_bits, out_slots, p);
+	if (rc != TRXHIP_OK)
+		return rc;
+	if (device && with_device(s->ctx))
+		return TRXHIP_EIO;
+	const hipStream_t st = static_cast<hipStream_t>(stream);
+
+	if (p.extend) {
+		if (device) {
+			if (launch_join(s, d_in, cf32, 0, s->carried, 0, (uint32_t)n_samples, st) != TRXHIP_OK ||
+			    hipEventRecord(s->ev, st) != hipSuccess)
+				return TRXHIP_EIO;
+			s->ev_used = true;
+			s->rem_half ^= 1;
+		}
+		commit(*s, p);
+		if (n_slots)
+			*n_slots = 0;
+		if (n_carried)
+			*n_carried = s->carried;
+		return TRXHIP_OK;
+	}
+
+	// the correction of the pull before: the first of the two waits
+	if (s->tracking && fold_correction(s) != TRXHIP_OK)
+		return TRXHIP_EIO;
+	// the straddling SCH slot alone: the second
+	int64_t prelim_corr = 0;
+	if (p.prelim && device) {
+		if (launch_join(s, d_in, cf32, 1, 0, 0, 0, st) != TRXHIP_OK ||
+		    launch_rx(s, d_in, cf32, true, 0, p.fn, p.tn, d_ind, d_bits, 1, true, st) != TRXHIP_OK ||
+		    hipEventSynchronize(s->ev_corr) != hipSuccess)
+			return TRXHIP_EIO;
+		prelim_corr = *s->h_corr;
+	}
+	rc = plan_finish(*s, device, device, out_slots, prelim_corr, p);
+	if (rc != TRXHIP_OK)
+		return rc;
+
+	if (device) {
+		rc = TRXHIP_OK;
+		const bool edge = p.straddle && !p.waited;
+		if (edge || p.frac)
+			rc = launch_join(s, d_in, cf32, edge, 0, (size_t)(p.to_skip + p.full * TRX_MSS_SLOT), (uint32_t)p.frac, st);
+		const size_t k0 = p.waited ? 1 : 0;
+		const bool sum = s->tracking && p.sch_full != 0;
+		if (rc == TRXHIP_OK && (size_t)p.cnt > k0) {
 			uint32_t fnk;
 			int tnk;
-			trx_mss_clock_add(fn0, tn0, k0, &fnk, &tnk);
-			rc = launch_rx(s, d_in, cf32, edge, to_skip, fnk, tnk, d_ind + k0, d_bits ? d_bits + k0 * 148 : nullptr, (size_t)cnt - k0, sum,
-				       st);
+			trx_mss_clock_add(p.fn0, p.tn0, k0, &fnk, &tnk);
+			rc = launch_rx(s, d_in, cf32, edge, p.to_skip, fnk, tnk, d_ind + k0, d_bits ? d_bits + k0 * 148 : nullptr, (size_t)p.cnt - k0,
+				       sum, st);
 		}
 		if (rc == TRXHIP_OK && hipEventRecord(s->ev, st) != hipSuccess)
 			rc = TRXHIP_EIO;
 		if (rc != TRXHIP_OK)
 			return TRXHIP_EIO;
 		s->ev_used = true;
-		if (frac)
+		if (p.frac)
 			s->rem_half ^= 1;
 		if (sum)
 			s->unread = true;
-	} else if (s->tracking) {
-		for (uint64_t i = 0; i < sch_full; i++)
-			pending += fed_correction(s, feed_at);
 	}
-
-	// the slots in the chunk: inc_and_update_safe(first_ts + to_skip + i * 625), :413-417
-	if (full) {
-		jumps += jump(first_ts + to_skip - ts);
-		trx_mss_clock_add(fn, tn, (uint64_t)full, &fn, &tn);
-		ts = first_ts + to_skip + (full - 1) * TRX_MSS_SLOT;
-	}
-	s->last.fn0 = fn0;
-	s->last.tn0 = tn0;
-	s->last.n = (size_t)cnt;
-	s->last.straddle = straddle;
-	s->last.carried = carried;
-	s->last.to_skip = to_skip;
-	s->last.first_ts = first_ts;
-	s->last.tsc = s->tsc;
-	s->last.active = s->active;
-	s->fn = fn;
-	s->tn = tn;
-	s->ts = ts;
-	s->first_call = false;
-	s->carried = (uint32_t)frac;
-	s->carried_cf32 = cf32;
-	s->pending = pending;
-	s->feed_at = feed_at;
-	s->to_skip_last = to_skip;
-	s->clock_jumps += jumps;
-	s->pulls++;
-	s->slots += (uint64_t)cnt;
-	s->sch_slots += sch_all;
+	commit(*s, p);
 	if (n_slots)
-		*n_slots = (size_t)cnt;
+		*n_slots = (size_t)p.cnt;
 	if (n_carried)
-		*n_carried = (size_t)frac;
+		*n_carried = (size_t)p.frac;
 	return TRXHIP_OK;
+}
+
+// what a found SCH burst sets (handle_sch(true), decode_sch(bits, true))
+void acquired(ms_member &m, const trxhip_sch_sync_result &r, int64_t first_ts)
+{
+	m.fn = (uint32_t)r.fn;                                         /* timekeeper.set(fn, 0): GSM::Time(fn), ts 0 (:91) */
+	m.tn = 0;
+	m.ts = 0;
+	m.tsc = (uint8_t)(r.bsic & 7);                                 /* mTSC = sch.bsic & 0x7 (:90) */
+	m.first_sch_ts_start = first_ts + r.start - 4 * 4 - 1;         /* :198 */
+	m.clock_set = true;
+	m.first_call = true;
+	m.carried = 0;
+	m.pending = 0;
+	m.unread = false;
 }
 
 int acquire(trxhip_ms_sched *s, const void *d_buf, int cf32, size_t n_samples, int64_t first_ts, trxhip_sch_sync_result *h_res, void *stream)
@@ -374,18 +535,394 @@ int acquire(trxhip_ms_sched *s, const void *d_buf, int cf32, size_t n_samples, i
 		return 0;
 	if (r.fn < 0 || (uint32_t)r.fn >= TRX_MSS_HYPERFRAME)
 		return TRXHIP_EINVAL;
-	s->fn = (uint32_t)r.fn;                                        /* timekeeper.set(fn, 0): GSM::Time(fn), ts 0 (:91) */
-	s->tn = 0;
-	s->ts = 0;
-	s->tsc = (uint8_t)(r.bsic & 7);                                /* mTSC = sch.bsic & 0x7 (:90) */
-	s->first_sch_ts_start = first_ts + r.start - 4 * 4 - 1;        /* :198 */
-	s->clock_set = true;
-	s->first_call = true;
-	s->carried = 0;
-	s->pending = 0;
-	s->unread = false;
+	acquired(*s, r, first_ts);
 	return 1;
 }
+
+void set_clock(ms_member &m, uint32_t fn, int tn, int64_t ts)
+{
+	m.fn = fn;
+	m.tn = tn;
+	m.ts = ts;
+	m.clock_set = true;
+	m.first_call = false;
+	m.carried = 0;
+	m.pending = 0;
+	m.unread = false;
+}
+
+int64_t slots_of(const ms_member &m, size_t n_samples)
+{
+	if (n_samples > kMaxSamples)
+		return TRXHIP_EINVAL;
+	const uint32_t carried = m.first_call ? 0u : m.carried;
+	const int64_t bound = (int64_t)((carried + n_samples) / TRX_MSS_SLOT) + 1;
+	if (m.first_call)
+		return bound;
+	const bool straddle = carried && n_samples >= TRX_MSS_SLOT - carried;
+	if (m.tracking) {
+		uint32_t fn;
+		int tn;
+		trx_mss_clock_add(m.fn, m.tn, 1, &fn, &tn);
+		if (m.unread || m.pending || (straddle && trx_mss_is_sch(fn, tn)))
+			return bound;
+	}
+	if (!carried)
+		return (int64_t)(n_samples / TRX_MSS_SLOT);
+	return straddle ? 1 + (int64_t)((n_samples - (TRX_MSS_SLOT - carried)) / TRX_MSS_SLOT) : 0;
+}
+
+int plan_of(const ms_member &m, trxhip_ms_plan *h_out, size_t n)
+{
+	if ((!h_out && n) || n > m.last.n)
+		return TRXHIP_EINVAL;
+	for (size_t k = 0; k < n; k++) {
+		trxhip_ms_plan p;
+		memset(&p, 0, sizeof(p));
+		int tn;
+		trx_mss_clock_add(m.last.fn0, m.last.tn0, k, &p.fn, &tn);
+		p.tn = (uint8_t)tn;
+		p.kind = (uint8_t)trx_mss_kind(p.fn, tn, m.last.tsc);
+		p.flags = (uint8_t)(((m.last.active >> tn) & 1u) ? TRXHIP_MS_SLOT_ACTIVE : 0);
+		p.ts = (m.last.straddle && k == 0) ? m.last.first_ts - m.last.carried
+						   : m.last.first_ts + m.last.to_skip + (int64_t)(k - (m.last.straddle ? 1 : 0)) * TRX_MSS_SLOT;
+		p.src_off = (int32_t)(p.ts - m.last.first_ts);
+		h_out[k] = p;
+	}
+	return TRXHIP_OK;
+}
+
+void state_of(const ms_member &m, trxhip_ms_sched_status *out)
+{
+	memset(out, 0, sizeof(*out));
+	out->to_skip = m.to_skip_last;
+	out->pending = m.pending;
+	out->first_sch_ts_start = m.first_sch_ts_start;
+	out->carried = m.carried;
+	out->carried_cf32 = (uint8_t)m.carried_cf32;
+	out->first_call = m.first_call;
+	out->tracking = m.tracking;
+	out->tsc = m.tsc;
+	out->active_tns = m.active;
+	out->clock_set = m.clock_set;
+	out->clock_jumps = m.clock_jumps;
+	out->pulls = m.pulls;
+	out->slots = m.slots;
+	out->sch_slots = m.sch_slots;
+}
+
+bool cfg_ok(const trxhip_ms_sched_cfg *cfg) { return cfg->tsc <= 7 && std::isfinite(cfg->rx_full_scale) && cfg->rx_full_scale > 0.0f; }
+
+// ------------------------------------------------------------------------------------------------
+// The group: the pulls of its members issued as one.
+// ------------------------------------------------------------------------------------------------
+
+// a pinned area for the next table; it is free once the launch set that read it kTabSlots sets ago is through
+char *stage_table(trxhip_ms_group *g)
+{
+	const int h = g->tab_at;
+	if (g->tab_used[h] && hipEventSynchronize(g->ev_tab[h]) != hipSuccess)
+		return nullptr;
+	return g->h_tab + (size_t)h * 2 * g->m.size() * 64;
+}
+
+// one launch set of a group pull: the table's n_rx receiver entries and n_join join entries (staged behind one another in `tab`)
+// go up in one copy; one join launch; with sum one clear of the correction words, and their copy to the mailbox behind the
+// receiver launch; one event behind all of it
+int issue_table(trxhip_ms_group *g, char *tab, size_t n_rx, size_t n_join, size_t n_waves, int cf32, bool sum, hipStream_t st)
+{
+	if (n_rx + n_join == 0)
+		return TRXHIP_OK;                                      /* (no slot and no join: no sum either) */
+	if (hipMemcpyAsync(g->d_tab, tab, (n_rx + n_join) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
+		return TRXHIP_EIO;
+	if (n_join) {
+		const trx_mss_join *jt = reinterpret_cast<const trx_mss_join *>(g->d_tab + n_rx * 64);
+		if (cf32)
+			hipLaunchKernelGGL(ms_join_group_kernel<float2>, dim3((unsigned)n_join), dim3(kThreads), 0, st, jt);
+		else
+			hipLaunchKernelGGL(ms_join_group_kernel<uint32_t>, dim3((unsigned)n_join), dim3(kThreads), 0, st, jt);
+		if (launched() != TRXHIP_OK)
+			return TRXHIP_EIO;
+	}
+	const size_t corr_bytes = g->m.size() * sizeof(int32_t);
+	if (sum && hipMemsetAsync(g->d_corr, 0, corr_bytes, st) != hipSuccess)
+		return TRXHIP_EIO;
+	if (n_rx && trx_launch_ms_rx_group(reinterpret_cast<const trx_mss_member *>(g->d_tab), !cf32, n_rx, n_waves, 1.0f / g->rx_full_scale,
+					   g->rx_full_scale, st) != 0)
+		return TRXHIP_EIO;
+	if (sum && hipMemcpyAsync(g->h_corr, g->d_corr, corr_bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+		return TRXHIP_EIO;
+	const int h = g->tab_at;
+	if (hipEventRecord(g->ev_tab[h], st) != hipSuccess)
+		return TRXHIP_EIO;
+	g->tab_used[h] = true;
+	if (sum)
+		g->corr_at = h;
+	g->tab_at = (h + 1) % kTabSlots;
+	return TRXHIP_OK;
+}
+
+char *rem_of(trxhip_ms_group *g, size_t i, int half, int cf32)
+{
+	return g->d_rem + (i * 2 * TRX_MSS_REM_STRIDE) * 8 + (size_t)half * TRX_MSS_REM_STRIDE * (cf32 ? 8 : 4);
+}
+
+int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf32, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+	       size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream)
+{
+	if (bad_member)
+		*bad_member = -1;
+	if (!g || !h_chunks)
+		return TRXHIP_EINVAL;
+	const size_t n = g->m.size();
+	const bool device = g->ctx != nullptr;
+	const bool bounded = device || out_stride != 0;                /* a plan-only group checks the counts against a stride it is given */
+	size_t first = n;
+	for (size_t i = n; i-- > 0;)
+		if (h_chunks[i].n_samples)
+			first = i;
+	if (first == n)
+		return TRXHIP_EINVAL;                                  /* no member has a chunk */
+	if (device && with_device(g->ctx))
+		return TRXHIP_EIO;
+	const hipStream_t st = static_cast<hipStream_t>(stream);
+
+	// ---- every member's plan up to its straddling slot
+	int worst = TRXHIP_OK;
+	size_t bad = n;
+	auto refuse = [&](size_t i, int rc) {
+		g->rc[i] = rc;
+		if (i < bad) {
+			bad = i;
+			worst = rc;
+		}
+	};
+	bool any_tracked = false, any_prelim = false;
+	for (size_t i = 0; i < n; i++) {
+		g->rc[i] = TRXHIP_OK;
+		if (!h_chunks[i].n_samples)
+			continue;
+		const int rc = plan_begin(g->m[i], device, bounded, cf32, h_chunks[i].n_samples, h_chunks[i].first_ts, h_chunks[i].d_in,
+					  d_ind, d_bits, out_stride, g->plan[i]);     /* (a record is 32 bytes: d_ind's alignment is every row's) */
+		if (rc != TRXHIP_OK) {
+			refuse(i, rc);
+			continue;
+		}
+		if (!g->plan[i].extend) {
+			any_tracked = any_tracked || g->m[i].tracking;
+			any_prelim = any_prelim || g->plan[i].prelim;
+		}
+	}
+
+	// ---- the corrections of the pull before: the first of the two waits, once for the group
+	if (device && any_tracked && fold_correction(g) != TRXHIP_OK)
+		return TRXHIP_EIO;
+
+	// ---- the straddling SCH slots the cutters follow, one slot per member in one launch set: the second
+	if (device && any_prelim) {
+		char *tab = stage_table(g);
+		if (!tab)
+			return TRXHIP_EIO;
+		size_t n_pre = 0;
+		for (size_t i = 0; i < n; i++)
+			n_pre += h_chunks[i].n_samples && g->rc[i] == TRXHIP_OK && g->plan[i].prelim;
+		trx_mss_member *rx = reinterpret_cast<trx_mss_member *>(tab);
+		trx_mss_join *jn = reinterpret_cast<trx_mss_join *>(tab + n_pre * 64);
+		size_t k = 0;
+		for (size_t i = 0; i < n; i++) {
+			const ms_plan &p = g->plan[i];
+			if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK || !p.prelim)
+				continue;
+			char *edge = g->d_edge + i * TRX_MSS_SLOT * 8;
+			memset(&rx[k], 0, sizeof(rx[k]));
+			rx[k].chunk = h_chunks[i].d_in;
+			rx[k].sa.edge_row = edge;
+			rx[k].sa.corr = g->d_corr + i;
+			rx[k].sa.fn0 = p.fn;
+			rx[k].sa.tn0 = (uint8_t)p.tn;
+			rx[k].sa.tsc = g->m[i].tsc;
+			rx[k].sa.active = g->m[i].active;
+			rx[k].ind = d_ind + i * out_stride;
+			rx[k].bits = d_bits ? d_bits + i * out_stride * 148 : nullptr;
+			rx[k].n_slots = 1;
+			rx[k].first_wave = (uint32_t)k;
+			memset(&jn[k], 0, sizeof(jn[k]));
+			jn[k].in = h_chunks[i].d_in;
+			jn[k].rem_in = rem_of(g, i, g->m[i].rem_half, cf32);
+			jn[k].rem_out = rem_of(g, i, g->m[i].rem_half ^ 1, cf32);
+			jn[k].edge_row = edge;
+			jn[k].carried = p.carried;
+			jn[k].do_edge = 1;
+			k++;
+		}
+		if (issue_table(g, tab, n_pre, n_pre, n_pre, cf32, true, st) != TRXHIP_OK || hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess)
+			return TRXHIP_EIO;
+	}
+
+	// ---- the rest of every plan
+	size_t n_rx = 0, n_join = 0, n_waves = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK)
+			continue;
+		ms_plan &p = g->plan[i];
+		if (p.extend) {
+			n_join++;
+			continue;
+		}
+		const int rc = plan_finish(g->m[i], device, bounded, out_stride, (device && p.prelim) ? g->h_corr[i] : 0, p);
+		if (rc != TRXHIP_OK) {
+			refuse(i, rc);
+			continue;
+		}
+		const size_t k0 = p.waited ? 1 : 0;
+		if ((p.straddle && !p.waited) || p.frac)
+			n_join++;
+		if ((size_t)p.cnt > k0) {
+			n_rx++;
+			n_waves += ((size_t)p.cnt - k0 + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
+		}
+	}
+	if (bad == n && n_waves > 0x7fffffffu) {
+		bad = first;
+		worst = TRXHIP_EINVAL;
+	}
+	if (bad != n) {                                                /* all or nothing: no member has moved */
+		if (bad_member)
+			*bad_member = (int)bad;
+		return worst;
+	}
+
+	// ---- the issue: one table, one join launch, one clear, one receiver launch, one mailbox copy
+	if (device) {
+		char *tab = stage_table(g);
+		if (!tab)
+			return TRXHIP_EIO;
+		trx_mss_member *rx = reinterpret_cast<trx_mss_member *>(tab);
+		trx_mss_join *jn = reinterpret_cast<trx_mss_join *>(tab + n_rx * 64);
+		size_t kr = 0, kj = 0, wave = 0;
+		bool any_sum = false;
+		for (size_t i = 0; i < n; i++) {
+			if (!h_chunks[i].n_samples)
+				continue;
+			const ms_plan &p = g->plan[i];
+			const ms_member &m = g->m[i];
+			char *edge_row = g->d_edge + i * TRX_MSS_SLOT * 8;
+			const bool edge = !p.extend && p.straddle && !p.waited;
+			if (p.extend || edge || p.frac) {
+				trx_mss_join &j = jn[kj++];
+				memset(&j, 0, sizeof(j));
+				j.in = h_chunks[i].d_in;
+				j.rem_in = rem_of(g, i, m.rem_half, cf32);
+				j.rem_out = rem_of(g, i, m.rem_half ^ 1, cf32);
+				j.edge_row = edge_row;
+				j.carried = m.carried;
+				j.do_edge = edge;
+				j.keep = p.extend ? m.carried : 0;
+				j.tail_at = p.extend ? 0 : (uint64_t)(p.to_skip + p.full * TRX_MSS_SLOT);
+				j.n_tail = p.extend ? (uint32_t)p.n_samples : (uint32_t)p.frac;
+			}
+			const size_t k0 = p.waited ? 1 : 0;
+			if (p.extend || (size_t)p.cnt <= k0)
+				continue;
+			const bool sum = m.tracking && p.sch_full != 0;
+			any_sum = any_sum || sum;
+			trx_mss_member &e = rx[kr++];
+			memset(&e, 0, sizeof(e));
+			uint32_t fnk;
+			int tnk;
+			trx_mss_clock_add(p.fn0, p.tn0, k0, &fnk, &tnk);
+			e.chunk = h_chunks[i].d_in;
+			e.sa.edge_row = edge ? edge_row : nullptr;
+			e.sa.first = p.to_skip;
+			e.sa.corr = sum ? g->d_corr + i : nullptr;
+			e.sa.fn0 = fnk;
+			e.sa.tn0 = (uint8_t)tnk;
+			e.sa.tsc = m.tsc;
+			e.sa.active = m.active;
+			e.ind = d_ind + i * out_stride + k0;
+			e.bits = d_bits ? d_bits + (i * out_stride + k0) * 148 : nullptr;
+			e.n_slots = (uint32_t)((size_t)p.cnt - k0);
+			e.first_wave = (uint32_t)wave;
+			wave += (e.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
+		}
+		if (kr != n_rx || kj != n_join || wave != n_waves)
+			return TRXHIP_EIO;
+		if (issue_table(g, tab, n_rx, n_join, n_waves, cf32, any_sum, st) != TRXHIP_OK)
+			return TRXHIP_EIO;
+	}
+
+	// ---- and every member moves
+	for (size_t i = 0; i < n; i++) {
+		ms_member &m = g->m[i];
+		if (h_chunks[i].n_samples) {
+			const ms_plan &p = g->plan[i];
+			if (device) {
+				if (p.extend || p.frac)
+					m.rem_half ^= 1;
+				if (!p.extend && m.tracking && p.sch_full != 0)
+					m.unread = true;
+			}
+			commit(m, p);
+		}
+		if (h_n_slots)
+			h_n_slots[i] = h_chunks[i].n_samples ? m.last.n : 0;
+		if (h_n_carried)
+			h_n_carried[i] = m.first_call ? 0 : m.carried;
+	}
+	return TRXHIP_OK;
+}
+
+int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const void *d_bufs, int cf32, size_t buf_stride, size_t buf_len,
+		  const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+{
+	if (!g || !members || !first_ts || n == 0 || n > g->m.size() || buf_len < 512 + 20 || buf_len > TRXHIP_SCH_SYNC_MAX_LEN)
+		return TRXHIP_EINVAL;
+	std::vector<bool> seen(g->m.size(), false);
+	for (size_t i = 0; i < n; i++) {
+		if (members[i] >= g->m.size() || seen[members[i]])
+			return TRXHIP_EINVAL;                                  /* a member listed twice */
+		seen[members[i]] = true;
+	}
+	const trxhip_sch_sync_result *res;
+	if (!g->ctx) {
+		if (d_bufs || !h_res)
+			return TRXHIP_EINVAL;
+		res = h_res;                                           /* plan-only: the receiver's answers come from outside */
+	} else {
+		if (!d_bufs || (reinterpret_cast<uintptr_t>(d_bufs) & (cf32 ? 7 : 3)) || buf_stride < buf_len)
+			return TRXHIP_EINVAL;
+		const float scale = 1.0f / g->rx_full_scale;
+		const int rc = cf32 ? trxhip_sch_sync_batch_cf32(g->ctx, static_cast<const float *>(d_bufs), buf_stride, g->d_acq, nullptr, n, buf_len,
+								 TRXHIP_SCH_SYNC_ACQ, scale, stream)
+				    : trxhip_sch_sync_batch_i16(g->ctx, static_cast<const int16_t *>(d_bufs), buf_stride, g->d_acq, nullptr, n, buf_len,
+								TRXHIP_SCH_SYNC_ACQ, scale, stream);
+		if (rc != TRXHIP_OK)
+			return rc;
+		const hipStream_t st = static_cast<hipStream_t>(stream);
+		if (hipMemcpyAsync(g->h_acq, g->d_acq, n * sizeof(*g->h_acq), hipMemcpyDeviceToHost, st) != hipSuccess ||
+		    hipEventRecord(g->ev, st) != hipSuccess || hipEventSynchronize(g->ev) != hipSuccess)
+			return TRXHIP_EIO;
+		res = g->h_acq;
+		if (h_res)
+			memcpy(h_res, res, n * sizeof(*res));
+	}
+	for (size_t i = 0; i < n; i++)
+		if (res[i].rc == 1 && (res[i].fn < 0 || (uint32_t)res[i].fn >= TRX_MSS_HYPERFRAME))
+			return TRXHIP_EINVAL;
+	int found = 0;
+	for (size_t i = 0; i < n; i++) {
+		const bool ok = res[i].rc == 1;
+		if (ok)
+			acquired(g->m[members[i]], res[i], first_ts[i]);
+		if (h_found)
+			h_found[i] = ok;
+		found += ok;
+	}
+	return found;
+}
+
+ms_member *member_of(trxhip_ms_group *g, uint32_t i) { return (g && i < g->m.size()) ? &g->m[i] : nullptr; }
+const ms_member *member_of(const trxhip_ms_group *g, uint32_t i) { return (g && i < g->m.size()) ? &g->m[i] : nullptr; }
 
 }  // namespace
 
@@ -393,7 +930,7 @@ extern "C" {
 
 int trxhip_ms_sched_create(trxhip_ctx *ctx, const trxhip_ms_sched_cfg *cfg, trxhip_ms_sched **out)
 {
-	if (!cfg || !out || cfg->tsc > 7 || !std::isfinite(cfg->rx_full_scale) || !(cfg->rx_full_scale > 0.0f))
+	if (!cfg || !out || !cfg_ok(cfg))
 		return TRXHIP_EINVAL;
 	if (ctx && with_device(ctx))
 		return TRXHIP_EINVAL;
@@ -451,14 +988,7 @@ int trxhip_ms_sched_set_clock(trxhip_ms_sched *s, uint32_t fn, int tn, int64_t t
 {
 	if (!s || fn >= TRX_MSS_HYPERFRAME || tn < 0 || tn > 7)
 		return TRXHIP_EINVAL;
-	s->fn = fn;
-	s->tn = tn;
-	s->ts = ts;
-	s->clock_set = true;
-	s->first_call = false;
-	s->carried = 0;
-	s->pending = 0;
-	s->unread = false;
+	set_clock(*s, fn, tn, ts);
 	return TRXHIP_OK;
 }
 
@@ -519,23 +1049,7 @@ int trxhip_ms_sched_acquire_cf32(trxhip_ms_sched *s, const float *d_buf, size_t 
 
 int64_t trxhip_ms_sched_slots(const trxhip_ms_sched *s, size_t n_samples)
 {
-	if (!s || n_samples > kMaxSamples)
-		return TRXHIP_EINVAL;
-	const uint32_t carried = s->first_call ? 0u : s->carried;
-	const int64_t bound = (int64_t)((carried + n_samples) / TRX_MSS_SLOT) + 1;
-	if (s->first_call)
-		return bound;
-	const bool straddle = carried && n_samples >= TRX_MSS_SLOT - carried;
-	if (s->tracking) {
-		uint32_t fn;
-		int tn;
-		trx_mss_clock_add(s->fn, s->tn, 1, &fn, &tn);
-		if (s->unread || s->pending || (straddle && trx_mss_is_sch(fn, tn)))
-			return bound;
-	}
-	if (!carried)
-		return (int64_t)(n_samples / TRX_MSS_SLOT);
-	return straddle ? 1 + (int64_t)((n_samples - (TRX_MSS_SLOT - carried)) / TRX_MSS_SLOT) : 0;
+	return s ? slots_of(*s, n_samples) : TRXHIP_EINVAL;
 }
 
 int trxhip_ms_sched_pull_s16(trxhip_ms_sched *s, const int16_t *d_in, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind,
@@ -552,22 +1066,7 @@ int trxhip_ms_sched_pull_cf32(trxhip_ms_sched *s, const float *d_in, size_t n_sa
 
 int trxhip_ms_sched_plan(const trxhip_ms_sched *s, trxhip_ms_plan *h_out, size_t n)
 {
-	if (!s || (!h_out && n) || n > s->last.n)
-		return TRXHIP_EINVAL;
-	for (size_t k = 0; k < n; k++) {
-		trxhip_ms_plan p;
-		memset(&p, 0, sizeof(p));
-		int tn;
-		trx_mss_clock_add(s->last.fn0, s->last.tn0, k, &p.fn, &tn);
-		p.tn = (uint8_t)tn;
-		p.kind = (uint8_t)trx_mss_kind(p.fn, tn, s->last.tsc);
-		p.flags = (uint8_t)(((s->last.active >> tn) & 1u) ? TRXHIP_MS_SLOT_ACTIVE : 0);
-		p.ts = (s->last.straddle && k == 0) ? s->last.first_ts - s->last.carried
-						     : s->last.first_ts + s->last.to_skip + (int64_t)(k - (s->last.straddle ? 1 : 0)) * TRX_MSS_SLOT;
-		p.src_off = (int32_t)(p.ts - s->last.first_ts);
-		h_out[k] = p;
-	}
-	return TRXHIP_OK;
+	return s ? plan_of(*s, h_out, n) : TRXHIP_EINVAL;
 }
 
 int trxhip_ms_sched_state(trxhip_ms_sched *s, trxhip_ms_sched_status *out)
@@ -576,22 +1075,186 @@ int trxhip_ms_sched_state(trxhip_ms_sched *s, trxhip_ms_sched_status *out)
 		return TRXHIP_EINVAL;
 	if (s->ctx && fold_correction(s) != TRXHIP_OK)
 		return TRXHIP_EIO;
-	memset(out, 0, sizeof(*out));
-	out->to_skip = s->to_skip_last;
-	out->pending = s->pending;
-	out->first_sch_ts_start = s->first_sch_ts_start;
-	out->carried = s->carried;
-	out->carried_cf32 = (uint8_t)s->carried_cf32;
-	out->first_call = s->first_call;
-	out->tracking = s->tracking;
-	out->tsc = s->tsc;
-	out->active_tns = s->active;
-	out->clock_set = s->clock_set;
-	out->clock_jumps = s->clock_jumps;
-	out->pulls = s->pulls;
-	out->slots = s->slots;
-	out->sch_slots = s->sch_slots;
+	state_of(*s, out);
 	return TRXHIP_OK;
+}
+
+// ---- the group ----------------------------------------------------------------------------------
+
+int trxhip_ms_group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const trxhip_ms_sched_cfg *cfgs, trxhip_ms_group **out)
+{
+	if (!cfgs || !out || n_members < 1 || n_members > TRXHIP_MS_GROUP_MAX_MEMBERS || !std::isfinite(rx_full_scale) || !(rx_full_scale > 0.0f))
+		return TRXHIP_EINVAL;
+	for (size_t i = 0; i < n_members; i++)
+		if (!cfg_ok(&cfgs[i]) || cfgs[i].rx_full_scale != rx_full_scale)
+			return TRXHIP_EINVAL;
+	if (ctx && with_device(ctx))
+		return TRXHIP_EINVAL;
+	trxhip_ms_group *g = new (std::nothrow) trxhip_ms_group();
+	if (!g)
+		return TRXHIP_ENOMEM;
+	g->rx_full_scale = rx_full_scale;
+	g->m.resize(n_members);
+	g->plan.resize(n_members);
+	g->rc.resize(n_members);
+	for (size_t i = 0; i < n_members; i++) {
+		g->m[i].rx_full_scale = rx_full_scale;
+		g->m[i].tsc = cfgs[i].tsc;
+		g->m[i].active = cfgs[i].active_tns;
+		g->m[i].tracking = cfgs[i].tracking != 0;
+	}
+	if (!ctx) {
+		*out = g;
+		return TRXHIP_OK;
+	}
+	g->ctx = ctx;
+	const size_t n = n_members;
+	const size_t rem_bytes = n * 2 * TRX_MSS_REM_STRIDE * 8, tab_bytes = 2 * n * 64;     /* tab_bytes: one table */
+	bool ok = hipMalloc((void **)&g->d_rem, rem_bytes) == hipSuccess && hipMalloc((void **)&g->d_edge, n * TRX_MSS_SLOT * 8) == hipSuccess &&
+		  hipMalloc((void **)&g->d_corr, n * sizeof(int32_t)) == hipSuccess && hipMalloc((void **)&g->d_acq, n * sizeof(*g->d_acq)) == hipSuccess &&
+		  hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
+		  hipHostMalloc((void **)&g->h_corr, n * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
+		  hipHostMalloc((void **)&g->h_acq, n * sizeof(*g->h_acq), hipHostMallocDefault) == hipSuccess &&
+		  hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess &&
+		  hipEventCreateWithFlags(&g->ev, hipEventDisableTiming) == hipSuccess;
+	for (int h = 0; h < kTabSlots; h++)
+		ok = ok && hipEventCreateWithFlags(&g->ev_tab[h], hipEventDisableTiming) == hipSuccess;
+	ok = ok && hipMemset(g->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(g->d_corr, 0, n * sizeof(int32_t)) == hipSuccess &&
+	     hipStreamSynchronize(nullptr) == hipSuccess;
+	if (!ok) {
+		trxhip_ms_group_destroy(g);
+		return TRXHIP_ENOMEM;
+	}
+	memset(g->h_corr, 0, n * sizeof(int32_t));
+	*out = g;
+	return TRXHIP_OK;
+}
+
+void trxhip_ms_group_destroy(trxhip_ms_group *g)
+{
+	if (!g)
+		return;
+	if (g->ctx && with_device(g->ctx) == 0) {
+		for (int h = 0; h < kTabSlots; h++) {
+			if (g->tab_used[h] && g->ev_tab[h])
+				(void)hipEventSynchronize(g->ev_tab[h]);
+			if (g->ev_tab[h]) (void)hipEventDestroy(g->ev_tab[h]);
+		}
+		if (g->ev) (void)hipEventDestroy(g->ev);
+		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab };
+		for (void *p : bufs)
+			if (p) (void)hipFree(p);
+		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab };
+		for (void *p : pinned)
+			if (p) (void)hipHostFree(p);
+	}
+	delete g;
+}
+
+int trxhip_ms_group_members(const trxhip_ms_group *g) { return g ? (int)g->m.size() : TRXHIP_EINVAL; }
+
+int trxhip_ms_group_set_clock(trxhip_ms_group *g, uint32_t member, uint32_t fn, int tn, int64_t ts)
+{
+	ms_member *m = member_of(g, member);
+	if (!m || fn >= TRX_MSS_HYPERFRAME || tn < 0 || tn > 7)
+		return TRXHIP_EINVAL;
+	set_clock(*m, fn, tn, ts);
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_group_clock(const trxhip_ms_group *g, uint32_t member, uint32_t *fn, int *tn, int64_t *ts)
+{
+	const ms_member *m = member_of(g, member);
+	if (!m || !fn || !tn || !ts || !m->clock_set)
+		return TRXHIP_EINVAL;
+	*fn = m->fn;
+	*tn = m->tn;
+	*ts = m->ts;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_group_set_tsc(trxhip_ms_group *g, uint32_t member, int tsc)
+{
+	ms_member *m = member_of(g, member);
+	if (!m || tsc < 0 || tsc > 7)
+		return TRXHIP_EINVAL;
+	m->tsc = (uint8_t)tsc;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_group_set_active(trxhip_ms_group *g, uint32_t member, uint8_t tn_mask)
+{
+	ms_member *m = member_of(g, member);
+	if (!m)
+		return TRXHIP_EINVAL;
+	m->active = tn_mask;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_group_set_tracking(trxhip_ms_group *g, uint32_t member, int on)
+{
+	ms_member *m = member_of(g, member);
+	if (!m)
+		return TRXHIP_EINVAL;
+	m->tracking = on != 0;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_group_feed_starts(trxhip_ms_group *g, uint32_t member, const int32_t *starts, size_t n)
+{
+	ms_member *m = member_of(g, member);
+	if (!m || g->ctx || (!starts && n))
+		return TRXHIP_EINVAL;
+	m->feed.assign(starts, starts + n);
+	m->feed_at = 0;
+	return TRXHIP_OK;
+}
+
+int64_t trxhip_ms_group_slots(const trxhip_ms_group *g, uint32_t member, size_t n_samples)
+{
+	const ms_member *m = member_of(g, member);
+	return m ? slots_of(*m, n_samples) : TRXHIP_EINVAL;
+}
+
+int trxhip_ms_group_plan(const trxhip_ms_group *g, uint32_t member, trxhip_ms_plan *h_out, size_t n)
+{
+	const ms_member *m = member_of(g, member);
+	return m ? plan_of(*m, h_out, n) : TRXHIP_EINVAL;
+}
+
+int trxhip_ms_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_sched_status *out)
+{
+	const ms_member *m = member_of(g, member);
+	if (!m || !out)
+		return TRXHIP_EINVAL;
+	if (g->ctx && fold_correction(g) != TRXHIP_OK)
+		return TRXHIP_EIO;
+	state_of(*m, out);
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_group_acquire_s16(trxhip_ms_group *g, const uint32_t *members, size_t n, const int16_t *d_bufs, size_t buf_stride,
+				size_t buf_len, const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+{
+	return group_acquire(g, members, n, d_bufs, 0, buf_stride, buf_len, first_ts, h_res, h_found, stream);
+}
+
+int trxhip_ms_group_acquire_cf32(trxhip_ms_group *g, const uint32_t *members, size_t n, const float *d_bufs, size_t buf_stride,
+				 size_t buf_len, const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+{
+	return group_acquire(g, members, n, d_bufs, 1, buf_stride, buf_len, first_ts, h_res, h_found, stream);
+}
+
+int trxhip_ms_group_pull_s16(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+			     size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream)
+{
+	return group_pull(g, h_chunks, 0, d_ind, d_bits, out_stride, h_n_slots, h_n_carried, bad_member, stream);
+}
+
+int trxhip_ms_group_pull_cf32(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+			      size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream)
+{
+	return group_pull(g, h_chunks, 1, d_ind, d_bits, out_stride, h_n_slots, h_n_carried, bad_member, stream);
 }
 
 }  // extern "C"

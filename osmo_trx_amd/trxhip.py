@@ -204,6 +204,22 @@ SYMBOLS = {
     "trxhip_ms_sched_pull_cf32": (_I, [_VP, _VP, _SZ, C.c_int64, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), _VP]),
     "trxhip_ms_sched_plan": (_I, [_VP, _VP, _SZ]),
     "trxhip_ms_sched_state": (_I, [_VP, _VP]),
+    "trxhip_ms_group_create": (_I, [_VP, _F, _SZ, _VP, C.POINTER(_VP)]),
+    "trxhip_ms_group_destroy": (None, [_VP]),
+    "trxhip_ms_group_members": (_I, [_VP]),
+    "trxhip_ms_group_set_clock": (_I, [_VP, C.c_uint32, C.c_uint32, _I, C.c_int64]),
+    "trxhip_ms_group_clock": (_I, [_VP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "trxhip_ms_group_set_tsc": (_I, [_VP, C.c_uint32, _I]),
+    "trxhip_ms_group_set_active": (_I, [_VP, C.c_uint32, C.c_uint8]),
+    "trxhip_ms_group_set_tracking": (_I, [_VP, C.c_uint32, _I]),
+    "trxhip_ms_group_feed_starts": (_I, [_VP, C.c_uint32, _VP, _SZ]),
+    "trxhip_ms_group_slots": (C.c_int64, [_VP, C.c_uint32, _SZ]),
+    "trxhip_ms_group_plan": (_I, [_VP, C.c_uint32, _VP, _SZ]),
+    "trxhip_ms_group_state": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_group_acquire_s16": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP]),
+    "trxhip_ms_group_acquire_cf32": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP]),
+    "trxhip_ms_group_pull_s16": (_I, [_VP, _VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(_I), _VP]),
+    "trxhip_ms_group_pull_cf32": (_I, [_VP, _VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(_I), _VP]),
     "trxhip_ms_tx_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
     "trxhip_ms_tx_destroy": (None, [_VP]),
     "trxhip_ms_tx_set_ta": (_I, [_VP, _I]),
@@ -1233,6 +1249,181 @@ class MsRxScheduler:
     def close(self):
         if getattr(self, "h", None):
             self.L.trxhip_ms_sched_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MS_GROUP_MAX_MEMBERS = 4096                          # TRXHIP_MS_GROUP_MAX_MEMBERS
+MS_GROUP_CHUNK_DTYPE = np.dtype([("d_in", "<u8"), ("n_samples", "<u8"), ("first_ts", "<i8")])   # trxhip_ms_group_chunk
+
+
+def _per_member(v, n, what):
+    if not isinstance(v, (list, tuple, np.ndarray)):
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError("%s: %d values for %d members" % (what, len(v), n))
+    return v
+
+
+class MsRxSchedulerGroup:
+    """A group of MS-side downlink streams (trxhip_ms_group_*): n members, each what one MsRxScheduler is, whose pulls are cut
+    and received as one step -- one table, one join launch, one receiver launch, at most two waits, whatever n is.  tsc,
+    active_tns and tracking: one value for all members or one per member; rx_full_scale belongs to the group.  trx=None: a
+    plan-only group."""
+
+    def __init__(self, trx=None, n=1, rx_full_scale=2047.0, tsc=0, active_tns=0xFF, tracking=True):
+        self.trx = trx
+        self.L = trx.L if trx is not None else load_library()
+        self.n = int(n)
+        if self.n < 0:
+            raise ValueError("n")
+        cfgs = (_MsSchedCfg * max(self.n, 1))()
+        for m, (t, a, k) in enumerate(zip(_per_member(tsc, self.n, "tsc"), _per_member(active_tns, self.n, "active_tns"),
+                                          _per_member(tracking, self.n, "tracking"))):
+            cfgs[m] = _MsSchedCfg(rx_full_scale, t, a, int(bool(k)), 0)
+        h = _VP()
+        _check(self.L.trxhip_ms_group_create(trx.h if trx is not None else None, rx_full_scale, self.n, C.cast(cfgs, _VP), C.byref(h)),
+               "trxhip_ms_group_create")
+        self.h = h
+        self.n_slots = [0] * self.n                  # of each member's last pull
+        self.carried = [0] * self.n
+
+    def set_clock(self, m, fn, tn, ts=0):
+        _check(self.L.trxhip_ms_group_set_clock(self.h, m, fn, tn, ts), "trxhip_ms_group_set_clock")
+        self.carried[m] = 0
+
+    def clock(self, m):
+        """(fn, tn, ts) of the last slot member m cut"""
+        fn, tn, ts = C.c_uint32(), _I(), C.c_int64()
+        _check(self.L.trxhip_ms_group_clock(self.h, m, C.byref(fn), C.byref(tn), C.byref(ts)), "trxhip_ms_group_clock")
+        return fn.value, tn.value, ts.value
+
+    def set_tsc(self, m, tsc):
+        _check(self.L.trxhip_ms_group_set_tsc(self.h, m, tsc), "trxhip_ms_group_set_tsc")
+
+    def set_active(self, m, tn_mask):
+        _check(self.L.trxhip_ms_group_set_active(self.h, m, tn_mask), "trxhip_ms_group_set_active")
+
+    def set_tracking(self, m, on):
+        _check(self.L.trxhip_ms_group_set_tracking(self.h, m, int(bool(on))), "trxhip_ms_group_set_tracking")
+
+    def feed_starts(self, m, starts):
+        """plan-only: the `start` of the next SCH slots member m cuts with tracking on (MS_SCHED_NO_SCH: not decoded)"""
+        a = np.ascontiguousarray(starts, dtype=np.int32)
+        _check(self.L.trxhip_ms_group_feed_starts(self.h, m, a.ctypes.data_as(_VP), len(a)), "trxhip_ms_group_feed_starts")
+
+    def acquire(self, members, bufs=None, first_ts=0, results=None, stream=None):
+        """handle_sch(true) for the listed members in one launch and one wait.  bufs: int16[n, len, 2] or complex64[n, len] device
+        tensor, row i the buffer of members[i]; first_ts: one timestamp or one per buffer.  Returns (found: bool[n], records:
+        SCH_SYNC_DTYPE[n]).  Plan-only: results are the records the receiver would have given."""
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        n = len(members)
+        ts = np.ascontiguousarray(_per_member(first_ts, n, "first_ts"), dtype=np.int64)
+        rec = np.zeros(n, dtype=SCH_SYNC_DTYPE)
+        found = np.zeros(n, dtype=np.int32)
+        if self.trx is None:
+            rec[:] = results
+            rc = self.L.trxhip_ms_group_acquire_s16(self.h, members.ctypes.data_as(_VP), n, None, 60000, 60000, ts.ctypes.data_as(_VP),
+                                                    rec.ctypes.data_as(_VP), found.ctypes.data_as(_VP), None)
+        else:
+            s16 = bufs.dtype == self.trx.torch.int16
+            assert bufs.is_contiguous() and bufs.shape[0] == n and bufs.dim() == (3 if s16 else 2), (bufs.shape, bufs.dtype)
+            fn = self.L.trxhip_ms_group_acquire_s16 if s16 else self.L.trxhip_ms_group_acquire_cf32
+            rc = fn(self.h, members.ctypes.data_as(_VP), n, self.trx._dev(bufs), bufs.shape[1], bufs.shape[1], ts.ctypes.data_as(_VP),
+                    rec.ctypes.data_as(_VP), found.ctypes.data_as(_VP), self.trx._stream(stream))
+        if rc < 0:
+            _check(rc, "trxhip_ms_group_acquire")
+        for m, f in zip(members, found):
+            if f:
+                self.carried[int(m)] = 0
+        return found.astype(bool), rec
+
+    def slots(self, m, n_samples):
+        n = self.L.trxhip_ms_group_slots(self.h, m, n_samples)
+        if n < 0:
+            _check(int(n), "trxhip_ms_group_slots")
+        return int(n)
+
+    def pull(self, chunks=None, first_ts=0, out_stride=None, bits=True, stream=None, out=None, n_samples=None):
+        """chunks: per member an int16[n, 2] or complex64[n] device tensor (all of one format) or None (no chunk in this pull);
+        first_ts: one timestamp or one per member.  Returns ([(ind uint8[k, 32], sbits int8[k, 148] or None) per member], [k per
+        member]): views of outputs with out_stride rows per member (default: the largest trxhip_ms_group_slots() of the pull), or
+        of out = (ind uint8[n, out_stride, 32], sbits int8[n, out_stride, 148] or None).  Plan-only: n_samples per member (0 or
+        None: no chunk); returns ([n_slots], [n_carried]).  A plan-only group given an out_stride other than None / 0 refuses a
+        pull in which a member would cut more slots than that, as the GPU group does; the plan-only MsRxScheduler has no such
+        bound (it takes no outputs), and neither has the group with out_stride None / 0."""
+        ts = _per_member(first_ts, self.n, "first_ts")
+        ch = np.zeros(self.n, dtype=MS_GROUP_CHUNK_DTYPE)
+        ns, nc = (_SZ * self.n)(), (_SZ * self.n)()
+        bad = _I(-1)
+        if self.trx is None:
+            sizes = _per_member(n_samples, self.n, "n_samples")
+            for m in range(self.n):
+                ch[m] = (0, sizes[m] or 0, ts[m])
+            rc = self.L.trxhip_ms_group_pull_s16(self.h, ch.ctypes.data_as(_VP), None, None, int(out_stride or 0), C.cast(ns, _VP), C.cast(nc, _VP),
+                                                 C.byref(bad), None)
+            self.bad_member = bad.value
+            _check(rc, "trxhip_ms_group_pull_s16 (member %d)" % bad.value)
+            self.n_slots, self.carried = list(ns), list(nc)
+            return list(ns), list(nc)
+        torch = self.trx.torch
+        chunks = _per_member(chunks, self.n, "chunks") if isinstance(chunks, (list, tuple)) else [chunks] * self.n
+        have = [x for x in chunks if x is not None]
+        if not have:
+            raise ValueError("no member has a chunk")
+        s16 = have[0].dtype == torch.int16
+        cap = 1
+        for m, x in enumerate(chunks):
+            if x is None:
+                continue
+            assert x.dtype == have[0].dtype and x.is_contiguous(), (m, x.dtype)
+            assert x.dtype == torch.complex64 and x.dim() == 1 or (s16 and x.dim() == 2 and x.shape[1] == 2), (x.shape, x.dtype)
+            ch[m] = (x.data_ptr(), x.shape[0], ts[m])
+            if out_stride is None and out is None:
+                cap = max(cap, self.slots(m, x.shape[0]))
+        dev = f"cuda:{self.trx.device}"
+        if out is not None:
+            ind, sb = out
+            stride = ind.shape[1]
+            assert ind.is_contiguous() and tuple(ind.shape) == (self.n, stride, MS_IND_DTYPE.itemsize) and ind.dtype == torch.uint8
+            assert sb is None or (sb.is_contiguous() and tuple(sb.shape) == (self.n, stride, 148) and sb.dtype == torch.int8)
+        else:
+            stride = cap if out_stride is None else int(out_stride)
+            ind = torch.empty((self.n, max(stride, 1), MS_IND_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            sb = torch.empty((self.n, max(stride, 1), 148), dtype=torch.int8, device=dev) if bits else None
+        fn = self.L.trxhip_ms_group_pull_s16 if s16 else self.L.trxhip_ms_group_pull_cf32
+        rc = fn(self.h, ch.ctypes.data_as(_VP), self.trx._dev(ind), self.trx._dev(sb) if sb is not None else None, stride,
+                C.cast(ns, _VP), C.cast(nc, _VP), C.byref(bad), self.trx._stream(stream))
+        self.bad_member = bad.value
+        _check(rc, "trxhip_ms_group_pull (member %d)" % bad.value)
+        self.n_slots, self.carried = list(ns), list(nc)
+        return [(ind[m, :k], sb[m, :k] if sb is not None else None) for m, k in enumerate(self.n_slots)], list(self.n_slots)
+
+    def plan(self, m, n=None):
+        """MS_PLAN_DTYPE[n] of member m's last pull (default: all its slots)"""
+        if n is None:
+            n = self.n_slots[m]
+        a = np.zeros(n, dtype=MS_PLAN_DTYPE)
+        _check(self.L.trxhip_ms_group_plan(self.h, m, a.ctypes.data_as(_VP), n), "trxhip_ms_group_plan")
+        return a
+
+    def state(self, m):
+        """MS_SCHED_STATE_DTYPE record of member m; waits for the group's corrections in flight"""
+        a = np.zeros(1, dtype=MS_SCHED_STATE_DTYPE)
+        _check(self.L.trxhip_ms_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_group_state")
+        return a[0]
+
+    ind_to_numpy = staticmethod(MsRxScheduler.ind_to_numpy)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.trxhip_ms_group_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1,0 +1,223 @@
+#!/usr/bin/env python3
+"""The MS-side scheduler group on one GPU against single scheduler objects on the same chunks and the same stream, HIP-event
+time, int16, the 51-multiframe mix over 8 TNs (per 408 slots: 5 FCCH, 5 SCH, 398 traffic), all ACTIVE, tracking on.  Member m's
+stream begins at frame m % 51 of the multiframe, so the members do not meet their SCH slots in the same pull.
+  g64 / s64      64 members, 8 slots (one frame) per member and pull, `frames` pulls in a row from fresh clocks: one group pull
+                 per frame against 64 trxhip_ms_sched_pull_s16 per frame; reported per frame
+  g256 / s256    the same with 256 members
+  g1 / s1        one member, 8 slots per pull
+  gbig / sbig    one member, one pull of `slots` slots (set_clock + pull per call)
+Every round is a fresh process under its own time limit; inside a round the legs are timed in turns, the order reversed every
+other turn and the number of turns even, so that every leg is timed as often in front of its partner as behind it; every timed
+region follows one untimed call of the same leg, so that what ran before a leg is that leg, whatever the order.  Median per leg over the rounds, spread = max - min over the rounds -> profiles/ms_group_bench.json.  The first step
+that fails ends the run.
+
+   python3 tools/bench_ms_group.py [--rounds 5] [--slots N] [--frames F] [--inner I] [--warmup W] [--reps R] [--timeout S] [--trace LEG] [--out FILE]"""
+import argparse
+import json
+import os
+import re
+import shutil
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+FULL_SCALE = 2047.0
+BASE_FN = 51 * 4321
+FRAME = 8 * 625
+PAIRS = (("g64", "s64"), ("g256", "s256"), ("g1", "s1"), ("gbig", "sbig"))
+
+
+def child(a):
+    """One round: the legs in turns -> one JSON line {leg: median ms per frame (per pull for gbig / sbig)}."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from bench_ms_rx import TSC, multiframe
+    from osmo_trx_amd import TrxHip, trxhip
+    trx = TrxHip(0)
+    base_iq = multiframe(trx, BASE_FN)[0]
+    names = [k for pair in PAIRS for k in pair if not a.legs or k in a.legs.split(",")]
+    L, st = trx.L, trx._stream()
+    vp = C.c_void_p
+    frames = a.frames
+    assert 1 <= frames <= 51
+    iq = base_iq.repeat(3, 1, 1).contiguous()                      # 153 frames: member m reads the frames m % 51 + k, k < frames
+    big = None
+    if "gbig" in names or "sbig" in names:
+        big = base_iq.repeat((a.slots + 407) // 408, 1, 1)[:a.slots].contiguous()
+    stride = 9                                                     # 8 slots and the straddling one
+    ns1, nc1 = C.c_size_t(), C.c_size_t()
+
+    def members(n):
+        """(group, singles, chunk tables per frame, outputs) for n members of 8-slot pulls"""
+        g = trxhip.MsRxSchedulerGroup(trx, n=n, rx_full_scale=FULL_SCALE, tsc=TSC, active_tns=0xFF, tracking=True)
+        ss = [trxhip.MsRxScheduler(trx, rx_full_scale=FULL_SCALE, tsc=TSC, active_tns=0xFF, tracking=True) for _ in range(n)]
+        tabs = []
+        for k in range(frames):
+            ch = np.zeros(n, dtype=trxhip.MS_GROUP_CHUNK_DTYPE)
+            ch["d_in"] = [iq.data_ptr() + ((m % 51) + k) * FRAME * 4 for m in range(n)]
+            ch["n_samples"], ch["first_ts"] = FRAME, k * FRAME
+            tabs.append(ch)
+        ind = torch.zeros((2, n, stride, 32), dtype=torch.uint8, device="cuda:0")
+        bits = torch.zeros((2, n, stride, 148), dtype=torch.int8, device="cuda:0")
+        cnt = (C.c_size_t * n)()
+        return g, ss, tabs, ind, bits, cnt
+
+    def group_leg(n):
+        g, ss, tabs, ind, bits, cnt = members(n)
+
+        def run():
+            for m in range(n):
+                g.set_clock(m, BASE_FN + (m % 51) - 1, 7, -625)
+            for ch in tabs:
+                trxhip._check(L.trxhip_ms_group_pull_s16(g.h, ch.ctypes.data_as(vp), vp(ind[0].data_ptr()), vp(bits[0].data_ptr()), stride,
+                                                         C.cast(cnt, vp), None, None, st), "group pull")
+
+        pull16 = L.trxhip_ms_sched_pull_s16
+        args = [[(ss[m].h, vp(int(ch["d_in"][m])), FRAME, int(ch["first_ts"][m]), vp(ind[1, m].data_ptr()), vp(bits[1, m].data_ptr()), stride,
+                  C.byref(ns1), C.byref(nc1), st) for m in range(n)] for ch in tabs]     # (made once: the loop below only calls)
+
+        def run_singles():
+            for m in range(n):
+                ss[m].set_clock(BASE_FN + (m % 51) - 1, 7, -625)
+            for row in args:
+                for arg in row:
+                    if pull16(*arg) != 0:
+                        raise RuntimeError("trxhip_ms_sched_pull_s16 failed")
+
+        def check():
+            """the last frame of both paths holds the same bytes, member for member"""
+            ind.zero_()
+            bits.zero_()
+            run()
+            run_singles()
+            torch.cuda.synchronize()
+            assert torch.equal(ind[0], ind[1]) and torch.equal(bits[0], bits[1]), "the group's slots differ from the single objects'"
+            assert all(int(g.state(m)["slots"]) == int(ss[m].state()["slots"]) for m in range(n))
+            assert min(list(cnt)) >= 7, "8-slot pulls cut too few slots"
+
+        return run, run_singles, check
+
+    legs, checks = {}, []
+    for n, (gn, sn) in ((64, PAIRS[0]), (256, PAIRS[1]), (1, PAIRS[2])):
+        if gn in names or sn in names:
+            run, run_singles, check = group_leg(n)
+            legs[gn], legs[sn] = (run, frames), (run_singles, frames)
+            checks.append(check)
+    if big is not None:
+        gb = trxhip.MsRxSchedulerGroup(trx, n=1, rx_full_scale=FULL_SCALE, tsc=TSC, active_tns=0xFF, tracking=True)
+        sb = trxhip.MsRxScheduler(trx, rx_full_scale=FULL_SCALE, tsc=TSC, active_tns=0xFF, tracking=True)
+        ind_b = torch.empty((2, a.slots, 32), dtype=torch.uint8, device="cuda:0")
+        bits_b = torch.empty((2, a.slots, 148), dtype=torch.int8, device="cuda:0")
+        chb = np.zeros(1, dtype=trxhip.MS_GROUP_CHUNK_DTYPE)
+        chb["d_in"], chb["n_samples"], chb["first_ts"] = big.data_ptr(), a.slots * 625, 0
+        cntb = (C.c_size_t * 1)()
+
+        def gbig():
+            gb.set_clock(0, BASE_FN - 1, 7, -625)
+            trxhip._check(L.trxhip_ms_group_pull_s16(gb.h, chb.ctypes.data_as(vp), vp(ind_b[0].data_ptr()), vp(bits_b[0].data_ptr()), a.slots,
+                                                     C.cast(cntb, vp), None, None, st), "group pull")
+
+        def sbig():
+            sb.set_clock(BASE_FN - 1, 7, -625)
+            trxhip._check(L.trxhip_ms_sched_pull_s16(sb.h, vp(big.data_ptr()), a.slots * 625, 0, vp(ind_b[1].data_ptr()), vp(bits_b[1].data_ptr()),
+                                                     a.slots, C.byref(ns1), C.byref(nc1), st), "pull")
+
+        def check_big():
+            gbig()
+            sbig()
+            torch.cuda.synchronize()
+            assert cntb[0] == ns1.value == a.slots
+            assert torch.equal(ind_b[0], ind_b[1]) and torch.equal(bits_b[0], bits_b[1]), "the group's slots differ from the single object's"
+
+        legs["gbig"], legs["sbig"] = (gbig, 1), (sbig, 1)
+        checks.append(check_big)
+    names = [k for k in names if k in legs]
+    times = {k: [] for k in names}
+    for name in names:
+        for _ in range(a.warmup):
+            legs[name][0]()
+    torch.cuda.synchronize()
+    for i in range(a.inner):
+        for name in (names if (a.round + i) % 2 == 0 else names[::-1]):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            legs[name][0]()                                        # untimed: the timed calls follow a call of their own kind
+            ev[0].record()
+            for _ in range(a.reps):
+                legs[name][0]()
+            ev[1].record()
+            torch.cuda.synchronize()
+            times[name].append(ev[0].elapsed_time(ev[1]) / a.reps / legs[name][1])
+    if not a.legs:
+        for check in checks:
+            check()
+    print(json.dumps({k: statistics.median(v) for k, v in times.items()}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--slots", type=int, default=1 << 18)
+    ap.add_argument("--frames", type=int, default=17, help="8-slot pulls in a row per timed call")
+    ap.add_argument("--inner", type=int, default=6, help="turns per leg inside a round (even: both orders equally often)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--timeout", type=int, default=150, help="seconds per round")
+    ap.add_argument("--trace", default="", help="also take a kernel trace of these legs (comma-separated), each in a run of its own")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ms_group_bench.json"))
+    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
+    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
+    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.round is not None:
+        return child(a)
+    if a.rounds < 5:
+        ap.error("at least five rounds")
+    if a.inner % 2:
+        ap.error("an even number of turns")
+    import measure
+    os.makedirs(a.logs, exist_ok=True)
+    per_leg = {}
+    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--frames", str(a.frames)]
+    for r in range(a.rounds):
+        log = os.path.join(a.logs, "ms_group_round_%d.log" % (r + 1))
+        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--inner", str(a.inner), "--warmup", str(a.warmup), "--reps",
+                                                 str(a.reps)], log, a.timeout)
+        for k, v in measure.last_json(log).items():
+            per_leg.setdefault(k, []).append(v)
+        print("round %d done" % (r + 1), flush=True)
+    res = {"workload": "ms_group", "slots": a.slots, "small_pull_slots": 8, "frames_per_call": a.frames, "slot_len": 625,
+           "mix_per_408": {"fcch": 5, "sch": 5, "traffic": 398}, "input": "int16", "tracking": True, "rounds": a.rounds, "inner": a.inner,
+           "reps": a.reps, "unit": "ms per frame of all members (gbig / sbig: per pull)", "legs": {}, "pairs": {}}
+    for name, xs in per_leg.items():
+        med = statistics.median(xs)
+        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs])
+    lg = res["legs"]
+    for gn, sn in PAIRS:
+        if gn in lg and sn in lg:
+            res["pairs"][gn + "_over_" + sn] = dict(ratio=round(lg[gn]["median_ms"] / lg[sn]["median_ms"], 4),
+                                                    diff_ms=round(lg[gn]["median_ms"] - lg[sn]["median_ms"], 4),
+                                                    larger_spread_ms=max(lg[gn]["spread_ms"], lg[sn]["spread_ms"]))
+    if a.trace:
+        from bench_rx_sched import trace_rows
+        d = os.path.join(a.logs, "ms_group_trace")
+        res["kernel_trace_us"] = {}
+        for leg in a.trace.split(","):
+            shutil.rmtree(d, ignore_errors=True)
+            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "ms_group",
+                                                 "--"] + me + ["--round", "0", "--inner", "1", "--warmup", "1", "--reps", "1", "--legs", leg],
+                         os.path.join(a.logs, "ms_group_trace_%s.log" % leg), a.timeout)
+            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(trace_rows(d).items()) if re.match(r"ms_rx|ms_join", k)}
+        shutil.rmtree(d, ignore_errors=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
