@@ -84,7 +84,7 @@ struct trx_mss_member {
 	uint32_t               first_wave;
 };
 
-/* One block of ms_join_group_kernel: ms_join_kernel's arguments for one member.  64 bytes */
+/* The join of one member: ms_join_kernel's argument (the single object), one block's table entry of ms_join_group_kernel.  64 bytes */
 struct trx_mss_join {
 	const void *in, *rem_in;
 	void       *rem_out, *edge_row;

@@ -6,18 +6,20 @@
 //   ms_trx::grab_bursts()                         ms/ms_rx_lower.cpp:354-422             the cutter (trxhip_ms_sched_pull_*)
 //   ms_trx::handle_sch_or_nb() / handle_sch(false) :130-153, :157-205                    what a cut slot is, temp_ts_corr_offset
 //   time_keeper                                   ms/ms.h:160-221                        the GSM clock and its timestamp
-// A pull is: the plan on the host (cut position, clock, count -- integers), ms_join_kernel (the slot that straddles the carried
-// partial slot and the chunk is assembled into a row; the chunk's tail is saved as the new partial slot) and the stream instance
-// of ms_rx_kernel (trx_ms_rx.hip) over every slot of the pull, read where it lies.  The cut position depends on SCH results of
-// the device in two places, which are the scheduler's only waits (see include/trxhip.h).  Per SCH-carrying launch the correction
-// is summed on the device into one word that starts at zero and is copied to a pinned mailbox behind the launch; the host adds
-// it to temp_ts_corr_offset when the next pull plans.
+// There is one object, the group of streams (trxhip_ms_group_*); the single object (trxhip_ms_sched_*) is a group of one member
+// whose entry points forward to the group's.  A pull is: per member the plan on the host (plan_begin / plan_finish: cut position,
+// clock, count -- integers only, nothing moves), the issue of one launch set for all members, and commit(), which moves the
+// members' states.  A launch set is a join (the slot that straddles the carried partial slot and the chunk is assembled into a
+// row; the chunk's tail is saved as the new partial slot), a clear of the correction words, the receiver (trx_ms_rx.hip) over
+// every slot of the pull, read where it lies, a copy of the correction words to a pinned mailbox, and one event.  The cut
+// position depends on SCH results of the device in two places, which are the scheduler's only waits (see include/trxhip.h): per
+// SCH-carrying launch set the correction is summed on the device into a word per member that starts at zero; the host adds it to
+// temp_ts_corr_offset when the next pull plans.
+// issue_table() says once what a member's plan puts into a launch set, as entries (trx_ms_sched.h), and sends them one of two
+// ways.  A group copies them up as one table from a pinned area and launches ms_join_group_kernel and the receiver's group form
+// over it.  The single object (`direct`) has at most one entry of each kind and passes them as kernel arguments, to
+// ms_join_kernel and the receiver's stream form: no table, no pinned area, none of a table's waits.
 // With ctx == NULL the object is plan-only: cutter, clock and plan, no device memory; SCH starts come from a queue.
-// A pull is written in two steps that the single object and the group (trxhip_ms_group_*) share: the plan of one member
-// (plan_begin / plan_finish: integers only, nothing moves) and the issue; commit() then moves the member's state.  The group
-// issues the pulls of all its members as one table (trx_ms_sched.h), one ms_join_group_kernel, one clear of the correction
-// words, one group launch of the receiver (trx_ms_rx.hip), one copy of the correction words, one event -- and at most the same
-// two waits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -37,7 +39,8 @@ constexpr size_t kMaxSamples = (size_t)1 << 40;
 constexpr int kTabSlots = 4;                   /* pinned table areas of a group: the host runs at most this many launch sets ahead */
 
 // ------------------------------------------------------------------------------------------------
-// ms_join_kernel: one block.  The stream of a pull is the carried partial slot (rem_in, `carried` samples) followed by the chunk.
+// The join of one member, one block, from its entry (trx_mss_join).  The stream of a pull is the carried partial slot (rem_in,
+// `carried` samples) followed by the chunk.
 //   do_edge : its first 625 samples, the one slot that does not lie in the chunk, are assembled into edge_row (:385-394)
 //   the new partial slot (:419-421) goes to the OTHER half of the partial-slot area: the first `keep` samples of the old one
 //   (a chunk shorter than the missing part: :388-391) and n_tail samples of the chunk from tail_at on
@@ -57,28 +60,33 @@ __device__ __forceinline__ void ms_join(const T *__restrict__ in, const T *__res
 }
 
 template <typename T>
-__global__ void __launch_bounds__(kThreads)
-ms_join_kernel(const T *__restrict__ in, const T *__restrict__ rem_in, T *__restrict__ rem_out, T *__restrict__ edge_row,
-	       uint32_t carried, int do_edge, uint32_t keep, size_t tail_at, uint32_t n_tail)
+__device__ __forceinline__ void ms_join(const trx_mss_join &j)
 {
-	ms_join<T>(in, rem_in, rem_out, edge_row, carried, do_edge, keep, tail_at, n_tail);
+	ms_join<T>(static_cast<const T *>(j.in), static_cast<const T *>(j.rem_in), static_cast<T *>(j.rem_out), static_cast<T *>(j.edge_row),
+		   j.carried, j.do_edge, j.keep, (size_t)j.tail_at, j.n_tail);
 }
 
-// ms_join_group_kernel: one block per member of a group pull that needs a join, its arguments from the table
+// ms_join_kernel: the single object's join, its entry a kernel argument
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+ms_join_kernel(const trx_mss_join j)
+{
+	ms_join<T>(j);
+}
+
+// ms_join_group_kernel: one block per member of a group pull that needs a join, its entry from the table
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
 ms_join_group_kernel(const trx_mss_join *__restrict__ tab)
 {
 	const trx_mss_join j = tab[blockIdx.x];
-	ms_join<T>(static_cast<const T *>(j.in), static_cast<const T *>(j.rem_in), static_cast<T *>(j.rem_out), static_cast<T *>(j.edge_row),
-		   j.carried, j.do_edge, j.keep, (size_t)j.tail_at, j.n_tail);
+	ms_join<T>(j);
 }
 
 static_assert(sizeof(trx_mss_join) == 64 && sizeof(trx_mss_member) == 64, "table entries");
 
-// One downlink stream on the host: what a single object is apart from its device memory, and what a group holds per member
+// One downlink stream on the host: what a group holds per member
 struct ms_member {
-	float rx_full_scale = 0.0f;
 	uint8_t tsc = 0, active = 0;
 	bool tracking = false;
 	// time_keeper, and grab_bursts()' statics
@@ -90,7 +98,7 @@ struct ms_member {
 	uint32_t carried = 0;                  /* partial_rdofs */
 	int carried_cf32 = 0;                  /* its format */
 	int64_t pending = 0;                   /* temp_ts_corr_offset, without what `unread` says is still on its way */
-	bool unread = false;                   /* a launch with SCH slots was issued: its sum arrives in the mailbox behind ev_corr */
+	bool unread = false;                   /* a launch with SCH slots was issued: its sum arrives in the mailbox behind the set's event */
 	int64_t to_skip_last = 0;
 	uint64_t clock_jumps = 0, pulls = 0, slots = 0, sch_slots = 0;
 	// the last pull, for trxhip_ms_sched_plan()
@@ -133,20 +141,12 @@ struct ms_plan {
 
 }  // namespace
 
-struct trxhip_ms_sched : ms_member {
-	trxhip_ctx *ctx = nullptr;
-	// device state (ctx != NULL)
-	void *d_rem = nullptr;                 /* [2][TRX_MSS_REM_STRIDE] samples of either format */
-	void *d_edge_row = nullptr;            /* 625 samples of either format */
-	int32_t *d_corr = nullptr, *h_corr = nullptr;
-	trxhip_sch_sync_result *d_acq = nullptr, *h_acq = nullptr;
-	hipEvent_t ev_corr = nullptr, ev = nullptr;
-	bool ev_used = false;
-};
-
+// A trxhip_ms_sched * is the handle of a group of one member that issues directly (trxhip_ms_sched_create()); the type has no
+// definition of its own.
 struct trxhip_ms_group {
 	trxhip_ctx *ctx = nullptr;
 	float rx_full_scale = 0.0f;
+	bool direct = false;                   /* the single object: one member, its entries sent as kernel arguments, no table */
 	std::vector<ms_member> m;
 	std::vector<ms_plan> plan;             /* scratch of a pull */
 	std::vector<int> rc;
@@ -155,14 +155,15 @@ struct trxhip_ms_group {
 	char *d_edge = nullptr;                /* [n][625] samples of either format */
 	int32_t *d_corr = nullptr, *h_corr = nullptr;      /* [n] correction words and their pinned mailbox */
 	trxhip_sch_sync_result *d_acq = nullptr, *h_acq = nullptr;   /* [n] */
-	// the table of a launch set: up to n receiver entries followed by up to n join entries, 64 bytes each.  It is staged in one of
-	// kTabSlots pinned areas taken in turn.  A launch set records ONE event, its area's, behind everything it issues: the area is
-	// written again only behind that event, and where the set sums corrections the same event says that the mailbox holds them
+	// A launch set records ONE event behind everything it issues, the next of kTabSlots taken in turn: where the set sums
+	// corrections the event says that the mailbox holds them.
+	// The table of a launch set (not with `direct`): up to n receiver entries followed by up to n join entries, 64 bytes each.  It
+	// is staged in the pinned area that belongs to the set's event: the area is written again only behind that event
 	char *d_tab = nullptr, *h_tab = nullptr;
 	hipEvent_t ev_tab[kTabSlots] = {};
 	bool tab_used[kTabSlots] = {};
-	int tab_at = 0;                        /* the area the next launch set takes */
-	int corr_at = 0;                       /* the area of the last launch set that summed corrections */
+	int tab_at = 0;                        /* the event, and the area, the next launch set takes */
+	int corr_at = 0;                       /* those of the last launch set that summed corrections */
 	hipEvent_t ev = nullptr;               /* acquire's */
 };
 
@@ -170,19 +171,8 @@ namespace {
 
 int launched() { return hipGetLastError() == hipSuccess ? TRXHIP_OK : TRXHIP_EIO; }
 
-// the sum of a launch in flight joins temp_ts_corr_offset: the wait of the pull behind a pull that cut an SCH slot
-int fold_correction(trxhip_ms_sched *s)
-{
-	if (!s->unread)
-		return TRXHIP_OK;
-	if (with_device(s->ctx) || hipEventSynchronize(s->ev_corr) != hipSuccess)
-		return TRXHIP_EIO;
-	s->pending += *s->h_corr;
-	s->unread = false;
-	return TRXHIP_OK;
-}
-
-// the same for a group: one wait, and every member's word
+// the sums of a launch set in flight join temp_ts_corr_offset: the wait of the pull behind a pull that cut an SCH slot -- one wait,
+// and every member's word
 int fold_correction(trxhip_ms_group *g)
 {
 	bool any = false;
@@ -202,48 +192,6 @@ int fold_correction(trxhip_ms_group *g)
 
 // inc_and_update_safe()'s asserts (ms.h:192-194): diff < 1.5 * 625 and diff > 0.5 * 625
 bool jump(int64_t diff) { return !(2 * diff < 3 * TRX_MSS_SLOT) || !(2 * diff > TRX_MSS_SLOT); }
-
-int launch_join(trxhip_ms_sched *s, const void *d_in, int cf32, int do_edge, uint32_t keep, size_t tail_at, uint32_t n_tail,
-		hipStream_t st)
-{
-	const size_t esz = cf32 ? 8 : 4;
-	const char *rem_in = static_cast<const char *>(s->d_rem) + (size_t)s->rem_half * TRX_MSS_REM_STRIDE * esz;
-	char *rem_out = static_cast<char *>(s->d_rem) + (size_t)(s->rem_half ^ 1) * TRX_MSS_REM_STRIDE * esz;
-	if (cf32)
-		hipLaunchKernelGGL(ms_join_kernel<float2>, dim3(1), dim3(kThreads), 0, st, static_cast<const float2 *>(d_in),
-				   reinterpret_cast<const float2 *>(rem_in), reinterpret_cast<float2 *>(rem_out),
-				   static_cast<float2 *>(s->d_edge_row), s->carried, do_edge, keep, tail_at, n_tail);
-	else
-		hipLaunchKernelGGL(ms_join_kernel<uint32_t>, dim3(1), dim3(kThreads), 0, st, static_cast<const uint32_t *>(d_in),
-				   reinterpret_cast<const uint32_t *>(rem_in), reinterpret_cast<uint32_t *>(rem_out),
-				   static_cast<uint32_t *>(s->d_edge_row), s->carried, do_edge, keep, tail_at, n_tail);
-	return launched();
-}
-
-// the stream instance of ms_rx_kernel over `cnt` slots whose first has the clock (fn0, tn0); sum: the launch holds SCH slots
-// whose starts the cutter follows -- the correction word starts at zero and goes to the mailbox behind the launch
-int launch_rx(trxhip_ms_sched *s, const void *d_in, int cf32, bool edge, int64_t first, uint32_t fn0, int tn0, trxhip_ms_burst_ind *d_ind,
-	      int8_t *d_bits, size_t cnt, bool sum, hipStream_t st)
-{
-	trx_mss_stream sa;
-	memset(&sa, 0, sizeof(sa));
-	sa.edge_row = edge ? s->d_edge_row : nullptr;
-	sa.first = first;
-	sa.corr = sum ? s->d_corr : nullptr;
-	sa.fn0 = fn0;
-	sa.tn0 = (uint8_t)tn0;
-	sa.tsc = s->tsc;
-	sa.active = s->active;
-	if (sum && hipMemsetAsync(s->d_corr, 0, sizeof(int32_t), st) != hipSuccess)
-		return TRXHIP_EIO;
-	/* 1.f / float(rxFullScale) (ms_upper.cpp:203), as trxhip_ms_rx_batch_*() */
-	if (trx_launch_ms_rx_stream(d_in, !cf32, &sa, d_ind, d_bits, cnt, 1.0f / s->rx_full_scale, s->rx_full_scale, st) != 0)
-		return TRXHIP_EIO;
-	if (sum && (hipMemcpyAsync(s->h_corr, s->d_corr, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-		    hipEventRecord(s->ev_corr, st) != hipSuccess))
-		return TRXHIP_EIO;
-	return TRXHIP_OK;
-}
 
 // plan-only: the next fed start as handle_sch(false) would add it (:199-203)
 int64_t fed_correction(const ms_member &m, size_t &at)
@@ -410,84 +358,6 @@ void commit(ms_member &m, const ms_plan &p)
 	m.sch_slots += p.sch_all;
 }
 
-int pull(trxhip_ms_sched *s, const void *d_in, int cf32, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
-	 size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
-{
-	if (!s)
-		return TRXHIP_EINVAL;
-	const bool device = s->ctx != nullptr;
-	ms_plan p;
-	int rc = plan_begin(*s, device, device, cf32, n_samples, first_ts, d_in, d_ind, d_bits, out_slots, p);
-	if (rc != TRXHIP_OK)
-		return rc;
-	if (device && with_device(s->ctx))
-		return TRXHIP_EIO;
-	const hipStream_t st = static_cast<hipStream_t>(stream);
-
-	if (p.extend) {
-		if (device) {
-			if (launch_join(s, d_in, cf32, 0, s->carried, 0, (uint32_t)n_samples, st) != TRXHIP_OK ||
-			    hipEventRecord(s->ev, st) != hipSuccess)
-				return TRXHIP_EIO;
-			s->ev_used = true;
-			s->rem_half ^= 1;
-		}
-		commit(*s, p);
-		if (n_slots)
-			*n_slots = 0;
-		if (n_carried)
-			*n_carried = s->carried;
-		return TRXHIP_OK;
-	}
-
-	// the correction of the pull before: the first of the two waits
-	if (s->tracking && fold_correction(s) != TRXHIP_OK)
-		return TRXHIP_EIO;
-	// the straddling SCH slot alone: the second
-	int64_t prelim_corr = 0;
-	if (p.prelim && device) {
-		if (launch_join(s, d_in, cf32, 1, 0, 0, 0, st) != TRXHIP_OK ||
-		    launch_rx(s, d_in, cf32, true, 0, p.fn, p.tn, d_ind, d_bits, 1, true, st) != TRXHIP_OK ||
-		    hipEventSynchronize(s->ev_corr) != hipSuccess)
-			return TRXHIP_EIO;
-		prelim_corr = *s->h_corr;
-	}
-	rc = plan_finish(*s, device, device, out_slots, prelim_corr, p);
-	if (rc != TRXHIP_OK)
-		return rc;
-
-	if (device) {
-		rc = TRXHIP_OK;
-		const bool edge = p.straddle && !p.waited;
-		if (edge || p.frac)
-			rc = launch_join(s, d_in, cf32, edge, 0, (size_t)(p.to_skip + p.full * TRX_MSS_SLOT), (uint32_t)p.frac, st);
-		const size_t k0 = p.waited ? 1 : 0;
-		const bool sum = s->tracking && p.sch_full != 0;
-		if (rc == TRXHIP_OK && (size_t)p.cnt > k0) {
-			uint32_t fnk;
-			int tnk;
-			trx_mss_clock_add(p.fn0, p.tn0, k0, &fnk, &tnk);
-			rc = launch_rx(s, d_in, cf32, edge, p.to_skip, fnk, tnk, d_ind + k0, d_bits ? d_bits + k0 * 148 : nullptr, (size_t)p.cnt - k0,
-				       sum, st);
-		}
-		if (rc == TRXHIP_OK && hipEventRecord(s->ev, st) != hipSuccess)
-			rc = TRXHIP_EIO;
-		if (rc != TRXHIP_OK)
-			return TRXHIP_EIO;
-		s->ev_used = true;
-		if (p.frac)
-			s->rem_half ^= 1;
-		if (sum)
-			s->unread = true;
-	}
-	commit(*s, p);
-	if (n_slots)
-		*n_slots = (size_t)p.cnt;
-	if (n_carried)
-		*n_carried = (size_t)p.frac;
-	return TRXHIP_OK;
-}
-
 // what a found SCH burst sets (handle_sch(true), decode_sch(bits, true))
 void acquired(ms_member &m, const trxhip_sch_sync_result &r, int64_t first_ts)
 {
@@ -501,42 +371,6 @@ void acquired(ms_member &m, const trxhip_sch_sync_result &r, int64_t first_ts)
 	m.carried = 0;
 	m.pending = 0;
 	m.unread = false;
-}
-
-int acquire(trxhip_ms_sched *s, const void *d_buf, int cf32, size_t n_samples, int64_t first_ts, trxhip_sch_sync_result *h_res, void *stream)
-{
-	if (!s || n_samples < 512 + 20 || n_samples > TRXHIP_SCH_SYNC_MAX_LEN)
-		return TRXHIP_EINVAL;
-	trxhip_sch_sync_result r;
-	if (!s->ctx) {
-		if (d_buf || !h_res)
-			return TRXHIP_EINVAL;
-		r = *h_res;                                            /* plan-only: the receiver's answer comes from outside */
-	} else {
-		if (!d_buf || (reinterpret_cast<uintptr_t>(d_buf) & (cf32 ? 7 : 3)))
-			return TRXHIP_EINVAL;
-		const float scale = 1.0f / s->rx_full_scale;           /* 1.f / float(rxFullScale), :168 */
-		const int rc = cf32 ? trxhip_sch_sync_batch_cf32(s->ctx, static_cast<const float *>(d_buf), n_samples, s->d_acq, nullptr, 1, n_samples,
-								 TRXHIP_SCH_SYNC_ACQ, scale, stream)
-				    : trxhip_sch_sync_batch_i16(s->ctx, static_cast<const int16_t *>(d_buf), n_samples, s->d_acq, nullptr, 1, n_samples,
-								TRXHIP_SCH_SYNC_ACQ, scale, stream);
-		if (rc != TRXHIP_OK)
-			return rc;
-		const hipStream_t st = static_cast<hipStream_t>(stream);
-		if (hipMemcpyAsync(s->h_acq, s->d_acq, sizeof(r), hipMemcpyDeviceToHost, st) != hipSuccess ||
-		    hipEventRecord(s->ev, st) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
-			return TRXHIP_EIO;
-		s->ev_used = false;
-		r = *s->h_acq;
-		if (h_res)
-			*h_res = r;
-	}
-	if (r.rc != 1)
-		return 0;
-	if (r.fn < 0 || (uint32_t)r.fn >= TRX_MSS_HYPERFRAME)
-		return TRXHIP_EINVAL;
-	acquired(*s, r, first_ts);
-	return 1;
 }
 
 void set_clock(ms_member &m, uint32_t fn, int tn, int64_t ts)
@@ -626,18 +460,117 @@ char *stage_table(trxhip_ms_group *g)
 	return g->h_tab + (size_t)h * 2 * g->m.size() * 64;
 }
 
-// one launch set of a group pull: the table's n_rx receiver entries and n_join join entries (staged behind one another in `tab`)
-// go up in one copy; one join launch; with sum one clear of the correction words, and their copy to the mailbox behind the
-// receiver launch; one event behind all of it
-int issue_table(trxhip_ms_group *g, char *tab, size_t n_rx, size_t n_join, size_t n_waves, int cf32, bool sum, hipStream_t st)
+char *rem_of(trxhip_ms_group *g, size_t i, int half, int cf32)
 {
+	return g->d_rem + (i * 2 * TRX_MSS_REM_STRIDE) * 8 + (size_t)half * TRX_MSS_REM_STRIDE * (cf32 ? 8 : 4);
+}
+
+// What of its plan a member puts into a launch set.  prelim: the set of the second wait -- the straddling SCH slot alone, assembled
+// into its row and demodulated, its correction summed.  Else the pull's own set: a join where the partial slot is extended, a new
+// one is saved, or the straddling slot's row is still to assemble (edge), and the slots from k0 on -- slot 0 is through where
+// the pull has waited for it; sum: SCH slots whose starts the cutter follows are among them
+struct ms_work {
+	bool join, edge, sum;
+	size_t k0, n_slots;
+};
+
+ms_work work_of(const ms_member &m, const ms_plan &p, bool prelim)
+{
+	ms_work w;
+	w.edge = prelim || (!p.extend && p.straddle && !p.waited);
+	w.join = w.edge || p.extend || p.frac != 0;            /* (before plan_finish() p.frac is 0) */
+	w.k0 = (!prelim && p.waited) ? 1 : 0;
+	w.n_slots = prelim ? 1 : p.extend ? 0 : (size_t)p.cnt - w.k0;
+	w.sum = prelim || (m.tracking && p.sch_full != 0);
+	return w;
+}
+
+// One launch set of a pull, and the only place that knows what its entries hold and how they reach the device.  The set is the
+// prelim work of the members whose plan says prelim, or the pull's own work of every member with a chunk; the caller has counted
+// its n_rx receiver entries, n_join join entries and n_waves waves.
+// A group stages the entries as one table in the next pinned area, receiver entries first, and issues: one copy of the table, one
+// join launch over its join entries, one clear of the correction words where a member sums, one receiver launch over its receiver
+// entries, the copy of the correction words to the mailbox, one event behind all of it.
+// The single object (direct) issues the same sequence without the table: its one join entry and its one receiver entry are the
+// arguments of ms_join_kernel and of the receiver's stream form.
+int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf32, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+		size_t out_stride, bool prelim, size_t n_rx, size_t n_join, size_t n_waves, hipStream_t st)
+{
+	trx_mss_member own_rx;
+	trx_mss_join own_join;
+	trx_mss_member *rx = &own_rx;
+	trx_mss_join *jn = &own_join;
+	if (!g->direct) {
+		char *tab = stage_table(g);
+		if (!tab)
+			return TRXHIP_EIO;
+		rx = reinterpret_cast<trx_mss_member *>(tab);
+		jn = reinterpret_cast<trx_mss_join *>(tab + n_rx * 64);
+	}
 	if (n_rx + n_join == 0)
 		return TRXHIP_OK;                                      /* (no slot and no join: no sum either) */
-	if (hipMemcpyAsync(g->d_tab, tab, (n_rx + n_join) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
+
+	size_t kr = 0, kj = 0, wave = 0;
+	bool sum = false;
+	for (size_t i = 0; i < g->m.size(); i++) {
+		const ms_plan &p = g->plan[i];
+		if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK || (prelim && !p.prelim))
+			continue;
+		const ms_member &m = g->m[i];
+		const ms_work w = work_of(m, p, prelim);
+		char *edge_row = g->d_edge + i * TRX_MSS_SLOT * 8;
+		if (w.join) {
+			trx_mss_join &j = jn[kj++];
+			memset(&j, 0, sizeof(j));
+			j.in = h_chunks[i].d_in;
+			j.rem_in = rem_of(g, i, m.rem_half, cf32);
+			j.rem_out = rem_of(g, i, m.rem_half ^ 1, cf32);
+			j.edge_row = edge_row;
+			j.carried = m.carried;
+			j.do_edge = w.edge;
+			if (p.extend) {
+				j.keep = m.carried;
+				j.n_tail = (uint32_t)p.n_samples;
+			} else if (!prelim) {
+				j.tail_at = (uint64_t)(p.to_skip + p.full * TRX_MSS_SLOT);
+				j.n_tail = (uint32_t)p.frac;
+			}
+		}
+		if (!w.n_slots)
+			continue;
+		sum = sum || w.sum;
+		trx_mss_member &e = rx[kr++];
+		memset(&e, 0, sizeof(e));
+		uint32_t fnk = p.fn;                                   /* prelim: the straddling slot's clock */
+		int tnk = p.tn;
+		if (!prelim)
+			trx_mss_clock_add(p.fn0, p.tn0, w.k0, &fnk, &tnk);
+		e.chunk = h_chunks[i].d_in;
+		e.sa.edge_row = w.edge ? edge_row : nullptr;
+		e.sa.first = prelim ? 0 : p.to_skip;
+		e.sa.corr = w.sum ? g->d_corr + i : nullptr;
+		e.sa.fn0 = fnk;
+		e.sa.tn0 = (uint8_t)tnk;
+		e.sa.tsc = m.tsc;
+		e.sa.active = m.active;
+		e.ind = d_ind + i * out_stride + w.k0;
+		e.bits = d_bits ? d_bits + (i * out_stride + w.k0) * 148 : nullptr;
+		e.n_slots = (uint32_t)w.n_slots;
+		e.first_wave = (uint32_t)wave;
+		wave += (w.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
+	}
+	if (kr != n_rx || kj != n_join || wave != n_waves)
+		return TRXHIP_EIO;
+
+	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, (n_rx + n_join) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
 		return TRXHIP_EIO;
 	if (n_join) {
-		const trx_mss_join *jt = reinterpret_cast<const trx_mss_join *>(g->d_tab + n_rx * 64);
-		if (cf32)
+		const trx_mss_join *jt = g->direct ? nullptr : reinterpret_cast<const trx_mss_join *>(g->d_tab + n_rx * 64);
+		if (g->direct && cf32)
+			hipLaunchKernelGGL(ms_join_kernel<float2>, dim3(1), dim3(kThreads), 0, st, *jn);
+		else if (g->direct)
+			hipLaunchKernelGGL(ms_join_kernel<uint32_t>, dim3(1), dim3(kThreads), 0, st, *jn);
+		else if (cf32)
 			hipLaunchKernelGGL(ms_join_group_kernel<float2>, dim3((unsigned)n_join), dim3(kThreads), 0, st, jt);
 		else
 			hipLaunchKernelGGL(ms_join_group_kernel<uint32_t>, dim3((unsigned)n_join), dim3(kThreads), 0, st, jt);
@@ -647,9 +580,14 @@ int issue_table(trxhip_ms_group *g, char *tab, size_t n_rx, size_t n_join, size_
 	const size_t corr_bytes = g->m.size() * sizeof(int32_t);
 	if (sum && hipMemsetAsync(g->d_corr, 0, corr_bytes, st) != hipSuccess)
 		return TRXHIP_EIO;
-	if (n_rx && trx_launch_ms_rx_group(reinterpret_cast<const trx_mss_member *>(g->d_tab), !cf32, n_rx, n_waves, 1.0f / g->rx_full_scale,
-					   g->rx_full_scale, st) != 0)
-		return TRXHIP_EIO;
+	if (n_rx) {
+		const float fs = g->rx_full_scale;                     /* 1.f / float(rxFullScale) (ms_upper.cpp:203), as trxhip_ms_rx_batch_*() */
+		const int rc = g->direct ? trx_launch_ms_rx_stream(rx->chunk, !cf32, &rx->sa, rx->ind, rx->bits, rx->n_slots, 1.0f / fs, fs, st)
+					 : trx_launch_ms_rx_group(reinterpret_cast<const trx_mss_member *>(g->d_tab), !cf32, n_rx, n_waves,
+								  1.0f / fs, fs, st);
+		if (rc != 0)
+			return TRXHIP_EIO;
+	}
 	if (sum && hipMemcpyAsync(g->h_corr, g->d_corr, corr_bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
 		return TRXHIP_EIO;
 	const int h = g->tab_at;
@@ -662,11 +600,6 @@ int issue_table(trxhip_ms_group *g, char *tab, size_t n_rx, size_t n_join, size_
 	return TRXHIP_OK;
 }
 
-char *rem_of(trxhip_ms_group *g, size_t i, int half, int cf32)
-{
-	return g->d_rem + (i * 2 * TRX_MSS_REM_STRIDE) * 8 + (size_t)half * TRX_MSS_REM_STRIDE * (cf32 ? 8 : 4);
-}
-
 int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf32, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
 	       size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream)
 {
@@ -676,7 +609,8 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		return TRXHIP_EINVAL;
 	const size_t n = g->m.size();
 	const bool device = g->ctx != nullptr;
-	const bool bounded = device || out_stride != 0;                /* a plan-only group checks the counts against a stride it is given */
+	/* a plan-only group checks the counts against a stride it is given; the plan-only single object checks none */
+	const bool bounded = device || (!g->direct && out_stride != 0);
 	size_t first = n;
 	for (size_t i = n; i-- > 0;)
 		if (h_chunks[i].n_samples)
@@ -697,7 +631,8 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 			worst = rc;
 		}
 	};
-	bool any_tracked = false, any_prelim = false;
+	bool any_tracked = false;
+	size_t n_pre = 0;
 	for (size_t i = 0; i < n; i++) {
 		g->rc[i] = TRXHIP_OK;
 		if (!h_chunks[i].n_samples)
@@ -710,7 +645,7 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		}
 		if (!g->plan[i].extend) {
 			any_tracked = any_tracked || g->m[i].tracking;
-			any_prelim = any_prelim || g->plan[i].prelim;
+			n_pre += g->plan[i].prelim;
 		}
 	}
 
@@ -719,45 +654,10 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		return TRXHIP_EIO;
 
 	// ---- the straddling SCH slots the cutters follow, one slot per member in one launch set: the second
-	if (device && any_prelim) {
-		char *tab = stage_table(g);
-		if (!tab)
-			return TRXHIP_EIO;
-		size_t n_pre = 0;
-		for (size_t i = 0; i < n; i++)
-			n_pre += h_chunks[i].n_samples && g->rc[i] == TRXHIP_OK && g->plan[i].prelim;
-		trx_mss_member *rx = reinterpret_cast<trx_mss_member *>(tab);
-		trx_mss_join *jn = reinterpret_cast<trx_mss_join *>(tab + n_pre * 64);
-		size_t k = 0;
-		for (size_t i = 0; i < n; i++) {
-			const ms_plan &p = g->plan[i];
-			if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK || !p.prelim)
-				continue;
-			char *edge = g->d_edge + i * TRX_MSS_SLOT * 8;
-			memset(&rx[k], 0, sizeof(rx[k]));
-			rx[k].chunk = h_chunks[i].d_in;
-			rx[k].sa.edge_row = edge;
-			rx[k].sa.corr = g->d_corr + i;
-			rx[k].sa.fn0 = p.fn;
-			rx[k].sa.tn0 = (uint8_t)p.tn;
-			rx[k].sa.tsc = g->m[i].tsc;
-			rx[k].sa.active = g->m[i].active;
-			rx[k].ind = d_ind + i * out_stride;
-			rx[k].bits = d_bits ? d_bits + i * out_stride * 148 : nullptr;
-			rx[k].n_slots = 1;
-			rx[k].first_wave = (uint32_t)k;
-			memset(&jn[k], 0, sizeof(jn[k]));
-			jn[k].in = h_chunks[i].d_in;
-			jn[k].rem_in = rem_of(g, i, g->m[i].rem_half, cf32);
-			jn[k].rem_out = rem_of(g, i, g->m[i].rem_half ^ 1, cf32);
-			jn[k].edge_row = edge;
-			jn[k].carried = p.carried;
-			jn[k].do_edge = 1;
-			k++;
-		}
-		if (issue_table(g, tab, n_pre, n_pre, n_pre, cf32, true, st) != TRXHIP_OK || hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess)
-			return TRXHIP_EIO;
-	}
+	if (device && n_pre &&
+	    (issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, true, n_pre, n_pre, n_pre, st) != TRXHIP_OK ||
+	     hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess))
+		return TRXHIP_EIO;
 
 	// ---- the rest of every plan
 	size_t n_rx = 0, n_join = 0, n_waves = 0;
@@ -765,21 +665,18 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK)
 			continue;
 		ms_plan &p = g->plan[i];
-		if (p.extend) {
-			n_join++;
-			continue;
+		if (!p.extend) {
+			const int rc = plan_finish(g->m[i], device, bounded, out_stride, (device && p.prelim) ? g->h_corr[i] : 0, p);
+			if (rc != TRXHIP_OK) {
+				refuse(i, rc);
+				continue;
+			}
 		}
-		const int rc = plan_finish(g->m[i], device, bounded, out_stride, (device && p.prelim) ? g->h_corr[i] : 0, p);
-		if (rc != TRXHIP_OK) {
-			refuse(i, rc);
-			continue;
-		}
-		const size_t k0 = p.waited ? 1 : 0;
-		if ((p.straddle && !p.waited) || p.frac)
-			n_join++;
-		if ((size_t)p.cnt > k0) {
+		const ms_work w = work_of(g->m[i], p, false);
+		n_join += w.join;
+		if (w.n_slots) {
 			n_rx++;
-			n_waves += ((size_t)p.cnt - k0 + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
+			n_waves += (w.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
 		}
 	}
 	if (bad == n && n_waves > 0x7fffffffu) {
@@ -792,64 +689,9 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		return worst;
 	}
 
-	// ---- the issue: one table, one join launch, one clear, one receiver launch, one mailbox copy
-	if (device) {
-		char *tab = stage_table(g);
-		if (!tab)
-			return TRXHIP_EIO;
-		trx_mss_member *rx = reinterpret_cast<trx_mss_member *>(tab);
-		trx_mss_join *jn = reinterpret_cast<trx_mss_join *>(tab + n_rx * 64);
-		size_t kr = 0, kj = 0, wave = 0;
-		bool any_sum = false;
-		for (size_t i = 0; i < n; i++) {
-			if (!h_chunks[i].n_samples)
-				continue;
-			const ms_plan &p = g->plan[i];
-			const ms_member &m = g->m[i];
-			char *edge_row = g->d_edge + i * TRX_MSS_SLOT * 8;
-			const bool edge = !p.extend && p.straddle && !p.waited;
-			if (p.extend || edge || p.frac) {
-				trx_mss_join &j = jn[kj++];
-				memset(&j, 0, sizeof(j));
-				j.in = h_chunks[i].d_in;
-				j.rem_in = rem_of(g, i, m.rem_half, cf32);
-				j.rem_out = rem_of(g, i, m.rem_half ^ 1, cf32);
-				j.edge_row = edge_row;
-				j.carried = m.carried;
-				j.do_edge = edge;
-				j.keep = p.extend ? m.carried : 0;
-				j.tail_at = p.extend ? 0 : (uint64_t)(p.to_skip + p.full * TRX_MSS_SLOT);
-				j.n_tail = p.extend ? (uint32_t)p.n_samples : (uint32_t)p.frac;
-			}
-			const size_t k0 = p.waited ? 1 : 0;
-			if (p.extend || (size_t)p.cnt <= k0)
-				continue;
-			const bool sum = m.tracking && p.sch_full != 0;
-			any_sum = any_sum || sum;
-			trx_mss_member &e = rx[kr++];
-			memset(&e, 0, sizeof(e));
-			uint32_t fnk;
-			int tnk;
-			trx_mss_clock_add(p.fn0, p.tn0, k0, &fnk, &tnk);
-			e.chunk = h_chunks[i].d_in;
-			e.sa.edge_row = edge ? edge_row : nullptr;
-			e.sa.first = p.to_skip;
-			e.sa.corr = sum ? g->d_corr + i : nullptr;
-			e.sa.fn0 = fnk;
-			e.sa.tn0 = (uint8_t)tnk;
-			e.sa.tsc = m.tsc;
-			e.sa.active = m.active;
-			e.ind = d_ind + i * out_stride + k0;
-			e.bits = d_bits ? d_bits + (i * out_stride + k0) * 148 : nullptr;
-			e.n_slots = (uint32_t)((size_t)p.cnt - k0);
-			e.first_wave = (uint32_t)wave;
-			wave += (e.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
-		}
-		if (kr != n_rx || kj != n_join || wave != n_waves)
-			return TRXHIP_EIO;
-		if (issue_table(g, tab, n_rx, n_join, n_waves, cf32, any_sum, st) != TRXHIP_OK)
-			return TRXHIP_EIO;
-	}
+	// ---- the issue: the pull's own launch set
+	if (device && issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, false, n_rx, n_join, n_waves, st) != TRXHIP_OK)
+		return TRXHIP_EIO;
 
 	// ---- and every member moves
 	for (size_t i = 0; i < n; i++) {
@@ -859,7 +701,7 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 			if (device) {
 				if (p.extend || p.frac)
 					m.rem_half ^= 1;
-				if (!p.extend && m.tracking && p.sch_full != 0)
+				if (work_of(m, p, false).sum)
 					m.unread = true;
 			}
 			commit(m, p);
@@ -924,164 +766,8 @@ int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const v
 ms_member *member_of(trxhip_ms_group *g, uint32_t i) { return (g && i < g->m.size()) ? &g->m[i] : nullptr; }
 const ms_member *member_of(const trxhip_ms_group *g, uint32_t i) { return (g && i < g->m.size()) ? &g->m[i] : nullptr; }
 
-}  // namespace
-
-extern "C" {
-
-int trxhip_ms_sched_create(trxhip_ctx *ctx, const trxhip_ms_sched_cfg *cfg, trxhip_ms_sched **out)
-{
-	if (!cfg || !out || !cfg_ok(cfg))
-		return TRXHIP_EINVAL;
-	if (ctx && with_device(ctx))
-		return TRXHIP_EINVAL;
-	trxhip_ms_sched *s = new (std::nothrow) trxhip_ms_sched();
-	if (!s)
-		return TRXHIP_ENOMEM;
-	s->rx_full_scale = cfg->rx_full_scale;
-	s->tsc = cfg->tsc;
-	s->active = cfg->active_tns;
-	s->tracking = cfg->tracking != 0;
-	if (!ctx) {
-		*out = s;
-		return TRXHIP_OK;
-	}
-	s->ctx = ctx;
-	const size_t rem_bytes = 2 * TRX_MSS_REM_STRIDE * 8;
-	bool ok = hipMalloc(&s->d_rem, rem_bytes) == hipSuccess && hipMalloc(&s->d_edge_row, TRX_MSS_SLOT * 8) == hipSuccess &&
-		  hipMalloc((void **)&s->d_corr, sizeof(int32_t)) == hipSuccess && hipMalloc((void **)&s->d_acq, sizeof(*s->d_acq)) == hipSuccess &&
-		  hipHostMalloc((void **)&s->h_corr, sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
-		  hipHostMalloc((void **)&s->h_acq, sizeof(*s->h_acq), hipHostMallocDefault) == hipSuccess &&
-		  hipEventCreateWithFlags(&s->ev_corr, hipEventDisableTiming) == hipSuccess &&
-		  hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) == hipSuccess;
-	ok = ok && hipMemset(s->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(s->d_corr, 0, sizeof(int32_t)) == hipSuccess &&
-	     hipStreamSynchronize(nullptr) == hipSuccess;      /* the first pull may come on a stream that does not wait for the null stream */
-	if (!ok) {
-		trxhip_ms_sched_destroy(s);
-		return TRXHIP_ENOMEM;
-	}
-	*s->h_corr = 0;
-	*out = s;
-	return TRXHIP_OK;
-}
-
-void trxhip_ms_sched_destroy(trxhip_ms_sched *s)
-{
-	if (!s)
-		return;
-	if (s->ctx && with_device(s->ctx) == 0) {
-		if (s->unread && s->ev_corr)
-			(void)hipEventSynchronize(s->ev_corr);
-		if (s->ev_used && s->ev)
-			(void)hipEventSynchronize(s->ev);
-		if (s->ev_corr) (void)hipEventDestroy(s->ev_corr);
-		if (s->ev) (void)hipEventDestroy(s->ev);
-		void *bufs[] = { s->d_rem, s->d_edge_row, s->d_corr, s->d_acq };
-		for (void *p : bufs)
-			if (p) (void)hipFree(p);
-		if (s->h_corr) (void)hipHostFree(s->h_corr);
-		if (s->h_acq) (void)hipHostFree(s->h_acq);
-	}
-	delete s;
-}
-
-int trxhip_ms_sched_set_clock(trxhip_ms_sched *s, uint32_t fn, int tn, int64_t ts)
-{
-	if (!s || fn >= TRX_MSS_HYPERFRAME || tn < 0 || tn > 7)
-		return TRXHIP_EINVAL;
-	set_clock(*s, fn, tn, ts);
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_sched_clock(const trxhip_ms_sched *s, uint32_t *fn, int *tn, int64_t *ts)
-{
-	if (!s || !fn || !tn || !ts || !s->clock_set)
-		return TRXHIP_EINVAL;
-	*fn = s->fn;
-	*tn = s->tn;
-	*ts = s->ts;
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_sched_set_tsc(trxhip_ms_sched *s, int tsc)
-{
-	if (!s || tsc < 0 || tsc > 7)
-		return TRXHIP_EINVAL;
-	s->tsc = (uint8_t)tsc;
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_sched_set_active(trxhip_ms_sched *s, uint8_t tn_mask)
-{
-	if (!s)
-		return TRXHIP_EINVAL;
-	s->active = tn_mask;
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_sched_set_tracking(trxhip_ms_sched *s, int on)
-{
-	if (!s)
-		return TRXHIP_EINVAL;
-	s->tracking = on != 0;
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_sched_feed_starts(trxhip_ms_sched *s, const int32_t *starts, size_t n)
-{
-	if (!s || s->ctx || (!starts && n))
-		return TRXHIP_EINVAL;
-	s->feed.assign(starts, starts + n);                            /* replaces what is still queued */
-	s->feed_at = 0;
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_sched_acquire_s16(trxhip_ms_sched *s, const int16_t *d_buf, size_t n_samples, int64_t first_ts, trxhip_sch_sync_result *h_res,
-				void *stream)
-{
-	return acquire(s, d_buf, 0, n_samples, first_ts, h_res, stream);
-}
-
-int trxhip_ms_sched_acquire_cf32(trxhip_ms_sched *s, const float *d_buf, size_t n_samples, int64_t first_ts, trxhip_sch_sync_result *h_res,
-				 void *stream)
-{
-	return acquire(s, d_buf, 1, n_samples, first_ts, h_res, stream);
-}
-
-int64_t trxhip_ms_sched_slots(const trxhip_ms_sched *s, size_t n_samples)
-{
-	return s ? slots_of(*s, n_samples) : TRXHIP_EINVAL;
-}
-
-int trxhip_ms_sched_pull_s16(trxhip_ms_sched *s, const int16_t *d_in, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind,
-			     int8_t *d_bits, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
-{
-	return pull(s, d_in, 0, n_samples, first_ts, d_ind, d_bits, out_slots, n_slots, n_carried, stream);
-}
-
-int trxhip_ms_sched_pull_cf32(trxhip_ms_sched *s, const float *d_in, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind,
-			      int8_t *d_bits, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
-{
-	return pull(s, d_in, 1, n_samples, first_ts, d_ind, d_bits, out_slots, n_slots, n_carried, stream);
-}
-
-int trxhip_ms_sched_plan(const trxhip_ms_sched *s, trxhip_ms_plan *h_out, size_t n)
-{
-	return s ? plan_of(*s, h_out, n) : TRXHIP_EINVAL;
-}
-
-int trxhip_ms_sched_state(trxhip_ms_sched *s, trxhip_ms_sched_status *out)
-{
-	if (!s || !out)
-		return TRXHIP_EINVAL;
-	if (s->ctx && fold_correction(s) != TRXHIP_OK)
-		return TRXHIP_EIO;
-	state_of(*s, out);
-	return TRXHIP_OK;
-}
-
-// ---- the group ----------------------------------------------------------------------------------
-
-int trxhip_ms_group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const trxhip_ms_sched_cfg *cfgs, trxhip_ms_group **out)
+// direct: the single object, which needs no table
+int group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const trxhip_ms_sched_cfg *cfgs, bool direct, trxhip_ms_group **out)
 {
 	if (!cfgs || !out || n_members < 1 || n_members > TRXHIP_MS_GROUP_MAX_MEMBERS || !std::isfinite(rx_full_scale) || !(rx_full_scale > 0.0f))
 		return TRXHIP_EINVAL;
@@ -1094,11 +780,11 @@ int trxhip_ms_group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_member
 	if (!g)
 		return TRXHIP_ENOMEM;
 	g->rx_full_scale = rx_full_scale;
+	g->direct = direct;
 	g->m.resize(n_members);
 	g->plan.resize(n_members);
 	g->rc.resize(n_members);
 	for (size_t i = 0; i < n_members; i++) {
-		g->m[i].rx_full_scale = rx_full_scale;
 		g->m[i].tsc = cfgs[i].tsc;
 		g->m[i].active = cfgs[i].active_tns;
 		g->m[i].tracking = cfgs[i].tracking != 0;
@@ -1112,15 +798,16 @@ int trxhip_ms_group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_member
 	const size_t rem_bytes = n * 2 * TRX_MSS_REM_STRIDE * 8, tab_bytes = 2 * n * 64;     /* tab_bytes: one table */
 	bool ok = hipMalloc((void **)&g->d_rem, rem_bytes) == hipSuccess && hipMalloc((void **)&g->d_edge, n * TRX_MSS_SLOT * 8) == hipSuccess &&
 		  hipMalloc((void **)&g->d_corr, n * sizeof(int32_t)) == hipSuccess && hipMalloc((void **)&g->d_acq, n * sizeof(*g->d_acq)) == hipSuccess &&
-		  hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
 		  hipHostMalloc((void **)&g->h_corr, n * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
 		  hipHostMalloc((void **)&g->h_acq, n * sizeof(*g->h_acq), hipHostMallocDefault) == hipSuccess &&
-		  hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess &&
 		  hipEventCreateWithFlags(&g->ev, hipEventDisableTiming) == hipSuccess;
+	if (!direct)
+		ok = ok && hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
+		     hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess;
 	for (int h = 0; h < kTabSlots; h++)
 		ok = ok && hipEventCreateWithFlags(&g->ev_tab[h], hipEventDisableTiming) == hipSuccess;
 	ok = ok && hipMemset(g->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(g->d_corr, 0, n * sizeof(int32_t)) == hipSuccess &&
-	     hipStreamSynchronize(nullptr) == hipSuccess;
+	     hipStreamSynchronize(nullptr) == hipSuccess;      /* the first pull may come on a stream that does not wait for the null stream */
 	if (!ok) {
 		trxhip_ms_group_destroy(g);
 		return TRXHIP_ENOMEM;
@@ -1130,6 +817,20 @@ int trxhip_ms_group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_member
 	return TRXHIP_OK;
 }
 
+// the single object's handle and the group of one behind it
+trxhip_ms_group *group_of(trxhip_ms_sched *s) { return reinterpret_cast<trxhip_ms_group *>(s); }
+const trxhip_ms_group *group_of(const trxhip_ms_sched *s) { return reinterpret_cast<const trxhip_ms_group *>(s); }
+
+}  // namespace
+
+extern "C" {
+
+int trxhip_ms_group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const trxhip_ms_sched_cfg *cfgs, trxhip_ms_group **out)
+{
+	return group_create(ctx, rx_full_scale, n_members, cfgs, false, out);
+}
+
+// waits for what is in flight before it frees
 void trxhip_ms_group_destroy(trxhip_ms_group *g)
 {
 	if (!g)
@@ -1255,6 +956,72 @@ int trxhip_ms_group_pull_cf32(trxhip_ms_group *g, const trxhip_ms_group_chunk *h
 			      size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream)
 {
 	return group_pull(g, h_chunks, 1, d_ind, d_bits, out_stride, h_n_slots, h_n_carried, bad_member, stream);
+}
+
+// ---- the single object: member 0 of a group of one that issues directly -------------------------
+
+int trxhip_ms_sched_create(trxhip_ctx *ctx, const trxhip_ms_sched_cfg *cfg, trxhip_ms_sched **out)
+{
+	trxhip_ms_group *g = nullptr;
+	if (!cfg || !out)
+		return TRXHIP_EINVAL;
+	const int rc = group_create(ctx, cfg->rx_full_scale, 1, cfg, true, &g);
+	if (rc == TRXHIP_OK)
+		*out = reinterpret_cast<trxhip_ms_sched *>(g);
+	return rc;
+}
+
+void trxhip_ms_sched_destroy(trxhip_ms_sched *s) { trxhip_ms_group_destroy(group_of(s)); }
+
+int trxhip_ms_sched_set_clock(trxhip_ms_sched *s, uint32_t fn, int tn, int64_t ts) { return trxhip_ms_group_set_clock(group_of(s), 0, fn, tn, ts); }
+
+int trxhip_ms_sched_clock(const trxhip_ms_sched *s, uint32_t *fn, int *tn, int64_t *ts) { return trxhip_ms_group_clock(group_of(s), 0, fn, tn, ts); }
+
+int trxhip_ms_sched_set_tsc(trxhip_ms_sched *s, int tsc) { return trxhip_ms_group_set_tsc(group_of(s), 0, tsc); }
+
+int trxhip_ms_sched_set_active(trxhip_ms_sched *s, uint8_t tn_mask) { return trxhip_ms_group_set_active(group_of(s), 0, tn_mask); }
+
+int trxhip_ms_sched_set_tracking(trxhip_ms_sched *s, int on) { return trxhip_ms_group_set_tracking(group_of(s), 0, on); }
+
+int trxhip_ms_sched_feed_starts(trxhip_ms_sched *s, const int32_t *starts, size_t n)
+{
+	return trxhip_ms_group_feed_starts(group_of(s), 0, starts, n);
+}
+
+int64_t trxhip_ms_sched_slots(const trxhip_ms_sched *s, size_t n_samples) { return trxhip_ms_group_slots(group_of(s), 0, n_samples); }
+
+int trxhip_ms_sched_plan(const trxhip_ms_sched *s, trxhip_ms_plan *h_out, size_t n) { return trxhip_ms_group_plan(group_of(s), 0, h_out, n); }
+
+int trxhip_ms_sched_state(trxhip_ms_sched *s, trxhip_ms_sched_status *out) { return trxhip_ms_group_state(group_of(s), 0, out); }
+
+// 1 (found) or 0, as the group's count of one buffer
+int trxhip_ms_sched_acquire_s16(trxhip_ms_sched *s, const int16_t *d_buf, size_t n_samples, int64_t first_ts, trxhip_sch_sync_result *h_res,
+				void *stream)
+{
+	const uint32_t member = 0;
+	return group_acquire(group_of(s), &member, 1, d_buf, 0, n_samples, n_samples, &first_ts, h_res, nullptr, stream);
+}
+
+int trxhip_ms_sched_acquire_cf32(trxhip_ms_sched *s, const float *d_buf, size_t n_samples, int64_t first_ts, trxhip_sch_sync_result *h_res,
+				 void *stream)
+{
+	const uint32_t member = 0;
+	return group_acquire(group_of(s), &member, 1, d_buf, 1, n_samples, n_samples, &first_ts, h_res, nullptr, stream);
+}
+
+// one chunk, out_slots as the stride; *n_slots and *n_carried (the new partial slot, or the extended one) are member 0's
+int trxhip_ms_sched_pull_s16(trxhip_ms_sched *s, const int16_t *d_in, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind,
+			     int8_t *d_bits, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
+{
+	const trxhip_ms_group_chunk c = { d_in, n_samples, first_ts };
+	return group_pull(group_of(s), &c, 0, d_ind, d_bits, out_slots, n_slots, n_carried, nullptr, stream);
+}
+
+int trxhip_ms_sched_pull_cf32(trxhip_ms_sched *s, const float *d_in, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind,
+			      int8_t *d_bits, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
+{
+	const trxhip_ms_group_chunk c = { d_in, n_samples, first_ts };
+	return group_pull(group_of(s), &c, 1, d_ind, d_bits, out_slots, n_slots, n_carried, nullptr, stream);
 }
 
 }  // extern "C"
