@@ -1167,6 +1167,60 @@ int  trxhip_ms_tx_submit(trxhip_ms_tx *s, const trxhip_ms_tx_req *h_reqs, size_t
 int  trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, int64_t first_ts, size_t *n_drawn, void *stream);
 int  trxhip_ms_tx_state(const trxhip_ms_tx *s, trxhip_ms_tx_status *out);
 
+/* ---- The MS-side uplink scheduler group: N uplink streams, their submits and their renders each issued as one step ----------
+ * N of the objects above behind one radio type: tx_full_scale, rxtx_delay and max_pending (per member) belong to the group, and
+ * every member has its own timing advance, queue, window state and counters.  A member IS the single object -- the same code
+ * plans its requests, places them in its queue, walks its windows and retires its bursts -- so per request the plan record and
+ * the status rules (LATE, WRAPPED, EXPIRED, OVERLAP, FULL, QUEUED, in that order), and per member the 96-byte state record, are
+ * the single object's, and so is every int16 of a member's window.
+ * submit: h_member[i] names the member of request i; requests of one member keep their order, members do not interact.  h_now
+ *   holds one clock per member (trxhip_ms_group_clock()) and is read only for the members that are named.  All or nothing: a
+ *   member index out of range, tn > 7, fn >= 2715648 or a bad clock of a named member fails the whole call with every member
+ *   untouched, *bad (may be NULL; (size_t)-1 otherwise) the first such request.  h_plan (may be NULL): one record per request.
+ *   Issued per call, whatever N is: the QUEUED rows (160 bytes each), packed and followed by their ring destinations, go up in one
+ *   copy from one of four pinned buffers taken in turn; one launch scatters them into the [N][max_pending] ring; one event.
+ * render: member m's window [h_first_ts[m], h_first_ts[m] + h_n_samples[m]) is written at d_out + 2 * m * out_stride int16.
+ *   h_n_samples[m] == 0: member m is not rendered and its state does not move.  Every member has its own window, as every MS has
+ *   its own timebase.  Every sample of every rendered window is written exactly once, nothing outside a window is written.
+ *   h_n_drawn (may be NULL): N values, per member the bursts this render retired as drawn.  All or nothing: a window that goes
+ *   backwards, h_n_samples[m] > out_stride (or > 2^31), |h_first_ts[m]| > 2^62 fails the call with *bad_member (may be NULL; -1
+ *   otherwise) the lowest such member, no member moved and no sample written; so does a d_out that is NULL or not 4-byte
+ *   aligned, and a render of more than 2^31 - 1 tiles of 625 samples.
+ *   Issued per call, whatever N is: one copy of a table from one of four pinned areas taken in turn -- 32 bytes per rendered
+ *   member {out offset, n_samples, first_wave, first burst, n_bursts}, then 8 bytes {radio_ts - first_ts, ring row} per queued
+ *   burst with samples in that member's window, no zero stretches -- one launch (one wave per tile of at most 625 samples) and
+ *   one event.
+ * Waits: a submit waits for the submit issued 4 submits earlier, a render for the render issued 4 renders earlier (a pinned area
+ *   is written again only behind the event of the launch that read its copy), and either may allocate when a call is larger
+ *   than any before.  Nothing else waits; nothing calls hipDeviceSynchronize.  Issue every call of one group on one stream; one
+ *   group is not thread-safe.  TRXHIP_EIO from submit or render: destroy the group.
+ * ctx == NULL: a plan-only group -- submit, plan, windows, counters; render takes d_out == NULL, and out_stride == 0 leaves the
+ *   window lengths unbounded while any other value bounds them as on the GPU.
+ * TRXHIP_EINVAL from create: n_members outside 1 .. 4096, what the single object refuses (tx_full_scale > 21477, max_pending
+ *   outside 1 .. 2^22), n_members * max_pending > 2^32 - 1. */
+#define TRXHIP_MS_TX_GROUP_MAX_MEMBERS 4096
+typedef struct trxhip_ms_tx_group_cfg {
+	uint32_t n_members;      /* 1 .. 4096 */
+	uint32_t tx_full_scale;  /* as trxhip_ms_tx_cfg, for every member */
+	int32_t  rxtx_delay;
+	uint32_t max_pending;    /* queued bursts per member */
+} trxhip_ms_tx_group_cfg;
+typedef struct trxhip_ms_tx_clock {  /* 16 bytes: a member's timekeeper pair */
+	uint32_t fn;
+	int32_t  tn;
+	int64_t  ts;
+} trxhip_ms_tx_clock;
+typedef struct trxhip_ms_tx_group trxhip_ms_tx_group;
+int  trxhip_ms_tx_group_create(trxhip_ctx *ctx, const trxhip_ms_tx_group_cfg *cfg, trxhip_ms_tx_group **out);
+void trxhip_ms_tx_group_destroy(trxhip_ms_tx_group *g);
+int  trxhip_ms_tx_group_size(const trxhip_ms_tx_group *g);   /* n_members */
+int  trxhip_ms_tx_group_set_ta(trxhip_ms_tx_group *g, uint32_t member, int val);
+int  trxhip_ms_tx_group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, const trxhip_ms_tx_req *h_reqs, size_t n,
+			       const trxhip_ms_tx_clock *h_now, trxhip_ms_tx_plan *h_plan, size_t *bad, void *stream);
+int  trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t out_stride, const int64_t *h_first_ts,
+				   const size_t *h_n_samples, size_t *h_n_drawn, int *bad_member, void *stream);
+int  trxhip_ms_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_tx_status *out);
+
 #ifdef __cplusplus
 }
 #endif

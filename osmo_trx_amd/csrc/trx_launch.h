@@ -166,6 +166,14 @@ struct trx_mstx_seg;
 struct trx_mstx_row;
 int trx_launch_ms_tx_render(const trx_mstx_seg *d_segs, size_t n_segs, const trx_mstx_row *d_rows, const trx_tx_tables *d_tab,
 			    int16_t *d_out, hipStream_t stream);
+/* the group's two launches (trx_tx.hip): ms_tx_stage_kernel scatters the n rows of a submit to ring rows d_dst[i] < ring_rows;
+ * ms_tx_render_group_kernel draws the n_waves tiles of the n_entries members of a table (trx_ms_tx.h), its bursts behind the
+ * entries, into d_out (int16 I, Q; 4-byte aligned) */
+struct trx_mstx_gmember;
+int trx_launch_ms_tx_stage(const trx_mstx_row *d_src, const uint32_t *d_dst, size_t n, trx_mstx_row *d_rows, size_t ring_rows,
+			   hipStream_t stream);
+int trx_launch_ms_tx_render_group(const trx_mstx_gmember *d_tab, uint32_t n_entries, uint32_t n_waves, const trx_mstx_row *d_rows,
+				  const trx_tx_tables *d_tab_tx, int16_t *d_out, hipStream_t stream);
 /* trx_capi.cpp: a transmit front end's logical channels, block length and output samples per block */
 int trx_tx_frontend_geometry(const trxhip_tx_frontend *f, int *chans, int *block_len, size_t *out_per_block);
 

@@ -10,6 +10,12 @@
 // stretches of queued bursts and zeros in between, at most 625 samples each, that tile the window.  The device half
 // (trx_tx.hip, ms_tx_render_kernel) draws every segment where it lies.  With ctx == NULL the object is plan-only: the same
 // arithmetic and queue, no device memory.
+//
+// The group (trxhip_ms_tx_group_*) is N such members behind one radio type.  A member -- its timing advance, queue, window state,
+// counters and ring rows -- is one struct (Member) with one set of rules (plan_request, queue_place, place_request, retire,
+// walk_window), used by the single object and by every member of a group alike.  The single object tiles its window with host-made
+// segments; the group uploads one table per render -- an entry per rendered member, then the queued bursts that intersect its
+// window -- and ms_tx_render_group_kernel finds each tile's bursts on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -104,22 +110,28 @@ double pulse_bound()
 	return best * (1.0 + 1.0 / (1 << 20));      /* the float roundings of at most 6 products, 6 sums and the scale: < 2^-20 */
 }
 
-}  // namespace
-
-struct trxhip_ms_tx {
-	trxhip_ctx *ctx = nullptr;
-	trxhip_ms_tx_cfg cfg{};
+// One MS: what set_ta(), submit_burst() and the windows of its stream act on.  The single object is one, a group has N.
+struct Member {
 	int32_t timing_advance = 0;
 	std::vector<Pending> q;                    /* [head, size): queued bursts by radio_ts */
 	size_t head = 0;
 	bool window_set = false;
 	int64_t rendered_end = 0;
 	trxhip_ms_tx_status ctr{};
+	// ring rows (device objects only)
+	std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> free_rows;   /* freed rows, lowest first */
+	uint32_t fresh = 0;                        /* rows >= fresh were never used */
+};
+
+}  // namespace
+
+struct trxhip_ms_tx {
+	trxhip_ctx *ctx = nullptr;
+	trxhip_ms_tx_cfg cfg{};
+	Member m;
 
 	// device state (ctx != NULL)
 	trx_mstx_row *d_rows = nullptr;
-	std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> free_rows;   /* freed rows, lowest first */
-	uint32_t fresh = 0;                        /* rows >= fresh were never used */
 	PinBuf stage[kBufs];                       /* submit: the call's rows */
 	int next_stage = 0;
 	PinBuf seg[kBufs];                         /* render: the window's segments */
@@ -129,9 +141,27 @@ struct trxhip_ms_tx {
 	std::vector<uint32_t> call_rows;
 };
 
+struct trxhip_ms_tx_group {
+	trxhip_ctx *ctx = nullptr;
+	trxhip_ms_tx_cfg cfg{};                    /* of every member */
+	std::vector<Member> mem;
+
+	// device state (ctx != NULL)
+	trx_mstx_row *d_rows = nullptr;            /* [n_members][max_pending] */
+	PinBuf stage[kBufs];                       /* submit: the call's rows, then their ring destinations */
+	uint8_t *d_stage[kBufs] = {};
+	size_t d_stage_cap[kBufs] = {};
+	int next_stage = 0;
+	std::vector<uint32_t> call_dst;
+	PinBuf tab[kBufs];                        /* render: the member entries, then the bursts of their windows */
+	uint8_t *d_tab[kBufs] = {};
+	size_t d_tab_cap[kBufs] = {};
+	int next_tab = 0;
+};
+
 namespace {
 
-size_t pending(const trxhip_ms_tx *s) { return s->q.size() - s->head; }
+size_t pending(const Member &m) { return m.q.size() - m.head; }
 
 // the buffer for a call that needs `bytes`: waits for the call that used it last, grows it when it is too small
 int pin_acquire(PinBuf &b, size_t bytes)
@@ -171,13 +201,14 @@ void pin_destroy(PinBuf &b)
 }
 
 // submit_burst() for one request: everything but the queue
-trxhip_ms_tx_plan plan_request(const trxhip_ms_tx *s, const trxhip_ms_tx_req &r, uint32_t now_fn, int now_tn, int64_t now_ts)
+trxhip_ms_tx_plan plan_request(const Member &m, const trxhip_ms_tx_cfg &cfg, const trxhip_ms_tx_req &r, uint32_t now_fn, int now_tn,
+			       int64_t now_ts)
 {
 	trxhip_ms_tx_plan p;
 	memset(&p, 0, sizeof(p));
 	// driveTx(), ms_upper.cpp:328, :336: int RSSI = (int)pwr; txFullScale * pow(10, -RSSI / 10) in double, complex(float)
 	const int rssi = (int)r.pwr;
-	p.scale = (float)((double)s->cfg.tx_full_scale * pow(10, -rssi / 10));
+	p.scale = (float)((double)cfg.tx_full_scale * pow(10, -rssi / 10));
 
 	GsmTime target = { (int)r.fn, (int)r.tn };
 	target.incTN(3);                                           /* ul dl offset, ms.cpp:118 */
@@ -198,35 +229,164 @@ trxhip_ms_tx_plan plan_request(const trxhip_ms_tx *s, const trxhip_ms_tx_req &r,
 	}
 	// :139 -- ONE_TS_BURST_LEN is unsigned int: int * int, then * unsigned (modulo 2^32), widened by the int64 sum
 	const unsigned one_ts = (unsigned)TRX_MSTX_BURST;
-	p.send_ts = now_ts + (unsigned)(tosend.fn * 8) * one_ts + (unsigned)tosend.tn * one_ts - s->timing_advance;
-	p.radio_ts = p.send_ts + s->cfg.rxtx_delay;                 /* submit_burst_ts(): ts + rxtxdelay */
+	p.send_ts = now_ts + (unsigned)(tosend.fn * 8) * one_ts + (unsigned)tosend.tn * one_ts - m.timing_advance;
+	p.radio_ts = p.send_ts + cfg.rxtx_delay;                    /* submit_burst_ts(): ts + rxtxdelay */
 	p.status = (diff_fn == 0 && target_tn < now_tn) ? TRXHIP_MS_TX_WRAPPED : TRXHIP_MS_TX_QUEUED;
 	return p;
 }
 
 // where a burst at radio_ts goes in the queue, or -1: its samples intersect a queued burst's
-ptrdiff_t queue_place(const trxhip_ms_tx *s, int64_t radio_ts)
+ptrdiff_t queue_place(const Member &m, int64_t radio_ts)
 {
-	const auto first = s->q.begin() + (ptrdiff_t)s->head;
-	const auto it = std::upper_bound(first, s->q.end(), radio_ts, [](int64_t t, const Pending &b) { return t < b.radio_ts; });
+	const auto first = m.q.begin() + (ptrdiff_t)m.head;
+	const auto it = std::upper_bound(first, m.q.end(), radio_ts, [](int64_t t, const Pending &b) { return t < b.radio_ts; });
 	if (it != first && (it - 1)->radio_ts + kBurst > radio_ts)
 		return -1;
-	if (it != s->q.end() && radio_ts + kBurst > it->radio_ts)
+	if (it != m.q.end() && radio_ts + kBurst > it->radio_ts)
 		return -1;
-	return it - s->q.begin();
+	return it - m.q.begin();
 }
 
-void retire(trxhip_ms_tx *s, const Pending &b, size_t *n_drawn)
+// One request against one member: the plan record, the status rules in their order, the counters and the queue.  True when the
+// burst was queued; with_rows (a device object): *row is the ring row it takes.
+bool place_request(Member &m, const trxhip_ms_tx_cfg &cfg, bool with_rows, const trxhip_ms_tx_req &r, uint32_t now_fn, int now_tn,
+		   int64_t now_ts, trxhip_ms_tx_plan &p, uint32_t *row)
+{
+	p = plan_request(m, cfg, r, now_fn, now_tn, now_ts);
+	m.ctr.submitted++;
+	ptrdiff_t at = -1;
+	if (p.status == TRXHIP_MS_TX_QUEUED) {
+		if (m.window_set && p.radio_ts < m.rendered_end)
+			p.status = TRXHIP_MS_TX_EXPIRED;
+		else if ((at = queue_place(m, p.radio_ts)) < 0)
+			p.status = TRXHIP_MS_TX_OVERLAP;
+		else if (pending(m) >= cfg.max_pending)
+			p.status = TRXHIP_MS_TX_FULL;
+	}
+	switch (p.status) {
+	case TRXHIP_MS_TX_LATE: m.ctr.late++; return false;
+	case TRXHIP_MS_TX_WRAPPED: m.ctr.wrapped++; return false;
+	case TRXHIP_MS_TX_EXPIRED: m.ctr.expired++; return false;
+	case TRXHIP_MS_TX_OVERLAP: m.ctr.overlap++; return false;
+	case TRXHIP_MS_TX_FULL: m.ctr.full++; return false;
+	default: break;
+	}
+	Pending b = { p.radio_ts, 0u, false };
+	if (with_rows) {
+		/* pending < max_pending: a freed row, or a row never used, exists */
+		if (!m.free_rows.empty()) {
+			b.row = m.free_rows.top();
+			m.free_rows.pop();
+		} else {
+			b.row = m.fresh++;
+		}
+		*row = b.row;
+	}
+	m.q.insert(m.q.begin() + at, b);
+	m.ctr.queued++;
+	return true;
+}
+
+// what a queued burst is on the device
+void fill_row(trx_mstx_row &row, const trxhip_ms_tx_req &r, float scale)
+{
+	memcpy(row.bits, r.bits, sizeof(row.bits));
+	memset(row.pad, 0, sizeof(row.pad));
+	row.scale = scale;
+	row.reserved = 0;
+}
+
+void retire(Member &m, bool with_rows, const Pending &b, size_t *n_drawn)
 {
 	if (b.touched) {
-		s->ctr.drawn++;
+		m.ctr.drawn++;
 		if (n_drawn)
 			(*n_drawn)++;
 	} else {
-		s->ctr.missed++;
+		m.ctr.missed++;
 	}
-	if (s->ctx)
-		s->free_rows.push(b.row);
+	if (with_rows)
+		m.free_rows.push(b.row);
+}
+
+// The window [first_ts, end) of one member: retire what lies before it, hand every queued burst that has samples in it to
+// on_burst(burst, from, to) -- [from, to) its stretch inside the window, in ascending order -- and retire what ends in it.
+template <class F>
+void walk_window(Member &m, bool with_rows, int64_t first_ts, int64_t end, size_t *n_drawn, const F &on_burst)
+{
+	while (m.head < m.q.size() && m.q[m.head].radio_ts + kBurst <= first_ts)       /* ended in the gap in front of the window */
+		retire(m, with_rows, m.q[m.head++], n_drawn);
+	while (m.head < m.q.size() && m.q[m.head].radio_ts < end) {
+		Pending &b = m.q[m.head];
+		on_burst(b, std::max(b.radio_ts, first_ts), std::min(b.radio_ts + kBurst, end));
+		b.touched = true;
+		if (b.radio_ts + kBurst > end)
+			break;                                             /* crosses the window's end: the next render draws the rest */
+		retire(m, with_rows, b, n_drawn);
+		m.head++;
+	}
+	if (m.head > 4096 && m.head * 2 > m.q.size()) {
+		m.q.erase(m.q.begin(), m.q.begin() + (ptrdiff_t)m.head);
+		m.head = 0;
+	}
+	m.window_set = true;
+	m.rendered_end = end;
+}
+
+// queued bursts that begin before `end`: no window that ends there meets more
+size_t bursts_before(const Member &m, int64_t end)
+{
+	const auto first = m.q.begin() + (ptrdiff_t)m.head;
+	return (size_t)(std::lower_bound(first, m.q.end(), end, [](const Pending &b, int64_t t) { return b.radio_ts < t; }) - first);
+}
+
+bool valid_request(const trxhip_ms_tx_req &r) { return r.tn <= 7 && r.fn < (uint32_t)kHyperframe; }
+
+bool valid_clock(uint32_t now_fn, int now_tn, int64_t now_ts)
+{
+	return now_fn < (uint32_t)kHyperframe && now_tn >= 0 && now_tn <= 7 && now_ts >= -kMaxTs && now_ts <= kMaxTs;
+}
+
+bool valid_window(const Member &m, size_t n_samples, int64_t first_ts)
+{
+	return n_samples <= kMaxWindow && !(m.window_set && first_ts < m.rendered_end) && first_ts >= -kMaxTs && first_ts <= kMaxTs;
+}
+
+bool valid_ta(int val) { return val > -127 && val < 128; }         /* set_ta(), ms/ms.h:299-303 */
+
+// the largest scale is tx_full_scale itself (pwr 0..9): the product with a modulator sample must stay below 32768, where
+// static_cast<int16_t>(float) is defined
+bool valid_cfg(const trxhip_ms_tx_cfg &c)
+{
+	return c.max_pending >= 1 && c.max_pending <= kMaxPending && (double)c.tx_full_scale * pulse_bound() < 32768.0;
+}
+
+void member_state(const Member &m, trxhip_ms_tx_status *out)
+{
+	*out = m.ctr;
+	out->pending = pending(m);
+	out->rendered_end = m.window_set ? m.rendered_end : 0;
+	out->timing_advance = m.timing_advance;
+	out->window_set = m.window_set;
+	memset(out->reserved, 0, sizeof(out->reserved));
+}
+
+// a device buffer of at least `bytes`, kept between calls
+int dev_reserve(uint8_t *&d, size_t &cap, size_t bytes)
+{
+	if (cap >= bytes)
+		return TRXHIP_OK;
+	if (d)
+		(void)hipFree(d);
+	d = nullptr;
+	cap = 0;
+	const size_t want = std::max(bytes, (size_t)4096);
+	if (hipMalloc(reinterpret_cast<void **>(&d), want) != hipSuccess) {
+		d = nullptr;
+		return TRXHIP_ENOMEM;
+	}
+	cap = want;
+	return TRXHIP_OK;
 }
 
 // zeros over [from, to) of the window that starts at first_ts, in segments of at most 625 samples
@@ -249,13 +409,9 @@ size_t zero_segs(trx_mstx_seg *segs, size_t k, int64_t from, int64_t to, int64_t
 // in it.  Returns the number of segments.
 size_t plan_window(trxhip_ms_tx *s, int64_t first_ts, int64_t end, trx_mstx_seg *segs, size_t *n_drawn)
 {
-	while (s->head < s->q.size() && s->q[s->head].radio_ts + kBurst <= first_ts)       /* ended in the gap in front of the window */
-		retire(s, s->q[s->head++], n_drawn);
 	size_t k = 0;
 	int64_t cur = first_ts;
-	while (s->head < s->q.size() && s->q[s->head].radio_ts < end) {
-		Pending &b = s->q[s->head];
-		const int64_t from = std::max(b.radio_ts, first_ts), to = std::min(b.radio_ts + kBurst, end);
+	walk_window(s->m, s->ctx != nullptr, first_ts, end, n_drawn, [&](const Pending &b, int64_t from, int64_t to) {
 		k = zero_segs(segs, k, cur, from, first_ts);
 		if (segs) {
 			trx_mstx_seg &g = segs[k];
@@ -267,20 +423,8 @@ size_t plan_window(trxhip_ms_tx *s, int64_t first_ts, int64_t end, trx_mstx_seg 
 		}
 		k++;
 		cur = to;
-		b.touched = true;
-		if (b.radio_ts + kBurst > end)
-			break;                                             /* crosses the window's end: the next render draws the rest */
-		retire(s, b, n_drawn);
-		s->head++;
-	}
-	k = zero_segs(segs, k, cur, end, first_ts);
-	if (s->head > 4096 && s->head * 2 > s->q.size()) {
-		s->q.erase(s->q.begin(), s->q.begin() + (ptrdiff_t)s->head);
-		s->head = 0;
-	}
-	s->window_set = true;
-	s->rendered_end = end;
-	return k;
+	});
+	return zero_segs(segs, k, cur, end, first_ts);
 }
 
 }  // namespace
@@ -292,11 +436,7 @@ int trxhip_ms_tx_create(trxhip_ctx *ctx, const trxhip_ms_tx_cfg *cfg, trxhip_ms_
 	if (!cfg || !out)
 		return TRXHIP_EINVAL;
 	const trxhip_ms_tx_cfg c = *cfg;
-	if (c.max_pending < 1 || c.max_pending > kMaxPending)
-		return TRXHIP_EINVAL;
-	// the largest scale is tx_full_scale itself (pwr 0..9): the product with a modulator sample must stay below 32768, where
-	// static_cast<int16_t>(float) is defined
-	if (!((double)c.tx_full_scale * pulse_bound() < 32768.0))
+	if (!valid_cfg(c))
 		return TRXHIP_EINVAL;
 	if (ctx && (!ctx->d_tx_tables || with_device(ctx)))
 		return TRXHIP_EINVAL;
@@ -336,19 +476,19 @@ void trxhip_ms_tx_destroy(trxhip_ms_tx *s)
 
 int trxhip_ms_tx_set_ta(trxhip_ms_tx *s, int val)
 {
-	if (!s || !(val > -127 && val < 128))                      /* set_ta(), ms/ms.h:299-303 */
+	if (!s || !valid_ta(val))
 		return TRXHIP_EINVAL;
-	s->timing_advance = val * 4;
+	s->m.timing_advance = val * 4;
 	return TRXHIP_OK;
 }
 
 int trxhip_ms_tx_submit(trxhip_ms_tx *s, const trxhip_ms_tx_req *h_reqs, size_t n, uint32_t now_fn, int now_tn, int64_t now_ts,
 			trxhip_ms_tx_plan *h_plan, void *stream)
 {
-	if (!s || (!h_reqs && n) || now_fn >= (uint32_t)kHyperframe || now_tn < 0 || now_tn > 7 || now_ts < -kMaxTs || now_ts > kMaxTs)
+	if (!s || (!h_reqs && n) || !valid_clock(now_fn, now_tn, now_ts))
 		return TRXHIP_EINVAL;
 	for (size_t i = 0; i < n; i++)
-		if (h_reqs[i].tn > 7 || h_reqs[i].fn >= (uint32_t)kHyperframe)
+		if (!valid_request(h_reqs[i]))
 			return TRXHIP_EINVAL;
 	if (n == 0)
 		return TRXHIP_OK;
@@ -367,45 +507,11 @@ int trxhip_ms_tx_submit(trxhip_ms_tx *s, const trxhip_ms_tx_req *h_reqs, size_t 
 		s->call_rows.clear();
 	}
 	for (size_t i = 0; i < n; i++) {
-		const trxhip_ms_tx_req &r = h_reqs[i];
-		trxhip_ms_tx_plan p = plan_request(s, r, now_fn, now_tn, now_ts);
-		s->ctr.submitted++;
-		ptrdiff_t at = -1;
-		if (p.status == TRXHIP_MS_TX_QUEUED) {
-			if (s->window_set && p.radio_ts < s->rendered_end)
-				p.status = TRXHIP_MS_TX_EXPIRED;
-			else if ((at = queue_place(s, p.radio_ts)) < 0)
-				p.status = TRXHIP_MS_TX_OVERLAP;
-			else if (pending(s) >= s->cfg.max_pending)
-				p.status = TRXHIP_MS_TX_FULL;
-		}
-		switch (p.status) {
-		case TRXHIP_MS_TX_LATE: s->ctr.late++; break;
-		case TRXHIP_MS_TX_WRAPPED: s->ctr.wrapped++; break;
-		case TRXHIP_MS_TX_EXPIRED: s->ctr.expired++; break;
-		case TRXHIP_MS_TX_OVERLAP: s->ctr.overlap++; break;
-		case TRXHIP_MS_TX_FULL: s->ctr.full++; break;
-		default: {
-			Pending b = { p.radio_ts, 0u, false };
-			if (s->ctx) {
-				/* pending < max_pending: a freed row, or a row never used, exists */
-				if (!s->free_rows.empty()) {
-					b.row = s->free_rows.top();
-					s->free_rows.pop();
-				} else {
-					b.row = s->fresh++;
-				}
-				trx_mstx_row &row = rows[s->call_rows.size()];
-				memcpy(row.bits, r.bits, sizeof(row.bits));
-				memset(row.pad, 0, sizeof(row.pad));
-				row.scale = p.scale;
-				row.reserved = 0;
-				s->call_rows.push_back(b.row);
-			}
-			s->q.insert(s->q.begin() + at, b);
-			s->ctr.queued++;
-			break;
-		}
+		trxhip_ms_tx_plan p;
+		uint32_t ring_row = 0;
+		if (place_request(s->m, s->cfg, s->ctx != nullptr, h_reqs[i], now_fn, now_tn, now_ts, p, &ring_row) && s->ctx) {
+			fill_row(rows[s->call_rows.size()], h_reqs[i], p.scale);
+			s->call_rows.push_back(ring_row);
 		}
 		if (h_plan)
 			h_plan[i] = p;
@@ -435,7 +541,7 @@ int trxhip_ms_tx_submit(trxhip_ms_tx *s, const trxhip_ms_tx_req *h_reqs, size_t 
 
 int trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, int64_t first_ts, size_t *n_drawn, void *stream)
 {
-	if (!s || n_samples > kMaxWindow || (s->window_set && first_ts < s->rendered_end) || first_ts < -kMaxTs || first_ts > kMaxTs)
+	if (!s || !valid_window(s->m, n_samples, first_ts))
 		return TRXHIP_EINVAL;
 	if (s->ctx ? (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 3)) : d_out != nullptr)
 		return TRXHIP_EINVAL;
@@ -453,9 +559,7 @@ int trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, i
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	// at most: a zero segment per 625 samples, and per queued burst that begins before the window's end the burst's segment and
 	// one more zero segment in front of it
-	const auto first = s->q.begin() + (ptrdiff_t)s->head;
-	const size_t nb = (size_t)(std::lower_bound(first, s->q.end(), end, [](const Pending &b, int64_t t) { return b.radio_ts < t; }) - first);
-	const size_t bound = n_samples / (size_t)kBurst + 2 * nb + 2;
+	const size_t bound = n_samples / (size_t)kBurst + 2 * bursts_before(s->m, end) + 2;
 	const int k = s->next_seg;
 	PinBuf &pb = s->seg[k];
 	int rc = pin_acquire(pb, bound * sizeof(trx_mstx_seg));     /* waits for the render 4 calls back: it read d_seg[k] */
@@ -495,12 +599,251 @@ int trxhip_ms_tx_state(const trxhip_ms_tx *s, trxhip_ms_tx_status *out)
 {
 	if (!s || !out)
 		return TRXHIP_EINVAL;
-	*out = s->ctr;
-	out->pending = pending(s);
-	out->rendered_end = s->window_set ? s->rendered_end : 0;
-	out->timing_advance = s->timing_advance;
-	out->window_set = s->window_set;
-	memset(out->reserved, 0, sizeof(out->reserved));
+	member_state(s->m, out);
+	return TRXHIP_OK;
+}
+
+// ---- the group: N members, their submits and their renders each issued as one step ----
+
+int trxhip_ms_tx_group_create(trxhip_ctx *ctx, const trxhip_ms_tx_group_cfg *cfg, trxhip_ms_tx_group **out)
+{
+	if (!cfg || !out)
+		return TRXHIP_EINVAL;
+	const trxhip_ms_tx_cfg c = { cfg->tx_full_scale, cfg->rxtx_delay, cfg->max_pending, 0 };
+	// a ring row is named by a uint32 over all members
+	if (cfg->n_members < 1 || cfg->n_members > TRXHIP_MS_TX_GROUP_MAX_MEMBERS || !valid_cfg(c) ||
+	    (uint64_t)cfg->n_members * c.max_pending > 0xffffffffull)
+		return TRXHIP_EINVAL;
+	if (ctx && (!ctx->d_tx_tables || with_device(ctx)))
+		return TRXHIP_EINVAL;
+	trxhip_ms_tx_group *g = new (std::nothrow) trxhip_ms_tx_group();
+	if (!g)
+		return TRXHIP_ENOMEM;
+	g->cfg = c;
+	try {
+		g->mem.resize(cfg->n_members);
+	} catch (const std::bad_alloc &) {
+		delete g;
+		return TRXHIP_ENOMEM;
+	}
+	if (ctx) {
+		g->ctx = ctx;
+		if (hipMalloc(reinterpret_cast<void **>(&g->d_rows), (size_t)cfg->n_members * c.max_pending * sizeof(trx_mstx_row)) != hipSuccess) {
+			g->d_rows = nullptr;
+			trxhip_ms_tx_group_destroy(g);
+			return TRXHIP_ENOMEM;
+		}
+	}
+	*out = g;
+	return TRXHIP_OK;
+}
+
+void trxhip_ms_tx_group_destroy(trxhip_ms_tx_group *g)
+{
+	if (!g)
+		return;
+	if (g->ctx && with_device(g->ctx) == 0) {
+		for (int k = 0; k < kBufs; k++) {
+			pin_destroy(g->stage[k]);
+			pin_destroy(g->tab[k]);
+			if (g->d_stage[k])
+				(void)hipFree(g->d_stage[k]);
+			if (g->d_tab[k])
+				(void)hipFree(g->d_tab[k]);
+		}
+		if (g->d_rows)
+			(void)hipFree(g->d_rows);
+	}
+	delete g;
+}
+
+int trxhip_ms_tx_group_size(const trxhip_ms_tx_group *g)
+{
+	return g ? (int)g->mem.size() : TRXHIP_EINVAL;
+}
+
+int trxhip_ms_tx_group_set_ta(trxhip_ms_tx_group *g, uint32_t member, int val)
+{
+	if (!g || member >= g->mem.size() || !valid_ta(val))
+		return TRXHIP_EINVAL;
+	g->mem[member].timing_advance = val * 4;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_tx_group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, const trxhip_ms_tx_req *h_reqs, size_t n,
+			      const trxhip_ms_tx_clock *h_now, trxhip_ms_tx_plan *h_plan, size_t *bad, void *stream)
+{
+	if (bad)
+		*bad = (size_t)-1;
+	if (!g || ((!h_member || !h_reqs || !h_now) && n))
+		return TRXHIP_EINVAL;
+	for (size_t i = 0; i < n; i++) {
+		const bool ok = h_member[i] < g->mem.size() && valid_request(h_reqs[i]) &&
+				valid_clock(h_now[h_member[i]].fn, h_now[h_member[i]].tn, h_now[h_member[i]].ts);
+		if (!ok) {
+			if (bad)
+				*bad = i;
+			return TRXHIP_EINVAL;
+		}
+	}
+	if (n == 0)
+		return TRXHIP_OK;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	const bool dev = g->ctx != nullptr;
+	const size_t ring = g->mem.size() * (size_t)g->cfg.max_pending;
+	const size_t most = std::min(n, ring);                         /* no call queues more */
+	const int k = g->next_stage;
+	PinBuf &pb = g->stage[k];
+	if (dev) {
+		if (with_device(g->ctx))
+			return TRXHIP_EIO;
+		const size_t bytes = most * (sizeof(trx_mstx_row) + sizeof(uint32_t));
+		int rc = pin_acquire(pb, bytes);                           /* waits for the submit 4 calls back: it read d_stage[k] */
+		if (rc == TRXHIP_OK)
+			rc = dev_reserve(g->d_stage[k], g->d_stage_cap[k], bytes);
+		if (rc != TRXHIP_OK)
+			return rc;
+	}
+	trx_mstx_row *rows = reinterpret_cast<trx_mstx_row *>(pb.h);
+	std::vector<uint32_t> &call_dst = g->call_dst;                 /* they go behind the rows once their number is known */
+	call_dst.clear();
+	size_t nq = 0;
+	for (size_t i = 0; i < n; i++) {
+		const uint32_t mi = h_member[i];
+		const trxhip_ms_tx_clock &now = h_now[mi];
+		trxhip_ms_tx_plan p;
+		uint32_t ring_row = 0;
+		if (place_request(g->mem[mi], g->cfg, dev, h_reqs[i], now.fn, now.tn, now.ts, p, &ring_row) && dev) {
+			fill_row(rows[nq++], h_reqs[i], p.scale);
+			call_dst.push_back(mi * g->cfg.max_pending + ring_row);
+		}
+		if (h_plan)
+			h_plan[i] = p;
+	}
+	if (!dev || nq == 0)
+		return TRXHIP_OK;
+	memcpy(rows + nq, call_dst.data(), nq * sizeof(uint32_t));
+	int rc = hipMemcpyAsync(g->d_stage[k], pb.h, nq * (sizeof(trx_mstx_row) + sizeof(uint32_t)), hipMemcpyHostToDevice, st) == hipSuccess
+			 ? TRXHIP_OK
+			 : TRXHIP_EIO;
+	if (rc == TRXHIP_OK)
+		rc = trx_launch_ms_tx_stage(reinterpret_cast<const trx_mstx_row *>(g->d_stage[k]),
+					    reinterpret_cast<const uint32_t *>(g->d_stage[k] + nq * sizeof(trx_mstx_row)), nq, g->d_rows, ring, st);
+	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
+		rc = TRXHIP_EIO;
+	if (rc != TRXHIP_OK) {
+		(void)hipStreamSynchronize(st);
+		return TRXHIP_EIO;
+	}
+	pb.used = true;
+	g->next_stage = (k + 1) % kBufs;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t out_stride, const int64_t *h_first_ts,
+				  const size_t *h_n_samples, size_t *h_n_drawn, int *bad_member, void *stream)
+{
+	if (bad_member)
+		*bad_member = -1;
+	if (!g || !h_first_ts || !h_n_samples)
+		return TRXHIP_EINVAL;
+	const bool dev = g->ctx != nullptr;
+	if (dev ? (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 3)) : d_out != nullptr)
+		return TRXHIP_EINVAL;
+	const size_t n_mem = g->mem.size();
+	// every member's window, before anything moves; a plan-only group with out_stride 0 has no output to bound
+	size_t n_rendered = 0, n_bursts = 0;
+	uint64_t n_waves = 0;
+	for (size_t m = 0; m < n_mem; m++) {
+		const size_t ns = h_n_samples[m];
+		if (ns == 0)
+			continue;
+		if (!valid_window(g->mem[m], ns, h_first_ts[m]) || ((dev || out_stride) && ns > out_stride)) {
+			if (bad_member)
+				*bad_member = (int)m;
+			return TRXHIP_EINVAL;
+		}
+		n_rendered++;
+		n_waves += (ns + TRX_MSTX_BURST - 1) / TRX_MSTX_BURST;
+		n_bursts += bursts_before(g->mem[m], h_first_ts[m] + (int64_t)ns);
+	}
+	if (n_waves > 0x7fffffffull || n_bursts > 0xffffffffull)
+		return TRXHIP_EINVAL;
+	if (h_n_drawn)
+		memset(h_n_drawn, 0, n_mem * sizeof(size_t));
+	if (n_rendered == 0)
+		return TRXHIP_OK;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	const int k = g->next_tab;
+	PinBuf &pb = g->tab[k];
+	if (dev) {
+		if (with_device(g->ctx))
+			return TRXHIP_EIO;
+		const size_t bytes = n_rendered * sizeof(trx_mstx_gmember) + n_bursts * sizeof(trx_mstx_gburst);
+		int rc = pin_acquire(pb, bytes);                           /* waits for the render 4 calls back: it read d_tab[k] */
+		if (rc == TRXHIP_OK)
+			rc = dev_reserve(g->d_tab[k], g->d_tab_cap[k], bytes);
+		if (rc != TRXHIP_OK)
+			return rc;
+	}
+	trx_mstx_gmember *ent = reinterpret_cast<trx_mstx_gmember *>(pb.h);
+	trx_mstx_gburst *bur = dev ? reinterpret_cast<trx_mstx_gburst *>(ent + n_rendered) : nullptr;
+	size_t ke = 0, kb = 0;
+	uint32_t wave = 0;
+	for (size_t m = 0; m < n_mem; m++) {
+		const size_t ns = h_n_samples[m];
+		if (ns == 0)
+			continue;
+		const int64_t first_ts = h_first_ts[m];
+		const size_t kb0 = kb;
+		walk_window(g->mem[m], dev, first_ts, first_ts + (int64_t)ns, h_n_drawn ? h_n_drawn + m : nullptr,
+			    [&](const Pending &b, int64_t, int64_t) {
+				    if (dev) {
+					    bur[kb].rel = (int32_t)(b.radio_ts - first_ts);      /* -624 .. ns - 1: it has samples in the window */
+					    bur[kb].row = (uint32_t)m * g->cfg.max_pending + b.row;
+				    }
+				    kb++;
+			    });
+		if (dev) {
+			trx_mstx_gmember &e = ent[ke];
+			e.out_off = (uint64_t)m * out_stride;
+			e.n_samples = (uint32_t)ns;
+			e.first_wave = wave;
+			e.first_burst = (uint32_t)kb0;
+			e.n_bursts = (uint32_t)(kb - kb0);
+			e.reserved[0] = e.reserved[1] = 0;
+		}
+		ke++;
+		wave += (uint32_t)((ns + TRX_MSTX_BURST - 1) / TRX_MSTX_BURST);
+	}
+	if (!dev)
+		return TRXHIP_OK;
+	if (ke != n_rendered || kb > n_bursts || wave != (uint32_t)n_waves)
+		return TRXHIP_EIO;                                     /* cannot happen: see the bounds */
+	// the bursts stand right behind the entries: the table is one piece whatever kb is
+	int rc = hipMemcpyAsync(g->d_tab[k], pb.h, n_rendered * sizeof(trx_mstx_gmember) + kb * sizeof(trx_mstx_gburst), hipMemcpyHostToDevice,
+				st) == hipSuccess
+			 ? TRXHIP_OK
+			 : TRXHIP_EIO;
+	if (rc == TRXHIP_OK)
+		rc = trx_launch_ms_tx_render_group(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k]), (uint32_t)n_rendered, wave, g->d_rows,
+						   g->ctx->d_tx_tables, d_out, st);
+	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
+		rc = TRXHIP_EIO;
+	if (rc != TRXHIP_OK) {
+		(void)hipStreamSynchronize(st);
+		return TRXHIP_EIO;
+	}
+	pb.used = true;
+	g->next_tab = (k + 1) % kBufs;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_tx_status *out)
+{
+	if (!g || member >= g->mem.size() || !out)
+		return TRXHIP_EINVAL;
+	member_state(g->mem[member], out);
 	return TRXHIP_OK;
 }
 

@@ -26,3 +26,22 @@ struct trx_mstx_seg {
 	uint32_t reserved;
 };
 static_assert(sizeof(trx_mstx_seg) == 16, "trx_mstx_seg layout");
+
+/* The group's render (trxhip_ms_tx_group_*, ms_tx_render_group_kernel): one table per call -- an entry per rendered member, in the
+ * order of their waves, and right behind the entries the queued bursts that have samples in those members' windows.  The window
+ * is cut into tiles of 625 samples (the last one shorter); wave w draws tile w - first_wave of the entry with the largest
+ * first_wave <= w.  first_wave rises strictly from 0; an entry has n_samples >= 1.  32 bytes */
+struct trx_mstx_gmember {
+	uint64_t out_off;                      /* the window's first sample, in samples from d_out */
+	uint32_t n_samples;
+	uint32_t first_wave;
+	uint32_t first_burst, n_bursts;        /* its bursts in the list behind the entries: ascending rel, 625 or more apart */
+	uint32_t reserved[2];
+};
+static_assert(sizeof(trx_mstx_gmember) == 32, "trx_mstx_gmember layout");
+
+struct trx_mstx_gburst {
+	int32_t  rel;                          /* radio_ts - first_ts: -624 .. n_samples - 1 */
+	uint32_t row;                          /* member * max_pending + ring row */
+};
+static_assert(sizeof(trx_mstx_gburst) == 8, "trx_mstx_gburst layout");

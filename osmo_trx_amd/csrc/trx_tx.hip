@@ -739,6 +739,179 @@ extern "C" int trx_launch_ms_tx_render(const trx_mstx_seg *d_segs, size_t n_segs
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
 
+// The second burst of a tile of ms_tx_render_group_kernel: its staging areas, per wave as tx_lds's (which holds the first
+// burst's and the pulse taps).
+struct tx_lds_second {
+	c32 sym0[TX_WAVES][TX_SYMS];
+	c32 sym1[TX_WAVES][TX_SYMS];
+	uint8_t bits[TX_WAVES][TX_BITS];
+};
+
+// The uplink scheduler group's render (trxhip_ms_tx_group_*; trx_ms_tx.cpp builds the table, trx_ms_tx.h describes it): one wave
+// per tile of at most 625 samples of one member's window, four per workgroup.  Wave gw finds its member by bisection on
+// first_wave, its tile is gw - first_wave, and it finds the bursts that have samples in the tile by a search over the member's
+// sorted burst list (a bisection with 64 probes per round, one per lane): the first burst that ends behind the tile's start (A)
+// and, when that one begins before the tile's end, its successor (B) if it begins in the tile too.  A member's bursts are disjoint and 625 long, so no third one meets a tile of 625.  The wave stages A in tx_lds and B in
+// tx_lds_second, then writes five pieces in order, each through tx_store_row: zeros, A's stretch, zeros, B's stretch, zeros.  A
+// burst piece evaluates tx_sample at i + first exactly as ms_tx_render_kernel does, so a burst drawn by two tiles, or in two
+// windows, gives the samples of one drawn whole.  Every sample of every rendered window is written once, nothing else is.
+// Barriers: all four waves reach both __syncthreads(), idle waves (behind n_waves) and tiles with one burst or none included; no
+// wave returns before the second.
+__global__ void __launch_bounds__(64 * TX_WAVES)
+ms_tx_render_group_kernel(const trx_mstx_gmember *__restrict__ tab, uint32_t n_entries, uint32_t n_waves,
+			  const trx_mstx_row *__restrict__ rows, const trx_tx_tables *__restrict__ ttab, int16_t *__restrict__ out)
+{
+	__shared__ tx_lds L;
+	__shared__ tx_lds_second L2;
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const uint32_t gw = blockIdx.x * TX_WAVES + w;
+	const bool active = gw < n_waves;
+
+	if (threadIdx.x < 16)
+		L.p0[threadIdx.x] = ttab->pulse4_c0[threadIdx.x];
+	else if (threadIdx.x < 24)
+		L.p1[threadIdx.x - 16] = ttab->pulse4_c1[threadIdx.x - 16];
+
+	// ---- the tile and its bursts (wave-uniform); positions count from the tile's first sample ----
+	const trx_mstx_row *ra = nullptr, *rb = nullptr;
+	size_t off = 0;
+	int len = 0, a_lo = 0, a_hi = 0, a_first = 0, b_lo = 0, b_hi = 0;
+	if (active) {
+		unsigned lo = 0, hi = n_entries;                           // tab[lo].first_wave <= gw < tab[hi].first_wave
+		while (hi - lo > 1) {
+			const unsigned mid = (lo + hi) >> 1;
+			if (tab[mid].first_wave <= gw)
+				lo = mid;
+			else
+				hi = mid;
+		}
+		const trx_mstx_gmember e = tab[lo];
+		const uint32_t t0 = (gw - e.first_wave) * TRX_MSTX_BURST;  // the tile's first sample in the window: < n_samples <= 2^31
+		len = (int)min(TRX_MSTX_BURST, e.n_samples - t0);
+		off = (size_t)e.out_off + t0;
+		const trx_mstx_gburst *bl = reinterpret_cast<const trx_mstx_gburst *>(tab + n_entries) + e.first_burst;
+		// The first burst that ends behind the tile's start, i0 in [i0, i1].  The list is sorted, so "burst i ends at or before the
+		// tile's start" holds for a prefix of it.  The search is the wave's: the range is cut into 64 chunks, lane l asks about the
+		// last burst of chunk l, and the number of lanes that say yes names the chunk that holds i0 -- three rounds of one load
+		// for 262 144 bursts where a lane's bisection takes eighteen loads one behind the other.
+		unsigned i0 = 0, i1 = e.n_bursts;
+		while (i0 < i1) {
+			const unsigned step = (i1 - i0 + 63) >> 6;
+			const uint64_t at = (uint64_t)i0 + (uint64_t)lane * step + (step - 1);
+			const bool before = at < i1 && (int64_t)bl[at].rel + (int64_t)TRX_MSTX_BURST <= (int64_t)t0;
+			const unsigned whole = (unsigned)__popcll(__ballot(before));               // chunks that lie wholly before the tile
+			i0 = (unsigned)min((uint64_t)i1, (uint64_t)i0 + (uint64_t)whole * step);
+			i1 = (unsigned)min((uint64_t)i1, (uint64_t)i0 + step - 1);                 // that chunk's last burst said no, or lies at i1
+		}
+		if (i0 < e.n_bursts) {
+			const trx_mstx_gburst ba = bl[i0];
+			const int64_t da = (int64_t)ba.rel - (int64_t)t0;      // > -625
+			if (da < len) {
+				ra = rows + ba.row;
+				a_lo = da > 0 ? (int)da : 0;
+				a_hi = min((int)da + (int)TRX_MSTX_BURST, len);
+				a_first = a_lo - (int)da;
+				if (i0 + 1 < e.n_bursts) {
+					const trx_mstx_gburst bb = bl[i0 + 1];
+					const int64_t db = (int64_t)bb.rel - (int64_t)t0;      // >= da + 625 > 0: B begins in the tile or behind it
+					if (db >= a_hi && db < len) {
+						rb = rows + bb.row;
+						b_lo = (int)db;
+						b_hi = len;                                    // db + 625 > len
+					}
+				}
+			}
+		}
+		if (!rb)
+			b_lo = b_hi = a_hi;
+	}
+
+	trx_tx_desc d;
+	d.status = 0;
+	d.mode = TX_LAURENT;                       /* modulateBurst(bits, 8 + (tn % 4 == 0), 4), ms_upper.cpp:335 */
+	d.nbits = 148;
+	d.len = (int)TRX_MSTX_BURST;
+	d.scale = make_float2(1.0f, 0.0f);
+	d.scaled = true;                           /* scaleVector() runs on every burst, :336 */
+
+	uint8_t *lba = L.bits[w], *lbb = L2.bits[w];
+	if (ra)
+		for (int i = lane; i < d.nbits; i += 64)
+			lba[i] = ra->bits[i] & 0x01;
+	if (rb)
+		for (int i = lane; i < d.nbits; i += 64)
+			lbb[i] = rb->bits[i] & 0x01;
+	__syncthreads();
+
+	if (ra)
+		tx_stage_syms(d, lba, L.sym0[w], L.sym1[w], lane, ttab);
+	if (rb)
+		tx_stage_syms(d, lbb, L2.sym0[w], L2.sym1[w], lane, ttab);
+	__syncthreads();
+	if (!active)
+		return;
+
+	// ---- the five pieces: zeros [0, a_lo), A [a_lo, a_hi), zeros [a_hi, b_lo), B [b_lo, b_hi), zeros [b_hi, len) ----
+	const c32 *rot = reinterpret_cast<const c32 *>(ttab->rot4);
+	const float scale_a = ra ? ra->scale : 1.0f, scale_b = rb ? rb->scale : 1.0f;
+	for (int p = 0; p < 5; p++) {
+		const int from = p == 0 ? 0 : p == 1 ? a_lo : p == 2 ? a_hi : p == 3 ? b_lo : b_hi;
+		const int to = p == 0 ? a_lo : p == 1 ? a_hi : p == 2 ? b_lo : p == 3 ? b_hi : len;
+		if (to <= from)
+			continue;
+		const bool second = p == 3;
+		trx_tx_desc dp = d;
+		dp.len = (p & 1) ? (int)TRX_MSTX_BURST : 0;             /* 0: zeros */
+		dp.scale = make_float2(second ? scale_b : scale_a, 0.0f);
+		const c32 *s0 = second ? L2.sym0[w] : L.sym0[w], *s1 = second ? L2.sym1[w] : L.sym1[w];
+		const uint8_t *lb = second ? lbb : lba;
+		const int first = p == 1 ? a_first : 0;                    /* B begins in the tile: its sample 0 */
+		auto sample = [&](int i) -> c32 { return tx_sample(dp, s0, s1, lb, L, rot, 4, i + first); };
+		tx_store_row(sample, nullptr, out, 2 * (off + (size_t)from), 1.0f, to - from, lane);
+	}
+}
+
+// A group submit's rows to their ring rows: row i of the call goes to rows[dst[i]], one thread per 32-bit word of a row.
+__global__ void __launch_bounds__(256)
+ms_tx_stage_kernel(const trx_mstx_row *__restrict__ src, const uint32_t *__restrict__ dst, size_t n, trx_mstx_row *__restrict__ rows,
+		   size_t ring_rows)
+{
+	const int words = (int)(sizeof(trx_mstx_row) / 4);
+	const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x, i = id / words;
+	if (i >= n)
+		return;
+	const uint32_t r = dst[i];
+	if (r >= ring_rows)
+		return;                                /* the host names rows of the ring only */
+	const int k = (int)(id - i * words);
+	reinterpret_cast<uint32_t *>(rows + r)[k] = reinterpret_cast<const uint32_t *>(src + i)[k];
+}
+
+extern "C" int trx_launch_ms_tx_stage(const trx_mstx_row *d_src, const uint32_t *d_dst, size_t n, trx_mstx_row *d_rows, size_t ring_rows,
+				      hipStream_t stream)
+{
+	if (n == 0)
+		return 0;
+	const size_t blocks = (n * (sizeof(trx_mstx_row) / 4) + 255) / 256;
+	if (blocks > 0x7fffffffu)
+		return TRXHIP_EINVAL;
+	hipLaunchKernelGGL(ms_tx_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_src, d_dst, n, d_rows, ring_rows);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+extern "C" int trx_launch_ms_tx_render_group(const trx_mstx_gmember *d_tab, uint32_t n_entries, uint32_t n_waves, const trx_mstx_row *d_rows,
+					     const trx_tx_tables *d_tab_tx, int16_t *d_out, hipStream_t stream)
+{
+	if (n_waves == 0)
+		return 0;
+	if (n_entries == 0 || n_waves > 0x7fffffffu)
+		return TRXHIP_EINVAL;
+	const unsigned blocks = (n_waves + TX_WAVES - 1) / TX_WAVES;
+	hipLaunchKernelGGL(ms_tx_render_group_kernel, dim3(blocks), dim3(64 * TX_WAVES), 0, stream, d_tab, n_entries, n_waves, d_rows, d_tab_tx,
+			   d_out);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host: the transmit tables, built as sigProcLibSetup() builds the reference's (sigProcLib.cpp:2139-2172), with each
 // generator's operand order and float/double promotion points.

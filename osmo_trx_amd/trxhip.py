@@ -226,6 +226,13 @@ SYMBOLS = {
     "trxhip_ms_tx_submit": (_I, [_VP, _VP, _SZ, C.c_uint32, _I, C.c_int64, _VP, _VP]),
     "trxhip_ms_tx_render_s16": (_I, [_VP, _VP, _SZ, C.c_int64, C.POINTER(_SZ), _VP]),
     "trxhip_ms_tx_state": (_I, [_VP, _VP]),
+    "trxhip_ms_tx_group_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
+    "trxhip_ms_tx_group_destroy": (None, [_VP]),
+    "trxhip_ms_tx_group_size": (_I, [_VP]),
+    "trxhip_ms_tx_group_set_ta": (_I, [_VP, C.c_uint32, _I]),
+    "trxhip_ms_tx_group_submit": (_I, [_VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(_SZ), _VP]),
+    "trxhip_ms_tx_group_render_s16": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, C.POINTER(_I), _VP]),
+    "trxhip_ms_tx_group_state": (_I, [_VP, C.c_uint32, _VP]),
 }
 
 
@@ -1506,6 +1513,102 @@ class MsTxScheduler:
     def close(self):
         if getattr(self, "h", None):
             self.L.trxhip_ms_tx_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MS_TX_GROUP_MAX_MEMBERS = 4096                       # TRXHIP_MS_TX_GROUP_MAX_MEMBERS
+MS_TX_CLOCK_DTYPE = np.dtype([("fn", "<u4"), ("tn", "<i4"), ("ts", "<i8")])        # trxhip_ms_tx_clock
+assert MS_TX_CLOCK_DTYPE.itemsize == 16
+
+
+class _MsTxGroupCfg(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("tx_full_scale", C.c_uint32), ("rxtx_delay", C.c_int32), ("max_pending", C.c_uint32)]
+
+
+class MsTxSchedulerGroup:
+    """N MS-side uplink burst schedulers behind one radio type (trxhip_ms_tx_group_*): every member is a MsTxScheduler -- its own
+    timing advance, queue, window state and counters -- and the group issues the members' submits as one copy and one launch and
+    their renders as one table copy and one launch, whatever N is.
+    trx=None: a plan-only group (no GPU): submit, plan, windows and counters; render draws nothing."""
+
+    def __init__(self, trx=None, n_members=1, tx_full_scale=2047, rxtx_delay=0, max_pending=1024):
+        self.trx = trx
+        self.L = trx.L if trx is not None else load_library()
+        self.n = int(n_members)
+        cfg = _MsTxGroupCfg(self.n, tx_full_scale, rxtx_delay, max_pending)
+        h = _VP()
+        _check(self.L.trxhip_ms_tx_group_create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_ms_tx_group_create")
+        self.h = h
+        self.bad = -1                                # of the last refused submit (a request) or render (a member)
+
+    def set_ta(self, m, val):
+        _check(self.L.trxhip_ms_tx_group_set_ta(self.h, m, val), "trxhip_ms_tx_group_set_ta")
+
+    def submit(self, members, reqs, clocks, stream=None):
+        """members: the member of each request (one index for all, or n); reqs: MS_TX_REQ_DTYPE[n] (ms_tx_requests()); clocks: per
+        member its timekeeper's (fn, tn, ts), MsRxSchedulerGroup.clock(m) -- a sequence of n_members entries or a dict by member;
+        None or a missing entry is fine for a member no request names.  Returns the plan, MS_TX_PLAN_DTYPE[n]."""
+        reqs = np.ascontiguousarray(reqs, dtype=MS_TX_REQ_DTYPE).reshape(-1)
+        members = np.ascontiguousarray(np.broadcast_to(np.asarray(members, dtype=np.uint32), (len(reqs),)))
+        now = np.zeros(self.n, dtype=MS_TX_CLOCK_DTYPE)
+        now["fn"] = 0xFFFFFFFF                       # not a clock: a request that names a member without one is refused
+        for m, c in (clocks.items() if isinstance(clocks, dict) else enumerate(_per_member(list(clocks), self.n, "clocks"))):
+            if c is not None:
+                now[m] = tuple(c)
+        plan = np.zeros(len(reqs), dtype=MS_TX_PLAN_DTYPE)
+        bad = _SZ()
+        rc = self.L.trxhip_ms_tx_group_submit(self.h, members.ctypes.data_as(_VP), reqs.ctypes.data_as(_VP), len(reqs),
+                                              now.ctypes.data_as(_VP), plan.ctypes.data_as(_VP), C.byref(bad),
+                                              self.trx._stream(stream) if self.trx is not None else None)
+        self.bad = -1 if bad.value == _SZ(-1).value else bad.value
+        _check(rc, "trxhip_ms_tx_group_submit (request %d)" % self.bad)
+        return plan
+
+    def render(self, n_samples, first_ts, out=None, out_stride=None, stream=None):
+        """member m's window [first_ts[m], first_ts[m] + n_samples[m]); n_samples, first_ts: one value for all members or one per
+        member, n_samples[m] == 0 (or None): m is not rendered.  Returns (int16[n_members, out_stride, 2] device tensor -- member
+        m's window is [m, :n_samples[m]] --, [n_drawn per member]); out: such a tensor to write instead; out_stride: default the
+        longest window.  Plan-only: (None, [n_drawn]); out_stride None / 0 leaves the window lengths unbounded."""
+        ns = np.array([x or 0 for x in _per_member(n_samples, self.n, "n_samples")], dtype=np.uintp)
+        ts = np.array(_per_member(first_ts, self.n, "first_ts"), dtype=np.int64)
+        nd = np.zeros(self.n, dtype=np.uintp)
+        bad = _I(-1)
+        if self.trx is None:
+            rc = self.L.trxhip_ms_tx_group_render_s16(self.h, None, int(out_stride or 0), ts.ctypes.data_as(_VP), ns.ctypes.data_as(_VP),
+                                                      nd.ctypes.data_as(_VP), C.byref(bad), None)
+            self.bad = bad.value
+            _check(rc, "trxhip_ms_tx_group_render_s16 (member %d)" % bad.value)
+            return None, [int(x) for x in nd]
+        torch = self.trx.torch
+        if out is None:
+            stride = max(int(ns.max()), 1) if out_stride is None else int(out_stride)
+            out = torch.empty((self.n, max(stride, 1), 2), dtype=torch.int16, device=f"cuda:{self.trx.device}")
+        else:
+            assert out.dtype == torch.int16 and out.is_contiguous() and out.dim() == 3 and out.shape[0] == self.n and out.shape[2] == 2, \
+                (out.shape, out.dtype)
+            stride = out.shape[1] if out_stride is None else int(out_stride)
+            assert stride <= out.shape[1]
+        rc = self.L.trxhip_ms_tx_group_render_s16(self.h, out.data_ptr(), stride, ts.ctypes.data_as(_VP), ns.ctypes.data_as(_VP),
+                                                  nd.ctypes.data_as(_VP), C.byref(bad), self.trx._stream(stream))
+        self.bad = bad.value
+        _check(rc, "trxhip_ms_tx_group_render_s16 (member %d)" % bad.value)
+        return out, [int(x) for x in nd]
+
+    def state(self, m):
+        """MS_TX_STATE_DTYPE record of member m: the counters and the window state"""
+        a = np.zeros(1, dtype=MS_TX_STATE_DTYPE)
+        _check(self.L.trxhip_ms_tx_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_tx_group_state")
+        return a[0]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.trxhip_ms_tx_group_destroy(self.h)
             self.h = None
 
     def __del__(self):

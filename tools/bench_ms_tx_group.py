@@ -1,0 +1,263 @@
+#!/usr/bin/env python3
+"""The MS-side uplink scheduler group on one GPU against single uplink scheduler objects on the same requests, the same windows
+and the same stream, HIP-event time, int16, a burst on every TN unless said.
+  g64 / s64        64 members, one frame (8 slots) per member and render, `frames` frames in a row, each with the submit of that
+                   frame's requests: one group submit and one group render per frame against 64 trxhip_ms_tx_submit and 64
+                   trxhip_ms_tx_render_s16; reported per frame
+  g256 / s256      the same with 256 members
+  g1 / s1          one member, 8 slots per render, with its submit
+  gdense / sdense    one member, one render of `slots` slots with a burst on every TN (the submit before it is not timed)
+  gsparse / ssparse  the same window with a burst on one TN in 8
+Every round is a fresh process under its own time limit; inside a round the legs are timed in turns, the order reversed every
+other turn and the number of turns even; every timed region follows one untimed call of the same leg.  Every round ends with a
+byte comparison of the group's outputs with the single objects'.  Median per leg over the rounds, spread = max - min over the
+rounds -> profiles/ms_tx_group_bench.json.  --trace takes the kernel times of the named legs from rocprofv3 --kernel-trace runs
+of their own.  The first step that fails ends the run.
+
+   python3 tools/bench_ms_tx_group.py [--rounds 5] [--slots N] [--frames F] [--inner I] [--warmup W] [--reps R] [--timeout S] [--trace LEGS] [--out FILE]"""
+import argparse
+import json
+import os
+import re
+import shutil
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+FULL_SCALE = 2047
+BASE_FN = 51 * 4321
+FRAME = 8 * 625
+PAIRS = (("g64", "s64"), ("g256", "s256"), ("g1", "s1"), ("gdense", "sdense"), ("gsparse", "ssparse"))
+
+
+def slot_requests(trxhip, np, slots, bits):
+    """request k is heard in slot slots[k] of a stream that starts at the clock (BASE_FN, 0): its target after incTN(3)"""
+    return trxhip.ms_tx_requests(BASE_FN + (slots - 3) // 8, (slots - 3) % 8, (slots * 3) % 30, bits)
+
+
+def child(a):
+    """One round: the legs in turns -> one JSON line {leg: median ms per frame (per render for the big legs)}."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from osmo_trx_amd import TrxHip, trxhip
+    trx = TrxHip(0)
+    names = [k for pair in PAIRS for k in pair if not a.legs or k in a.legs.split(",")]
+    L, st = trx.L, trx._stream()
+    vp = C.c_void_p
+    frames = a.frames
+    rng = np.random.default_rng(3)
+    now = [0]                                                       # every run's windows lie behind the last run's
+
+    def frame_legs(n):
+        """n members: per run `frames` frames, each the submit of its 8 requests per member and the render of its 5000 samples"""
+        g = trxhip.MsTxSchedulerGroup(trx, n_members=n, tx_full_scale=FULL_SCALE, rxtx_delay=0, max_pending=16)
+        ss = [trxhip.MsTxScheduler(trx, tx_full_scale=FULL_SCALE, rxtx_delay=0, max_pending=16) for _ in range(n)]
+        out = torch.zeros((2, n, FRAME, 2), dtype=torch.int16, device="cuda:0")
+        # frame f of a run holds slots 8 (f + 1) .. 8 (f + 1) + 7 behind the run's clock (the first three lie behind the clock)
+        reqs = [[slot_requests(trxhip, np, 8 * (f + 1) + np.arange(8), rng.integers(0, 2, (8, 148))) for _ in range(n)] for f in range(frames)]
+        greqs = [np.concatenate(r) for r in reqs]
+        member = np.repeat(np.arange(n, dtype=np.uint32), 8)
+        clocks = np.zeros(n, dtype=trxhip.MS_TX_CLOCK_DTYPE)
+        clocks["fn"] = BASE_FN
+        first = [np.zeros(n, dtype=np.int64) for _ in range(frames)]
+        sizes = np.full(n, FRAME, dtype=np.uintp)
+        now_c = C.c_int64()
+        first_c = [C.c_int64() for _ in range(frames)]
+        nd1, bad, badm = C.c_size_t(), C.c_size_t(), C.c_int()
+        g_sub = [(g.h, member.ctypes.data_as(vp), r.ctypes.data_as(vp), len(r), clocks.ctypes.data_as(vp), None, C.byref(bad), st) for r in greqs]
+        g_ren = [(g.h, vp(out[0].data_ptr()), FRAME, t.ctypes.data_as(vp), sizes.ctypes.data_as(vp), None, C.byref(badm), st) for t in first]
+        s_sub = [[(ss[m].h, reqs[f][m].ctypes.data_as(vp), 8, BASE_FN, 0, now_c, None, st) for m in range(n)] for f in range(frames)]
+        s_ren = [[(ss[m].h, vp(out[1, m].data_ptr()), FRAME, first_c[f], C.byref(nd1), st) for m in range(n)] for f in range(frames)]
+        gsubmit, grender = L.trxhip_ms_tx_group_submit, L.trxhip_ms_tx_group_render_s16
+        ssubmit, srender = L.trxhip_ms_tx_submit, L.trxhip_ms_tx_render_s16
+
+        def advance():
+            now[0] += (frames + 4) * FRAME
+            return now[0]
+
+        def run():
+            t = advance()
+            clocks["ts"] = t
+            for f in range(frames):
+                first[f][:] = t + (f + 1) * FRAME
+            for sub, ren in zip(g_sub, g_ren):
+                if gsubmit(*sub) != 0 or grender(*ren) != 0:
+                    raise RuntimeError("group call failed")
+
+        def run_singles():
+            t = advance()
+            now_c.value = t
+            for f in range(frames):
+                first_c[f].value = t + (f + 1) * FRAME
+            for subs, rens in zip(s_sub, s_ren):
+                for sub in subs:
+                    if ssubmit(*sub) != 0:
+                        raise RuntimeError("trxhip_ms_tx_submit failed")
+                for ren in rens:
+                    if srender(*ren) != 0:
+                        raise RuntimeError("trxhip_ms_tx_render_s16 failed")
+
+        def check():
+            """the last frame of both paths holds the same bytes, member for member, and every burst was drawn"""
+            out.zero_()
+            run()
+            run_singles()
+            torch.cuda.synchronize()
+            assert torch.equal(out[0], out[1]) and bool(out[0].any(dim=2).any(dim=1).all()), "the group's streams differ from the single objects'"
+            for m in (0, n - 1):
+                a_, b_ = g.state(m), ss[m].state()
+                assert a_["drawn"] == b_["drawn"] == a_["queued"] and a_["pending"] == 0 and a_["missed"] == 0, (a_, b_)
+
+        return run, run_singles, check
+
+    legs, checks = {}, []
+    for n, (gn, sn) in ((64, PAIRS[0]), (256, PAIRS[1]), (1, PAIRS[2])):
+        if gn in names or sn in names:
+            run, run_singles, check = frame_legs(n)
+            legs[gn], legs[sn] = (None, run, frames), (None, run_singles, frames)
+            checks.append(check)
+    if any(k in names for pair in PAIRS[3:] for k in pair):
+        n = a.slots
+        assert n % 8 == 0 and n >= 64
+        k = np.arange(n)
+        dense = slot_requests(trxhip, np, k, rng.integers(0, 2, (n, 148)))
+        big = {"dense": dense, "sparse": dense[5::8].copy()}
+        gb = trxhip.MsTxSchedulerGroup(trx, n_members=1, tx_full_scale=FULL_SCALE, rxtx_delay=0, max_pending=n)
+        sb = trxhip.MsTxScheduler(trx, tx_full_scale=FULL_SCALE, rxtx_delay=0, max_pending=n)
+        window = torch.empty((2, n * 625, 2), dtype=torch.int16, device="cuda:0")
+        ndb = C.c_size_t()
+
+        def submit_big(obj, name):
+            now[0] += (n + 16) * 625
+            clock = (BASE_FN, 0, now[0])
+            plan = obj.submit(0, big[name], [clock]) if obj is gb else obj.submit(big[name], clock)
+            assert (plan["status"][3 if name == "dense" else 0:] == trxhip.MS_TX_QUEUED).all(), np.bincount(plan["status"])
+            return now[0]
+
+        at = {}
+
+        def gbig():
+            _, nd = gb.render([n * 625], [at["g"]], out=window[0:1])
+            return nd[0]
+
+        def sbig():
+            trxhip._check(L.trxhip_ms_tx_render_s16(sb.h, vp(window[1].data_ptr()), n * 625, at["s"], C.byref(ndb), st), "render")
+            return ndb.value
+
+        for name in ("dense", "sparse"):
+            legs["g" + name] = (lambda name=name: at.__setitem__("g", submit_big(gb, name)), gbig, 1)
+            legs["s" + name] = (lambda name=name: at.__setitem__("s", submit_big(sb, name)), sbig, 1)
+
+        def check_big():
+            for name, want in (("dense", n - 3), ("sparse", n // 8)):
+                legs["g" + name][0]()
+                legs["s" + name][0]()
+                assert gbig() == sbig() == want
+                torch.cuda.synchronize()
+                assert torch.equal(window[0], window[1]) and bool(window[0].any()), "the group's stream differs from the single object's"
+
+        checks.append(check_big)
+    names = [k for k in names if k in legs]
+    times = {k: [] for k in names}
+
+    def run_leg(name, reps):
+        """reps calls of a leg (each after its untimed preparation) -> ms per call"""
+        prep, call, per = legs[name]
+        total = 0.0
+        if prep is None:                                           # the submits are part of the timed region
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(reps):
+                call()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) / reps / per
+        for _ in range(reps):
+            prep()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            call()
+            ev[1].record()
+            torch.cuda.synchronize()
+            total += ev[0].elapsed_time(ev[1])
+        return total / reps / per
+
+    for name in names:
+        run_leg(name, a.warmup)
+    for i in range(a.inner):
+        for name in (names if (a.round + i) % 2 == 0 else names[::-1]):
+            run_leg(name, 1)                                       # untimed: the timed calls follow a call of their own kind
+            times[name].append(run_leg(name, a.reps))
+    if not a.legs:
+        for check in checks:
+            check()
+    print(json.dumps({k: statistics.median(v) for k, v in times.items()}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--slots", type=int, default=1 << 18)
+    ap.add_argument("--frames", type=int, default=17, help="frames in a row per timed call")
+    ap.add_argument("--inner", type=int, default=6, help="turns per leg inside a round (even: both orders equally often)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--timeout", type=int, default=150, help="seconds per round")
+    ap.add_argument("--trace", default="", help="also take a kernel trace of these legs (comma-separated), each in a run of its own")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ms_tx_group_bench.json"))
+    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
+    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
+    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.round is not None:
+        return child(a)
+    if a.rounds < 5:
+        ap.error("at least five rounds")
+    if a.inner % 2:
+        ap.error("an even number of turns")
+    import measure
+    os.makedirs(a.logs, exist_ok=True)
+    per_leg = {}
+    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--frames", str(a.frames)]
+    for r in range(a.rounds):
+        log = os.path.join(a.logs, "ms_tx_group_round_%d.log" % (r + 1))
+        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--inner", str(a.inner), "--warmup", str(a.warmup), "--reps",
+                                                 str(a.reps)], log, a.timeout)
+        for k, v in measure.last_json(log).items():
+            per_leg.setdefault(k, []).append(v)
+        print("round %d done" % (r + 1), flush=True)
+    res = {"workload": "ms_tx_group", "slots": a.slots, "small_render_slots": 8, "frames_per_call": a.frames, "slot_len": 625,
+           "output": "int16", "rounds": a.rounds, "inner": a.inner, "reps": a.reps,
+           "unit": "ms per frame of all members, submits included (gdense / sdense / gsparse / ssparse: per render)", "legs": {}, "pairs": {}}
+    for name, xs in per_leg.items():
+        med = statistics.median(xs)
+        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs])
+    lg = res["legs"]
+    for gn, sn in PAIRS:
+        if gn in lg and sn in lg:
+            res["pairs"][gn + "_over_" + sn] = dict(ratio=round(lg[gn]["median_ms"] / lg[sn]["median_ms"], 4),
+                                                    diff_ms=round(lg[gn]["median_ms"] - lg[sn]["median_ms"], 4),
+                                                    larger_spread_ms=max(lg[gn]["spread_ms"], lg[sn]["spread_ms"]))
+    if a.trace:
+        from bench_rx_sched import trace_rows
+        d = os.path.join(a.logs, "ms_tx_group_trace")
+        res["kernel_trace_us"] = {}
+        for leg in a.trace.split(","):
+            shutil.rmtree(d, ignore_errors=True)
+            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "ms_tx_group",
+                                                 "--"] + me + ["--round", "0", "--inner", "2", "--warmup", "1", "--reps", "1", "--legs", leg],
+                         os.path.join(a.logs, "ms_tx_group_trace_%s.log" % leg), a.timeout)
+            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(trace_rows(d).items()) if re.match(r"ms_tx_", k)}
+        shutil.rmtree(d, ignore_errors=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
