@@ -932,7 +932,8 @@ int  trxhip_rx_sched_noise_state(trxhip_rx_sched *s, int chan, float *ring20, ui
  *   (may be NULL) and returns 1 (burst found) or 0 (not found, state untouched).  On 1: the clock becomes (fn, 0) with ts 0
  *   (timekeeper.set(fn, 0), :91), mTSC = bsic & 7 (:90), first_sch_ts_start = first_ts + start - 16 - 1 (:198); the carried
  *   partial slot and any pending correction are dropped, and the next pull is grab_bursts()' first call.  The level gate and
- *   the gain steps around it (:333-347) stay with the caller.  A plan-only object READS *h_res as the receiver's answer.
+ *   the gain steps around it (:333-347) stay with the caller (trxhip_ms_level_batch_i16() and trxhip_ms_agc_gate(), below).
+ *   A plan-only object READS *h_res as the receiver's answer.
  * pull: one call of grab_bursts() with the chunk as `rcd` (n_samples samples from timestamp first_ts), literally:
  *   first call after an acquire (:362-383): next_burst_start = first_ts - first_sch_ts_start in int64; fullts, fracts by C's
  *     division; to_skip = 625 - fracts (a whole slot when fracts == 0); the clock fullts incTN() later, one more when fracts,
@@ -1076,6 +1077,74 @@ int  trxhip_ms_group_pull_s16(trxhip_ms_group *g, const trxhip_ms_group_chunk *h
 			      size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream);
 int  trxhip_ms_group_pull_cf32(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
 			       size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream);
+
+/* ---- MS-side receive gain control: slot levels and maybe_update_gain() on the device ----------------------------------------
+ * What the reference does with do_auto_gain (ms/ms_upper.cpp:491): normed_abs_sum() (ms/ms.h:116-126) of every cut slot and
+ * ms_trx::maybe_update_gain() on it (ms/ms_rx_lower.cpp:101-126, called at :149-150), and the level gate of search_for_sch()
+ * (:333-347) in front of an acquire.  Bit for bit: there is no tolerance in any of it.
+ * level: float sum = 0; for the 2 * len int16 values in order: sum += abs(value) (abs(-32768) is 32768); sum /= 2 * len -- the
+ *   reference's sequential float sum.
+ * maybe_update_gain(sum), per cut slot: runmean = gain_check ? (runmean * (gain_check + 2) - 1 + sum) / (gain_check + 2) : sum,
+ *   every operation rounded to float; at gain_check == 159 the decision: gainoffset (a bool: the variable is `auto` from a
+ *   comparison) = runmean < (rxFullScale / 2 ? 2 : 1); newgain = runmean < (rxFullScale * 2) / 3 ? rxgain + gainoffset : rxgain -
+ *   gainoffset; applied when newgain != rxgain && newgain <= 60; then runmean = 0; gain_check = (gain_check + 1) % 160.
+ * gate: search when level > rxFullScale / 8 (unsigned division) || rxgain >= 60, else raise the gain by 4.
+ * rxFullScale is the object's rx_full_scale truncated to unsigned.  Defined where the reference is not: an SCH slot is measured
+ *   on its own 625 samples (the reference sums a union that holds the 148 sch_bits and stale stack, ms/ms.h:128-144); an applied
+ *   decision is the member's rx_gain at once (the reference hands setRxGain() to a worker thread).
+ * trxhip_ms_level_batch_i16(): d_level[r] = the level of row r, row_len (1 .. TRXHIP_SCH_SYNC_MAX_LEN) int16 I, Q samples at
+ *   d_in + 2 * r * row_stride; d_in 4-byte aligned, row_stride >= row_len in samples (rows are 4-byte aligned only).
+ * trxhip_ms_agc_gate(): pure host; TRXHIP_MS_AGC_SEARCH (*new_gain = rx_gain) or TRXHIP_MS_AGC_RAISE (*new_gain = rx_gain + 4).
+ * A scheduler member with gain control on (trxhip_ms_agc_sched_set / trxhip_ms_agc_group_set: {enable, rx_gain, d_level}; the
+ *   calls of the single object are those of member 0 of a group of one): every int16 pull measures the slots it cuts, slot k
+ *   of member m to d_level[m * out_stride + k] where d_level is given (float, 4-byte aligned; the single object: d_level[k],
+ *   k < *n_slots; a group passes one array to all its members), and runs maybe_update_gain() over them in order.  The state is
+ *   per member and lives on the device: gain_check, runmean, rx_gain, counters, the last TRXHIP_MS_AGC_RING decisions.
+ *   set leaves gain_check, runmean, the counters and the ring as they are; set_clock and acquire do not touch any of it (the
+ *   reference's gain_check and runmean are function statics).  Members are on or off independently; a member without a chunk,
+ *   or one whose chunk only extends the partial slot, keeps its state.  A refused pull moves no AGC state.  A complex64 pull
+ *   on a member with gain control on is TRXHIP_EINVAL, state untouched (the reference's radio buffers are int16).
+ *   Issued per pull in which a member with gain control on cuts a slot, whatever n_members is: three launches (levels, the
+ *   recurrence by pieces of a 160-slot window, the decisions) and one event record behind the pull's own; 64 bytes per such
+ *   member ride in the pull's table; no wait, no further copy.  A pull whose level and piece results need more room than any
+ *   before it allocates first.  With gain control off everywhere a pull issues what it issued before.
+ *   _set, _set_gain and _state wait for the AGC launches in flight.  _state: ring[0 .. n_records) oldest first.
+ *   Plan-only objects take the levels of the slots they cut from the queue of _feed_levels (it replaces the queue; a pull that
+ *   cuts more slots than the queue holds is TRXHIP_EINVAL) and run the same recurrence on the host; they take no d_level. */
+#define TRXHIP_MS_AGC_RING   8
+#define TRXHIP_MS_AGC_RAISE  0
+#define TRXHIP_MS_AGC_SEARCH 1
+typedef struct trxhip_ms_agc_cfg {  /* 16 bytes */
+	int32_t  enable;
+	float    rx_gain;        /* rxgain, dB */
+	float   *d_level;        /* device, may be NULL */
+} trxhip_ms_agc_cfg;
+typedef struct trxhip_ms_agc_record {  /* 32 bytes: one decision */
+	uint64_t slot;           /* the slots measured before the one that closed the window */
+	float    runmean, sum;   /* at the decision; sum: the closing slot's level */
+	float    old_gain, new_gain;
+	uint32_t applied;        /* newgain != rxgain && newgain <= 60: new_gain became rx_gain */
+	uint32_t reserved;
+} trxhip_ms_agc_record;
+typedef struct trxhip_ms_agc_status {  /* 304 bytes */
+	float    rx_gain, runmean;
+	uint32_t gain_check;
+	uint8_t  enable, reserved[3];
+	uint64_t slots, decisions, applied;
+	uint32_t n_records, reserved2;
+	trxhip_ms_agc_record ring[TRXHIP_MS_AGC_RING];
+} trxhip_ms_agc_status;
+int  trxhip_ms_level_batch_i16(trxhip_ctx *ctx, const int16_t *d_in, size_t n_rows, size_t row_len, size_t row_stride, float *d_level,
+			       void *stream);
+int  trxhip_ms_agc_gate(float level, float rx_full_scale, float rx_gain, float *new_gain);
+int  trxhip_ms_agc_sched_set(trxhip_ms_sched *s, const trxhip_ms_agc_cfg *cfg);
+int  trxhip_ms_agc_sched_set_gain(trxhip_ms_sched *s, float rx_gain);
+int  trxhip_ms_agc_sched_state(trxhip_ms_sched *s, trxhip_ms_agc_status *out);
+int  trxhip_ms_agc_sched_feed_levels(trxhip_ms_sched *s, const float *levels, size_t n);   /* plan-only objects */
+int  trxhip_ms_agc_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_agc_cfg *cfg);
+int  trxhip_ms_agc_group_set_gain(trxhip_ms_group *g, uint32_t member, float rx_gain);
+int  trxhip_ms_agc_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_agc_status *out);
+int  trxhip_ms_agc_group_feed_levels(trxhip_ms_group *g, uint32_t member, const float *levels, size_t n);   /* plan-only groups */
 
 /* ---- The MS-side uplink burst scheduler: burst requests in, the radio's transmit sample stream out --------------------------
  * What the reference does between trxcon's burst request and the radio: upper_trx::driveTx() (ms/ms_upper.cpp:306-355),

@@ -87,6 +87,15 @@ int trx_launch_ms_rx_group(const struct trx_mss_member *d_tab, int i16, size_t n
 			   hipStream_t stream);
 #define TRX_MS_RX_SLOTS_PER_WAVE 4      /* VA_BPW: slots per wave in all three forms */
 
+/* trx_ms_agc.hip: the MS-side receive gain control.  _level_rows: normed_abs_sum() of n_rows rows of row_len int16 samples,
+ * row_stride samples apart.  _agc: the three launches of a pull with gain control on (trx_ms_agc.h) -- the levels of n_waves
+ * slots, one per wave, the recurrence over n_pieces pieces, the decisions of n_entries members -- over the one entry h_entry,
+ * passed as a kernel argument (d_tab unused), or over the n_entries entries of d_tab (h_entry NULL) */
+struct trx_agc_entry;
+int trx_launch_ms_level_rows(const int16_t *d_in, size_t n_rows, size_t row_len, size_t row_stride, float *d_level, hipStream_t stream);
+int trx_launch_ms_agc(const struct trx_agc_entry *h_entry, const struct trx_agc_entry *d_tab, size_t n_entries, size_t n_waves,
+		      size_t n_pieces, uint32_t full_scale, hipStream_t stream);
+
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,
 			 size_t n_bursts, float rssi_offset, hipStream_t stream);

@@ -30,6 +30,7 @@
 #include "../../include/trxhip.h"
 #include "trx_ctx.h"
 #include "trx_launch.h"
+#include "trx_ms_agc.h"
 #include "trx_ms_sched.h"
 
 namespace {
@@ -37,6 +38,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr size_t kMaxSamples = (size_t)1 << 40;
 constexpr int kTabSlots = 4;                   /* pinned table areas of a group: the host runs at most this many launch sets ahead */
+constexpr size_t kTabEntries = 3;              /* table entries per member: receiver, join, gain control */
 
 // ------------------------------------------------------------------------------------------------
 // The join of one member, one block, from its entry (trx_mss_join).  The stream of a pull is the carried partial slot (rem_in,
@@ -83,7 +85,8 @@ ms_join_group_kernel(const trx_mss_join *__restrict__ tab)
 	ms_join<T>(j);
 }
 
-static_assert(sizeof(trx_mss_join) == 64 && sizeof(trx_mss_member) == 64, "table entries");
+static_assert(sizeof(trx_mss_join) == 64 && sizeof(trx_mss_member) == 64 && sizeof(trx_agc_entry) == 64, "table entries");
+static_assert(sizeof(trxhip_ms_agc_record) == 32 && sizeof(trxhip_ms_agc_status) == 304 && sizeof(trxhip_ms_agc_cfg) == 16, "public AGC structs");
 
 // One downlink stream on the host: what a group holds per member
 struct ms_member {
@@ -115,6 +118,13 @@ struct ms_member {
 	std::vector<int32_t> feed;
 	size_t feed_at = 0;
 	int rem_half = 0;                      /* device: the half of the partial-slot area the next pull reads */
+	// gain control (trx_ms_agc.h).  agc: the state of a plan-only member; of a device member its gain_check alone, which only
+	// counts slots -- the rest lives on the device
+	bool agc_on = false;
+	float *d_level = nullptr;
+	trx_agc_state agc = {};
+	std::vector<float> lv_feed;            /* plan-only: the levels fed from outside */
+	size_t lv_at = 0;
 };
 
 // The plan of one member's pull.  plan_begin() fills the first part, plan_finish() the second; neither moves the member.
@@ -165,6 +175,13 @@ struct trxhip_ms_group {
 	int tab_at = 0;                        /* the event, and the area, the next launch set takes */
 	int corr_at = 0;                       /* those of the last launch set that summed corrections */
 	hipEvent_t ev = nullptr;               /* acquire's */
+	// gain control: the members' states, the levels and piece results of the pull in flight (it grows), the event behind the
+	// AGC launches of the last pull that had any
+	trx_agc_state *d_agc = nullptr;
+	float *d_work = nullptr;
+	size_t work_floats = 0;
+	hipEvent_t ev_agc = nullptr;
+	bool agc_used = false;
 };
 
 namespace {
@@ -457,7 +474,39 @@ char *stage_table(trxhip_ms_group *g)
 	const int h = g->tab_at;
 	if (g->tab_used[h] && hipEventSynchronize(g->ev_tab[h]) != hipSuccess)
 		return nullptr;
-	return g->h_tab + (size_t)h * 2 * g->m.size() * 64;
+	return g->h_tab + (size_t)h * kTabEntries * g->m.size() * 64;
+}
+
+// What a member with gain control on adds to the pull's own launch set: an entry, a wave per slot, its pieces, and room for its
+// levels and piece results.  Every slot the pull cuts counts, slot 0 too where the pull has waited for it (its row is assembled)
+struct agc_work {
+	size_t n_slots, n_pieces, floats;
+};
+
+agc_work agc_work_of(const ms_member &m, const ms_plan &p)
+{
+	agc_work w = { 0, 0, 0 };
+	if (!m.agc_on || p.extend || p.cnt == 0)
+		return w;
+	w.n_slots = (size_t)p.cnt;
+	w.n_pieces = trx_agc_pieces(m.agc.gain_check, (uint64_t)p.cnt);
+	w.floats = w.n_slots + 2 * w.n_pieces;
+	return w;
+}
+
+// room for the levels and piece results of a pull; a pull that needs more than any before waits for the device and allocates
+int reserve_work(trxhip_ms_group *g, size_t floats)
+{
+	if (floats <= g->work_floats)
+		return TRXHIP_OK;
+	if (g->d_work && hipFree(g->d_work) != hipSuccess)
+		return TRXHIP_EIO;
+	g->d_work = nullptr;
+	g->work_floats = 0;
+	if (hipMalloc((void **)&g->d_work, floats * sizeof(float)) != hipSuccess)
+		return TRXHIP_ENOMEM;
+	g->work_floats = floats;
+	return TRXHIP_OK;
 }
 
 char *rem_of(trxhip_ms_group *g, size_t i, int half, int cf32)
@@ -493,24 +542,30 @@ ms_work work_of(const ms_member &m, const ms_plan &p, bool prelim)
 // entries, the copy of the correction words to the mailbox, one event behind all of it.
 // The single object (direct) issues the same sequence without the table: its one join entry and its one receiver entry are the
 // arguments of ms_join_kernel and of the receiver's stream form.
+// Gain control (n_agc members of the pull's own set have it on and cut a slot; none in a prelim set): their entries
+// (trx_ms_agc.h) ride in the same table behind the join entries, or are the single object's kernel argument, and BEHIND the
+// set's event -- so that nothing that waits for a correction waits for them -- come the three AGC launches and their own event.
 int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf32, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
-		size_t out_stride, bool prelim, size_t n_rx, size_t n_join, size_t n_waves, hipStream_t st)
+		size_t out_stride, bool prelim, size_t n_rx, size_t n_join, size_t n_waves, size_t n_agc, hipStream_t st)
 {
 	trx_mss_member own_rx;
 	trx_mss_join own_join;
+	trx_agc_entry own_agc;
 	trx_mss_member *rx = &own_rx;
 	trx_mss_join *jn = &own_join;
+	trx_agc_entry *ag = &own_agc;
 	if (!g->direct) {
 		char *tab = stage_table(g);
 		if (!tab)
 			return TRXHIP_EIO;
 		rx = reinterpret_cast<trx_mss_member *>(tab);
 		jn = reinterpret_cast<trx_mss_join *>(tab + n_rx * 64);
+		ag = reinterpret_cast<trx_agc_entry *>(tab + (n_rx + n_join) * 64);
 	}
-	if (n_rx + n_join == 0)
+	if (n_rx + n_join + n_agc == 0)
 		return TRXHIP_OK;                                      /* (no slot and no join: no sum either) */
 
-	size_t kr = 0, kj = 0, wave = 0;
+	size_t kr = 0, kj = 0, wave = 0, ka = 0, agc_waves = 0, agc_pieces = 0, agc_floats = 0;
 	bool sum = false;
 	for (size_t i = 0; i < g->m.size(); i++) {
 		const ms_plan &p = g->plan[i];
@@ -536,6 +591,24 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 				j.n_tail = (uint32_t)p.frac;
 			}
 		}
+		const agc_work a = prelim ? agc_work{ 0, 0, 0 } : agc_work_of(m, p);
+		if (a.n_slots) {
+			trx_agc_entry &e = ag[ka++];
+			memset(&e, 0, sizeof(e));
+			e.chunk = h_chunks[i].d_in;
+			e.edge_row = p.straddle ? edge_row : nullptr;          /* assembled by this set's join, or by the prelim set's */
+			e.first = p.to_skip;
+			e.state = g->d_agc + i;
+			e.level = m.d_level ? m.d_level + i * out_stride : nullptr;
+			e.work = g->d_work + agc_floats;
+			e.n_slots = (uint32_t)a.n_slots;
+			e.first_wave = (uint32_t)agc_waves;
+			e.first_piece = (uint32_t)agc_pieces;
+			e.gain_check = m.agc.gain_check;
+			agc_waves += a.n_slots;
+			agc_pieces += a.n_pieces;
+			agc_floats += a.floats;
+		}
 		if (!w.n_slots)
 			continue;
 		sum = sum || w.sum;
@@ -559,10 +632,10 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		e.first_wave = (uint32_t)wave;
 		wave += (w.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
 	}
-	if (kr != n_rx || kj != n_join || wave != n_waves)
+	if (kr != n_rx || kj != n_join || wave != n_waves || ka != n_agc || agc_floats > g->work_floats)
 		return TRXHIP_EIO;
 
-	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, (n_rx + n_join) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
+	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, (n_rx + n_join + n_agc) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
 		return TRXHIP_EIO;
 	if (n_join) {
 		const trx_mss_join *jt = g->direct ? nullptr : reinterpret_cast<const trx_mss_join *>(g->d_tab + n_rx * 64);
@@ -597,6 +670,13 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 	if (sum)
 		g->corr_at = h;
 	g->tab_at = (h + 1) % kTabSlots;
+	if (n_agc) {
+		const trx_agc_entry *at = g->direct ? nullptr : reinterpret_cast<const trx_agc_entry *>(g->d_tab + (n_rx + n_join) * 64);
+		if (trx_launch_ms_agc(g->direct ? ag : nullptr, at, n_agc, agc_waves, agc_pieces, trx_agc_full_scale(g->rx_full_scale), st) != 0 ||
+		    hipEventRecord(g->ev_agc, st) != hipSuccess)
+			return TRXHIP_EIO;
+		g->agc_used = true;
+	}
 	return TRXHIP_OK;
 }
 
@@ -643,6 +723,10 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 			refuse(i, rc);
 			continue;
 		}
+		if (g->m[i].agc_on && cf32) {
+			refuse(i, TRXHIP_EINVAL);                              /* gain control measures int16 samples */
+			continue;
+		}
 		if (!g->plan[i].extend) {
 			any_tracked = any_tracked || g->m[i].tracking;
 			n_pre += g->plan[i].prelim;
@@ -655,12 +739,12 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 
 	// ---- the straddling SCH slots the cutters follow, one slot per member in one launch set: the second
 	if (device && n_pre &&
-	    (issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, true, n_pre, n_pre, n_pre, st) != TRXHIP_OK ||
+	    (issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, true, n_pre, n_pre, n_pre, 0, st) != TRXHIP_OK ||
 	     hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess))
 		return TRXHIP_EIO;
 
 	// ---- the rest of every plan
-	size_t n_rx = 0, n_join = 0, n_waves = 0;
+	size_t n_rx = 0, n_join = 0, n_waves = 0, n_agc = 0, agc_floats = 0;
 	for (size_t i = 0; i < n; i++) {
 		if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK)
 			continue;
@@ -672,6 +756,13 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 				continue;
 			}
 		}
+		const agc_work a = agc_work_of(g->m[i], p);
+		if (!device && a.n_slots > g->m[i].lv_feed.size() - g->m[i].lv_at) {
+			refuse(i, TRXHIP_EINVAL);                              /* plan-only: more slots than levels fed */
+			continue;
+		}
+		n_agc += a.n_slots != 0;
+		agc_floats += a.floats;
 		const ms_work w = work_of(g->m[i], p, false);
 		n_join += w.join;
 		if (w.n_slots) {
@@ -679,7 +770,7 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 			n_waves += (w.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
 		}
 	}
-	if (bad == n && n_waves > 0x7fffffffu) {
+	if (bad == n && (n_waves > 0x7fffffffu || agc_floats > 0x7fffffffu)) {     /* (agc_floats: more than a wave per measured slot) */
 		bad = first;
 		worst = TRXHIP_EINVAL;
 	}
@@ -690,7 +781,12 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 	}
 
 	// ---- the issue: the pull's own launch set
-	if (device && issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, false, n_rx, n_join, n_waves, st) != TRXHIP_OK)
+	if (device && n_agc) {
+		const int rc = reserve_work(g, agc_floats);
+		if (rc != TRXHIP_OK)
+			return rc;
+	}
+	if (device && issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, false, n_rx, n_join, n_waves, n_agc, st) != TRXHIP_OK)
 		return TRXHIP_EIO;
 
 	// ---- and every member moves
@@ -703,6 +799,13 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 					m.rem_half ^= 1;
 				if (work_of(m, p, false).sum)
 					m.unread = true;
+			}
+			const agc_work a = agc_work_of(m, p);
+			if (a.n_slots && device) {
+				m.agc.gain_check = (uint32_t)((m.agc.gain_check + a.n_slots) % TRX_AGC_WINDOW);
+			} else if (a.n_slots) {
+				trx_agc_run(&m.agc, m.lv_feed.data() + m.lv_at, a.n_slots, trx_agc_full_scale(g->rx_full_scale));
+				m.lv_at += a.n_slots;
 			}
 			commit(m, p);
 		}
@@ -795,19 +898,21 @@ int group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const t
 	}
 	g->ctx = ctx;
 	const size_t n = n_members;
-	const size_t rem_bytes = n * 2 * TRX_MSS_REM_STRIDE * 8, tab_bytes = 2 * n * 64;     /* tab_bytes: one table */
+	const size_t rem_bytes = n * 2 * TRX_MSS_REM_STRIDE * 8, tab_bytes = kTabEntries * n * 64;     /* tab_bytes: one table */
 	bool ok = hipMalloc((void **)&g->d_rem, rem_bytes) == hipSuccess && hipMalloc((void **)&g->d_edge, n * TRX_MSS_SLOT * 8) == hipSuccess &&
 		  hipMalloc((void **)&g->d_corr, n * sizeof(int32_t)) == hipSuccess && hipMalloc((void **)&g->d_acq, n * sizeof(*g->d_acq)) == hipSuccess &&
 		  hipHostMalloc((void **)&g->h_corr, n * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
 		  hipHostMalloc((void **)&g->h_acq, n * sizeof(*g->h_acq), hipHostMallocDefault) == hipSuccess &&
-		  hipEventCreateWithFlags(&g->ev, hipEventDisableTiming) == hipSuccess;
+		  hipEventCreateWithFlags(&g->ev, hipEventDisableTiming) == hipSuccess &&
+		  hipMalloc((void **)&g->d_agc, n * sizeof(trx_agc_state)) == hipSuccess &&
+		  hipEventCreateWithFlags(&g->ev_agc, hipEventDisableTiming) == hipSuccess;
 	if (!direct)
 		ok = ok && hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
 		     hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess;
 	for (int h = 0; h < kTabSlots; h++)
 		ok = ok && hipEventCreateWithFlags(&g->ev_tab[h], hipEventDisableTiming) == hipSuccess;
 	ok = ok && hipMemset(g->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(g->d_corr, 0, n * sizeof(int32_t)) == hipSuccess &&
-	     hipStreamSynchronize(nullptr) == hipSuccess;      /* the first pull may come on a stream that does not wait for the null stream */
+	     hipMemset(g->d_agc, 0, n * sizeof(trx_agc_state)) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;      /* the first pull may come on a stream that does not wait for the null stream */
 	if (!ok) {
 		trxhip_ms_group_destroy(g);
 		return TRXHIP_ENOMEM;
@@ -842,7 +947,12 @@ void trxhip_ms_group_destroy(trxhip_ms_group *g)
 			if (g->ev_tab[h]) (void)hipEventDestroy(g->ev_tab[h]);
 		}
 		if (g->ev) (void)hipEventDestroy(g->ev);
-		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab };
+		if (g->ev_agc) {
+			if (g->agc_used)
+				(void)hipEventSynchronize(g->ev_agc);
+			(void)hipEventDestroy(g->ev_agc);
+		}
+		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work };
 		for (void *p : bufs)
 			if (p) (void)hipFree(p);
 		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab };
@@ -956,6 +1066,84 @@ int trxhip_ms_group_pull_cf32(trxhip_ms_group *g, const trxhip_ms_group_chunk *h
 			      size_t out_stride, size_t *h_n_slots, size_t *h_n_carried, int *bad_member, void *stream)
 {
 	return group_pull(g, h_chunks, 1, d_ind, d_bits, out_stride, h_n_slots, h_n_carried, bad_member, stream);
+}
+
+// ---- gain control (trx_ms_agc.h) -----------------------------------------------------------------
+
+// the AGC launches in flight are through: the member's state on the device may be read or written from the host
+static int agc_settled(trxhip_ms_group *g)
+{
+	if (with_device(g->ctx) || (g->agc_used && hipEventSynchronize(g->ev_agc) != hipSuccess))
+		return TRXHIP_EIO;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_agc_group_set_gain(trxhip_ms_group *g, uint32_t member, float rx_gain)
+{
+	ms_member *m = member_of(g, member);
+	if (!m || !std::isfinite(rx_gain))
+		return TRXHIP_EINVAL;
+	if (g->ctx && (agc_settled(g) != TRXHIP_OK ||
+		       hipMemcpy(&g->d_agc[member].rx_gain, &rx_gain, sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
+		return TRXHIP_EIO;
+	m->agc.rx_gain = rx_gain;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_agc_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_agc_cfg *cfg)
+{
+	ms_member *m = member_of(g, member);
+	if (!m || !cfg || !std::isfinite(cfg->rx_gain) || (cfg->d_level && (!g->ctx || (reinterpret_cast<uintptr_t>(cfg->d_level) & 3))))
+		return TRXHIP_EINVAL;
+	const int rc = trxhip_ms_agc_group_set_gain(g, member, cfg->rx_gain);
+	if (rc != TRXHIP_OK)
+		return rc;
+	m->agc_on = cfg->enable != 0;
+	m->d_level = cfg->d_level;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_agc_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_agc_status *out)
+{
+	const ms_member *m = member_of(g, member);
+	if (!m || !out)
+		return TRXHIP_EINVAL;
+	trx_agc_state s = m->agc;
+	if (g->ctx && (agc_settled(g) != TRXHIP_OK || hipMemcpy(&s, g->d_agc + member, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess))
+		return TRXHIP_EIO;
+	memset(out, 0, sizeof(*out));
+	out->rx_gain = s.rx_gain;
+	out->runmean = s.runmean;
+	out->gain_check = s.gain_check;
+	out->enable = m->agc_on;
+	out->slots = s.slots;
+	out->decisions = s.decisions;
+	out->applied = s.applied;
+	out->n_records = (uint32_t)(s.decisions < TRX_AGC_RING ? s.decisions : TRX_AGC_RING);
+	for (uint32_t k = 0; k < out->n_records; k++)
+		out->ring[k] = s.ring[(s.decisions - out->n_records + k) % TRX_AGC_RING];
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_agc_group_feed_levels(trxhip_ms_group *g, uint32_t member, const float *levels, size_t n)
+{
+	ms_member *m = member_of(g, member);
+	if (!m || g->ctx || (!levels && n))
+		return TRXHIP_EINVAL;
+	m->lv_feed.assign(levels, levels + n);
+	m->lv_at = 0;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_agc_sched_set(trxhip_ms_sched *s, const trxhip_ms_agc_cfg *cfg) { return trxhip_ms_agc_group_set(group_of(s), 0, cfg); }
+
+int trxhip_ms_agc_sched_set_gain(trxhip_ms_sched *s, float rx_gain) { return trxhip_ms_agc_group_set_gain(group_of(s), 0, rx_gain); }
+
+int trxhip_ms_agc_sched_state(trxhip_ms_sched *s, trxhip_ms_agc_status *out) { return trxhip_ms_agc_group_state(group_of(s), 0, out); }
+
+int trxhip_ms_agc_sched_feed_levels(trxhip_ms_sched *s, const float *levels, size_t n)
+{
+	return trxhip_ms_agc_group_feed_levels(group_of(s), 0, levels, n);
 }
 
 // ---- the single object: member 0 of a group of one that issues directly -------------------------

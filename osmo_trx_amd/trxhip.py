@@ -220,6 +220,16 @@ SYMBOLS = {
     "trxhip_ms_group_acquire_cf32": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP]),
     "trxhip_ms_group_pull_s16": (_I, [_VP, _VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(_I), _VP]),
     "trxhip_ms_group_pull_cf32": (_I, [_VP, _VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(_I), _VP]),
+    "trxhip_ms_level_batch_i16": (_I, [_VP, _VP, _SZ, _SZ, _SZ, _VP, _VP]),
+    "trxhip_ms_agc_gate": (_I, [_F, _F, _F, C.POINTER(_F)]),
+    "trxhip_ms_agc_sched_set": (_I, [_VP, _VP]),
+    "trxhip_ms_agc_sched_set_gain": (_I, [_VP, _F]),
+    "trxhip_ms_agc_sched_state": (_I, [_VP, _VP]),
+    "trxhip_ms_agc_sched_feed_levels": (_I, [_VP, _VP, _SZ]),
+    "trxhip_ms_agc_group_set": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_agc_group_set_gain": (_I, [_VP, C.c_uint32, _F]),
+    "trxhip_ms_agc_group_state": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_agc_group_feed_levels": (_I, [_VP, C.c_uint32, _VP, _SZ]),
     "trxhip_ms_tx_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
     "trxhip_ms_tx_destroy": (None, [_VP]),
     "trxhip_ms_tx_set_ta": (_I, [_VP, _I]),
@@ -249,7 +259,8 @@ def load_library():
     except OSError as e:  # pragma: no cover
         raise TrxHipError(f"cannot load {path}: {e}") from e
     for name, (res, args) in SYMBOLS.items():
-        if (name == "trxhip_fast_stats" or name.startswith("trxhip_hostpipe_")) and os.environ.get("TRXHIP_LIB") and not hasattr(L, name):
+        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_"))) and \
+                os.environ.get("TRXHIP_LIB") and not hasattr(L, name):
             continue          # tools/measure.py ab against an older measurement build of the library (product: always bound)
         f = getattr(L, name)  # AttributeError if the export is missing
         f.restype = res
@@ -602,6 +613,23 @@ class TrxHip:
                   n, rx_full_scale, self._stream(stream)), name)
         rec = ind.cpu().numpy().reshape(-1).view(MS_IND_DTYPE)
         return rec, (bits.cpu().numpy() if want_bits else None)
+
+    def ms_level(self, rows, row_len=None, row_stride=None, n_rows=None, stream=None):
+        """normed_abs_sum() (ms/ms.h:116-126) of int16 rows, bit for bit the reference's sequential float sum: rows int16[n, len, 2],
+        or a flat int16[total, 2] buffer (a view that begins at any sample) holding n_rows rows of row_len samples, row_stride
+        samples apart.  Returns a float32[n] device tensor; does not wait."""
+        torch = self.torch
+        assert rows.dtype == torch.int16 and rows.shape[-1] == 2, (rows.shape, rows.dtype)
+        if rows.dim() == 3:
+            n, length = rows.shape[0], rows.shape[1]
+            stride = length
+        else:
+            n, length, stride = int(n_rows), int(row_len), int(row_stride if row_stride is not None else row_len)
+            assert rows.dim() == 2 and n >= 0 and (n == 0 or (n - 1) * stride + length <= rows.shape[0]), (rows.shape, n, length, stride)
+        out = torch.empty((n,), dtype=torch.float32, device=rows.device)
+        _check(self.L.trxhip_ms_level_batch_i16(self.h, self._dev(rows), n, length, stride, self._dev(out), self._stream(stream)),
+               "trxhip_ms_level_batch_i16")
+        return out
 
     @staticmethod
     def results_to_numpy(results):
@@ -1142,6 +1170,38 @@ MS_SCHED_STATE_DTYPE = np.dtype([("to_skip", "<i8"), ("pending", "<i8"), ("first
                                  ("clock_set", "u1"), ("reserved", "u1", (6,)), ("clock_jumps", "<u8"), ("pulls", "<u8"),
                                  ("slots", "<u8"), ("sch_slots", "<u8")])
 assert MS_PLAN_DTYPE.itemsize == 24 and MS_SCHED_STATE_DTYPE.itemsize == 72
+# MS-side receive gain control: trxhip_ms_agc_record / _status, TRXHIP_MS_AGC_*
+MS_AGC_RAISE, MS_AGC_SEARCH = 0, 1
+MS_AGC_RING = 8
+RAISE = "RAISE"                                      # acquire_gated(): the buffer is below the gate, (RAISE, new_gain)
+MS_AGC_RECORD_DTYPE = np.dtype([("slot", "<u8"), ("runmean", "<f4"), ("sum", "<f4"), ("old_gain", "<f4"), ("new_gain", "<f4"),
+                                ("applied", "<u4"), ("reserved", "<u4")])
+MS_AGC_STATE_DTYPE = np.dtype([("rx_gain", "<f4"), ("runmean", "<f4"), ("gain_check", "<u4"), ("enable", "u1"), ("reserved", "u1", (3,)),
+                               ("slots", "<u8"), ("decisions", "<u8"), ("applied", "<u8"), ("n_records", "<u4"), ("reserved2", "<u4"),
+                               ("ring", MS_AGC_RECORD_DTYPE, (MS_AGC_RING,))])
+assert MS_AGC_RECORD_DTYPE.itemsize == 32 and MS_AGC_STATE_DTYPE.itemsize == 304
+
+
+class _MsAgcCfg(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("rx_gain", C.c_float), ("d_level", C.c_void_p)]
+
+
+def ms_agc_gate(level, rx_full_scale, rx_gain):
+    """The level gate of search_for_sch() (ms/ms_rx_lower.cpp:333-347), pure host: (MS_AGC_SEARCH, rx_gain) when level >
+    rxFullScale / 8 or rx_gain >= 60, else (MS_AGC_RAISE, rx_gain + 4)."""
+    new = _F()
+    rc = load_library().trxhip_ms_agc_gate(level, rx_full_scale, rx_gain, C.byref(new))
+    if rc < 0:
+        _check(rc, "trxhip_ms_agc_gate")
+    return rc, new.value
+
+
+def _agc_state_dict(a):
+    """MS_AGC_STATE_DTYPE record -> dict; "ring": the last decisions, oldest first, as dicts"""
+    d = {k: a[k].item() for k in ("rx_gain", "runmean", "gain_check", "slots", "decisions", "applied")}
+    d["enable"] = bool(a["enable"])
+    d["ring"] = [{k: r[k].item() for k in ("slot", "runmean", "sum", "old_gain", "new_gain", "applied")} for r in a["ring"][:int(a["n_records"])]]
+    return d
 
 
 class _MsSchedCfg(C.Structure):
@@ -1163,6 +1223,8 @@ class MsRxScheduler:
         self.h = h
         self._last = 0
         self.carried = 0
+        self.rx_full_scale = float(rx_full_scale)
+        self._agc, self._levels, self._lv = False, False, None
 
     def set_clock(self, fn, tn, ts=0):
         _check(self.L.trxhip_ms_sched_set_clock(self.h, fn, tn, ts), "trxhip_ms_sched_set_clock")
@@ -1205,6 +1267,53 @@ class MsRxScheduler:
             self.carried = 0
         return bool(rc), rec[0]
 
+    # ---- receive gain control (trxhip_ms_agc_sched_*) ----
+    def _agc_set(self, enable, rx_gain, lv):
+        cfg = _MsAgcCfg(int(bool(enable)), rx_gain, lv.data_ptr() if lv is not None else None)
+        _check(self.L.trxhip_ms_agc_sched_set(self.h, C.byref(cfg)), "trxhip_ms_agc_sched_set")
+
+    def set_agc(self, enable, rx_gain, levels=False):
+        """maybe_update_gain() (ms/ms_rx_lower.cpp:101-126) over every slot an int16 pull cuts, starting from rx_gain; levels:
+        pull() also returns the slots' levels.  gain_check, runmean, the counters and the ring stay as they are."""
+        self._agc, self._levels = bool(enable), bool(enable) and bool(levels) and self.trx is not None
+        if not self._levels:
+            self._lv = None
+        self._agc_set(enable, rx_gain, self._lv)
+
+    def agc_set_gain(self, rx_gain):
+        _check(self.L.trxhip_ms_agc_sched_set_gain(self.h, rx_gain), "trxhip_ms_agc_sched_set_gain")
+
+    def agc_state(self):
+        """dict: rx_gain, runmean, gain_check, enable, slots, decisions, applied, ring (the last 8 decisions, oldest first);
+        waits for the AGC work in flight"""
+        a = np.zeros(1, dtype=MS_AGC_STATE_DTYPE)
+        _check(self.L.trxhip_ms_agc_sched_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_agc_sched_state")
+        return _agc_state_dict(a[0])
+
+    def feed_levels(self, levels):
+        """plan-only: the levels of the next slots cut with gain control on"""
+        a = np.ascontiguousarray(levels, dtype=np.float32)
+        _check(self.L.trxhip_ms_agc_sched_feed_levels(self.h, a.ctypes.data_as(_VP), len(a)), "trxhip_ms_agc_sched_feed_levels")
+
+    def _level_room(self, n):
+        """the level array of the pulls holds n floats (a larger one is set with the gain as it stands: that waits)"""
+        if self._lv is None or self._lv.numel() < n:
+            self._lv = self.trx.torch.empty((max(n, 64),), dtype=self.trx.torch.float32, device=f"cuda:{self.trx.device}")
+            self._agc_set(True, self.agc_state()["rx_gain"], self._lv)
+
+    def acquire_gated(self, x, first_ts=0, rx_gain=None, stream=None):
+        """search_for_sch()'s worker (ms/ms_rx_lower.cpp:333-347) on the int16[n, 2] buffer x: its level, one wait, the gate with
+        rx_gain (default: the object's), then acquire()'s (found, record) -- or (RAISE, rx_gain + 4), nothing else touched."""
+        lv = self.trx.ms_level(x.reshape(1, -1, 2), stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        level = lv.item()
+        gain = self.agc_state()["rx_gain"] if rx_gain is None else rx_gain
+        what, new = ms_agc_gate(level, self.rx_full_scale, gain)
+        if what == MS_AGC_RAISE:
+            return RAISE, new
+        return self.acquire(x, first_ts, stream=stream)
+
     def slots(self, n_samples):
         n = self.L.trxhip_ms_sched_slots(self.h, n_samples)
         if n < 0:
@@ -1214,7 +1323,8 @@ class MsRxScheduler:
     def pull(self, x=None, first_ts=0, n_samples=None, want_bits=True, stream=None):
         """x: int16[n, 2] or complex64[n] device tensor, the chunk whose first sample has timestamp first_ts; plan-only:
         n_samples.  Returns (n_slots, n_carried) for a plan-only object, otherwise (ind uint8[n_slots, 32] (MS_IND_DTYPE),
-        sbits int8[n_slots, 148] or None) device tensors."""
+        sbits int8[n_slots, 148] or None) device tensors; after set_agc(..., levels=True) a third: the slots' levels,
+        float32[n_slots]."""
         ns, nc = _SZ(), _SZ()
         if self.trx is None:
             _check(self.L.trxhip_ms_sched_pull_s16(self.h, None, n_samples, first_ts, None, None, 0, C.byref(ns), C.byref(nc), None),
@@ -1229,10 +1339,14 @@ class MsRxScheduler:
         dev = f"cuda:{self.trx.device}"
         ind = torch.empty((max(cap, 1), MS_IND_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         bits = torch.empty((max(cap, 1), 148), dtype=torch.int8, device=dev) if want_bits else None
+        if self._levels:
+            self._level_room(cap)
         fn = self.L.trxhip_ms_sched_pull_s16 if s16 else self.L.trxhip_ms_sched_pull_cf32
         _check(fn(self.h, self.trx._dev(x), n_in, first_ts, self.trx._dev(ind), self.trx._dev(bits) if want_bits else None, cap,
                   C.byref(ns), C.byref(nc), self.trx._stream(stream)), "trxhip_ms_sched_pull")
         self._last, self.carried = ns.value, nc.value
+        if self._levels:                                     # (a view of the object's level array: the next pull writes it again)
+            return ind[:ns.value], (bits[:ns.value] if want_bits else None), self._lv[:ns.value]
         return ind[:ns.value], (bits[:ns.value] if want_bits else None)
 
     def plan(self, n=None):
@@ -1300,6 +1414,8 @@ class MsRxSchedulerGroup:
         self.h = h
         self.n_slots = [0] * self.n                  # of each member's last pull
         self.carried = [0] * self.n
+        self.rx_full_scale = float(rx_full_scale)
+        self._levels, self._lv = [False] * self.n, None
 
     def set_clock(self, m, fn, tn, ts=0):
         _check(self.L.trxhip_ms_group_set_clock(self.h, m, fn, tn, ts), "trxhip_ms_group_set_clock")
@@ -1351,6 +1467,62 @@ class MsRxSchedulerGroup:
                 self.carried[int(m)] = 0
         return found.astype(bool), rec
 
+    # ---- receive gain control (trxhip_ms_agc_group_*), per member ----
+    def _agc_set(self, m, enable, rx_gain, lv):
+        cfg = _MsAgcCfg(int(bool(enable)), rx_gain, lv.data_ptr() if lv is not None else None)
+        _check(self.L.trxhip_ms_agc_group_set(self.h, m, C.byref(cfg)), "trxhip_ms_agc_group_set")
+
+    def set_agc(self, m, enable, rx_gain, levels=False):
+        """member m: maybe_update_gain() over every slot its int16 pulls cut, starting from rx_gain; levels: pull() also returns
+        the member's levels.  Members are on or off independently."""
+        self._levels[m] = bool(enable) and bool(levels) and self.trx is not None
+        self._agc_set(m, enable, rx_gain, self._lv if self._levels[m] else None)
+
+    def agc_set_gain(self, m, rx_gain):
+        _check(self.L.trxhip_ms_agc_group_set_gain(self.h, m, rx_gain), "trxhip_ms_agc_group_set_gain")
+
+    def agc_state(self, m):
+        """member m's dict as MsRxScheduler.agc_state(); waits for the group's AGC work in flight"""
+        a = np.zeros(1, dtype=MS_AGC_STATE_DTYPE)
+        _check(self.L.trxhip_ms_agc_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_agc_group_state")
+        return _agc_state_dict(a[0])
+
+    def feed_levels(self, m, levels):
+        """plan-only: the levels of the next slots member m cuts with gain control on"""
+        a = np.ascontiguousarray(levels, dtype=np.float32)
+        _check(self.L.trxhip_ms_agc_group_feed_levels(self.h, m, a.ctypes.data_as(_VP), len(a)), "trxhip_ms_agc_group_feed_levels")
+
+    def _level_room(self, n):
+        """the group-wide level array holds n floats (a larger one is set on every member that returns levels, with its gain
+        as it stands: that waits)"""
+        if self._lv is None or self._lv.numel() < n:
+            self._lv = self.trx.torch.empty((max(n, 64),), dtype=self.trx.torch.float32, device=f"cuda:{self.trx.device}")
+            for m in range(self.n):
+                if self._levels[m]:
+                    self._agc_set(m, True, self.agc_state(m)["rx_gain"], self._lv)
+
+    def acquire_gated(self, members, bufs, first_ts=0, rx_gain=None, stream=None):
+        """The level gate in front of acquire(), int16 buffers: the levels of all buffers in one launch, one wait, the gate per member
+        with rx_gain (one value, one per buffer, or None: the members' own), then acquire() for the members that pass.  Returns
+        (found bool[n], records SCH_SYNC_DTYPE[n], new_gain: None where the member searched, else the raised gain, nothing of
+        that member touched)."""
+        members = [int(m) for m in members]
+        n = len(members)
+        lv = self.trx.ms_level(bufs, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        lv = lv.cpu().numpy()
+        gains = [self.agc_state(m)["rx_gain"] for m in members] if rx_gain is None else _per_member(rx_gain, n, "rx_gain")
+        ts = _per_member(first_ts, n, "first_ts")
+        gate = [ms_agc_gate(float(lv[i]), self.rx_full_scale, gains[i]) for i in range(n)]
+        go = [i for i in range(n) if gate[i][0] == MS_AGC_SEARCH]
+        found, rec = np.zeros(n, dtype=bool), np.zeros(n, dtype=SCH_SYNC_DTYPE)
+        if go:
+            sub = bufs if len(go) == n else bufs[go].contiguous()
+            f, r = self.acquire([members[i] for i in go], sub, [ts[i] for i in go], stream=stream)
+            found[go], rec[go] = f, r
+        return found, rec, [None if gate[i][0] == MS_AGC_SEARCH else gate[i][1] for i in range(n)]
+
     def slots(self, m, n_samples):
         n = self.L.trxhip_ms_group_slots(self.h, m, n_samples)
         if n < 0:
@@ -1364,7 +1536,8 @@ class MsRxSchedulerGroup:
         of out = (ind uint8[n, out_stride, 32], sbits int8[n, out_stride, 148] or None).  Plan-only: n_samples per member (0 or
         None: no chunk); returns ([n_slots], [n_carried]).  A plan-only group given an out_stride other than None / 0 refuses a
         pull in which a member would cut more slots than that, as the GPU group does; the plan-only MsRxScheduler has no such
-        bound (it takes no outputs), and neither has the group with out_stride None / 0."""
+        bound (it takes no outputs), and neither has the group with out_stride None / 0.  Where a member returns levels
+        (set_agc(m, ..., levels=True)) a third list follows: per member float32[k] levels, or None."""
         ts = _per_member(first_ts, self.n, "first_ts")
         ch = np.zeros(self.n, dtype=MS_GROUP_CHUNK_DTYPE)
         ns, nc = (_SZ * self.n)(), (_SZ * self.n)()
@@ -1404,13 +1577,19 @@ class MsRxSchedulerGroup:
             stride = cap if out_stride is None else int(out_stride)
             ind = torch.empty((self.n, max(stride, 1), MS_IND_DTYPE.itemsize), dtype=torch.uint8, device=dev)
             sb = torch.empty((self.n, max(stride, 1), 148), dtype=torch.int8, device=dev) if bits else None
+        if any(self._levels):
+            self._level_room(self.n * max(stride, 1))
         fn = self.L.trxhip_ms_group_pull_s16 if s16 else self.L.trxhip_ms_group_pull_cf32
         rc = fn(self.h, ch.ctypes.data_as(_VP), self.trx._dev(ind), self.trx._dev(sb) if sb is not None else None, stride,
                 C.cast(ns, _VP), C.cast(nc, _VP), C.byref(bad), self.trx._stream(stream))
         self.bad_member = bad.value
         _check(rc, "trxhip_ms_group_pull (member %d)" % bad.value)
         self.n_slots, self.carried = list(ns), list(nc)
-        return [(ind[m, :k], sb[m, :k] if sb is not None else None) for m, k in enumerate(self.n_slots)], list(self.n_slots)
+        res = [(ind[m, :k], sb[m, :k] if sb is not None else None) for m, k in enumerate(self.n_slots)]
+        if any(self._levels):                                # (views of the group's level array: the next pull writes it again)
+            return res, list(self.n_slots), [self._lv[m * stride:m * stride + k] if self._levels[m] else None
+                                             for m, k in enumerate(self.n_slots)]
+        return res, list(self.n_slots)
 
     def plan(self, m, n=None):
         """MS_PLAN_DTYPE[n] of member m's last pull (default: all its slots)"""

@@ -1,0 +1,226 @@
+#!/usr/bin/env python3
+"""The cost of the MS-side receive gain control on one GPU: the same pulls on scheduler objects with gain control on and off, HIP-
+event time, int16, the 51-multiframe mix of tools/bench_ms_group.py, all ACTIVE, tracking on.
+  on64 / off64     a group of 64 members, 8 slots (one frame) per member and pull, `frames` pulls in a row; per frame
+  on256 / off256   the same with 256 members
+  on1 / off1       the single object, 8 slots per pull
+  onbig / offbig   the single object, one pull of `slots` slots (set_clock + pull per call)
+  gate             trxhip_ms_level_batch_i16 over one buffer of 60 000 full-scale samples whose sum passes 2^24 within the first
+                   tile -- acquire_gated()'s level, the longest ordered tail; per call
+Every round is a fresh process under its own time limit; inside a round the legs are timed in turns, the order reversed every
+other turn; every timed region follows one untimed call of the same leg.  Median per leg over the rounds, spread = max - min
+over the rounds -> profiles/ms_agc_bench.json.  The first step that fails ends the run.
+
+   python3 tools/bench_ms_agc.py [--rounds 5] [--slots N] [--frames F] [--inner I] [--warmup W] [--reps R] [--timeout S] [--trace LEG] [--out FILE]"""
+import argparse
+import json
+import os
+import re
+import shutil
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+FULL_SCALE = 2047.0
+BASE_FN = 51 * 4321
+FRAME = 8 * 625
+PAIRS = (("on64", "off64"), ("on256", "off256"), ("on1", "off1"), ("onbig", "offbig"))
+SLOT_BYTES = 2500 + 4                  # the level pass reads a slot and writes a float
+
+
+def child(a):
+    """One round: the legs in turns -> one JSON line {leg: median ms per frame (per pull for the big legs, per call for gate)}."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from bench_ms_rx import TSC, multiframe
+    from osmo_trx_amd import TrxHip, trxhip
+    trx = TrxHip(0)
+    base_iq = multiframe(trx, BASE_FN)[0]
+    names = [k for k in [k for pair in PAIRS for k in pair] + ["gate"] if not a.legs or k in a.legs.split(",")]
+    L, st = trx.L, trx._stream()
+    vp = C.c_void_p
+    frames = a.frames
+    assert 1 <= frames <= 51
+    iq = base_iq.repeat(3, 1, 1).contiguous()
+    stride = 9
+    ns1, nc1 = C.c_size_t(), C.c_size_t()
+    legs, checks = {}, []
+
+    def group_pair(n):
+        gs = [trxhip.MsRxSchedulerGroup(trx, n=n, rx_full_scale=FULL_SCALE, tsc=TSC, active_tns=0xFF, tracking=True) for _ in range(2)]
+        for m in range(n):
+            gs[0].set_agc(m, True, 30.0)
+        tabs = []
+        for k in range(frames):
+            ch = np.zeros(n, dtype=trxhip.MS_GROUP_CHUNK_DTYPE)
+            ch["d_in"] = [iq.data_ptr() + ((m % 51) + k) * FRAME * 4 for m in range(n)]
+            ch["n_samples"], ch["first_ts"] = FRAME, k * FRAME
+            tabs.append(ch)
+        ind = torch.zeros((2, n, stride, 32), dtype=torch.uint8, device="cuda:0")
+        bits = torch.zeros((2, n, stride, 148), dtype=torch.int8, device="cuda:0")
+        cnt = (C.c_size_t * n)()
+
+        def leg(i):
+            def run():
+                for m in range(n):
+                    gs[i].set_clock(m, BASE_FN + (m % 51) - 1, 7, -625)
+                for ch in tabs:
+                    trxhip._check(L.trxhip_ms_group_pull_s16(gs[i].h, ch.ctypes.data_as(vp), vp(ind[i].data_ptr()), vp(bits[i].data_ptr()),
+                                                             stride, C.cast(cnt, vp), None, None, st), "group pull")
+            return run
+
+        def check():
+            before = gs[0].agc_state(n - 1)["slots"]
+            ind.zero_()
+            bits.zero_()
+            leg(0)()
+            leg(1)()
+            torch.cuda.synchronize()
+            assert torch.equal(ind[0], ind[1]) and torch.equal(bits[0], bits[1]), "gain control changed what a pull returns"
+            assert gs[0].agc_state(n - 1)["slots"] - before >= 7 * frames and gs[1].agc_state(0)["slots"] == 0
+
+        return leg(0), leg(1), check
+
+    for n, (on, off) in ((64, PAIRS[0]), (256, PAIRS[1])):
+        if on in names or off in names:
+            legs[on], legs[off], check = group_pair(n)
+            legs[on], legs[off] = (legs[on], frames), (legs[off], frames)
+            checks.append(check)
+
+    def single_pair(x, n_samples, out_slots, per_call_clock, tabs_ts):
+        ss = [trxhip.MsRxScheduler(trx, rx_full_scale=FULL_SCALE, tsc=TSC, active_tns=0xFF, tracking=True) for _ in range(2)]
+        ss[0].set_agc(True, 30.0)
+        ind = torch.zeros((2, out_slots, 32), dtype=torch.uint8, device="cuda:0")
+        bits = torch.zeros((2, out_slots, 148), dtype=torch.int8, device="cuda:0")
+
+        def leg(i):
+            args = [(ss[i].h, vp(x.data_ptr() + k * n_samples * 4), n_samples, ts, vp(ind[i].data_ptr()), vp(bits[i].data_ptr()), out_slots,
+                     C.byref(ns1), C.byref(nc1), st) for k, ts in enumerate(tabs_ts)]
+
+            def run():
+                ss[i].set_clock(*per_call_clock)
+                for arg in args:
+                    if L.trxhip_ms_sched_pull_s16(*arg) != 0:
+                        raise RuntimeError("trxhip_ms_sched_pull_s16 failed")
+            return run
+
+        def check():
+            before = ss[0].agc_state()["slots"]
+            leg(0)()
+            leg(1)()
+            torch.cuda.synchronize()
+            assert torch.equal(ind[0], ind[1]) and torch.equal(bits[0], bits[1]), "gain control changed what a pull returns"
+            assert ss[0].agc_state()["slots"] - before >= (n_samples // 625 - 1) * len(tabs_ts) and ss[1].agc_state()["slots"] == 0
+
+        return leg(0), leg(1), check
+
+    if "on1" in names or "off1" in names:
+        r0, r1, check = single_pair(iq, FRAME, stride, (BASE_FN - 1, 7, -625), [k * FRAME for k in range(frames)])
+        legs["on1"], legs["off1"] = (r0, frames), (r1, frames)
+        checks.append(check)
+    if "onbig" in names or "offbig" in names:
+        big = base_iq.repeat((a.slots + 407) // 408, 1, 1)[:a.slots].contiguous()
+        r0, r1, check = single_pair(big, a.slots * 625, a.slots, (BASE_FN - 1, 7, -625), [0])
+        legs["onbig"], legs["offbig"] = (r0, 1), (r1, 1)
+        checks.append(check)
+    if "gate" in names:
+        buf = torch.full((1, 60000, 2), 32767, dtype=torch.int16, device="cuda:0")
+        lv = torch.empty((1,), dtype=torch.float32, device="cuda:0")
+
+        def gate():
+            trxhip._check(L.trxhip_ms_level_batch_i16(trx.h, vp(buf.data_ptr()), 1, 60000, 60000, vp(lv.data_ptr()), st), "level")
+
+        legs["gate"] = (gate, 1)
+    names = [k for k in names if k in legs]
+    times = {k: [] for k in names}
+    for name in names:
+        for _ in range(a.warmup):
+            legs[name][0]()
+    torch.cuda.synchronize()
+    for i in range(a.inner):
+        for name in (names if (a.round + i) % 2 == 0 else names[::-1]):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            legs[name][0]()                                        # untimed: the timed calls follow a call of their own kind
+            ev[0].record()
+            for _ in range(a.reps):
+                legs[name][0]()
+            ev[1].record()
+            torch.cuda.synchronize()
+            times[name].append(ev[0].elapsed_time(ev[1]) / a.reps / legs[name][1])
+    if not a.legs:
+        for check in checks:
+            check()
+    print(json.dumps({k: statistics.median(v) for k, v in times.items()}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--slots", type=int, default=1 << 18)
+    ap.add_argument("--frames", type=int, default=17, help="8-slot pulls in a row per timed call")
+    ap.add_argument("--inner", type=int, default=6, help="turns per leg inside a round (even: both orders equally often)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--timeout", type=int, default=150, help="seconds per round")
+    ap.add_argument("--trace", default="", help="also take a kernel trace of these legs (comma-separated), each in a run of its own")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ms_agc_bench.json"))
+    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
+    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
+    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.round is not None:
+        return child(a)
+    if a.rounds < 5:
+        ap.error("at least five rounds")
+    if a.inner % 2:
+        ap.error("an even number of turns")
+    import measure
+    os.makedirs(a.logs, exist_ok=True)
+    per_leg = {}
+    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--frames", str(a.frames)]
+    for r in range(a.rounds):
+        log = os.path.join(a.logs, "ms_agc_round_%d.log" % (r + 1))
+        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--inner", str(a.inner), "--warmup", str(a.warmup), "--reps",
+                                                 str(a.reps)], log, a.timeout)
+        for k, v in measure.last_json(log).items():
+            per_leg.setdefault(k, []).append(v)
+        print("round %d done" % (r + 1), flush=True)
+    res = {"workload": "ms_agc", "slots": a.slots, "small_pull_slots": 8, "frames_per_call": a.frames, "slot_len": 625, "input": "int16",
+           "tracking": True, "rounds": a.rounds, "inner": a.inner, "reps": a.reps,
+           "unit": "ms per frame of all members (onbig / offbig: per pull; gate: per call)", "legs": {}, "pairs": {}}
+    for name, xs in per_leg.items():
+        med = statistics.median(xs)
+        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs])
+    lg = res["legs"]
+    for on, off in PAIRS:
+        if on in lg and off in lg:
+            res["pairs"][on + "_over_" + off] = dict(ratio=round(lg[on]["median_ms"] / lg[off]["median_ms"], 4),
+                                                     diff_ms=round(lg[on]["median_ms"] - lg[off]["median_ms"], 4),
+                                                     larger_spread_ms=max(lg[on]["spread_ms"], lg[off]["spread_ms"]))
+    if a.trace:
+        from bench_rx_sched import trace_rows
+        d = os.path.join(a.logs, "ms_agc_trace")
+        res["kernel_trace_us"] = {}
+        for leg in a.trace.split(","):
+            shutil.rmtree(d, ignore_errors=True)
+            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "ms_agc",
+                                                 "--"] + me + ["--round", "0", "--inner", "1", "--warmup", "1", "--reps", "1", "--legs", leg],
+                         os.path.join(a.logs, "ms_agc_trace_%s.log" % leg), a.timeout)
+            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(trace_rows(d).items()) if re.match(r"ms_rx|ms_join|ms_level|ms_gain", k)}
+        shutil.rmtree(d, ignore_errors=True)
+        for k, v in res["kernel_trace_us"].get("onbig", {}).items():       # the level pass of the large pull against its traffic
+            if k.startswith("ms_level") and v["avg_us"]:
+                res["level_pass"] = dict(kernel=k, us=v["avg_us"], bytes=a.slots * SLOT_BYTES,
+                                         fraction_of_8TBps=round(a.slots * SLOT_BYTES / 8e12 / (v["avg_us"] * 1e-6), 4))
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
