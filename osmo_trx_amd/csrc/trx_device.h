@@ -545,6 +545,41 @@ __device__ __forceinline__ c32 interp_point(const c32 *cz, int ix512, const floa
 	return interp_taps(cz + (fl - 7), sincv + sinc_base_lo(f), sincv + sinc_base_hi(f));
 }
 
+// The same two on a LUT stored as row pairs (trx_tables.h, trx_sincp_idx: the normal-burst kernel's LDS copy): the weight of
+// row k at column slot s is sincp[trx_sincp_idx(k, s)]; sa / sb are the slots sinc_base_lo(f) / sinc_base_hi(f) (512 for f = 0:
+// column 0 of the next row).  The same products and sums in the same order.
+__device__ __forceinline__ c32 interp_taps_pairs(const c32 *c, const float *sincp, int sa, int sb)
+{
+	typedef const volatile trx_v2f __attribute__((address_space(3))) *lds_ptr;
+	lds_ptr cp = (lds_ptr)c;
+	asm("" : "+v"(cp));
+	c32 p = make_float2(0.0f, 0.0f);
+#pragma unroll
+	for (int u = 0; u < 8; u++) {                    // i = fl-7 .. fl   (k = 7 .. 0)
+		const trx_v2f v = cp[u];
+		const float w = sincp[trx_sincp_idx(7 - u, sa)];
+		p.x += v.x * w;
+		p.y += v.y * w;
+	}
+#pragma unroll
+	for (int u = 0; u < 8; u++) {                    // i = fl+1 .. fl+8 (k = 0 .. 7)
+		const trx_v2f v = cp[8 + u];
+		const float w = sincp[trx_sincp_idx(u, sb)];
+		p.x += v.x * w;
+		p.y += v.y * w;
+	}
+	return p;
+}
+
+template <bool PAIRS>
+__device__ __forceinline__ c32 interp_point_l(const c32 *cz, int ix512, const float *sincv)
+{
+	if (!PAIRS)
+		return interp_point(cz, ix512, sincv);
+	const int fl = ix512 >> 9, f = ix512 & 511;
+	return interp_taps_pairs(cz + (fl - 7), sincv, sinc_base_lo(f), sinc_base_hi(f));
+}
+
 // Lane constants of the speculative bisection (functions of the lane id only): computed once per kernel,
 // they cost 5 VGPRs instead of ~40 VALU instructions per burst.
 struct PeakConst {
@@ -627,6 +662,9 @@ __device__ __forceinline__ int walk_tree(float nv, int inc0, bool &tie)
 // ------------------------------------------------------------------------------------------------
 //   wa4 : optional (4-SPS fused kernel) LDS table of round A's weights, float4 q of lane l at wa4[64 q + l] (the weights of
 //         round A depend on the lane only): four conflict-free 16-byte reads instead of sixteen 4-byte gathers
+//   PAIRS: sincv is stored as row pairs (trx_tables.h, trx_sincp_idx: the normal-burst kernel's LDS copy); such a caller hands
+//         over wa4 (round A's weights are not read from the LUT)
+template <bool PAIRS = false>
 __device__ __forceinline__ void peak_detect_spec(const c32 *cz, int max_idx, const float *sincv, const PeakConst &pc,
 						  int lane, int *toa512_out, c32 *val_out, const float4 *wa4 = nullptr)
 {
@@ -638,7 +676,8 @@ __device__ __forceinline__ void peak_detect_spec(const c32 *cz, int max_idx, con
 		// ix = E + offA with E a multiple of 512: floor and fraction come from the lane constants
 		const c32 *const ca = cz + ((max_idx - 1) + pc.flA - 7);
 		const float nv = wa4 ? norm2(interp_taps_w(ca, wa4[lane], wa4[64 + lane], wa4[128 + lane], wa4[192 + lane]))
-				     : norm2(interp_taps(ca, sincv + pc.loA, sincv + pc.hiA));
+				     : PAIRS ? norm2(interp_taps_pairs(ca, sincv, pc.loA, pc.hiA))
+					     : norm2(interp_taps(ca, sincv + pc.loA, sincv + pc.hiA));
 		// (lanes 62,63 evaluate a harmless extra node)
 		E += walk_tree<5>(nv, 256, tie);
 	}
@@ -647,7 +686,7 @@ __device__ __forceinline__ void peak_detect_spec(const c32 *cz, int max_idx, con
 	if (!tie) {
 		// ---- round B: levels 5..8 (incr = 1/64 .. 1/512) on lanes 0..29, the 16 possible final
 		// positions (earlyIndex + 1) on lanes 32..47
-		const c32 pv = interp_point(cz, E + pc.offB, sincv);
+		const c32 pv = interp_point_l<PAIRS>(cz, E + pc.offB, sincv);
 		const float nv = norm2(pv);
 		const int offB = walk_tree<4>(nv, 8, tie);
 		E += offB;
@@ -658,7 +697,7 @@ __device__ __forceinline__ void peak_detect_spec(const c32 *cz, int max_idx, con
 	}
 	if (tie) {                                        // rare: equal early/late power -> loop left early
 		final_ix = E + 512;
-		val = interp_point(cz, final_ix, sincv);
+		val = interp_point_l<PAIRS>(cz, final_ix, sincv);
 	}
 	*toa512_out = final_ix;
 	*val_out = val;

@@ -45,6 +45,7 @@
 // waves fill what is left: +0.5 % same box (5 rounds, three alternatives within +-0.3 % of it: profiles/r06_ab_runs.txt).
 typedef float v3f __attribute__((ext_vector_type(3)));
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v2i __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) v2f lds_v2f;
 
 // byte address of an LDS object (what the ds_* instructions of the asm blocks take)
@@ -82,14 +83,14 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	const int wave = uni((int)(threadIdx.x >> 6));
 
 	// ---- LDS carve: [tables][per-wave slices][work counter, pool ring]
-	float *const sincv = reinterpret_cast<float *>(smem);           // [4128] swizzled sinc LUT (at LDS offset 0)
+	float *const sincv = reinterpret_cast<float *>(smem);           // [4128] swizzled sinc LUT as row pairs (at LDS offset 0; trx_sincp_idx)
 	float *const wa4f = sincv + TRX_SINCV_LDS;                     // [4][64] float4: round A's interpolation weights by lane
 	const float4 *const wa4 = reinterpret_cast<const float4 *>(wa4f);
 	float *const comp = wa4f + 16 * WAVE;                          // [65][36] composite delay-o-decimate filters (shifted by TRX_FUSED_SH)
 	float *const gdec = comp + NB_COMP_ROWS * 36;                  // [16] decimator taps
 	float *const lhdr = gdec + 16;                                 // [8][8] headers of the eight training sequences
 	int *const pkcl = reinterpret_cast<int *>(lhdr + 8 * 8);       // [5][64] PeakConst fields by lane (the exact re-run of the TOA search)
-	int *const lcn = pkcl + 5 * WAVE;                              // [5][64] lane constants of the hand-placed blocks (below)
+	int *const lcn = pkcl + 5 * WAVE;                              // lane constants of the hand-placed blocks (below): [2][64] pairs, [64]
 	c32 *const lseq = reinterpret_cast<c32 *>(lcn + 5 * WAVE);     // [8][16] training-sequence taps (the multiplying correlation: guard failures)
 	c32 *const wbase = reinterpret_cast<c32 *>(smem + NB_TABLES_BYTES) + (size_t)wave * NB_SLICE;
 	int *const wg_next = reinterpret_cast<int *>(reinterpret_cast<c32 *>(smem + NB_TABLES_BYTES) + (size_t)NB_WPB * NB_SLICE);
@@ -99,8 +100,13 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	c32 *const cz = D + NB_D_LEN + TRX_CZ_PAD;                     // zero-padded correlation
 
 	// ---- one-time staging of the tables; zero this wave's slice (pads stay zero)
-	for (int i = threadIdx.x; i < TRX_SINCV_LDS; i += blockDim.x)
-		sincv[i] = (i < TRX_SINCV_LEN) ? tab->sincv[i] : 0.0f;
+	// (the sinc LUT as pairs of rows -- trx_tables.h, trx_sincp_idx: block DETB reads the weights of two taps as one 8-byte entry.
+	// The blob's index 512 r + s is row r, column slot s: the swizzle leaves the row alone.  Slot 512 of a pair: column 0 of the next row)
+	static_assert(4 * TRX_SINCP_STRIDE <= TRX_SINCV_LDS, "the row pairs fit the LUT's LDS space");
+	for (int i = threadIdx.x; i < TRX_SINCV_LDS; i += blockDim.x) {
+		const int src = trx_sincp_src(i);
+		sincv[i] = (src >= 0) ? tab->sincv[src] : 0.0f;
+	}
 	for (int i = threadIdx.x; i < 16 * WAVE; i += blockDim.x) {
 		const int l = i & (WAVE - 1), u = i >> 6;
 		const PeakConst pcl = peak_const(l);
@@ -126,16 +132,17 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		pkcl[3 * WAVE + threadIdx.x] = pc0.offB;
 		pkcl[4 * WAVE + threadIdx.x] = pc0.ratio_off;
 		// byte offsets relative to &cz[bidx]: the lane's peak-ratio term; round A's first tap (cz + bidx - 1 + flA - 7); round B's offset
-		lcn[0 * WAVE + threadIdx.x] = pc0.ratio_off * 8;
-		lcn[1 * WAVE + threadIdx.x] = (pc0.flA - 8) * 8;
-		lcn[2 * WAVE + threadIdx.x] = pc0.offB;
+		// (two 8-byte entries per lane -- (kr, ka), (kb, kic) -- and ktp by itself: three reads in block AMAX's wait states)
+		lcn[2 * threadIdx.x + 0] = pc0.ratio_off * 8;
+		lcn[2 * threadIdx.x + 1] = (pc0.flA - 8) * 8;
+		lcn[2 * (WAVE + threadIdx.x) + 0] = pc0.offB;
 		// the demodulator's lanes (tools/gen_nb_asm.py, fir_moving: every lane holds twelve samples = three symbols, the sums move
 		// two lanes up): 0..49 samples from symbol 4 + 3 lane on, composite row (50, 51: idle, as 49); 52 + 3 e + t, low-edge symbol
 		// e: t = 0, 1 main part -- samples from symbol e / e + 3, row e of the parked block; t = 2 its taps u < 8 -- samples from
 		// symbol e - 3, row 4 + e
 		const int l = threadIdx.x, e = (l - 52) / 3, t = (l - 52) % 3;
 		const bool sp = l >= 52;
-		lcn[3 * WAVE + l] = 8 * (sp ? (t == 0 ? e : t == 1 ? e + 3 : e - 3) : 4 + 3 * (l < 49 ? l : 49));   // first symbol, bytes
+		lcn[2 * (WAVE + l) + 1] = 8 * (sp ? (t == 0 ? e : t == 1 ? e + 3 : e - 3) : 4 + 3 * (l < 49 ? l : 49));   // first symbol, bytes
 		lcn[4 * WAVE + l] = sp ? (e + (t == 2 ? 4 : 0)) * K4_NTP * 4 : -1;                 // tap row inside the parked block, bytes
 	}
 	for (int i = lane0; i < NB_SLICE; i += WAVE)
@@ -604,14 +611,15 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					// reductions' wait states
 					DIAG_MARK(3);
 					int m_bits, es_bits, bidx;
-					int kr, ka, kb, kic, ktp;                                   // lane constants (lcn[])
-					asm volatile(NB_ASM_AMAX("ds_read_b32 %[kr], %[l4] offset:%c[lc]", "ds_read_b32 %[ka], %[l4] offset:%c[lc]+256",
-								 "ds_read_b32 %[kb], %[l4] offset:%c[lc]+512", "ds_read_b32 %[kic], %[l4] offset:%c[lc]+768",
-								 "ds_read_b32 %[ktp], %[l4] offset:%c[lc]+1024", "s_nop 0", "s_nop 0", "s_nop 0")
+					v2i kra, kbc;                                               // lane constants (lcn[]): (kr, ka), (kb, kic)
+					int ktp;
+					// (8 * lane for the two 8-byte entries is made here, in one of the block's temporaries: no register is kept for it)
+					asm volatile(NB_ASM_AMAX("v_lshlrev_b32_e32 v90, 1, %[l4]", "ds_read_b64 %[kra], v90 offset:%c[lc]",
+								 "ds_read_b64 %[kbc], v90 offset:%c[lc]+512", "ds_read_b32 %[ktp], %[l4] offset:%c[lc]+1024",
+								 "s_nop 0", "s_nop 0", "s_nop 0", "s_nop 0")
 						     "s_sub_u32 %[bidx], %[bidx], %[lag0]\n\t"                 // arg-max lane -> lag (no maximum: -lag0)
 						     "s_waitcnt lgkmcnt(0)"
-						     : [m] "=&s"(m_bits), [es] "=&s"(es_bits), [bidx] "=&s"(bidx), [kr] "=&v"(kr), [ka] "=&v"(ka), [kb] "=&v"(kb),
-						       [kic] "=&v"(kic), [ktp] "=&v"(ktp)
+						     : [m] "=&s"(m_bits), [es] "=&s"(es_bits), [bidx] "=&s"(bidx), [kra] "=&v"(kra), [kbc] "=&v"(kbc), [ktp] "=&v"(ktp)
 						     : [nrm] "v"(v), [ep] "v"(epart), [l4] "v"(a_l4), [lag0] "s"(lag0),
 						       [lc] "n"((TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 64 + 5 * WAVE) * 4)
 						     : NB_ASM_CLOBBERS);
@@ -628,7 +636,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					float km;
 					asm volatile(NB_ASM_DETA
 						     : [st] "=&" NB_ASM_ST(st), [e] "=&s"(e512), [km] "=&v"(km)
-						     : [bidx] "s"(bidx), [len] "s"(len), [czb] "s"(lds_addr(cz)), [kr] "v"(kr), [ka] "v"(ka), [l16] "v"(a_l16),
+						     : [bidx] "s"(bidx), [len] "s"(len), [czb] "s"(lds_addr(cz)), [kr] "v"(kra.x), [ka] "v"(kra.y), [l16] "v"(a_l16),
 						       [gkv] "v"(gkv), [c0] "v"(gc0)
 						     : NB_ASM_CLOBBERS_ST);
 					DIAG_MARK(5);
@@ -636,7 +644,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					if (__builtin_expect(st == 1, 1)) {
 						asm volatile(NB_ASM_DETB
 							     : [st] "=&" NB_ASM_ST(st), [toa] "=&s"(toa512), [xr] "=&s"(xr_bits), [xi] "=&s"(xi_bits)
-							     : [e] "s"(e512), [kb] "v"(kb), [czb] "s"(lds_addr(cz)), [km] "v"(km)
+							     : [e] "s"(e512), [kb] "v"(kbc.x), [czb] "s"(lds_addr(cz)), [km] "v"(km)
 							     : NB_ASM_CLOBBERS_ST);
 						DIAG_MARK(6);
 					}
@@ -654,7 +662,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 							pkc.flA = pkcl[0 * WAVE + lane]; pkc.loA = pkcl[1 * WAVE + lane]; pkc.hiA = pkcl[2 * WAVE + lane];
 							pkc.offB = pkcl[3 * WAVE + lane]; pkc.ratio_off = pkcl[4 * WAVE + lane];
 							c32 xcorr;
-							peak_detect_spec(cz, bidx, sincv, pkc, lane, &toa512, &xcorr, wa4);
+							peak_detect_spec<true>(cz, bidx, sincv, pkc, lane, &toa512, &xcorr, wa4);
 							toa512 = uni(toa512);
 							xr_bits = uni(__float_as_int(xcorr.x));
 							xi_bits = uni(__float_as_int(xcorr.y));
@@ -693,14 +701,15 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 							     : [toa] "s"(toa512), [xr] "s"(xr_bits), [xi] "s"(xi_bits), [t5] "s"(t5), [hdrb] "s"(lds_addr(lhdr) + 32u * (unsigned)tsc),
 							       [e8lo] "s"((unsigned)e8_addr), [e8hi] "s"((unsigned)(e8_addr >> 32)), [l16] "v"(a_l16),
 							       [aw] "v"(a_w), [pb] "s"(lds_addr(P)), [cb] "s"(lds_addr(comp) + 4u * (K4_U0 + TRX_FUSED_SH)), [db] "s"(lds_addr(D)),
-							       [kic] "v"(kic), [ktp] "v"(ktp)
+							       [kic] "v"(kbc.y), [ktp] "v"(ktp)
 							     : NB_ASM_CLOBBERS);
 						DIAG_MARK(10);
 						asm volatile("s_setprio 2");
-						// vectorSlicer: 0.5 * (x + 1), clamped (:546-556); the cold demodulator below writes its own over them
-						o.x = __builtin_amdgcn_fmed3f(fmaf(0.5f, d0, 0.5f), 0.0f, 1.0f);
-						o.y = __builtin_amdgcn_fmed3f(fmaf(0.5f, d1, 0.5f), 0.0f, 1.0f);
-						o.z = __builtin_amdgcn_fmed3f(fmaf(0.5f, d2, 0.5f), 0.0f, 1.0f);
+						// (sliced in the block's output stage -- vectorSlicer: 0.5 * (x + 1), clamped (:546-556); the cold demodulator
+						// below writes its own over them)
+						o.x = d0;
+						o.y = d1;
+						o.z = d2;
 						// the record's inputs are queued in front of the geometry test -- no test of "left" behind it, and none of them is
 						// carried across the rare side's filter in a scalar register; a burst left to the general kernel there gives its
 						// place in the queue back

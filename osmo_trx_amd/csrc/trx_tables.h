@@ -116,6 +116,34 @@ __host__ __device__
 #endif
 int trx_sincv_swz(int q) { return q ^ ((q >> 4) & 31); }
 
+// The normal-burst kernel's LDS copy of sincv[] (trx_kernel_nb.hip; the blob and every other kernel keep the layout above):
+// rows 2j and 2j + 1 of the LUT interleaved, so that the weights of two adjacent taps of interpolatePoint() are one 8-byte
+// entry.  Row r = q >> 9; column slot s = trx_sincv_swz(q) & 511 (the swizzle leaves the row alone), or s = 512 for "column 0
+// of row r + 1" -- what the taps above the peak address when the fraction is 0 (q = 512 (k + 1); row 8 is the zero tail): a
+// pair of rows has 513 slots, and the ascending taps need no special case.  Banks: an 8-byte slot s of a 32-lane half takes
+// banks 2 s and 2 s + 1 mod 64, so the gather is conflict-free exactly where the 4-byte one on sincv[] was.
+#define TRX_SINCP_STRIDE 1026   /* floats per pair of rows; 4 pairs = 4104 <= TRX_SINCV_LEN + 32 */
+static inline
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+int trx_sincp_idx(int row, int slot) { return (row >> 1) * TRX_SINCP_STRIDE + 2 * slot + (row & 1); }
+// what float i of that copy holds: an index into the blob's sincv[], or -1 for a zero (row 8, and the space behind the pairs)
+static inline
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+int trx_sincp_src(int i)
+{
+	const int pair = i / TRX_SINCP_STRIDE, rem = i % TRX_SINCP_STRIDE;
+	const int row = 2 * pair + (rem & 1), slot = rem >> 1;
+	if (pair >= 4)
+		return -1;
+	if (slot < 512)
+		return 512 * row + slot;
+	return (row + 1 < 8) ? 512 * (row + 1) : -1;
+}
+
 // Host-side generation (no GPU needed).  Returns 0 on success.
 int trx_tables_generate(trx_tables *out);
 

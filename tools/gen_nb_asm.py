@@ -804,8 +804,18 @@ def block_deta(wa4_off):
 #   out: status 1 / 3 in the fixed register NB_ASM_ST; %[toa] SGPR final position * 512; %[xr] %[xi] SGPR interpolated value
 #        (status 3: undefined).  The careful walk is in NB_ASM_COLD (see DETA).
 # sinc LUT index of a fraction f: taps i <= fl use q = 512 k + f, taps i > fl use q = 512 k + (512 - f), XOR-swizzled
-# (trx_tables.h: q ^ ((q >> 4) & 31); swz(512) = 512, so f = 0 needs no special case).  sincv[] sits at LDS offset 0.
+# (trx_tables.h: q ^ ((q >> 4) & 31), which leaves the row 512 k alone; swz(512) = 512).  This kernel's LDS copy of the LUT
+# (offset 0) holds rows 2j and 2j + 1 interleaved -- trx_tables.h, trx_sincp_idx: entry (row r, column slot s) at float
+# (r >> 1) * 1026 + 2 s + (r & 1) -- so that the weights of taps k and k + 1 are ONE 8-byte read (a 4-byte read costs the LDS
+# pipe what an 8-byte one costs).  The descending side (rows 7 - u) finds its pair in swapped order: the op_sel of the FMA
+# picks the half.  The ascending side's column slot 512 (f = 0: q = 512 (u + 1), column 0 of the NEXT row) is a pair of its own,
+# rows 2j + 1 and 2j + 2 at column 0, behind the 512 slots of pair j (the zero tail is its last entry): no special case here.
+# Banks: an 8-byte slot s of a 32-lane half occupies banks 2 s, 2 s + 1 mod 64 -- conflict-free exactly where the 4-byte gather
+# was (s mod 32 distinct), so the swizzle stays (tools/lds_stride_conflicts.py, sinc_pairs()).
 # ------------------------------------------------------------------------------------------------------------------
+SINCP_PAIR_BYTES = 1026 * 4     # TRX_SINCP_STRIDE floats (trx_tables.h): one pair of rows, 513 column slots of 8 bytes
+
+
 def block_detb():
     b = Block("DETB", ("e", "czb", "toa", "xr", "xi"))
     cold = Block("DETB_COLD")
@@ -826,26 +836,29 @@ def block_detb():
     b("v_sub_u32_e32 v72, 0x200, v70")
     b("v_xor_b32_e32 v71, v71, v70")
     b("v_bfe_u32 v73, v72, 4, 5")
-    b("v_lshlrev_b32_e32 v71, 2, v71")                             # taps fl-7 .. fl: sincv[swz(f) + 512 (7 - u)]
+    b("v_lshlrev_b32_e32 v71, 3, v71")                             # taps fl-7 .. fl: rows 7 - u, column slot swz(f) of the row pairs
     b("v_xor_b32_e32 v72, v73, v72")
-    b("v_lshlrev_b32_e32 v72, 2, v72")                             # taps fl+1 .. fl+8: sincv[swz(512 - f) + 512 u]
+    b("v_lshlrev_b32_e32 v72, 3, v72")                             # taps fl+1 .. fl+8: rows u, column slot swz(512 - f)
     for u in range(8):
         b(f"ds_read_b64 {X(u)}, v69 offset:{8 * u}")
-        b(f"ds_read_b32 {vreg(W(u))}, v71 offset:{2048 * (7 - u)}")
+        if not (u & 1):
+            # rows 6 - u, 7 - u are ONE 8-byte entry of pair 3 - u / 2: the weight of tap u + 1 in the low register, of tap u in the high one
+            b(f"ds_read_b64 {vreg(W(u), 2)}, v71 offset:{SINCP_PAIR_BYTES * (3 - (u >> 1))}")
 
-    def fma2(xs, ws, u):
-        b(f"v_pk_fma_f32 v[64:65], {xs(u)}, {vreg(ws(u), 2)}, v[64:65] op_sel:[0,0,0] op_sel_hi:[1,0,1]")
-        b(f"v_pk_fma_f32 v[66:67], {xs(u + 1)}, {vreg(ws(u), 2)}, v[66:67] op_sel:[0,1,0] op_sel_hi:[1,1,1]")
-    # software pipeline: 12..16 loads in flight; each step consumes two taps of the first half and issues two of the second
+    def fma2(xs, ws, u, swapped):
+        lo, hi = "op_sel:[0,0,0] op_sel_hi:[1,0,1]", "op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+        b(f"v_pk_fma_f32 v[64:65], {xs(u)}, {vreg(ws(u), 2)}, v[64:65] {hi if swapped else lo}")
+        b(f"v_pk_fma_f32 v[66:67], {xs(u + 1)}, {vreg(ws(u), 2)}, v[66:67] {lo if swapped else hi}")
+    # software pipeline: 12 loads in flight; each step consumes two taps of the first half and issues two of the second
     for k in range(4):
-        b("s_waitcnt lgkmcnt(12)")
-        fma2(X, W, 2 * k)
-        for u in (2 * k, 2 * k + 1):
-            b(f"ds_read_b64 {Y(u)}, v69 offset:{8 * (8 + u)}")
-            b(f"ds_read_b32 {vreg(V(u))}, v72 offset:{2048 * u}")
+        b("s_waitcnt lgkmcnt(9)")
+        fma2(X, W, 2 * k, True)
+        b(f"ds_read_b64 {Y(2 * k)}, v69 offset:{8 * (8 + 2 * k)}")
+        b(f"ds_read_b64 {vreg(V(2 * k), 2)}, v72 offset:{SINCP_PAIR_BYTES * k}")      # rows 2k, 2k + 1: taps 2k, 2k + 1 in order
+        b(f"ds_read_b64 {Y(2 * k + 1)}, v69 offset:{8 * (8 + 2 * k + 1)}")
     for k in range(4):
-        b(f"s_waitcnt lgkmcnt({12 - 4 * k})")
-        fma2(Y, V, 2 * k)
+        b(f"s_waitcnt lgkmcnt({9 - 3 * k})")
+        fma2(Y, V, 2 * k, False)
     b("s_mov_b64 exec, -1")
     b("v_pk_add_f32 v[74:75], v[64:65], v[66:67]")                 # interpolated value at this lane's position
     b("s_add_u32 s92, %[e], 497")
@@ -893,6 +906,9 @@ def block_detb():
 #        VGPR l16 (16 * lane), aw (slice base + 8 * lane: D[lane] is offset AW_D of it); SGPR pairs modd = 0xaaaa.., m23 = 0xcccc..
 #   out: SGPR ok (0: TOA outside the straight-line geometry -- left through NB_ASM_COLD, S done), ssum (S); VGPR d0 d1 d2 (block DEMOD)
 # ------------------------------------------------------------------------------------------------------------------
+FIDX = "s99"                     # TAIL: the burst's delay-filter row, from the row fetch at the head to the composite row's address
+
+
 def block_tail():
     b = Block("TAIL", ("toa", "xr", "xi", "t5", "hdrb", "e8lo", "e8hi", "ok", "ssum", "pb", "cb", "db"))
     cold = Block("TAIL_COLD")
@@ -902,10 +918,10 @@ def block_tail():
     b("s_add_u32 s87, s88, 5120")                                  # nk = -(toa512 - t5 - 10 * 512)
     b("s_mov_b32 %[ok], 0")
     b("s_and_b32 s91, s87, 127")
-    b("s_lshr_b32 s92, s91, 1")
+    b(f"s_lshr_b32 {FIDX}, s91, 1")
     b("s_cmp_ge_u32 s91, 2")
-    b("s_cselect_b32 s92, s92, 64")                                # delay filter row (64 = none)
-    b("s_mul_i32 s93, s92, 768")
+    b(f"s_cselect_b32 {FIDX}, {FIDX}, 64")                           # delay filter row (64 = none): kept for the composite row (DEMOD)
+    b(f"s_mul_i32 s93, {FIDX}, 768")
     b("s_add_u32 s94, %[e8lo], s93")
     b("s_addc_u32 s95, %[e8hi], 0")
     b("s_abs_i32 s96, %[toa]")                                     # roundf(toa): half away from zero on k / 512
@@ -964,7 +980,7 @@ def block_tail():
 #   in : SGPR nk, pb (LDS byte address of P[0] of this wave), cb (LDS byte address of comp + 32: tap U0 of row 0), db (LDS
 #        byte address of D); VGPR rows (4), vp, l16, kic (lane constant: 8 * first symbol of the lane's twelve samples), ktp
 #        (lane constant: byte offset of the lane's tap row inside D, -1 for the lanes on the composite row)
-#   out: VGPR d0 d1 d2: real((-j)^i z / amp) of the three symbols that END in the lane (the slicer's input)
+#   out: VGPR d0 d1 d2: the sliced soft bits of the three symbols that END in the lane: real((-j)^i z / amp) through vectorSlicer
 # ------------------------------------------------------------------------------------------------------------------
 def block_demod(b):
     # the straight-line geometry: shift w = nk >> 7 in -36 .. 0 (0 <= TOA <= 9 symbols); other bursts leave with ok = 0 -- 1 / amp
@@ -978,42 +994,37 @@ def block_demod(b):
     b("v_pk_mul_f32 v[66:67], v[66:67], v[66:67]")
     b("s_ashr_i32 s88, s87, 7")                                    # w
     b("v_add_f32_e32 v81, v67, v66")                               # |sample|^2
-    b("s_and_b32 s89, s87, 127")
-    b("s_lshr_b32 s90, s89, 1")
-    b(f"v_add_f32_dpp v81, v81, v81 quad_perm:[1,0,3,2] {D_ALL}")
-    b("s_cmp_ge_u32 s89, 2")
-    b("s_cselect_b32 s90, s90, 64")                                # fidx
-    b(f"v_add_f32_dpp v81, v81, v81 quad_perm:[2,3,0,1] {D_ALL}")
     b("s_sub_u32 s91, -18, s88")                                   # c = -24 - w + U0: tap U0 of symbol i reads sample 4 i + c
     b("s_and_b32 s92, s91, 3")                                     # ph0
-    b(f"v_add_f32_dpp v81, v81, v81 row_half_mirror {D_ALL}")
+    b(f"v_add_f32_dpp v81, v81, v81 quad_perm:[1,0,3,2] {D_ALL}")
     b("s_ashr_i32 s93, s91, 2")
     b("s_mul_i32 s94, s92, 180")
-    b(f"v_add_f32_dpp v81, v81, v81 row_mirror {D_ALL}")
+    b(f"v_add_f32_dpp v81, v81, v81 quad_perm:[2,3,0,1] {D_ALL}")
     b("s_add_u32 s94, s94, s93")
     b("s_lshl3_add_u32 s94, s94, %[pb]")                           # &P[ph0][m = c >> 2] - 12 entries
-    b("v_mul_f32_e32 v81, 0x3d800000, v81")                        # S = sum / 16 (row 0)
-    b("s_mul_i32 s95, s90, 144")
+    b(f"v_add_f32_dpp v81, v81, v81 row_half_mirror {D_ALL}")
+    b(f"s_mul_i32 s95, {FIDX}, 144")                                 # (the filter's row: made once, at the block's head)
     b("s_add_u32 s95, s95, %[cb]")                                 # composite row of the burst's delay filter, from tap U0
+    b(f"v_add_f32_dpp v81, v81, v81 row_mirror {D_ALL}")
+    b("v_mul_f32_e32 v81, 0x3d800000, v81")                        # S = sum / 16 (row 0)
+    b("s_sub_u32 s96, 0, s88")
     b("v_readlane_b32 %[ssum], v81, 0")
     b("s_mov_b64 exec, -1")
-    b("s_sub_u32 s96, 0, s88")
     b("s_cmp_gt_u32 s96, 36")
     b("s_cbranch_scc1 .Lnbc_tl_wait")
     b("s_mov_b32 %[ok], 1")
     b(f"v_add_u32_e32 {vreg(P[0])}, s94, %[kic]")
     for k in range(1, 4):
-        # p[k] = p[0] + (k * PH_A + ((ph0 + k) >> 2) * (1 - 4 * PH_A)) entries
-        b(f"s_add_u32 s96, s92, {k}")
-        b("s_lshr_b32 s96, s96, 2")
-        b(f"s_mul_i32 s96, s96, {(1 - 4 * PH_A) * 8}")
-        b(f"s_add_u32 s96, s96, {k * PH_A * 8}")
+        # p[k] = p[0] + (k * PH_A + ((ph0 + k) >> 2) * (1 - 4 * PH_A)) entries: the carry (ph0 + k >= 4) is one compare, and the
+        # k * PH_A entries are in the offset field of the reads
+        b(f"s_cmp_gt_u32 s92, {3 - k}")
+        b(f"s_cselect_b32 s96, {(1 - 4 * PH_A) * 8}, 0")
         b(f"v_add_u32_e32 {vreg(P[k])}, s96, {vreg(P[0])}")
     PH0 = 96                                                       # byte offset of PH_M0 entries
     # (all 64 lanes run the filter: an accumulator passes through every lane below the one it ends in)
     # the lane's twelve samples do not depend on the tap rows: requested in front of the wait for those (L2 latency)
     for r in range(12):
-        b(f"ds_read_b64 {X(r)}, {vreg(P[r & 3])} offset:{PH0 + 8 * (r >> 2)}")
+        b(f"ds_read_b64 {X(r)}, {vreg(P[r & 3])} offset:{PH0 + 8 * (r >> 2) + (r & 3) * PH_A * 8}")
     b("v_add_u32_e32 v116, %[db], %[l16]")
     b("v_cmp_lt_i32_e32 vcc, -1, %[ktp]")
     b("v_add_u32_e32 v117, %[db], %[ktp]")
@@ -1037,6 +1048,9 @@ def block_demod(b):
     b(f"v_fmac_f32_dpp %[d1], v119, v67 quad_perm:[2,1,0,3] {D_ALL}")
     b(f"v_fmac_f32_dpp %[d2], v119, v69 quad_perm:[3,2,1,0] {D_ALL}")
     b(f"v_fmac_f32_dpp %[d0], v119, v65 quad_perm:[1,0,3,2] {D_ALL}")
+    # vectorSlicer (:546-556): 0.5 * (x + 1) clamped to [0, 1] -- the clamp is the output modifier of the FMA that forms the value
+    for d in ("d1", "d2", "d0"):
+        b(f"v_fma_f32 %[{d}], %[{d}], 0.5, 0.5 clamp")
 
 
 # ------------------------------------------------------------------------------------------------------------------
