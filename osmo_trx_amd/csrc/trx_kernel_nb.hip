@@ -26,7 +26,8 @@
 #define NB_CZ_LEN   (TRX_CZ_PAD + TRX_CORR_NARROW + TRX_CZ_PAD)
 #define NB_SLICE    (K4_XS + NB_D_LEN + NB_CZ_LEN)                /* complex samples per wave */
 #define NB_COMP_ROWS (TRX_DELAY_FILTS + 1)
-#define NB_TABLES_FLOATS (TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 8 * 8 + 5 * WAVE + 5 * WAVE + 2 * 8 * 16)
+#define NB_AMP_FLOATS (8 * 8)                                      /* [8 TSC][A by lane & 3, B by lane & 3]: trx_tables.h, trx_amp_lane_coef */
+#define NB_TABLES_FLOATS (TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36 + 16 + 8 * 8 + 5 * WAVE + 5 * WAVE + 2 * 8 * 16 + NB_AMP_FLOATS)
 #define NB_TABLES_BYTES (NB_TABLES_FLOATS * 4)
 #define NB_WPB 16
 #define NB_POOL_RING 64
@@ -74,7 +75,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	static_assert(NB_LDS_BYTES <= 160 * 1024, "LDS");
 	static_assert(NB_ASM_GDEC_OFF == (TRX_SINCV_LDS + 16 * WAVE + NB_COMP_ROWS * 36) * 4, "tools/gen_nb_asm.py: LDS offset of the decimator taps");
 	static_assert(NB_ASM_DEC_MAX_NACT == 15 + NB_ASM_CORR_MAX_LEN, "tools/gen_nb_asm.py: DEC and CORR change form at the same window (one test)");
-	static_assert(NB_ASM_LSEQ_OFF == (NB_TABLES_FLOATS - 2 * 8 * 16) * 4, "tools/gen_nb_asm.py: LDS offset of the training-sequence taps");
+	static_assert(NB_ASM_LSEQ_OFF == (NB_TABLES_FLOATS - NB_AMP_FLOATS - 2 * 8 * 16) * 4, "tools/gen_nb_asm.py: LDS offset of the training-sequence taps");
 	static_assert(NB_ASM_AW_PD == (PH_M0 + 52) * 8 && NB_ASM_AW_D == K4_XS * 8 && NB_ASM_AW_CZ == (K4_XS + NB_D_LEN + TRX_CZ_PAD) * 8,
 		      "tools/gen_nb_asm.py: offsets of P, D[] and cz[] inside a wave's slice");
 	constexpr int NLD = 10;
@@ -92,6 +93,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	int *const pkcl = reinterpret_cast<int *>(lhdr + 8 * 8);       // [5][64] PeakConst fields by lane (the exact re-run of the TOA search)
 	int *const lcn = pkcl + 5 * WAVE;                              // lane constants of the hand-placed blocks (below): [2][64] pairs, [64]
 	c32 *const lseq = reinterpret_cast<c32 *>(lcn + 5 * WAVE);     // [8][16] training-sequence taps (the multiplying correlation: guard failures)
+	float *const lamp = reinterpret_cast<float *>(lseq + 8 * 16);  // [8][8] 1 / gain of the eight sequences as block TAIL's lanes take it: a row of 32 bytes
+	                                                               // per sequence, (A, B) of lane & 3 sixteen bytes apart (trx_tables.h, trx_amp_lane_coef)
 	c32 *const wbase = reinterpret_cast<c32 *>(smem + NB_TABLES_BYTES) + (size_t)wave * NB_SLICE;
 	int *const wg_next = reinterpret_cast<int *>(reinterpret_cast<c32 *>(smem + NB_TABLES_BYTES) + (size_t)NB_WPB * NB_SLICE);
 	int *const pool_g = wg_next + 4;
@@ -124,6 +127,10 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						tab->seq[TRX_SEQ_TSC0 + (threadIdx.x >> 4)].taps[threadIdx.x & 15].im);
 	if (threadIdx.x < 64)
 		lhdr[threadIdx.x] = reinterpret_cast<const float *>(&tab->seq[TRX_SEQ_TSC0 + (threadIdx.x >> 3)].gain)[threadIdx.x & 7];
+	if (threadIdx.x < NB_AMP_FLOATS) {
+		const trx_c32 gi = tab->seq[TRX_SEQ_TSC0 + (threadIdx.x >> 3)].gain_inv;
+		lamp[threadIdx.x] = trx_amp_lane_coef(gi.re, gi.im, (int)(threadIdx.x & 7));
+	}
 	if (threadIdx.x < WAVE) {
 		const PeakConst pc0 = peak_const(threadIdx.x);
 		pkcl[0 * WAVE + threadIdx.x] = pc0.flA;
@@ -318,7 +325,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 			const float rssi = rssi_db(full_scale, energy);
 			const float p2 = xi * xi + xr * xr;
 			const float C = p2 * h[7];                              // |peak|^2 / ci_den (:1633), table: RN(1 / ci_den)
-			const float S = __int_as_float(q_s);
+			const float S = __int_as_float(q_s) * 0.0625f;          // computeCI's sum / 16: block TAIL parks the raw sum (a power of two: exact here as there)
 			const float ci = 3.0103f * __log2f(C * __builtin_amdgcn_rcpf(S - C));   // (:1637)
 			// (stores the compiler does not see, like every other store of the loop: with its own stores outstanding across the
 			// loop's back edge it waits for vmcnt(0) -- the soft bits just stored -- in front of the next prefetch; measured: -3 %)
@@ -636,7 +643,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 					float km;
 					asm volatile(NB_ASM_DETA
 						     : [st] "=&" NB_ASM_ST(st), [e] "=&s"(e512), [km] "=&v"(km)
-						     : [bidx] "s"(bidx), [len] "s"(len), [czb] "s"(lds_addr(cz)), [kr] "v"(kra.x), [ka] "v"(kra.y), [l16] "v"(a_l16),
+						     : [bidx] "s"(bidx), [len] "s"(len), [czb] "s"(lds_addr(cz)), [m] "s"(m_bits), [kr] "v"(kra.x), [ka] "v"(kra.y), [l16] "v"(a_l16),
 						       [gkv] "v"(gkv), [c0] "v"(gc0)
 						     : NB_ASM_CLOBBERS_ST);
 					DIAG_MARK(5);
@@ -698,8 +705,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 						asm volatile("s_setprio 0");
 						asm volatile(NB_ASM_TAIL
 							     : [ok] "=&s"(ok), [ssum] "=&s"(s_bits), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2)
-							     : [toa] "s"(toa512), [xr] "s"(xr_bits), [xi] "s"(xi_bits), [t5] "s"(t5), [hdrb] "s"(lds_addr(lhdr) + 32u * (unsigned)tsc),
-							       [e8lo] "s"((unsigned)e8_addr), [e8hi] "s"((unsigned)(e8_addr >> 32)), [l16] "v"(a_l16),
+							     : [toa] "s"(toa512), [xr] "s"(xr_bits), [xi] "s"(xi_bits), [t5] "s"(t5), [ampb] "s"(lds_addr(lamp) + 32u * (unsigned)tsc),
+							       [e8lo] "s"((unsigned)e8_addr), [e8hi] "s"((unsigned)(e8_addr >> 32)), [l16] "v"(a_l16), [l4] "v"(a_l4),
 							       [aw] "v"(a_w), [pb] "s"(lds_addr(P)), [cb] "s"(lds_addr(comp) + 4u * (K4_U0 + TRX_FUSED_SH)), [db] "s"(lds_addr(D)),
 							       [kic] "v"(kbc.y), [ktp] "v"(ktp)
 							     : NB_ASM_CLOBBERS);
@@ -722,7 +729,8 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 							const float *const h = lhdr + 8 * tsc;
 							const float xr = __int_as_float(xr_bits), xi = __int_as_float(xi_bits);
 							const float a0 = xr * h[2], a1 = xr * h[3], a2 = xi * h[3], a3 = xi * h[2];
-							const c32 ampv = make_float2(unif(a0 - a2), unif(a1 + a3));     // amp = peak / gain, as block TAIL has it
+							// amp = peak / gain (Complex.h:74), whole: block TAIL forms per lane only the component its multiplier needs
+							const c32 ampv = make_float2(unif(a0 - a2), unif(a1 + a3));
 							if (!demod_general(t5 + 10 * 512 - toa512, ampv, lane)) {
 								q_n--;
 								mark_left(b);

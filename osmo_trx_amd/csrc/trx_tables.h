@@ -144,6 +144,26 @@ int trx_sincp_src(int i)
 	return (row + 1 < 8) ? 512 * (row + 1) : -1;
 }
 
+// The normal-burst kernel's LDS copy of a training sequence's 1 / gain (trx_kernel_nb.hip; block TAIL of tools/gen_nb_asm.py):
+// lane l of the output stage multiplies by VP[l & 3] = (sx, sy, -sx, -sy), (sx, sy) = 1 / amp, amp = peak * (1 / gain)
+// (sigProcLib.cpp:1701; Complex.h:74-75).  With the pair (A, B) of its variant v = l & 3 a lane forms its own component
+// fl(fl(xr A) + fl(xi B)) = +amp.re, -amp.im, -amp.re, +amp.im -- the bits of fl(xr g0) - fl(xi g1) and fl(xr g1) + fl(xi g0),
+// negated where VP is (negation is exact; a - b is a + (-b); a component that cancels to an exact zero is +0 in every variant,
+// which no soft bit sees: tools/gen_nb_asm.py, amp_lane).  Float k of a sequence's row of eight: k < 4 is A of variant k,
+// k >= 4 is B of variant k - 4; (A, B) = (g0, -g1), (-g1, -g0), (-g0, g1), (g1, g0) for (g0, g1) = 1 / gain.
+static inline
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+float trx_amp_lane_coef(float g0, float g1, int k)
+{
+	const int v = k & 3;
+	const bool first = ((v & 1) == 0) != (k >= 4);                  // g0: A of the even variants, B of the odd ones
+	const float g = first ? g0 : g1;
+	const bool neg = (k < 4) ? (v == 1 || v == 2) : (v == 0 || v == 1);
+	return neg ? -g : g;
+}
+
 // Host-side generation (no GPU needed).  Returns 0 on success.
 int trx_tables_generate(trx_tables *out);
 

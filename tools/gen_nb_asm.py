@@ -577,6 +577,7 @@ def check_paths(b):
             continue                                                # (a backward branch: the join re-enters checked code)
         v = Block(f"{b.name}[{t.strip()}]", [n[2:-1] for n in b.sgpr_ops])
         v.ins = lines[:i] + lines[j:]
+        v.exec_ok = getattr(b, "exec_ok", ())
         for e in v.check():
             if e.split(": ", 1)[1] not in [x.split(": ", 1)[1] for x in errs]:
                 errs.append(e)
@@ -635,6 +636,24 @@ KAPPA = 6e-6                     # TRX_FAST_KAPPA (trx_device.h): certified-comp
 D_ALL = "row_mask:0xf bank_mask:0xf"
 
 
+def chain_term(b, acc, x, hp, half, first):
+    """One term of a product-sum chain acc += x * h, h = the low (half 0) or high (half 1) float of the pair hp, on both
+    components of x.  The chain's FIRST term is the product itself (v_pk_mul_f32), not an FMA onto an accumulator zeroed for it:
+    fma(x, h, +0) and fl(x h) round the same exact product the same way and differ only where that product is an exact zero --
+    +0 + -0 = +0, while the product keeps -0.  What that does to a chain: a sum in round-to-nearest is -0 only if both addends
+    are -0, so a chain is -0 at some point only if EVERY product up to there is -0; behind the first product that is +0 or not a
+    zero the accumulator is what it was when the chain started at +0 (s + -0 = s for every s but -0, and fma(x, h, -0) =
+    fl(x h) for a non-zero product).  So the one difference a chain can show is an END at -0 in place of +0, when all of its
+    products are -0 -- an x that is +0 (no sample and no correlation value of this kernel is ever -0: converted int16, and sums
+    that start at +0) under weights that are all negative.  Where each chain's end goes, and why the sign of that zero reaches
+    no output, is said at the chain: DETA, DETB, fir_moving."""
+    sel = ("op_sel:[0,1{z}] op_sel_hi:[1,1{o}]" if half else "op_sel:[0,0{z}] op_sel_hi:[1,0{o}]")
+    if first:
+        b(f"v_pk_mul_f32 {acc}, {x}, {hp} " + sel.format(z="", o=""))
+    else:
+        b(f"v_pk_fma_f32 {acc}, {x}, {hp}, {acc} " + sel.format(z=",0", o=",1"))
+
+
 def fast_walk(b, c, p, pos, levels, w="b64"):
     """three scalar instructions per level of the bisection tree: bit position of node (L, p), its "early < late" bit, p = 2p + bit"""
     b(f"s_mov_b32 {p}, 0")
@@ -659,7 +678,7 @@ def careful_walk(b, c, cd, p, pos, levels, unsure_label, w="b64"):
 # block DETA: detectBurst() behind fastPeakDetect (sigProcLib.cpp:1683-1695): edge gate, computePeakRatio gate (:1541-1571)
 # on an estimate with a proven margin, round A of peakDetect()'s bisection (levels 0..4, trx_device.h peak_detect_fast) and
 # its certified tree walk.
-#   in : %[bidx] %[len] %[czb] SGPR (czb = LDS byte address of cz[0]); %[kr] %[ka] VGPR lane constants (byte offsets of the
+#   in : %[bidx] %[len] %[czb] SGPR (czb = LDS byte address of cz[0]); %[m] SGPR |corr[bidx]|^2 (block AMAX's maximum); %[kr] %[ka] VGPR lane constants (byte offsets of the
 #        lane's peak-ratio term and of round A's first tap, relative to &cz[bidx]); %[l16] VGPR 16 * lane; %[gkv] VGPR lane n =
 #        thresh^2 / n (n = 5..8); %[c0] VGPR thresh^2 * 1.0001e-5
 #   out: status in the FIXED register NB_ASM_ST (the kernel binds its operand to it: "={s98}"), 0 miss / 1 found / 2 gate too
@@ -674,7 +693,7 @@ def careful_walk(b, c, cd, p, pos, levels, unsure_label, w="b64"):
 # a certain pass; in between (one burst in ~5e4) the burst is left to the general kernel, which rounds as the reference does.
 # ------------------------------------------------------------------------------------------------------------------
 def block_deta(wa4_off):
-    b = Block("DETA", ("bidx", "len", "czb", "e"))
+    b = Block("DETA", ("bidx", "len", "czb", "e", "m"))
     cold = Block("DETA_COLD")
     X = lambda k: vreg(88 + 2 * k, 2)            # round A samples 0..7
     Y = lambda k: vreg(112 + 2 * k, 2)           # samples 8..15
@@ -687,11 +706,9 @@ def block_deta(wa4_off):
     b("s_cbranch_scc1 .Lnb_da_end")
     b("s_lshl3_add_u32 s89, %[bidx], %[czb]")                      # &cz[bidx]
     b("s_add_u32 s90, %[len], -1")
-    b("v_mov_b32_e32 v64, s89")
     b("v_add_u32_e32 v65, s89, %[kr]")
     b("s_lshl3_add_u32 s90, s90, %[czb]")                          # &cz[len - 1]
     b("v_add_u32_e32 v66, s89, %[ka]")
-    b("ds_read_b64 v[68:69], v64")                                 # corr[bidx]
     b("v_mov_b32_e32 v67, s90")
     b("v_mov_b64_e32 v[72:73], 0")
     # (the chip runs at its power limit: what only a few lanes need runs on those lanes -- the eight terms of the gate on lanes 0..7)
@@ -704,8 +721,11 @@ def block_deta(wa4_off):
     b(f"ds_read_b128 v[80:83], %[l16] offset:{wa4_off + 1024}")
     for u in range(8):
         b(f"ds_read_b64 {X(u)}, v66 offset:{8 * u}")
-    b("v_mov_b64_e32 v[84:85], 0")                                 # p0, p1 of the two-chain sums
-    b("v_mov_b64_e32 v[86:87], 0")
+    # m = |corr[bidx]|^2 is block AMAX's wave maximum, bit for bit: CORR's tail forms |corr|^2 of the lane that holds lag bidx as
+    # v_pk_mul_f32 / v_add_f32 (im^2 + re^2) on the value it stores to cz[bidx] -- in the moving, the wide and the multiplying
+    # form alike -- and the maximum IS that lane's value (v_cmp_eq found it): no read of cz[bidx], no second square.  It goes
+    # into the fixed register the cold gate exit reads.
+    b("v_mov_b32_e32 v74, %[m]")
     # number of in-range terms (:1555-1562) -> thresh^2 / num: scalar instructions, placed in the wait states of the vector ones
     # (thresh^2 / num, num = 5..8: lane num of %[gkv], made in front of the burst loop -- one v_readlane in place of three
     # compare / select pairs, and no scalar register is held for the four constants across the loop)
@@ -713,11 +733,9 @@ def block_deta(wa4_off):
           "s_min_u32 s92, s92, 4", "s_add_u32 s91, s91, s92", "v_readlane_b32 s92, %[gkv], s91"]
     for t in sc[:3]:
         b(t)
-    b("s_waitcnt lgkmcnt(11)")
-    b("v_pk_mul_f32 v[68:69], v[68:69], v[68:69]")
-    b(sc[3])
-    b("v_add_f32_e32 v74, v69, v68")                               # m = |corr[bidx]|^2
     b(f"v_mul_f32_e32 %[km], {fhex(KAPPA)}, v74")
+    b(sc[3])
+    b("s_waitcnt lgkmcnt(11)")
     # (the chip runs at its power limit: what only a few lanes need runs on those lanes -- the eight terms of the gate on lanes 0..7)
     b("s_bfm_b64 exec, 8, 0")
     b("v_pk_mul_f32 v[70:71], v[70:71], v[70:71]")
@@ -744,15 +762,17 @@ def block_deta(wa4_off):
         b(f"ds_read_b64 {Y(u)}, v66 offset:{8 * (8 + u)}")
     b("s_waitcnt lgkmcnt(10)")
 
-    def fmas(xs, qa, qb):
+    # (p0, p1 of the two-chain sums START as the product of their first tap -- chain_term, below; a chain that ends at -0
+    # where it ended at +0 vanishes in |interp|^2)
+    def fmas(xs, qa, qb, first):
         for u in range(0, 8, 2):
             q = qb if (u & 4) else qa
             hp = vreg(q + (2 if (u & 2) else 0), 2)
-            b(f"v_pk_fma_f32 v[84:85], {xs(u)}, {hp}, v[84:85] op_sel:[0,0,0] op_sel_hi:[1,0,1]")
-            b(f"v_pk_fma_f32 v[86:87], {xs(u + 1)}, {hp}, v[86:87] op_sel:[0,1,0] op_sel_hi:[1,1,1]")
-    fmas(X, 76, 80)
+            chain_term(b, "v[84:85]", xs(u), hp, 0, first and u == 0)
+            chain_term(b, "v[86:87]", xs(u + 1), hp, 1, first and u == 0)
+    fmas(X, 76, 80, True)
     b("s_waitcnt lgkmcnt(0)")
-    fmas(Y, 104, 108)
+    fmas(Y, 104, 108, False)
     b("s_nop 0")
     b("v_pk_add_f32 v[84:85], v[84:85], v[86:87]")
     b("s_nop 0")
@@ -823,8 +843,15 @@ def block_detb():
     W = lambda k: 96 + k
     Y = lambda k: vreg(104 + 2 * k, 2)
     V = lambda k: 120 + k
-    b("v_mov_b64_e32 v[64:65], 0")                                 # p0, p1 (lanes outside the round keep 0: |interp|^2 = 0)
-    b("v_mov_b64_e32 v[66:67], 0")
+    # p0, p1 (v[64:65], v[66:67]) start as the products of taps 0 and 1 (chain_term), under the round's mask: lanes 30, 31 and
+    # 48..63 keep whatever the block in front left there, the sum and the compare below run on it, and NOTHING reads the
+    # result -- the walks test bits 0..29 of the compare (fast: even bits up to 28, masked by 0x15555555; careful: bit pos and,
+    # through c | c >> 1, bit pos + 1 <= 29), the v_readlane pair reads lanes 32 + p, p = 0..15.  (exec_ok: told to the checker.)
+    # The sign of a zero: lanes 0..29 go through |interp|^2.  The final positions' value (lanes 32..47) is read as it is, per
+    # component p0 + p1.  p1 holds tap fl, the tap AT the peak's floor: its weight is sincv[f], f = 0..511 -- sinc on [0, 1),
+    # positive for every fraction, 1 at fraction 0 (tests/test_nb_amp_lanes_cpu.py checks the blob) -- and cz[] is never -0
+    # (sums from +0) nor subnormal, so that product is -0 for no input: p1 never ends at -0, and p0 + p1 with p0 = -0 is p1 +
+    # (+0) bit for bit (p1 = +0: +0 + -0 = +0).
     b("v_add_u32_e32 v68, %[e], %[kb]")                            # position of this lane (1/512 symbol)
     b("s_add_u32 s88, %[czb], -56")
     b("s_mov_b32 exec_lo, 0x3fffffff")                             # lanes 0..29: 15 nodes x {early, late}; 32..47: final positions
@@ -845,14 +872,13 @@ def block_detb():
             # rows 6 - u, 7 - u are ONE 8-byte entry of pair 3 - u / 2: the weight of tap u + 1 in the low register, of tap u in the high one
             b(f"ds_read_b64 {vreg(W(u), 2)}, v71 offset:{SINCP_PAIR_BYTES * (3 - (u >> 1))}")
 
-    def fma2(xs, ws, u, swapped):
-        lo, hi = "op_sel:[0,0,0] op_sel_hi:[1,0,1]", "op_sel:[0,1,0] op_sel_hi:[1,1,1]"
-        b(f"v_pk_fma_f32 v[64:65], {xs(u)}, {vreg(ws(u), 2)}, v[64:65] {hi if swapped else lo}")
-        b(f"v_pk_fma_f32 v[66:67], {xs(u + 1)}, {vreg(ws(u), 2)}, v[66:67] {lo if swapped else hi}")
+    def fma2(xs, ws, u, swapped, first=False):
+        chain_term(b, "v[64:65]", xs(u), vreg(ws(u), 2), 1 if swapped else 0, first)
+        chain_term(b, "v[66:67]", xs(u + 1), vreg(ws(u), 2), 0 if swapped else 1, first)
     # software pipeline: 12 loads in flight; each step consumes two taps of the first half and issues two of the second
     for k in range(4):
         b("s_waitcnt lgkmcnt(9)")
-        fma2(X, W, 2 * k, True)
+        fma2(X, W, 2 * k, True, k == 0)
         b(f"ds_read_b64 {Y(2 * k)}, v69 offset:{8 * (8 + 2 * k)}")
         b(f"ds_read_b64 {vreg(V(2 * k), 2)}, v72 offset:{SINCP_PAIR_BYTES * k}")      # rows 2k, 2k + 1: taps 2k, 2k + 1 in order
         b(f"ds_read_b64 {Y(2 * k + 1)}, v69 offset:{8 * (8 + 2 * k + 1)}")
@@ -883,6 +909,7 @@ def block_detb():
     b("v_readlane_b32 %[xr], v74, s93")
     b("v_readlane_b32 %[xi], v75, s93")
     b(".Lnb_db_end:")
+    b.exec_ok = {"v64", "v65", "v66", "v67"}                       # (read under the full mask, used from the round's lanes only: above)
     # ---- cold (NB_ASM_COLD): fixed registers only
     cold(".Lnbc_db_careful:")
     careful_walk(cold, "s88", "s90", "s94", "s95", 4, ".Lnbc_db_unsure", "b32")
@@ -897,23 +924,24 @@ def block_detb():
 # burst's result record.
 #   * TOA in 1/512 symbol -> shift and delay-filter row of the straight-line demodulator; fetch of the burst's low-edge
 #     tap rows (trx_tables.edge8: 768 bytes, 16 per lane) from L2, as early as possible
-#   * computeCI (:1608-1639): S = mean power of the 16 samples at the rounded TOA (tree sum), C = |peak|^2 / ci_den
+#   * computeCI (:1608-1639): 16 S = the summed power of the 16 samples at the rounded TOA (tree sum; the scale 1 / 16, exact, and
+#     C = |peak|^2 / ci_den are flush_records()'s, once per 64 bursts)
 #   * amp = peak / gain (:1701), toa = position - sync->toa - head (:1704, :1768)
-#   * 1 / amp -> the per-lane multiplier VP of the output stage (block DEMOD); RSSI (Transceiver.cpp:741,751)
+#   * 1 / amp -> the per-lane multiplier VP of the output stage (block DEMOD), each lane its own component: amp_lane()
 #   * the result record: field k in lane k of one register (rc, toa, amp.re, amp.im, ci, energy, rssi, flags)
-#   in : SGPR toa (position * 512), xr / xi (peak value), t5 ((int)(sync->toa * 512)), hdrb (LDS byte address of the
-#        sequence header), e8lo / e8hi (address of tab->edge8), es (energy sum), fsdb (20 log10 full_scale), flags;
-#        VGPR l16 (16 * lane), aw (slice base + 8 * lane: D[lane] is offset AW_D of it); SGPR pairs modd = 0xaaaa.., m23 = 0xcccc..
-#   out: SGPR ok (0: TOA outside the straight-line geometry -- left through NB_ASM_COLD, S done), ssum (S); VGPR d0 d1 d2 (block DEMOD)
+#   in : SGPR toa (position * 512), xr / xi (peak value), t5 ((int)(sync->toa * 512)), ampb (LDS byte address of the
+#        sequence's row of (A, B) pairs: trx_kernel_nb.hip lamp, 16-byte aligned), e8lo / e8hi (address of tab->edge8), es (energy sum), fsdb (20 log10 full_scale), flags;
+#        VGPR l16 (16 * lane), l4 (4 * lane), aw (slice base + 8 * lane: D[lane] is offset AW_D of it)
+#   out: SGPR ok (0: TOA outside the straight-line geometry -- left through NB_ASM_COLD, the sum done), ssum (16 S); VGPR d0 d1 d2 (block DEMOD)
 # ------------------------------------------------------------------------------------------------------------------
 FIDX = "s99"                     # TAIL: the burst's delay-filter row, from the row fetch at the head to the composite row's address
 
 
 def block_tail():
-    b = Block("TAIL", ("toa", "xr", "xi", "t5", "hdrb", "e8lo", "e8hi", "ok", "ssum", "pb", "cb", "db"))
+    b = Block("TAIL", ("toa", "xr", "xi", "t5", "ampb", "e8lo", "e8hi", "ok", "ssum", "pb", "cb", "db"))
     cold = Block("TAIL_COLD")
-    b("v_mov_b32_e32 v65, %[hdrb]")
-    b("ds_read_b128 v[68:71], v65")                                # gain, 1 / gain
+    b("v_and_or_b32 v65, %[l4], 12, %[ampb]")                      # &A[lane & 3] of the sequence's row (32 bytes, 16-byte aligned)
+    b("ds_read2_b32 v[70:71], v65 offset1:4")                      # this lane's (A, B) of 1 / gain: amp_lane(), below
     b("s_sub_u32 s88, %[t5], %[toa]")
     b("s_add_u32 s87, s88, 5120")                                  # nk = -(toa512 - t5 - 10 * 512)
     b("s_mov_b32 %[ok], 0")
@@ -936,26 +964,6 @@ def block_tail():
     b("s_bfm_b64 exec, 16, 0")
     b(f"ds_read_b64 v[66:67], v64 offset:{AW_D}")                              # computeCI's sixteen samples (:1608-1639)
     b("s_mov_b64 exec, -1")
-    b("s_waitcnt lgkmcnt(1)")
-    # ---- every lane: amp = peak / gain (:1701), 1 / amp, the output stage's multiplier VP
-    b("v_mul_f32_e32 v82, %[xr], v70")                             # peak * (1 / gain): Complex.h:74
-    b("v_mul_f32_e32 v83, %[xr], v71")
-    b("v_mul_f32_e32 v84, %[xi], v71")
-    b("v_mul_f32_e32 v85, %[xi], v70")
-    b("v_sub_f32_e32 v86, v82, v84")                               # amp.re
-    b("v_add_f32_e32 v87, v83, v85")                               # amp.im
-    b("v_mul_f32_e32 v90, v86, v86")
-    b("v_mul_f32_e32 v89, v87, v87")
-    b("v_add_f32_e32 v89, v89, v90")                               # |amp|^2
-    b("v_rcp_f32_e32 v89, v89")
-    b("s_mov_b32 s88, 0xaaaaaaaa")
-    b("s_mov_b32 s89, 0xaaaaaaaa")
-    b("v_mul_f32_e32 v91, v86, v89")                               # 1 / amp = conj(amp) / |amp|^2 (Complex.h:75,144-150)
-    b("v_mul_f32_e64 v92, -v87, v89")
-    b("v_cndmask_b32_e64 v119, v91, v92, s[88:89]")               # VP[lane & 3] = sx, sy, -sx, -sy (odd lanes: sy)
-    b("s_mov_b32 s88, 0xcccccccc")
-    b("s_mov_b32 s89, 0xcccccccc")
-    b("v_cndmask_b32_e64 v119, v119, -v119, s[88:89]")            # (lanes 2, 3 mod 4: negated)
     # (the burst's record -- C/I, RSSI, amp, toa -- is not made here: its inputs go into lane `slot` of seven registers and 64
     # records are made at once, trx_kernel_nb.hip flush_records; what is per burst is S, computeCI's mean sample power)
     block_demod(b)
@@ -982,13 +990,46 @@ def block_tail():
 #        (lane constant: byte offset of the lane's tap row inside D, -1 for the lanes on the composite row)
 #   out: VGPR d0 d1 d2: the sliced soft bits of the three symbols that END in the lane: real((-j)^i z / amp) through vectorSlicer
 # ------------------------------------------------------------------------------------------------------------------
+def amp_lane(b, fill):
+    """amp = peak / gain (:1701) and the output stage's multiplier VP[lane & 3] = (sx, sy, -sx, -sy), (sx, sy) = 1 / amp =
+    conj(amp) / |amp|^2 (Complex.h:75, 144-150), made per LANE: a lane needs its own component of amp and the square of the
+    other one, not the whole wave-uniform value and two selects.  The kernel stages, per training sequence, the four pairs
+    (A, B) by lane & 3 of (g0, g1) = 1 / gain (trx_tables.h, trx_amp_lane_pair: (g0, -g1), (-g1, -g0), (-g0, g1), (g1, g0)):
+        comp = fl(fl(xr A) + fl(xi B)) = +amp.re, -amp.im, -amp.re, +amp.im  -- the bits of Complex.h:74's fl(xr g0) - fl(xi g1)
+                                         and fl(xr g1) + fl(xi g0): negation is exact, and a - b IS a + (-b);
+        n    = fl(comp^2) + the quad neighbour's fl(comp^2) (lanes 0 <-> 1, 2 <-> 3)  = |amp|^2 as fl(im^2) + fl(re^2): a square
+                                         loses the sign, the addition is commutative;
+        VP   = fl(comp * rcp(n))         -- sx = fl(re r), sy = fl(-im r), and fl(-x r) = -fl(x r).
+    One case is not the same bits: a component of amp that cancels to an EXACT zero is +0 in every lane here, where the negated
+    variants (-amp.im, -amp.re) had -(+0) = -0.  That lane's VP is then a zero of the other sign, its product with a filter sum a
+    zero of some sign, and the output stage adds the other component's product onto it (a non-zero addend absorbs it; two zeros
+    give a zero) in front of the slicer's fma(d, 0.5, 0.5), which takes +0 and -0 alike to 0.5: no soft bit sees it, and n, a sum
+    of squares, does not either (tests/test_nb_amp_lanes_cpu.py models both forms through the slicer).
+    In: v[70:71] = (A, B), the peak in %[xr] %[xi] (SGPR); out: v119.  Temporaries: v70, v71, v112 (P[0], dead behind the
+    sample reads).  fill: five independent instructions of the caller -- the DPP source's two wait states and the reciprocal's
+    one among them.  The geometry's cold exit leaves in front of this: it forms amp in C++ (trx_kernel_nb.hip), as it did."""
+    assert len(fill) == 5
+    b("v_mul_f32_e32 v70, %[xr], v70")
+    b("v_mul_f32_e32 v71, %[xi], v71")
+    b(fill[0])
+    b("v_add_f32_e32 v119, v70, v71")                              # comp
+    b(fill[1])
+    b("v_mul_f32_e32 v112, v119, v119")
+    b(fill[2])
+    b(fill[3])
+    b(f"v_add_f32_dpp v112, v112, v112 quad_perm:[1,0,3,2] {D_ALL}")     # |amp|^2
+    b("v_rcp_f32_e32 v112, v112")
+    b(fill[4])
+    b("v_mul_f32_e32 v119, v119, v112")                            # VP
+
+
 def block_demod(b):
-    # the straight-line geometry: shift w = nk >> 7 in -36 .. 0 (0 <= TOA <= 9 symbols); other bursts leave with ok = 0 -- 1 / amp
-    # and S are done -- and take the general form of the demodulator (trx_kernel_nb.hip, cold)
+    # the straight-line geometry: shift w = nk >> 7 in -36 .. 0 (0 <= TOA <= 9 symbols); other bursts leave with ok = 0 -- the sum
+    # of computeCI is done, 1 / amp is not -- and take the general form of the demodulator (trx_kernel_nb.hip, cold)
     ACC = [64, 66, 68]
     X = lambda r: vreg(72 + 2 * r, 2)
     P = [112, 113, 114, 115]
-    # S = mean |sample|^2 of computeCI's sixteen samples (lanes 0..15: a tree sum), in the wait states of the address arithmetic
+    # 16 S = the sum of |sample|^2 over computeCI's sixteen samples (lanes 0..15: a tree sum), in the wait states of the address arithmetic
     b("s_bfm_b64 exec, 16, 0")
     b("s_waitcnt lgkmcnt(0)")
     b("v_pk_mul_f32 v[66:67], v[66:67], v[66:67]")
@@ -1005,8 +1046,7 @@ def block_demod(b):
     b(f"v_add_f32_dpp v81, v81, v81 row_half_mirror {D_ALL}")
     b(f"s_mul_i32 s95, {FIDX}, 144")                                 # (the filter's row: made once, at the block's head)
     b("s_add_u32 s95, s95, %[cb]")                                 # composite row of the burst's delay filter, from tap U0
-    b(f"v_add_f32_dpp v81, v81, v81 row_mirror {D_ALL}")
-    b("v_mul_f32_e32 v81, 0x3d800000, v81")                        # S = sum / 16 (row 0)
+    b(f"v_add_f32_dpp v81, v81, v81 row_mirror {D_ALL}")         # 16 S (row 0): the power-of-two scale is flush_records()'s, once per 64 bursts
     b("s_sub_u32 s96, 0, s88")
     b("v_readlane_b32 %[ssum], v81, 0")
     b("s_mov_b64 exec, -1")
@@ -1025,13 +1065,10 @@ def block_demod(b):
     # the lane's twelve samples do not depend on the tap rows: requested in front of the wait for those (L2 latency)
     for r in range(12):
         b(f"ds_read_b64 {X(r)}, {vreg(P[r & 3])} offset:{PH0 + 8 * (r >> 2) + (r & 3) * PH_A * 8}")
-    b("v_add_u32_e32 v116, %[db], %[l16]")
-    b("v_cmp_lt_i32_e32 vcc, -1, %[ktp]")
-    b("v_add_u32_e32 v117, %[db], %[ktp]")
-    b("v_mov_b32_e32 v118, s95")
-    for j_ in range(3):
-        b(f"v_mov_b64_e32 {vreg(ACC[j_], 2)}, 0")
-    b("v_cndmask_b32_e32 v117, v118, v117, vcc")                   # this lane's tap row
+    # the tap row's address and the output stage's multiplier (amp_lane) share the slots: each is the other's wait states
+    amp_lane(b, ["v_cmp_lt_i32_e32 vcc, -1, %[ktp]", "v_add_u32_e32 v117, %[db], %[ktp]", "v_mov_b32_e32 v118, s95",
+                 "v_add_u32_e32 v116, %[db], %[l16]",
+                 "v_cndmask_b32_e32 v117, v118, v117, vcc"])       # this lane's tap row
     b("s_waitcnt vmcnt(0)")
     b("ds_write_b128 v116, v[120:123]")                            # park the low-edge rows: lane l < 48 holds floats 4l .. 4l+3 of the 8 x 24 block
     fir_moving(b, ACC, X)
@@ -1103,7 +1140,9 @@ def fir_moving(b, ACC, X):
     lane l + s holds: in stage s lane m adds X_m[r] h[12 s + r - 4 j] into slot j for the r with 0 <= 12 s + r - 4 j < 24, r
     ascending, and between two stages the slot's accumulator moves one lane up (v_mov_b32_dpp wave_shr:1).  Every output is the
     same 24 FMAs in the same order from the same +0 -- the same bits -- and ends in lane l + 2 (slot 0 has no stage 2: it is
-    carried there by a second move, so that the three sums of a lane belong to adjacent symbols).
+    carried there by a second move, so that the three sums of a lane belong to adjacent symbols).  (Since the chains start as
+    products -- chain_term, no accumulator is zeroed -- "from the same +0" reads "up to the sign of an exact zero": see the
+    paragraph on zero taps below.)
         terms (stage, slot):   slot 0: 12 12 0    slot 1: 8 12 4    slot 2: 4 12 8           = 72 FMAs per lane
     A slot is one dependent chain (packed FMA -> reader: 1 wait state, -> DPP source: 2); the three chains are interleaved so
     that every wait state is another chain's instruction.
@@ -1114,10 +1153,17 @@ def fir_moving(b, ACC, X):
                 sum_{r = 4..11} x[W - 12 + r] row[r - 4] = sum_{u = 0..7} x[W - 8 + u] row[u] -- the low part, u ascending from +0.
                 Slot 1's moves are masked off for lanes 52..63 (EXEC = lanes 0..51 around them), so the sum stays in its lane,
                 and its stages 1 and 2 multiply the zero taps 8..23.
-      Zero taps are bit-safe: the samples are converted int16, hence finite, so x * 0 = +-0; a round-to-nearest sum that starts
-      at +0 is never -0 (+0 + -0 = +0, and a non-zero sum stays non-zero), so fma(x, 0, acc) = acc for every acc that occurs and
-      fma(x, T, acc) behind leading zero taps sees acc = +0, as if it were the first.  The low part is thereby the same FMAs
-      on the same operands as before for u < 8 and no-ops behind; main + low is one add, as before.
+      Zero taps are bit-safe: the samples are converted int16, hence finite and never -0, so x * 0 = +-0.  A chain starts as the
+      product of its first term (chain_term), so behind leading zero taps -- the low part's two, a truncated row's -- the
+      accumulator is +0 or -0 where a chain from +0 had +0; the first tap T that is not zero then gives fma(x, T, +-0) =
+      fl(x T), the same bits either way, unless that product is a zero too, and from the first non-zero product on the chain
+      is what it was (s + -0 = s).  Zero taps BEHIND a sum leave it alone (fma(x, 0, s) = s for s not zero; a zero stays a
+      zero).  So a slot's sum is the same bits as before, or -- all of its products zeros: every sample under a non-zero tap
+      is 0 -- a zero whose sign may differ.  Where such a zero goes: main + low is one add (a zero of either sign added to a
+      non-zero sum changes nothing, two zeros give a zero); the output stage multiplies z by VP, adds the other component's
+      product -- a zero of either sign is absorbed by a non-zero addend, two zeros give a zero -- and the slicer's fma(d, 0.5,
+      0.5) takes +0 and -0 alike to 0.5.  No soft bit sees the sign.  (tests/test_gpu_nb_amp_lanes.py: bursts whose first 48
+      samples are zero, an all-zero burst, a zeroed polyphase row -- bytes against the general kernel.)
     Registers: six tap quads v96..v111, v124..v127, v120..v123 (the last one behind the first LDS wait: v120..v123 hold the
     parked rows until the ds_write in front has read them); v117 = the lane's tap row."""
     Q = [96, 100, 104, 108, 124, 120]
@@ -1184,9 +1230,7 @@ def fir_moving(b, ACC, X):
                     q5_issued = True
                     pos += 1
             hp = vreg(Q[q] + (2 if (t & 2) else 0), 2)
-            sel = "op_sel:[0,1,0] op_sel_hi:[1,1,1]" if (t & 1) else "op_sel:[0,0,0] op_sel_hi:[1,0,1]"
-            a = vreg(ACC[j], 2)
-            b(f"v_pk_fma_f32 {a}, {X(r)}, {hp}, {a} {sel}")
+            chain_term(b, vreg(ACC[j], 2), X(r), hp, t & 1, ip[j] == 1)   # (a slot's first term starts its chain: no zeroed accumulator)
             last[j] = (pos, "fma")
             pos += 1
         else:
@@ -1265,6 +1309,7 @@ def main(out=OUT):
         v = Block(b.name, [n[2:-1] for n in b.sgpr_ops])
         assert b.ins[-1].endswith("_end:")
         v.ins = b.ins[:-1] + ["s_branch " + b.ins[-1][:-1]] + c.ins + [b.ins[-1]]
+        v.exec_ok = getattr(b, "exec_ok", ())
         return v
     errs = [e for p in dc_paths for e in p.check()] + \
         check_paths(with_cold(blocks["DETA"], da_cold)) + check_paths(with_cold(blocks["DETB"], db_cold)) + \
