@@ -17,13 +17,12 @@ import argparse
 import json
 import os
 import re
-import shutil
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 FULL_SCALE = 2047.0
 BASE_FN = 51 * 4321
@@ -36,11 +35,11 @@ def child(a):
     import ctypes as C
     import numpy as np
     import torch
-    from bench_ms_rx import TSC, multiframe
     from osmo_trx_amd import TrxHip, trxhip
+    from workloads import TSC, multiframe
     trx = TrxHip(0)
     base_iq = multiframe(trx, BASE_FN)[0]
-    names = [k for pair in PAIRS for k in pair if not a.legs or k in a.legs.split(",")]
+    names = br.select_legs([k for pair in PAIRS for k in pair], a.legs)
     L, st = trx.L, trx._stream()
     vp = C.c_void_p
     frames = a.frames
@@ -137,85 +136,40 @@ def child(a):
         legs["gbig"], legs["sbig"] = (gbig, 1), (sbig, 1)
         checks.append(check_big)
     names = [k for k in names if k in legs]
-    times = {k: [] for k in names}
-    for name in names:
-        for _ in range(a.warmup):
-            legs[name][0]()
-    torch.cuda.synchronize()
-    for i in range(a.inner):
-        for name in (names if (a.round + i) % 2 == 0 else names[::-1]):
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            legs[name][0]()                                        # untimed: the timed calls follow a call of their own kind
-            ev[0].record()
-            for _ in range(a.reps):
-                legs[name][0]()
-            ev[1].record()
-            torch.cuda.synchronize()
-            times[name].append(ev[0].elapsed_time(ev[1]) / a.reps / legs[name][1])
+    times = br.time_in_turns(torch, legs, names, a, untimed_first=True)
     if not a.legs:
         for check in checks:
             check()
-    print(json.dumps({k: statistics.median(v) for k, v in times.items()}), flush=True)
+    print(json.dumps(times), flush=True)
+
+
+def summarise(per_leg, a):
+    res = {"workload": "ms_group", "slots": a.slots, "small_pull_slots": 8, "frames_per_call": a.frames, "slot_len": 625,
+           "mix_per_408": {"fcch": 5, "sch": 5, "traffic": 398}, "input": "int16", "tracking": True, "rounds": a.rounds, "inner": a.inner,
+           "reps": a.reps, "unit": "ms per frame of all members (gbig / sbig: per pull)",
+           "legs": {name: br.leg_summary(xs) for name, xs in per_leg.items()}, "pairs": {}}
+    for x, y in PAIRS:
+        if x in res["legs"] and y in res["legs"]:
+            res["pairs"][x + "_over_" + y] = br.pair(res["legs"], x, y)
+    return res
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--slots", type=int, default=1 << 18)
     ap.add_argument("--frames", type=int, default=17, help="8-slot pulls in a row per timed call")
-    ap.add_argument("--inner", type=int, default=6, help="turns per leg inside a round (even: both orders equally often)")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--timeout", type=int, default=150, help="seconds per round")
-    ap.add_argument("--trace", default="", help="also take a kernel trace of these legs (comma-separated), each in a run of its own")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ms_group_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    br.add_options(ap, "ms_group", warmup=2, reps=3, timeout=150, inner=6, even_inner=True, trace="legs")
     a = ap.parse_args()
     if a.round is not None:
         return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    if a.inner % 2:
-        ap.error("an even number of turns")
-    import measure
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg = {}
     me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--frames", str(a.frames)]
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, "ms_group_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--inner", str(a.inner), "--warmup", str(a.warmup), "--reps",
-                                                 str(a.reps)], log, a.timeout)
-        for k, v in measure.last_json(log).items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
-    res = {"workload": "ms_group", "slots": a.slots, "small_pull_slots": 8, "frames_per_call": a.frames, "slot_len": 625,
-           "mix_per_408": {"fcch": 5, "sch": 5, "traffic": 398}, "input": "int16", "tracking": True, "rounds": a.rounds, "inner": a.inner,
-           "reps": a.reps, "unit": "ms per frame of all members (gbig / sbig: per pull)", "legs": {}, "pairs": {}}
-    for name, xs in per_leg.items():
-        med = statistics.median(xs)
-        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs])
-    lg = res["legs"]
-    for gn, sn in PAIRS:
-        if gn in lg and sn in lg:
-            res["pairs"][gn + "_over_" + sn] = dict(ratio=round(lg[gn]["median_ms"] / lg[sn]["median_ms"], 4),
-                                                    diff_ms=round(lg[gn]["median_ms"] - lg[sn]["median_ms"], 4),
-                                                    larger_spread_ms=max(lg[gn]["spread_ms"], lg[sn]["spread_ms"]))
+    res = summarise(br.run_rounds("ms_group", me, a), a)
     if a.trace:
-        from bench_rx_sched import trace_rows
-        d = os.path.join(a.logs, "ms_group_trace")
         res["kernel_trace_us"] = {}
         for leg in a.trace.split(","):
-            shutil.rmtree(d, ignore_errors=True)
-            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "ms_group",
-                                                 "--"] + me + ["--round", "0", "--inner", "1", "--warmup", "1", "--reps", "1", "--legs", leg],
-                         os.path.join(a.logs, "ms_group_trace_%s.log" % leg), a.timeout)
-            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(trace_rows(d).items()) if re.match(r"ms_rx|ms_join", k)}
-        shutil.rmtree(d, ignore_errors=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+            rows = br.kernel_trace("ms_group", me, ["--inner", "1", "--warmup", "1", "--reps", "1"], leg, a)
+            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(rows.items()) if re.match(r"ms_rx|ms_join", k)}
+    br.write_json(a.out, res)
     print(json.dumps(res), flush=True)
 
 

@@ -17,42 +17,15 @@ import argparse
 import json
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 FULL_SCALE = 2047.0
-TSC = 5
-BSIC = 0o52
-
-
-def multiframe(trx, base_fn, seed=7):
-    """One 51-multiframe of a cell as the radio delivers it: (int16[408, 625, 2] on the GPU, MS_SLOT_DTYPE[408], sent bits
-    uint8[408, 148], kinds).  SCH and normal bursts come through the product's own modulator; FCCH slots hold a random burst."""
-    import numpy as np
-    import torch
-    from osmo_trx_amd import synth, trxhip
-    rng = np.random.default_rng(seed)
-    fns = np.repeat(np.arange(base_fn, base_fn + 51), 8)
-    tns = np.tile(np.arange(8), 51)
-    kinds = np.array([trxhip.ms_slot_kind(int(f), int(t)) for f, t in zip(fns, tns)])
-    sent = rng.integers(0, 2, (408, 148), dtype=np.uint8)
-    sent[:, :3] = 0
-    sent[:, -3:] = 0
-    sent[:, 61:87] = [int(c) for c in synth.TSC_BITS[TSC]]
-    for b in np.nonzero(kinds == trxhip.MS_KIND_SCH)[0]:
-        sent[b] = synth.sch_burst_bits(BSIC, int(fns[b]))
-    p = np.zeros(408, dtype=trxhip.TX_PARAMS_DTYPE)
-    p["nbits"], p["guard"], p["scale_re"] = 148, 8, 1.0
-    _, iq, _ = trx.modulate(torch.from_numpy(sent).to("cuda:0"), trx.tx_params_tensor(p), sps=4, cf32=False, s16_scale=1400.0)
-    slots = np.zeros(408, dtype=trxhip.MS_SLOT_DTYPE)
-    slots["fn"], slots["tn"], slots["tsc"], slots["flags"] = fns, tns, TSC, trxhip.MS_SLOT_ACTIVE
-    return iq, slots, sent, kinds
 
 
 def child(a):
@@ -61,6 +34,7 @@ def child(a):
     import numpy as np
     import torch
     from osmo_trx_amd import TrxHip, trxhip
+    from workloads import TSC, multiframe
     trx = TrxHip(0)
     base_iq, base_slots, sent, kinds = multiframe(trx, 51 * 4321)
     reps = (a.slots + 407) // 408
@@ -101,22 +75,9 @@ def child(a):
         trxhip._check(L.trxhip_sch_sync_batch_i16(trx.h, ptr(iq_s), 625, ptr(rec_s), ptr(bits_s), ns, 625, trxhip.SCH_SYNC_TRACK, scale, st),
                       "sch")
 
-    legs = {"ms_rx": ms_rx, "chain": chain}
-    names = [k for k in legs if not a.legs or k in a.legs.split(",")]
-    times = {k: [] for k in names}
-    for name in names:
-        for _ in range(a.warmup):
-            legs[name]()
-    torch.cuda.synchronize()
-    for i in range(a.inner):
-        for name in (names if (a.round + i) % 2 == 0 else names[::-1]):
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            for _ in range(a.reps):
-                legs[name]()
-            ev[1].record()
-            torch.cuda.synchronize()
-            times[name].append(ev[0].elapsed_time(ev[1]) / a.reps)
+    legs = {"ms_rx": (ms_rx, 1), "chain": (chain, 1)}
+    names = br.select_legs(legs, a.legs)
+    times = br.time_in_turns(torch, legs, names, a)
     # the timed calls received what was sent
     if "ms_rx" in names:
         r = ind.cpu().numpy().reshape(-1).view(trxhip.MS_IND_DTYPE)
@@ -126,83 +87,37 @@ def child(a):
         assert (r["sch_rc"][sch] == 1).all() and (r["sch_fn"][sch] % 51 == slots_np["fn"][sch] % 51).all(), "SCH slots did not decode"
         dem = (kind_all[:408] != trxhip.MS_KIND_FCCH)
         assert np.array_equal(b[:408][dem], np.where(sent[dem] > 0, -127, 127)), "the bits are not the ones sent"
-    print(json.dumps({k: statistics.median(v) for k, v in times.items()}), flush=True)
+    print(json.dumps(times), flush=True)
 
 
-def resource_usage():
-    """{kernel: {...}} from tools/resource_usage.sh"""
-    txt = subprocess.run(["bash", os.path.join(ROOT, "tools", "resource_usage.sh"), "trx_ms_rx.hip", "ms_rx"], stdout=subprocess.PIPE,
-                         text=True, check=True).stdout
-    out, cur = {}, None
-    keys = {"VGPRs": "vgprs", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
-            "LDS Size [bytes/block]": "lds_bytes_per_block", "Occupancy [waves/SIMD]": "occupancy_waves_per_simd"}
-    for line in txt.splitlines():
-        m = re.match(r"Function Name: (\S+)", line)
-        if m:
-            name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, text=True).stdout.strip() or m.group(1)
-            cur = out.setdefault(name.split("(")[0].replace("void ", ""), {})
-            continue
-        m = re.match(r"\s+([^:]+): (\d+)$", line)
-        if m and cur is not None and m.group(1) in keys:
-            cur[keys[m.group(1)]] = int(m.group(2))
-    return out
+def summarise(per_leg, a):
+    res = {"workload": "ms_rx", "slots": a.slots, "slot_len": 625, "mix_per_408": {"fcch": 5, "sch": 5, "traffic": 398}, "input": "int16",
+           "rounds": a.rounds, "inner": a.inner, "reps": a.reps, "legs": {}}
+    for name, xs in per_leg.items():
+        res["legs"][name] = br.leg_summary(xs, us_per_slot=round(statistics.median(xs) * 1e3 / a.slots, 5))
+    res["chain_over_ms_rx"] = round(res["legs"]["chain"]["median_ms"] / res["legs"]["ms_rx"]["median_ms"], 3)
+    return res
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--slots", type=int, default=1 << 18)
-    ap.add_argument("--inner", type=int, default=5, help="turns per leg inside a round")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--timeout", type=int, default=180, help="seconds per round")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ms_rx_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    br.add_options(ap, "ms_rx", warmup=2, reps=3, timeout=180, inner=5, trace="off")
     a = ap.parse_args()
     if a.round is not None:
         return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    import measure
-    from bench_rx_sched import trace_rows
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg = {}
     me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots)]
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, "ms_rx_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--inner", str(a.inner), "--warmup", str(a.warmup), "--reps",
-                                                 str(a.reps)], log, a.timeout)
-        for k, v in measure.last_json(log).items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
-    res = {"workload": "ms_rx", "slots": a.slots, "slot_len": 625, "mix_per_408": {"fcch": 5, "sch": 5, "traffic": 398}, "input": "int16",
-           "rounds": a.rounds, "inner": a.inner, "reps": a.reps, "legs": {}}
-    for name, xs in per_leg.items():
-        med = statistics.median(xs)
-        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs],
-                                 us_per_slot=round(med * 1e3 / a.slots, 5))
-    res["chain_over_ms_rx"] = round(res["legs"]["chain"]["median_ms"] / res["legs"]["ms_rx"]["median_ms"], 3)
+    res = summarise(br.run_rounds("ms_rx", me, a), a)
     if not a.no_trace:
-        d = os.path.join(a.logs, "ms_rx_trace")
         res["kernel_trace_us"] = {}
         for leg in ("ms_rx", "chain"):
-            shutil.rmtree(d, ignore_errors=True)
-            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "ms_rx",
-                                                 "--"] + me + ["--round", "0", "--inner", "1", "--warmup", "1", "--reps", "3", "--legs", leg],
-                         os.path.join(a.logs, "ms_rx_trace_%s.log" % leg), a.timeout)
-            rows = {k: v for k, v in sorted(trace_rows(d).items())
+            rows = {k: v for k, v in sorted(br.kernel_trace("ms_rx", me, ["--inner", "1", "--warmup", "1", "--reps", "3"], leg, a).items())
                     if re.match(r"ms_rx|sch_sync|va_demod|energy|convert", k)}
             for v in rows.values():
                 v["ns_per_slot"] = round(v["avg_us"] * 1e3 / a.slots, 3)
             res["kernel_trace_us"][leg] = rows
-        shutil.rmtree(d, ignore_errors=True)
-    res["resource_usage"] = resource_usage()
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    res["resource_usage"] = br.resource_usage("trx_ms_rx.hip", "ms_rx")
+    br.write_json(a.out, res)
     print(json.dumps(res), flush=True)
 
 

@@ -20,13 +20,12 @@ import argparse
 import json
 import os
 import re
-import shutil
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 FULL_SCALE = 2047.0
 BASE_FN = 51 * 4321
@@ -37,8 +36,8 @@ def child(a):
     import ctypes as C
     import numpy as np
     import torch
-    from bench_ms_rx import TSC, multiframe
     from osmo_trx_amd import TrxHip, trxhip
+    from workloads import TSC, multiframe
     trx = TrxHip(0)
     base_iq, base_slots, sent, kinds = multiframe(trx, BASE_FN)
     reps = (a.slots + 407) // 408
@@ -79,21 +78,8 @@ def child(a):
 
     legs = {"sched": (sched, 1), "rows": (rows, 1), "sched8": (sched8, 51), "rows8": (rows8, 51)}
     assert a.slots >= small
-    names = [k for k in legs if not a.legs or k in a.legs.split(",")]
-    times = {k: [] for k in names}
-    for name in names:
-        for _ in range(a.warmup):
-            legs[name][0]()
-    torch.cuda.synchronize()
-    for i in range(a.inner):
-        for name in (names if (a.round + i) % 2 == 0 else names[::-1]):
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            for _ in range(a.reps):
-                legs[name][0]()
-            ev[1].record()
-            torch.cuda.synchronize()
-            times[name].append(ev[0].elapsed_time(ev[1]) / a.reps / legs[name][1])
+    names = br.select_legs(legs, a.legs)
+    times = br.time_in_turns(torch, legs, names, a)
     # the two paths gave the same bytes, and the slots received what was sent
     if "sched" in names and "rows" in names:
         sched()
@@ -112,60 +98,34 @@ def child(a):
         sched8()
         torch.cuda.synchronize()
         assert 51 * 7 <= int(s.state()["slots"]) - before <= small, "8-slot pulls cut too few slots"
-    print(json.dumps({k: statistics.median(v) for k, v in times.items()}), flush=True)
+    print(json.dumps(times), flush=True)
+
+
+def summarise(per_leg, a):
+    res = {"workload": "ms_sched", "slots": a.slots, "small_pull_slots": 8, "slot_len": 625, "mix_per_408": {"fcch": 5, "sch": 5, "traffic": 398},
+           "input": "int16", "tracking": True, "rounds": a.rounds, "inner": a.inner, "reps": a.reps,
+           "legs": {name: br.leg_summary(xs) for name, xs in per_leg.items()}}
+    lg = res["legs"]
+    res["sched_over_rows"] = round(lg["sched"]["median_ms"] / lg["rows"]["median_ms"], 4)
+    res["sched8_over_rows8"] = round(lg["sched8"]["median_ms"] / lg["rows8"]["median_ms"], 4)
+    return res
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--slots", type=int, default=1 << 18)
-    ap.add_argument("--inner", type=int, default=5, help="turns per leg inside a round")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--timeout", type=int, default=180, help="seconds per round")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ms_sched_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    br.add_options(ap, "ms_sched", warmup=2, reps=3, timeout=180, inner=5, trace="off")
     a = ap.parse_args()
     if a.round is not None:
         return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    import measure
-    from bench_rx_sched import trace_rows
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg = {}
     me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots)]
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, "ms_sched_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--inner", str(a.inner), "--warmup", str(a.warmup), "--reps",
-                                                 str(a.reps)], log, a.timeout)
-        for k, v in measure.last_json(log).items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
-    res = {"workload": "ms_sched", "slots": a.slots, "small_pull_slots": 8, "slot_len": 625, "mix_per_408": {"fcch": 5, "sch": 5, "traffic": 398},
-           "input": "int16", "tracking": True, "rounds": a.rounds, "inner": a.inner, "reps": a.reps, "legs": {}}
-    for name, xs in per_leg.items():
-        med = statistics.median(xs)
-        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs])
-    lg = res["legs"]
-    res["sched_over_rows"] = round(lg["sched"]["median_ms"] / lg["rows"]["median_ms"], 4)
-    res["sched8_over_rows8"] = round(lg["sched8"]["median_ms"] / lg["rows8"]["median_ms"], 4)
+    res = summarise(br.run_rounds("ms_sched", me, a), a)
     if not a.no_trace:
-        d = os.path.join(a.logs, "ms_sched_trace")
         res["kernel_trace_us"] = {}
         for leg in ("sched", "rows", "sched8"):
-            shutil.rmtree(d, ignore_errors=True)
-            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "ms_sched",
-                                                 "--"] + me + ["--round", "0", "--inner", "1", "--warmup", "1", "--reps", "3", "--legs", leg],
-                         os.path.join(a.logs, "ms_sched_trace_%s.log" % leg), a.timeout)
-            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(trace_rows(d).items()) if re.match(r"ms_rx|ms_join", k)}
-        shutil.rmtree(d, ignore_errors=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+            rows = br.kernel_trace("ms_sched", me, ["--inner", "1", "--warmup", "1", "--reps", "3"], leg, a)
+            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(rows.items()) if re.match(r"ms_rx|ms_join", k)}
+    br.write_json(a.out, res)
     print(json.dumps(res), flush=True)
 
 

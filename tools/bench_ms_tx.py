@@ -21,13 +21,12 @@ import argparse
 import json
 import os
 import re
-import shutil
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 FULL_SCALE = 2047
 BASE_FN = 51 * 4321
@@ -41,7 +40,7 @@ def child(a):
     from osmo_trx_amd import TrxHip, trxhip
     trx = TrxHip(0)
     n = a.slots
-    assert n % 8 == 0 and n >= 51 * 8
+    assert n % 8 == 0 and n >= 51 * 8 + 8                            # dense8 / rows8 write slots 3 .. 3 + 51 * 8 of the window / the rows
     rng = np.random.default_rng(3)
     bits = rng.integers(0, 2, (n, 148)).astype(np.uint8)
     # request k is heard in slot k of the window: its target after incTN(3) is the clock k slots on, the window starts at the clock
@@ -76,39 +75,20 @@ def child(a):
     def modulate(b, p, out, cnt):
         trxhip._check(L.trxhip_modulate_batch(trx.h, b, 148, p, None, out, 1.0, 625, ptr(d_len), cnt, 4, st), "modulate")
 
+    alone = lambda: None   # noqa: E731  no preparation, but timed call by call like the legs that have one
     # (prepare, timed call, calls per timed call)
     legs = {
         "dense": (lambda: submit("dense"), lambda: render(n), 1),
-        "dense_rows": (None, lambda: modulate(ptr(d_bits), ptr(d_par), ptr(rows), n), 1),
+        "dense_rows": (alone, lambda: modulate(ptr(d_bits), ptr(d_par), ptr(rows), n), 1),
         "sparse": (lambda: submit("sparse"), lambda: render(n), 1),
-        "sparse_rows": (None, lambda: modulate(ptr(d_bits_s), ptr(d_par_s), ptr(rows), n // 8), 1),
-        "fill": (None, lambda: window.zero_(), 1),
+        "sparse_rows": (alone, lambda: modulate(ptr(d_bits_s), ptr(d_par_s), ptr(rows), n // 8), 1),
+        "fill": (alone, lambda: window.zero_(), 1),
         "dense8": (lambda: submit("dense8"), lambda: [render(8, 3 + 8 * j) for j in range(51)], 51),
-        "rows8": (None, lambda: [modulate(ptr(d_bits, (3 + 8 * j) * 148), ptr(d_par, (3 + 8 * j) * 16), ptr(rows, (3 + 8 * j) * 2500), 8)
-                                 for j in range(51)], 51),
+        "rows8": (alone, lambda: [modulate(ptr(d_bits, (3 + 8 * j) * 148), ptr(d_par, (3 + 8 * j) * 16), ptr(rows, (3 + 8 * j) * 2500), 8)
+                                  for j in range(51)], 51),
     }
-    names = [x for x in legs if not a.legs or x in a.legs.split(",")]
-    times = {x: [] for x in names}
-
-    def run(name, timed):
-        prep, call, per = legs[name]
-        total = 0.0
-        for _ in range(a.reps if timed else a.warmup):
-            if prep:
-                prep()
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            call()
-            ev[1].record()
-            torch.cuda.synchronize()
-            total += ev[0].elapsed_time(ev[1])
-        return total / max(a.reps, 1) / per
-
-    for name in names:
-        run(name, False)
-    for i in range(a.inner):
-        for name in (names if (a.round + i) % 2 == 0 else names[::-1]):
-            times[name].append(run(name, True))
+    names = br.select_legs(legs, a.legs)
+    times = br.time_in_turns(torch, legs, names, a)
     # the dense stream is the rows, slot for slot (the first three requests lie behind the clock: zeros)
     if "dense" in names and "dense_rows" in names:
         submit("dense")
@@ -127,61 +107,34 @@ def child(a):
         assert nd.value == n // 8 and torch.equal(w[:, 5], rows.view(n // 8, 8, 625, 2)[:, 5]) and not w[:, :5].any() and not w[:, 6:].any()
     st_ = tx.state()
     assert st_["pending"] == 0 and st_["missed"] == 0 and st_["overlap"] == 0 and st_["expired"] == 0, st_
-    print(json.dumps({x: statistics.median(v) for x, v in times.items()}), flush=True)
+    print(json.dumps(times), flush=True)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--slots", type=int, default=1 << 18)
-    ap.add_argument("--inner", type=int, default=5, help="turns per leg inside a round")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--timeout", type=int, default=180, help="seconds per round")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ms_tx_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.round is not None:
-        return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    import measure
-    from bench_rx_sched import trace_rows
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg = {}
-    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots)]
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, "ms_tx_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--inner", str(a.inner), "--warmup", str(a.warmup), "--reps",
-                                                 str(a.reps)], log, a.timeout)
-        for k, v in measure.last_json(log).items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
+def summarise(per_leg, a):
     res = {"workload": "ms_tx", "slots": a.slots, "small_render_slots": 8, "slot_len": 625, "output": "int16", "rounds": a.rounds,
-           "inner": a.inner, "reps": a.reps, "legs": {}}
-    for name, xs in per_leg.items():
-        med = statistics.median(xs)
-        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs])
+           "inner": a.inner, "reps": a.reps, "legs": {name: br.leg_summary(xs) for name, xs in per_leg.items()}}
     lg = res["legs"]
     res["dense_over_rows"] = round(lg["dense"]["median_ms"] / lg["dense_rows"]["median_ms"], 4)
     res["sparse_over_fill"] = round(lg["sparse"]["median_ms"] / lg["fill"]["median_ms"], 4)
     res["dense8_over_rows8"] = round(lg["dense8"]["median_ms"] / lg["rows8"]["median_ms"], 4)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--slots", type=int, default=1 << 18)
+    br.add_options(ap, "ms_tx", warmup=2, reps=3, timeout=180, inner=5, trace="off")
+    a = ap.parse_args()
+    if a.round is not None:
+        return child(a)
+    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots)]
+    res = summarise(br.run_rounds("ms_tx", me, a), a)
     if not a.no_trace:
-        d = os.path.join(a.logs, "ms_tx_trace")
         res["kernel_trace_us"] = {}
         for leg in ("dense", "dense_rows", "sparse"):
-            shutil.rmtree(d, ignore_errors=True)
-            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "ms_tx",
-                                                 "--"] + me + ["--round", "0", "--inner", "1", "--warmup", "1", "--reps", "3", "--legs", leg],
-                         os.path.join(a.logs, "ms_tx_trace_%s.log" % leg), a.timeout)
-            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(trace_rows(d).items()) if re.match(r"ms_tx_render|tx_modulate", k)}
-        shutil.rmtree(d, ignore_errors=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+            rows = br.kernel_trace("ms_tx", me, ["--inner", "1", "--warmup", "1", "--reps", "3"], leg, a)
+            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(rows.items()) if re.match(r"ms_tx_render|tx_modulate", k)}
+    br.write_json(a.out, res)
     print(json.dumps(res), flush=True)
 
 

@@ -19,6 +19,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 PEAK = 8e12
 RESAMP = (("65_96", 65, 96, 1536), ("52_75", 52, 75, 1200))
@@ -40,7 +41,7 @@ def child(a):
     for name, chans in (("four_rows", None), ("chans3", 3), ("chans2", 2), ("chans1", 1)):
         fe = trxhip.RxFrontEnd(trx, 192, 65, 48, chans=chans)
         keep.append(fe)
-        legs["multi_" + name] = (lambda fe=fe: trxhip._check(
+        legs["multi_" + name] = (None, lambda fe=fe: trxhip._check(
             L.trxhip_rx_frontend_pull(fe.h, ptr(wide), nb, ptr(out), n_out, st), "pull"))
     for tag, p, q, bl in RESAMP:
         n_in = nb * 192 // bl * bl                                     # about as many input samples as one MULTI channel
@@ -51,65 +52,24 @@ def child(a):
         xf = torch.empty((n_in, 2), dtype=torch.float32, device="cuda:0")
         fe = trxhip.RxFrontEnd(trx, bl, p, q, chans=1, mode="resamp")
         keep.append(fe)
-        legs["resamp_%s_one_pass" % tag] = (lambda fe=fe, x=x, y=y, n=n_in // bl: trxhip._check(
+        legs["resamp_%s_one_pass" % tag] = (None, lambda fe=fe, x=x, y=y, n=n_in // bl: trxhip._check(
             L.trxhip_rx_frontend_pull(fe.h, ptr(x), n, ptr(y), y.numel(), st), "pull"))
 
         def two(x=x, xf=xf, y=y, n_in=n_in, p=p, q=q):
             trxhip._check(L.trxhip_convert_short_float(trx.h, ptr(xf), ptr(x), 2 * n_in, st), "convert")
             trxhip._check(L.trxhip_resample_batch(trx.h, ptr(xf), ptr(y), n_in, p, q, 1, n_in, y.numel(), st), "resample")
-        legs["resamp_%s_two_calls" % tag] = two
-    names = list(legs)
-    if a.round % 2:
-        names.reverse()
-    res = {}
-    for name in names:
-        f = legs[name]
-        for _ in range(a.warmup):
-            f()
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(a.reps):
-            f()
-        ev[1].record()
-        torch.cuda.synchronize()
-        res[name] = ev[0].elapsed_time(ev[1]) / a.reps
-    print(json.dumps(res), flush=True)
+        legs["resamp_%s_two_calls" % tag] = (None, two)
+    print(json.dumps(br.time_in_order(torch, legs, br.select_legs(legs, a.legs), a)), flush=True)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=1 << 18)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per round")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rx_frontend_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    a = ap.parse_args()
-    if a.round is not None:
-        return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    import measure
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg = {}
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, "rx_frontend_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), [sys.executable, os.path.abspath(__file__), "--round", str(r), "--blocks", str(a.blocks),
-                                            "--warmup", str(a.warmup), "--reps", str(a.reps)], log, a.timeout)
-        for k, v in measure.last_json(log).items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
+def summarise(per_leg, a):
     nb = a.blocks
     res = {"workload": "rx_frontend", "blocks": nb, "rounds": a.rounds, "reps": a.reps, "peak_bytes_per_s": PEAK, "legs": {}}
 
     def leg(name, n_bytes, extra):
         xs = per_leg[name]
-        med = statistics.median(xs)
-        res["legs"][name] = dict(extra, median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs],
-                                 bytes=n_bytes, frac_of_8tbs=round(n_bytes / (med * 1e-3) / PEAK, 3))
+        res["legs"][name] = dict(extra, **br.leg_summary(xs, bytes=n_bytes,
+                                                         frac_of_8tbs=round(n_bytes / (statistics.median(xs) * 1e-3) / PEAK, 3)))
     for name, rows in (("four_rows", 4), ("chans3", 3), ("chans2", 2), ("chans1", 1)):
         leg("multi_" + name, nb * (3072 + rows * 260 * 8), {"rows": rows, "bytes_per_block": 3072 + rows * 260 * 8})
     for tag, p, q, bl in RESAMP:
@@ -123,9 +83,18 @@ def main():
         d = L["resamp_%s_one_pass" % tag]["median_ms"] - L["resamp_%s_two_calls" % tag]["median_ms"]
         res["resamp_%s_one_pass_minus_two_calls_ms" % tag] = round(d, 4)
         res["resamp_%s_within_two_calls_spread" % tag] = d <= L["resamp_%s_two_calls" % tag]["spread_ms"]
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--blocks", type=int, default=1 << 18)
+    br.add_options(ap, "rx_frontend", warmup=5, reps=20, timeout=240)
+    a = ap.parse_args()
+    if a.round is not None:
+        return child(a)
+    res = summarise(br.run_rounds("rx_frontend", [sys.executable, os.path.abspath(__file__), "--blocks", str(a.blocks)], a), a)
+    br.write_json(a.out, res)
     print(json.dumps(res), flush=True)
 
 

@@ -18,18 +18,16 @@ under the key "sps1" of the same file and the 4-SPS entries stay.
 
    python3 tools/bench_rx_sched.py [--sps 4|1] [--rounds 5] [--slots N] [--warmup W] [--reps R] [--timeout S] [--no-trace] [--out FILE]"""
 import argparse
-import csv
 import ctypes as C
-import glob
 import json
 import os
-import shutil
 import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 TSC = 0
 
@@ -96,91 +94,38 @@ def child(a):
         pull(total + 1)                                                # leaves one sample: the next pulls of `total` cut n slots each
 
     legs = {"two_calls": (None, two_calls), "pull": (start_steady, pull_steady), "pull_aligned": (None, pull_aligned)}
-    names = [k for k in legs if not a.legs or k in a.legs.split(",")]
-    if a.round % 2:
-        names.reverse()
-    out = {}
-    for name in names:
-        prep, f = legs[name]
-        if prep:
-            prep()
-        for _ in range(a.warmup):
-            f()
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(a.reps):
-            f()
-        ev[1].record()
-        torch.cuda.synchronize()
-        out[name] = ev[0].elapsed_time(ev[1]) / a.reps
-    print(json.dumps(out), flush=True)
+    print(json.dumps(br.time_in_order(torch, legs, br.select_legs(legs, a.legs), a)), flush=True)
 
 
-def trace_rows(d):
-    """{kernel: {calls, avg_us}} of a rocprofv3 --kernel-trace --stats directory"""
-    rows = {}
-    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-        with open(path, newline="") as f:
-            for r in csv.DictReader(f):
-                name = r["Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0].strip()
-                rows[name] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2)}
-    return rows
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--sps", type=int, default=4, choices=(4, 1))
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--slots", type=int, default=1 << 18)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per round")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rx_sched_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.round is not None:
-        return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    if a.sps == 1 and a.slots % 8:
-        ap.error("--sps 1: whole frames (the steady-state pull starts at TN 0 every time)")
-    import measure
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg = {}
-    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--sps", str(a.sps)]
-    tag = "rx_sched" if a.sps == 4 else "rx_sched_sps1"
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, tag + "_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--warmup", str(a.warmup), "--reps", str(a.reps)], log, a.timeout)
-        for k, v in measure.last_json(log).items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
+def summarise(per_leg, a):
     n = a.slots
     res = {"workload": "rx_sched", "sps": a.sps, "slots": n, "chans": 1, "rounds": a.rounds, "reps": a.reps, "legs": {}}
     if a.sps == 4:
         del res["sps"]
     for name, xs in per_leg.items():
-        med = statistics.median(xs)
-        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs],
-                                 ns_per_slot=round(med * 1e6 / n, 2))
+        res["legs"][name] = br.leg_summary(xs, ns_per_slot=round(statistics.median(xs) * 1e6 / n, 2))
     two = res["legs"]["two_calls"]["median_ms"]
     for name in ("pull", "pull_aligned"):
         res[name + "_minus_two_calls_ms"] = round(res["legs"][name]["median_ms"] - two, 4)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sps", type=int, default=4, choices=(4, 1))
+    ap.add_argument("--slots", type=int, default=1 << 18)
+    br.add_options(ap, "rx_sched", warmup=3, reps=10, timeout=240, trace="off")
+    a = ap.parse_args()
+    if a.round is not None:
+        return child(a)
+    if a.sps == 1 and a.slots % 8:
+        ap.error("--sps 1: whole frames (the steady-state pull starts at TN 0 every time)")
+    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--sps", str(a.sps)]
+    tag = "rx_sched" if a.sps == 4 else "rx_sched_sps1"
+    res = summarise(br.run_rounds(tag, me, a), a)
     if not a.no_trace:
-        d = os.path.join(a.logs, tag + "_trace")
-
-        def trace(legs):
-            shutil.rmtree(d, ignore_errors=True)
-            measure.step("kernel trace", ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "rx_sched", "--"] +
-                         me + ["--round", "0", "--warmup", "1", "--reps", "3", "--legs", legs], os.path.join(a.logs, tag + "_trace.log"),
-                         a.timeout)
-            return trace_rows(d)
-
-        rows = trace("pull")
+        n, small = a.slots, ["--warmup", "1", "--reps", "3"]
+        rows = br.kernel_trace(tag, me, small, "pull", a)
         res["kernel_trace_us"] = {k: v for k, v in sorted(rows.items()) if k.startswith(("rx_", "pack_trxd_wire", "nb_pull4", "burst_pull4", "burst_pull_"))}
         new = sum(v["avg_us"] for k, v in rows.items() if k.startswith("rx_"))
         res["new_kernels_us_per_pull"] = round(new, 2)
@@ -191,25 +136,18 @@ def main():
             spread = max(res["legs"]["pull"]["spread_ms"], res["legs"]["two_calls"]["spread_ms"])
             res["allowed_excess_ms"] = round(new / 1e3 + spread, 4)
             res["within_allowance"] = res["pull_minus_two_calls_ms"] <= res["allowed_excess_ms"]
-            both = trace("pull_aligned,two_calls")
+            both = br.kernel_trace(tag, me, small, "pull_aligned,two_calls", a)
             res["stream_vs_row_kernel_us"] = {k: both[k] for k in ("burst_pull_stream_kernel<false>", "burst_pull_kernel<1, false, 3>")}
             res["stream_vs_row_kernel_ns_per_slot"] = [round(v["avg_us"] * 1e3 / n, 3) for v in res["stream_vs_row_kernel_us"].values()]
-        shutil.rmtree(d, ignore_errors=True)
-    out = res
-    if a.sps == 1:                                                         # under a key of its own: the 4-SPS entries stay
-        out = {}
-        if os.path.exists(a.out):
-            with open(a.out) as f:
-                out = json.load(f)
-        out["sps1"] = res
-    elif os.path.exists(a.out):
+    old = {}
+    if os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
-        if "sps1" in old:
-            out = dict(res, sps1=old["sps1"])
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    if a.sps == 1:                                                         # under a key of its own: the 4-SPS entries stay
+        out = dict(old, sps1=res)
+    else:
+        out = dict(res, sps1=old["sps1"]) if "sps1" in old else res
+    br.write_json(a.out, out)
     print(json.dumps(res), flush=True)
 
 

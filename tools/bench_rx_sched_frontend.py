@@ -16,13 +16,13 @@ import argparse
 import ctypes as C
 import json
 import os
-import shutil
 import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 CHANS, TSC = 3, 0
 
@@ -70,39 +70,33 @@ def child(a):
         trxhip._check(L.trxhip_rx_sched_pull_frontend(sj.h, fej.h, ptr(wide), nb, ptr(work), work.shape[1], ptr(pkt), 160, ptr(plen),
                                                       ptr(ind), ptr(soft), cap, None, None, st), "pull_frontend")
 
-    legs = {"two_calls": two_calls, "pull_frontend": pull_frontend}
-    names = [k for k in legs if not a.legs or k in a.legs.split(",")]
-    if a.round % 2:
-        names.reverse()
-    out = {}
-    for name in names:
-        f = legs[name]
-        for _ in range(max(a.warmup, 1)):                              # the first pull leaves the remainder the others find
-            f()
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(a.reps):
-            f()
-        ev[1].record()
-        torch.cuda.synchronize()
-        out[name] = ev[0].elapsed_time(ev[1]) / a.reps
-    out["order"] = names
+    legs = {"two_calls": (None, two_calls), "pull_frontend": (None, pull_frontend)}
+    a.warmup = max(a.warmup, 1)                                        # the first pull leaves the remainder the others find
+    out = br.time_in_order(torch, legs, br.select_legs(legs, a.legs), a)
+    out["order"] = list(out)
     print(json.dumps(out), flush=True)
+
+
+def summarise(per_leg, a):
+    per_leg = dict(per_leg)
+    by_pos = {}
+    for r, order in enumerate(per_leg.pop("order")):                   # the leg a process times first pays for its first touches
+        for pos, k in enumerate(order):
+            by_pos.setdefault(k, {}).setdefault(("first", "second")[pos], []).append(round(per_leg[k][r], 4))
+    res = {"workload": "rx_sched_frontend", "mode": "MULTI", "chans": CHANS, "blocks": a.blocks, "samples_per_chan": a.blocks * 260,
+           "rounds": a.rounds, "reps": a.reps, "legs": {name: br.leg_summary(xs) for name, xs in per_leg.items()}}
+    res["pull_frontend_minus_two_calls_ms"] = round(res["legs"]["pull_frontend"]["median_ms"] - res["legs"]["two_calls"]["median_ms"], 4)
+    res["larger_spread_ms"] = max(v["spread_ms"] for v in res["legs"].values())
+    res["no_slower_beyond_spread"] = res["pull_frontend_minus_two_calls_ms"] <= res["larger_spread_ms"]
+    res["by_position_ms"] = by_pos                                     # the legs alternate: compare like with like
+    res["by_position_median_ms"] = {k: {w: round(statistics.median(xs), 4) for w, xs in v.items()} for k, v in by_pos.items()}
+    return res
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--blocks", type=int, default=1 << 18, help="192-step blocks per pull")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=None)
-    ap.add_argument("--reps", type=int, default=None)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per round")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rx_sched_frontend_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    br.add_options(ap, "rx_sched_frontend", warmup=None, reps=None, timeout=240, trace="off")
     a = ap.parse_args()
     small = a.blocks < 4096
     if a.warmup is None:
@@ -111,53 +105,21 @@ def main():
         a.reps = 500 if small else 10
     if a.round is not None:
         return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    import measure
-    from bench_rx_sched import trace_rows
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg, by_pos = {}, {}
     me = [sys.executable, os.path.abspath(__file__), "--blocks", str(a.blocks)]
     tag = "rx_sched_frontend_%d" % a.blocks
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, tag + "_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--warmup", str(a.warmup), "--reps", str(a.reps)], log, a.timeout)
-        line = measure.last_json(log)
-        for pos, k in enumerate(line.pop("order")):                    # the leg a process times first pays for its first touches
-            by_pos.setdefault(k, {}).setdefault(("first", "second")[pos], []).append(round(line[k], 4))
-        for k, v in line.items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
-    res = {"workload": "rx_sched_frontend", "mode": "MULTI", "chans": CHANS, "blocks": a.blocks, "samples_per_chan": a.blocks * 260,
-           "rounds": a.rounds, "reps": a.reps, "legs": {}}
-    for name, xs in per_leg.items():
-        med = statistics.median(xs)
-        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs])
-    res["pull_frontend_minus_two_calls_ms"] = round(res["legs"]["pull_frontend"]["median_ms"] - res["legs"]["two_calls"]["median_ms"], 4)
-    res["larger_spread_ms"] = max(v["spread_ms"] for v in res["legs"].values())
-    res["no_slower_beyond_spread"] = res["pull_frontend_minus_two_calls_ms"] <= res["larger_spread_ms"]
-    res["by_position_ms"] = by_pos                                     # the legs alternate: compare like with like
-    res["by_position_median_ms"] = {k: {w: round(statistics.median(xs), 4) for w, xs in v.items()} for k, v in by_pos.items()}
+    res = summarise(br.run_rounds(tag, me, a), a)
     if not a.no_trace:
-        d = os.path.join(a.logs, tag + "_trace")
         res["kernel_trace_us"] = {}
         for leg in ("pull_frontend", "two_calls"):
-            shutil.rmtree(d, ignore_errors=True)
-            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o",
-                                                 "rx_sched_frontend", "--"] + me + ["--round", "0", "--warmup", "1", "--reps", "3", "--legs", leg],
-                         os.path.join(a.logs, tag + "_trace_%s.log" % leg), a.timeout)
-            rows = trace_rows(d)
+            rows = br.kernel_trace(tag, me, ["--warmup", "1", "--reps", "3"], leg, a)
             res["kernel_trace_us"][leg] = {k: v for k, v in sorted(rows.items()) if k.startswith(
                 ("rx_", "frontend_fused", "save_wide_hist", "pack_trxd_wire", "burst_pull4", "burst_pull_"))}
-        shutil.rmtree(d, ignore_errors=True)
     out = {}
     if os.path.exists(a.out):
         with open(a.out) as f:
             out = json.load(f)
     out["blocks_%d" % a.blocks] = res
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    br.write_json(a.out, out)
     print(json.dumps(res), flush=True)
 
 

@@ -19,13 +19,13 @@ import argparse
 import ctypes as C
 import json
 import os
-import shutil
 import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 TSC = 0
 SMALL = 8
@@ -92,77 +92,38 @@ def child(a):
             s.set_clock(0, 0)
             pull(total + 1)                                            # leaves one sample: the next pulls of `total` cut n slots each
 
-        legs = [("composition", None, composition), ("pull", start_steady, pull)]
-        if a.round % 2:
-            legs.reverse()
-        reps = a.reps if n == big else 20 * a.reps
-        r = {}
-        for name, prep, f in legs:
-            if prep:
-                prep()
-            for _ in range(a.warmup):
-                f()
-            torch.cuda.synchronize()
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            for _ in range(reps):
-                f()
-            ev[1].record()
-            torch.cuda.synchronize()
-            r[name] = ev[0].elapsed_time(ev[1]) / reps
-        out["%s_%d" % (fmt, n)] = r
+        legs = {"composition": (None, composition), "pull": (start_steady, pull)}
+        out["%s_%d" % (fmt, n)] = br.time_in_order(torch, legs, list(legs), a, reps=a.reps if n == big else 20 * a.reps)
         s.close()
         del shift, cf, x, rows
     print(json.dumps(out), flush=True)
 
 
+def summarise(per, a):
+    """per: {"<fmt>_<slots>": [{leg: ms} per round]}"""
+    res = {"workload": "rx_sched_va", "chans": 1, "rounds": a.rounds, "reps": a.reps, "cases": {}}
+    for case, rounds in per.items():
+        n = int(case.split("_")[1])
+        c = {"slots": n, "legs": {}}
+        for name in rounds[0]:
+            xs = [r[name] for r in rounds]
+            c["legs"][name] = br.leg_summary(xs, ns_per_slot=round(statistics.median(xs) * 1e6 / n, 2))
+        c["pull_minus_composition_ms"] = round(c["legs"]["pull"]["median_ms"] - c["legs"]["composition"]["median_ms"], 4)
+        res["cases"][case] = c
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--slots", type=int, default=1 << 18)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per round")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rx_sched_va_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
+    br.add_options(ap, "rx_sched_va", warmup=2, reps=5, timeout=240, trace="off")
     a = ap.parse_args()
     if a.round is not None:
         return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    import measure
-    from bench_rx_sched import trace_rows
-    os.makedirs(a.logs, exist_ok=True)
-    per = {}
     me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots)]
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, "rx_sched_va_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--warmup", str(a.warmup), "--reps", str(a.reps)], log, a.timeout)
-        for case, legs in measure.last_json(log).items():
-            for k, v in legs.items():
-                per.setdefault(case, {}).setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
-    res = {"workload": "rx_sched_va", "chans": 1, "rounds": a.rounds, "reps": a.reps, "cases": {}}
-    for case, legs in per.items():
-        n = int(case.split("_")[1])
-        c = {"slots": n, "legs": {}}
-        for name, xs in legs.items():
-            med = statistics.median(xs)
-            c["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs],
-                                   ns_per_slot=round(med * 1e6 / n, 2))
-        c["pull_minus_composition_ms"] = round(c["legs"]["pull"]["median_ms"] - c["legs"]["composition"]["median_ms"], 4)
-        res["cases"][case] = c
+    res = summarise(br.run_rounds("rx_sched_va", me, a), a)
     if not a.no_trace:
-        d = os.path.join(a.logs, "rx_sched_va_trace")
-        shutil.rmtree(d, ignore_errors=True)
-        big = "s16_%d,cf32_%d" % (a.slots, a.slots)
-        measure.step("kernel trace", ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "rx_sched_va", "--"] +
-                     me + ["--round", "0", "--warmup", "1", "--reps", "3", "--legs", big], os.path.join(a.logs, "rx_sched_va_trace.log"),
-                     a.timeout)
-        rows = trace_rows(d)
+        rows = br.kernel_trace("rx_sched_va", me, ["--warmup", "1", "--reps", "3"], "s16_%d,cf32_%d" % (a.slots, a.slots), a)
         keep = ("rx_", "va_demod", "energy_detect", "convert_short", "diversity_power", "pack_trxd_wire", "nb_pull4", "burst_pull4")
         res["kernel_trace_us"] = {k: v for k, v in sorted(rows.items()) if k.startswith(keep)}
         # the two new kernels' own durations as shares of the large pull of their format (the detect kernels, the packer and the
@@ -174,10 +135,7 @@ def main():
                 if k.startswith("rx_va_") and t in k:
                     shares[k] = dict(avg_us=v["avg_us"], share_of_pull=round(v["avg_us"] / 1e3 / pull_ms, 4))
         res["new_kernels"] = shares
-        shutil.rmtree(d, ignore_errors=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    br.write_json(a.out, res)
     print(json.dumps(res), flush=True)
 
 

@@ -16,15 +16,13 @@ resource report go to profiles/sch_sync_bench.json.
 import argparse
 import json
 import os
-import re
-import shutil
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_rounds as br   # noqa: E402
 
 ACQ_LEN = 60000
 
@@ -74,23 +72,10 @@ def child(a):
         trxhip._check(L.trxhip_demod_va_batch_cf32(trx.h, ptr(slots), ptr(d_params), None, ptr(soft), ptr(starts), a.slots, 625,
                                                    1.0 / 16383.0, 156, 0, st), "va")
 
-    legs = {"track": track, "acq": acq, "detect_full": detect_full, "detect_buffer": detect_buffer, "va_demod": va_demod}
-    names = [k for k in legs if not a.legs or k in a.legs.split(",")]
-    if a.round % 2:
-        names.reverse()
-    out = {}
-    for name in names:
-        f = legs[name]
-        for _ in range(a.warmup):
-            f()
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(a.reps):
-            f()
-        ev[1].record()
-        torch.cuda.synchronize()
-        out[name] = ev[0].elapsed_time(ev[1]) / a.reps
+    legs = {"track": (None, track), "acq": (None, acq), "detect_full": (None, detect_full), "detect_buffer": (None, detect_buffer),
+            "va_demod": (None, va_demod)}
+    names = br.select_legs(legs, a.legs)
+    out = br.time_in_order(torch, legs, names, a)
     # the timed calls decoded what was sent
     r = rec_s.cpu().numpy().reshape(-1).view(trxhip.SCH_SYNC_DTYPE)[:base.shape[0]]
     rb = rec_b.cpu().numpy().reshape(-1).view(trxhip.SCH_SYNC_DTYPE)[:bbase.shape[0]]
@@ -101,75 +86,32 @@ def child(a):
     print(json.dumps(out), flush=True)
 
 
-def resource_usage():
-    """{kernel: {VGPRs, SGPRs spill, VGPRs spill, scratch bytes/lane, LDS bytes/block, occupancy}} from tools/resource_usage.sh"""
-    txt = subprocess.run(["bash", os.path.join(ROOT, "tools", "resource_usage.sh"), "trx_sch_sync.hip", "sch_"], stdout=subprocess.PIPE,
-                         text=True, check=True).stdout
-    out, cur = {}, None
-    keys = {"VGPRs": "vgprs", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
-            "LDS Size [bytes/block]": "lds_bytes_per_block", "Occupancy [waves/SIMD]": "occupancy_waves_per_simd"}
-    for line in txt.splitlines():
-        m = re.match(r"Function Name: (\S+)", line)
-        if m:
-            name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, text=True).stdout.strip() or m.group(1)
-            cur = out.setdefault(name.split("(")[0].replace("void ", ""), {})
-            continue
-        m = re.match(r"\s+([^:]+): (\d+)$", line)
-        if m and cur is not None and m.group(1) in keys:
-            cur[keys[m.group(1)]] = int(m.group(2))
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--slots", type=int, default=1 << 18)
-    ap.add_argument("--bufs", type=int, default=256)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per round")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sch_sync_bench.json"))
-    ap.add_argument("--logs", default=os.path.join(ROOT, "build", "measure"))
-    ap.add_argument("--round", type=int, default=None, help=argparse.SUPPRESS)     # child: run one round on the GPU
-    ap.add_argument("--legs", default="", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.round is not None:
-        return child(a)
-    if a.rounds < 5:
-        ap.error("at least five rounds")
-    import measure
-    from bench_rx_sched import trace_rows
-    os.makedirs(a.logs, exist_ok=True)
-    per_leg = {}
-    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--bufs", str(a.bufs)]
-    for r in range(a.rounds):
-        log = os.path.join(a.logs, "sch_sync_round_%d.log" % (r + 1))
-        measure.step("round %d" % (r + 1), me + ["--round", str(r), "--warmup", str(a.warmup), "--reps", str(a.reps)], log, a.timeout)
-        for k, v in measure.last_json(log).items():
-            per_leg.setdefault(k, []).append(v)
-        print("round %d done" % (r + 1), flush=True)
+def summarise(per_leg, a):
     units = {"track": a.slots, "detect_full": a.slots, "va_demod": a.slots, "acq": a.bufs, "detect_buffer": a.bufs}
     res = {"workload": "sch_sync", "slots": a.slots, "slot_len": 625, "bufs": a.bufs, "buf_len": ACQ_LEN, "rounds": a.rounds,
            "reps": a.reps, "legs": {}}
     for name, xs in per_leg.items():
-        med = statistics.median(xs)
-        res["legs"][name] = dict(median_ms=round(med, 4), spread_ms=round(max(xs) - min(xs), 4), ms=[round(x, 4) for x in xs],
-                                 us_per_unit=round(med * 1e3 / units[name], 4))
+        res["legs"][name] = br.leg_summary(xs, us_per_unit=round(statistics.median(xs) * 1e3 / units[name], 4))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--slots", type=int, default=1 << 18)
+    ap.add_argument("--bufs", type=int, default=256)
+    br.add_options(ap, "sch_sync", warmup=2, reps=5, timeout=240, trace="off")
+    a = ap.parse_args()
+    if a.round is not None:
+        return child(a)
+    me = [sys.executable, os.path.abspath(__file__), "--slots", str(a.slots), "--bufs", str(a.bufs)]
+    res = summarise(br.run_rounds("sch_sync", me, a), a)
     if not a.no_trace:
-        d = os.path.join(a.logs, "sch_sync_trace")
         res["kernel_trace_us"] = {}
         for leg in ("track", "acq"):                                       # one trace per mode: both run sch_sync_demod_kernel
-            shutil.rmtree(d, ignore_errors=True)
-            measure.step("kernel trace " + leg, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o",
-                                                 "sch_sync", "--"] + me + ["--round", "0", "--warmup", "1", "--reps", "3", "--legs", leg],
-                         os.path.join(a.logs, "sch_sync_trace_%s.log" % leg), a.timeout)
-            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(trace_rows(d).items()) if k.startswith("sch_")}
-        shutil.rmtree(d, ignore_errors=True)
-    res["resource_usage"] = resource_usage()
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+            rows = br.kernel_trace("sch_sync", me, ["--warmup", "1", "--reps", "3"], leg, a)
+            res["kernel_trace_us"][leg] = {k: v for k, v in sorted(rows.items()) if k.startswith("sch_")}
+    res["resource_usage"] = br.resource_usage("trx_sch_sync.hip", "sch_")
+    br.write_json(a.out, res)
     print(json.dumps(res), flush=True)
 
 

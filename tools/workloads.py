@@ -12,7 +12,8 @@ bursts as complex64), exact (normal, exact demodulator), va (normal, Viterbi alt
 bursts spread over 60 symbols of delay, max_toa 63 / 112: the windowed path), mixed_blocked (mixed, the access bursts moved
 to the end of the batch).  Others: sch_full (detectSCHBurst FULL, 16384 x 625 samples), sch_buffer (BUFFER search,
 256 x 60000 samples), frontend (configs[3]: channelizer, resampler and the fused front end over 256 Ki blocks), tx_frontend
-(the transmit front end: 3 logical channels through trxhip_tx_frontend_push to int16, 256 Ki blocks of 260 samples)."""
+(the transmit front end: 3 logical channels through trxhip_tx_frontend_push to int16, 256 Ki blocks of 260 samples).
+multiframe(): the 51-multiframe of a cell behind the MS-side benches (tools/bench_ms_*.py)."""
 import argparse
 import json
 import os
@@ -26,6 +27,8 @@ from osmo_trx_amd import TrxHip, synth, trxhip
 NAMES = ("normal", "rach", "ext", "mixed", "edge", "1sps", "cf32", "exact", "va", "nb_toa63", "nb_toa112", "mixed_blocked",
          "sch_full", "sch_buffer", "frontend", "tx_frontend")
 DEFAULT_N = {"sch_full": 16384, "sch_buffer": 256, "frontend": 1 << 18, "tx_frontend": 1 << 18}
+TSC = 5                                 # the cell of multiframe()
+BSIC = 0o52
 
 
 def make(name, n, device="cuda:0", seed=None):
@@ -98,6 +101,27 @@ def launcher(trx, name, iq, params, kw, hint=False):
     soft = torch.empty((iq.shape[0], kw["soft_stride"]), dtype=torch.float32, device=iq.device)
     h = trxhip.few_nb_hint(params) if hint else None
     return lambda: trx.detect_demod(iq, dp, results=res, soft=soft, hint=h, **kw)
+
+
+def multiframe(trx, base_fn, seed=7):
+    """One 51-multiframe of a cell as the radio delivers it: (int16[408, 625, 2] on the GPU, MS_SLOT_DTYPE[408], sent bits
+    uint8[408, 148], kinds).  SCH and normal bursts come through the product's own modulator; FCCH slots hold a random burst."""
+    rng = np.random.default_rng(seed)
+    fns = np.repeat(np.arange(base_fn, base_fn + 51), 8)
+    tns = np.tile(np.arange(8), 51)
+    kinds = np.array([trxhip.ms_slot_kind(int(f), int(t)) for f, t in zip(fns, tns)])
+    sent = rng.integers(0, 2, (408, 148), dtype=np.uint8)
+    sent[:, :3] = 0
+    sent[:, -3:] = 0
+    sent[:, 61:87] = [int(c) for c in synth.TSC_BITS[TSC]]
+    for b in np.nonzero(kinds == trxhip.MS_KIND_SCH)[0]:
+        sent[b] = synth.sch_burst_bits(BSIC, int(fns[b]))
+    p = np.zeros(408, dtype=trxhip.TX_PARAMS_DTYPE)
+    p["nbits"], p["guard"], p["scale_re"] = 148, 8, 1.0
+    _, iq, _ = trx.modulate(torch.from_numpy(sent).to("cuda:0"), trx.tx_params_tensor(p), sps=4, cf32=False, s16_scale=1400.0)
+    slots = np.zeros(408, dtype=trxhip.MS_SLOT_DTYPE)
+    slots["fn"], slots["tn"], slots["tsc"], slots["flags"] = fns, tns, TSC, trxhip.MS_SLOT_ACTIVE
+    return iq, slots, sent, kinds
 
 
 def main():
