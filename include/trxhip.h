@@ -1146,6 +1146,76 @@ int  trxhip_ms_agc_group_set_gain(trxhip_ms_group *g, uint32_t member, float rx_
 int  trxhip_ms_agc_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_agc_status *out);
 int  trxhip_ms_agc_group_feed_levels(trxhip_ms_group *g, uint32_t member, const float *levels, size_t n);   /* plan-only groups */
 
+/* ---- MS-side FCCH frequency-offset measurement (AFC) on the device -----------------------------------------------------------
+ * The estimator the reference ships for the FCCH slot and never calls: gsm_fcch_offset() with ac_sum_with_lag() and pinv()
+ * (ms/sch.c:255-314), restated literally on the slot's 625 samples after convert_and_scale by 1.f / rx_full_scale -- the float
+ * samples ms_rx_kernel makes for a traffic slot; complex64 samples need no conversion and are multiplied by the same factor, as
+ * trxhip_ms_rx_batch_cf32() does:
+ *   start = 3 * 4 + 10 * 4 = 52, L1 = 3, L2 = 32, N1 = N2 = 92 (:206, :255-258, :292)
+ *   v_L = sum over s < 92 of x[52 + L + s] * conj(x[52 + s]) (:273-279): samples 52 .. 175 are read and no others
+ *   alpha_L = cargf(v_L); P = roundf((L1 * alpha_two - L2 * alpha_one) / (2 * M_PI)) (:293-297)
+ *   (r, s): the first pair with P == 32 * i - 3 * j, i < 3, j < 32, or (0, 0) (:262-270, :299-300)
+ *   omegal1 = (alpha_one + 2 * M_PI * r) / 3, omegal2 = (alpha_two + 2 * M_PI * s) / 32 (:302-303)
+ *   reval = GSM_SYM_RATE / (2 * M_PI) * (expected_fcch_val - (omegal1 + omegal2) / 2); the result is -reval (:308, :313)
+ * with the reference's types at every step: the float locals, the double M_PI sub-expressions, fs = 13. / 48. * 1e6 * 4 as a
+ * float, expected_fcch_val = ((2 * M_PI) / fs) * 67700 (67700, not 67708.33: a tone exactly on the FCCH frequency reads
+ * +8.33 Hz).  Only the order of the 92 additions differs (one wave per slot, a cross-lane reduction).  An all-zero slot has
+ * atan2f(0, 0) = 0 for both angles and follows from that.  The range is about -85 .. +90 kHz; below it the estimate aliases.
+ * Deliberately not reproduced: gsm_fcch_offset() also calls org_gsm_fcch_offset() (:305), whose value is discarded and which
+ *   multiplies the caller's burst by a reference tone in place -- the input is never written here; the len > GSM_MAX_BURST_LEN
+ *   clamp (:289-290) has no effect at 625.
+ * mag_one, mag_two and energy are defined here, not by the reference, which has no validity test: mag_one / energy is near 1 on
+ *   a tone and near 0 on noise, and is the caller's to threshold.
+ * trxhip_ms_fcch_batch_*(): row r = the 625 samples at d_iq + r * slot_stride samples -> d_out[r].  The arguments are those of
+ *   trxhip_ms_rx_batch_*(): slot_stride >= 625, n_slots 1 .. 2^31 - 1, rx_full_scale finite and positive; int16 rows are 4-byte
+ *   aligned only (complex64: 8), d_out 4-byte aligned; else TRXHIP_EINVAL.  The int16 conversion happens in the load.
+ * A scheduler member with AFC on (trxhip_ms_afc_sched_set / trxhip_ms_afc_group_set: {enable, d_fcch}; the single object's
+ *   calls are those of member 0 of a group of one): every pull, int16 or complex64, measures the FCCH slots it cuts, ACTIVE or
+ *   not (the policy the lower layer has for SCH slots), on exactly the 625 samples the receiver sees -- the slot assembled
+ *   across two pulls and a slot that begins in the carried partial slot included -- and slot k of member m goes to
+ *   d_fcch[m * out_stride + k] where d_fcch is given (4-byte aligned; the single object: d_fcch[k]); entries of other slots are
+ *   not touched.  Per member on the device: the count of FCCH slots measured, the last record, and the last TRXHIP_MS_AFC_RING
+ *   {fn, hz, mag_one, energy}.  _set leaves the state alone; set_clock and acquire do not touch it; a refused pull moves none
+ *   of it.  Nothing is fed back into the stream: there is no oscillator here to steer, temp_ts_corr_offset stays the only
+ *   feedback.  Issued per pull in which a member with AFC on cuts an FCCH slot: one launch (a wave per FCCH slot, found by
+ *   arithmetic on the pull's clock) and one event record behind the pull's own; 64 bytes per such member ride in the pull's
+ *   table; no wait, no copy.  With AFC off everywhere a pull issues what it issued before.  _set and _state wait for the AFC
+ *   launches in flight.  _state: ring[0 .. n_records) oldest first.  Plan-only objects have no samples: _set is TRXHIP_EINVAL. */
+#define TRXHIP_MS_AFC_RING 8
+typedef struct {            /* 32 bytes */
+	float hz;               /* -reval: the carrier offset in Hz, + = received tone above 67.7 kHz */
+	float alpha_one, alpha_two;
+	float mag_one, mag_two; /* |v_L1|, |v_L2| */
+	float energy;           /* sum over s < 92 of |x[52 + s]|^2: mag_one / energy is the caller's tone test */
+	int16_t p;              /* P */
+	int8_t r, s;
+	uint32_t reserved;      /* zero */
+} trxhip_ms_fcch;
+typedef struct trxhip_ms_afc_cfg {  /* 16 bytes */
+	int32_t enable;
+	int32_t reserved;
+	trxhip_ms_fcch *d_fcch;  /* device, may be NULL */
+} trxhip_ms_afc_cfg;
+typedef struct trxhip_ms_afc_entry {  /* 16 bytes: one measured FCCH slot */
+	uint32_t fn;
+	float hz, mag_one, energy;
+} trxhip_ms_afc_entry;
+typedef struct trxhip_ms_afc_status {  /* 176 bytes */
+	uint64_t count;          /* FCCH slots measured */
+	uint32_t n_records;
+	uint8_t  enable, reserved[3];
+	trxhip_ms_fcch last;     /* zero while count == 0 */
+	trxhip_ms_afc_entry ring[TRXHIP_MS_AFC_RING];
+} trxhip_ms_afc_status;
+int  trxhip_ms_fcch_batch_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t slot_stride, trxhip_ms_fcch *d_out, size_t n_slots,
+			      float rx_full_scale, void *stream);
+int  trxhip_ms_fcch_batch_cf32(trxhip_ctx *ctx, const float *d_iq_cf32, size_t slot_stride, trxhip_ms_fcch *d_out, size_t n_slots,
+			       float rx_full_scale, void *stream);
+int  trxhip_ms_afc_sched_set(trxhip_ms_sched *s, const trxhip_ms_afc_cfg *cfg);
+int  trxhip_ms_afc_sched_state(trxhip_ms_sched *s, trxhip_ms_afc_status *out);
+int  trxhip_ms_afc_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_afc_cfg *cfg);
+int  trxhip_ms_afc_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_afc_status *out);
+
 /* ---- The MS-side uplink burst scheduler: burst requests in, the radio's transmit sample stream out --------------------------
  * What the reference does between trxcon's burst request and the radio: upper_trx::driveTx() (ms/ms_upper.cpp:306-355),
  * ms_trx::submit_burst() (ms/ms.cpp:114-160), set_ta() (ms/ms.h:299-303) and submit_burst_ts() (ms/uhd_specific.h:260-269,

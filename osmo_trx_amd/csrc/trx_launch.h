@@ -96,6 +96,16 @@ int trx_launch_ms_level_rows(const int16_t *d_in, size_t n_rows, size_t row_len,
 int trx_launch_ms_agc(const struct trx_agc_entry *h_entry, const struct trx_agc_entry *d_tab, size_t n_entries, size_t n_waves,
 		      size_t n_pieces, uint32_t full_scale, hipStream_t stream);
 
+/* trx_ms_afc.hip: the MS-side FCCH frequency-offset measurement.  _fcch_rows: gsm_fcch_offset() of n_slots rows of 625 samples
+ * (int16 pairs or complex64), slot_stride samples apart.  _afc: the one launch of a pull with AFC on (trx_ms_afc.h) -- n_waves
+ * FCCH slots, one per wave -- over the one job h_job, passed as a kernel argument (d_tab unused), or over the n_jobs jobs of
+ * d_tab (h_job NULL) */
+struct trx_afc_job;
+int trx_launch_ms_fcch_rows(const void *d_iq, int i16, size_t slot_stride, trxhip_ms_fcch *d_out, size_t n_slots, float scale,
+			    hipStream_t stream);
+int trx_launch_ms_afc(const struct trx_afc_job *h_job, const struct trx_afc_job *d_tab, int i16, size_t n_jobs, size_t n_waves,
+		      float scale, hipStream_t stream);
+
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,
 			 size_t n_bursts, float rssi_offset, hipStream_t stream);

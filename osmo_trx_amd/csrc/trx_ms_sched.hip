@@ -30,6 +30,7 @@
 #include "../../include/trxhip.h"
 #include "trx_ctx.h"
 #include "trx_launch.h"
+#include "trx_ms_afc.h"
 #include "trx_ms_agc.h"
 #include "trx_ms_sched.h"
 
@@ -38,7 +39,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr size_t kMaxSamples = (size_t)1 << 40;
 constexpr int kTabSlots = 4;                   /* pinned table areas of a group: the host runs at most this many launch sets ahead */
-constexpr size_t kTabEntries = 3;              /* table entries per member: receiver, join, gain control */
+constexpr size_t kTabEntries = 4;              /* table entries per member: receiver, join, gain control, AFC */
 
 // ------------------------------------------------------------------------------------------------
 // The join of one member, one block, from its entry (trx_mss_join).  The stream of a pull is the carried partial slot (rem_in,
@@ -85,7 +86,8 @@ ms_join_group_kernel(const trx_mss_join *__restrict__ tab)
 	ms_join<T>(j);
 }
 
-static_assert(sizeof(trx_mss_join) == 64 && sizeof(trx_mss_member) == 64 && sizeof(trx_agc_entry) == 64, "table entries");
+static_assert(sizeof(trx_mss_join) == 64 && sizeof(trx_mss_member) == 64 && sizeof(trx_agc_entry) == 64 && sizeof(trx_afc_job) == 64,
+	      "table entries");
 static_assert(sizeof(trxhip_ms_agc_record) == 32 && sizeof(trxhip_ms_agc_status) == 304 && sizeof(trxhip_ms_agc_cfg) == 16, "public AGC structs");
 
 // One downlink stream on the host: what a group holds per member
@@ -125,6 +127,10 @@ struct ms_member {
 	trx_agc_state agc = {};
 	std::vector<float> lv_feed;            /* plan-only: the levels fed from outside */
 	size_t lv_at = 0;
+	// FCCH frequency-offset measurement (trx_ms_afc.h): the count of FCCH slots measured -- the rest of the state is on the device
+	bool afc_on = false;
+	trxhip_ms_fcch *d_fcch = nullptr;
+	uint64_t afc_count = 0;
 };
 
 // The plan of one member's pull.  plan_begin() fills the first part, plan_finish() the second; neither moves the member.
@@ -167,8 +173,9 @@ struct trxhip_ms_group {
 	trxhip_sch_sync_result *d_acq = nullptr, *h_acq = nullptr;   /* [n] */
 	// A launch set records ONE event behind everything it issues, the next of kTabSlots taken in turn: where the set sums
 	// corrections the event says that the mailbox holds them.
-	// The table of a launch set (not with `direct`): up to n receiver entries followed by up to n join entries, 64 bytes each.  It
-	// is staged in the pinned area that belongs to the set's event: the area is written again only behind that event
+	// The table of a launch set (not with `direct`): up to n receiver entries followed by up to n join entries, then those of gain
+	// control and of AFC where members have them on, 64 bytes each.  It is staged in the pinned area that belongs to the set's
+	// event: the area is written again only behind that event
 	char *d_tab = nullptr, *h_tab = nullptr;
 	hipEvent_t ev_tab[kTabSlots] = {};
 	bool tab_used[kTabSlots] = {};
@@ -182,6 +189,11 @@ struct trxhip_ms_group {
 	size_t work_floats = 0;
 	hipEvent_t ev_agc = nullptr;
 	bool agc_used = false;
+	// AFC: the members' states, the event behind the AFC launch of the last pull that had one
+	trx_afc_state *d_afc = nullptr;
+	hipEvent_t ev_afc = nullptr;
+	bool afc_used = false;
+	size_t afc_members = 0;                /* members with AFC on: while there is none a pull does not look at its slots' kinds */
 };
 
 namespace {
@@ -509,6 +521,14 @@ int reserve_work(trxhip_ms_group *g, size_t floats)
 	return TRXHIP_OK;
 }
 
+// The FCCH slots a member with AFC on measures in its pull: those among every slot the pull cuts, ACTIVE or not, slot 0 too
+size_t afc_work_of(const ms_member &m, const ms_plan &p)
+{
+	if (!m.afc_on || p.extend || p.cnt == 0)
+		return 0;
+	return (size_t)trx_afc_count(p.fn0, p.tn0, (uint64_t)p.cnt);
+}
+
 char *rem_of(trxhip_ms_group *g, size_t i, int half, int cf32)
 {
 	return g->d_rem + (i * 2 * TRX_MSS_REM_STRIDE) * 8 + (size_t)half * TRX_MSS_REM_STRIDE * (cf32 ? 8 : 4);
@@ -545,8 +565,10 @@ ms_work work_of(const ms_member &m, const ms_plan &p, bool prelim)
 // Gain control (n_agc members of the pull's own set have it on and cut a slot; none in a prelim set): their entries
 // (trx_ms_agc.h) ride in the same table behind the join entries, or are the single object's kernel argument, and BEHIND the
 // set's event -- so that nothing that waits for a correction waits for them -- come the three AGC launches and their own event.
+// AFC (n_afc members of the pull's own set have it on and cut an FCCH slot) does the same with its jobs (trx_ms_afc.h), behind
+// the AGC entries: one launch and its own event at the very end.
 int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf32, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
-		size_t out_stride, bool prelim, size_t n_rx, size_t n_join, size_t n_waves, size_t n_agc, hipStream_t st)
+		size_t out_stride, bool prelim, size_t n_rx, size_t n_join, size_t n_waves, size_t n_agc, size_t n_afc, hipStream_t st)
 {
 	trx_mss_member own_rx;
 	trx_mss_join own_join;
@@ -554,6 +576,8 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 	trx_mss_member *rx = &own_rx;
 	trx_mss_join *jn = &own_join;
 	trx_agc_entry *ag = &own_agc;
+	trx_afc_job own_afc;
+	trx_afc_job *af = &own_afc;
 	if (!g->direct) {
 		char *tab = stage_table(g);
 		if (!tab)
@@ -561,11 +585,12 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		rx = reinterpret_cast<trx_mss_member *>(tab);
 		jn = reinterpret_cast<trx_mss_join *>(tab + n_rx * 64);
 		ag = reinterpret_cast<trx_agc_entry *>(tab + (n_rx + n_join) * 64);
+		af = reinterpret_cast<trx_afc_job *>(tab + (n_rx + n_join + n_agc) * 64);
 	}
-	if (n_rx + n_join + n_agc == 0)
+	if (n_rx + n_join + n_agc + n_afc == 0)
 		return TRXHIP_OK;                                      /* (no slot and no join: no sum either) */
 
-	size_t kr = 0, kj = 0, wave = 0, ka = 0, agc_waves = 0, agc_pieces = 0, agc_floats = 0;
+	size_t kr = 0, kj = 0, wave = 0, ka = 0, agc_waves = 0, agc_pieces = 0, agc_floats = 0, kf = 0, afc_waves = 0;
 	bool sum = false;
 	for (size_t i = 0; i < g->m.size(); i++) {
 		const ms_plan &p = g->plan[i];
@@ -609,6 +634,22 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 			agc_pieces += a.n_pieces;
 			agc_floats += a.floats;
 		}
+		const size_t n_fcch = (prelim || !n_afc) ? 0 : afc_work_of(m, p);
+		if (n_fcch) {
+			trx_afc_job &e = af[kf++];
+			memset(&e, 0, sizeof(e));
+			e.chunk = h_chunks[i].d_in;
+			e.edge_row = p.straddle ? edge_row : nullptr;          /* assembled by this set's join, or by the prelim set's */
+			e.first = p.to_skip;
+			e.state = g->d_afc + i;
+			e.out = m.d_fcch ? m.d_fcch + i * out_stride : nullptr;
+			e.count = m.afc_count;
+			e.n_fcch = (uint32_t)n_fcch;
+			e.first_wave = (uint32_t)afc_waves;
+			e.fn0 = p.fn0;
+			e.tn0 = (uint8_t)p.tn0;
+			afc_waves += n_fcch;
+		}
 		if (!w.n_slots)
 			continue;
 		sum = sum || w.sum;
@@ -632,10 +673,10 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		e.first_wave = (uint32_t)wave;
 		wave += (w.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
 	}
-	if (kr != n_rx || kj != n_join || wave != n_waves || ka != n_agc || agc_floats > g->work_floats)
+	if (kr != n_rx || kj != n_join || wave != n_waves || ka != n_agc || agc_floats > g->work_floats || kf != n_afc)
 		return TRXHIP_EIO;
 
-	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, (n_rx + n_join + n_agc) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
+	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, (n_rx + n_join + n_agc + n_afc) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
 		return TRXHIP_EIO;
 	if (n_join) {
 		const trx_mss_join *jt = g->direct ? nullptr : reinterpret_cast<const trx_mss_join *>(g->d_tab + n_rx * 64);
@@ -676,6 +717,13 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		    hipEventRecord(g->ev_agc, st) != hipSuccess)
 			return TRXHIP_EIO;
 		g->agc_used = true;
+	}
+	if (n_afc) {
+		const trx_afc_job *ft = g->direct ? nullptr : reinterpret_cast<const trx_afc_job *>(g->d_tab + (n_rx + n_join + n_agc) * 64);
+		if (trx_launch_ms_afc(g->direct ? af : nullptr, ft, !cf32, n_afc, afc_waves, 1.0f / g->rx_full_scale, st) != 0 ||
+		    hipEventRecord(g->ev_afc, st) != hipSuccess)
+			return TRXHIP_EIO;
+		g->afc_used = true;
 	}
 	return TRXHIP_OK;
 }
@@ -739,12 +787,12 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 
 	// ---- the straddling SCH slots the cutters follow, one slot per member in one launch set: the second
 	if (device && n_pre &&
-	    (issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, true, n_pre, n_pre, n_pre, 0, st) != TRXHIP_OK ||
+	    (issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, true, n_pre, n_pre, n_pre, 0, 0, st) != TRXHIP_OK ||
 	     hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess))
 		return TRXHIP_EIO;
 
 	// ---- the rest of every plan
-	size_t n_rx = 0, n_join = 0, n_waves = 0, n_agc = 0, agc_floats = 0;
+	size_t n_rx = 0, n_join = 0, n_waves = 0, n_agc = 0, agc_floats = 0, n_afc = 0;
 	for (size_t i = 0; i < n; i++) {
 		if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK)
 			continue;
@@ -763,6 +811,7 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		}
 		n_agc += a.n_slots != 0;
 		agc_floats += a.floats;
+		n_afc += g->afc_members && afc_work_of(g->m[i], p) != 0;
 		const ms_work w = work_of(g->m[i], p, false);
 		n_join += w.join;
 		if (w.n_slots) {
@@ -786,7 +835,7 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		if (rc != TRXHIP_OK)
 			return rc;
 	}
-	if (device && issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, false, n_rx, n_join, n_waves, n_agc, st) != TRXHIP_OK)
+	if (device && issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, false, n_rx, n_join, n_waves, n_agc, n_afc, st) != TRXHIP_OK)
 		return TRXHIP_EIO;
 
 	// ---- and every member moves
@@ -807,6 +856,8 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 				trx_agc_run(&m.agc, m.lv_feed.data() + m.lv_at, a.n_slots, trx_agc_full_scale(g->rx_full_scale));
 				m.lv_at += a.n_slots;
 			}
+			if (g->afc_members)
+				m.afc_count += afc_work_of(m, p);
 			commit(m, p);
 		}
 		if (h_n_slots)
@@ -905,14 +956,17 @@ int group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const t
 		  hipHostMalloc((void **)&g->h_acq, n * sizeof(*g->h_acq), hipHostMallocDefault) == hipSuccess &&
 		  hipEventCreateWithFlags(&g->ev, hipEventDisableTiming) == hipSuccess &&
 		  hipMalloc((void **)&g->d_agc, n * sizeof(trx_agc_state)) == hipSuccess &&
-		  hipEventCreateWithFlags(&g->ev_agc, hipEventDisableTiming) == hipSuccess;
+		  hipEventCreateWithFlags(&g->ev_agc, hipEventDisableTiming) == hipSuccess &&
+		  hipMalloc((void **)&g->d_afc, n * sizeof(trx_afc_state)) == hipSuccess &&
+		  hipEventCreateWithFlags(&g->ev_afc, hipEventDisableTiming) == hipSuccess;
 	if (!direct)
 		ok = ok && hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
 		     hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess;
 	for (int h = 0; h < kTabSlots; h++)
 		ok = ok && hipEventCreateWithFlags(&g->ev_tab[h], hipEventDisableTiming) == hipSuccess;
 	ok = ok && hipMemset(g->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(g->d_corr, 0, n * sizeof(int32_t)) == hipSuccess &&
-	     hipMemset(g->d_agc, 0, n * sizeof(trx_agc_state)) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;      /* the first pull may come on a stream that does not wait for the null stream */
+	     hipMemset(g->d_agc, 0, n * sizeof(trx_agc_state)) == hipSuccess && hipMemset(g->d_afc, 0, n * sizeof(trx_afc_state)) == hipSuccess &&
+	     hipStreamSynchronize(nullptr) == hipSuccess;      /* the first pull may come on a stream that does not wait for the null stream */
 	if (!ok) {
 		trxhip_ms_group_destroy(g);
 		return TRXHIP_ENOMEM;
@@ -952,7 +1006,12 @@ void trxhip_ms_group_destroy(trxhip_ms_group *g)
 				(void)hipEventSynchronize(g->ev_agc);
 			(void)hipEventDestroy(g->ev_agc);
 		}
-		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work };
+		if (g->ev_afc) {
+			if (g->afc_used)
+				(void)hipEventSynchronize(g->ev_afc);
+			(void)hipEventDestroy(g->ev_afc);
+		}
+		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work, g->d_afc };
 		for (void *p : bufs)
 			if (p) (void)hipFree(p);
 		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab };
@@ -1145,6 +1204,51 @@ int trxhip_ms_agc_sched_feed_levels(trxhip_ms_sched *s, const float *levels, siz
 {
 	return trxhip_ms_agc_group_feed_levels(group_of(s), 0, levels, n);
 }
+
+// ---- FCCH frequency-offset measurement (trx_ms_afc.h) ---------------------------------------------
+
+// the AFC launch in flight is through: the members' states on the device may be read from the host, d_fcch may change
+static int afc_settled(trxhip_ms_group *g)
+{
+	if (with_device(g->ctx) || (g->afc_used && hipEventSynchronize(g->ev_afc) != hipSuccess))
+		return TRXHIP_EIO;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_afc_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_afc_cfg *cfg)
+{
+	ms_member *m = member_of(g, member);
+	if (!m || !cfg || !g->ctx || (reinterpret_cast<uintptr_t>(cfg->d_fcch) & 3))      /* a plan-only object has no samples */
+		return TRXHIP_EINVAL;
+	if (afc_settled(g) != TRXHIP_OK)
+		return TRXHIP_EIO;
+	g->afc_members += (cfg->enable != 0) - (m->afc_on ? 1 : 0);
+	m->afc_on = cfg->enable != 0;
+	m->d_fcch = cfg->d_fcch;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_afc_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_afc_status *out)
+{
+	const ms_member *m = member_of(g, member);
+	if (!m || !out)
+		return TRXHIP_EINVAL;
+	trx_afc_state s = {};
+	if (g->ctx && (afc_settled(g) != TRXHIP_OK || hipMemcpy(&s, g->d_afc + member, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess))
+		return TRXHIP_EIO;
+	memset(out, 0, sizeof(*out));
+	out->count = s.count;
+	out->enable = m->afc_on;
+	out->last = s.last;
+	out->n_records = (uint32_t)(s.count < TRX_AFC_RING ? s.count : TRX_AFC_RING);
+	for (uint32_t k = 0; k < out->n_records; k++)
+		out->ring[k] = s.ring[(s.count - out->n_records + k) % TRX_AFC_RING];
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_afc_sched_set(trxhip_ms_sched *s, const trxhip_ms_afc_cfg *cfg) { return trxhip_ms_afc_group_set(group_of(s), 0, cfg); }
+
+int trxhip_ms_afc_sched_state(trxhip_ms_sched *s, trxhip_ms_afc_status *out) { return trxhip_ms_afc_group_state(group_of(s), 0, out); }
 
 // ---- the single object: member 0 of a group of one that issues directly -------------------------
 

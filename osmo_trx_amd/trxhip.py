@@ -230,6 +230,12 @@ SYMBOLS = {
     "trxhip_ms_agc_group_set_gain": (_I, [_VP, C.c_uint32, _F]),
     "trxhip_ms_agc_group_state": (_I, [_VP, C.c_uint32, _VP]),
     "trxhip_ms_agc_group_feed_levels": (_I, [_VP, C.c_uint32, _VP, _SZ]),
+    "trxhip_ms_fcch_batch_i16": (_I, [_VP, _VP, _SZ, _VP, _SZ, _F, _VP]),
+    "trxhip_ms_fcch_batch_cf32": (_I, [_VP, _VP, _SZ, _VP, _SZ, _F, _VP]),
+    "trxhip_ms_afc_sched_set": (_I, [_VP, _VP]),
+    "trxhip_ms_afc_sched_state": (_I, [_VP, _VP]),
+    "trxhip_ms_afc_group_set": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_afc_group_state": (_I, [_VP, C.c_uint32, _VP]),
     "trxhip_ms_tx_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
     "trxhip_ms_tx_destroy": (None, [_VP]),
     "trxhip_ms_tx_set_ta": (_I, [_VP, _I]),
@@ -259,7 +265,7 @@ def load_library():
     except OSError as e:  # pragma: no cover
         raise TrxHipError(f"cannot load {path}: {e}") from e
     for name, (res, args) in SYMBOLS.items():
-        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_"))) and \
+        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_", "trxhip_ms_afc_", "trxhip_ms_fcch_"))) and \
                 os.environ.get("TRXHIP_LIB") and not hasattr(L, name):
             continue          # tools/measure.py ab against an older measurement build of the library (product: always bound)
         f = getattr(L, name)  # AttributeError if the export is missing
@@ -630,6 +636,31 @@ class TrxHip:
         _check(self.L.trxhip_ms_level_batch_i16(self.h, self._dev(rows), n, length, stride, self._dev(out), self._stream(stream)),
                "trxhip_ms_level_batch_i16")
         return out
+
+    def ms_fcch(self, iq, rx_full_scale=2047.0, slot_stride=625, n_slots=None, stream=None):
+        """gsm_fcch_offset() (ms/sch.c:255-314) of slots of 625 samples: iq int16[n, stride, 2] or complex64[n, stride], or a flat
+        int16[total, 2] / complex64[total] buffer (a view that begins at any sample) holding n_slots rows slot_stride samples
+        apart; samples 52 .. 175 of a row are read.  Returns MS_FCCH_DTYPE[n] (numpy); synchronises."""
+        torch = self.torch
+        if iq.dtype == torch.int16 and iq.shape[-1] == 2 and iq.dim() in (2, 3):
+            i16, flat = True, iq.dim() == 2
+        elif iq.dtype == torch.complex64 and iq.dim() in (1, 2):
+            i16, flat = False, iq.dim() == 1
+        else:
+            raise TrxHipError(f"iq must be int16[n, stride, 2] / [total, 2] or complex64[n, stride] / [total], not {iq.dtype}{list(iq.shape)}")
+        if flat:
+            n, stride = int(n_slots), int(slot_stride)
+            if n < 1 or stride < MS_SLOT_LEN or (n - 1) * stride + MS_SLOT_LEN > iq.shape[0]:
+                raise TrxHipError(f"{n} rows of {MS_SLOT_LEN} samples, {stride} apart, do not lie in {iq.shape[0]} samples")
+        else:
+            n, stride = int(iq.shape[0]), int(iq.shape[1])
+        if n == 0 or stride < MS_SLOT_LEN:
+            raise TrxHipError(f"need at least one slot of {MS_SLOT_LEN} samples, got {n} x {stride}")
+        out = torch.empty((n, MS_FCCH_DTYPE.itemsize), dtype=torch.uint8, device=iq.device)
+        fn, name = (self.L.trxhip_ms_fcch_batch_i16, "trxhip_ms_fcch_batch_i16") if i16 else \
+            (self.L.trxhip_ms_fcch_batch_cf32, "trxhip_ms_fcch_batch_cf32")
+        _check(fn(self.h, self._dev(iq), stride, self._dev(out), n, rx_full_scale, self._stream(stream)), name)
+        return out.cpu().numpy().reshape(-1).view(MS_FCCH_DTYPE)
 
     @staticmethod
     def results_to_numpy(results):
@@ -1182,6 +1213,36 @@ MS_AGC_STATE_DTYPE = np.dtype([("rx_gain", "<f4"), ("runmean", "<f4"), ("gain_ch
 assert MS_AGC_RECORD_DTYPE.itemsize == 32 and MS_AGC_STATE_DTYPE.itemsize == 304
 
 
+# MS-side FCCH frequency-offset measurement: trxhip_ms_fcch, trxhip_ms_afc_entry / _status, TRXHIP_MS_AFC_RING
+MS_AFC_RING = 8
+MS_FCCH_DTYPE = np.dtype([("hz", "<f4"), ("alpha_one", "<f4"), ("alpha_two", "<f4"), ("mag_one", "<f4"), ("mag_two", "<f4"),
+                          ("energy", "<f4"), ("p", "<i2"), ("r", "i1"), ("s", "i1"), ("reserved", "<u4")])
+MS_AFC_ENTRY_DTYPE = np.dtype([("fn", "<u4"), ("hz", "<f4"), ("mag_one", "<f4"), ("energy", "<f4")])
+MS_AFC_STATE_DTYPE = np.dtype([("count", "<u8"), ("n_records", "<u4"), ("enable", "u1"), ("reserved", "u1", (3,)),
+                               ("last", MS_FCCH_DTYPE), ("ring", MS_AFC_ENTRY_DTYPE, (MS_AFC_RING,))])
+assert MS_FCCH_DTYPE.itemsize == 32 and MS_AFC_ENTRY_DTYPE.itemsize == 16 and MS_AFC_STATE_DTYPE.itemsize == 176
+
+
+class _MsAfcCfg(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("reserved", C.c_int32), ("d_fcch", C.c_void_p)]
+
+
+def _afc_cfg(enable, out):
+    """trxhip_ms_afc_cfg from set_afc()'s arguments; out: a contiguous device uint8[rows, 32] tensor (MS_FCCH_DTYPE rows) or None"""
+    if out is not None:
+        assert out.is_cuda and out.is_contiguous() and out.dim() == 2 and out.shape[1] == MS_FCCH_DTYPE.itemsize and \
+            out.element_size() == 1, (out.shape, out.dtype)
+    return _MsAfcCfg(int(bool(enable)), 0, out.data_ptr() if out is not None else None)
+
+
+def _afc_state_dict(a):
+    """MS_AFC_STATE_DTYPE record -> dict; "last": the last record (MS_FCCH_DTYPE) or None, "ring": the last measurements,
+    oldest first, as dicts"""
+    d = {"count": int(a["count"]), "enable": bool(a["enable"]), "last": a["last"].copy() if a["count"] else None}
+    d["ring"] = [{k: r[k].item() for k in ("fn", "hz", "mag_one", "energy")} for r in a["ring"][:int(a["n_records"])]]
+    return d
+
+
 class _MsAgcCfg(C.Structure):
     _fields_ = [("enable", C.c_int32), ("rx_gain", C.c_float), ("d_level", C.c_void_p)]
 
@@ -1225,6 +1286,7 @@ class MsRxScheduler:
         self.carried = 0
         self.rx_full_scale = float(rx_full_scale)
         self._agc, self._levels, self._lv = False, False, None
+        self._fcch = None
 
     def set_clock(self, fn, tn, ts=0):
         _check(self.L.trxhip_ms_sched_set_clock(self.h, fn, tn, ts), "trxhip_ms_sched_set_clock")
@@ -1313,6 +1375,23 @@ class MsRxScheduler:
         if what == MS_AGC_RAISE:
             return RAISE, new
         return self.acquire(x, first_ts, stream=stream)
+
+    # ---- FCCH frequency-offset measurement (trxhip_ms_afc_sched_*) ----
+    def set_afc(self, enable, out=None):
+        """gsm_fcch_offset() (ms/sch.c:255-314) on every FCCH slot a pull cuts, ACTIVE or not.  out: a device uint8[rows, 32]
+        tensor (MS_FCCH_DTYPE rows) whose row k receives slot k's record where slot k of a pull is an FCCH slot -- the caller gives
+        it as many rows as its largest pull cuts slots (slots()); other rows are not touched.  The state stays as it is; waits for
+        AFC work in flight.  A plan-only object refuses."""
+        cfg = _afc_cfg(enable, out)
+        _check(self.L.trxhip_ms_afc_sched_set(self.h, C.byref(cfg)), "trxhip_ms_afc_sched_set")
+        self._fcch = out                                     # (kept alive while the object may write it)
+
+    def afc_state(self):
+        """dict: count (FCCH slots measured), enable, last (MS_FCCH_DTYPE record or None), ring (the last 8 {fn, hz, mag_one,
+        energy}, oldest first); waits for the AFC work in flight"""
+        a = np.zeros(1, dtype=MS_AFC_STATE_DTYPE)
+        _check(self.L.trxhip_ms_afc_sched_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_afc_sched_state")
+        return _afc_state_dict(a[0])
 
     def slots(self, n_samples):
         n = self.L.trxhip_ms_sched_slots(self.h, n_samples)
@@ -1416,6 +1495,7 @@ class MsRxSchedulerGroup:
         self.carried = [0] * self.n
         self.rx_full_scale = float(rx_full_scale)
         self._levels, self._lv = [False] * self.n, None
+        self._fcch = {}
 
     def set_clock(self, m, fn, tn, ts=0):
         _check(self.L.trxhip_ms_group_set_clock(self.h, m, fn, tn, ts), "trxhip_ms_group_set_clock")
@@ -1522,6 +1602,21 @@ class MsRxSchedulerGroup:
             f, r = self.acquire([members[i] for i in go], sub, [ts[i] for i in go], stream=stream)
             found[go], rec[go] = f, r
         return found, rec, [None if gate[i][0] == MS_AGC_SEARCH else gate[i][1] for i in range(n)]
+
+    # ---- FCCH frequency-offset measurement (trxhip_ms_afc_group_*), per member ----
+    def set_afc(self, m, enable, out=None):
+        """member m: gsm_fcch_offset() on every FCCH slot its pulls cut.  out: a device uint8[n * out_stride, 32] tensor
+        (MS_FCCH_DTYPE rows) for pulls with that out_stride: slot k of member m goes to row m * out_stride + k where it is an FCCH
+        slot; a group passes one array to all its members.  Members are on or off independently."""
+        cfg = _afc_cfg(enable, out)
+        _check(self.L.trxhip_ms_afc_group_set(self.h, m, C.byref(cfg)), "trxhip_ms_afc_group_set")
+        self._fcch[m] = out                                  # (kept alive while the group may write it)
+
+    def afc_state(self, m):
+        """member m's dict as MsRxScheduler.afc_state(); waits for the group's AFC work in flight"""
+        a = np.zeros(1, dtype=MS_AFC_STATE_DTYPE)
+        _check(self.L.trxhip_ms_afc_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_afc_group_state")
+        return _afc_state_dict(a[0])
 
     def slots(self, m, n_samples):
         n = self.L.trxhip_ms_group_slots(self.h, m, n_samples)
