@@ -1176,8 +1176,7 @@ int  trxhip_ms_agc_group_feed_levels(trxhip_ms_group *g, uint32_t member, const 
  *   d_fcch[m * out_stride + k] where d_fcch is given (4-byte aligned; the single object: d_fcch[k]); entries of other slots are
  *   not touched.  Per member on the device: the count of FCCH slots measured, the last record, and the last TRXHIP_MS_AFC_RING
  *   {fn, hz, mag_one, energy}.  _set leaves the state alone; set_clock and acquire do not touch it; a refused pull moves none
- *   of it.  Nothing is fed back into the stream: there is no oscillator here to steer, temp_ts_corr_offset stays the only
- *   feedback.  Issued per pull in which a member with AFC on cuts an FCCH slot: one launch (a wave per FCCH slot, found by
+ *   of it.  The measurement feeds nothing back by itself: the caller reads it and sets the NCO below.  Issued per pull in which a member with AFC on cuts an FCCH slot: one launch (a wave per FCCH slot, found by
  *   arithmetic on the pull's clock) and one event record behind the pull's own; 64 bytes per such member ride in the pull's
  *   table; no wait, no copy.  With AFC off everywhere a pull issues what it issued before.  _set and _state wait for the AFC
  *   launches in flight.  _state: ring[0 .. n_records) oldest first.  Plan-only objects have no samples: _set is TRXHIP_EINVAL. */
@@ -1215,6 +1214,80 @@ int  trxhip_ms_afc_sched_set(trxhip_ms_sched *s, const trxhip_ms_afc_cfg *cfg);
 int  trxhip_ms_afc_sched_state(trxhip_ms_sched *s, trxhip_ms_afc_status *out);
 int  trxhip_ms_afc_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_afc_cfg *cfg);
 int  trxhip_ms_afc_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_afc_status *out);
+
+/* ---- MS-side frequency correction: a numerically controlled oscillator (NCO) per member in the receive path -------------------
+ * The AFC above measures the carrier offset; this acts on it.  A group holds thousands of streams and no hardware can be trimmed
+ * per member, so the oscillator is software: the receiver rotates every sample of a member's stream while it fills the slot's
+ * window, in the same pass that converts and scales it.  The loop is feed-forward: the caller reads afc_state() and sets the NCO.
+ * State per member: inc (int32, phase increment per sample), acc (uint32, the phase at ts_ref), ts_ref (int64), enable.
+ *   phase      p(ts) = acc + (uint32_t)(ts - ts_ref) * (uint32_t)inc, all modulo 2^32; ts - ts_ref may be negative.  The phase of
+ *              a sample depends on its absolute timestamp alone, so the result does not depend on how the stream is chunked.
+ *   increment  inc = (int32_t)llrint(hz * (4294967296.0 / (13e6 / 12.0))) in double; |hz| <= 500000, else TRXHIP_EINVAL (NaN too).
+ *              hz is the shift applied to the stream, + = the spectrum moves up: to cancel a measured offset pass
+ *              -(fcch.hz - TRXHIP_MS_FCCH_BIAS_HZ) -- a tone on the FCCH frequency reads +25 / 3 Hz (see above).
+ *   phasor     two float tables of 1024 (cos, sin) pairs: C[a] = (cos, sin)(2 pi a / 2^10), a = p >> 22, and
+ *              F[b] = (cos, sin)(2 pi b / 2^20), b = (p >> 12) & 1023; the low 12 bits of p are dropped (a phase error below
+ *              6e-6 rad, under float32 resolution of the products).  Entries are made in double and rounded to float; C is its
+ *              first quadrant turned three times, so C[0] = (1, 0), C[256] = (0, 1), C[512] = (-1, 0), C[768] = (0, -1) exactly.
+ *              r = (Cc Fc - Cs Fs, Cc Fs + Cs Fc), every product and sum rounded to float (no contraction).  16 KB on the
+ *              device, made on the host at context creation and uploaded once.
+ *   rotation   out = ((xr rc - xi rs) scale, (xr rs + xi rc) scale), x the float of the int16 sample or the complex64 sample:
+ *              rotation first, convert_and_scale's factor second, each product and sum rounded to float.  The receiver with the
+ *              NCO on therefore equals "rotate, then the complex64 receiver" bit for bit.  inc = 0 at phase 0 is the identity
+ *              (r = (1, 0); a complex64 component of -0.0 may come out as +0.0).
+ * Host-only, no GPU: trxhip_ms_nco_tables_host() (C then F, 4096 floats), trxhip_ms_nco_inc(), trxhip_ms_nco_phase().
+ * trxhip_ms_nco_batch_*(): the rotation alone, no scale.  Row r = the row_len samples (1 .. 2^31 - 1) at d_in + r * row_stride
+ *   samples, rotated by d_rec[r] = {phase0, inc} (sample i: phase0 + i * inc; a device array of 8-byte records, 4-byte aligned)
+ *   into the complex64 row at d_out_cf32 + r * out_stride samples (8-byte aligned).  int16 rows are 4-byte aligned, complex64
+ *   rows 8-byte; n_rows 1 .. 2^31 - 1; both strides >= row_len; else TRXHIP_EINVAL.  A wave per run of 64 samples.
+ * A scheduler member (trxhip_ms_nco_sched_set / trxhip_ms_nco_group_set: {enable, hz}; the single object's calls are those of
+ *   member 0 of a group of one).  _set acts at the member's clock ts_now, the ts trxhip_ms_sched_clock() reports (0 before a
+ *   clock is set): acc <- p(ts_now), ts_ref <- ts_now, inc <- new, so the phase stays continuous across a change of frequency;
+ *   switching on from off starts at acc = 0, and switching off leaves acc = 0.  A slot that straddles two pulls and is received
+ *   after a _set is rotated whole with the new setting, extrapolated backwards.  _set and _state touch host state only and wait
+ *   for nothing: a pull takes the member's setting by value.  set_clock, set_tsc, set_active, acquire and a refused pull leave the
+ *   NCO alone.  Plan-only objects keep the same bookkeeping with no samples.
+ *   Pulls (int16 and complex64, single and group): a pull in which any member with work has the NCO on runs the rotating
+ *   instance of the receiver; members with it off ride with inc = 0 at phase 0.  Per receiver entry 16 bytes ride beside the
+ *   table (the single object: a kernel argument): {phase of the first slot in the chunk, inc, phase of the slot assembled across
+ *   two pulls, 0} -- the two phases are separate because a correction of the cut (temp_ts_corr_offset) can lie between those
+ *   two slots.  They are computed on the host from the planner's timestamps after the waits the pull already has: no new launch,
+ *   no new wait, no other copy.  With the NCO off everywhere a pull issues exactly what it issued before.  The join, the AGC
+ *   levels and the FCCH measurement keep reading the stream as received: hz of the AFC stays the radio's offset, and d_fcch, the
+ *   AFC ring and the AGC state are the same bytes with the NCO on or off.
+ *   Acquire (trxhip_ms_sched_acquire_*, trxhip_ms_group_acquire_*): when a listed member has the NCO on, the buffers of the call
+ *   go through trxhip_ms_nco_batch_*() (row i: phase p(first_ts[i]) of members[i], inc 0 at phase 0 for a member with it off)
+ *   into an internal complex64 work buffer of n * buf_len * 8 bytes for the n buffers of that call, grown on demand and kept
+ *   until the object is destroyed, and the search runs on that: the result is that of acquire_cf32 on the batch call's output. */
+#define TRXHIP_MS_FCCH_BIAS_HZ (25.0 / 3.0)
+typedef struct trxhip_ms_nco_row {  /* 8 bytes */
+	uint32_t phase0;
+	int32_t  inc;
+} trxhip_ms_nco_row;
+typedef struct trxhip_ms_nco_cfg {  /* 16 bytes */
+	int32_t enable;
+	int32_t reserved;
+	double  hz;
+} trxhip_ms_nco_cfg;
+typedef struct trxhip_ms_nco_status {  /* 32 bytes */
+	uint8_t  enable, reserved[3];
+	int32_t  inc;
+	uint32_t acc;
+	uint32_t reserved2;
+	int64_t  ts_ref;
+	double   hz;
+} trxhip_ms_nco_status;
+int  trxhip_ms_nco_tables_host(float *out4096);
+int  trxhip_ms_nco_inc(double hz, int32_t *inc);
+uint32_t trxhip_ms_nco_phase(uint32_t acc, int64_t ts_ref, int32_t inc, int64_t ts);
+int  trxhip_ms_nco_batch_i16(trxhip_ctx *ctx, const int16_t *d_in, size_t row_stride, const trxhip_ms_nco_row *d_rec, float *d_out_cf32,
+			     size_t out_stride, size_t n_rows, size_t row_len, void *stream);
+int  trxhip_ms_nco_batch_cf32(trxhip_ctx *ctx, const float *d_in_cf32, size_t row_stride, const trxhip_ms_nco_row *d_rec,
+			      float *d_out_cf32, size_t out_stride, size_t n_rows, size_t row_len, void *stream);
+int  trxhip_ms_nco_sched_set(trxhip_ms_sched *s, const trxhip_ms_nco_cfg *cfg);
+int  trxhip_ms_nco_sched_state(trxhip_ms_sched *s, trxhip_ms_nco_status *out);
+int  trxhip_ms_nco_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_nco_cfg *cfg);
+int  trxhip_ms_nco_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_nco_status *out);
 
 /* ---- The MS-side uplink burst scheduler: burst requests in, the radio's transmit sample stream out --------------------------
  * What the reference does between trxcon's burst request and the radio: upper_trx::driveTx() (ms/ms_upper.cpp:306-355),

@@ -15,7 +15,8 @@ from .trxhip import (TrxHip, TrxHipError, PARAMS_DTYPE, RESULT_DTYPE, lib_path, 
                      MS_SCHED_NO_SCH, MsTxScheduler, MsTxSchedulerGroup, ms_tx_requests, MS_TX_REQ_DTYPE, MS_TX_PLAN_DTYPE, MS_TX_STATE_DTYPE,
                      MS_TX_QUEUED, MS_TX_LATE, MS_TX_WRAPPED, MS_TX_EXPIRED, MS_TX_OVERLAP, MS_TX_FULL,
                      ms_agc_gate, MS_AGC_RAISE, MS_AGC_SEARCH, MS_AGC_RECORD_DTYPE, MS_AGC_STATE_DTYPE,
-                     MS_FCCH_DTYPE, MS_AFC_ENTRY_DTYPE, MS_AFC_STATE_DTYPE, MS_AFC_RING)
+                     MS_FCCH_DTYPE, MS_AFC_ENTRY_DTYPE, MS_AFC_STATE_DTYPE, MS_AFC_RING,
+                     MS_NCO_ROW_DTYPE, MS_NCO_STATE_DTYPE, MS_FCCH_BIAS_HZ, nco_hz_from_fcch, ms_nco_inc, ms_nco_phase, ms_nco_tables_host)
 
 __all__ = ["TrxHip", "TrxHipError", "PARAMS_DTYPE", "RESULT_DTYPE", "lib_path", "load_library",
            "OFF", "TSC", "EXT_RACH", "RACH", "SCH", "EDGE", "IDLE",
@@ -24,4 +25,5 @@ __all__ = ["TrxHip", "TrxHipError", "PARAMS_DTYPE", "RESULT_DTYPE", "lib_path", 
            "MS_SCHED_NO_SCH", "MsTxScheduler", "MsTxSchedulerGroup", "ms_tx_requests", "MS_TX_REQ_DTYPE", "MS_TX_PLAN_DTYPE", "MS_TX_STATE_DTYPE",
            "MS_TX_QUEUED", "MS_TX_LATE", "MS_TX_WRAPPED", "MS_TX_EXPIRED", "MS_TX_OVERLAP", "MS_TX_FULL",
            "ms_agc_gate", "MS_AGC_RAISE", "MS_AGC_SEARCH", "MS_AGC_RECORD_DTYPE", "MS_AGC_STATE_DTYPE",
-           "MS_FCCH_DTYPE", "MS_AFC_ENTRY_DTYPE", "MS_AFC_STATE_DTYPE", "MS_AFC_RING"]
+           "MS_FCCH_DTYPE", "MS_AFC_ENTRY_DTYPE", "MS_AFC_STATE_DTYPE", "MS_AFC_RING",
+           "MS_NCO_ROW_DTYPE", "MS_NCO_STATE_DTYPE", "MS_FCCH_BIAS_HZ", "nco_hz_from_fcch", "ms_nco_inc", "ms_nco_phase", "ms_nco_tables_host"]

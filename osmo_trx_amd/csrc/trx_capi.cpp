@@ -14,6 +14,7 @@
 #include "trx_tables.h"
 #include "trx_ctx.h"
 #include "trx_launch.h"
+#include "trx_ms_nco.h"
 
 extern "C" {
 
@@ -134,6 +135,22 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 		}
 		free(tx);
 	}
+	if (rc == TRXHIP_OK) {
+		/* the NCO's phasor tables (trx_ms_nco.h) */
+		float *nco = static_cast<float *>(malloc(TRX_NCO_FLOATS * sizeof(float)));
+		if (!nco) {
+			rc = TRXHIP_ENOMEM;
+		} else {
+			trx_nco_tables(nco);
+			if (hipMalloc(reinterpret_cast<void **>(&ctx->d_nco_tab), TRX_NCO_FLOATS * sizeof(float)) != hipSuccess) {
+				ctx->d_nco_tab = nullptr;
+				rc = TRXHIP_ENOMEM;
+			} else if (hipMemcpy(ctx->d_nco_tab, nco, TRX_NCO_FLOATS * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+				rc = TRXHIP_EIO;
+			}
+			free(nco);
+		}
+	}
 	if (rc != TRXHIP_OK) {
 		trxhip_destroy(ctx);
 		return rc;
@@ -169,6 +186,7 @@ void trxhip_destroy(trxhip_ctx *ctx)
 		if (ctx->d_tables) (void)hipFree(ctx->d_tables);
 		if (ctx->d_pool) (void)hipFree(ctx->d_pool);
 		if (ctx->d_tx_tables) (void)hipFree(ctx->d_tx_tables);
+		if (ctx->d_nco_tab) (void)hipFree(ctx->d_nco_tab);
 		for (float *t : ctx->d_rs_resamp)
 			if (t) (void)hipFree(t);
 		ctx->redo.destroy();

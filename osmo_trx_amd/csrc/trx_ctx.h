@@ -190,6 +190,7 @@ struct trxhip_ctx {
 	std::mutex rs_mu;
 	float *d_rs_resamp[2] = { nullptr, nullptr };
 	trx_sch_scratch sch_sync;
+	float *d_nco_tab = nullptr;        /* the NCO's two phasor tables (trx_ms_nco.h): 4096 floats, made on the host and uploaded at creation */
 };
 
 static inline int with_device(const trxhip_ctx *ctx)

@@ -106,6 +106,20 @@ int trx_launch_ms_fcch_rows(const void *d_iq, int i16, size_t slot_stride, trxhi
 int trx_launch_ms_afc(const struct trx_afc_job *h_job, const struct trx_afc_job *d_tab, int i16, size_t n_jobs, size_t n_waves,
 		      float scale, hipStream_t stream);
 
+/* trx_ms_nco.hip: the MS-side NCO (trx_ms_nco.h).  _nco_rows: n_rows rows of row_len samples (int16 pairs or complex64),
+ * row_stride samples apart, row r rotated by d_rec[r] into the complex64 row at d_out + r * out_stride samples; d_tab: the
+ * context's phasor tables.
+ * trx_ms_rx.hip: the rotating instances of the receiver's stream and group forms -- the same launches as above with the launch's
+ * oscillator (the stream form: *nco, by value) or the entries' (the group form: d_nco[k] beside d_tab[k]) */
+struct trx_nco_slot;
+int trx_launch_ms_nco_rows(const void *d_in, int i16, size_t row_stride, const trxhip_ms_nco_row *d_rec, float *d_out, size_t out_stride,
+			   size_t n_rows, size_t row_len, const float *d_tab, hipStream_t stream);
+int trx_launch_ms_rx_stream_nco(const void *d_chunk, int i16, const struct trx_mss_stream *sa, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+				size_t n_slots, float scale, float rx_full_scale, const struct trx_nco_slot *nco, const float *d_nco_tab,
+				hipStream_t stream);
+int trx_launch_ms_rx_group_nco(const struct trx_mss_member *d_tab, int i16, size_t n_entries, size_t n_waves, float scale,
+			       float rx_full_scale, const struct trx_nco_slot *d_nco, const float *d_nco_tab, hipStream_t stream);
+
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,
 			 size_t n_bursts, float rssi_offset, hipStream_t stream);

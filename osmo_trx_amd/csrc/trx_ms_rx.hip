@@ -17,8 +17,12 @@
 // slot), and a decoded SCH slot with abs(start) > 1 adds -start to the pull's correction word.
 // THE GROUP FORM (trxhip_ms_group_*) is the stream form behind a table: a wave's four slots belong to one member of a group of
 // streams, and the wave takes chunk, descriptor and outputs from that member's table entry.
+// THE ROTATING INSTANCES (ROT) of the stream and group forms are the same body with the NCO (trx_ms_nco.h) in the slot fill: the
+// sample is read unscaled, multiplied by the phasor of its phase and then by scale, so the window holds what the non-rotating
+// instance makes of the rotated stream, bit for bit.  The zero padding stays zero; nothing else changes.
 #include "trx_sch_common.h"
 #include "trx_launch.h"
+#include "trx_ms_nco.h"
 #include "trx_ms_sched.h"
 
 #define MS_SLOT 625                      // ONE_TS_BURST_LEN (ms.h:50)
@@ -95,11 +99,29 @@ __device__ __forceinline__ const char *ms_slot_src(const void *iq, size_t slot_s
 	return reinterpret_cast<const char *>(iq) + (size_t)b * slot_stride * (I16 ? 4 : 8);
 }
 
+// The oscillator of a rotating instance: the entry's record and the phasor tables; empty in the others
+struct ms_rx_nco {
+	trx_nco_slot o;
+	const float *tab;
+};
+
+// convert_and_scale behind the NCO: sample i of the slot whose first sample has the phase p_slot
+template <bool I16>
+__device__ __forceinline__ c32 ms_load_rot(const void *src, size_t i, float scale, uint32_t p_slot, const ms_rx_nco &nco)
+{
+	const c32 x = ss_load<I16>(src, i, 1.0f);                      // (x * 1.0f is x)
+	float rc, rs, yr, yi;
+	trx_nco_phasor(nco.tab, p_slot + (uint32_t)i * (uint32_t)nco.o.inc, &rc, &rs);
+	trx_nco_rotate(x.x, x.y, rc, rs, &yr, &yi);
+	return make_float2(yr * scale, yi * scale);
+}
+
 // The receiver of one wave: the VA_BPW slots from q0 on, of n_slots.  wave: the wave's index in its block (its LDS slice)
-template <bool I16, bool STREAM>
+template <bool I16, bool STREAM, bool ROT = false>
 __device__ __forceinline__ void ms_rx_wave(const void *__restrict__ iq, size_t slot_stride, const trxhip_ms_slot *__restrict__ slots,
 					   trxhip_ms_burst_ind *__restrict__ ind, int8_t *__restrict__ bits, unsigned n_slots, float scale,
-					   float rx_full_scale, const trx_mss_stream &sa, const int wave, const unsigned q0)
+					   float rx_full_scale, const trx_mss_stream &sa, const int wave, const unsigned q0,
+					   const ms_rx_nco &nco = ms_rx_nco())
 {
 	__shared__ __attribute__((aligned(16))) char smem[SS_WPB * MS_SLICE_BYTES];
 	const int lane = threadIdx.x & (WAVE - 1);
@@ -154,9 +176,20 @@ __device__ __forceinline__ void ms_rx_wave(const void *__restrict__ iq, size_t s
 		}
 		// the slot 40 samples into the zeroed array (ms_upper.cpp:164-171, ms_rx_lower.cpp:162-164), scaled on the way in
 		const char *src = ms_slot_src<I16, STREAM>(iq, slot_stride, sa, b);
-		for (int j = lane; j < SS_WIN; j += WAVE) {
-			const int g = j - 40;
-			xs[(j & 3) * SS_XA + (j >> 2)] = (g >= 0 && g < MS_SLOT) ? ss_load<I16>(src, (size_t)g, scale) : make_float2(0.0f, 0.0f);
+		if (ROT) {
+			// slot b's first sample: the edge row's own phase, else b slots of 625 behind the chunk's first (trx_ms_nco.h)
+			const bool edge = sa.edge_row != nullptr;
+			const uint32_t ps = (edge && b == 0) ? nco.o.edge : nco.o.phase0 + (b - (edge ? 1u : 0u)) * (uint32_t)MS_SLOT * (uint32_t)nco.o.inc;
+			for (int j = lane; j < SS_WIN; j += WAVE) {
+				const int g = j - 40;
+				xs[(j & 3) * SS_XA + (j >> 2)] =
+					(g >= 0 && g < MS_SLOT) ? ms_load_rot<I16>(src, (size_t)g, scale, ps, nco) : make_float2(0.0f, 0.0f);
+			}
+		} else {
+			for (int j = lane; j < SS_WIN; j += WAVE) {
+				const int g = j - 40;
+				xs[(j & 3) * SS_XA + (j >> 2)] = (g >= 0 && g < MS_SLOT) ? ss_load<I16>(src, (size_t)g, scale) : make_float2(0.0f, 0.0f);
+			}
 		}
 		wave_sync();
 		float pow = 0.0f;
@@ -327,6 +360,43 @@ ms_rx_group_kernel(const trx_mss_member *__restrict__ tab, unsigned n_entries, u
 	ms_rx_wave<I16, true>(e->chunk, (size_t)MS_SLOT, nullptr, e->ind, e->bits, n_slots, scale, rx_full_scale, sa, wave, q0);
 }
 
+// the rotating instances of the two: the launch's oscillator as an argument, the entries' beside the table
+template <bool I16>
+__global__ void __launch_bounds__(SS_WPB * WAVE)
+ms_rx_nco_kernel(const void *__restrict__ iq, trxhip_ms_burst_ind *__restrict__ ind, int8_t *__restrict__ bits, unsigned n_slots, float scale,
+		 float rx_full_scale, const trx_mss_stream sa, const trx_nco_slot o, const float *__restrict__ nco_tab)
+{
+	const int wave = uni((int)(threadIdx.x >> 6));
+	const unsigned q0 = (blockIdx.x * SS_WPB + wave) * VA_BPW;
+	const ms_rx_nco nco = { o, nco_tab };
+	ms_rx_wave<I16, true, true>(iq, (size_t)MS_SLOT, nullptr, ind, bits, n_slots, scale, rx_full_scale, sa, wave, q0, nco);
+}
+
+template <bool I16>
+__global__ void __launch_bounds__(SS_WPB * WAVE)
+ms_rx_group_nco_kernel(const trx_mss_member *__restrict__ tab, unsigned n_entries, unsigned n_waves, float scale, float rx_full_scale,
+		       const trx_nco_slot *__restrict__ osc, const float *__restrict__ nco_tab)
+{
+	const int wave = uni((int)(threadIdx.x >> 6));
+	const unsigned gw = blockIdx.x * SS_WPB + wave;
+	if (gw >= n_waves)
+		return;
+	unsigned lo = 0, hi = n_entries;                               // tab[lo].first_wave <= gw < tab[hi].first_wave
+	while (hi - lo > 1) {
+		const unsigned mid = (lo + hi) >> 1;
+		if (tab[mid].first_wave <= gw)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	const trx_mss_member *e = tab + lo;
+	const trx_mss_stream sa = e->sa;
+	const unsigned n_slots = e->n_slots;
+	const unsigned q0 = (gw - e->first_wave) * VA_BPW;
+	const ms_rx_nco nco = { osc[lo], nco_tab };
+	ms_rx_wave<I16, true, true>(e->chunk, (size_t)MS_SLOT, nullptr, e->ind, e->bits, n_slots, scale, rx_full_scale, sa, wave, q0, nco);
+}
+
 extern "C" int trx_launch_ms_rx(const void *d_iq, int i16, size_t slot_stride, const trxhip_ms_slot *d_slots, trxhip_ms_burst_ind *d_ind,
 				int8_t *d_bits, size_t n_slots, float scale, float rx_full_scale, hipStream_t stream)
 {
@@ -376,6 +446,41 @@ extern "C" int trx_launch_ms_rx_group(const trx_mss_member *d_tab, int i16, size
 	else
 		hipLaunchKernelGGL((ms_rx_group_kernel<false>), dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_tab, (unsigned)n_entries,
 				   (unsigned)n_waves, scale, rx_full_scale);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+extern "C" int trx_launch_ms_rx_stream_nco(const void *d_chunk, int i16, const trx_mss_stream *sa, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
+					   size_t n_slots, float scale, float rx_full_scale, const trx_nco_slot *nco, const float *d_nco_tab,
+					   hipStream_t stream)
+{
+	if (n_slots == 0)
+		return 0;
+	if (!nco || !d_nco_tab)
+		return TRXHIP_EINVAL;
+	const size_t per_block = SS_WPB * VA_BPW;
+	const size_t grid = (n_slots + per_block - 1) / per_block;
+	if (i16)
+		hipLaunchKernelGGL(ms_rx_nco_kernel<true>, dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_chunk, d_ind, d_bits,
+				   (unsigned)n_slots, scale, rx_full_scale, *sa, *nco, d_nco_tab);
+	else
+		hipLaunchKernelGGL(ms_rx_nco_kernel<false>, dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_chunk, d_ind, d_bits,
+				   (unsigned)n_slots, scale, rx_full_scale, *sa, *nco, d_nco_tab);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+extern "C" int trx_launch_ms_rx_group_nco(const trx_mss_member *d_tab, int i16, size_t n_entries, size_t n_waves, float scale,
+					  float rx_full_scale, const trx_nco_slot *d_nco, const float *d_nco_tab, hipStream_t stream)
+{
+	if (n_entries == 0 || n_waves == 0)
+		return 0;
+	if (n_entries > n_waves || n_waves > 0x7fffffffu || !d_nco || !d_nco_tab)
+		return TRXHIP_EINVAL;
+	const size_t grid = (n_waves + SS_WPB - 1) / SS_WPB;
+	if (i16)
+		hipLaunchKernelGGL(ms_rx_group_nco_kernel<true>, dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_tab, (unsigned)n_entries,
+				   (unsigned)n_waves, scale, rx_full_scale, d_nco, d_nco_tab);
+	else
+		hipLaunchKernelGGL(ms_rx_group_nco_kernel<false>, dim3((unsigned)grid), dim3(SS_WPB * WAVE), 0, stream, d_tab, (unsigned)n_entries,
+				   (unsigned)n_waves, scale, rx_full_scale, d_nco, d_nco_tab);
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
 static_assert(TRX_MS_RX_SLOTS_PER_WAVE == VA_BPW, "slots per wave");

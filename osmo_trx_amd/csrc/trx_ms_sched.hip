@@ -32,6 +32,7 @@
 #include "trx_launch.h"
 #include "trx_ms_afc.h"
 #include "trx_ms_agc.h"
+#include "trx_ms_nco.h"
 #include "trx_ms_sched.h"
 
 namespace {
@@ -39,7 +40,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr size_t kMaxSamples = (size_t)1 << 40;
 constexpr int kTabSlots = 4;                   /* pinned table areas of a group: the host runs at most this many launch sets ahead */
-constexpr size_t kTabEntries = 4;              /* table entries per member: receiver, join, gain control, AFC */
+constexpr size_t kTabEntries = 5;              /* table entries per member: receiver, join, gain control, AFC; the fifth holds the NCO's 16 bytes */
 
 // ------------------------------------------------------------------------------------------------
 // The join of one member, one block, from its entry (trx_mss_join).  The stream of a pull is the carried partial slot (rem_in,
@@ -131,6 +132,8 @@ struct ms_member {
 	bool afc_on = false;
 	trxhip_ms_fcch *d_fcch = nullptr;
 	uint64_t afc_count = 0;
+	// the NCO (trx_ms_nco.h): all of it is here -- a pull takes it by value
+	trx_nco_state nco = {};
 };
 
 // The plan of one member's pull.  plan_begin() fills the first part, plan_finish() the second; neither moves the member.
@@ -194,6 +197,10 @@ struct trxhip_ms_group {
 	hipEvent_t ev_afc = nullptr;
 	bool afc_used = false;
 	size_t afc_members = 0;                /* members with AFC on: while there is none a pull does not look at its slots' kinds */
+	// the NCO in front of acquire: the rows' records and their pinned staging ([n] each), the complex64 work buffer (it grows)
+	trxhip_ms_nco_row *d_nco_rec = nullptr, *h_nco_rec = nullptr;
+	float *d_nco_work = nullptr;
+	size_t nco_work_samples = 0;
 };
 
 namespace {
@@ -578,6 +585,9 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 	trx_agc_entry *ag = &own_agc;
 	trx_afc_job own_afc;
 	trx_afc_job *af = &own_afc;
+	trx_nco_slot own_nco;
+	trx_nco_slot *nc = &own_nco;                           /* the receiver entries' oscillators, beside them: nc[k] with rx[k] */
+	const size_t n_ent = n_rx + n_join + n_agc + n_afc;
 	if (!g->direct) {
 		char *tab = stage_table(g);
 		if (!tab)
@@ -586,12 +596,13 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		jn = reinterpret_cast<trx_mss_join *>(tab + n_rx * 64);
 		ag = reinterpret_cast<trx_agc_entry *>(tab + (n_rx + n_join) * 64);
 		af = reinterpret_cast<trx_afc_job *>(tab + (n_rx + n_join + n_agc) * 64);
+		nc = reinterpret_cast<trx_nco_slot *>(tab + n_ent * 64);
 	}
-	if (n_rx + n_join + n_agc + n_afc == 0)
+	if (n_ent == 0)
 		return TRXHIP_OK;                                      /* (no slot and no join: no sum either) */
 
 	size_t kr = 0, kj = 0, wave = 0, ka = 0, agc_waves = 0, agc_pieces = 0, agc_floats = 0, kf = 0, afc_waves = 0;
-	bool sum = false;
+	bool sum = false, rot = false;                         /* rot: a member with receiver work has the NCO on */
 	for (size_t i = 0; i < g->m.size(); i++) {
 		const ms_plan &p = g->plan[i];
 		if (!h_chunks[i].n_samples || g->rc[i] != TRXHIP_OK || (prelim && !p.prelim))
@@ -653,6 +664,15 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		if (!w.n_slots)
 			continue;
 		sum = sum || w.sum;
+		// the oscillator by absolute timestamp: the straddling slot begins at first_ts - carried, the chunk's first at first_ts + to_skip
+		trx_nco_slot &o = nc[kr];
+		memset(&o, 0, sizeof(o));
+		if (m.nco.enable) {
+			rot = true;
+			o.inc = m.nco.inc;
+			o.edge = trx_nco_phase(m.nco.acc, m.nco.ts_ref, m.nco.inc, p.first_ts - (int64_t)p.carried);
+			o.phase0 = trx_nco_phase(m.nco.acc, m.nco.ts_ref, m.nco.inc, p.first_ts + p.to_skip);
+		}
 		trx_mss_member &e = rx[kr++];
 		memset(&e, 0, sizeof(e));
 		uint32_t fnk = p.fn;                                   /* prelim: the straddling slot's clock */
@@ -676,7 +696,7 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 	if (kr != n_rx || kj != n_join || wave != n_waves || ka != n_agc || agc_floats > g->work_floats || kf != n_afc)
 		return TRXHIP_EIO;
 
-	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, (n_rx + n_join + n_agc + n_afc) * 64, hipMemcpyHostToDevice, st) != hipSuccess)
+	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, n_ent * 64 + (rot ? n_rx * sizeof(trx_nco_slot) : 0), hipMemcpyHostToDevice, st) != hipSuccess)
 		return TRXHIP_EIO;
 	if (n_join) {
 		const trx_mss_join *jt = g->direct ? nullptr : reinterpret_cast<const trx_mss_join *>(g->d_tab + n_rx * 64);
@@ -696,9 +716,16 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		return TRXHIP_EIO;
 	if (n_rx) {
 		const float fs = g->rx_full_scale;                     /* 1.f / float(rxFullScale) (ms_upper.cpp:203), as trxhip_ms_rx_batch_*() */
-		const int rc = g->direct ? trx_launch_ms_rx_stream(rx->chunk, !cf32, &rx->sa, rx->ind, rx->bits, rx->n_slots, 1.0f / fs, fs, st)
-					 : trx_launch_ms_rx_group(reinterpret_cast<const trx_mss_member *>(g->d_tab), !cf32, n_rx, n_waves,
-								  1.0f / fs, fs, st);
+		const trx_mss_member *rt = reinterpret_cast<const trx_mss_member *>(g->d_tab);
+		const float *nt = g->ctx->d_nco_tab;
+		int rc;
+		if (!rot)
+			rc = g->direct ? trx_launch_ms_rx_stream(rx->chunk, !cf32, &rx->sa, rx->ind, rx->bits, rx->n_slots, 1.0f / fs, fs, st)
+				       : trx_launch_ms_rx_group(rt, !cf32, n_rx, n_waves, 1.0f / fs, fs, st);
+		else
+			rc = g->direct ? trx_launch_ms_rx_stream_nco(rx->chunk, !cf32, &rx->sa, rx->ind, rx->bits, rx->n_slots, 1.0f / fs, fs, nc, nt, st)
+				       : trx_launch_ms_rx_group_nco(rt, !cf32, n_rx, n_waves, 1.0f / fs, fs,
+								    reinterpret_cast<const trx_nco_slot *>(g->d_tab + n_ent * 64), nt, st);
 		if (rc != 0)
 			return TRXHIP_EIO;
 	}
@@ -868,6 +895,22 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 	return TRXHIP_OK;
 }
 
+// room for the rotated buffers of an acquire; a call that needs more than any before frees and allocates (nothing is in flight:
+// an acquire ends with a wait)
+int reserve_nco_work(trxhip_ms_group *g, size_t samples)
+{
+	if (samples <= g->nco_work_samples)
+		return TRXHIP_OK;
+	if (g->d_nco_work && hipFree(g->d_nco_work) != hipSuccess)
+		return TRXHIP_EIO;
+	g->d_nco_work = nullptr;
+	g->nco_work_samples = 0;
+	if (hipMalloc((void **)&g->d_nco_work, samples * 2 * sizeof(float)) != hipSuccess)
+		return TRXHIP_ENOMEM;
+	g->nco_work_samples = samples;
+	return TRXHIP_OK;
+}
+
 int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const void *d_bufs, int cf32, size_t buf_stride, size_t buf_len,
 		  const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream)
 {
@@ -888,13 +931,35 @@ int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const v
 		if (!d_bufs || (reinterpret_cast<uintptr_t>(d_bufs) & (cf32 ? 7 : 3)) || buf_stride < buf_len)
 			return TRXHIP_EINVAL;
 		const float scale = 1.0f / g->rx_full_scale;
+		const hipStream_t st = static_cast<hipStream_t>(stream);
+		bool rot = false;
+		for (size_t i = 0; i < n; i++)
+			rot = rot || g->m[members[i]].nco.enable;
+		if (rot) {
+			// the buffers by absolute timestamp through the batch call into the work buffer; the search then reads complex64
+			if (with_device(g->ctx))
+				return TRXHIP_EIO;
+			const int rw = reserve_nco_work(g, n * buf_len);
+			if (rw != TRXHIP_OK)
+				return rw;
+			for (size_t i = 0; i < n; i++) {
+				const trx_nco_state &o = g->m[members[i]].nco;
+				g->h_nco_rec[i].phase0 = o.enable ? trx_nco_phase(o.acc, o.ts_ref, o.inc, first_ts[i]) : 0u;
+				g->h_nco_rec[i].inc = o.enable ? o.inc : 0;
+			}
+			if (hipMemcpyAsync(g->d_nco_rec, g->h_nco_rec, n * sizeof(trxhip_ms_nco_row), hipMemcpyHostToDevice, st) != hipSuccess ||
+			    trx_launch_ms_nco_rows(d_bufs, !cf32, buf_stride, g->d_nco_rec, g->d_nco_work, buf_len, n, buf_len, g->ctx->d_nco_tab, st) != 0)
+				return TRXHIP_EIO;
+			d_bufs = g->d_nco_work;
+			buf_stride = buf_len;
+			cf32 = 1;
+		}
 		const int rc = cf32 ? trxhip_sch_sync_batch_cf32(g->ctx, static_cast<const float *>(d_bufs), buf_stride, g->d_acq, nullptr, n, buf_len,
 								 TRXHIP_SCH_SYNC_ACQ, scale, stream)
 				    : trxhip_sch_sync_batch_i16(g->ctx, static_cast<const int16_t *>(d_bufs), buf_stride, g->d_acq, nullptr, n, buf_len,
 								TRXHIP_SCH_SYNC_ACQ, scale, stream);
 		if (rc != TRXHIP_OK)
 			return rc;
-		const hipStream_t st = static_cast<hipStream_t>(stream);
 		if (hipMemcpyAsync(g->h_acq, g->d_acq, n * sizeof(*g->h_acq), hipMemcpyDeviceToHost, st) != hipSuccess ||
 		    hipEventRecord(g->ev, st) != hipSuccess || hipEventSynchronize(g->ev) != hipSuccess)
 			return TRXHIP_EIO;
@@ -958,7 +1023,9 @@ int group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const t
 		  hipMalloc((void **)&g->d_agc, n * sizeof(trx_agc_state)) == hipSuccess &&
 		  hipEventCreateWithFlags(&g->ev_agc, hipEventDisableTiming) == hipSuccess &&
 		  hipMalloc((void **)&g->d_afc, n * sizeof(trx_afc_state)) == hipSuccess &&
-		  hipEventCreateWithFlags(&g->ev_afc, hipEventDisableTiming) == hipSuccess;
+		  hipEventCreateWithFlags(&g->ev_afc, hipEventDisableTiming) == hipSuccess &&
+		  hipMalloc((void **)&g->d_nco_rec, n * sizeof(trxhip_ms_nco_row)) == hipSuccess &&
+		  hipHostMalloc((void **)&g->h_nco_rec, n * sizeof(trxhip_ms_nco_row), hipHostMallocDefault) == hipSuccess;
 	if (!direct)
 		ok = ok && hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
 		     hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess;
@@ -1011,10 +1078,10 @@ void trxhip_ms_group_destroy(trxhip_ms_group *g)
 				(void)hipEventSynchronize(g->ev_afc);
 			(void)hipEventDestroy(g->ev_afc);
 		}
-		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work, g->d_afc };
+		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work, g->d_afc, g->d_nco_rec, g->d_nco_work };
 		for (void *p : bufs)
 			if (p) (void)hipFree(p);
-		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab };
+		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab, g->h_nco_rec };
 		for (void *p : pinned)
 			if (p) (void)hipHostFree(p);
 	}
@@ -1249,6 +1316,36 @@ int trxhip_ms_afc_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_afc
 int trxhip_ms_afc_sched_set(trxhip_ms_sched *s, const trxhip_ms_afc_cfg *cfg) { return trxhip_ms_afc_group_set(group_of(s), 0, cfg); }
 
 int trxhip_ms_afc_sched_state(trxhip_ms_sched *s, trxhip_ms_afc_status *out) { return trxhip_ms_afc_group_state(group_of(s), 0, out); }
+
+// ---- the NCO (trx_ms_nco.h): host state only, a pull takes it by value -----------------------------
+
+int trxhip_ms_nco_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_nco_cfg *cfg)
+{
+	ms_member *m = member_of(g, member);
+	int32_t inc;
+	if (!m || !cfg || trx_nco_inc(cfg->hz, &inc) != 0)
+		return TRXHIP_EINVAL;
+	trx_nco_set(&m->nco, cfg->enable != 0, cfg->hz, inc, m->ts);
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_nco_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_nco_status *out)
+{
+	const ms_member *m = member_of(g, member);
+	if (!m || !out)
+		return TRXHIP_EINVAL;
+	memset(out, 0, sizeof(*out));
+	out->enable = m->nco.enable;
+	out->inc = m->nco.inc;
+	out->acc = m->nco.acc;
+	out->ts_ref = m->nco.ts_ref;
+	out->hz = m->nco.hz;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_nco_sched_set(trxhip_ms_sched *s, const trxhip_ms_nco_cfg *cfg) { return trxhip_ms_nco_group_set(group_of(s), 0, cfg); }
+
+int trxhip_ms_nco_sched_state(trxhip_ms_sched *s, trxhip_ms_nco_status *out) { return trxhip_ms_nco_group_state(group_of(s), 0, out); }
 
 // ---- the single object: member 0 of a group of one that issues directly -------------------------
 

@@ -236,6 +236,15 @@ SYMBOLS = {
     "trxhip_ms_afc_sched_state": (_I, [_VP, _VP]),
     "trxhip_ms_afc_group_set": (_I, [_VP, C.c_uint32, _VP]),
     "trxhip_ms_afc_group_state": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_nco_tables_host": (_I, [_VP]),
+    "trxhip_ms_nco_inc": (_I, [C.c_double, C.POINTER(C.c_int32)]),
+    "trxhip_ms_nco_phase": (C.c_uint32, [C.c_uint32, C.c_int64, C.c_int32, C.c_int64]),
+    "trxhip_ms_nco_batch_i16": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _SZ, _SZ, _VP]),
+    "trxhip_ms_nco_batch_cf32": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _SZ, _SZ, _VP]),
+    "trxhip_ms_nco_sched_set": (_I, [_VP, _VP]),
+    "trxhip_ms_nco_sched_state": (_I, [_VP, _VP]),
+    "trxhip_ms_nco_group_set": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_nco_group_state": (_I, [_VP, C.c_uint32, _VP]),
     "trxhip_ms_tx_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
     "trxhip_ms_tx_destroy": (None, [_VP]),
     "trxhip_ms_tx_set_ta": (_I, [_VP, _I]),
@@ -265,7 +274,7 @@ def load_library():
     except OSError as e:  # pragma: no cover
         raise TrxHipError(f"cannot load {path}: {e}") from e
     for name, (res, args) in SYMBOLS.items():
-        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_", "trxhip_ms_afc_", "trxhip_ms_fcch_"))) and \
+        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_", "trxhip_ms_afc_", "trxhip_ms_fcch_", "trxhip_ms_nco_"))) and \
                 os.environ.get("TRXHIP_LIB") and not hasattr(L, name):
             continue          # tools/measure.py ab against an older measurement build of the library (product: always bound)
         f = getattr(L, name)  # AttributeError if the export is missing
@@ -661,6 +670,30 @@ class TrxHip:
             (self.L.trxhip_ms_fcch_batch_cf32, "trxhip_ms_fcch_batch_cf32")
         _check(fn(self.h, self._dev(iq), stride, self._dev(out), n, rx_full_scale, self._stream(stream)), name)
         return out.cpu().numpy().reshape(-1).view(MS_FCCH_DTYPE)
+
+    def ms_nco(self, rows, phase0, inc, stream=None):
+        """The NCO alone (trxhip_ms_nco_batch_*): rows int16[n, len, 2] or complex64[n, len], row r rotated by the phase
+        phase0[r] + i * inc[r] at sample i (uint32 / int32, one value or one per row), no scale.  Returns a complex64[n, len]
+        device tensor; does not wait."""
+        torch = self.torch
+        if rows.dtype == torch.int16 and rows.dim() == 3 and rows.shape[-1] == 2:
+            i16 = True
+        elif rows.dtype == torch.complex64 and rows.dim() == 2:
+            i16 = False
+        else:
+            raise TrxHipError(f"rows must be int16[n, len, 2] or complex64[n, len], not {rows.dtype}{list(rows.shape)}")
+        assert rows.is_contiguous()
+        n, length = int(rows.shape[0]), int(rows.shape[1])
+        rec = np.zeros(n, dtype=MS_NCO_ROW_DTYPE)
+        rec["phase0"] = np.asarray(phase0, dtype=np.uint64) & 0xFFFFFFFF
+        rec["inc"] = inc
+        d_rec = torch.from_numpy(rec.view(np.uint8).reshape(n, 8)).to(rows.device)
+        out = torch.empty((n, length), dtype=torch.complex64, device=rows.device)
+        fn, name = (self.L.trxhip_ms_nco_batch_i16, "trxhip_ms_nco_batch_i16") if i16 else \
+            (self.L.trxhip_ms_nco_batch_cf32, "trxhip_ms_nco_batch_cf32")
+        _check(fn(self.h, self._dev(rows), length, self._dev(d_rec), self._dev(out), length, n, length, self._stream(stream)), name)
+        self._nco_rec = d_rec                                # (kept alive until the next call: the launch reads it)
+        return out
 
     @staticmethod
     def results_to_numpy(results):
@@ -1243,6 +1276,46 @@ def _afc_state_dict(a):
     return d
 
 
+# MS-side NCO: trxhip_ms_nco_row, trxhip_ms_nco_cfg / _status, TRXHIP_MS_FCCH_BIAS_HZ
+MS_FCCH_BIAS_HZ = 25.0 / 3.0
+MS_NCO_ROW_DTYPE = np.dtype([("phase0", "<u4"), ("inc", "<i4")])
+MS_NCO_STATE_DTYPE = np.dtype([("enable", "u1"), ("reserved", "u1", (3,)), ("inc", "<i4"), ("acc", "<u4"), ("reserved2", "<u4"),
+                               ("ts_ref", "<i8"), ("hz", "<f8")])
+assert MS_NCO_ROW_DTYPE.itemsize == 8 and MS_NCO_STATE_DTYPE.itemsize == 32
+
+
+class _MsNcoCfg(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("reserved", C.c_int32), ("hz", C.c_double)]
+
+
+def nco_hz_from_fcch(hz):
+    """The NCO setting that cancels a measured FCCH offset: -(hz - 25 / 3) -- a tone on the FCCH frequency reads +8.33 Hz"""
+    return -(float(hz) - MS_FCCH_BIAS_HZ)
+
+
+def ms_nco_inc(hz):
+    """trxhip_ms_nco_inc(): the phase increment per sample of a shift by hz; pure host.  |hz| > 500000 and NaN raise."""
+    inc = C.c_int32()
+    _check(load_library().trxhip_ms_nco_inc(hz, C.byref(inc)), "trxhip_ms_nco_inc")
+    return inc.value
+
+
+def ms_nco_phase(acc, ts_ref, inc, ts):
+    """trxhip_ms_nco_phase(): acc + (ts - ts_ref) * inc modulo 2^32; pure host"""
+    return int(load_library().trxhip_ms_nco_phase(acc & 0xFFFFFFFF, ts_ref, inc, ts))
+
+
+def ms_nco_tables_host():
+    """trxhip_ms_nco_tables_host(): (coarse float32[1024, 2], fine float32[1024, 2]) of (cos, sin) pairs; pure host"""
+    a = np.zeros(4096, dtype=np.float32)
+    _check(load_library().trxhip_ms_nco_tables_host(a.ctypes.data_as(_VP)), "trxhip_ms_nco_tables_host")
+    return a[:2048].reshape(1024, 2).copy(), a[2048:].reshape(1024, 2).copy()
+
+
+def _nco_state_dict(a):
+    return {"enable": bool(a["enable"]), "inc": int(a["inc"]), "acc": int(a["acc"]), "ts_ref": int(a["ts_ref"]), "hz": float(a["hz"])}
+
+
 class _MsAgcCfg(C.Structure):
     _fields_ = [("enable", C.c_int32), ("rx_gain", C.c_float), ("d_level", C.c_void_p)]
 
@@ -1392,6 +1465,20 @@ class MsRxScheduler:
         a = np.zeros(1, dtype=MS_AFC_STATE_DTYPE)
         _check(self.L.trxhip_ms_afc_sched_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_afc_sched_state")
         return _afc_state_dict(a[0])
+
+    # ---- frequency correction (trxhip_ms_nco_sched_*) ----
+    def set_nco(self, enable, hz=0.0):
+        """The NCO in the receive path: every sample a pull or an acquire receives is rotated by the phase of its absolute
+        timestamp, a shift by hz (+ = up; nco_hz_from_fcch() of a measured offset cancels it).  Acts at the object's clock; the
+        phase stays continuous across a change.  Host state only: no wait."""
+        cfg = _MsNcoCfg(int(bool(enable)), 0, hz)
+        _check(self.L.trxhip_ms_nco_sched_set(self.h, C.byref(cfg)), "trxhip_ms_nco_sched_set")
+
+    def nco_state(self):
+        """dict: enable, inc, acc (the phase at ts_ref), ts_ref, hz"""
+        a = np.zeros(1, dtype=MS_NCO_STATE_DTYPE)
+        _check(self.L.trxhip_ms_nco_sched_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_nco_sched_state")
+        return _nco_state_dict(a[0])
 
     def slots(self, n_samples):
         n = self.L.trxhip_ms_sched_slots(self.h, n_samples)
@@ -1617,6 +1704,18 @@ class MsRxSchedulerGroup:
         a = np.zeros(1, dtype=MS_AFC_STATE_DTYPE)
         _check(self.L.trxhip_ms_afc_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_afc_group_state")
         return _afc_state_dict(a[0])
+
+    # ---- frequency correction (trxhip_ms_nco_group_*), per member ----
+    def set_nco(self, m, enable, hz=0.0):
+        """member m's NCO as MsRxScheduler.set_nco(); members are on or off independently"""
+        cfg = _MsNcoCfg(int(bool(enable)), 0, hz)
+        _check(self.L.trxhip_ms_nco_group_set(self.h, m, C.byref(cfg)), "trxhip_ms_nco_group_set")
+
+    def nco_state(self, m):
+        """member m's dict as MsRxScheduler.nco_state()"""
+        a = np.zeros(1, dtype=MS_NCO_STATE_DTYPE)
+        _check(self.L.trxhip_ms_nco_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_nco_group_state")
+        return _nco_state_dict(a[0])
 
     def slots(self, m, n_samples):
         n = self.L.trxhip_ms_group_slots(self.h, m, n_samples)
