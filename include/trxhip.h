@@ -1289,6 +1289,87 @@ int  trxhip_ms_nco_sched_state(trxhip_ms_sched *s, trxhip_ms_nco_status *out);
 int  trxhip_ms_nco_group_set(trxhip_ms_group *g, uint32_t member, const trxhip_ms_nco_cfg *cfg);
 int  trxhip_ms_nco_group_state(trxhip_ms_group *g, uint32_t member, trxhip_ms_nco_status *out);
 
+/* ---- MS-side FCCH search: cold-start frequency acquisition ---------------------------------------------------------------------
+ * The AFC above measures FCCH slots that a clock points at, the clock comes from acquire, and acquire is the SCH receiver, which
+ * decodes nothing from a carrier a few kHz off: an MS whose oscillator is that far off at power-up could never start the loop.
+ * This finds the frequency-correction burst in a buffer with NO clock, at any carrier offset the estimator covers, measures it with
+ * the estimator above and -- in the scheduler calls -- sets the NCO and runs the existing acquire through it.  The reference has no
+ * such search (it trusts the radio's oscillator): the definition is this project's.
+ * The search of one row of buf_len samples, x[n] = re + i im (int16 parts as integers, nothing is scaled: the score is a ratio):
+ *   constants  HOP = 16, W = 576 (36 blocks of 16, two halves of 18), lag L = 8 samples (two symbols)
+ *   per sample p[n] = x[n + L] conj(x[n]),  e[n] = |x[n]|^2            (int16: exact in int64)
+ *   per block  block b = samples 16 b .. 16 b + 15: the sums of p and of e over them; nb = (buf_len - L) / 16 whole blocks, samples
+ *              behind the last whole block are ignored
+ *   per window window j, pos = 16 j, for every j with j + 36 <= nb:  Ra = sum of p over blocks j .. j + 17,  Rb = sum of p over blocks
+ *              j + 18 .. j + 35,  E = sum of e over all 36 blocks     (int16: integers below 2^41, the same bits in any order)
+ *   score      4 (Ra.re Rb.re + Ra.im Rb.im) / (E E) in IEEE double from the sums converted to double, in exactly that order of
+ *              operations, no contraction; E == 0 gives 0, and so does a NaN (complex64 rows with non-finite samples).  On a clean
+ *              tone it is |Ra + Rb|^2 / E^2 = 1, everywhere it is at most that; it does not depend on the carrier offset
+ *   answer     the window with the largest score, the comparison strict >, so the lowest pos wins ties; found = score >= min_score
+ *   complex64  the same definition; the products are unfused float operations, block and window sums in the order the kernel has
+ *              (16-term block sums in float, everything above them in double), so these rows are specified to a bar -- each sum within
+ *              2^-19 of the sum of |x[n + L]| |x[n]| (of |x[n]|^2 for E) over its terms --, not to the bit
+ * The record (trxhip_ms_fcch_hit, 64 bytes): found, pos, score and the five sums as doubles (int16: exact integers).
+ * The measurement: in the same call, with no host round trip, gsm_fcch_offset() as trxhip_ms_fcch_batch_*() computes it on the 625
+ *   samples that begin at the row's pos -- it reads pos + 52 .. pos + 175 and nothing else, which lies inside the window -- into
+ *   d_fcch[r] (may be NULL): the same bytes as trxhip_ms_fcch_batch_*() on that slot.  A row with found == 0 is measured too; its
+ *   record is what the estimator says there.  rx_full_scale is used by the measurement only.
+ * What the score cannot tell apart: a burst of all ones is the same tone, and an alternating bit pattern is a tone 135 kHz lower,
+ *   where the estimator aliases.  The SCH decode that follows in the scheduler calls is the verification.
+ * min_score: TRXHIP_MS_FSEARCH_MIN_SCORE lies midway between the two figures of tests/test_ms_fsearch_cpu.py, measured on the numpy
+ *   model with the oracle's modulator: 0.08, the largest score more than 700 samples away from an FCCH burst (traffic on every
+ *   slot, 10 and 25 dB), and 0.81, the smallest score of an FCCH burst at 10 dB.
+ * trxhip_ms_fcch_search_*(): row r = the buf_len samples at d_iq + r * buf_stride samples.  Two launches (a workgroup per row and
+ *   segment of 256 windows writes one candidate; a wave per row picks, writes the hit and measures), no atomics, no wait; the
+ *   candidates live in a work array of the context (64 bytes per row and segment) that grows on demand and is kept -- calls on
+ *   one stream follow each other without a wait, a call on another stream waits for the one before.  TRXHIP_EINVAL, nothing
+ *   written: buf_len < 584 (W + L) or > 2^31 - 1, buf_stride < buf_len, n_bufs == 0 or > 2^31 - 1, min_score not in (0, 1] (NaN
+ *   too), rx_full_scale not finite and positive, d_iq or d_hit NULL, d_iq not 4-byte (int16) / 8-byte (complex64) aligned, d_hit or
+ *   d_fcch not 8-byte aligned.
+ * The scheduler calls (trxhip_ms_afc_sched_acquire_*, trxhip_ms_afc_group_acquire_*; named like trxhip_ms_afc_*_set: the objects'
+ *   own lists of entry points, trxhip_ms_sched_* and trxhip_ms_group_*, stay as they are) are the composition of public calls:
+ *   1. trxhip_ms_fcch_search_*() over the buffers AS RECEIVED -- an NCO that is already on does not rotate them: AFC reads the
+ *      stream as received -- with the object's rx_full_scale;
+ *   2. one wait; hit and fcch of every buffer to the host (h_hit, h_fcch: n records each, either may be NULL);
+ *   3. for every member with found: trxhip_ms_nco_*_set({1, -(fcch.hz - TRXHIP_MS_FCCH_BIAS_HZ)}) -- an absolute setting, not an
+ *      increment on what the member had;
+ *   4. trxhip_ms_group_acquire_*() for exactly those members, in the caller's order: one call per run of consecutive listed
+ *      members with found (one call where every member is found; each call has its own wait).
+ *   Members without found are not acquired and nothing of theirs is touched: h_found[i] = 0, h_res[i] is not written.  A member
+ *   whose FCCH is found but whose SCH is not keeps its new NCO setting: the frequency is known, and the caller retries with the
+ *   plain acquire on the next buffer.  Returns the number of members whose SCH was found; h_found[i] (may be NULL) says which.
+ *   Refusals are those of acquire plus those of the search, all-or-nothing, decided before anything is set: TRXHIP_EINVAL with no
+ *   member's state, NCO or output changed.  (A measured offset that trxhip_ms_nco_*_set refuses -- only non-finite complex64
+ *   samples give one -- refuses the call in the same way, behind the search's wait.)  Plan-only objects have no samples:
+ *   TRXHIP_EINVAL, as trxhip_ms_afc_*_set. */
+#define TRXHIP_MS_FSEARCH_HOP 16
+#define TRXHIP_MS_FSEARCH_W   576
+#define TRXHIP_MS_FSEARCH_LAG 8
+#define TRXHIP_MS_FSEARCH_MIN_SCORE 0.44
+typedef struct trxhip_ms_fcch_hit {  /* 64 bytes */
+	int32_t  found;          /* score >= min_score */
+	uint32_t pos;            /* the best window's first sample in the row */
+	double   score;
+	double   ra_re, ra_im;   /* Ra, Rb and E of that window */
+	double   rb_re, rb_im;
+	double   energy;
+	uint64_t reserved;       /* 0 */
+} trxhip_ms_fcch_hit;
+int  trxhip_ms_fcch_search_i16(trxhip_ctx *ctx, const int16_t *d_iq, size_t buf_stride, size_t buf_len, size_t n_bufs, double min_score,
+			       float rx_full_scale, trxhip_ms_fcch_hit *d_hit, trxhip_ms_fcch *d_fcch, void *stream);
+int  trxhip_ms_fcch_search_cf32(trxhip_ctx *ctx, const float *d_iq_cf32, size_t buf_stride, size_t buf_len, size_t n_bufs,
+				double min_score, float rx_full_scale, trxhip_ms_fcch_hit *d_hit, trxhip_ms_fcch *d_fcch, void *stream);
+int  trxhip_ms_afc_sched_acquire_s16(trxhip_ms_sched *s, const int16_t *d_buf, size_t n_samples, int64_t first_ts, double min_score,
+				     trxhip_ms_fcch_hit *h_hit, trxhip_ms_fcch *h_fcch, trxhip_sch_sync_result *h_res, void *stream);
+int  trxhip_ms_afc_sched_acquire_cf32(trxhip_ms_sched *s, const float *d_buf, size_t n_samples, int64_t first_ts, double min_score,
+				      trxhip_ms_fcch_hit *h_hit, trxhip_ms_fcch *h_fcch, trxhip_sch_sync_result *h_res, void *stream);
+int  trxhip_ms_afc_group_acquire_s16(trxhip_ms_group *g, const uint32_t *members, size_t n, const int16_t *d_bufs, size_t buf_stride,
+				     size_t buf_len, const int64_t *first_ts, double min_score, trxhip_ms_fcch_hit *h_hit,
+				     trxhip_ms_fcch *h_fcch, trxhip_sch_sync_result *h_res, int *h_found, void *stream);
+int  trxhip_ms_afc_group_acquire_cf32(trxhip_ms_group *g, const uint32_t *members, size_t n, const float *d_bufs, size_t buf_stride,
+				      size_t buf_len, const int64_t *first_ts, double min_score, trxhip_ms_fcch_hit *h_hit,
+				      trxhip_ms_fcch *h_fcch, trxhip_sch_sync_result *h_res, int *h_found, void *stream);
+
 /* ---- The MS-side uplink burst scheduler: burst requests in, the radio's transmit sample stream out --------------------------
  * What the reference does between trxcon's burst request and the radio: upper_trx::driveTx() (ms/ms_upper.cpp:306-355),
  * ms_trx::submit_burst() (ms/ms.cpp:114-160), set_ta() (ms/ms.h:299-303) and submit_burst_ts() (ms/uhd_specific.h:260-269,

@@ -191,6 +191,7 @@ void trxhip_destroy(trxhip_ctx *ctx)
 			if (t) (void)hipFree(t);
 		ctx->redo.destroy();
 		ctx->sch_sync.destroy();
+		ctx->fsearch.destroy();
 	}
 	delete ctx;
 }

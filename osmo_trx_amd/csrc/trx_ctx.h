@@ -159,6 +159,56 @@ struct trx_sch_scratch {
 	}
 };
 
+/* Work array of trxhip_ms_fcch_search_*() (trx_ms_fsearch.hip): one 64-byte candidate per (buffer, segment).  One per context,
+ * grown on demand and kept, under the rules of trx_sch_scratch: `mu` is held from acquire() to launched(), and the array is handed
+ * out to another stream, or freed to grow, only once the launches that used it last have completed; calls on one stream follow each
+ * other without a wait. */
+struct trx_fsearch_scratch {
+	std::mutex mu;
+	trxhip_ms_fcch_hit *d_cand = nullptr;
+	size_t cap = 0;                    /* candidates */
+	hipEvent_t ev = nullptr;
+	hipStream_t last = nullptr;        /* the stream of the launches the event is behind */
+	bool busy = false;
+
+	bool acquire(size_t n_cand, hipStream_t stream)
+	{
+		if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+			ev = nullptr;
+			return false;
+		}
+		if (busy && (stream != last || cap < n_cand)) {            /* the same stream orders the calls itself: no wait */
+			busy = false;
+			if (hipEventSynchronize(ev) != hipSuccess)
+				return false;
+		}
+		if (cap < n_cand) {
+			if (d_cand) (void)hipFree(d_cand);
+			cap = 0;
+			if (hipMalloc(reinterpret_cast<void **>(&d_cand), n_cand * sizeof(trxhip_ms_fcch_hit)) != hipSuccess) {
+				d_cand = nullptr;
+				return false;
+			}
+			cap = n_cand;
+		}
+		return true;
+	}
+	void launched(hipStream_t stream)
+	{
+		last = stream;
+		if (hipEventRecord(ev, stream) == hipSuccess)
+			busy = true;
+		else
+			(void)hipStreamSynchronize(stream);
+	}
+	void destroy()
+	{
+		if (busy) (void)hipEventSynchronize(ev);
+		if (ev) (void)hipEventDestroy(ev);
+		if (d_cand) (void)hipFree(d_cand);
+	}
+};
+
 struct trxhip_ctx {
 	int device = 0;
 	int n_cu = 0;
@@ -190,6 +240,7 @@ struct trxhip_ctx {
 	std::mutex rs_mu;
 	float *d_rs_resamp[2] = { nullptr, nullptr };
 	trx_sch_scratch sch_sync;
+	trx_fsearch_scratch fsearch;
 	float *d_nco_tab = nullptr;        /* the NCO's two phasor tables (trx_ms_nco.h): 4096 floats, made on the host and uploaded at creation */
 };
 

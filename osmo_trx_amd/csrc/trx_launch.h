@@ -120,6 +120,12 @@ int trx_launch_ms_rx_stream_nco(const void *d_chunk, int i16, const struct trx_m
 int trx_launch_ms_rx_group_nco(const struct trx_mss_member *d_tab, int i16, size_t n_entries, size_t n_waves, float scale,
 			       float rx_full_scale, const struct trx_nco_slot *d_nco, const float *d_nco_tab, hipStream_t stream);
 
+/* trx_ms_fsearch.hip: the MS-side FCCH search (trx_ms_fsearch.h).  n_bufs rows of buf_len samples (>= 584), buf_stride samples
+ * apart; d_cand: room for n_bufs * trx_fs_segments(buf_len) candidates; the hit of row r to d_hit[r] and, where d_fcch is given, the
+ * estimator's record of the slot at its pos to d_fcch[r].  Two launches */
+int trx_launch_ms_fsearch(const void *d_iq, int i16, size_t buf_stride, size_t buf_len, size_t n_bufs, double min_score, float scale,
+			  trxhip_ms_fcch_hit *d_cand, trxhip_ms_fcch_hit *d_hit, trxhip_ms_fcch *d_fcch, hipStream_t stream);
+
 /* ---- trx_aux_kernels.hip ---- */
 int trx_launch_pack_trxd(const trxhip_burst_result *d_results, const float *d_soft, int soft_stride, uint8_t *d_pkt,
 			 size_t n_bursts, float rssi_offset, hipStream_t stream);

@@ -201,6 +201,9 @@ struct trxhip_ms_group {
 	trxhip_ms_nco_row *d_nco_rec = nullptr, *h_nco_rec = nullptr;
 	float *d_nco_work = nullptr;
 	size_t nco_work_samples = 0;
+	// acquire_afc: the search's hit and measurement per listed buffer and their pinned copies ([n] each)
+	trxhip_ms_fcch_hit *d_fs_hit = nullptr, *h_fs_hit = nullptr;
+	trxhip_ms_fcch *d_fs_fcch = nullptr, *h_fs_fcch = nullptr;
 };
 
 namespace {
@@ -911,8 +914,8 @@ int reserve_nco_work(trxhip_ms_group *g, size_t samples)
 	return TRXHIP_OK;
 }
 
-int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const void *d_bufs, int cf32, size_t buf_stride, size_t buf_len,
-		  const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+// what an acquire refuses before it looks at a buffer
+int acquire_list(const trxhip_ms_group *g, const uint32_t *members, size_t n, size_t buf_len, const int64_t *first_ts)
 {
 	if (!g || !members || !first_ts || n == 0 || n > g->m.size() || buf_len < 512 + 20 || buf_len > TRXHIP_SCH_SYNC_MAX_LEN)
 		return TRXHIP_EINVAL;
@@ -922,6 +925,15 @@ int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const v
 			return TRXHIP_EINVAL;                                  /* a member listed twice */
 		seen[members[i]] = true;
 	}
+	return TRXHIP_OK;
+}
+
+int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const void *d_bufs, int cf32, size_t buf_stride, size_t buf_len,
+		  const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+{
+	const int la = acquire_list(g, members, n, buf_len, first_ts);
+	if (la != TRXHIP_OK)
+		return la;
 	const trxhip_sch_sync_result *res;
 	if (!g->ctx) {
 		if (d_bufs || !h_res)
@@ -982,6 +994,64 @@ int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const v
 	return found;
 }
 
+// Cold start (include/trxhip.h, "MS-side FCCH search"): the composition of the public calls -- the search over the buffers as
+// received, one wait, the NCO of every member whose FCCH is found set from its measurement, then the acquire above for exactly
+// those members, one call per run of consecutive listed members.  Every refusal comes before anything is set.
+int group_acquire_afc(trxhip_ms_group *g, const uint32_t *members, size_t n, const void *d_bufs, int cf32, size_t buf_stride, size_t buf_len,
+		      const int64_t *first_ts, double min_score, trxhip_ms_fcch_hit *h_hit, trxhip_ms_fcch *h_fcch,
+		      trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+{
+	const int la = acquire_list(g, members, n, buf_len, first_ts);
+	if (la != TRXHIP_OK)
+		return la;
+	if (!g->ctx || !d_bufs || (reinterpret_cast<uintptr_t>(d_bufs) & (cf32 ? 7 : 3)) || buf_stride < buf_len)
+		return TRXHIP_EINVAL;                                  /* (plan-only: no samples to search) */
+	const int rs = cf32 ? trxhip_ms_fcch_search_cf32(g->ctx, static_cast<const float *>(d_bufs), buf_stride, buf_len, n, min_score,
+							 g->rx_full_scale, g->d_fs_hit, g->d_fs_fcch, stream)
+			    : trxhip_ms_fcch_search_i16(g->ctx, static_cast<const int16_t *>(d_bufs), buf_stride, buf_len, n, min_score,
+							g->rx_full_scale, g->d_fs_hit, g->d_fs_fcch, stream);
+	if (rs != TRXHIP_OK)
+		return rs;
+	const hipStream_t st = static_cast<hipStream_t>(stream);
+	if (hipMemcpyAsync(g->h_fs_hit, g->d_fs_hit, n * sizeof(*g->h_fs_hit), hipMemcpyDeviceToHost, st) != hipSuccess ||
+	    hipMemcpyAsync(g->h_fs_fcch, g->d_fs_fcch, n * sizeof(*g->h_fs_fcch), hipMemcpyDeviceToHost, st) != hipSuccess ||
+	    hipEventRecord(g->ev, st) != hipSuccess || hipEventSynchronize(g->ev) != hipSuccess)
+		return TRXHIP_EIO;
+	std::vector<int32_t> inc(n, 0);
+	for (size_t i = 0; i < n; i++)
+		if (g->h_fs_hit[i].found && trx_nco_inc(-((double)g->h_fs_fcch[i].hz - TRXHIP_MS_FCCH_BIAS_HZ), &inc[i]) != 0)
+			return TRXHIP_EINVAL;                                  /* what trxhip_ms_nco_group_set would refuse */
+	if (h_hit)
+		memcpy(h_hit, g->h_fs_hit, n * sizeof(*h_hit));
+	if (h_fcch)
+		memcpy(h_fcch, g->h_fs_fcch, n * sizeof(*h_fcch));
+	if (h_found)
+		memset(h_found, 0, n * sizeof(*h_found));
+	for (size_t i = 0; i < n; i++)
+		if (g->h_fs_hit[i].found) {
+			ms_member &m = g->m[members[i]];
+			trx_nco_set(&m.nco, true, -((double)g->h_fs_fcch[i].hz - TRXHIP_MS_FCCH_BIAS_HZ), inc[i], m.ts);
+		}
+	int found = 0;
+	const char *bufs = static_cast<const char *>(d_bufs);
+	for (size_t a = 0; a < n;) {
+		if (!g->h_fs_hit[a].found) {
+			a++;
+			continue;
+		}
+		size_t b = a + 1;
+		while (b < n && g->h_fs_hit[b].found)
+			b++;
+		const int rc = group_acquire(g, members + a, b - a, bufs + a * buf_stride * (cf32 ? 8 : 4), cf32, buf_stride, buf_len, first_ts + a,
+					     h_res ? h_res + a : nullptr, h_found ? h_found + a : nullptr, stream);
+		if (rc < 0)
+			return rc;
+		found += rc;
+		a = b;
+	}
+	return found;
+}
+
 ms_member *member_of(trxhip_ms_group *g, uint32_t i) { return (g && i < g->m.size()) ? &g->m[i] : nullptr; }
 const ms_member *member_of(const trxhip_ms_group *g, uint32_t i) { return (g && i < g->m.size()) ? &g->m[i] : nullptr; }
 
@@ -1025,7 +1095,11 @@ int group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const t
 		  hipMalloc((void **)&g->d_afc, n * sizeof(trx_afc_state)) == hipSuccess &&
 		  hipEventCreateWithFlags(&g->ev_afc, hipEventDisableTiming) == hipSuccess &&
 		  hipMalloc((void **)&g->d_nco_rec, n * sizeof(trxhip_ms_nco_row)) == hipSuccess &&
-		  hipHostMalloc((void **)&g->h_nco_rec, n * sizeof(trxhip_ms_nco_row), hipHostMallocDefault) == hipSuccess;
+		  hipHostMalloc((void **)&g->h_nco_rec, n * sizeof(trxhip_ms_nco_row), hipHostMallocDefault) == hipSuccess &&
+		  hipMalloc((void **)&g->d_fs_hit, n * sizeof(trxhip_ms_fcch_hit)) == hipSuccess &&
+		  hipHostMalloc((void **)&g->h_fs_hit, n * sizeof(trxhip_ms_fcch_hit), hipHostMallocDefault) == hipSuccess &&
+		  hipMalloc((void **)&g->d_fs_fcch, n * sizeof(trxhip_ms_fcch)) == hipSuccess &&
+		  hipHostMalloc((void **)&g->h_fs_fcch, n * sizeof(trxhip_ms_fcch), hipHostMallocDefault) == hipSuccess;
 	if (!direct)
 		ok = ok && hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
 		     hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess;
@@ -1078,10 +1152,11 @@ void trxhip_ms_group_destroy(trxhip_ms_group *g)
 				(void)hipEventSynchronize(g->ev_afc);
 			(void)hipEventDestroy(g->ev_afc);
 		}
-		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work, g->d_afc, g->d_nco_rec, g->d_nco_work };
+		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work, g->d_afc, g->d_nco_rec, g->d_nco_work, g->d_fs_hit,
+				 g->d_fs_fcch };
 		for (void *p : bufs)
 			if (p) (void)hipFree(p);
-		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab, g->h_nco_rec };
+		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab, g->h_nco_rec, g->h_fs_hit, g->h_fs_fcch };
 		for (void *p : pinned)
 			if (p) (void)hipHostFree(p);
 	}
@@ -1180,6 +1255,20 @@ int trxhip_ms_group_acquire_cf32(trxhip_ms_group *g, const uint32_t *members, si
 				 size_t buf_len, const int64_t *first_ts, trxhip_sch_sync_result *h_res, int *h_found, void *stream)
 {
 	return group_acquire(g, members, n, d_bufs, 1, buf_stride, buf_len, first_ts, h_res, h_found, stream);
+}
+
+int trxhip_ms_afc_group_acquire_s16(trxhip_ms_group *g, const uint32_t *members, size_t n, const int16_t *d_bufs, size_t buf_stride,
+				    size_t buf_len, const int64_t *first_ts, double min_score, trxhip_ms_fcch_hit *h_hit, trxhip_ms_fcch *h_fcch,
+				    trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+{
+	return group_acquire_afc(g, members, n, d_bufs, 0, buf_stride, buf_len, first_ts, min_score, h_hit, h_fcch, h_res, h_found, stream);
+}
+
+int trxhip_ms_afc_group_acquire_cf32(trxhip_ms_group *g, const uint32_t *members, size_t n, const float *d_bufs, size_t buf_stride,
+				     size_t buf_len, const int64_t *first_ts, double min_score, trxhip_ms_fcch_hit *h_hit, trxhip_ms_fcch *h_fcch,
+				     trxhip_sch_sync_result *h_res, int *h_found, void *stream)
+{
+	return group_acquire_afc(g, members, n, d_bufs, 1, buf_stride, buf_len, first_ts, min_score, h_hit, h_fcch, h_res, h_found, stream);
 }
 
 int trxhip_ms_group_pull_s16(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, trxhip_ms_burst_ind *d_ind, int8_t *d_bits,
@@ -1399,6 +1488,22 @@ int trxhip_ms_sched_acquire_cf32(trxhip_ms_sched *s, const float *d_buf, size_t 
 }
 
 // one chunk, out_slots as the stride; *n_slots and *n_carried (the new partial slot, or the extended one) are member 0's
+int trxhip_ms_afc_sched_acquire_s16(trxhip_ms_sched *s, const int16_t *d_buf, size_t n_samples, int64_t first_ts, double min_score,
+				    trxhip_ms_fcch_hit *h_hit, trxhip_ms_fcch *h_fcch, trxhip_sch_sync_result *h_res, void *stream)
+{
+	const uint32_t member = 0;
+	return group_acquire_afc(group_of(s), &member, 1, d_buf, 0, n_samples, n_samples, &first_ts, min_score, h_hit, h_fcch, h_res, nullptr,
+				 stream);
+}
+
+int trxhip_ms_afc_sched_acquire_cf32(trxhip_ms_sched *s, const float *d_buf, size_t n_samples, int64_t first_ts, double min_score,
+				     trxhip_ms_fcch_hit *h_hit, trxhip_ms_fcch *h_fcch, trxhip_sch_sync_result *h_res, void *stream)
+{
+	const uint32_t member = 0;
+	return group_acquire_afc(group_of(s), &member, 1, d_buf, 1, n_samples, n_samples, &first_ts, min_score, h_hit, h_fcch, h_res, nullptr,
+				 stream);
+}
+
 int trxhip_ms_sched_pull_s16(trxhip_ms_sched *s, const int16_t *d_in, size_t n_samples, int64_t first_ts, trxhip_ms_burst_ind *d_ind,
 			     int8_t *d_bits, size_t out_slots, size_t *n_slots, size_t *n_carried, void *stream)
 {

@@ -245,6 +245,12 @@ SYMBOLS = {
     "trxhip_ms_nco_sched_state": (_I, [_VP, _VP]),
     "trxhip_ms_nco_group_set": (_I, [_VP, C.c_uint32, _VP]),
     "trxhip_ms_nco_group_state": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_fcch_search_i16": (_I, [_VP, _VP, _SZ, _SZ, _SZ, C.c_double, C.c_float, _VP, _VP, _VP]),
+    "trxhip_ms_fcch_search_cf32": (_I, [_VP, _VP, _SZ, _SZ, _SZ, C.c_double, C.c_float, _VP, _VP, _VP]),
+    "trxhip_ms_afc_sched_acquire_s16": (_I, [_VP, _VP, _SZ, C.c_int64, C.c_double, _VP, _VP, _VP, _VP]),
+    "trxhip_ms_afc_sched_acquire_cf32": (_I, [_VP, _VP, _SZ, C.c_int64, C.c_double, _VP, _VP, _VP, _VP]),
+    "trxhip_ms_afc_group_acquire_s16": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _VP, C.c_double, _VP, _VP, _VP, _VP, _VP]),
+    "trxhip_ms_afc_group_acquire_cf32": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _VP, C.c_double, _VP, _VP, _VP, _VP, _VP]),
     "trxhip_ms_tx_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
     "trxhip_ms_tx_destroy": (None, [_VP]),
     "trxhip_ms_tx_set_ta": (_I, [_VP, _I]),
@@ -670,6 +676,34 @@ class TrxHip:
             (self.L.trxhip_ms_fcch_batch_cf32, "trxhip_ms_fcch_batch_cf32")
         _check(fn(self.h, self._dev(iq), stride, self._dev(out), n, rx_full_scale, self._stream(stream)), name)
         return out.cpu().numpy().reshape(-1).view(MS_FCCH_DTYPE)
+
+    def ms_fcch_search(self, iq, min_score=None, rx_full_scale=2047.0, buf_len=None, stream=None):
+        """The FCCH search with no clock (trxhip_ms_fcch_search_*): iq int16[n, stride, 2] or complex64[n, stride], row r searched
+        over its first buf_len samples (default: the whole row) for the 576-sample window that looks most like a tone, and
+        gsm_fcch_offset() measured on the slot that begins there.  Returns (hits uint8[n, 64], fcch uint8[n, 32]) device tensors
+        (MS_FCCH_HIT_DTYPE / MS_FCCH_DTYPE rows: fsearch_to_numpy()); does not wait."""
+        torch = self.torch
+        if iq.dtype == torch.int16 and iq.dim() == 3 and iq.shape[-1] == 2:
+            i16 = True
+        elif iq.dtype == torch.complex64 and iq.dim() == 2:
+            i16 = False
+        else:
+            raise TrxHipError(f"iq must be int16[n, stride, 2] or complex64[n, stride], not {iq.dtype}{list(iq.shape)}")
+        assert iq.is_contiguous()
+        n, stride = int(iq.shape[0]), int(iq.shape[1])
+        length = stride if buf_len is None else int(buf_len)
+        hits = torch.empty((n, MS_FCCH_HIT_DTYPE.itemsize), dtype=torch.uint8, device=iq.device)
+        fcch = torch.empty((n, MS_FCCH_DTYPE.itemsize), dtype=torch.uint8, device=iq.device)
+        fn, name = (self.L.trxhip_ms_fcch_search_i16, "trxhip_ms_fcch_search_i16") if i16 else \
+            (self.L.trxhip_ms_fcch_search_cf32, "trxhip_ms_fcch_search_cf32")
+        _check(fn(self.h, self._dev(iq), stride, length, n, MS_FSEARCH_MIN_SCORE if min_score is None else min_score, rx_full_scale,
+                  self._dev(hits), self._dev(fcch), self._stream(stream)), name)
+        return hits, fcch
+
+    @staticmethod
+    def fsearch_to_numpy(hits, fcch):
+        """(MS_FCCH_HIT_DTYPE[n], MS_FCCH_DTYPE[n]) of ms_fcch_search()'s tensors; synchronises"""
+        return hits.cpu().numpy().reshape(-1).view(MS_FCCH_HIT_DTYPE), fcch.cpu().numpy().reshape(-1).view(MS_FCCH_DTYPE)
 
     def ms_nco(self, rows, phase0, inc, stream=None):
         """The NCO alone (trxhip_ms_nco_batch_*): rows int16[n, len, 2] or complex64[n, len], row r rotated by the phase
@@ -1316,6 +1350,14 @@ def _nco_state_dict(a):
     return {"enable": bool(a["enable"]), "inc": int(a["inc"]), "acc": int(a["acc"]), "ts_ref": int(a["ts_ref"]), "hz": float(a["hz"])}
 
 
+# MS-side FCCH search: trxhip_ms_fcch_hit, TRXHIP_MS_FSEARCH_*
+MS_FSEARCH_HOP, MS_FSEARCH_W, MS_FSEARCH_LAG = 16, 576, 8
+MS_FSEARCH_MIN_SCORE = 0.44
+MS_FCCH_HIT_DTYPE = np.dtype([("found", "<i4"), ("pos", "<u4"), ("score", "<f8"), ("ra_re", "<f8"), ("ra_im", "<f8"), ("rb_re", "<f8"),
+                              ("rb_im", "<f8"), ("energy", "<f8"), ("reserved", "<u8")])
+assert MS_FCCH_HIT_DTYPE.itemsize == 64
+
+
 class _MsAgcCfg(C.Structure):
     _fields_ = [("enable", C.c_int32), ("rx_gain", C.c_float), ("d_level", C.c_void_p)]
 
@@ -1401,6 +1443,28 @@ class MsRxScheduler:
         if rc == 1:
             self.carried = 0
         return bool(rc), rec[0]
+
+    def acquire_afc(self, x=None, first_ts=0, min_score=None, stream=None):
+        """Cold start (trxhip_ms_afc_sched_acquire_*): the FCCH search over the buffer x as received, one wait, set_nco(True,
+        nco_hz_from_fcch(hz)) from its measurement where the burst is found, then acquire() through the NCO.  Returns (found,
+        SCH_SYNC_DTYPE record or None where no FCCH was found, MS_FCCH_HIT_DTYPE record, MS_FCCH_DTYPE record).  A found FCCH
+        with no SCH behind it leaves the NCO set: retry with acquire() on the next buffer."""
+        rec = np.zeros(1, dtype=SCH_SYNC_DTYPE)
+        hit, fc = np.zeros(1, dtype=MS_FCCH_HIT_DTYPE), np.zeros(1, dtype=MS_FCCH_DTYPE)
+        score = MS_FSEARCH_MIN_SCORE if min_score is None else min_score
+        if self.trx is None:                                 # a plan-only object has no samples: the library refuses
+            rc = self.L.trxhip_ms_afc_sched_acquire_s16(self.h, None, 60000, first_ts, score, hit.ctypes.data_as(_VP),
+                                                        fc.ctypes.data_as(_VP), rec.ctypes.data_as(_VP), None)
+        else:
+            s16 = x.dtype == self.trx.torch.int16
+            fn = self.L.trxhip_ms_afc_sched_acquire_s16 if s16 else self.L.trxhip_ms_afc_sched_acquire_cf32
+            rc = fn(self.h, self.trx._dev(x), x.shape[0], first_ts, score, hit.ctypes.data_as(_VP), fc.ctypes.data_as(_VP),
+                    rec.ctypes.data_as(_VP), self.trx._stream(stream))
+        if rc < 0:
+            _check(rc, "trxhip_ms_afc_sched_acquire")
+        if rc == 1:
+            self.carried = 0
+        return bool(rc), (rec[0] if hit[0]["found"] else None), hit[0], fc[0]
 
     # ---- receive gain control (trxhip_ms_agc_sched_*) ----
     def _agc_set(self, enable, rx_gain, lv):
@@ -1633,6 +1697,35 @@ class MsRxSchedulerGroup:
             if f:
                 self.carried[int(m)] = 0
         return found.astype(bool), rec
+
+    def acquire_afc(self, members, bufs=None, first_ts=0, min_score=None, stream=None):
+        """Cold start for the listed members (trxhip_ms_afc_group_acquire_*): the FCCH search over all buffers as received in one
+        call, one wait, set_nco() from its measurement for the members whose burst is found, then acquire() for exactly those.
+        Returns (found bool[n]: the SCH, records SCH_SYNC_DTYPE[n] (zero where no FCCH was found), hits MS_FCCH_HIT_DTYPE[n],
+        fcch MS_FCCH_DTYPE[n]); members without an FCCH are untouched."""
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        n = len(members)
+        ts = np.ascontiguousarray(_per_member(first_ts, n, "first_ts"), dtype=np.int64)
+        rec = np.zeros(n, dtype=SCH_SYNC_DTYPE)
+        found = np.zeros(n, dtype=np.int32)
+        hit, fc = np.zeros(n, dtype=MS_FCCH_HIT_DTYPE), np.zeros(n, dtype=MS_FCCH_DTYPE)
+        score = MS_FSEARCH_MIN_SCORE if min_score is None else min_score
+        out = (hit.ctypes.data_as(_VP), fc.ctypes.data_as(_VP), rec.ctypes.data_as(_VP), found.ctypes.data_as(_VP))
+        if self.trx is None:                                 # a plan-only group has no samples: the library refuses
+            rc = self.L.trxhip_ms_afc_group_acquire_s16(self.h, members.ctypes.data_as(_VP), n, None, 60000, 60000, ts.ctypes.data_as(_VP),
+                                                        score, *out, None)
+        else:
+            s16 = bufs.dtype == self.trx.torch.int16
+            assert bufs.is_contiguous() and bufs.shape[0] == n and bufs.dim() == (3 if s16 else 2), (bufs.shape, bufs.dtype)
+            fn = self.L.trxhip_ms_afc_group_acquire_s16 if s16 else self.L.trxhip_ms_afc_group_acquire_cf32
+            rc = fn(self.h, members.ctypes.data_as(_VP), n, self.trx._dev(bufs), bufs.shape[1], bufs.shape[1], ts.ctypes.data_as(_VP),
+                    score, *out, self.trx._stream(stream))
+        if rc < 0:
+            _check(rc, "trxhip_ms_afc_group_acquire")
+        for m, f in zip(members, found):
+            if f:
+                self.carried[int(m)] = 0
+        return found.astype(bool), rec, hit, fc
 
     # ---- receive gain control (trxhip_ms_agc_group_*), per member ----
     def _agc_set(self, m, enable, rx_gain, lv):
