@@ -1514,6 +1514,47 @@ int  trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t
 				   const size_t *h_n_samples, size_t *h_n_drawn, int *bad_member, void *stream);
 int  trxhip_ms_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_tx_status *out);
 
+/* ---- MS-side uplink frequency correction: the NCO in the transmit render ------------------------------------------------------
+ * The receive-side NCO above cancels the MS oscillator's error on the downlink; the same error leaves on the uplink.  One
+ * oscillator per uplink member -- the single object, every member of a group -- applied inside the render between the modulator's
+ * scaled sample and the int16 cast.  It is the oscillator defined above (phase, increment, phasor, rotation: the same tables, the
+ * same expressions); nothing is defined again here.
+ *   state      per member {enable, inc, acc, ts_ref, hz}, on the render's timeline: first_ts + i, the radio_ts of the plans.  The
+ *              sample with timestamp ts has phase p(ts) = acc + (uint32_t)(ts - ts_ref) * (uint32_t)inc, a function of the absolute
+ *              timestamp alone: windowing, tiling and a burst drawn across two renders cannot change a bit.
+ *   sample     x = the modulator's sample after scaleVector's (scale, 0); r = the phasor of p(ts); y = (xr rc - xi rs, xr rs + xi rc);
+ *              then the cast (int16_t)(int)(y * 1.0f).  Scale, rotate, cast; every product and sum rounded to float.  The int16
+ *              are those of trxhip_modulate_batch (complex64, the plan's scale) -> trxhip_ms_nco_batch_cf32 with {p(radio_ts), inc}
+ *              -> trxhip_convert_float_short(scale 1), placed at radio_ts - first_ts.
+ *   direction  hz > 0 moves the spectrum up, as on the receive side.  An MS whose receive NCO is set to rx_hz (it cancels the
+ *              offset seen on the downlink carrier) sets -rx_hz * (f_uplink / f_downlink) here.
+ *   zeros      every sample outside a burst is written as 0 and reads no table.
+ *   _set       {enable, hz} acts at ts_now = the member's rendered_end, or 0 before its first window: acc <- p(ts_now),
+ *              ts_ref <- ts_now, inc <- new, so the phase stays continuous across a change of frequency; on from off starts at
+ *              acc = 0, off leaves acc = 0.  It applies to samples rendered afterwards: a burst that crosses the end of a window
+ *              and is finished by the next render after a _set is drawn partly with the old setting and partly with the new one,
+ *              continuous at rendered_end.  _set and _state touch host state only and wait for nothing; a render takes the
+ *              setting by value.  set_ta, submit and a refused render leave it alone.  Plan-only objects keep the same bookkeeping.
+ *   render     a render in which a rendered member has the NCO on runs the rotating instance of its kernel; members with it off
+ *              ride with inc = 0 at phase 0, the identity on the int16 (r = (1, 0) exactly).  The single object passes {p(first_ts),
+ *              inc} and the context's 16 KB tables as two more kernel arguments; the group writes them into the 8 bytes of the
+ *              member's table entry that were reserved.  No table grows; no copy, launch, event or wait is added.  With the NCO
+ *              off everywhere a render issues exactly what it issued before.
+ *   the cast   stays defined for every tx_full_scale that create accepts.  The component bound 1.52568 * scale rests on real taps
+ *              against symbols of modulus 1, so the same triangle inequality bounds the MODULUS of x, and a component of x * r is
+ *              at most |x||r|.  Roundings (u = 2^-24): the modulator's and the scale's, below 2^-20 relative on |x| (the allowance
+ *              create already carries); table entries |C|, |F| <= 1 + u; the phasor's three per component, |r| < 1 + 6.3u; the
+ *              rotation's three, 3u: together below 2^-20 again.  1.52568 * 21477 = 32767.03 leaves 2.96e-5 = 497u; the two
+ *              allowances use 32u, so 21477 passes.  The check is made at create from the generated tables (with the largest
+ *              modulus of the rotation table's entries as max|symbol|); should it ever fail, _set with enable != 0 returns
+ *              TRXHIP_EINVAL on that object and create's own bound stays what it is.
+ * TRXHIP_EINVAL, the member's NCO and every other state untouched: |hz| > 500000 or NaN (trxhip_ms_nco_inc()), cfg / out / object
+ *   NULL, member >= n_members.  trxhip_ms_tx_status stays 96 bytes; the NCO has its own record, trxhip_ms_nco_status. */
+int  trxhip_ms_nco_tx_set(trxhip_ms_tx *s, const trxhip_ms_nco_cfg *cfg);
+int  trxhip_ms_nco_tx_state(const trxhip_ms_tx *s, trxhip_ms_nco_status *out);
+int  trxhip_ms_nco_tx_group_set(trxhip_ms_tx_group *g, uint32_t member, const trxhip_ms_nco_cfg *cfg);
+int  trxhip_ms_nco_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_nco_status *out);
+
 #ifdef __cplusplus
 }
 #endif

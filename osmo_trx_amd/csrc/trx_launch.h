@@ -213,6 +213,13 @@ int trx_launch_ms_tx_stage(const trx_mstx_row *d_src, const uint32_t *d_dst, siz
 			   hipStream_t stream);
 int trx_launch_ms_tx_render_group(const trx_mstx_gmember *d_tab, uint32_t n_entries, uint32_t n_waves, const trx_mstx_row *d_rows,
 				  const trx_tx_tables *d_tab_tx, int16_t *d_out, hipStream_t stream);
+/* the rotating instances of the two renders (ms_tx_render_nco_kernel, ms_tx_render_group_nco_kernel): the member's uplink
+ * oscillator between the modulator's sample and the cast.  nco = {phase of the window's first sample, inc} (the group: in the
+ * entries), d_nco_tab the context's phasor tables (trx_ms_nco.h) */
+int trx_launch_ms_tx_render_nco(const trx_mstx_seg *d_segs, size_t n_segs, const trx_mstx_row *d_rows, const trx_tx_tables *d_tab,
+				int16_t *d_out, trxhip_ms_nco_row nco, const float *d_nco_tab, hipStream_t stream);
+int trx_launch_ms_tx_render_group_nco(const trx_mstx_gmember *d_tab, uint32_t n_entries, uint32_t n_waves, const trx_mstx_row *d_rows,
+				      const trx_tx_tables *d_tab_tx, int16_t *d_out, const float *d_nco_tab, hipStream_t stream);
 /* trx_capi.cpp: a transmit front end's logical channels, block length and output samples per block */
 int trx_tx_frontend_geometry(const trxhip_tx_frontend *f, int *chans, int *block_len, size_t *out_per_block);
 

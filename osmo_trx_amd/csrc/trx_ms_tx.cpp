@@ -16,6 +16,12 @@
 // walk_window), used by the single object and by every member of a group alike.  The single object tiles its window with host-made
 // segments; the group uploads one table per render -- an entry per rendered member, then the queued bursts that intersect its
 // window -- and ms_tx_render_group_kernel finds each tile's bursts on the device.
+//
+// The uplink oscillator (trxhip_ms_nco_tx_*; trx_ms_nco.h is the arithmetic, include/trxhip.h the contract) is a trx_nco_state in
+// the Member.  _set is trx_nco_set() at the member's rendered_end; a render hands the kernel {p(first_ts), inc} by value -- a kernel
+// argument for the single object, the two words of the member's table entry for the group -- and runs the rotating instance of its
+// kernel when a rendered member has the oscillator on.  No copy, launch or event is added, and with it off everywhere a render
+// issues what it issued before there was one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,7 +35,9 @@
 #include "../../include/trxhip.h"
 #include "trx_ctx.h"
 #include "trx_launch.h"
+#include "trx_ms_nco.h"
 #include "trx_ms_tx.h"
+#include "trx_tx_tables.h"
 
 namespace {
 
@@ -110,6 +118,33 @@ double pulse_bound()
 	return best * (1.0 + 1.0 / (1 << 20));      /* the float roundings of at most 6 products, 6 sums and the scale: < 2^-20 */
 }
 
+// The largest |component| behind the uplink oscillator, per unit of scale.  pulse_bound() bounds a component of the modulator's
+// sample x; the rotation mixes the two components, so here the MODULUS of x is bounded, by the same triangle inequality: the taps
+// are real and a sample is sum(tap * symbol), so |x| <= sum|taps| * max|symbol| per phase of the grid.  A c0 symbol is +-rot4[4m],
+// a c1 symbol that times (0, +-1) (tx_stage_syms), so max|symbol| = max|rot4[4m]|, taken from the table (1 up to the rounding of
+// cos and sin to float).  Roundings, u = 2^-24:
+//   x       a component's error is at most 8u * sum|tap * symbol component| (at most 6 products, 6 sums, the real scale), so the
+//           modulus grows by at most sqrt(2) * 8u < 2^-20 relative: the allowance pulse_bound() already carries
+//   tables  an entry is (cos, sin) rounded per component: |C|, |F| <= 1 + u
+//   phasor  r = (Cc Fc - Cs Fs, Cc Fs + Cs Fc): |C||F| <= 1 + 2u + u^2; per component two products and a sum, error at most
+//           3u (|Cc Fc| + |Cs Fs|) <= 3u |C||F|, so |r| <= (1 + 2u + u^2)(1 + 3 sqrt(2) u) < 1 + 6.3u
+//   rotate  a component of x * r is at most |x||r|; two products and a sum add at most 3u (|xr rc| + |xi rs|) <= 3u |x||r|
+// together |y component| <= |x| (1 + 6.3u)(1 + 3u) < |x| (1 + 10u), allowed for here as 16u = 2^-20.  The cast's own factor 1.0f is
+// exact.  The gap that 21477 leaves is 2.96e-5 = 497u; the two allowances use 32u.
+double nco_bound()
+{
+	trx_tx_tables *tab = static_cast<trx_tx_tables *>(malloc(sizeof(trx_tx_tables)));
+	if (!tab || trx_tx_tables_generate(tab) != 0) {
+		free(tab);
+		return INFINITY;
+	}
+	double sym = 0.0;
+	for (int m = 0; m <= 149; m++)              /* tx_stage_syms: m = 0 .. nbits + 1 */
+		sym = std::max(sym, std::hypot((double)tab->rot4[4 * m].re, (double)tab->rot4[4 * m].im));
+	free(tab);
+	return pulse_bound() * sym * (1.0 + 1.0 / (1 << 20));
+}
+
 // One MS: what set_ta(), submit_burst() and the windows of its stream act on.  The single object is one, a group has N.
 struct Member {
 	int32_t timing_advance = 0;
@@ -118,6 +153,7 @@ struct Member {
 	bool window_set = false;
 	int64_t rendered_end = 0;
 	trxhip_ms_tx_status ctr{};
+	trx_nco_state nco{};                       /* the uplink oscillator, on the radio_ts timeline of the windows */
 	// ring rows (device objects only)
 	std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> free_rows;   /* freed rows, lowest first */
 	uint32_t fresh = 0;                        /* rows >= fresh were never used */
@@ -128,6 +164,7 @@ struct Member {
 struct trxhip_ms_tx {
 	trxhip_ctx *ctx = nullptr;
 	trxhip_ms_tx_cfg cfg{};
+	bool nco_ok = false;                       /* the cast stays defined behind the oscillator at this tx_full_scale */
 	Member m;
 
 	// device state (ctx != NULL)
@@ -144,6 +181,7 @@ struct trxhip_ms_tx {
 struct trxhip_ms_tx_group {
 	trxhip_ctx *ctx = nullptr;
 	trxhip_ms_tx_cfg cfg{};                    /* of every member */
+	bool nco_ok = false;                       /* as trxhip_ms_tx's */
 	std::vector<Member> mem;
 
 	// device state (ctx != NULL)
@@ -361,6 +399,37 @@ bool valid_cfg(const trxhip_ms_tx_cfg &c)
 	return c.max_pending >= 1 && c.max_pending <= kMaxPending && (double)c.tx_full_scale * pulse_bound() < 32768.0;
 }
 
+// the rotated product must stay below 32768 too: nco_bound() in place of pulse_bound()
+bool valid_nco_scale(const trxhip_ms_tx_cfg &c) { return (double)c.tx_full_scale * nco_bound() < 32768.0; }
+
+// trxhip_ms_nco_tx_*_set for one member: at rendered_end, or 0 before the first window
+int member_nco_set(Member &m, bool nco_ok, const trxhip_ms_nco_cfg *cfg)
+{
+	int32_t inc;
+	if (!cfg || trx_nco_inc(cfg->hz, &inc) != 0 || (cfg->enable != 0 && !nco_ok))
+		return TRXHIP_EINVAL;
+	trx_nco_set(&m.nco, cfg->enable != 0, cfg->hz, inc, m.window_set ? m.rendered_end : 0);
+	return TRXHIP_OK;
+}
+
+void member_nco_state(const Member &m, trxhip_ms_nco_status *out)
+{
+	memset(out, 0, sizeof(*out));
+	out->enable = m.nco.enable;
+	out->inc = m.nco.inc;
+	out->acc = m.nco.acc;
+	out->ts_ref = m.nco.ts_ref;
+	out->hz = m.nco.hz;
+}
+
+// what a render that begins at first_ts hands the kernel for this member; off rides as the identity
+trxhip_ms_nco_row member_nco_row(const Member &m, int64_t first_ts)
+{
+	if (!m.nco.enable)
+		return trxhip_ms_nco_row{ 0u, 0 };
+	return trxhip_ms_nco_row{ trx_nco_phase(m.nco.acc, m.nco.ts_ref, m.nco.inc, first_ts), m.nco.inc };
+}
+
 void member_state(const Member &m, trxhip_ms_tx_status *out)
 {
 	*out = m.ctr;
@@ -445,6 +514,7 @@ int trxhip_ms_tx_create(trxhip_ctx *ctx, const trxhip_ms_tx_cfg *cfg, trxhip_ms_
 		return TRXHIP_ENOMEM;
 	s->cfg = c;
 	s->cfg.reserved = 0;
+	s->nco_ok = valid_nco_scale(c);
 	if (ctx) {
 		s->ctx = ctx;
 		if (hipMalloc(reinterpret_cast<void **>(&s->d_rows), (size_t)c.max_pending * sizeof(trx_mstx_row)) != hipSuccess) {
@@ -578,12 +648,15 @@ int trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, i
 		s->d_seg_cap[k] = cap;
 	}
 	trx_mstx_seg *segs = reinterpret_cast<trx_mstx_seg *>(pb.h);
+	const trxhip_ms_nco_row nco = member_nco_row(s->m, first_ts);
 	const size_t n_segs = plan_window(s, first_ts, end, segs, n_drawn);
 	if (n_segs > bound)
 		return TRXHIP_EIO;                                     /* cannot happen: see the bound */
 	rc = hipMemcpyAsync(s->d_seg[k], segs, n_segs * sizeof(trx_mstx_seg), hipMemcpyHostToDevice, st) == hipSuccess ? TRXHIP_OK : TRXHIP_EIO;
 	if (rc == TRXHIP_OK)
-		rc = trx_launch_ms_tx_render(s->d_seg[k], n_segs, s->d_rows, s->ctx->d_tx_tables, d_out, st);
+		rc = s->m.nco.enable
+			     ? trx_launch_ms_tx_render_nco(s->d_seg[k], n_segs, s->d_rows, s->ctx->d_tx_tables, d_out, nco, s->ctx->d_nco_tab, st)
+			     : trx_launch_ms_tx_render(s->d_seg[k], n_segs, s->d_rows, s->ctx->d_tx_tables, d_out, st);
 	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
 		rc = TRXHIP_EIO;
 	if (rc != TRXHIP_OK) {
@@ -600,6 +673,19 @@ int trxhip_ms_tx_state(const trxhip_ms_tx *s, trxhip_ms_tx_status *out)
 	if (!s || !out)
 		return TRXHIP_EINVAL;
 	member_state(s->m, out);
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_nco_tx_set(trxhip_ms_tx *s, const trxhip_ms_nco_cfg *cfg)
+{
+	return s ? member_nco_set(s->m, s->nco_ok, cfg) : TRXHIP_EINVAL;
+}
+
+int trxhip_ms_nco_tx_state(const trxhip_ms_tx *s, trxhip_ms_nco_status *out)
+{
+	if (!s || !out)
+		return TRXHIP_EINVAL;
+	member_nco_state(s->m, out);
 	return TRXHIP_OK;
 }
 
@@ -620,6 +706,7 @@ int trxhip_ms_tx_group_create(trxhip_ctx *ctx, const trxhip_ms_tx_group_cfg *cfg
 	if (!g)
 		return TRXHIP_ENOMEM;
 	g->cfg = c;
+	g->nco_ok = valid_nco_scale(c);
 	try {
 		g->mem.resize(cfg->n_members);
 	} catch (const std::bad_alloc &) {
@@ -790,6 +877,7 @@ int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t 
 	trx_mstx_gburst *bur = dev ? reinterpret_cast<trx_mstx_gburst *>(ent + n_rendered) : nullptr;
 	size_t ke = 0, kb = 0;
 	uint32_t wave = 0;
+	bool nco_on = false;                                           /* a rendered member has its oscillator on */
 	for (size_t m = 0; m < n_mem; m++) {
 		const size_t ns = h_n_samples[m];
 		if (ns == 0)
@@ -811,7 +899,10 @@ int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t 
 			e.first_wave = wave;
 			e.first_burst = (uint32_t)kb0;
 			e.n_bursts = (uint32_t)(kb - kb0);
-			e.reserved[0] = e.reserved[1] = 0;
+			const trxhip_ms_nco_row nco = member_nco_row(g->mem[m], first_ts);
+			e.nco_phase0 = nco.phase0;
+			e.nco_inc = nco.inc;
+			nco_on = nco_on || g->mem[m].nco.enable;
 		}
 		ke++;
 		wave += (uint32_t)((ns + TRX_MSTX_BURST - 1) / TRX_MSTX_BURST);
@@ -826,8 +917,10 @@ int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t 
 			 ? TRXHIP_OK
 			 : TRXHIP_EIO;
 	if (rc == TRXHIP_OK)
-		rc = trx_launch_ms_tx_render_group(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k]), (uint32_t)n_rendered, wave, g->d_rows,
-						   g->ctx->d_tx_tables, d_out, st);
+		rc = nco_on ? trx_launch_ms_tx_render_group_nco(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k]), (uint32_t)n_rendered, wave,
+								g->d_rows, g->ctx->d_tx_tables, d_out, g->ctx->d_nco_tab, st)
+			    : trx_launch_ms_tx_render_group(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k]), (uint32_t)n_rendered, wave,
+							    g->d_rows, g->ctx->d_tx_tables, d_out, st);
 	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
 		rc = TRXHIP_EIO;
 	if (rc != TRXHIP_OK) {
@@ -836,6 +929,19 @@ int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t 
 	}
 	pb.used = true;
 	g->next_tab = (k + 1) % kBufs;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_nco_tx_group_set(trxhip_ms_tx_group *g, uint32_t member, const trxhip_ms_nco_cfg *cfg)
+{
+	return g && member < g->mem.size() ? member_nco_set(g->mem[member], g->nco_ok, cfg) : TRXHIP_EINVAL;
+}
+
+int trxhip_ms_nco_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_nco_status *out)
+{
+	if (!g || member >= g->mem.size() || !out)
+		return TRXHIP_EINVAL;
+	member_nco_state(g->mem[member], out);
 	return TRXHIP_OK;
 }
 

@@ -36,7 +36,8 @@ struct trx_mstx_gmember {
 	uint32_t n_samples;
 	uint32_t first_wave;
 	uint32_t first_burst, n_bursts;        /* its bursts in the list behind the entries: ascending rel, 625 or more apart */
-	uint32_t reserved[2];
+	uint32_t nco_phase0;                   /* the uplink oscillator (trx_ms_nco.h): the phase of the window's first sample and the */
+	int32_t  nco_inc;                      /* increment; 0 and 0 for a member with it off.  Read by the rotating instance only */
 };
 static_assert(sizeof(trx_mstx_gmember) == 32, "trx_mstx_gmember layout");
 

@@ -22,6 +22,7 @@
 #include "trx_tx_tables.h"
 #include "trx_tx_sched.h"
 #include "trx_ms_tx.h"
+#include "trx_ms_nco.h"
 #include "trx_launch.h"
 
 typedef float2 c32;
@@ -670,9 +671,17 @@ extern "C" int trx_launch_tx_fill_update(const trx_tx_fill_update *d_upd, size_t
 // tx_sample at i + first: a burst drawn in two windows gives the samples of one drawn whole.  The int16 are those of
 // tx_modulate_kernel with s16_scale 1 -- driveTx()'s static_cast<int16_t>(x * 1) -- through tx_store_row: a lone head sample when
 // the segment starts 4 bytes off an 8-byte boundary, 8-byte stores, a lone tail.  Every sample of the window is written once.
-__global__ void __launch_bounds__(64 * TX_WAVES)
-ms_tx_render_kernel(const trx_mstx_seg *__restrict__ segs, size_t n_segs, const trx_mstx_row *__restrict__ rows,
-		    const trx_tx_tables *__restrict__ tab, int16_t *__restrict__ out)
+//
+// ROT (ms_tx_render_nco_kernel): the member's uplink oscillator (trx_ms_nco.h, include/trxhip.h) between tx_sample() and the cast.
+// nco = {phase of the window's first sample, inc}: sample i of a segment has phase phase0 + (out_off + i) * inc modulo 2^32, a
+// function of its timestamp alone, so the tiling cannot change a bit.  The order is scale (inside tx_sample), rotate, cast.  Zero
+// segments are written as zeros and read no table.  The two table reads go through the vector cache, as the receive side's do:
+// the tables are 16 KB that every wave of the launch reads and that stay cache-resident, where a staged copy would move 16 KB
+// into LDS per workgroup of at most 2500 samples and more than double the workgroup's LDS.
+template <bool ROT>
+__device__ __forceinline__ void ms_tx_render_body(const trx_mstx_seg *__restrict__ segs, size_t n_segs, const trx_mstx_row *__restrict__ rows,
+						  const trx_tx_tables *__restrict__ tab, int16_t *__restrict__ out, trxhip_ms_nco_row nco,
+						  const float *__restrict__ nco_tab)
 {
 	__shared__ tx_lds L;
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -723,8 +732,39 @@ ms_tx_render_kernel(const trx_mstx_seg *__restrict__ segs, size_t n_segs, const 
 		return;
 
 	const c32 *rot = reinterpret_cast<const c32 *>(tab->rot4);
+	if (ROT) {
+		const uint32_t p0 = nco.phase0 + (uint32_t)off * (uint32_t)nco.inc;
+		auto rotated = [&](int i) -> c32 {
+			const c32 x = tx_sample(d, s0, s1, lb, L, rot, 4, i + first);
+			float rc, rs, yr, yi;
+			trx_nco_phasor(nco_tab, p0 + (uint32_t)i * (uint32_t)nco.inc, &rc, &rs);
+			trx_nco_rotate(x.x, x.y, rc, rs, &yr, &yi);
+			return make_float2(yr, yi);
+		};
+		auto zeros = [](int) -> c32 { return make_float2(0.0f, 0.0f); };
+		if (ok)
+			tx_store_row(rotated, nullptr, out, 2 * off, 1.0f, len, lane);
+		else
+			tx_store_row(zeros, nullptr, out, 2 * off, 1.0f, len, lane);
+		return;
+	}
 	auto sample = [&](int i) -> c32 { return tx_sample(d, s0, s1, lb, L, rot, 4, i + first); };
 	tx_store_row(sample, nullptr, out, 2 * off, 1.0f, len, lane);
+}
+
+__global__ void __launch_bounds__(64 * TX_WAVES)
+ms_tx_render_kernel(const trx_mstx_seg *__restrict__ segs, size_t n_segs, const trx_mstx_row *__restrict__ rows,
+		    const trx_tx_tables *__restrict__ tab, int16_t *__restrict__ out)
+{
+	ms_tx_render_body<false>(segs, n_segs, rows, tab, out, trxhip_ms_nco_row{ 0u, 0 }, nullptr);
+}
+
+__global__ void __launch_bounds__(64 * TX_WAVES)
+ms_tx_render_nco_kernel(const trx_mstx_seg *__restrict__ segs, size_t n_segs, const trx_mstx_row *__restrict__ rows,
+			const trx_tx_tables *__restrict__ tab, int16_t *__restrict__ out, trxhip_ms_nco_row nco,
+			const float *__restrict__ nco_tab)
+{
+	ms_tx_render_body<true>(segs, n_segs, rows, tab, out, nco, nco_tab);
 }
 
 extern "C" int trx_launch_ms_tx_render(const trx_mstx_seg *d_segs, size_t n_segs, const trx_mstx_row *d_rows, const trx_tx_tables *d_tab,
@@ -736,6 +776,19 @@ extern "C" int trx_launch_ms_tx_render(const trx_mstx_seg *d_segs, size_t n_segs
 	if (blocks > 0x7fffffffu)
 		return TRXHIP_EINVAL;
 	hipLaunchKernelGGL(ms_tx_render_kernel, dim3((unsigned)blocks), dim3(64 * TX_WAVES), 0, stream, d_segs, n_segs, d_rows, d_tab, d_out);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+extern "C" int trx_launch_ms_tx_render_nco(const trx_mstx_seg *d_segs, size_t n_segs, const trx_mstx_row *d_rows, const trx_tx_tables *d_tab,
+					   int16_t *d_out, trxhip_ms_nco_row nco, const float *d_nco_tab, hipStream_t stream)
+{
+	if (n_segs == 0)
+		return 0;
+	const size_t blocks = (n_segs + TX_WAVES - 1) / TX_WAVES;
+	if (blocks > 0x7fffffffu || !d_nco_tab)
+		return TRXHIP_EINVAL;
+	hipLaunchKernelGGL(ms_tx_render_nco_kernel, dim3((unsigned)blocks), dim3(64 * TX_WAVES), 0, stream, d_segs, n_segs, d_rows, d_tab, d_out,
+			   nco, d_nco_tab);
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
 
@@ -757,9 +810,15 @@ struct tx_lds_second {
 // windows, gives the samples of one drawn whole.  Every sample of every rendered window is written once, nothing else is.
 // Barriers: all four waves reach both __syncthreads(), idle waves (behind n_waves) and tiles with one burst or none included; no
 // wave returns before the second.
-__global__ void __launch_bounds__(64 * TX_WAVES)
-ms_tx_render_group_kernel(const trx_mstx_gmember *__restrict__ tab, uint32_t n_entries, uint32_t n_waves,
-			  const trx_mstx_row *__restrict__ rows, const trx_tx_tables *__restrict__ ttab, int16_t *__restrict__ out)
+//
+// ROT (ms_tx_render_group_nco_kernel): every member's uplink oscillator as in ms_tx_render_body.  The entry carries the member's
+// {nco_phase0, nco_inc}, nco_phase0 the phase of its window's first sample, and sample i of a piece that begins `from` samples
+// into the tile that begins t0 samples into the window has phase nco_phase0 + (t0 + from + i) * nco_inc.  A member with its
+// oscillator off rides with inc 0 at phase 0: r = (1, 0) exactly, the identity on the int16.  Zero pieces read no table.
+template <bool ROT>
+__device__ __forceinline__ void ms_tx_render_group_body(const trx_mstx_gmember *__restrict__ tab, uint32_t n_entries, uint32_t n_waves,
+							const trx_mstx_row *__restrict__ rows, const trx_tx_tables *__restrict__ ttab,
+							int16_t *__restrict__ out, const float *__restrict__ nco_tab)
 {
 	__shared__ tx_lds L;
 	__shared__ tx_lds_second L2;
@@ -776,6 +835,7 @@ ms_tx_render_group_kernel(const trx_mstx_gmember *__restrict__ tab, uint32_t n_e
 	const trx_mstx_row *ra = nullptr, *rb = nullptr;
 	size_t off = 0;
 	int len = 0, a_lo = 0, a_hi = 0, a_first = 0, b_lo = 0, b_hi = 0;
+	uint32_t nco_p0 = 0, nco_inc = 0;                             // ROT: the phase of the tile's first sample, the increment
 	if (active) {
 		unsigned lo = 0, hi = n_entries;                           // tab[lo].first_wave <= gw < tab[hi].first_wave
 		while (hi - lo > 1) {
@@ -789,6 +849,10 @@ ms_tx_render_group_kernel(const trx_mstx_gmember *__restrict__ tab, uint32_t n_e
 		const uint32_t t0 = (gw - e.first_wave) * TRX_MSTX_BURST;  // the tile's first sample in the window: < n_samples <= 2^31
 		len = (int)min(TRX_MSTX_BURST, e.n_samples - t0);
 		off = (size_t)e.out_off + t0;
+		if (ROT) {
+			nco_inc = (uint32_t)e.nco_inc;
+			nco_p0 = e.nco_phase0 + t0 * nco_inc;
+		}
 		const trx_mstx_gburst *bl = reinterpret_cast<const trx_mstx_gburst *>(tab + n_entries) + e.first_burst;
 		// The first burst that ends behind the tile's start, i0 in [i0, i1].  The list is sorted, so "burst i ends at or before the
 		// tile's start" holds for a prefix of it.  The search is the wave's: the range is cut into 64 chunks, lane l asks about the
@@ -866,9 +930,40 @@ ms_tx_render_group_kernel(const trx_mstx_gmember *__restrict__ tab, uint32_t n_e
 		const c32 *s0 = second ? L2.sym0[w] : L.sym0[w], *s1 = second ? L2.sym1[w] : L.sym1[w];
 		const uint8_t *lb = second ? lbb : lba;
 		const int first = p == 1 ? a_first : 0;                    /* B begins in the tile: its sample 0 */
+		if (ROT) {
+			const uint32_t p0 = nco_p0 + (uint32_t)from * nco_inc;
+			auto rotated = [&](int i) -> c32 {
+				const c32 x = tx_sample(dp, s0, s1, lb, L, rot, 4, i + first);
+				float rc, rs, yr, yi;
+				trx_nco_phasor(nco_tab, p0 + (uint32_t)i * nco_inc, &rc, &rs);
+				trx_nco_rotate(x.x, x.y, rc, rs, &yr, &yi);
+				return make_float2(yr, yi);
+			};
+			auto zeros = [](int) -> c32 { return make_float2(0.0f, 0.0f); };
+			if (p & 1)
+				tx_store_row(rotated, nullptr, out, 2 * (off + (size_t)from), 1.0f, to - from, lane);
+			else
+				tx_store_row(zeros, nullptr, out, 2 * (off + (size_t)from), 1.0f, to - from, lane);
+			continue;
+		}
 		auto sample = [&](int i) -> c32 { return tx_sample(dp, s0, s1, lb, L, rot, 4, i + first); };
 		tx_store_row(sample, nullptr, out, 2 * (off + (size_t)from), 1.0f, to - from, lane);
 	}
+}
+
+__global__ void __launch_bounds__(64 * TX_WAVES)
+ms_tx_render_group_kernel(const trx_mstx_gmember *__restrict__ tab, uint32_t n_entries, uint32_t n_waves,
+			  const trx_mstx_row *__restrict__ rows, const trx_tx_tables *__restrict__ ttab, int16_t *__restrict__ out)
+{
+	ms_tx_render_group_body<false>(tab, n_entries, n_waves, rows, ttab, out, nullptr);
+}
+
+__global__ void __launch_bounds__(64 * TX_WAVES)
+ms_tx_render_group_nco_kernel(const trx_mstx_gmember *__restrict__ tab, uint32_t n_entries, uint32_t n_waves,
+			      const trx_mstx_row *__restrict__ rows, const trx_tx_tables *__restrict__ ttab, int16_t *__restrict__ out,
+			      const float *__restrict__ nco_tab)
+{
+	ms_tx_render_group_body<true>(tab, n_entries, n_waves, rows, ttab, out, nco_tab);
 }
 
 // A group submit's rows to their ring rows: row i of the call goes to rows[dst[i]], one thread per 32-bit word of a row.
@@ -909,6 +1004,19 @@ extern "C" int trx_launch_ms_tx_render_group(const trx_mstx_gmember *d_tab, uint
 	const unsigned blocks = (n_waves + TX_WAVES - 1) / TX_WAVES;
 	hipLaunchKernelGGL(ms_tx_render_group_kernel, dim3(blocks), dim3(64 * TX_WAVES), 0, stream, d_tab, n_entries, n_waves, d_rows, d_tab_tx,
 			   d_out);
+	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
+}
+
+extern "C" int trx_launch_ms_tx_render_group_nco(const trx_mstx_gmember *d_tab, uint32_t n_entries, uint32_t n_waves, const trx_mstx_row *d_rows,
+						 const trx_tx_tables *d_tab_tx, int16_t *d_out, const float *d_nco_tab, hipStream_t stream)
+{
+	if (n_waves == 0)
+		return 0;
+	if (n_entries == 0 || n_waves > 0x7fffffffu || !d_nco_tab)
+		return TRXHIP_EINVAL;
+	const unsigned blocks = (n_waves + TX_WAVES - 1) / TX_WAVES;
+	hipLaunchKernelGGL(ms_tx_render_group_nco_kernel, dim3(blocks), dim3(64 * TX_WAVES), 0, stream, d_tab, n_entries, n_waves, d_rows,
+			   d_tab_tx, d_out, d_nco_tab);
 	return hipGetLastError() == hipSuccess ? 0 : TRXHIP_EIO;
 }
 

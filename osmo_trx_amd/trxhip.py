@@ -264,6 +264,10 @@ SYMBOLS = {
     "trxhip_ms_tx_group_submit": (_I, [_VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(_SZ), _VP]),
     "trxhip_ms_tx_group_render_s16": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, C.POINTER(_I), _VP]),
     "trxhip_ms_tx_group_state": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_nco_tx_set": (_I, [_VP, _VP]),
+    "trxhip_ms_nco_tx_state": (_I, [_VP, _VP]),
+    "trxhip_ms_nco_tx_group_set": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_ms_nco_tx_group_state": (_I, [_VP, C.c_uint32, _VP]),
 }
 
 
@@ -1327,6 +1331,16 @@ def nco_hz_from_fcch(hz):
     return -(float(hz) - MS_FCCH_BIAS_HZ)
 
 
+def nco_tx_hz(rx_nco_hz, dl_hz=None, ul_hz=None):
+    """The uplink NCO setting (MsTxScheduler.set_nco) that goes with a receive NCO setting rx_nco_hz: -rx_nco_hz * (ul_hz / dl_hz).
+    The receive NCO cancels the offset seen on the downlink carrier; the same oscillator error shows on the uplink with the
+    opposite sign, scaled by the ratio of the carrier frequencies (1 when none are given)."""
+    if (dl_hz is None) != (ul_hz is None):
+        raise ValueError("give both carrier frequencies or neither")
+    ratio = 1.0 if dl_hz is None else float(ul_hz) / float(dl_hz)
+    return -float(rx_nco_hz) * ratio
+
+
 def ms_nco_inc(hz):
     """trxhip_ms_nco_inc(): the phase increment per sample of a shift by hz; pure host.  |hz| > 500000 and NaN raise."""
     inc = C.c_int32()
@@ -1976,6 +1990,20 @@ class MsTxScheduler:
         _check(self.L.trxhip_ms_tx_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_tx_state")
         return a[0]
 
+    # ---- uplink frequency correction (trxhip_ms_nco_tx_*) ----
+    def set_nco(self, enable, hz=0.0):
+        """The uplink NCO: every burst sample rendered from now on is rotated by a phase that depends only on its timestamp, a
+        shift by hz (+ = up; nco_tx_hz() of the receive NCO's hz cancels the oscillator's error).  Acts at the end of the last
+        rendered window, phase-continuous across a change; host state only, no GPU work.  |hz| > 500000 raises."""
+        cfg = _MsNcoCfg(1 if enable else 0, 0, float(hz))
+        _check(self.L.trxhip_ms_nco_tx_set(self.h, C.byref(cfg)), "trxhip_ms_nco_tx_set")
+
+    def nco_state(self):
+        """dict(enable, inc, acc, ts_ref, hz) as MsRxScheduler.nco_state(), on the radio_ts timeline of the windows"""
+        a = np.zeros(1, dtype=MS_NCO_STATE_DTYPE)
+        _check(self.L.trxhip_ms_nco_tx_state(self.h, a.ctypes.data_as(_VP)), "trxhip_ms_nco_tx_state")
+        return _nco_state_dict(a[0])
+
     def close(self):
         if getattr(self, "h", None):
             self.L.trxhip_ms_tx_destroy(self.h)
@@ -2071,6 +2099,18 @@ class MsTxSchedulerGroup:
         a = np.zeros(1, dtype=MS_TX_STATE_DTYPE)
         _check(self.L.trxhip_ms_tx_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_tx_group_state")
         return a[0]
+
+    # ---- uplink frequency correction (trxhip_ms_nco_tx_group_*), per member ----
+    def set_nco(self, m, enable, hz=0.0):
+        """member m's uplink NCO as MsTxScheduler.set_nco(); members are on or off independently"""
+        cfg = _MsNcoCfg(1 if enable else 0, 0, float(hz))
+        _check(self.L.trxhip_ms_nco_tx_group_set(self.h, m, C.byref(cfg)), "trxhip_ms_nco_tx_group_set")
+
+    def nco_state(self, m):
+        """member m's dict as MsTxScheduler.nco_state()"""
+        a = np.zeros(1, dtype=MS_NCO_STATE_DTYPE)
+        _check(self.L.trxhip_ms_nco_tx_group_state(self.h, m, a.ctypes.data_as(_VP)), "trxhip_ms_nco_tx_group_state")
+        return _nco_state_dict(a[0])
 
     def close(self):
         if getattr(self, "h", None):

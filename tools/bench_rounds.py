@@ -121,6 +121,16 @@ def write_json(path, res):
         f.write("\n")
 
 
+def merge_json(path, key, res):
+    """res under `key` of the JSON object in `path`, its other keys kept: the file two tools report into"""
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    doc[key] = res
+    write_json(path, doc)
+
+
 def select_legs(all_names, legs):
     """all_names, or those of them that --legs names"""
     return [k for k in all_names if not legs or k in legs.split(",")]
