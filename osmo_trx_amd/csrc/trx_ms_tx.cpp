@@ -6,22 +6,25 @@
 //   ms_trx::set_ta()              ms/ms.h:299-303
 //   submit_burst_ts()             ms/uhd_specific.h:260-269, ms/bladerf_specific.h:461-478   (ts + rxtxdelay)
 //   GSM::Time::incTN / decTN      GSM/GSMCommon.h:129-150;  GSM::FNDelta  GSM/GSMCommon.cpp:71-78
-// keeps the queued bursts ordered by the timestamp of their first sample, and turns a window of the stream into segments:
-// stretches of queued bursts and zeros in between, at most 625 samples each, that tile the window.  The device half
-// (trx_tx.hip, ms_tx_render_kernel) draws every segment where it lies.  With ctx == NULL the object is plan-only: the same
+// and keeps the queued bursts ordered by the timestamp of their first sample.  With ctx == NULL an object is plan-only: the same
 // arithmetic and queue, no device memory.
 //
-// The group (trxhip_ms_tx_group_*) is N such members behind one radio type.  A member -- its timing advance, queue, window state,
-// counters and ring rows -- is one struct (Member) with one set of rules (plan_request, queue_place, place_request, retire,
-// walk_window), used by the single object and by every member of a group alike.  The single object tiles its window with host-made
-// segments; the group uploads one table per render -- an entry per rendered member, then the queued bursts that intersect its
-// window -- and ms_tx_render_group_kernel finds each tile's bursts on the device.
+// There is one object, the group (trxhip_ms_tx_group_*): N members behind one radio type.  A member -- its timing advance, queue,
+// window state, counters and ring rows -- is one struct (Member) with one set of rules (plan_request, queue_place, place_request,
+// retire, walk_window).  A group's render uploads one table -- an entry per rendered member, then the queued bursts that
+// intersect its window -- and the device half (trx_tx.hip, ms_tx_render_group_kernel) cuts every window into tiles of 625
+// samples and finds each tile's bursts.  The single object (trxhip_ms_tx_*) is a group of one member with the flag `direct`, its
+// entry points forwards to member 0 through the same create, submit and render.  `direct` chooses how the one member's work
+// reaches the device: a submit copies every run of consecutive ring rows to where it lies (a group sends rows and destinations
+// up in one copy and scatters them with ms_tx_stage_kernel), and a render tiles the window with host-made segments --
+// stretches of queued bursts and zeros in between, at most 625 samples each -- that ms_tx_render_kernel draws where they lie:
+// on a render of 8 slots that kernel is 0.9 us faster than the tile kernel.
 //
 // The uplink oscillator (trxhip_ms_nco_tx_*; trx_ms_nco.h is the arithmetic, include/trxhip.h the contract) is a trx_nco_state in
 // the Member.  _set is trx_nco_set() at the member's rendered_end; a render hands the kernel {p(first_ts), inc} by value -- a kernel
-// argument for the single object, the two words of the member's table entry for the group -- and runs the rotating instance of its
-// kernel when a rendered member has the oscillator on.  No copy, launch or event is added, and with it off everywhere a render
-// issues what it issued before there was one.
+// argument with `direct`, the two words of the member's table entry otherwise -- and runs the rotating instance of its kernel
+// when a rendered member has the oscillator on.  No copy, launch or event is added, and with it off everywhere a render issues
+// what it issued before there was one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -145,7 +148,7 @@ double nco_bound()
 	return pulse_bound() * sym * (1.0 + 1.0 / (1 << 20));
 }
 
-// One MS: what set_ta(), submit_burst() and the windows of its stream act on.  The single object is one, a group has N.
+// One MS: what set_ta(), submit_burst() and the windows of its stream act on.  A group has N, the single object one.
 struct Member {
 	int32_t timing_advance = 0;
 	std::vector<Pending> q;                    /* [head, size): queued bursts by radio_ts */
@@ -161,37 +164,23 @@ struct Member {
 
 }  // namespace
 
-struct trxhip_ms_tx {
-	trxhip_ctx *ctx = nullptr;
-	trxhip_ms_tx_cfg cfg{};
-	bool nco_ok = false;                       /* the cast stays defined behind the oscillator at this tx_full_scale */
-	Member m;
-
-	// device state (ctx != NULL)
-	trx_mstx_row *d_rows = nullptr;
-	PinBuf stage[kBufs];                       /* submit: the call's rows */
-	int next_stage = 0;
-	PinBuf seg[kBufs];                         /* render: the window's segments */
-	trx_mstx_seg *d_seg[kBufs] = {};
-	size_t d_seg_cap[kBufs] = {};
-	int next_seg = 0;
-	std::vector<uint32_t> call_rows;
-};
-
+// A trxhip_ms_tx * is the handle of a group of one member that issues directly (trxhip_ms_tx_create()); the type has no
+// definition of its own.
 struct trxhip_ms_tx_group {
 	trxhip_ctx *ctx = nullptr;
 	trxhip_ms_tx_cfg cfg{};                    /* of every member */
-	bool nco_ok = false;                       /* as trxhip_ms_tx's */
+	bool nco_ok = false;                       /* the cast stays defined behind the oscillator at this tx_full_scale */
+	bool direct = false;                       /* the single object: one member, rows copied straight into the ring, host-made segments */
 	std::vector<Member> mem;
 
 	// device state (ctx != NULL)
 	trx_mstx_row *d_rows = nullptr;            /* [n_members][max_pending] */
-	PinBuf stage[kBufs];                       /* submit: the call's rows, then their ring destinations */
-	uint8_t *d_stage[kBufs] = {};
+	PinBuf stage[kBufs];                       /* submit: the call's rows, then (not with `direct`) their ring destinations */
+	uint8_t *d_stage[kBufs] = {};              /* not with `direct` */
 	size_t d_stage_cap[kBufs] = {};
 	int next_stage = 0;
 	std::vector<uint32_t> call_dst;
-	PinBuf tab[kBufs];                        /* render: the member entries, then the bursts of their windows */
+	PinBuf tab[kBufs];                        /* render: the member entries, then the bursts of their windows; `direct`: the segments */
 	uint8_t *d_tab[kBufs] = {};
 	size_t d_tab_cap[kBufs] = {};
 	int next_tab = 0;
@@ -476,11 +465,11 @@ size_t zero_segs(trx_mstx_seg *segs, size_t k, int64_t from, int64_t to, int64_t
 
 // The window [first_ts, end): retire what lies before it, tile it with segments (written when segs != NULL), retire what ends
 // in it.  Returns the number of segments.
-size_t plan_window(trxhip_ms_tx *s, int64_t first_ts, int64_t end, trx_mstx_seg *segs, size_t *n_drawn)
+size_t plan_window(Member &m, bool with_rows, int64_t first_ts, int64_t end, trx_mstx_seg *segs, size_t *n_drawn)
 {
 	size_t k = 0;
 	int64_t cur = first_ts;
-	walk_window(s->m, s->ctx != nullptr, first_ts, end, n_drawn, [&](const Pending &b, int64_t from, int64_t to) {
+	walk_window(m, with_rows, first_ts, end, n_drawn, [&](const Pending &b, int64_t from, int64_t to) {
 		k = zero_segs(segs, k, cur, from, first_ts);
 		if (segs) {
 			trx_mstx_seg &g = segs[k];
@@ -496,167 +485,37 @@ size_t plan_window(trxhip_ms_tx *s, int64_t first_ts, int64_t end, trx_mstx_seg 
 	return zero_segs(segs, k, cur, end, first_ts);
 }
 
-}  // namespace
-
-extern "C" {
-
-int trxhip_ms_tx_create(trxhip_ctx *ctx, const trxhip_ms_tx_cfg *cfg, trxhip_ms_tx **out)
+// group_render() with `direct`: the one member's checked window of n_samples >= 1 as segments, one copy, one launch, one event
+int render_segments(trxhip_ms_tx_group *g, int16_t *d_out, size_t n_samples, int64_t first_ts, size_t *n_drawn, hipStream_t st)
 {
-	if (!cfg || !out)
-		return TRXHIP_EINVAL;
-	const trxhip_ms_tx_cfg c = *cfg;
-	if (!valid_cfg(c))
-		return TRXHIP_EINVAL;
-	if (ctx && (!ctx->d_tx_tables || with_device(ctx)))
-		return TRXHIP_EINVAL;
-	trxhip_ms_tx *s = new (std::nothrow) trxhip_ms_tx();
-	if (!s)
-		return TRXHIP_ENOMEM;
-	s->cfg = c;
-	s->cfg.reserved = 0;
-	s->nco_ok = valid_nco_scale(c);
-	if (ctx) {
-		s->ctx = ctx;
-		if (hipMalloc(reinterpret_cast<void **>(&s->d_rows), (size_t)c.max_pending * sizeof(trx_mstx_row)) != hipSuccess) {
-			s->d_rows = nullptr;
-			trxhip_ms_tx_destroy(s);
-			return TRXHIP_ENOMEM;
-		}
-	}
-	*out = s;
-	return TRXHIP_OK;
-}
-
-void trxhip_ms_tx_destroy(trxhip_ms_tx *s)
-{
-	if (!s)
-		return;
-	if (s->ctx && with_device(s->ctx) == 0) {
-		for (int k = 0; k < kBufs; k++) {
-			pin_destroy(s->stage[k]);
-			pin_destroy(s->seg[k]);
-			if (s->d_seg[k])
-				(void)hipFree(s->d_seg[k]);
-		}
-		if (s->d_rows)
-			(void)hipFree(s->d_rows);
-	}
-	delete s;
-}
-
-int trxhip_ms_tx_set_ta(trxhip_ms_tx *s, int val)
-{
-	if (!s || !valid_ta(val))
-		return TRXHIP_EINVAL;
-	s->m.timing_advance = val * 4;
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_tx_submit(trxhip_ms_tx *s, const trxhip_ms_tx_req *h_reqs, size_t n, uint32_t now_fn, int now_tn, int64_t now_ts,
-			trxhip_ms_tx_plan *h_plan, void *stream)
-{
-	if (!s || (!h_reqs && n) || !valid_clock(now_fn, now_tn, now_ts))
-		return TRXHIP_EINVAL;
-	for (size_t i = 0; i < n; i++)
-		if (!valid_request(h_reqs[i]))
-			return TRXHIP_EINVAL;
-	if (n == 0)
-		return TRXHIP_OK;
-	hipStream_t st = static_cast<hipStream_t>(stream);
-	trx_mstx_row *rows = nullptr;
-	PinBuf *pb = nullptr;
-	if (s->ctx) {
-		if (with_device(s->ctx))
-			return TRXHIP_EIO;
-		pb = &s->stage[s->next_stage];
-		const size_t most = std::min(n, (size_t)s->cfg.max_pending);          /* no call queues more */
-		const int rc = pin_acquire(*pb, most * sizeof(trx_mstx_row));
-		if (rc != TRXHIP_OK)
-			return rc;
-		rows = reinterpret_cast<trx_mstx_row *>(pb->h);
-		s->call_rows.clear();
-	}
-	for (size_t i = 0; i < n; i++) {
-		trxhip_ms_tx_plan p;
-		uint32_t ring_row = 0;
-		if (place_request(s->m, s->cfg, s->ctx != nullptr, h_reqs[i], now_fn, now_tn, now_ts, p, &ring_row) && s->ctx) {
-			fill_row(rows[s->call_rows.size()], h_reqs[i], p.scale);
-			s->call_rows.push_back(ring_row);
-		}
-		if (h_plan)
-			h_plan[i] = p;
-	}
-	if (s->ctx && !s->call_rows.empty()) {
-		// one copy per run of consecutive ring rows
-		const std::vector<uint32_t> &cr = s->call_rows;
-		for (size_t i = 0; i < cr.size();) {
-			size_t j = i + 1;
-			while (j < cr.size() && cr[j] == cr[j - 1] + 1)
-				j++;
-			if (hipMemcpyAsync(s->d_rows + cr[i], rows + i, (j - i) * sizeof(trx_mstx_row), hipMemcpyHostToDevice, st) != hipSuccess) {
-				(void)hipStreamSynchronize(st);
-				return TRXHIP_EIO;
-			}
-			i = j;
-		}
-		if (hipEventRecord(pb->ev, st) != hipSuccess) {
-			(void)hipStreamSynchronize(st);
-			return TRXHIP_EIO;
-		}
-		pb->used = true;
-		s->next_stage = (s->next_stage + 1) % kBufs;
-	}
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, int64_t first_ts, size_t *n_drawn, void *stream)
-{
-	if (!s || !valid_window(s->m, n_samples, first_ts))
-		return TRXHIP_EINVAL;
-	if (s->ctx ? (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 3)) : d_out != nullptr)
-		return TRXHIP_EINVAL;
-	if (n_drawn)
-		*n_drawn = 0;
-	if (n_samples == 0)
-		return TRXHIP_OK;
+	Member &m = g->mem[0];
 	const int64_t end = first_ts + (int64_t)n_samples;
-	if (!s->ctx) {
-		plan_window(s, first_ts, end, nullptr, n_drawn);
+	if (!g->ctx) {
+		plan_window(m, false, first_ts, end, nullptr, n_drawn);
 		return TRXHIP_OK;
 	}
-	if (with_device(s->ctx))
+	if (with_device(g->ctx))
 		return TRXHIP_EIO;
-	hipStream_t st = static_cast<hipStream_t>(stream);
 	// at most: a zero segment per 625 samples, and per queued burst that begins before the window's end the burst's segment and
 	// one more zero segment in front of it
-	const size_t bound = n_samples / (size_t)kBurst + 2 * bursts_before(s->m, end) + 2;
-	const int k = s->next_seg;
-	PinBuf &pb = s->seg[k];
-	int rc = pin_acquire(pb, bound * sizeof(trx_mstx_seg));     /* waits for the render 4 calls back: it read d_seg[k] */
+	const size_t bound = n_samples / (size_t)kBurst + 2 * bursts_before(m, end) + 2;
+	const int k = g->next_tab;
+	PinBuf &pb = g->tab[k];
+	int rc = pin_acquire(pb, bound * sizeof(trx_mstx_seg));     /* waits for the render 4 calls back: it read d_tab[k] */
+	if (rc == TRXHIP_OK)
+		rc = dev_reserve(g->d_tab[k], g->d_tab_cap[k], bound * sizeof(trx_mstx_seg));
 	if (rc != TRXHIP_OK)
 		return rc;
-	if (s->d_seg_cap[k] < bound) {
-		if (s->d_seg[k])
-			(void)hipFree(s->d_seg[k]);
-		s->d_seg[k] = nullptr;
-		s->d_seg_cap[k] = 0;
-		const size_t cap = std::max(bound, (size_t)256);
-		if (hipMalloc(reinterpret_cast<void **>(&s->d_seg[k]), cap * sizeof(trx_mstx_seg)) != hipSuccess) {
-			s->d_seg[k] = nullptr;
-			return TRXHIP_ENOMEM;
-		}
-		s->d_seg_cap[k] = cap;
-	}
 	trx_mstx_seg *segs = reinterpret_cast<trx_mstx_seg *>(pb.h);
-	const trxhip_ms_nco_row nco = member_nco_row(s->m, first_ts);
-	const size_t n_segs = plan_window(s, first_ts, end, segs, n_drawn);
+	const trx_mstx_seg *d_segs = reinterpret_cast<const trx_mstx_seg *>(g->d_tab[k]);
+	const trxhip_ms_nco_row nco = member_nco_row(m, first_ts);
+	const size_t n_segs = plan_window(m, true, first_ts, end, segs, n_drawn);
 	if (n_segs > bound)
 		return TRXHIP_EIO;                                     /* cannot happen: see the bound */
-	rc = hipMemcpyAsync(s->d_seg[k], segs, n_segs * sizeof(trx_mstx_seg), hipMemcpyHostToDevice, st) == hipSuccess ? TRXHIP_OK : TRXHIP_EIO;
+	rc = hipMemcpyAsync(g->d_tab[k], segs, n_segs * sizeof(trx_mstx_seg), hipMemcpyHostToDevice, st) == hipSuccess ? TRXHIP_OK : TRXHIP_EIO;
 	if (rc == TRXHIP_OK)
-		rc = s->m.nco.enable
-			     ? trx_launch_ms_tx_render_nco(s->d_seg[k], n_segs, s->d_rows, s->ctx->d_tx_tables, d_out, nco, s->ctx->d_nco_tab, st)
-			     : trx_launch_ms_tx_render(s->d_seg[k], n_segs, s->d_rows, s->ctx->d_tx_tables, d_out, st);
+		rc = m.nco.enable ? trx_launch_ms_tx_render_nco(d_segs, n_segs, g->d_rows, g->ctx->d_tx_tables, d_out, nco, g->ctx->d_nco_tab, st)
+				  : trx_launch_ms_tx_render(d_segs, n_segs, g->d_rows, g->ctx->d_tx_tables, d_out, st);
 	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
 		rc = TRXHIP_EIO;
 	if (rc != TRXHIP_OK) {
@@ -664,41 +523,15 @@ int trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, i
 		return TRXHIP_EIO;
 	}
 	pb.used = true;
-	s->next_seg = (k + 1) % kBufs;
+	g->next_tab = (k + 1) % kBufs;
 	return TRXHIP_OK;
 }
 
-int trxhip_ms_tx_state(const trxhip_ms_tx *s, trxhip_ms_tx_status *out)
+// direct: the single object, which needs neither a scatter nor a table
+int group_create(trxhip_ctx *ctx, const trxhip_ms_tx_cfg &c, size_t n_members, bool direct, trxhip_ms_tx_group **out)
 {
-	if (!s || !out)
-		return TRXHIP_EINVAL;
-	member_state(s->m, out);
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_nco_tx_set(trxhip_ms_tx *s, const trxhip_ms_nco_cfg *cfg)
-{
-	return s ? member_nco_set(s->m, s->nco_ok, cfg) : TRXHIP_EINVAL;
-}
-
-int trxhip_ms_nco_tx_state(const trxhip_ms_tx *s, trxhip_ms_nco_status *out)
-{
-	if (!s || !out)
-		return TRXHIP_EINVAL;
-	member_nco_state(s->m, out);
-	return TRXHIP_OK;
-}
-
-// ---- the group: N members, their submits and their renders each issued as one step ----
-
-int trxhip_ms_tx_group_create(trxhip_ctx *ctx, const trxhip_ms_tx_group_cfg *cfg, trxhip_ms_tx_group **out)
-{
-	if (!cfg || !out)
-		return TRXHIP_EINVAL;
-	const trxhip_ms_tx_cfg c = { cfg->tx_full_scale, cfg->rxtx_delay, cfg->max_pending, 0 };
 	// a ring row is named by a uint32 over all members
-	if (cfg->n_members < 1 || cfg->n_members > TRXHIP_MS_TX_GROUP_MAX_MEMBERS || !valid_cfg(c) ||
-	    (uint64_t)cfg->n_members * c.max_pending > 0xffffffffull)
+	if (n_members < 1 || n_members > TRXHIP_MS_TX_GROUP_MAX_MEMBERS || !valid_cfg(c) || (uint64_t)n_members * c.max_pending > 0xffffffffull)
 		return TRXHIP_EINVAL;
 	if (ctx && (!ctx->d_tx_tables || with_device(ctx)))
 		return TRXHIP_EINVAL;
@@ -706,16 +539,18 @@ int trxhip_ms_tx_group_create(trxhip_ctx *ctx, const trxhip_ms_tx_group_cfg *cfg
 	if (!g)
 		return TRXHIP_ENOMEM;
 	g->cfg = c;
+	g->cfg.reserved = 0;
 	g->nco_ok = valid_nco_scale(c);
+	g->direct = direct;
 	try {
-		g->mem.resize(cfg->n_members);
+		g->mem.resize(n_members);
 	} catch (const std::bad_alloc &) {
 		delete g;
 		return TRXHIP_ENOMEM;
 	}
 	if (ctx) {
 		g->ctx = ctx;
-		if (hipMalloc(reinterpret_cast<void **>(&g->d_rows), (size_t)cfg->n_members * c.max_pending * sizeof(trx_mstx_row)) != hipSuccess) {
+		if (hipMalloc(reinterpret_cast<void **>(&g->d_rows), n_members * c.max_pending * sizeof(trx_mstx_row)) != hipSuccess) {
 			g->d_rows = nullptr;
 			trxhip_ms_tx_group_destroy(g);
 			return TRXHIP_ENOMEM;
@@ -725,48 +560,22 @@ int trxhip_ms_tx_group_create(trxhip_ctx *ctx, const trxhip_ms_tx_group_cfg *cfg
 	return TRXHIP_OK;
 }
 
-void trxhip_ms_tx_group_destroy(trxhip_ms_tx_group *g)
-{
-	if (!g)
-		return;
-	if (g->ctx && with_device(g->ctx) == 0) {
-		for (int k = 0; k < kBufs; k++) {
-			pin_destroy(g->stage[k]);
-			pin_destroy(g->tab[k]);
-			if (g->d_stage[k])
-				(void)hipFree(g->d_stage[k]);
-			if (g->d_tab[k])
-				(void)hipFree(g->d_tab[k]);
-		}
-		if (g->d_rows)
-			(void)hipFree(g->d_rows);
-	}
-	delete g;
-}
+trxhip_ms_tx_group *group_of(trxhip_ms_tx *s) { return reinterpret_cast<trxhip_ms_tx_group *>(s); }
+const trxhip_ms_tx_group *group_of(const trxhip_ms_tx *s) { return reinterpret_cast<const trxhip_ms_tx_group *>(s); }
 
-int trxhip_ms_tx_group_size(const trxhip_ms_tx_group *g)
-{
-	return g ? (int)g->mem.size() : TRXHIP_EINVAL;
-}
-
-int trxhip_ms_tx_group_set_ta(trxhip_ms_tx_group *g, uint32_t member, int val)
-{
-	if (!g || member >= g->mem.size() || !valid_ta(val))
-		return TRXHIP_EINVAL;
-	g->mem[member].timing_advance = val * 4;
-	return TRXHIP_OK;
-}
-
-int trxhip_ms_tx_group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, const trxhip_ms_tx_req *h_reqs, size_t n,
-			      const trxhip_ms_tx_clock *h_now, trxhip_ms_tx_plan *h_plan, size_t *bad, void *stream)
+// n requests, all or nothing.  h_member == NULL: every request is member 0's (the single object).  The QUEUED rows are packed
+// into a pinned buffer; a group sends them up in one copy with their ring destinations behind them and one launch scatters
+// them, `direct` copies every run of consecutive ring rows to where it lies.
+int group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, const trxhip_ms_tx_req *h_reqs, size_t n, const trxhip_ms_tx_clock *h_now,
+		 trxhip_ms_tx_plan *h_plan, size_t *bad, void *stream)
 {
 	if (bad)
 		*bad = (size_t)-1;
-	if (!g || ((!h_member || !h_reqs || !h_now) && n))
+	if (!g || ((!h_reqs || !h_now) && n))
 		return TRXHIP_EINVAL;
 	for (size_t i = 0; i < n; i++) {
-		const bool ok = h_member[i] < g->mem.size() && valid_request(h_reqs[i]) &&
-				valid_clock(h_now[h_member[i]].fn, h_now[h_member[i]].tn, h_now[h_member[i]].ts);
+		const uint32_t mi = h_member ? h_member[i] : 0;
+		const bool ok = mi < g->mem.size() && valid_request(h_reqs[i]) && valid_clock(h_now[mi].fn, h_now[mi].tn, h_now[mi].ts);
 		if (!ok) {
 			if (bad)
 				*bad = i;
@@ -779,24 +588,24 @@ int trxhip_ms_tx_group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, c
 	const bool dev = g->ctx != nullptr;
 	const size_t ring = g->mem.size() * (size_t)g->cfg.max_pending;
 	const size_t most = std::min(n, ring);                         /* no call queues more */
+	const size_t per_row = sizeof(trx_mstx_row) + (g->direct ? 0 : sizeof(uint32_t));
 	const int k = g->next_stage;
 	PinBuf &pb = g->stage[k];
 	if (dev) {
 		if (with_device(g->ctx))
 			return TRXHIP_EIO;
-		const size_t bytes = most * (sizeof(trx_mstx_row) + sizeof(uint32_t));
-		int rc = pin_acquire(pb, bytes);                           /* waits for the submit 4 calls back: it read d_stage[k] */
-		if (rc == TRXHIP_OK)
-			rc = dev_reserve(g->d_stage[k], g->d_stage_cap[k], bytes);
+		int rc = pin_acquire(pb, most * per_row);                  /* waits for the submit 4 calls back: its copies read the buffer */
+		if (rc == TRXHIP_OK && !g->direct)
+			rc = dev_reserve(g->d_stage[k], g->d_stage_cap[k], most * per_row);
 		if (rc != TRXHIP_OK)
 			return rc;
 	}
 	trx_mstx_row *rows = reinterpret_cast<trx_mstx_row *>(pb.h);
-	std::vector<uint32_t> &call_dst = g->call_dst;                 /* they go behind the rows once their number is known */
+	std::vector<uint32_t> &call_dst = g->call_dst;                 /* a group's go behind the rows once their number is known */
 	call_dst.clear();
 	size_t nq = 0;
 	for (size_t i = 0; i < n; i++) {
-		const uint32_t mi = h_member[i];
+		const uint32_t mi = h_member ? h_member[i] : 0;
 		const trxhip_ms_tx_clock &now = h_now[mi];
 		trxhip_ms_tx_plan p;
 		uint32_t ring_row = 0;
@@ -809,13 +618,24 @@ int trxhip_ms_tx_group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, c
 	}
 	if (!dev || nq == 0)
 		return TRXHIP_OK;
-	memcpy(rows + nq, call_dst.data(), nq * sizeof(uint32_t));
-	int rc = hipMemcpyAsync(g->d_stage[k], pb.h, nq * (sizeof(trx_mstx_row) + sizeof(uint32_t)), hipMemcpyHostToDevice, st) == hipSuccess
-			 ? TRXHIP_OK
-			 : TRXHIP_EIO;
-	if (rc == TRXHIP_OK)
-		rc = trx_launch_ms_tx_stage(reinterpret_cast<const trx_mstx_row *>(g->d_stage[k]),
-					    reinterpret_cast<const uint32_t *>(g->d_stage[k] + nq * sizeof(trx_mstx_row)), nq, g->d_rows, ring, st);
+	int rc = TRXHIP_OK;
+	if (g->direct) {
+		// one copy per run of consecutive ring rows: one per call while the free rows are not fragmented
+		for (size_t i = 0, j; i < nq && rc == TRXHIP_OK; i = j) {
+			j = i + 1;
+			while (j < nq && call_dst[j] == call_dst[j - 1] + 1)
+				j++;
+			if (hipMemcpyAsync(g->d_rows + call_dst[i], rows + i, (j - i) * sizeof(trx_mstx_row), hipMemcpyHostToDevice, st) != hipSuccess)
+				rc = TRXHIP_EIO;
+		}
+	} else {
+		memcpy(rows + nq, call_dst.data(), nq * sizeof(uint32_t));
+		if (hipMemcpyAsync(g->d_stage[k], pb.h, nq * per_row, hipMemcpyHostToDevice, st) != hipSuccess)
+			rc = TRXHIP_EIO;
+		if (rc == TRXHIP_OK)
+			rc = trx_launch_ms_tx_stage(reinterpret_cast<const trx_mstx_row *>(g->d_stage[k]),
+						    reinterpret_cast<const uint32_t *>(g->d_stage[k] + nq * sizeof(trx_mstx_row)), nq, g->d_rows, ring, st);
+	}
 	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
 		rc = TRXHIP_EIO;
 	if (rc != TRXHIP_OK) {
@@ -827,8 +647,10 @@ int trxhip_ms_tx_group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, c
 	return TRXHIP_OK;
 }
 
-int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t out_stride, const int64_t *h_first_ts,
-				  const size_t *h_n_samples, size_t *h_n_drawn, int *bad_member, void *stream)
+// Every member's window, all or nothing: one table (`direct`: the one member's segments), one copy, one launch, one event, for a
+// group of any size.
+int group_render(trxhip_ms_tx_group *g, int16_t *d_out, size_t out_stride, const int64_t *h_first_ts, const size_t *h_n_samples,
+		 size_t *h_n_drawn, int *bad_member, void *stream)
 {
 	if (bad_member)
 		*bad_member = -1;
@@ -861,6 +683,8 @@ int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t 
 	if (n_rendered == 0)
 		return TRXHIP_OK;
 	hipStream_t st = static_cast<hipStream_t>(stream);
+	if (g->direct)
+		return render_segments(g, d_out, h_n_samples[0], h_first_ts[0], h_n_drawn, st);
 	const int k = g->next_tab;
 	PinBuf &pb = g->tab[k];
 	if (dev) {
@@ -932,6 +756,76 @@ int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t 
 	return TRXHIP_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+// ---- the group: N members, their submits and their renders each issued as one step ----
+
+int trxhip_ms_tx_group_create(trxhip_ctx *ctx, const trxhip_ms_tx_group_cfg *cfg, trxhip_ms_tx_group **out)
+{
+	if (!cfg || !out)
+		return TRXHIP_EINVAL;
+	return group_create(ctx, trxhip_ms_tx_cfg{ cfg->tx_full_scale, cfg->rxtx_delay, cfg->max_pending, 0 }, cfg->n_members, false, out);
+}
+
+void trxhip_ms_tx_group_destroy(trxhip_ms_tx_group *g)
+{
+	if (!g)
+		return;
+	if (g->ctx && with_device(g->ctx) == 0) {
+		for (int k = 0; k < kBufs; k++) {
+			pin_destroy(g->stage[k]);
+			pin_destroy(g->tab[k]);
+			if (g->d_stage[k])
+				(void)hipFree(g->d_stage[k]);
+			if (g->d_tab[k])
+				(void)hipFree(g->d_tab[k]);
+		}
+		if (g->d_rows)
+			(void)hipFree(g->d_rows);
+	}
+	delete g;
+}
+
+int trxhip_ms_tx_group_size(const trxhip_ms_tx_group *g)
+{
+	return g ? (int)g->mem.size() : TRXHIP_EINVAL;
+}
+
+int trxhip_ms_tx_group_set_ta(trxhip_ms_tx_group *g, uint32_t member, int val)
+{
+	if (!g || member >= g->mem.size() || !valid_ta(val))
+		return TRXHIP_EINVAL;
+	g->mem[member].timing_advance = val * 4;
+	return TRXHIP_OK;
+}
+
+int trxhip_ms_tx_group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, const trxhip_ms_tx_req *h_reqs, size_t n,
+			      const trxhip_ms_tx_clock *h_now, trxhip_ms_tx_plan *h_plan, size_t *bad, void *stream)
+{
+	if (!h_member && n) {
+		if (bad)
+			*bad = (size_t)-1;
+		return TRXHIP_EINVAL;
+	}
+	return group_submit(g, h_member, h_reqs, n, h_now, h_plan, bad, stream);
+}
+
+int trxhip_ms_tx_group_render_s16(trxhip_ms_tx_group *g, int16_t *d_out, size_t out_stride, const int64_t *h_first_ts,
+				  const size_t *h_n_samples, size_t *h_n_drawn, int *bad_member, void *stream)
+{
+	return group_render(g, d_out, out_stride, h_first_ts, h_n_samples, h_n_drawn, bad_member, stream);
+}
+
+int trxhip_ms_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_tx_status *out)
+{
+	if (!g || member >= g->mem.size() || !out)
+		return TRXHIP_EINVAL;
+	member_state(g->mem[member], out);
+	return TRXHIP_OK;
+}
+
 int trxhip_ms_nco_tx_group_set(trxhip_ms_tx_group *g, uint32_t member, const trxhip_ms_nco_cfg *cfg)
 {
 	return g && member < g->mem.size() ? member_nco_set(g->mem[member], g->nco_ok, cfg) : TRXHIP_EINVAL;
@@ -945,12 +839,40 @@ int trxhip_ms_nco_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, t
 	return TRXHIP_OK;
 }
 
-int trxhip_ms_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_tx_status *out)
+// ---- the single object: member 0 of a group of one that issues directly ----
+
+int trxhip_ms_tx_create(trxhip_ctx *ctx, const trxhip_ms_tx_cfg *cfg, trxhip_ms_tx **out)
 {
-	if (!g || member >= g->mem.size() || !out)
+	return cfg && out ? group_create(ctx, *cfg, 1, true, reinterpret_cast<trxhip_ms_tx_group **>(out)) : TRXHIP_EINVAL;
+}
+
+void trxhip_ms_tx_destroy(trxhip_ms_tx *s) { trxhip_ms_tx_group_destroy(group_of(s)); }
+
+int trxhip_ms_tx_set_ta(trxhip_ms_tx *s, int val) { return trxhip_ms_tx_group_set_ta(group_of(s), 0, val); }
+
+int trxhip_ms_tx_state(const trxhip_ms_tx *s, trxhip_ms_tx_status *out) { return trxhip_ms_tx_group_state(group_of(s), 0, out); }
+
+int trxhip_ms_nco_tx_set(trxhip_ms_tx *s, const trxhip_ms_nco_cfg *cfg) { return trxhip_ms_nco_tx_group_set(group_of(s), 0, cfg); }
+
+int trxhip_ms_nco_tx_state(const trxhip_ms_tx *s, trxhip_ms_nco_status *out) { return trxhip_ms_nco_tx_group_state(group_of(s), 0, out); }
+
+// the one clock is h_now[0], read even when there is no request
+int trxhip_ms_tx_submit(trxhip_ms_tx *s, const trxhip_ms_tx_req *h_reqs, size_t n, uint32_t now_fn, int now_tn, int64_t now_ts,
+			trxhip_ms_tx_plan *h_plan, void *stream)
+{
+	if (!valid_clock(now_fn, now_tn, now_ts))
 		return TRXHIP_EINVAL;
-	member_state(g->mem[member], out);
-	return TRXHIP_OK;
+	const trxhip_ms_tx_clock now = { now_fn, now_tn, now_ts };
+	return group_submit(group_of(s), nullptr, h_reqs, n, &now, h_plan, nullptr, stream);
+}
+
+// The one window as arrays of length one, its stride its length.  A window of no samples is checked here: the group skips a
+// member with none unchecked.
+int trxhip_ms_tx_render_s16(trxhip_ms_tx *s, int16_t *d_out, size_t n_samples, int64_t first_ts, size_t *n_drawn, void *stream)
+{
+	if (!s || !valid_window(group_of(s)->mem[0], n_samples, first_ts))
+		return TRXHIP_EINVAL;
+	return group_render(group_of(s), d_out, n_samples, &first_ts, &n_samples, n_drawn, nullptr, stream);
 }
 
 }  // extern "C"

@@ -112,6 +112,51 @@ def test_straddle(trx, cut):
     assert np.array_equal(whole[40:665], row)
 
 
+# ---- windows and bursts round the 625-sample pieces a render is cut into (segments here, tiles in a group) ----
+
+@pytest.mark.parametrize("n", [1, 3, 624, 625, 626, 1249, 1251])
+def test_window_lengths_round_the_tile(trx, n):
+    """windows that start 1 sample before a burst and end inside the first tile, at its end, one sample into the second and round
+    the end of the second; the burst is retired once its last sample is drawn, and a second render draws the rest"""
+    tx, ts, row = one_burst(trx, np.random.default_rng(40))
+    got, nd = render(tx, n, ts - 1, shift=n & 1)
+    assert np.array_equal(got, expected_stream(n, ts - 1, [(ts, row)])) and row.any()
+    assert nd == (n >= 626) and tx.state()["pending"] == (n < 626)
+    rest, nd = render(tx, 700, ts - 1 + n)
+    assert np.array_equal(rest, expected_stream(700, ts - 1 + n, [(ts, row)])) and nd == (n < 626)
+    assert tx.state()["drawn"] == 1 and tx.state()["pending"] == 0
+
+
+@pytest.mark.parametrize("lead", [624, 625, 626])
+def test_burst_at_the_tile_boundary(trx, lead):
+    """the burst begins one sample before the window's second tile, exactly at it and one sample after it; the tiles behind hold
+    its tail and then nothing; the last tile is shorter than 625"""
+    tx, ts, row = one_burst(trx, np.random.default_rng(41))
+    got, nd = render(tx, 2000, ts - lead, shift=lead & 1)
+    assert nd == 1 and np.array_equal(got, expected_stream(2000, ts - lead, [(ts, row)]))
+    assert np.array_equal(got[lead:lead + 625], row) and row.any()
+
+
+@pytest.mark.parametrize("lead", [0, 1, 312])
+@pytest.mark.parametrize("gap", [0, 4])
+def test_two_bursts_in_one_tile(trx, gap, lead):
+    """adjacent TNs that touch, and 4 samples apart after a timing advance that fell by 1: a tile of the window holds the first
+    burst's tail, the gap (or none) and the second burst's head"""
+    rng = np.random.default_rng(42)
+    tx = trxhip.MsTxScheduler(trx, tx_full_scale=9830, rxtx_delay=0, max_pending=8)
+    bits = some_bits(rng, 2)
+    tx.set_ta(10)
+    a = tx.submit(trxhip.ms_tx_requests(1003, 4, 0, bits[:1]), CLOCK)
+    tx.set_ta(10 - gap // 4)
+    b = tx.submit(trxhip.ms_tx_requests(1003, 5, 15, bits[1:]), CLOCK)
+    ts = [int(a["radio_ts"][0]), int(b["radio_ts"][0])]
+    assert a["status"][0] == M.QUEUED and b["status"][0] == M.QUEUED and ts[1] - ts[0] == 625 + gap
+    rows = [rows_of(trx, bits[:1], 4, a["scale"])[0], rows_of(trx, bits[1:], 5, b["scale"])[0]]
+    got, nd = render(tx, 2400, ts[0] - lead, shift=lead & 1)
+    assert nd == 2 and np.array_equal(got, expected_stream(2400, ts[0] - lead, zip(ts, rows)))
+    assert rows[0].any() and rows[1].any() and not np.array_equal(rows[0], rows[1])
+
+
 def traffic(trx, tx_full_scale=2047):
     """8 frames, a burst on 5 of the 8 TNs, mixed pwr, two timing-advance changes (falling, so that nothing overlaps):
     returns the clock, the (ta, requests, the model's plan) steps and the bursts as (radio_ts, row of the row modulator)"""

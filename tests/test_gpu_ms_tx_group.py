@@ -1,7 +1,8 @@
 """The MS-side uplink scheduler group on the MI355X (trxhip_ms_tx_group_*, MsTxSchedulerGroup; ms_tx_stage_kernel,
-ms_tx_render_group_kernel): every int16 of every member's window, its state() and its n_drawn against a MsTxScheduler fed the
-same requests and windows -- wherever the bursts lie in the tiles and however the windows cut them --, nothing written outside a
-window, refusals that move nothing, and the row modulator as the pin to the reference path."""
+ms_tx_render_group_kernel): every int16 of every member's window against the row modulator's rows laid where the plans put them
+-- wherever the bursts lie in the tiles and however the windows cut them --, and the window, its state() and its n_drawn against a
+MsTxScheduler fed the same requests and windows (the same host object as a group of one: the row modulator is the yardstick
+that shares nothing with it), nothing written outside a window, and refusals that move nothing."""
 import ctypes as C
 
 import numpy as np
@@ -66,10 +67,12 @@ def single_render(tx, n, first_ts):
 
 
 class Pair:
-    """a group and one MsTxScheduler per member, fed the same"""
+    """a group and one MsTxScheduler per member, fed the same; bursts[m]: the (radio_ts, row of the row modulator) of every burst
+    member m has queued"""
 
     def __init__(self, trx, n, fs=9830, delay=-67, max_pending=64):
-        self.n = n
+        self.trx, self.n = trx, n
+        self.bursts = [[] for _ in range(n)]
         self.group = trxhip.MsTxSchedulerGroup(trx, n_members=n, tx_full_scale=fs, rxtx_delay=delay, max_pending=max_pending)
         self.single = [trxhip.MsTxScheduler(trx, tx_full_scale=fs, rxtx_delay=delay, max_pending=max_pending) for _ in range(n)]
 
@@ -83,10 +86,16 @@ class Pair:
         for m in sorted(set(members)):
             idx = [i for i, x in enumerate(members) if x == m]
             assert plan[idx].tobytes() == self.single[m].submit(reqs[idx], clocks[m]).tobytes(), m
+        queued = np.flatnonzero(plan["status"] == M.QUEUED)
+        if len(queued):
+            rows = rows_of(self.trx, reqs["bits"][queued], reqs["tn"][queued], plan["scale"][queued])
+            for i, row in zip(queued, rows):
+                self.bursts[members[i]].append((int(plan["radio_ts"][i]), row))
         return plan
 
     def render(self, sizes, first_ts, stride=None, shift=0):
-        """one group render against the members' single renders: windows, n_drawn, states.  Returns the windows."""
+        """one group render against the row modulator's rows where the plans put them, and against the members' single renders:
+        windows, n_drawn, states.  Returns the windows."""
         stride = stride or max(max(sizes), 1) + 3
         o = Out(self.n, stride, shift)
         _, nd = self.group.render(sizes, first_ts, out=o.out)
@@ -95,6 +104,8 @@ class Pair:
             if k:
                 want, nd_s = single_render(self.single[m], k, first_ts[m])
                 assert nd[m] == nd_s, (m, nd, nd_s)
+                assert np.array_equal(got[m], want), (m, k, np.flatnonzero((got[m] != want).any(axis=1))[:8])
+                want = expected_stream(k, first_ts[m], self.bursts[m])
                 assert np.array_equal(got[m], want), (m, k, np.flatnonzero((got[m] != want).any(axis=1))[:8])
             else:
                 assert nd[m] == 0

@@ -2,7 +2,8 @@
 rotating instances ms_tx_render_nco_kernel and ms_tx_render_group_nco_kernel): the rendered int16 against the composition of
 public calls -- modulate to complex64 with the plan's scale, the NCO batch call, convert_float_short -- wherever a burst lies and
 however the windows cut it, against the model (tests/ms_tx_nco_model.py) across a change of frequency and at full scale, the
-group against single objects, and the loop it closes: an uplink through a radio 2 kHz low into the BTS-side receiver."""
+group against the composition and against single objects, and the loop it closes: an uplink through a radio 2 kHz low into the
+BTS-side receiver."""
 import ctypes as C
 
 import numpy as np
@@ -279,7 +280,9 @@ def test_full_scale(trx, tabs):
 
 def group_case(trx, settings):
     """three members with their own timing advance, requests and windows, rendered twice; members[m] = (enable, hz) set before
-    the first render, and member 2's frequency halves between the renders.  Returns (group windows, single windows)"""
+    the first render, and member 2's frequency halves between the renders.  Every window is the composition's rows (composed_for
+    over rows_c64, under the member's oscillator state at that render) where the plan puts them.  Returns (group windows, single
+    windows)"""
     import torch
     rng = np.random.default_rng(66)
     g = trxhip.MsTxSchedulerGroup(trx, n_members=3, tx_full_scale=9830, rxtx_delay=-67, max_pending=16)
@@ -304,16 +307,22 @@ def group_case(trx, settings):
     for m in range(3):
         idx = [i for i, x in enumerate(members) if x == m]
         assert single[m].submit(reqs[idx], clocks[m]).tobytes() == plan[idx].tobytes()
+    x = rows_c64(trx, bits, tn, plan["scale"])
     out = []
     at = [int(plan["radio_ts"][[i for i, x in enumerate(members) if x == m]].min()) - 10 * (m + 1) for m in range(3)]
     for rnd, sizes in enumerate(([3000 + 313, 5000, 5001], [6000, 4999, 4000])):
         stride = max(sizes) + 3
         buf = torch.full((3, stride, 2), MARK, dtype=torch.int16, device="cuda:0")
+        states = [g.nco_state(m) for m in range(3)]
         _, nd = g.render(sizes, at, out=buf)
         torch.cuda.synchronize()
         a = buf.cpu().numpy()
         for m in range(3):
             assert (a[m, sizes[m]:] == MARK).all()
+            idx = [i for i, y in enumerate(members) if y == m]
+            ts = [int(t) for t in plan["radio_ts"][idx]]
+            want = expected_stream(sizes[m], at[m], zip(ts, composed_for(trx, states[m], x[idx], ts)))
+            assert np.array_equal(a[m, :sizes[m]], want), (rnd, m, np.flatnonzero((a[m, :sizes[m]] != want).any(axis=1))[:8])
             s, nd_s = render(single[m], sizes[m], at[m], shift=m & 1)
             assert nd_s == nd[m]
             out.append((a[m, :sizes[m]], s))
@@ -357,6 +366,8 @@ def test_group_render_of_the_off_member_alone(trx):
         assert nd == [3, 0, 0] and (a[1:] == MARK).all() and (a[0, 5999:] == MARK).all()
         outs.append(a[0, :5999])
         rows = rows_of(trx, bits, [4, 5, 0], plan["scale"])
+        assert np.array_equal(a[0, :5999], expected_stream(5999, ts - 5, zip([int(t) for t in plan["radio_ts"]], rows)))
+        rows = composed_for(trx, g.nco_state(0), rows_c64(trx, bits, [4, 5, 0], plan["scale"]), plan["radio_ts"])
         assert np.array_equal(a[0, :5999], expected_stream(5999, ts - 5, zip([int(t) for t in plan["radio_ts"]], rows)))
     assert np.array_equal(outs[0], outs[1])
 
