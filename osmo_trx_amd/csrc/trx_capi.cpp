@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/trxhip.h"
@@ -114,25 +115,19 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 		if (!(sum <= 2.6))
 			ctx->no_fast = 1;
 	}
-	int rc = TRXHIP_OK;
-	if (hipMalloc(reinterpret_cast<void **>(&ctx->d_tables), sizeof(trx_tables)) != hipSuccess) {
-		ctx->d_tables = nullptr;
-		rc = TRXHIP_ENOMEM;
-	} else if (hipMemcpy(ctx->d_tables, h_blob, sizeof(trx_tables), hipMemcpyHostToDevice) != hipSuccess) {
+	int rc = ctx->d_tables.alloc(1);
+	if (rc == TRXHIP_OK && hipMemcpy(ctx->d_tables, h_blob, sizeof(trx_tables), hipMemcpyHostToDevice) != hipSuccess)
 		rc = TRXHIP_EIO;
-	} else if (!ctx->redo.create()) {
-		rc = TRXHIP_ENOMEM;
-	} else {
+	if (rc == TRXHIP_OK)
+		rc = ctx->redo.create();
+	if (rc == TRXHIP_OK) {
 		/* the transmit tables (trx_tx_tables.h), next to the receive blob */
 		trx_tx_tables *tx = static_cast<trx_tx_tables *>(malloc(sizeof(trx_tx_tables)));
 		if (!tx || trx_tx_tables_generate(tx) != 0)
 			rc = TRXHIP_ENOMEM;
-		else if (hipMalloc(reinterpret_cast<void **>(&ctx->d_tx_tables), sizeof(trx_tx_tables)) != hipSuccess) {
-			ctx->d_tx_tables = nullptr;
-			rc = TRXHIP_ENOMEM;
-		} else if (hipMemcpy(ctx->d_tx_tables, tx, sizeof(trx_tx_tables), hipMemcpyHostToDevice) != hipSuccess) {
+		else if ((rc = ctx->d_tx_tables.alloc(1)) == TRXHIP_OK &&
+			 hipMemcpy(ctx->d_tx_tables, tx, sizeof(trx_tx_tables), hipMemcpyHostToDevice) != hipSuccess)
 			rc = TRXHIP_EIO;
-		}
 		free(tx);
 	}
 	if (rc == TRXHIP_OK) {
@@ -142,12 +137,9 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 			rc = TRXHIP_ENOMEM;
 		} else {
 			trx_nco_tables(nco);
-			if (hipMalloc(reinterpret_cast<void **>(&ctx->d_nco_tab), TRX_NCO_FLOATS * sizeof(float)) != hipSuccess) {
-				ctx->d_nco_tab = nullptr;
-				rc = TRXHIP_ENOMEM;
-			} else if (hipMemcpy(ctx->d_nco_tab, nco, TRX_NCO_FLOATS * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+			if ((rc = ctx->d_nco_tab.alloc(TRX_NCO_FLOATS)) == TRXHIP_OK &&
+			    hipMemcpy(ctx->d_nco_tab, nco, TRX_NCO_FLOATS * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
 				rc = TRXHIP_EIO;
-			}
 			free(nco);
 		}
 	}
@@ -155,11 +147,8 @@ int trxhip_create_from_tables(trxhip_ctx **out, int device, const void *h_blob, 
 		trxhip_destroy(ctx);
 		return rc;
 	}
-	if (hipMalloc(reinterpret_cast<void **>(&ctx->d_pool), TRX_POOL_SLOTS * 64) != hipSuccess ||
-	    hipMemset(ctx->d_pool, 0, TRX_POOL_SLOTS * 64) != hipSuccess) {
-		if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-		ctx->d_pool = nullptr;                                 /* (the kernels run without the pool) */
-	}
+	if (ctx->d_pool.alloc(TRX_POOL_SLOTS * 16) != TRXHIP_OK || hipMemset(ctx->d_pool, 0, TRX_POOL_SLOTS * 64) != hipSuccess)
+		(void)ctx->d_pool.reset();                             /* (the kernels run without the pool) */
 	*out = ctx;
 	return TRXHIP_OK;
 }
@@ -182,17 +171,7 @@ void trxhip_destroy(trxhip_ctx *ctx)
 {
 	if (!ctx)
 		return;
-	if (hipSetDevice(ctx->device) == hipSuccess) {
-		if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-		if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-		if (ctx->d_tx_tables) (void)hipFree(ctx->d_tx_tables);
-		if (ctx->d_nco_tab) (void)hipFree(ctx->d_nco_tab);
-		for (float *t : ctx->d_rs_resamp)
-			if (t) (void)hipFree(t);
-		ctx->redo.destroy();
-		ctx->sch_sync.destroy();
-		ctx->fsearch.destroy();
-	}
+	(void)with_device(ctx);
 	delete ctx;
 }
 
@@ -708,20 +687,18 @@ int trxhip_resample_batch(trxhip_ctx *ctx, const float *d_in, float *d_out, size
 		return TRXHIP_EINVAL;                  /* Resampler.cpp:100-104 */
 	if (with_device(ctx))
 		return TRXHIP_EIO;
-	const float *parts = (p == 65 && q == 48) ? &ctx->d_tables->rs6548_taps[0][0] : &ctx->d_tables->dec_taps[0];
+	const float *parts = (p == 65 && q == 48) ? &ctx->d_tables.p->rs6548_taps[0][0] : &ctx->d_tables.p->dec_taps[0];
 	if (resamp >= 0) {
 		std::lock_guard<std::mutex> lock(ctx->rs_mu);
 		if (!ctx->d_rs_resamp[resamp]) {
 			std::vector<float> taps((size_t)p * 16);
 			trx_polyphase_taps((unsigned)p, (unsigned)q, 16, 1.0f, taps.data());
-			float *d = nullptr;
-			if (hipMalloc((void **)&d, taps.size() * sizeof(float)) != hipSuccess)
+			trx_dev<float> d;
+			if (d.alloc(taps.size()) != TRXHIP_OK)
 				return TRXHIP_ENOMEM;
-			if (hipMemcpy(d, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-				(void)hipFree(d);
+			if (hipMemcpy(d, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
 				return TRXHIP_EIO;
-			}
-			ctx->d_rs_resamp[resamp] = d;
+			ctx->d_rs_resamp[resamp] = std::move(d);
 		}
 		parts = ctx->d_rs_resamp[resamp];
 	}
@@ -737,13 +714,12 @@ struct trxhip_rx_frontend {
 	int mode;                /* RXFE_FOUR_ROWS, TRXHIP_RXFE_MULTI or TRXHIP_RXFE_RESAMP */
 	int rows;                /* rows pull() writes: 4, chans, 1 */
 	int block_len, p, q;
-	float *d_parts;          /* [p][16] resampler partitions */
-	void *d_wide_hist;       /* 15 time steps x 4 int16 IQ samples; RESAMP: [2][16] int16 IQ samples, halves as d_chan_hist's */
-	void *d_chan_hist;       /* [2][4][16] complex64 ([2][rows][16] by logical channel in a MULTI object): the fused kernel reads
+	trx_dev<float> d_parts;  /* [p][16] resampler partitions */
+	trx_dev<char> d_wide_hist; /* 15 time steps x 4 int16 IQ samples; RESAMP: [2][16] int16 IQ samples, halves as d_chan_hist's */
+	trx_dev<char> d_chan_hist; /* [2][4][16] complex64 ([2][rows][16] by logical channel in a MULTI object): the fused kernel reads
 	                          * one half and leaves the other (its first and its last workgroup run at the same time) */
 	int hist_cur;
-	float *d_chan;           /* [4][cap] channelizer output scratch */
-	size_t cap;
+	trx_dev<float> d_chan;   /* [4][d_chan.cap / 8] complex64: channelizer output scratch */
 };
 
 static int rxfe_create(trxhip_ctx *ctx, int mode, int rows, int block_len, int p, int q, trxhip_rx_frontend **out)
@@ -756,12 +732,12 @@ static int rxfe_create(trxhip_ctx *ctx, int mode, int rows, int block_len, int p
 	if (!f)
 		return TRXHIP_ENOMEM;
 	f->ctx = ctx; f->mode = mode; f->rows = rows;
-	f->block_len = block_len; f->p = p; f->q = q; f->d_chan = nullptr; f->cap = 0; f->hist_cur = 0;
+	f->block_len = block_len; f->p = p; f->q = q; f->hist_cur = 0;
 	float *taps = static_cast<float *>(malloc((size_t)p * 16 * sizeof(float)));
 	if (!taps) { delete f; return TRXHIP_ENOMEM; }
 	trx_polyphase_taps((unsigned)p, (unsigned)q, 16, 1.0f, taps);
-	bool ok = hipMalloc((void **)&f->d_parts, (size_t)p * 16 * sizeof(float)) == hipSuccess &&
-		  hipMalloc(&f->d_wide_hist, 16 * 16) == hipSuccess && hipMalloc(&f->d_chan_hist, 2 * 4 * 16 * 8) == hipSuccess &&
+	bool ok = f->d_parts.alloc((size_t)p * 16) == TRXHIP_OK && f->d_wide_hist.alloc(16 * 16) == TRXHIP_OK &&
+		  f->d_chan_hist.alloc(2 * 4 * 16 * 8) == TRXHIP_OK &&
 		  hipMemcpy(f->d_parts, taps, (size_t)p * 16 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
 		  hipMemset(f->d_wide_hist, 0, 16 * 16) == hipSuccess && hipMemset(f->d_chan_hist, 0, 2 * 4 * 16 * 8) == hipSuccess;
 	free(taps);
@@ -813,12 +789,7 @@ void trxhip_rx_frontend_destroy(trxhip_rx_frontend *f)
 {
 	if (!f)
 		return;
-	if (with_device(f->ctx) == 0) {
-		if (f->d_parts) (void)hipFree(f->d_parts);
-		if (f->d_wide_hist) (void)hipFree(f->d_wide_hist);
-		if (f->d_chan_hist) (void)hipFree(f->d_chan_hist);
-		if (f->d_chan) (void)hipFree(f->d_chan);
-	}
+	(void)with_device(f->ctx);
 	delete f;
 }
 
@@ -844,25 +815,13 @@ int trxhip_rx_frontend_seed(trxhip_rx_frontend *f, const int16_t *d_wide_prev, s
 	/* run the preceding blocks through the very same two launches (their output is discarded): what they leave in
 	 * d_wide_hist / d_chan_hist is the state of a stream processed up to here */
 	const size_t n_out = n_blocks_prev * (size_t)f->block_len / f->q * f->p;
-	float *scratch = nullptr;
-	if (hipMalloc((void **)&scratch, (size_t)f->rows * n_out * 8) != hipSuccess)
+	trx_dev<float> scratch;
+	if (scratch.alloc((size_t)f->rows * n_out * 2) != TRXHIP_OK)
 		return TRXHIP_ENOMEM;
 	rc = trxhip_rx_frontend_pull(f, d_wide_prev, n_blocks_prev, scratch, n_out, stream);
 	if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess && rc == TRXHIP_OK)
 		rc = TRXHIP_EIO;
-	(void)hipFree(scratch);
 	return rc;
-}
-
-static int rxfe_scratch(trxhip_rx_frontend *f, size_t n_total)
-{
-	if (n_total <= f->cap)
-		return TRXHIP_OK;
-	if (f->d_chan) (void)hipFree(f->d_chan);
-	f->d_chan = nullptr;
-	if (hipMalloc((void **)&f->d_chan, 4 * n_total * 8) != hipSuccess) { f->cap = 0; return TRXHIP_ENOMEM; }
-	f->cap = n_total;
-	return TRXHIP_OK;
 }
 
 int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t n_blocks, float *d_out,
@@ -883,7 +842,7 @@ int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t
 	if (f->mode == TRXHIP_RXFE_RESAMP) {
 		/* int16 in, one row out (trx_rx_frontend.hip, rx_resamp_s16_kernel); the kernel reads one half of the carried samples
 		 * and leaves the other */
-		char *const sh = static_cast<char *>(f->d_wide_hist);
+		char *const sh = f->d_wide_hist;
 		const int rc = trx_launch_rx_resamp_s16(d_wide, d_out, n_total, f->p, f->q, f->d_parts, sh + (size_t)f->hist_cur * 64,
 							sh + (size_t)(f->hist_cur ^ 1) * 64, s);
 		if (rc == 0)
@@ -892,7 +851,7 @@ int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t
 	}
 	/* the four-row object: rows = the filterbank paths; a MULTI object: the active paths only, row l = logical channel l */
 	const size_t half = (size_t)f->rows * 16 * 8;
-	char *const hist = static_cast<char *>(f->d_chan_hist);
+	char *const hist = f->d_chan_hist;
 	char *const hist_in = hist + (size_t)f->hist_cur * half, *const hist_out = hist + (size_t)(f->hist_cur ^ 1) * half;
 	/* one pass, the channel-rate streams stay on the chip (trx_rx_frontend.hip, frontend_fused_kernel<rows>) ... */
 	int rc = trx_launch_frontend_fused(d_wide, d_out, n_total, f->rows, f->p, f->q, out_stride, f->d_parts, f->ctx->d_tables,
@@ -902,14 +861,15 @@ int trxhip_rx_frontend_pull(trxhip_rx_frontend *f, const int16_t *d_wide, size_t
 	if (rc != 1)
 		return rc;
 	/* ... or, for a geometry that fits no tile, the two kernels with the channel streams in a scratch buffer */
-	if ((rc = rxfe_scratch(f, n_total)) != TRXHIP_OK)
+	if ((rc = f->d_chan.reserve(4 * n_total * 2)) != TRXHIP_OK)
 		return rc;
-	rc = trx_launch_channelize(d_wide, f->d_chan, n_total, f->cap, f->ctx->d_tables, f->d_wide_hist, s);
+	const size_t cap = f->d_chan.cap / 8;                  /* samples per row */
+	rc = trx_launch_channelize(d_wide, f->d_chan, n_total, cap, f->ctx->d_tables, f->d_wide_hist, s);
 	if (f->mode == RXFE_FOUR_ROWS)
-		return rc ? rc : trx_launch_resample(f->d_chan, d_out, n_total, f->p, f->q, 4, f->cap, out_stride, f->d_parts, hist_in, s);
+		return rc ? rc : trx_launch_resample(f->d_chan, d_out, n_total, f->p, f->q, 4, cap, out_stride, f->d_parts, hist_in, s);
 	for (int l = 0; l < f->rows && rc == TRXHIP_OK; l++)
-		rc = trx_launch_resample(f->d_chan + 2 * (size_t)trx_arfcn_pchan(f->rows, l) * f->cap, d_out + 2 * (size_t)l * out_stride,
-					 n_total, f->p, f->q, 1, f->cap, out_stride, f->d_parts, hist_in + (size_t)l * 16 * 8, s);
+		rc = trx_launch_resample(f->d_chan + 2 * (size_t)trx_arfcn_pchan(f->rows, l) * cap, d_out + 2 * (size_t)l * out_stride,
+					 n_total, f->p, f->q, 1, cap, out_stride, f->d_parts, hist_in + (size_t)l * 16 * 8, s);
 	return rc;
 }
 
@@ -939,12 +899,11 @@ struct trxhip_tx_frontend {
 	int mode, chans, block_len, p, q;
 	bool fused;              /* MULTI whose geometry fits the fused kernel's tiles */
 	int hl;                  /* fused: low-rate samples of history per logical channel */
-	float *d_parts;          /* [p][16] resampler partitions, Resampler::initFilters(bw) */
-	void *d_hist;            /* fused: [chans][hl] complex64, the low-rate samples -hl .. -1 */
-	void *d_rs_hist;         /* otherwise: resample_kernel's [chans][16] (samples -15 .. -1 at 0 .. 14) */
-	void *d_row_hist;        /* MULTI unfused: [4][16], the channel-rate rows' samples -15 .. -1 */
-	float *d_scratch;        /* MULTI unfused: [4][cap] channel-rate rows; RESAMP: cap resampled samples (int16-only output) */
-	size_t cap;
+	trx_dev<float> d_parts;  /* [p][16] resampler partitions, Resampler::initFilters(bw) */
+	trx_dev<char> d_hist;    /* fused: [chans][hl] complex64, the low-rate samples -hl .. -1 */
+	trx_dev<char> d_rs_hist; /* otherwise: resample_kernel's [chans][16] (samples -15 .. -1 at 0 .. 14) */
+	trx_dev<char> d_row_hist; /* MULTI unfused: [4][16], the channel-rate rows' samples -15 .. -1 */
+	trx_dev<float> d_scratch; /* complex64; MULTI unfused: [4][cap] channel-rate rows; RESAMP: cap resampled samples (int16-only output) */
 };
 
 static size_t txfe_out_per_block(const trxhip_tx_frontend *f)
@@ -983,11 +942,10 @@ int trxhip_tx_frontend_create(trxhip_ctx *ctx, int mode, int chans, int block_le
 	float *taps = static_cast<float *>(malloc((size_t)p * 16 * sizeof(float)));
 	if (!taps) { delete f; return TRXHIP_ENOMEM; }
 	trx_polyphase_taps((unsigned)p, (unsigned)q, 16, bw, taps);
-	bool ok = hipMalloc((void **)&f->d_parts, (size_t)p * 16 * sizeof(float)) == hipSuccess &&
+	bool ok = f->d_parts.alloc((size_t)p * 16) == TRXHIP_OK &&
 		  hipMemcpy(f->d_parts, taps, (size_t)p * 16 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-		  hipMalloc(&f->d_hist, (size_t)chans * f->hl * 8) == hipSuccess &&
-		  hipMalloc(&f->d_rs_hist, (size_t)chans * 16 * 8) == hipSuccess &&
-		  hipMalloc(&f->d_row_hist, 4 * 16 * 8) == hipSuccess;
+		  f->d_hist.alloc((size_t)chans * f->hl * 8) == TRXHIP_OK && f->d_rs_hist.alloc((size_t)chans * 16 * 8) == TRXHIP_OK &&
+		  f->d_row_hist.alloc(4 * 16 * 8) == TRXHIP_OK;
 	free(taps);
 	if (!ok || trxhip_tx_frontend_reset(f, nullptr) != TRXHIP_OK || hipDeviceSynchronize() != hipSuccess) {
 		trxhip_tx_frontend_destroy(f);
@@ -1001,13 +959,7 @@ void trxhip_tx_frontend_destroy(trxhip_tx_frontend *f)
 {
 	if (!f)
 		return;
-	if (with_device(f->ctx) == 0) {
-		if (f->d_parts) (void)hipFree(f->d_parts);
-		if (f->d_hist) (void)hipFree(f->d_hist);
-		if (f->d_rs_hist) (void)hipFree(f->d_rs_hist);
-		if (f->d_row_hist) (void)hipFree(f->d_row_hist);
-		if (f->d_scratch) (void)hipFree(f->d_scratch);
-	}
+	(void)with_device(f->ctx);
 	delete f;
 }
 
@@ -1034,30 +986,26 @@ int trxhip_tx_frontend_seed(trxhip_tx_frontend *f, const float *d_in_prev, size_
 		return TRXHIP_EINVAL;
 	/* run the preceding blocks through the very same launches (their output is discarded): what they leave behind is the
 	 * state of a stream processed up to here */
-	float *scratch = nullptr;
-	if (hipMalloc((void **)&scratch, n_blocks_prev * txfe_out_per_block(f) * 8) != hipSuccess)
+	trx_dev<float> scratch;
+	if (scratch.alloc(n_blocks_prev * txfe_out_per_block(f) * 2) != TRXHIP_OK)
 		return TRXHIP_ENOMEM;
 	rc = trxhip_tx_frontend_push(f, d_in_prev, in_stride, n_blocks_prev, scratch, nullptr, 0.0f, stream);
 	if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess && rc == TRXHIP_OK)
 		rc = TRXHIP_EIO;
-	(void)hipFree(scratch);
 	return rc;
 }
 
+/* room for n samples per row, zeroed when it grows: the rows of inactive paths stay zero */
 static int txfe_scratch(trxhip_tx_frontend *f, size_t n, hipStream_t s)
 {
-	if (n <= f->cap)
+	const size_t floats = (f->mode == TRXHIP_TXFE_MULTI ? 4 : 1) * n * 2;
+	if (floats <= f->d_scratch.cap)
 		return TRXHIP_OK;
-	if (f->d_scratch) (void)hipFree(f->d_scratch);
-	f->d_scratch = nullptr;
-	f->cap = 0;
-	const size_t rows = f->mode == TRXHIP_TXFE_MULTI ? 4 : 1;
-	if (hipMalloc((void **)&f->d_scratch, rows * n * 8) != hipSuccess)
-		return TRXHIP_ENOMEM;
-	if (hipMemsetAsync(f->d_scratch, 0, rows * n * 8, s) != hipSuccess)      /* the rows of inactive paths stay zero */
-		return TRXHIP_EIO;
-	f->cap = n;
-	return TRXHIP_OK;
+	const int rc = f->d_scratch.reserve(floats);
+	if (rc != TRXHIP_OK || hipMemsetAsync(f->d_scratch, 0, floats * sizeof(float), s) == hipSuccess)
+		return rc;
+	(void)f->d_scratch.reset();
+	return TRXHIP_EIO;
 }
 
 int trxhip_tx_frontend_push(trxhip_tx_frontend *f, const float *d_in, size_t in_stride, size_t n_blocks, float *d_out_cf32,
@@ -1100,17 +1048,18 @@ int trxhip_tx_frontend_push(trxhip_tx_frontend *f, const float *d_in, size_t in_
 	/* a geometry that does not fit the fused kernel's tiles: the resampler into channel-rate rows, then the synthesis bank */
 	if ((rc = txfe_scratch(f, n_times, s)) != TRXHIP_OK)
 		return rc;
+	const size_t cap = f->d_scratch.cap / 8;               /* samples per row */
 	for (int l = 0; l < f->chans; l++) {
 		const int pc = trx_arfcn_pchan(f->chans, l);
-		rc = trx_launch_resample(d_in + 2 * (size_t)l * in_stride, f->d_scratch + 2 * (size_t)pc * f->cap, n_in, f->p, f->q, 1,
-					 in_stride, f->cap, f->d_parts, static_cast<char *>(f->d_rs_hist) + (size_t)l * 16 * 8, s);
+		rc = trx_launch_resample(d_in + 2 * (size_t)l * in_stride, f->d_scratch + 2 * (size_t)pc * cap, n_in, f->p, f->q, 1,
+					 in_stride, cap, f->d_parts, f->d_rs_hist + (size_t)l * 16 * 8, s);
 		if (rc)
 			return rc;
 	}
-	rc = trx_launch_synthesize(f->d_scratch, f->cap, f->d_row_hist, d_out_cf32, d_out_s16, s16_scale, n_times, f->ctx->d_tables, s);
+	rc = trx_launch_synthesize(f->d_scratch, cap, f->d_row_hist, d_out_cf32, d_out_s16, s16_scale, n_times, f->ctx->d_tables, s);
 	if (rc)
 		return rc;
-	return trx_launch_tx_save_hist(f->d_scratch, n_times, f->cap, 4, f->d_row_hist, 15, 16, s);
+	return trx_launch_tx_save_hist(f->d_scratch, n_times, cap, 4, f->d_row_hist, 15, 16, s);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include "../../include/trxhip.h"
 #include "trx_tables.h"
 #include "trx_tx_tables.h"
+#include "trx_mem.h"
 
 #define TRX_POOL_SLOTS 1024
 #define TRX_REDO_SLOTS 4
@@ -22,26 +23,23 @@
  * the first kernel's prefetch), then one launch probes again. */
 struct trx_redo_lists {
 	struct slot {
-		unsigned *d = nullptr;
-		size_t cap = 0;                /* bursts the buffer d has room for */
-		hipEvent_t ev = nullptr;
-		bool busy = false;             /* ev recorded after a launch that has not been waited for */
-		unsigned *h_left = nullptr;    /* pinned */
+		trx_dev<unsigned> d;           /* TRX_REDO_HDR words + one flag byte per burst */
+		trx_pin<unsigned> h_left;
 		size_t n_last = 0;             /* bursts of the launch that used the slot last */
+		trx_event ev;                  /* pending: recorded after a launch that has not been waited for */
 	};
 	std::mutex mu;
 	slot s[TRX_REDO_SLOTS];
 	unsigned next = 0;
 	unsigned backoff = 0;
 
-	/* every slot's event and pinned word; false: out of memory (destroy() releases what was made) */
-	bool create()
+	/* every slot's event and pinned word; TRXHIP_ENOMEM: out of memory */
+	int create()
 	{
 		for (slot &sl : s)
-			if (hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) != hipSuccess ||
-			    hipHostMalloc(reinterpret_cast<void **>(&sl.h_left), 64, hipHostMallocDefault) != hipSuccess)
-				return false;
-		return true;
+			if (sl.ev.create() != TRXHIP_OK || sl.h_left.alloc(16) != TRXHIP_OK)
+				return TRXHIP_ENOMEM;
+		return TRXHIP_OK;
 	}
 	/* the slot for a split launch of n bursts on `stream`, or NULL: back-off, or no list buffer (the general kernel alone) */
 	slot *acquire(size_t n, hipStream_t stream)
@@ -51,50 +49,31 @@ struct trx_redo_lists {
 			return nullptr;
 		}
 		slot &sl = s[next++ % TRX_REDO_SLOTS];
-		if (sl.busy) {
-			sl.busy = false;
-			if (hipEventSynchronize(sl.ev) != hipSuccess)
+		if (sl.ev.pending()) {
+			if (sl.ev.wait() != TRXHIP_OK)
 				return nullptr;
-			if (sl.n_last && (size_t)*reinterpret_cast<volatile unsigned *>(sl.h_left) * 32 > sl.n_last)
+			if (sl.n_last && (size_t)*reinterpret_cast<volatile unsigned *>(sl.h_left.p) * 32 > sl.n_last)
 				backoff = 63;
 		}
 		*sl.h_left = 0u;
 		sl.n_last = n;
-		if (sl.cap < n) {
-			if (sl.d) (void)hipFree(sl.d);
-			sl.d = nullptr;
-			sl.cap = 0;
-			const size_t cap = n < 65536 ? 65536 : n;
-			/* header words + one flag byte per burst, padded to whole chunks of 256; all zero between launches.  The memset
-			 * goes on the caller's stream, ahead of the two kernels that use the buffer (the slot's last launch has completed) */
-			const size_t bytes = TRX_REDO_HDR * sizeof(unsigned) + ((cap + 255) & ~(size_t)255);
-			if (hipMalloc(reinterpret_cast<void **>(&sl.d), bytes) != hipSuccess || hipMemsetAsync(sl.d, 0, bytes, stream) != hipSuccess) {
-				if (sl.d) (void)hipFree(sl.d);
-				sl.d = nullptr;
+		/* header words + one flag byte per burst (room for 65536 at the least), padded to whole chunks of 256 */
+		const size_t words = TRX_REDO_HDR + (((n < 65536 ? 65536 : n) + 255) & ~(size_t)255) / sizeof(unsigned);
+		if (sl.d.cap < words) {
+			/* all zero between launches.  The memset goes on the caller's stream, ahead of the two kernels that use the buffer
+			 * (the slot's last launch has completed) */
+			if (sl.d.reserve(words) != TRXHIP_OK || hipMemsetAsync(sl.d, 0, words * sizeof(unsigned), stream) != hipSuccess) {
+				(void)sl.d.reset();
 				return nullptr;
 			}
-			sl.cap = cap;
 		}
 		return &sl;
 	}
 	/* after the launch into sl (rc: its result) */
 	void launched(slot &sl, int rc, hipStream_t stream)
 	{
-		if (rc != 0)
-			return;
-		if (hipEventRecord(sl.ev, stream) == hipSuccess)
-			sl.busy = true;
-		else
+		if (rc == 0 && sl.ev.record(stream) != TRXHIP_OK)
 			(void)hipStreamSynchronize(stream);   /* no event: the slot is free once the stream has drained */
-	}
-	void destroy()
-	{
-		for (slot &sl : s) {
-			if (sl.busy) (void)hipEventSynchronize(sl.ev);
-			if (sl.ev) (void)hipEventDestroy(sl.ev);
-			if (sl.d) (void)hipFree(sl.d);
-			if (sl.h_left) (void)hipHostFree(sl.h_left);
-		}
 	}
 };
 
@@ -104,58 +83,20 @@ struct trx_redo_lists {
  * (the event), so ACQ calls on one context from several threads or streams run one behind the other. */
 struct trx_sch_scratch {
 	std::mutex mu;
-	float *d_power = nullptr;
-	size_t power_cap = 0;              /* floats */
-	int32_t *d_best = nullptr;
-	size_t best_cap = 0;               /* buffers */
-	hipEvent_t ev = nullptr;
-	bool busy = false;
+	trx_dev<float> d_power;
+	trx_dev<int32_t> d_best;           /* one per buffer */
+	trx_event ev;
 
 	/* room for n_bufs buffers of n_lags lags; false: out of memory */
 	bool acquire(size_t n_bufs, size_t n_lags)
 	{
-		if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-			ev = nullptr;
-			return false;
-		}
-		if (busy) {
-			busy = false;
-			if (hipEventSynchronize(ev) != hipSuccess)
-				return false;
-		}
-		if (power_cap < n_bufs * n_lags) {
-			if (d_power) (void)hipFree(d_power);
-			power_cap = 0;
-			if (hipMalloc(reinterpret_cast<void **>(&d_power), n_bufs * n_lags * sizeof(float)) != hipSuccess) {
-				d_power = nullptr;
-				return false;
-			}
-			power_cap = n_bufs * n_lags;
-		}
-		if (best_cap < n_bufs) {
-			if (d_best) (void)hipFree(d_best);
-			best_cap = 0;
-			if (hipMalloc(reinterpret_cast<void **>(&d_best), n_bufs * sizeof(int32_t)) != hipSuccess) {
-				d_best = nullptr;
-				return false;
-			}
-			best_cap = n_bufs;
-		}
-		return true;
+		return ev.create() == TRXHIP_OK && ev.wait() == TRXHIP_OK && d_power.reserve(n_bufs * n_lags) == TRXHIP_OK &&
+		       d_best.reserve(n_bufs) == TRXHIP_OK;
 	}
 	void launched(hipStream_t stream)
 	{
-		if (hipEventRecord(ev, stream) == hipSuccess)
-			busy = true;
-		else
+		if (ev.record(stream) != TRXHIP_OK)
 			(void)hipStreamSynchronize(stream);
-	}
-	void destroy()
-	{
-		if (busy) (void)hipEventSynchronize(ev);
-		if (ev) (void)hipEventDestroy(ev);
-		if (d_power) (void)hipFree(d_power);
-		if (d_best) (void)hipFree(d_best);
 	}
 };
 
@@ -165,54 +106,30 @@ struct trx_sch_scratch {
  * other without a wait. */
 struct trx_fsearch_scratch {
 	std::mutex mu;
-	trxhip_ms_fcch_hit *d_cand = nullptr;
-	size_t cap = 0;                    /* candidates */
-	hipEvent_t ev = nullptr;
+	trx_dev<trxhip_ms_fcch_hit> d_cand;
 	hipStream_t last = nullptr;        /* the stream of the launches the event is behind */
-	bool busy = false;
+	trx_event ev;
 
 	bool acquire(size_t n_cand, hipStream_t stream)
 	{
-		if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-			ev = nullptr;
+		if (ev.create() != TRXHIP_OK)
 			return false;
-		}
-		if (busy && (stream != last || cap < n_cand)) {            /* the same stream orders the calls itself: no wait */
-			busy = false;
-			if (hipEventSynchronize(ev) != hipSuccess)
-				return false;
-		}
-		if (cap < n_cand) {
-			if (d_cand) (void)hipFree(d_cand);
-			cap = 0;
-			if (hipMalloc(reinterpret_cast<void **>(&d_cand), n_cand * sizeof(trxhip_ms_fcch_hit)) != hipSuccess) {
-				d_cand = nullptr;
-				return false;
-			}
-			cap = n_cand;
-		}
-		return true;
+		if ((stream != last || d_cand.cap < n_cand) && ev.wait() != TRXHIP_OK)     /* the same stream orders the calls itself: no wait */
+			return false;
+		return d_cand.reserve(n_cand) == TRXHIP_OK;
 	}
 	void launched(hipStream_t stream)
 	{
 		last = stream;
-		if (hipEventRecord(ev, stream) == hipSuccess)
-			busy = true;
-		else
+		if (ev.record(stream) != TRXHIP_OK)
 			(void)hipStreamSynchronize(stream);
-	}
-	void destroy()
-	{
-		if (busy) (void)hipEventSynchronize(ev);
-		if (ev) (void)hipEventDestroy(ev);
-		if (d_cand) (void)hipFree(d_cand);
 	}
 };
 
 struct trxhip_ctx {
 	int device = 0;
 	int n_cu = 0;
-	trx_tables *d_tables = nullptr;
+	trx_dev<trx_tables> d_tables;
 	int no_unit = 0;    /* tables do not have the compiled-in unit structure: keep the multiplying correlation */
 	int sch_unit = 0;   /* the SCH sequence has the unit structure the kernel's compiled-in mask expects (trx_sch.hip) */
 	int no_sym = 0;     /* decimator taps not bitwise symmetric: the kernels' straight-line paths (mirrored taps) are off */
@@ -224,12 +141,12 @@ struct trxhip_ctx {
 	 * memset B, kernel A, kernel B left kernel B without a pool), no table of streams that fills up, and a launch
 	 * captured into a HIP graph is complete in itself (replays of one graph serialise).  Two launches share a pair only when
 	 * they are TRX_POOL_SLOTS pooled launches apart and still overlap -- 1024 outstanding batches of >= 32768 bursts. */
-	unsigned *d_pool = nullptr;
+	trx_dev<unsigned> d_pool;
 	int pool_enabled = 1;              /* trxhip_set_work_pool(); 0 when TRXHIP_NO_POOL is set at creation */
 	std::atomic<unsigned> pool_next{0u};
 	int nb_enabled = 1;                /* trxhip_set_nb_kernel(); 0 when TRXHIP_NO_NB_KERNEL is set at creation */
 	trx_redo_lists redo;
-	trx_tx_tables *d_tx_tables = nullptr;   /* transmit tables (trx_tx.hip), uploaded at creation */
+	trx_dev<trx_tx_tables> d_tx_tables;     /* transmit tables (trx_tx.hip), uploaded at creation */
 	/* trxhip_modulate_trxd_batch(): (float)(full_scale * pow(10, -att / 20.0)) for att = 0 .. 255, for the last full_scale */
 	std::mutex tx_mu;
 	double tx_full_scale = 0.0;
@@ -238,10 +155,10 @@ struct trxhip_ctx {
 	/* trxhip_resample_batch(): the partitions [p][16] of RadioInterfaceResamp's receive ratios (65, 96) and (52, 75), cutoff 1.0,
 	 * uploaded on first use */
 	std::mutex rs_mu;
-	float *d_rs_resamp[2] = { nullptr, nullptr };
+	trx_dev<float> d_rs_resamp[2];
 	trx_sch_scratch sch_sync;
 	trx_fsearch_scratch fsearch;
-	float *d_nco_tab = nullptr;        /* the NCO's two phasor tables (trx_ms_nco.h): 4096 floats, made on the host and uploaded at creation */
+	trx_dev<float> d_nco_tab;          /* the NCO's two phasor tables (trx_ms_nco.h): 4096 floats, made on the host and uploaded at creation */
 };
 
 static inline int with_device(const trxhip_ctx *ctx)

@@ -170,40 +170,41 @@ struct trxhip_ms_group {
 	std::vector<ms_plan> plan;             /* scratch of a pull */
 	std::vector<int> rc;
 	// device state (ctx != NULL)
-	char *d_rem = nullptr;                 /* [n][2][TRX_MSS_REM_STRIDE] samples of either format */
-	char *d_edge = nullptr;                /* [n][625] samples of either format */
-	int32_t *d_corr = nullptr, *h_corr = nullptr;      /* [n] correction words and their pinned mailbox */
-	trxhip_sch_sync_result *d_acq = nullptr, *h_acq = nullptr;   /* [n] */
+	trx_dev<char> d_rem;                   /* [n][2][TRX_MSS_REM_STRIDE] samples of either format */
+	trx_dev<char> d_edge;                  /* [n][625] samples of either format */
+	trx_dev<int32_t> d_corr;               /* [n] correction words and their pinned mailbox */
+	trx_pin<int32_t> h_corr;
+	trx_dev<trxhip_sch_sync_result> d_acq; /* [n] */
+	trx_pin<trxhip_sch_sync_result> h_acq;
 	// A launch set records ONE event behind everything it issues, the next of kTabSlots taken in turn: where the set sums
 	// corrections the event says that the mailbox holds them.
 	// The table of a launch set (not with `direct`): up to n receiver entries followed by up to n join entries, then those of gain
 	// control and of AFC where members have them on, 64 bytes each.  It is staged in the pinned area that belongs to the set's
 	// event: the area is written again only behind that event
-	char *d_tab = nullptr, *h_tab = nullptr;
-	hipEvent_t ev_tab[kTabSlots] = {};
-	bool tab_used[kTabSlots] = {};
+	trx_dev<char> d_tab;
+	trx_pin<char> h_tab;
 	int tab_at = 0;                        /* the event, and the area, the next launch set takes */
 	int corr_at = 0;                       /* those of the last launch set that summed corrections */
-	hipEvent_t ev = nullptr;               /* acquire's */
 	// gain control: the members' states, the levels and piece results of the pull in flight (it grows), the event behind the
 	// AGC launches of the last pull that had any
-	trx_agc_state *d_agc = nullptr;
-	float *d_work = nullptr;
-	size_t work_floats = 0;
-	hipEvent_t ev_agc = nullptr;
-	bool agc_used = false;
+	trx_dev<trx_agc_state> d_agc;
+	trx_dev<float> d_work;
 	// AFC: the members' states, the event behind the AFC launch of the last pull that had one
-	trx_afc_state *d_afc = nullptr;
-	hipEvent_t ev_afc = nullptr;
-	bool afc_used = false;
+	trx_dev<trx_afc_state> d_afc;
 	size_t afc_members = 0;                /* members with AFC on: while there is none a pull does not look at its slots' kinds */
 	// the NCO in front of acquire: the rows' records and their pinned staging ([n] each), the complex64 work buffer (it grows)
-	trxhip_ms_nco_row *d_nco_rec = nullptr, *h_nco_rec = nullptr;
-	float *d_nco_work = nullptr;
-	size_t nco_work_samples = 0;
+	trx_dev<trxhip_ms_nco_row> d_nco_rec;
+	trx_pin<trxhip_ms_nco_row> h_nco_rec;
+	trx_dev<float> d_nco_work;
 	// acquire_afc: the search's hit and measurement per listed buffer and their pinned copies ([n] each)
-	trxhip_ms_fcch_hit *d_fs_hit = nullptr, *h_fs_hit = nullptr;
-	trxhip_ms_fcch *d_fs_fcch = nullptr, *h_fs_fcch = nullptr;
+	trx_dev<trxhip_ms_fcch_hit> d_fs_hit;
+	trx_pin<trxhip_ms_fcch_hit> h_fs_hit;
+	trx_dev<trxhip_ms_fcch> d_fs_fcch;
+	trx_pin<trxhip_ms_fcch> h_fs_fcch;
+	// the events stand last: what is in flight is waited for before a buffer above is freed
+	trx_event ev_tab[kTabSlots];           /* the launch sets' */
+	trx_event ev;                          /* acquire's */
+	trx_event ev_agc, ev_afc;
 };
 
 namespace {
@@ -219,7 +220,7 @@ int fold_correction(trxhip_ms_group *g)
 		any = any || m.unread;
 	if (!any)
 		return TRXHIP_OK;
-	if (with_device(g->ctx) || hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess)
+	if (with_device(g->ctx) || g->ev_tab[g->corr_at].wait() != TRXHIP_OK)
 		return TRXHIP_EIO;
 	for (size_t i = 0; i < g->m.size(); i++)
 		if (g->m[i].unread) {
@@ -494,7 +495,7 @@ bool cfg_ok(const trxhip_ms_sched_cfg *cfg) { return cfg->tsc <= 7 && std::isfin
 char *stage_table(trxhip_ms_group *g)
 {
 	const int h = g->tab_at;
-	if (g->tab_used[h] && hipEventSynchronize(g->ev_tab[h]) != hipSuccess)
+	if (g->ev_tab[h].wait() != TRXHIP_OK)
 		return nullptr;
 	return g->h_tab + (size_t)h * kTabEntries * g->m.size() * 64;
 }
@@ -514,21 +515,6 @@ agc_work agc_work_of(const ms_member &m, const ms_plan &p)
 	w.n_pieces = trx_agc_pieces(m.agc.gain_check, (uint64_t)p.cnt);
 	w.floats = w.n_slots + 2 * w.n_pieces;
 	return w;
-}
-
-// room for the levels and piece results of a pull; a pull that needs more than any before waits for the device and allocates
-int reserve_work(trxhip_ms_group *g, size_t floats)
-{
-	if (floats <= g->work_floats)
-		return TRXHIP_OK;
-	if (g->d_work && hipFree(g->d_work) != hipSuccess)
-		return TRXHIP_EIO;
-	g->d_work = nullptr;
-	g->work_floats = 0;
-	if (hipMalloc((void **)&g->d_work, floats * sizeof(float)) != hipSuccess)
-		return TRXHIP_ENOMEM;
-	g->work_floats = floats;
-	return TRXHIP_OK;
 }
 
 // The FCCH slots a member with AFC on measures in its pull: those among every slot the pull cuts, ACTIVE or not, slot 0 too
@@ -696,7 +682,7 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		e.first_wave = (uint32_t)wave;
 		wave += (w.n_slots + TRX_MS_RX_SLOTS_PER_WAVE - 1) / TRX_MS_RX_SLOTS_PER_WAVE;
 	}
-	if (kr != n_rx || kj != n_join || wave != n_waves || ka != n_agc || agc_floats > g->work_floats || kf != n_afc)
+	if (kr != n_rx || kj != n_join || wave != n_waves || ka != n_agc || agc_floats > g->d_work.cap || kf != n_afc)
 		return TRXHIP_EIO;
 
 	if (!g->direct && hipMemcpyAsync(g->d_tab, rx, n_ent * 64 + (rot ? n_rx * sizeof(trx_nco_slot) : 0), hipMemcpyHostToDevice, st) != hipSuccess)
@@ -719,7 +705,7 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 		return TRXHIP_EIO;
 	if (n_rx) {
 		const float fs = g->rx_full_scale;                     /* 1.f / float(rxFullScale) (ms_upper.cpp:203), as trxhip_ms_rx_batch_*() */
-		const trx_mss_member *rt = reinterpret_cast<const trx_mss_member *>(g->d_tab);
+		const trx_mss_member *rt = reinterpret_cast<const trx_mss_member *>(g->d_tab.p);
 		const float *nt = g->ctx->d_nco_tab;
 		int rc;
 		if (!rot)
@@ -735,25 +721,22 @@ int issue_table(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int c
 	if (sum && hipMemcpyAsync(g->h_corr, g->d_corr, corr_bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
 		return TRXHIP_EIO;
 	const int h = g->tab_at;
-	if (hipEventRecord(g->ev_tab[h], st) != hipSuccess)
+	if (g->ev_tab[h].record(st) != TRXHIP_OK)
 		return TRXHIP_EIO;
-	g->tab_used[h] = true;
 	if (sum)
 		g->corr_at = h;
 	g->tab_at = (h + 1) % kTabSlots;
 	if (n_agc) {
 		const trx_agc_entry *at = g->direct ? nullptr : reinterpret_cast<const trx_agc_entry *>(g->d_tab + (n_rx + n_join) * 64);
 		if (trx_launch_ms_agc(g->direct ? ag : nullptr, at, n_agc, agc_waves, agc_pieces, trx_agc_full_scale(g->rx_full_scale), st) != 0 ||
-		    hipEventRecord(g->ev_agc, st) != hipSuccess)
+		    g->ev_agc.record(st) != TRXHIP_OK)
 			return TRXHIP_EIO;
-		g->agc_used = true;
 	}
 	if (n_afc) {
 		const trx_afc_job *ft = g->direct ? nullptr : reinterpret_cast<const trx_afc_job *>(g->d_tab + (n_rx + n_join + n_agc) * 64);
 		if (trx_launch_ms_afc(g->direct ? af : nullptr, ft, !cf32, n_afc, afc_waves, 1.0f / g->rx_full_scale, st) != 0 ||
-		    hipEventRecord(g->ev_afc, st) != hipSuccess)
+		    g->ev_afc.record(st) != TRXHIP_OK)
 			return TRXHIP_EIO;
-		g->afc_used = true;
 	}
 	return TRXHIP_OK;
 }
@@ -818,7 +801,7 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 	// ---- the straddling SCH slots the cutters follow, one slot per member in one launch set: the second
 	if (device && n_pre &&
 	    (issue_table(g, h_chunks, cf32, d_ind, d_bits, out_stride, true, n_pre, n_pre, n_pre, 0, 0, st) != TRXHIP_OK ||
-	     hipEventSynchronize(g->ev_tab[g->corr_at]) != hipSuccess))
+	     g->ev_tab[g->corr_at].wait() != TRXHIP_OK))
 		return TRXHIP_EIO;
 
 	// ---- the rest of every plan
@@ -859,9 +842,10 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		return worst;
 	}
 
-	// ---- the issue: the pull's own launch set
+	// ---- the issue: the pull's own launch set; the levels and piece results of a pull that needs more room than any before wait for
+	// the device and allocate
 	if (device && n_agc) {
-		const int rc = reserve_work(g, agc_floats);
+		const int rc = g->d_work.reserve(agc_floats);
 		if (rc != TRXHIP_OK)
 			return rc;
 	}
@@ -895,22 +879,6 @@ int group_pull(trxhip_ms_group *g, const trxhip_ms_group_chunk *h_chunks, int cf
 		if (h_n_carried)
 			h_n_carried[i] = m.first_call ? 0 : m.carried;
 	}
-	return TRXHIP_OK;
-}
-
-// room for the rotated buffers of an acquire; a call that needs more than any before frees and allocates (nothing is in flight:
-// an acquire ends with a wait)
-int reserve_nco_work(trxhip_ms_group *g, size_t samples)
-{
-	if (samples <= g->nco_work_samples)
-		return TRXHIP_OK;
-	if (g->d_nco_work && hipFree(g->d_nco_work) != hipSuccess)
-		return TRXHIP_EIO;
-	g->d_nco_work = nullptr;
-	g->nco_work_samples = 0;
-	if (hipMalloc((void **)&g->d_nco_work, samples * 2 * sizeof(float)) != hipSuccess)
-		return TRXHIP_ENOMEM;
-	g->nco_work_samples = samples;
 	return TRXHIP_OK;
 }
 
@@ -951,7 +919,8 @@ int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const v
 			// the buffers by absolute timestamp through the batch call into the work buffer; the search then reads complex64
 			if (with_device(g->ctx))
 				return TRXHIP_EIO;
-			const int rw = reserve_nco_work(g, n * buf_len);
+			// a call that needs more room than any before frees and allocates (nothing is in flight: an acquire ends with a wait)
+			const int rw = g->d_nco_work.reserve(n * buf_len * 2);
 			if (rw != TRXHIP_OK)
 				return rw;
 			for (size_t i = 0; i < n; i++) {
@@ -973,7 +942,7 @@ int group_acquire(trxhip_ms_group *g, const uint32_t *members, size_t n, const v
 		if (rc != TRXHIP_OK)
 			return rc;
 		if (hipMemcpyAsync(g->h_acq, g->d_acq, n * sizeof(*g->h_acq), hipMemcpyDeviceToHost, st) != hipSuccess ||
-		    hipEventRecord(g->ev, st) != hipSuccess || hipEventSynchronize(g->ev) != hipSuccess)
+		    g->ev.record(st) != TRXHIP_OK || g->ev.wait() != TRXHIP_OK)
 			return TRXHIP_EIO;
 		res = g->h_acq;
 		if (h_res)
@@ -1015,7 +984,7 @@ int group_acquire_afc(trxhip_ms_group *g, const uint32_t *members, size_t n, con
 	const hipStream_t st = static_cast<hipStream_t>(stream);
 	if (hipMemcpyAsync(g->h_fs_hit, g->d_fs_hit, n * sizeof(*g->h_fs_hit), hipMemcpyDeviceToHost, st) != hipSuccess ||
 	    hipMemcpyAsync(g->h_fs_fcch, g->d_fs_fcch, n * sizeof(*g->h_fs_fcch), hipMemcpyDeviceToHost, st) != hipSuccess ||
-	    hipEventRecord(g->ev, st) != hipSuccess || hipEventSynchronize(g->ev) != hipSuccess)
+	    g->ev.record(st) != TRXHIP_OK || g->ev.wait() != TRXHIP_OK)
 		return TRXHIP_EIO;
 	std::vector<int32_t> inc(n, 0);
 	for (size_t i = 0; i < n; i++)
@@ -1085,26 +1054,16 @@ int group_create(trxhip_ctx *ctx, float rx_full_scale, size_t n_members, const t
 	g->ctx = ctx;
 	const size_t n = n_members;
 	const size_t rem_bytes = n * 2 * TRX_MSS_REM_STRIDE * 8, tab_bytes = kTabEntries * n * 64;     /* tab_bytes: one table */
-	bool ok = hipMalloc((void **)&g->d_rem, rem_bytes) == hipSuccess && hipMalloc((void **)&g->d_edge, n * TRX_MSS_SLOT * 8) == hipSuccess &&
-		  hipMalloc((void **)&g->d_corr, n * sizeof(int32_t)) == hipSuccess && hipMalloc((void **)&g->d_acq, n * sizeof(*g->d_acq)) == hipSuccess &&
-		  hipHostMalloc((void **)&g->h_corr, n * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
-		  hipHostMalloc((void **)&g->h_acq, n * sizeof(*g->h_acq), hipHostMallocDefault) == hipSuccess &&
-		  hipEventCreateWithFlags(&g->ev, hipEventDisableTiming) == hipSuccess &&
-		  hipMalloc((void **)&g->d_agc, n * sizeof(trx_agc_state)) == hipSuccess &&
-		  hipEventCreateWithFlags(&g->ev_agc, hipEventDisableTiming) == hipSuccess &&
-		  hipMalloc((void **)&g->d_afc, n * sizeof(trx_afc_state)) == hipSuccess &&
-		  hipEventCreateWithFlags(&g->ev_afc, hipEventDisableTiming) == hipSuccess &&
-		  hipMalloc((void **)&g->d_nco_rec, n * sizeof(trxhip_ms_nco_row)) == hipSuccess &&
-		  hipHostMalloc((void **)&g->h_nco_rec, n * sizeof(trxhip_ms_nco_row), hipHostMallocDefault) == hipSuccess &&
-		  hipMalloc((void **)&g->d_fs_hit, n * sizeof(trxhip_ms_fcch_hit)) == hipSuccess &&
-		  hipHostMalloc((void **)&g->h_fs_hit, n * sizeof(trxhip_ms_fcch_hit), hipHostMallocDefault) == hipSuccess &&
-		  hipMalloc((void **)&g->d_fs_fcch, n * sizeof(trxhip_ms_fcch)) == hipSuccess &&
-		  hipHostMalloc((void **)&g->h_fs_fcch, n * sizeof(trxhip_ms_fcch), hipHostMallocDefault) == hipSuccess;
+	bool ok = g->d_rem.alloc(rem_bytes) == TRXHIP_OK && g->d_edge.alloc(n * TRX_MSS_SLOT * 8) == TRXHIP_OK && g->d_corr.alloc(n) == TRXHIP_OK &&
+		  g->d_acq.alloc(n) == TRXHIP_OK && g->h_corr.alloc(n) == TRXHIP_OK && g->h_acq.alloc(n) == TRXHIP_OK && g->ev.create() == TRXHIP_OK &&
+		  g->d_agc.alloc(n) == TRXHIP_OK && g->ev_agc.create() == TRXHIP_OK && g->d_afc.alloc(n) == TRXHIP_OK &&
+		  g->ev_afc.create() == TRXHIP_OK && g->d_nco_rec.alloc(n) == TRXHIP_OK && g->h_nco_rec.alloc(n) == TRXHIP_OK &&
+		  g->d_fs_hit.alloc(n) == TRXHIP_OK && g->h_fs_hit.alloc(n) == TRXHIP_OK && g->d_fs_fcch.alloc(n) == TRXHIP_OK &&
+		  g->h_fs_fcch.alloc(n) == TRXHIP_OK;
 	if (!direct)
-		ok = ok && hipMalloc((void **)&g->d_tab, tab_bytes) == hipSuccess &&
-		     hipHostMalloc((void **)&g->h_tab, kTabSlots * tab_bytes, hipHostMallocDefault) == hipSuccess;
+		ok = ok && g->d_tab.alloc(tab_bytes) == TRXHIP_OK && g->h_tab.alloc(kTabSlots * tab_bytes) == TRXHIP_OK;
 	for (int h = 0; h < kTabSlots; h++)
-		ok = ok && hipEventCreateWithFlags(&g->ev_tab[h], hipEventDisableTiming) == hipSuccess;
+		ok = ok && g->ev_tab[h].create() == TRXHIP_OK;
 	ok = ok && hipMemset(g->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(g->d_corr, 0, n * sizeof(int32_t)) == hipSuccess &&
 	     hipMemset(g->d_agc, 0, n * sizeof(trx_agc_state)) == hipSuccess && hipMemset(g->d_afc, 0, n * sizeof(trx_afc_state)) == hipSuccess &&
 	     hipStreamSynchronize(nullptr) == hipSuccess;      /* the first pull may come on a stream that does not wait for the null stream */
@@ -1135,31 +1094,8 @@ void trxhip_ms_group_destroy(trxhip_ms_group *g)
 {
 	if (!g)
 		return;
-	if (g->ctx && with_device(g->ctx) == 0) {
-		for (int h = 0; h < kTabSlots; h++) {
-			if (g->tab_used[h] && g->ev_tab[h])
-				(void)hipEventSynchronize(g->ev_tab[h]);
-			if (g->ev_tab[h]) (void)hipEventDestroy(g->ev_tab[h]);
-		}
-		if (g->ev) (void)hipEventDestroy(g->ev);
-		if (g->ev_agc) {
-			if (g->agc_used)
-				(void)hipEventSynchronize(g->ev_agc);
-			(void)hipEventDestroy(g->ev_agc);
-		}
-		if (g->ev_afc) {
-			if (g->afc_used)
-				(void)hipEventSynchronize(g->ev_afc);
-			(void)hipEventDestroy(g->ev_afc);
-		}
-		void *bufs[] = { g->d_rem, g->d_edge, g->d_corr, g->d_acq, g->d_tab, g->d_agc, g->d_work, g->d_afc, g->d_nco_rec, g->d_nco_work, g->d_fs_hit,
-				 g->d_fs_fcch };
-		for (void *p : bufs)
-			if (p) (void)hipFree(p);
-		void *pinned[] = { g->h_corr, g->h_acq, g->h_tab, g->h_nco_rec, g->h_fs_hit, g->h_fs_fcch };
-		for (void *p : pinned)
-			if (p) (void)hipHostFree(p);
-	}
+	if (g->ctx)
+		(void)with_device(g->ctx);
 	delete g;
 }
 
@@ -1288,7 +1224,7 @@ int trxhip_ms_group_pull_cf32(trxhip_ms_group *g, const trxhip_ms_group_chunk *h
 // the AGC launches in flight are through: the member's state on the device may be read or written from the host
 static int agc_settled(trxhip_ms_group *g)
 {
-	if (with_device(g->ctx) || (g->agc_used && hipEventSynchronize(g->ev_agc) != hipSuccess))
+	if (with_device(g->ctx) || g->ev_agc.wait() != TRXHIP_OK)
 		return TRXHIP_EIO;
 	return TRXHIP_OK;
 }
@@ -1366,7 +1302,7 @@ int trxhip_ms_agc_sched_feed_levels(trxhip_ms_sched *s, const float *levels, siz
 // the AFC launch in flight is through: the members' states on the device may be read from the host, d_fcch may change
 static int afc_settled(trxhip_ms_group *g)
 {
-	if (with_device(g->ctx) || (g->afc_used && hipEventSynchronize(g->ev_afc) != hipSuccess))
+	if (with_device(g->ctx) || g->ev_afc.wait() != TRXHIP_OK)
 		return TRXHIP_EIO;
 	return TRXHIP_OK;
 }

@@ -93,10 +93,8 @@ struct Pending {
 };
 
 struct PinBuf {
-	uint8_t *h = nullptr;
-	size_t cap = 0;            /* bytes */
-	hipEvent_t ev = nullptr;
-	bool used = false;
+	trx_pin<uint8_t> h;
+	trx_event ev;              /* pending: the call that used the buffer last (behind h: waited for before h is freed) */
 };
 
 // the largest |sample| the Laurent modulator makes: per phase of the 4-SPS grid a sample sums every 4th tap of c0 and of c1
@@ -174,16 +172,15 @@ struct trxhip_ms_tx_group {
 	std::vector<Member> mem;
 
 	// device state (ctx != NULL)
-	trx_mstx_row *d_rows = nullptr;            /* [n_members][max_pending] */
-	PinBuf stage[kBufs];                       /* submit: the call's rows, then (not with `direct`) their ring destinations */
-	uint8_t *d_stage[kBufs] = {};              /* not with `direct` */
-	size_t d_stage_cap[kBufs] = {};
+	trx_dev<trx_mstx_row> d_rows;              /* [n_members][max_pending] */
+	trx_dev<uint8_t> d_stage[kBufs];           /* not with `direct` */
+	trx_dev<uint8_t> d_tab[kBufs];
 	int next_stage = 0;
 	std::vector<uint32_t> call_dst;
-	PinBuf tab[kBufs];                        /* render: the member entries, then the bursts of their windows; `direct`: the segments */
-	uint8_t *d_tab[kBufs] = {};
-	size_t d_tab_cap[kBufs] = {};
 	int next_tab = 0;
+	// behind the device buffers: the calls that read those are waited for before they are freed
+	PinBuf stage[kBufs];                       /* submit: the call's rows, then (not with `direct`) their ring destinations */
+	PinBuf tab[kBufs];                         /* render: the member entries, then the bursts of their windows; `direct`: the segments */
 };
 
 namespace {
@@ -193,38 +190,10 @@ size_t pending(const Member &m) { return m.q.size() - m.head; }
 // the buffer for a call that needs `bytes`: waits for the call that used it last, grows it when it is too small
 int pin_acquire(PinBuf &b, size_t bytes)
 {
-	if (!b.ev && hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess) {
-		b.ev = nullptr;
-		return TRXHIP_ENOMEM;
-	}
-	if (b.used) {
-		if (hipEventSynchronize(b.ev) != hipSuccess)
-			return TRXHIP_EIO;
-		b.used = false;
-	}
-	if (b.cap < bytes) {
-		if (b.h)
-			(void)hipHostFree(b.h);
-		b.h = nullptr;
-		b.cap = 0;
-		const size_t cap = std::max(bytes, (size_t)4096);
-		if (hipHostMalloc(reinterpret_cast<void **>(&b.h), cap, hipHostMallocDefault) != hipSuccess) {
-			b.h = nullptr;
-			return TRXHIP_ENOMEM;
-		}
-		b.cap = cap;
-	}
-	return TRXHIP_OK;
-}
-
-void pin_destroy(PinBuf &b)
-{
-	if (b.used)
-		(void)hipEventSynchronize(b.ev);
-	if (b.ev)
-		(void)hipEventDestroy(b.ev);
-	if (b.h)
-		(void)hipHostFree(b.h);
+	int rc = b.ev.create();
+	if (rc == TRXHIP_OK)
+		rc = b.ev.wait();
+	return rc != TRXHIP_OK ? rc : b.h.reserve(std::max(bytes, (size_t)4096));
 }
 
 // submit_burst() for one request: everything but the queue
@@ -430,22 +399,7 @@ void member_state(const Member &m, trxhip_ms_tx_status *out)
 }
 
 // a device buffer of at least `bytes`, kept between calls
-int dev_reserve(uint8_t *&d, size_t &cap, size_t bytes)
-{
-	if (cap >= bytes)
-		return TRXHIP_OK;
-	if (d)
-		(void)hipFree(d);
-	d = nullptr;
-	cap = 0;
-	const size_t want = std::max(bytes, (size_t)4096);
-	if (hipMalloc(reinterpret_cast<void **>(&d), want) != hipSuccess) {
-		d = nullptr;
-		return TRXHIP_ENOMEM;
-	}
-	cap = want;
-	return TRXHIP_OK;
-}
+int dev_reserve(trx_dev<uint8_t> &d, size_t bytes) { return d.reserve(std::max(bytes, (size_t)4096)); }
 
 // zeros over [from, to) of the window that starts at first_ts, in segments of at most 625 samples
 size_t zero_segs(trx_mstx_seg *segs, size_t k, int64_t from, int64_t to, int64_t first_ts)
@@ -503,11 +457,11 @@ int render_segments(trxhip_ms_tx_group *g, int16_t *d_out, size_t n_samples, int
 	PinBuf &pb = g->tab[k];
 	int rc = pin_acquire(pb, bound * sizeof(trx_mstx_seg));     /* waits for the render 4 calls back: it read d_tab[k] */
 	if (rc == TRXHIP_OK)
-		rc = dev_reserve(g->d_tab[k], g->d_tab_cap[k], bound * sizeof(trx_mstx_seg));
+		rc = dev_reserve(g->d_tab[k], bound * sizeof(trx_mstx_seg));
 	if (rc != TRXHIP_OK)
 		return rc;
-	trx_mstx_seg *segs = reinterpret_cast<trx_mstx_seg *>(pb.h);
-	const trx_mstx_seg *d_segs = reinterpret_cast<const trx_mstx_seg *>(g->d_tab[k]);
+	trx_mstx_seg *segs = reinterpret_cast<trx_mstx_seg *>(pb.h.p);
+	const trx_mstx_seg *d_segs = reinterpret_cast<const trx_mstx_seg *>(g->d_tab[k].p);
 	const trxhip_ms_nco_row nco = member_nco_row(m, first_ts);
 	const size_t n_segs = plan_window(m, true, first_ts, end, segs, n_drawn);
 	if (n_segs > bound)
@@ -516,13 +470,12 @@ int render_segments(trxhip_ms_tx_group *g, int16_t *d_out, size_t n_samples, int
 	if (rc == TRXHIP_OK)
 		rc = m.nco.enable ? trx_launch_ms_tx_render_nco(d_segs, n_segs, g->d_rows, g->ctx->d_tx_tables, d_out, nco, g->ctx->d_nco_tab, st)
 				  : trx_launch_ms_tx_render(d_segs, n_segs, g->d_rows, g->ctx->d_tx_tables, d_out, st);
-	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
-		rc = TRXHIP_EIO;
+	if (rc == TRXHIP_OK)
+		rc = pb.ev.record(st);
 	if (rc != TRXHIP_OK) {
 		(void)hipStreamSynchronize(st);
 		return TRXHIP_EIO;
 	}
-	pb.used = true;
 	g->next_tab = (k + 1) % kBufs;
 	return TRXHIP_OK;
 }
@@ -550,8 +503,7 @@ int group_create(trxhip_ctx *ctx, const trxhip_ms_tx_cfg &c, size_t n_members, b
 	}
 	if (ctx) {
 		g->ctx = ctx;
-		if (hipMalloc(reinterpret_cast<void **>(&g->d_rows), n_members * c.max_pending * sizeof(trx_mstx_row)) != hipSuccess) {
-			g->d_rows = nullptr;
+		if (g->d_rows.alloc(n_members * c.max_pending) != TRXHIP_OK) {
 			trxhip_ms_tx_group_destroy(g);
 			return TRXHIP_ENOMEM;
 		}
@@ -596,11 +548,11 @@ int group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, const trxhip_m
 			return TRXHIP_EIO;
 		int rc = pin_acquire(pb, most * per_row);                  /* waits for the submit 4 calls back: its copies read the buffer */
 		if (rc == TRXHIP_OK && !g->direct)
-			rc = dev_reserve(g->d_stage[k], g->d_stage_cap[k], most * per_row);
+			rc = dev_reserve(g->d_stage[k], most * per_row);
 		if (rc != TRXHIP_OK)
 			return rc;
 	}
-	trx_mstx_row *rows = reinterpret_cast<trx_mstx_row *>(pb.h);
+	trx_mstx_row *rows = reinterpret_cast<trx_mstx_row *>(pb.h.p);
 	std::vector<uint32_t> &call_dst = g->call_dst;                 /* a group's go behind the rows once their number is known */
 	call_dst.clear();
 	size_t nq = 0;
@@ -633,16 +585,15 @@ int group_submit(trxhip_ms_tx_group *g, const uint32_t *h_member, const trxhip_m
 		if (hipMemcpyAsync(g->d_stage[k], pb.h, nq * per_row, hipMemcpyHostToDevice, st) != hipSuccess)
 			rc = TRXHIP_EIO;
 		if (rc == TRXHIP_OK)
-			rc = trx_launch_ms_tx_stage(reinterpret_cast<const trx_mstx_row *>(g->d_stage[k]),
+			rc = trx_launch_ms_tx_stage(reinterpret_cast<const trx_mstx_row *>(g->d_stage[k].p),
 						    reinterpret_cast<const uint32_t *>(g->d_stage[k] + nq * sizeof(trx_mstx_row)), nq, g->d_rows, ring, st);
 	}
-	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
-		rc = TRXHIP_EIO;
+	if (rc == TRXHIP_OK)
+		rc = pb.ev.record(st);
 	if (rc != TRXHIP_OK) {
 		(void)hipStreamSynchronize(st);
 		return TRXHIP_EIO;
 	}
-	pb.used = true;
 	g->next_stage = (k + 1) % kBufs;
 	return TRXHIP_OK;
 }
@@ -693,11 +644,11 @@ int group_render(trxhip_ms_tx_group *g, int16_t *d_out, size_t out_stride, const
 		const size_t bytes = n_rendered * sizeof(trx_mstx_gmember) + n_bursts * sizeof(trx_mstx_gburst);
 		int rc = pin_acquire(pb, bytes);                           /* waits for the render 4 calls back: it read d_tab[k] */
 		if (rc == TRXHIP_OK)
-			rc = dev_reserve(g->d_tab[k], g->d_tab_cap[k], bytes);
+			rc = dev_reserve(g->d_tab[k], bytes);
 		if (rc != TRXHIP_OK)
 			return rc;
 	}
-	trx_mstx_gmember *ent = reinterpret_cast<trx_mstx_gmember *>(pb.h);
+	trx_mstx_gmember *ent = reinterpret_cast<trx_mstx_gmember *>(pb.h.p);
 	trx_mstx_gburst *bur = dev ? reinterpret_cast<trx_mstx_gburst *>(ent + n_rendered) : nullptr;
 	size_t ke = 0, kb = 0;
 	uint32_t wave = 0;
@@ -741,17 +692,16 @@ int group_render(trxhip_ms_tx_group *g, int16_t *d_out, size_t out_stride, const
 			 ? TRXHIP_OK
 			 : TRXHIP_EIO;
 	if (rc == TRXHIP_OK)
-		rc = nco_on ? trx_launch_ms_tx_render_group_nco(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k]), (uint32_t)n_rendered, wave,
+		rc = nco_on ? trx_launch_ms_tx_render_group_nco(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k].p), (uint32_t)n_rendered, wave,
 								g->d_rows, g->ctx->d_tx_tables, d_out, g->ctx->d_nco_tab, st)
-			    : trx_launch_ms_tx_render_group(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k]), (uint32_t)n_rendered, wave,
+			    : trx_launch_ms_tx_render_group(reinterpret_cast<const trx_mstx_gmember *>(g->d_tab[k].p), (uint32_t)n_rendered, wave,
 							    g->d_rows, g->ctx->d_tx_tables, d_out, st);
-	if (rc == TRXHIP_OK && hipEventRecord(pb.ev, st) != hipSuccess)
-		rc = TRXHIP_EIO;
+	if (rc == TRXHIP_OK)
+		rc = pb.ev.record(st);
 	if (rc != TRXHIP_OK) {
 		(void)hipStreamSynchronize(st);
 		return TRXHIP_EIO;
 	}
-	pb.used = true;
 	g->next_tab = (k + 1) % kBufs;
 	return TRXHIP_OK;
 }
@@ -773,18 +723,8 @@ void trxhip_ms_tx_group_destroy(trxhip_ms_tx_group *g)
 {
 	if (!g)
 		return;
-	if (g->ctx && with_device(g->ctx) == 0) {
-		for (int k = 0; k < kBufs; k++) {
-			pin_destroy(g->stage[k]);
-			pin_destroy(g->tab[k]);
-			if (g->d_stage[k])
-				(void)hipFree(g->d_stage[k]);
-			if (g->d_tab[k])
-				(void)hipFree(g->d_tab[k]);
-		}
-		if (g->d_rows)
-			(void)hipFree(g->d_rows);
-	}
+	if (g->ctx)
+		(void)with_device(g->ctx);
 	delete g;
 }
 

@@ -295,21 +295,20 @@ struct trxhip_rx_sched {
 	size_t last_n = 0;
 	// device state (ctx != NULL)
 	int soft_stride = 148;
-	trxhip_burst_params *d_plan = nullptr, *d_params = nullptr, *d_edge_params = nullptr;
-	trxhip_trxd_meta *d_meta = nullptr;
-	trxhip_burst_result *d_res = nullptr, *d_edge_res = nullptr;
-	uint32_t *d_rank = nullptr, *d_idle_slot = nullptr;
-	float *d_soft = nullptr, *d_edge_soft = nullptr;
-	void *d_shift = nullptr;               /* TRXHIP_FLAG_USE_VA: [chans][max_slots][625] samples of shift_cf32's format, the detector's rows */
+	trx_dev<trxhip_burst_params> d_plan, d_params, d_edge_params;
+	trx_dev<trxhip_trxd_meta> d_meta;
+	trx_dev<trxhip_burst_result> d_res, d_edge_res;
+	trx_dev<uint32_t> d_rank, d_idle_slot;
+	trx_dev<float> d_soft, d_edge_soft;
+	trx_dev<char> d_shift;                 /* TRXHIP_FLAG_USE_VA: [chans][max_slots][625] samples of shift_cf32's format, the detector's rows */
 	int shift_cf32 = 0;
-	float *d_energy = nullptr;             /* TRXHIP_FLAG_USE_VA: [chans][max_slots], energyDetect of the slots as read */
-	void *d_edge_row = nullptr;            /* [chans][625] samples of either format (1 SPS: rows of slot 0's 157 or 156) */
-	void *d_rem = nullptr;                 /* [2][chans][TRX_RXS_REM_STRIDE] samples of either format */
-	trx_rxs_noise *d_noise = nullptr;      /* [2][chans] */
-	unsigned long long *d_ctrs = nullptr;  /* [chans][2]: rx_clipping, rx_no_burst_detected */
+	trx_dev<float> d_energy;               /* TRXHIP_FLAG_USE_VA: [chans][max_slots], energyDetect of the slots as read */
+	trx_dev<char> d_edge_row;              /* [chans][625] samples of either format (1 SPS: rows of slot 0's 157 or 156) */
+	trx_dev<char> d_rem;                   /* [2][chans][TRX_RXS_REM_STRIDE] samples of either format */
+	trx_dev<trx_rxs_noise> d_noise;        /* [2][chans] */
+	trx_dev<unsigned long long> d_ctrs;    /* [chans][2]: rx_clipping, rx_no_burst_detected */
 	int rem_half = 0, noise_half = 0;      /* the halves the next pull reads */
-	hipEvent_t ev = nullptr;               /* behind the last pull */
-	bool ev_used = false;
+	trx_event ev;                          /* behind the last pull (the last member: waited for before the buffers are freed) */
 };
 
 namespace {
@@ -321,10 +320,7 @@ int wait_pulls(trxhip_rx_sched *s)
 {
 	if (with_device(s->ctx))
 		return TRXHIP_EIO;
-	if (s->ev_used && hipEventSynchronize(s->ev) != hipSuccess)
-		return TRXHIP_EIO;
-	s->ev_used = false;
-	return TRXHIP_OK;
+	return s->ev.wait();
 }
 
 int launched() { return hipGetLastError() == hipSuccess ? TRXHIP_OK : TRXHIP_EIO; }
@@ -382,27 +378,22 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 		const bool va = (s->cfg.flags & TRXHIP_FLAG_USE_VA) != 0;
 		const bool edge_rec = straddle && !va;                 /* the straddling row has a record and a soft row of its own */
 		const size_t esz = cf32 ? 8 : 4;
-		const char *rem_in = static_cast<const char *>(s->d_rem) + (size_t)s->rem_half * chans * TRX_RXS_REM_STRIDE * esz;
-		char *rem_out = static_cast<char *>(s->d_rem) + (size_t)(s->rem_half ^ 1) * chans * TRX_RXS_REM_STRIDE * esz;
+		const char *rem_in = s->d_rem + (size_t)s->rem_half * chans * TRX_RXS_REM_STRIDE * esz;
+		char *rem_out = s->d_rem + (size_t)(s->rem_half ^ 1) * chans * TRX_RXS_REM_STRIDE * esz;
 		const unsigned bpc = (n + kThreads - 1) / kThreads;     /* blocks per channel */
 		if (n && !d_soft && !s->d_soft) {
 			/* the wire packer reads soft rows: a caller that takes none gets the object's own, chans * max_slots rows, allocated
 			 * on its first such pull (hipMalloc may wait for the device); nothing has changed yet if it fails */
-			if (hipMalloc((void **)&s->d_soft, (size_t)chans * s->cfg.max_slots * (size_t)s->soft_stride * sizeof(float)) != hipSuccess) {
-				s->d_soft = nullptr;
+			if (s->d_soft.alloc((size_t)chans * s->cfg.max_slots * (size_t)s->soft_stride) != TRXHIP_OK)
 				return TRXHIP_ENOMEM;
-			}
 		}
 		if (va && n && (!s->d_shift || s->shift_cf32 != cf32)) {
 			/* the detector's rows, in the stream's format: allocated on the first use_va pull, and again when the format changes
 			 * (only with nothing carried, see above); hipFree waits for the pulls that read the old rows.  Nothing has changed
 			 * yet if it fails */
-			if (s->d_shift)
-				(void)hipFree(s->d_shift);
-			if (hipMalloc(&s->d_shift, (size_t)chans * s->cfg.max_slots * TRX_RXS_SLOT * esz) != hipSuccess) {
-				s->d_shift = nullptr;
+			(void)s->d_shift.reset();
+			if (s->d_shift.alloc((size_t)chans * s->cfg.max_slots * TRX_RXS_SLOT * esz) != TRXHIP_OK)
 				return TRXHIP_ENOMEM;
-			}
 			s->shift_cf32 = cf32;
 		}
 		float *soft = d_soft ? d_soft : s->d_soft;
@@ -427,11 +418,11 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 			if (cf32)
 				hipLaunchKernelGGL(rx_edge_kernel<float2>, dim3(chans), dim3(kThreads), 0, st, static_cast<const float2 *>(d_in),
 						   in_stride, reinterpret_cast<const float2 *>(rem_in), reinterpret_cast<float2 *>(rem_out),
-						   s->carried, n, slot0, (size_t)cut, n_rem, static_cast<float2 *>(s->d_edge_row));
+						   s->carried, n, slot0, (size_t)cut, n_rem, reinterpret_cast<float2 *>(s->d_edge_row.p));
 			else
 				hipLaunchKernelGGL(rx_edge_kernel<uint32_t>, dim3(chans), dim3(kThreads), 0, st, static_cast<const uint32_t *>(d_in),
 						   in_stride, reinterpret_cast<const uint32_t *>(rem_in), reinterpret_cast<uint32_t *>(rem_out),
-						   s->carried, n, slot0, (size_t)cut, n_rem, static_cast<uint32_t *>(s->d_edge_row));
+						   s->carried, n, slot0, (size_t)cut, n_rem, reinterpret_cast<uint32_t *>(s->d_edge_row.p));
 			rc = launched();
 		}
 		/* use_va: detection alone, no soft bits from it (Transceiver.cpp:762-768) */
@@ -493,11 +484,10 @@ int pull(trxhip_rx_sched *s, const void *d_in, int cf32, size_t in_stride, size_
 			rc = trx_launch_pack_trxd_wire(s->d_res + o, s->d_plan + o, soft + o * (size_t)ss, ss, s->d_meta + o,
 						       d_pkt + o * (size_t)pkt_stride, pkt_stride, d_pkt_len + o, n, s->rssi_offset[c], st, nullptr);
 		}
-		if (rc == TRXHIP_OK && hipEventRecord(s->ev, st) != hipSuccess)
-			rc = TRXHIP_EIO;
+		if (rc == TRXHIP_OK)
+			rc = s->ev.record(st);
 		if (rc != TRXHIP_OK)
 			return rc == TRXHIP_EINVAL ? TRXHIP_EIO : rc;      /* (the arguments were the scheduler's own) */
-		s->ev_used = true;
 		s->rem_half ^= 1;
 		if (n)
 			s->noise_half ^= 1;
@@ -584,20 +574,12 @@ int create(trxhip_ctx *ctx, const trxhip_rx_sched_cfg *cfg, trxhip_rx_sched **ou
 	s->ctx = ctx;
 	const size_t slots = (size_t)c.chans * c.max_slots, ch = (size_t)c.chans;
 	const size_t rem_bytes = 2 * ch * TRX_RXS_REM_STRIDE * 8, noise_bytes = 2 * ch * sizeof(trx_rxs_noise);
-	bool ok = hipMalloc((void **)&s->d_plan, slots * sizeof(trxhip_burst_params)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_params, slots * sizeof(trxhip_burst_params)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_meta, slots * sizeof(trxhip_trxd_meta)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_res, slots * sizeof(trxhip_burst_result)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_rank, slots * sizeof(uint32_t)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_idle_slot, slots * sizeof(uint32_t)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_edge_params, ch * sizeof(trxhip_burst_params)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_edge_res, ch * sizeof(trxhip_burst_result)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_edge_soft, ch * (size_t)s->soft_stride * sizeof(float)) == hipSuccess &&
-		  hipMalloc((void **)&s->d_edge_row, ch * TRX_RXS_SLOT * 8) == hipSuccess &&
-		  hipMalloc((void **)&s->d_rem, rem_bytes) == hipSuccess && hipMalloc((void **)&s->d_noise, noise_bytes) == hipSuccess &&
-		  hipMalloc((void **)&s->d_ctrs, ch * 2 * sizeof(unsigned long long)) == hipSuccess &&
-		  (!va || hipMalloc((void **)&s->d_energy, slots * sizeof(float)) == hipSuccess) &&
-		  hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) == hipSuccess;
+	bool ok = s->d_plan.alloc(slots) == TRXHIP_OK && s->d_params.alloc(slots) == TRXHIP_OK && s->d_meta.alloc(slots) == TRXHIP_OK &&
+		  s->d_res.alloc(slots) == TRXHIP_OK && s->d_rank.alloc(slots) == TRXHIP_OK && s->d_idle_slot.alloc(slots) == TRXHIP_OK &&
+		  s->d_edge_params.alloc(ch) == TRXHIP_OK && s->d_edge_res.alloc(ch) == TRXHIP_OK &&
+		  s->d_edge_soft.alloc(ch * (size_t)s->soft_stride) == TRXHIP_OK && s->d_edge_row.alloc(ch * TRX_RXS_SLOT * 8) == TRXHIP_OK &&
+		  s->d_rem.alloc(rem_bytes) == TRXHIP_OK && s->d_noise.alloc(2 * ch) == TRXHIP_OK && s->d_ctrs.alloc(ch * 2) == TRXHIP_OK &&
+		  (!va || s->d_energy.alloc(slots) == TRXHIP_OK) && s->ev.create() == TRXHIP_OK;
 	/* the ring starts as std::vector<float>(20): zeros, itr 0, mNoiseLev 0 (Transceiver.cpp:64) */
 	ok = ok && hipMemset(s->d_rem, 0, rem_bytes) == hipSuccess && hipMemset(s->d_noise, 0, noise_bytes) == hipSuccess &&
 	     hipMemset(s->d_ctrs, 0, ch * 2 * sizeof(unsigned long long)) == hipSuccess &&
@@ -628,15 +610,8 @@ void trxhip_rx_sched_destroy(trxhip_rx_sched *s)
 {
 	if (!s)
 		return;
-	if (s->ctx && with_device(s->ctx) == 0) {
-		if (s->ev_used)
-			(void)hipEventSynchronize(s->ev);
-		if (s->ev) (void)hipEventDestroy(s->ev);
-		void *bufs[] = { s->d_plan, s->d_params, s->d_meta, s->d_res, s->d_rank, s->d_idle_slot, s->d_soft, s->d_edge_params,
-				 s->d_edge_res, s->d_edge_soft, s->d_edge_row, s->d_rem, s->d_noise, s->d_ctrs, s->d_shift, s->d_energy };
-		for (void *p : bufs)
-			if (p) (void)hipFree(p);
-	}
+	if (s->ctx)
+		(void)with_device(s->ctx);
 	delete s;
 }
 

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/trxhip.h"
@@ -102,21 +103,22 @@ struct trxhip_tx_sched {
 
 	// device state (ctx != NULL)
 	size_t n_rows = 0;
-	uint8_t *h_rows = nullptr, *d_rows = nullptr;          /* pinned mirror and device ring, TRX_TXS_ROW_STRIDE each */
+	trx_pin<uint8_t> h_rows;                               /* pinned mirror and device ring, TRX_TXS_ROW_STRIDE each */
+	trx_dev<uint8_t> d_rows;
 	std::vector<int32_t> free_rows, dirty_rows;
-	trx_tx_fill *d_fill = nullptr;                         /* [chans][TRX_TXS_ENTRIES] */
+	trx_dev<trx_tx_fill> d_fill;                           /* [chans][TRX_TXS_ENTRIES] */
 	size_t buf_words = 0, buf_bytes = 0;
-	uint8_t *h_buf[kBufs] = {}, *d_buf[kBufs] = {};         /* slot words, then fill updates */
-	hipEvent_t ev[kBufs] = {};
-	bool ev_used[kBufs] = {};
+	trx_pin<uint8_t> h_buf[kBufs];                         /* slot words, then fill updates */
+	trx_dev<uint8_t> d_buf[kBufs];
 	std::vector<int32_t> held[kBufs];                      /* rows the render in buffer k consumed */
 	int next_buf = 0;
 	uint64_t n_renders = 0;
 	std::vector<int32_t> consumed;                         /* rows consumed by the render being planned */
 	std::vector<trx_tx_fill_update> upd;
 	// front end remainder (render_frontend)
-	float *d_carry = nullptr;
-	size_t carry_stride = 0, carried = 0;
+	trx_dev<float> d_carry;                                /* [chans][d_carry.cap / (2 * chans)] complex64 */
+	size_t carried = 0;
+	trx_event ev[kBufs];                                   /* pending: the render in buffer k (last: waited for before anything is freed) */
 };
 
 namespace {
@@ -135,7 +137,6 @@ void release_buf(trxhip_tx_sched *s, int k)
 	for (int32_t r : s->held[k])
 		s->free_rows.push_back(r);
 	s->held[k].clear();
-	s->ev_used[k] = false;
 }
 
 // wait for the oldest render still holding rows (only when every staging row is taken)
@@ -143,9 +144,9 @@ int reclaim_rows(trxhip_tx_sched *s)
 {
 	for (int i = 0; i < kBufs; i++) {
 		const int k = (s->next_buf + i) % kBufs;     /* oldest first */
-		if (!s->ev_used[k] || s->held[k].empty())
+		if (!s->ev[k].pending() || s->held[k].empty())
 			continue;
-		if (hipEventSynchronize(s->ev[k]) != hipSuccess)
+		if (s->ev[k].wait() != TRXHIP_OK)
 			return TRXHIP_EIO;
 		release_buf(s, k);
 		return TRXHIP_OK;
@@ -271,8 +272,8 @@ int render_into(trxhip_tx_sched *s, size_t n_slots, float *d_cf32, size_t out_st
 	if (with_device(s->ctx))
 		return TRXHIP_EIO;
 	const int k = s->next_buf;
-	if (s->ev_used[k]) {                                   /* the render 4 calls back still reads this buffer */
-		if (hipEventSynchronize(s->ev[k]) != hipSuccess)
+	if (s->ev[k].pending()) {                              /* the render 4 calls back still reads this buffer */
+		if (s->ev[k].wait() != TRXHIP_OK)
 			return TRXHIP_EIO;
 		release_buf(s, k);
 	}
@@ -289,7 +290,7 @@ int render_into(trxhip_tx_sched *s, size_t n_slots, float *d_cf32, size_t out_st
 	}
 	s->dirty_rows.clear();
 
-	uint32_t *words = reinterpret_cast<uint32_t *>(s->h_buf[k]);
+	uint32_t *words = reinterpret_cast<uint32_t *>(s->h_buf[k].p);
 	const int tn0 = s->tn;
 	s->consumed.clear();
 	s->upd.clear();
@@ -302,14 +303,14 @@ int render_into(trxhip_tx_sched *s, size_t n_slots, float *d_cf32, size_t out_st
 	    hipSuccess)
 		rc = TRXHIP_EIO;
 	if (rc == TRXHIP_OK)
-		rc = trx_launch_tx_render(reinterpret_cast<const uint32_t *>(s->d_buf[k]), n_slots, (int)s->ch.size(), tn0,
+		rc = trx_launch_tx_render(reinterpret_cast<const uint32_t *>(s->d_buf[k].p), n_slots, (int)s->ch.size(), tn0,
 					  s->cfg.sps, s->d_rows, s->d_fill, s->att,
 					  s->ctx->d_tx_tables, d_cf32, d_s16, s16_scales, out_stride, stream);
 	if (rc == TRXHIP_OK)
 		rc = trx_launch_tx_fill_update(reinterpret_cast<const trx_tx_fill_update *>(s->d_buf[k] + uoff), s->upd.size(), s->d_rows,
 					       s->d_fill, stream);
-	if (rc == TRXHIP_OK && hipEventRecord(s->ev[k], stream) != hipSuccess)
-		rc = TRXHIP_EIO;
+	if (rc == TRXHIP_OK)
+		rc = s->ev[k].record(stream);
 	if (rc != TRXHIP_OK) {
 		/* the launch did not go in: wait for the stream before the rows are reused */
 		(void)hipStreamSynchronize(stream);
@@ -319,7 +320,6 @@ int render_into(trxhip_tx_sched *s, size_t n_slots, float *d_cf32, size_t out_st
 		return rc;
 	}
 	s->held[k].swap(s->consumed);
-	s->ev_used[k] = true;
 	s->next_buf = (k + 1) % kBufs;
 	s->n_renders++;
 	return TRXHIP_OK;
@@ -366,13 +366,11 @@ int trxhip_tx_sched_create(trxhip_ctx *ctx, const trxhip_tx_sched_cfg *cfg, trxh
 	s->buf_words = (size_t)c.max_slots * c.chans;
 	s->buf_bytes = ((s->buf_words * 4 + 15) & ~(size_t)15) + (size_t)c.chans * TRX_TXS_ENTRIES * sizeof(trx_tx_fill_update);
 	const size_t fill_bytes = (size_t)c.chans * TRX_TXS_ENTRIES * sizeof(trx_tx_fill);
-	bool ok = hipHostMalloc((void **)&s->h_rows, s->n_rows * TRX_TXS_ROW_STRIDE, hipHostMallocDefault) == hipSuccess &&
-		  hipMalloc((void **)&s->d_rows, s->n_rows * TRX_TXS_ROW_STRIDE) == hipSuccess &&
-		  hipMalloc((void **)&s->d_fill, fill_bytes) == hipSuccess;
+	bool ok = s->h_rows.alloc(s->n_rows * TRX_TXS_ROW_STRIDE) == TRXHIP_OK && s->d_rows.alloc(s->n_rows * TRX_TXS_ROW_STRIDE) == TRXHIP_OK &&
+		  s->d_fill.alloc((size_t)c.chans * TRX_TXS_ENTRIES) == TRXHIP_OK;
 	for (int k = 0; ok && k < kBufs; k++)
-		ok = hipHostMalloc((void **)&s->h_buf[k], s->buf_bytes, hipHostMallocDefault) == hipSuccess &&
-		     hipMalloc((void **)&s->d_buf[k], s->buf_bytes) == hipSuccess &&
-		     hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming) == hipSuccess;
+		ok = s->h_buf[k].alloc(s->buf_bytes) == TRXHIP_OK && s->d_buf[k].alloc(s->buf_bytes) == TRXHIP_OK &&
+		     s->ev[k].create() == TRXHIP_OK;
 	if (ok) {
 		/* the filler table as descriptors: channel 0 with FILLER_DUMMY holds the dummy burst (generateDummyBurst(), sigProcLib.cpp:
 		 * 856-862) scaled by (full_scale, 0) (init()'s float scale, :123); the zero fillers are never read (the plan says ZERO) */
@@ -410,19 +408,8 @@ void trxhip_tx_sched_destroy(trxhip_tx_sched *s)
 {
 	if (!s)
 		return;
-	if (s->ctx && with_device(s->ctx) == 0) {
-		for (int k = 0; k < kBufs; k++) {
-			if (s->ev_used[k])
-				(void)hipEventSynchronize(s->ev[k]);
-			if (s->ev[k]) (void)hipEventDestroy(s->ev[k]);
-			if (s->h_buf[k]) (void)hipHostFree(s->h_buf[k]);
-			if (s->d_buf[k]) (void)hipFree(s->d_buf[k]);
-		}
-		if (s->h_rows) (void)hipHostFree(s->h_rows);
-		if (s->d_rows) (void)hipFree(s->d_rows);
-		if (s->d_fill) (void)hipFree(s->d_fill);
-		if (s->d_carry) (void)hipFree(s->d_carry);
-	}
+	if (s->ctx)
+		(void)with_device(s->ctx);
 	delete s;
 }
 
@@ -596,38 +583,34 @@ int trxhip_tx_sched_render_frontend(trxhip_tx_sched *s, size_t n_slots, trxhip_t
 	size_t most = 0;
 	for (int t = 0; t < 8; t++)
 		most = std::max(most, slot_start(t, s->cfg.max_slots, s->cfg.sps));
-	const size_t need = (size_t)block_len + most + 8;
-	if (s->carry_stride < need) {                          /* first use, or a front end of a longer block */
+	const size_t need = (size_t)block_len + most + 8, row_floats = 2 * s->ch.size();
+	if (s->d_carry.cap < need * row_floats) {              /* first use, or a front end of a longer block */
 		if (with_device(s->ctx))
 			return TRXHIP_EIO;
-		float *p = nullptr;
-		const size_t stride = need;
-		if (hipMalloc((void **)&p, (size_t)s->ch.size() * stride * 8) != hipSuccess)
+		/* the one growth that keeps contents: copy, wait for the copy, then the old block goes */
+		trx_dev<float> p;
+		if (p.alloc(need * row_floats) != TRXHIP_OK)
 			return TRXHIP_ENOMEM;
 		if (s->carried && s->d_carry &&
-		    hipMemcpy2DAsync(p, stride * 8, s->d_carry, s->carry_stride * 8, s->carried * 8, s->ch.size(), hipMemcpyDeviceToDevice, st) !=
-			    hipSuccess) {
-			(void)hipFree(p);
+		    hipMemcpy2DAsync(p, need * 8, s->d_carry, s->d_carry.cap / row_floats * 8, s->carried * 8, s->ch.size(),
+				     hipMemcpyDeviceToDevice, st) != hipSuccess)
 			return TRXHIP_EIO;
-		}
-		if (s->d_carry) {
+		if (s->d_carry)
 			(void)hipStreamSynchronize(st);
-			(void)hipFree(s->d_carry);
-		}
-		s->d_carry = p;
-		s->carry_stride = stride;
+		s->d_carry = std::move(p);
 	}
+	const size_t carry_stride = s->d_carry.cap / row_floats;
 	*n_blocks = 0;
-	int rc = n_slots ? render_into(s, n_slots, s->d_carry + 2 * s->carried, s->carry_stride, nullptr, nullptr, st) : TRXHIP_OK;
+	int rc = n_slots ? render_into(s, n_slots, s->d_carry + 2 * s->carried, carry_stride, nullptr, nullptr, st) : TRXHIP_OK;
 	if (rc != TRXHIP_OK)
 		return rc;
 	if (nb) {
 		// RadioInterface::driveTransmitRadio(): while (pushBuffer()); -- every whole block goes out, the rest stays
-		rc = trxhip_tx_frontend_push(fe, s->d_carry, s->carry_stride, nb, d_out_cf32, d_out_s16, s16_scale, stream);
+		rc = trxhip_tx_frontend_push(fe, s->d_carry, carry_stride, nb, d_out_cf32, d_out_s16, s16_scale, stream);
 		if (rc != TRXHIP_OK)
 			return rc;
 		const size_t used = nb * (size_t)block_len, rest = total - used;
-		if (rest && hipMemcpy2DAsync(s->d_carry, s->carry_stride * 8, s->d_carry + 2 * used, s->carry_stride * 8, rest * 8, s->ch.size(),
+		if (rest && hipMemcpy2DAsync(s->d_carry, carry_stride * 8, s->d_carry + 2 * used, carry_stride * 8, rest * 8, s->ch.size(),
 					     hipMemcpyDeviceToDevice, st) != hipSuccess)
 			return TRXHIP_EIO;                          /* rest < block_len <= used: the ranges do not overlap */
 	}
