@@ -1555,6 +1555,94 @@ int  trxhip_ms_nco_tx_state(const trxhip_ms_tx *s, trxhip_ms_nco_status *out);
 int  trxhip_ms_nco_tx_group_set(trxhip_ms_tx_group *g, uint32_t member, const trxhip_ms_nco_cfg *cfg);
 int  trxhip_ms_nco_tx_group_state(const trxhip_ms_tx_group *g, uint32_t member, trxhip_ms_nco_status *out);
 
+/* ---- The air interface: an MS group and one BTS joined on the device ----------------------------------------------------------
+ * One object between a group of N MSs and one BTS.  uplink: the N member rows trxhip_ms_tx_group_render_s16 wrote in, one summed
+ * int16 stream out, what trxhip_rx_sched_pull_s16 takes.  downlink: one int16 stream in (trxhip_tx_sched_render's), N member rows out,
+ * what trxhip_ms_group_chunk.d_in takes.  Every path -- one per member and direction -- has a gain, a delay in whole samples, a
+ * carrier offset and the receiver's noise.  The reference has antennas here; this is the project's own definition.  Everything is
+ * an integer behind one float stage, so the output is fixed to the bit whatever the grid, the split of the members or the chunking,
+ * and a parallel sum needs no fixed order.
+ *   ts, x      ts = the int64 timestamp of an output sample, d the path's delay, x the source's int16 sample at ts - d, or 0 where
+ *              that lies in front of the direction's first sample or its last reset.
+ *   rotation   the oscillator of "MS-side frequency correction" above as it is: p(ts) from the path's {acc, ts_ref, inc}, r the
+ *              phasor of p, y = ((float)xr rc - (float)xi rs, (float)xr rs + (float)xi rc), every product and sum rounded to
+ *              float.  The phase belongs to the output timestamp, not the source's.
+ *   contribution  c = rint(y * g256) per component, round-half-even to a 32-bit integer, g256 = gain * 256.0f, 0 <= gain <= 16.
+ *              |y| <= 46342, so |c| < 2^31.  A zero sample contributes exactly 0.
+ *   noise      of receiver lane L = 2 rx + component at ts; rx = the member on the downlink, 4096 on the uplink.  fmix32 is
+ *              murmur3's finaliser (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16), lo and hi the
+ *              halves of (uint64_t)ts: key = fmix32(seed ^ fmix32(L)) + hi * 0x9e3779b9; w = fmix32(fmix32(lo) + key); s = the
+ *              sum of w's four bytes minus 510 (an Irwin-Hall sum: symmetric, variance 21845, kurtosis 2.7);
+ *              nq = (scale * s + 128) >> 8 with scale = llrint(rms * 65536 / 147.80054127099805), 0 <= rms <= 8192 in int16
+ *              units, so the product fits 32 bits.  seed 2024, L 3, ts 0, 1, 2, 2^32, 2^63: s = 34, 185, -111, -16, 259.
+ *   output     uplink: acc = the exact integer sum of c over all members + nq; downlink: acc = c + nq per member;
+ *              out = clamp((acc + 128) >> 8, -32768, 32767), arithmetic shift, per component.
+ *   windows    the windows of a direction are contiguous: first_ts must equal the direction's end_ts, except on the first call,
+ *              which takes any first_ts.  _reset(dir, ts) forgets the source's past and sets end_ts = ts: the next window starts
+ *              there.  The object carries the last max_delay samples of every source row (on the device for a device object), so
+ *              chunking never changes a bit, also where n < d.
+ *   _set_path  {gain, delay, hz} acts at end_ts (0 before the first window).  The oscillator changes as _set of the NCO does, on
+ *              for hz != 0: the phase is continuous across a change of frequency, gain and delay jump.  hz = 0 rides as inc = 0
+ *              at phase 0, the identity (r = (1, 0) exactly): gain 1, delay 0, hz 0, no noise and one member return the input
+ *              bytes.  A new object has every path at {1, 0, 0} and no noise.
+ *   _set_noise the rms of a receiver: the member's on the downlink, the BTS's on the uplink (member ignored).
+ *   layout     uplink: member m's row at d_tx + 2 * m * tx_stride, n samples out at d_out.  downlink: n samples at d_in, member
+ *              m's row at d_out + 2 * m * out_stride.  Source and output must not overlap.
+ * Issued per call, whatever N is: one copy of a table (16 bytes per path, 16 more per downlink receiver) from one of four pinned
+ *   areas taken in turn, at most three launches (the mix; the sum of its partials when the members are split across blocks; the
+ *   save of the source's tail) and one event.  A call waits for the call of its direction issued 4 calls earlier, and may
+ *   allocate when it is larger than any before; nothing else waits, nothing calls hipDeviceSynchronize.  Issue every call of one
+ *   direction on one stream; one object is not thread-safe.  TRXHIP_EIO: destroy the object.
+ * ctx == NULL: a host object.  The same calls on host pointers, the plain loop over the same inline functions, synchronous; the
+ *   stream is ignored.  Its phasor tables are trxhip_ms_nco_tables_host's.
+ * TRXHIP_EINVAL, nothing changed: n_members outside 1 .. 4096, max_delay > 65536, delay > max_delay, gain outside 0 .. 16 or NaN,
+ *   rms outside 0 .. 8192 or NaN, |hz| > 500000 or NaN, dir not TRXHIP_AIR_UL / _DL, member >= n_members, a window that is not
+ *   contiguous, a stride < n, pointers NULL or not 4-byte aligned, n == 0 or n > 2^31 - 1.
+ * Memory: the two rings hold (n_members + 1) * max_delay samples of 4 bytes, allocated at create -- device memory for a device
+ *   object, host memory (zero-filled) for a host object: 1 GiB at 4096 members and max_delay 65536, 1 MiB at 4096 and 64.  Ask for
+ *   the largest delay the paths will use, not for the limit.  A device object also keeps 64 KB of pinned tables per direction
+ *   and, once an uplink window has split its members, shares * n * 16 bytes of partials (about 2 MB at 4096 x 5000).
+ * trxhip_air_noise_host: nq of (seed, lane, ts) for a scale in 0 .. 3632402; scale = 256 returns s; a scale outside that range
+ *   returns 0.  Host only. */
+#define TRXHIP_AIR_UL 0
+#define TRXHIP_AIR_DL 1
+#define TRXHIP_AIR_MAX_MEMBERS 4096
+#define TRXHIP_AIR_MAX_DELAY   65536
+#define TRXHIP_AIR_UL_RX       4096
+typedef struct trxhip_air_cfg {  /* 16 bytes */
+	uint32_t n_members;      /* 1 .. 4096 */
+	uint32_t max_delay;      /* samples of every source row the object carries: 0 .. 65536 */
+	uint32_t seed;           /* of the noise */
+	uint32_t reserved;
+} trxhip_air_cfg;
+typedef struct trxhip_air_path {  /* 16 bytes */
+	float    gain;           /* 0 .. 16 */
+	uint32_t delay;          /* 0 .. max_delay */
+	double   hz;             /* |hz| <= 500000, + = up */
+} trxhip_air_path;
+typedef struct trxhip_air_path_status {  /* 48 bytes */
+	float    gain;
+	uint32_t delay;
+	double   hz;
+	int32_t  inc;
+	uint32_t acc;
+	int64_t  ts_ref;
+	int32_t  noise_scale;    /* of the path's receiver */
+	uint32_t started;        /* the direction has had a window or a reset */
+	int64_t  end_ts;         /* of the direction */
+} trxhip_air_path_status;
+typedef struct trxhip_air trxhip_air;
+int  trxhip_air_create(trxhip_ctx *ctx, const trxhip_air_cfg *cfg, trxhip_air **out);
+void trxhip_air_destroy(trxhip_air *a);
+int  trxhip_air_set_path(trxhip_air *a, int dir, uint32_t member, const trxhip_air_path *p);
+int  trxhip_air_set_noise(trxhip_air *a, int dir, uint32_t member, double rms);
+int  trxhip_air_path_state(const trxhip_air *a, int dir, uint32_t member, trxhip_air_path_status *out);
+int  trxhip_air_reset(trxhip_air *a, int dir, int64_t ts);
+int  trxhip_air_uplink_s16(trxhip_air *a, const int16_t *d_tx, size_t tx_stride, int64_t first_ts, size_t n, int16_t *d_out, void *stream);
+int  trxhip_air_downlink_s16(trxhip_air *a, const int16_t *d_in, int64_t first_ts, size_t n, int16_t *d_out, size_t out_stride,
+			     void *stream);
+int32_t trxhip_air_noise_host(uint32_t seed, uint32_t lane, int64_t ts, int32_t scale);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ HOSTCXX = [shutil.which("g++") or "g++", "-D__HIP_PLATFORM_AMD__", "-I", os.path
 HOSTLINK = ["-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-result"]
 
-LIB_SOURCES = ["trx_kernel4.hip", "trx_kernels.hip", "trx_aux_kernels.hip", "trx_sch.hip", "trx_va.hip", "trx_sch_sync.hip", "trx_ms_rx.hip", "trx_tx.hip", "trx_tx_frontend.hip", "trx_rx_frontend.hip", "trx_rx_sched.hip", "trx_rx_sched_va.hip", "trx_ms_sched.hip", "trx_ms_agc.hip", "trx_ms_afc.hip", "trx_ms_nco.hip", "trx_ms_fsearch.hip", "trx_tx_sched.cpp", "trx_ms_tx.cpp", "trx_capi.cpp",
+LIB_SOURCES = ["trx_kernel4.hip", "trx_kernels.hip", "trx_aux_kernels.hip", "trx_sch.hip", "trx_va.hip", "trx_sch_sync.hip", "trx_ms_rx.hip", "trx_tx.hip", "trx_tx_frontend.hip", "trx_rx_frontend.hip", "trx_rx_sched.hip", "trx_rx_sched_va.hip", "trx_ms_sched.hip", "trx_ms_agc.hip", "trx_ms_afc.hip", "trx_ms_nco.hip", "trx_ms_fsearch.hip", "trx_air.hip", "trx_tx_sched.cpp", "trx_ms_tx.cpp", "trx_capi.cpp",
                "trx_hostpipe.cpp", "trx_tables.cpp"]
 
 

@@ -268,6 +268,15 @@ SYMBOLS = {
     "trxhip_ms_nco_tx_state": (_I, [_VP, _VP]),
     "trxhip_ms_nco_tx_group_set": (_I, [_VP, C.c_uint32, _VP]),
     "trxhip_ms_nco_tx_group_state": (_I, [_VP, C.c_uint32, _VP]),
+    "trxhip_air_create": (_I, [_VP, _VP, C.POINTER(_VP)]),
+    "trxhip_air_destroy": (None, [_VP]),
+    "trxhip_air_set_path": (_I, [_VP, _I, C.c_uint32, _VP]),
+    "trxhip_air_set_noise": (_I, [_VP, _I, C.c_uint32, C.c_double]),
+    "trxhip_air_path_state": (_I, [_VP, _I, C.c_uint32, _VP]),
+    "trxhip_air_reset": (_I, [_VP, _I, C.c_int64]),
+    "trxhip_air_uplink_s16": (_I, [_VP, _VP, _SZ, C.c_int64, _SZ, _VP, _VP]),
+    "trxhip_air_downlink_s16": (_I, [_VP, _VP, C.c_int64, _SZ, _VP, _SZ, _VP]),
+    "trxhip_air_noise_host": (C.c_int32, [C.c_uint32, C.c_uint32, C.c_int64, C.c_int32]),
 }
 
 
@@ -284,7 +293,7 @@ def load_library():
     except OSError as e:  # pragma: no cover
         raise TrxHipError(f"cannot load {path}: {e}") from e
     for name, (res, args) in SYMBOLS.items():
-        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_", "trxhip_ms_afc_", "trxhip_ms_fcch_", "trxhip_ms_nco_"))) and \
+        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_", "trxhip_ms_afc_", "trxhip_ms_fcch_", "trxhip_ms_nco_", "trxhip_air_"))) and \
                 os.environ.get("TRXHIP_LIB") and not hasattr(L, name):
             continue          # tools/measure.py ab against an older measurement build of the library (product: always bound)
         f = getattr(L, name)  # AttributeError if the export is missing
@@ -2115,6 +2124,130 @@ class MsTxSchedulerGroup:
     def close(self):
         if getattr(self, "h", None):
             self.L.trxhip_ms_tx_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+AIR_UL, AIR_DL = 0, 1                                # TRXHIP_AIR_UL, TRXHIP_AIR_DL
+AIR_MAX_MEMBERS = 4096                               # TRXHIP_AIR_MAX_MEMBERS
+AIR_MAX_DELAY = 65536                                # TRXHIP_AIR_MAX_DELAY
+AIR_PATH_STATE_DTYPE = np.dtype([("gain", "<f4"), ("delay", "<u4"), ("hz", "<f8"), ("inc", "<i4"), ("acc", "<u4"), ("ts_ref", "<i8"),
+                                 ("noise_scale", "<i4"), ("started", "<u4"), ("end_ts", "<i8")])
+assert AIR_PATH_STATE_DTYPE.itemsize == 48
+
+
+class _AirCfg(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("max_delay", C.c_uint32), ("seed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _AirPath(C.Structure):
+    _fields_ = [("gain", C.c_float), ("delay", C.c_uint32), ("hz", C.c_double)]
+
+
+def air_noise_host(seed, lane, ts, scale=256):
+    """nq of receiver lane `lane` at ts (trxhip_air_noise_host); scale = 256 returns s itself.  ts: any int, taken modulo 2^64"""
+    ts = ((int(ts) + (1 << 63)) % (1 << 64)) - (1 << 63)
+    return int(load_library().trxhip_air_noise_host(seed & 0xFFFFFFFF, lane, ts, scale))
+
+
+class AirChannel:
+    """The air interface (trxhip_air_*): n_members MSs and one BTS joined on the device.  uplink() sums the members' int16 rows --
+    MsTxSchedulerGroup.render()'s tensor -- into the one stream RxScheduler.pull() takes; downlink() turns the one stream
+    TxScheduler.render() writes into the members' rows MsRxSchedulerGroup.pull() takes.  Per path and direction a gain, a delay in
+    whole samples (<= max_delay), a carrier offset and the receiver's noise; integer arithmetic behind one float stage, so the
+    bytes do not depend on the grid or the chunking.  Windows of a direction are contiguous.  The object holds
+    (n_members + 1) * max_delay * 4 bytes of history from creation on (1 GiB at 4096 members and 65536): ask for the largest
+    delay the paths will use.
+    trx=None: a host object -- numpy arrays in and out, the plain loop over the same arithmetic, no GPU."""
+
+    def __init__(self, trx=None, n_members=1, max_delay=0, seed=0):
+        self.trx = trx
+        self.L = trx.L if trx is not None else load_library()
+        self.n = int(n_members)
+        if not 1 <= self.n <= AIR_MAX_MEMBERS or not 0 <= int(max_delay) <= AIR_MAX_DELAY:      # before a c_uint32 wraps them
+            _check(-22, "trxhip_air_create (n_members %r, max_delay %r)" % (n_members, max_delay))
+        cfg = _AirCfg(self.n, int(max_delay), seed & 0xFFFFFFFF, 0)
+        h = _VP()
+        _check(self.L.trxhip_air_create(trx.h if trx is not None else None, C.byref(cfg), C.byref(h)), "trxhip_air_create")
+        self.h = h
+
+    def set_path(self, dir, member, gain=1.0, delay=0, hz=0.0):
+        """acts at the direction's end_ts: the phase stays continuous, gain and delay jump; hz = 0 is the identity rotation"""
+        if not 0 <= int(member) < self.n or not 0 <= int(delay) <= AIR_MAX_DELAY:
+            _check(-22, "trxhip_air_set_path (member %r, delay %r)" % (member, delay))
+        p = _AirPath(float(gain), int(delay), float(hz))
+        _check(self.L.trxhip_air_set_path(self.h, dir, member, C.byref(p)), "trxhip_air_set_path")
+
+    def set_noise(self, dir, member, rms):
+        """the rms, in int16 units, of member's receiver (AIR_DL) or of the BTS's (AIR_UL, member ignored)"""
+        member = 0 if dir == AIR_UL else int(member)
+        if not 0 <= member < self.n:
+            _check(-22, "trxhip_air_set_noise (member %r)" % member)
+        _check(self.L.trxhip_air_set_noise(self.h, dir, member, float(rms)), "trxhip_air_set_noise")
+
+    def path_state(self, dir, member):
+        """AIR_PATH_STATE_DTYPE record"""
+        a = np.zeros(1, dtype=AIR_PATH_STATE_DTYPE)
+        if not 0 <= int(member) < self.n:
+            _check(-22, "trxhip_air_path_state (member %r)" % member)
+        _check(self.L.trxhip_air_path_state(self.h, dir, member, a.ctypes.data_as(_VP)), "trxhip_air_path_state")
+        return a[0]
+
+    def reset(self, dir, ts):
+        """forget the direction's past: its next window starts at ts"""
+        _check(self.L.trxhip_air_reset(self.h, dir, ts), "trxhip_air_reset")
+
+    def _out(self, shape, out):
+        if self.trx is None:
+            if out is None:
+                out = np.empty(shape, dtype=np.int16)
+            assert out.dtype == np.int16 and out.flags.c_contiguous and out.shape == shape, (out.shape, out.dtype)
+            return out, out.ctypes.data
+        torch = self.trx.torch
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int16, device=f"cuda:{self.trx.device}")
+        assert out.dtype == torch.int16 and out.is_contiguous() and tuple(out.shape) == shape, (out.shape, out.dtype)
+        assert out.is_cuda and out.device.index == self.trx.device, out.device
+        return out, out.data_ptr()
+
+    def _in(self, x, dims):
+        if self.trx is None:
+            assert isinstance(x, np.ndarray) and x.dtype == np.int16 and x.flags.c_contiguous and x.ndim == dims and x.shape[-1] == 2, \
+                (type(x), getattr(x, "shape", None))
+            return x.ctypes.data
+        assert x.dtype == self.trx.torch.int16 and x.is_contiguous() and x.dim() == dims and x.shape[-1] == 2, (x.shape, x.dtype)
+        assert x.is_cuda and x.device.index == self.trx.device, x.device
+        return x.data_ptr()
+
+    def uplink(self, rows, first_ts, n=None, out=None, stream=None):
+        """rows: int16[n_members, stride, 2], member m's window [first_ts, first_ts + n) in rows[m, :n] (n: default stride).
+        Returns the BTS's int16[n, 2]; out: such an array to write instead"""
+        p = self._in(rows, 3)
+        assert rows.shape[0] == self.n, rows.shape
+        n = rows.shape[1] if n is None else int(n)
+        out, po = self._out((n, 2), out)
+        _check(self.L.trxhip_air_uplink_s16(self.h, p, rows.shape[1], first_ts, n, po,
+                                            self.trx._stream(stream) if self.trx is not None else None), "trxhip_air_uplink_s16")
+        return out
+
+    def downlink(self, x, first_ts, out=None, stream=None):
+        """x: int16[n, 2], the BTS's window [first_ts, first_ts + n).  Returns int16[n_members, n, 2]; out: such an array to write
+        instead"""
+        p = self._in(x, 2)
+        n = x.shape[0]
+        out, po = self._out((self.n, n, 2), out)
+        _check(self.L.trxhip_air_downlink_s16(self.h, p, first_ts, n, po, n, self.trx._stream(stream) if self.trx is not None else None),
+               "trxhip_air_downlink_s16")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.trxhip_air_destroy(self.h)
             self.h = None
 
     def __del__(self):
