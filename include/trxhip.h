@@ -1643,6 +1643,43 @@ int  trxhip_air_downlink_s16(trxhip_air *a, const int16_t *d_in, int64_t first_t
 			     void *stream);
 int32_t trxhip_air_noise_host(uint32_t seed, uint32_t lane, int64_t ts, int32_t scale);
 
+/* ---- The air interface: multipath rays per path (echoes, Doppler, fading) ------------------------------------------------------
+ * A path (member, direction) of a trxhip_air has either the plain state _set_path sets, or a list of 1 .. 64 rays; a ray is what
+ * a path is, {gain 0 .. 16, delay 0 .. max_delay in whole samples, hz with |hz| <= 500000, phase (uint32, 2^32 = one turn)}.
+ *   ray phase  p_r(ts) = phase + (uint32_t)(ts - ts_set) * (uint32_t)inc, inc = trxhip_ms_nco_inc(hz), ts_set the direction's
+ *              end_ts at the set call (0 before the first window).  Modulo 2^32 that is phase_at_0 + (uint32_t)ts * inc with
+ *              phase_at_0 = phase - (uint32_t)ts_set * inc: a function of the absolute timestamp, untouched by windows and resets.
+ *   ray        x = the source sample at ts - delay, or 0 in front of the direction's first sample or reset; c_r = the contribution
+ *              of x through {p_r(ts), gain * 256.0f} exactly as a path's above (phasor, rotation, rint).  A zero sample gives 0.
+ *   path       the exact integer sum of c_r over its rays.  |c_r| < 2^28, so 64 rays x 4096 members stay far inside int64; the
+ *              downlink too carries its per-member sum in 64 bits.  Noise, output, windows, rings and reset are as above.
+ *   side by side  while a path has rays its output is theirs.  _set_path still updates the plain state and _path_state reports
+ *              it, as without rays; setting zero rays returns the path to its plain state, whose oscillator has kept running (it
+ *              is a function of the absolute timestamp).  One ray {g, d, 0 Hz, phase 0} gives the bytes of the plain path {g, d, 0}.
+ * trxhip_multipath_set acts at the direction's end_ts and is all-or-nothing.  TRXHIP_EINVAL, nothing changed: n_rays > 64, rays
+ *   NULL with n_rays > 0, a gain outside 0 .. 16 or NaN, delay > max_delay, |hz| > 500000 or NaN, reserved != 0, a bad dir or
+ *   member, object NULL.
+ * trxhip_multipath_state writes min(cap, *n_rays) rays with phase advanced to the current end_ts, the number the path has to
+ *   *n_rays and the end_ts of the last _set (0 when there was none) to *ts_set; n_rays and ts_set may be NULL, out too when cap
+ *   is 0.  Feeding its output back to _set changes no later byte: that is how a caller changes a profile with continuous phases.
+ * Both work on host objects (the plain loop over the same inline functions) and on device objects.  On the device a direction in
+ *   which some path has rays keeps one flat list of ray entries (32 bytes each; a plain member of it is one entry; the downlink
+ *   adds 24 bytes per member) resident: the first window after a _set_path, trxhip_multipath_set or (downlink) _set_noise copies
+ *   it from the window's pinned area, a window with nothing changed copies nothing, whatever N and the number of rays.  Per
+ *   window: at most that one copy, three launches, one event, and the waits stated above.  A direction without rays issues what
+ *   it issued before. */
+#define TRXHIP_MULTIPATH_MAX_RAYS 64
+typedef struct trxhip_multipath_ray {  /* 24 bytes */
+	float    gain;           /* 0 .. 16 */
+	uint32_t delay;          /* 0 .. max_delay */
+	double   hz;             /* |hz| <= 500000, + = up */
+	uint32_t phase;          /* at the direction's end_ts; 2^32 = one turn */
+	uint32_t reserved;       /* 0 */
+} trxhip_multipath_ray;
+int  trxhip_multipath_set(trxhip_air *a, int dir, uint32_t member, const trxhip_multipath_ray *rays, uint32_t n_rays);
+int  trxhip_multipath_state(const trxhip_air *a, int dir, uint32_t member, trxhip_multipath_ray *out, uint32_t cap, uint32_t *n_rays,
+			    int64_t *ts_set);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from .trxhip import (TrxHip, TrxHipError, PARAMS_DTYPE, RESULT_DTYPE, lib_path, 
                      MS_FCCH_DTYPE, MS_AFC_ENTRY_DTYPE, MS_AFC_STATE_DTYPE, MS_AFC_RING,
                      MS_NCO_ROW_DTYPE, MS_NCO_STATE_DTYPE, MS_FCCH_BIAS_HZ, nco_hz_from_fcch, nco_tx_hz, ms_nco_inc, ms_nco_phase, ms_nco_tables_host,
                      MS_FCCH_HIT_DTYPE, MS_FSEARCH_HOP, MS_FSEARCH_W, MS_FSEARCH_LAG, MS_FSEARCH_MIN_SCORE,
-                     AirChannel, AIR_UL, AIR_DL, AIR_PATH_STATE_DTYPE, air_noise_host)
+                     AirChannel, AIR_UL, AIR_DL, AIR_PATH_STATE_DTYPE, air_noise_host, AIR_RAY_DTYPE, AIR_MAX_RAYS, air_rays)
 
 __all__ = ["TrxHip", "TrxHipError", "PARAMS_DTYPE", "RESULT_DTYPE", "lib_path", "load_library",
            "OFF", "TSC", "EXT_RACH", "RACH", "SCH", "EDGE", "IDLE",
@@ -30,4 +30,4 @@ __all__ = ["TrxHip", "TrxHipError", "PARAMS_DTYPE", "RESULT_DTYPE", "lib_path", 
            "MS_FCCH_DTYPE", "MS_AFC_ENTRY_DTYPE", "MS_AFC_STATE_DTYPE", "MS_AFC_RING",
            "MS_NCO_ROW_DTYPE", "MS_NCO_STATE_DTYPE", "MS_FCCH_BIAS_HZ", "nco_hz_from_fcch", "nco_tx_hz", "ms_nco_inc", "ms_nco_phase", "ms_nco_tables_host",
            "MS_FCCH_HIT_DTYPE", "MS_FSEARCH_HOP", "MS_FSEARCH_W", "MS_FSEARCH_LAG", "MS_FSEARCH_MIN_SCORE",
-           "AirChannel", "AIR_UL", "AIR_DL", "AIR_PATH_STATE_DTYPE", "air_noise_host"]
+           "AirChannel", "AIR_UL", "AIR_DL", "AIR_PATH_STATE_DTYPE", "air_noise_host", "AIR_RAY_DTYPE", "AIR_MAX_RAYS", "air_rays"]

@@ -5,6 +5,10 @@
 //   noise         s(seed, lane, ts) = the four bytes of a murmur3-finalised hash of (seed, lane, ts) summed, minus 510;
 //                 nq = (scale * s + 128) >> 8, scale = llrint(rms * 65536 / sqrt(21845))
 //   output        clamp((acc + 128) >> 8, -32768, 32767), arithmetic shift
+// and for a path with rays (include/trxhip.h, "multipath rays"):
+//   ray phase     p_r(ts) = phase_at_0 + (uint32_t)ts * (uint32_t)inc, phase_at_0 = phase - (uint32_t)ts_set * (uint32_t)inc
+//   ray           c_r = trx_air_path(tab, x at ts - delay, p_r(ts), gain * 256.0f), as a path
+//   path          the exact integer sum of c_r over its rays; |c_r| < 2^28 at int16 input, 64 bits carry every sum
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -32,6 +36,29 @@ struct trx_air_rx {
 	uint32_t key_re, key_im;   /* trx_air_lane_key of the lanes 2 rx and 2 rx + 1 */
 	uint32_t reserved;
 };
+
+#define TRX_AIR_MAX_RAYS 64
+
+/* one ray of a direction's resident list (a plain member of such a direction is one entry): 32 bytes.  The row does not depend
+ * on the window: the phase of output sample ts is phase_at_0 + (uint32_t)ts * inc.  A ray with inc == 0 carries its phasor,
+ * trx_nco_phasor(tab, phase_at_0) made on the host from the same tables, and reads no table on the device */
+struct trx_air_ray {
+	uint32_t phase_at_0;
+	int32_t  inc;
+	float    g256;
+	uint32_t delay;
+	uint32_t row;              /* the source row: the member on the uplink, 0 on the downlink */
+	float    rc, rs;           /* inc == 0 only */
+	uint32_t reserved;
+};
+
+/* a member's entries in the list, for the downlink: 8 bytes */
+struct trx_air_span {
+	uint32_t first, count;
+};
+
+/* phase_at_0 of an oscillator that stands at acc at ts_ref */
+inline uint32_t trx_air_phase_at_0(uint32_t acc, int64_t ts_ref, int32_t inc) { return acc - (uint32_t)(uint64_t)ts_ref * (uint32_t)inc; }
 
 /* one int16 sample */
 struct alignas(4) trx_air_s16 {
@@ -74,6 +101,12 @@ TRX_NCO_HD inline void trx_air_path(const float *tab, int16_t xr, int16_t xi, ui
 	trx_nco_rotate((float)xr, (float)xi, rc, rs, &yr, &yi);
 	*cr = trx_air_contrib(yr, g256);
 	*ci = trx_air_contrib(yi, g256);
+}
+
+/* p_r(ts) of a ray: a function of the absolute timestamp alone, modulo 2^32 */
+TRX_NCO_HD inline uint32_t trx_air_ray_phase(uint32_t phase_at_0, int32_t inc, int64_t ts)
+{
+	return phase_at_0 + (uint32_t)(uint64_t)ts * (uint32_t)inc;
 }
 
 TRX_NCO_HD inline uint32_t trx_air_fmix32(uint32_t h)

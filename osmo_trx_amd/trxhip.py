@@ -277,6 +277,8 @@ SYMBOLS = {
     "trxhip_air_uplink_s16": (_I, [_VP, _VP, _SZ, C.c_int64, _SZ, _VP, _VP]),
     "trxhip_air_downlink_s16": (_I, [_VP, _VP, C.c_int64, _SZ, _VP, _SZ, _VP]),
     "trxhip_air_noise_host": (C.c_int32, [C.c_uint32, C.c_uint32, C.c_int64, C.c_int32]),
+    "trxhip_multipath_set": (_I, [_VP, _I, C.c_uint32, _VP, C.c_uint32]),
+    "trxhip_multipath_state": (_I, [_VP, _I, C.c_uint32, _VP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]),
 }
 
 
@@ -293,7 +295,7 @@ def load_library():
     except OSError as e:  # pragma: no cover
         raise TrxHipError(f"cannot load {path}: {e}") from e
     for name, (res, args) in SYMBOLS.items():
-        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_", "trxhip_ms_afc_", "trxhip_ms_fcch_", "trxhip_ms_nco_", "trxhip_air_"))) and \
+        if (name == "trxhip_fast_stats" or name.startswith(("trxhip_hostpipe_", "trxhip_ms_agc_", "trxhip_ms_level_", "trxhip_ms_afc_", "trxhip_ms_fcch_", "trxhip_ms_nco_", "trxhip_air_", "trxhip_multipath_"))) and \
                 os.environ.get("TRXHIP_LIB") and not hasattr(L, name):
             continue          # tools/measure.py ab against an older measurement build of the library (product: always bound)
         f = getattr(L, name)  # AttributeError if the export is missing
@@ -2139,6 +2141,36 @@ AIR_MAX_DELAY = 65536                                # TRXHIP_AIR_MAX_DELAY
 AIR_PATH_STATE_DTYPE = np.dtype([("gain", "<f4"), ("delay", "<u4"), ("hz", "<f8"), ("inc", "<i4"), ("acc", "<u4"), ("ts_ref", "<i8"),
                                  ("noise_scale", "<i4"), ("started", "<u4"), ("end_ts", "<i8")])
 assert AIR_PATH_STATE_DTYPE.itemsize == 48
+AIR_MAX_RAYS = 64                                    # TRXHIP_MULTIPATH_MAX_RAYS
+AIR_RAY_DTYPE = np.dtype([("gain", "<f4"), ("delay", "<u4"), ("hz", "<f8"), ("phase", "<u4"), ("reserved", "<u4")])   # trxhip_multipath_ray
+assert AIR_RAY_DTYPE.itemsize == 24
+AIR_SAMPLE_HZ = 13e6 / 12.0
+
+
+def air_rays(delays_us, powers_db, doppler_hz=0.0, sinusoids=1, seed=0, gain=1.0):
+    """A tap-delay profile as AIR_RAY_DTYPE rays for AirChannel.set_rays; pure numpy, deterministic in seed.  Tap k lies
+    delays_us[k] behind the first sample, rounded to whole samples of 13e6 / 12 Hz, at powers_db[k] relative to the others, and
+    is `sinusoids` rays of equal gain: ray j of tap k at doppler_hz * cos(angle), angle = 2 pi (j + offset_k) / sinusoids with
+    offset_k drawn from numpy.random.default_rng(seed), as its uint32 phase is.  The sum of gain_r^2 is gain^2.  The profile is
+    the caller's: no standard tables are shipped."""
+    delays = np.atleast_1d(np.asarray(delays_us, dtype=np.float64))
+    powers = np.atleast_1d(np.asarray(powers_db, dtype=np.float64))
+    sinusoids = int(sinusoids)
+    if delays.shape != powers.shape or delays.ndim != 1 or len(delays) < 1 or sinusoids < 1 or (delays < 0).any() or \
+            len(delays) * sinusoids > AIR_MAX_RAYS:
+        raise ValueError("air_rays: 1 .. %d rays from matching 1-D delays (>= 0) and powers" % AIR_MAX_RAYS)
+    rng = np.random.default_rng(seed)
+    lin = 10.0 ** (powers / 10.0)
+    tap_gain = float(gain) * np.sqrt(lin / lin.sum() / sinusoids)
+    offset = rng.uniform(0.0, 1.0, size=len(delays))
+    phase = rng.integers(0, 1 << 32, size=(len(delays), sinusoids), dtype=np.uint64)
+    angle = 2.0 * np.pi * (np.arange(sinusoids)[None, :] + offset[:, None]) / sinusoids
+    rays = np.zeros((len(delays), sinusoids), dtype=AIR_RAY_DTYPE)
+    rays["gain"] = tap_gain[:, None]
+    rays["delay"] = np.rint(delays * 1e-6 * AIR_SAMPLE_HZ).astype(np.uint32)[:, None]
+    rays["hz"] = float(doppler_hz) * np.cos(angle)
+    rays["phase"] = phase.astype(np.uint32)
+    return rays.reshape(-1)
 
 
 class _AirCfg(C.Structure):
@@ -2163,6 +2195,8 @@ class AirChannel:
     bytes do not depend on the grid or the chunking.  Windows of a direction are contiguous.  The object holds
     (n_members + 1) * max_delay * 4 bytes of history from creation on (1 GiB at 4096 members and 65536): ask for the largest
     delay the paths will use.
+    set_rays() gives a path 1 .. AIR_MAX_RAYS rays instead (trxhip_multipath_*): each a gain, a delay, a carrier offset and a start
+    phase, summed as integers -- echoes, Doppler, fading; air_rays() turns a tap-delay profile into them.
     trx=None: a host object -- numpy arrays in and out, the plain loop over the same arithmetic, no GPU."""
 
     def __init__(self, trx=None, n_members=1, max_delay=0, seed=0):
@@ -2189,6 +2223,38 @@ class AirChannel:
         if not 0 <= member < self.n:
             _check(-22, "trxhip_air_set_noise (member %r)" % member)
         _check(self.L.trxhip_air_set_noise(self.h, dir, member, float(rms)), "trxhip_air_set_noise")
+
+    def set_rays(self, dir, member, rays):
+        """the path's rays (trxhip_multipath_set): an AIR_RAY_DTYPE array, or a list of dicts with gain, delay, hz, phase (the
+        defaults of set_path, phase 0; phase is a uint32, 2^32 one turn).  Acts at the direction's end_ts, all or nothing.  None or
+        an empty list clears them: the path is its plain state again"""
+        if rays is None:
+            rays = []
+        if not isinstance(rays, np.ndarray):
+            a = np.zeros(len(rays), dtype=AIR_RAY_DTYPE)
+            for k, r in enumerate(rays):
+                extra = set(r) - {"gain", "delay", "hz", "phase"}
+                if extra or not 0 <= int(r.get("delay", 0)) <= AIR_MAX_DELAY or not 0 <= int(r.get("phase", 0)) < 1 << 32:
+                    _check(-22, "trxhip_multipath_set (ray %d: %r)" % (k, r))
+                a[k] = (r.get("gain", 1.0), int(r.get("delay", 0)), r.get("hz", 0.0), int(r.get("phase", 0)), 0)
+            rays = a
+        assert rays.dtype == AIR_RAY_DTYPE and rays.ndim == 1, (rays.dtype, rays.shape)
+        rays = np.ascontiguousarray(rays)
+        if not 0 <= int(member) < self.n or len(rays) > AIR_MAX_RAYS:
+            _check(-22, "trxhip_multipath_set (member %r, %d rays)" % (member, len(rays)))
+        _check(self.L.trxhip_multipath_set(self.h, dir, member, rays.ctypes.data_as(_VP) if len(rays) else None, len(rays)),
+               "trxhip_multipath_set")
+
+    def rays(self, dir, member):
+        """(AIR_RAY_DTYPE array, ts_set): the path's rays with their phases at the direction's current end_ts, and the end_ts of
+        the last set_rays.  set_rays(dir, member, rays(dir, member)[0]) changes no later byte"""
+        if not 0 <= int(member) < self.n:
+            _check(-22, "trxhip_multipath_state (member %r)" % member)
+        a = np.zeros(AIR_MAX_RAYS, dtype=AIR_RAY_DTYPE)
+        n, ts = C.c_uint32(0), C.c_int64(0)
+        _check(self.L.trxhip_multipath_state(self.h, dir, member, a.ctypes.data_as(_VP), AIR_MAX_RAYS, C.byref(n), C.byref(ts)),
+               "trxhip_multipath_state")
+        return a[:n.value].copy(), ts.value
 
     def path_state(self, dir, member):
         """AIR_PATH_STATE_DTYPE record"""
