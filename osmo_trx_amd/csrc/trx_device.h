@@ -664,6 +664,9 @@ __device__ __forceinline__ int walk_tree(float nv, int inc0, bool &tie)
 //         round A depend on the lane only): four conflict-free 16-byte reads instead of sixteen 4-byte gathers
 //   PAIRS: sincv is stored as row pairs (trx_tables.h, trx_sincp_idx: the normal-burst kernel's LDS copy); such a caller hands
 //         over wa4 (round A's weights are not read from the LUT)
+//   lane : used ONLY as the index into wa4[] -- the position constants come from pc.  The normal-burst kernel relies on that: its
+//         wa4 stands in its own lane layout, and its re-run passes the lane that holds this lane's node there (nb_walk_dst,
+//         trx_kernel_nb.hip).  A use of `lane` for anything else here breaks that re-run.
 template <bool PAIRS = false>
 __device__ __forceinline__ void peak_detect_spec(const c32 *cz, int max_idx, const float *sincv, const PeakConst &pc,
 						  int lane, int *toa512_out, c32 *val_out, const float4 *wa4 = nullptr)

@@ -65,6 +65,32 @@ __device__ __forceinline__ int nb_lane_id()
 	return lane;
 }
 
+// Lane layout of the TOA search in the hand-placed blocks DETA / DETB (tools/gen_nb_asm.py, walk_rank): the nodes of a round of
+// LEVELS levels stand in POSITION order -- node (level k, index i) at in-order rank r = (2 i + 1) * 2^(LEVELS - 1 - k) - 1, on
+// lanes 2 r (early) and 2 r + 1 (late) -- where peak_const() (trx_device.h) has heap node n = 2^k - 1 + i on lanes 2 n, 2 n + 1.
+// The layout is this kernel's own: only what the blocks read by lane is staged through it (wa4f, ka, kb).  Lanes that hold no
+// node of the round (round A: 62, 63; round B: 30 .. 63) keep their place.
+//   nb_walk_src(l): the peak_const() lane whose constants lane l of the blocks takes;  nb_walk_dst(): its inverse
+template <int LEVELS>
+__device__ __forceinline__ int nb_walk_src(int l)
+{
+	const int r = l >> 1;
+	if (r >= (1 << LEVELS) - 1)
+		return l;
+	const int t = __ffs(r + 1) - 1;                                // LEVELS - 1 - k
+	const int k = LEVELS - 1 - t, i = (r + 1) >> (t + 1);
+	return 2 * ((1 << k) - 1 + i) + (l & 1);
+}
+template <int LEVELS>
+__device__ __forceinline__ int nb_walk_dst(int l)
+{
+	const int n = l >> 1;
+	if (n >= (1 << LEVELS) - 1)
+		return l;
+	const int k = 31 - __clz(n + 1), i = n + 1 - (1 << k);
+	return 2 * (((2 * i + 1) << (LEVELS - 1 - k)) - 1) + (l & 1);
+}
+
 __global__ void __launch_bounds__(NB_WPB * WAVE)
 nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__restrict__ params,
 		trxhip_burst_result *__restrict__ results, float *__restrict__ soft, const trx_tables *__restrict__ tab,
@@ -112,7 +138,7 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 	}
 	for (int i = threadIdx.x; i < 16 * WAVE; i += blockDim.x) {
 		const int l = i & (WAVE - 1), u = i >> 6;
-		const PeakConst pcl = peak_const(l);
+		const PeakConst pcl = peak_const(nb_walk_src<5>(l));         // (round A's weights: in the blocks' lane layout)
 		const int q = (u < 8) ? pcl.loA + 512 * (7 - u) : pcl.hiA + 512 * (u - 8);
 		wa4f[((u >> 2) * WAVE + l) * 4 + (u & 3)] = (q < TRX_SINCV_LEN) ? tab->sincv[q] : 0.0f;
 	}
@@ -140,9 +166,10 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 		pkcl[4 * WAVE + threadIdx.x] = pc0.ratio_off;
 		// byte offsets relative to &cz[bidx]: the lane's peak-ratio term; round A's first tap (cz + bidx - 1 + flA - 7); round B's offset
 		// (two 8-byte entries per lane -- (kr, ka), (kb, kic) -- and ktp by itself: three reads in block AMAX's wait states)
+		// (ka and kb in the blocks' lane layout, nb_walk_src; the gate's terms kr are no nodes: lanes 0 .. 7 as they are)
 		lcn[2 * threadIdx.x + 0] = pc0.ratio_off * 8;
-		lcn[2 * threadIdx.x + 1] = (pc0.flA - 8) * 8;
-		lcn[2 * (WAVE + threadIdx.x) + 0] = pc0.offB;
+		lcn[2 * threadIdx.x + 1] = (peak_const(nb_walk_src<5>((int)threadIdx.x)).flA - 8) * 8;
+		lcn[2 * (WAVE + threadIdx.x) + 0] = peak_const(nb_walk_src<4>((int)threadIdx.x)).offB;
 		// the demodulator's lanes (tools/gen_nb_asm.py, fir_moving: every lane holds twelve samples = three symbols, the sums move
 		// two lanes up): 0..49 samples from symbol 4 + 3 lane on, composite row (50, 51: idle, as 49); 52 + 3 e + t, low-edge symbol
 		// e: t = 0, 1 main part -- samples from symbol e / e + 3, row e of the parked block; t = 2 its taps u < 8 -- samples from
@@ -669,7 +696,9 @@ nb_pull4_kernel(const uint32_t *__restrict__ iq, const trxhip_burst_params *__re
 							pkc.flA = pkcl[0 * WAVE + lane]; pkc.loA = pkcl[1 * WAVE + lane]; pkc.hiA = pkcl[2 * WAVE + lane];
 							pkc.offB = pkcl[3 * WAVE + lane]; pkc.ratio_off = pkcl[4 * WAVE + lane];
 							c32 xcorr;
-							peak_detect_spec<true>(cz, bidx, sincv, pkc, lane, &toa512, &xcorr, wa4);
+							// (pkcl[] is in peak_const()'s order; the one thing peak_detect_spec() takes by lane number is round A's
+							// weights, which stand in the blocks' layout: the lane that holds this lane's node there)
+							peak_detect_spec<true>(cz, bidx, sincv, pkc, nb_walk_dst<5>(lane), &toa512, &xcorr, wa4);
 							toa512 = uni(toa512);
 							xr_bits = uni(__float_as_int(xcorr.x));
 							xi_bits = uni(__float_as_int(xcorr.y));

@@ -654,30 +654,54 @@ def chain_term(b, acc, x, hp, half, first):
         b(f"v_pk_fma_f32 {acc}, {x}, {hp}, {acc} " + sel.format(z=",0", o=",1"))
 
 
-def fast_walk(b, c, p, pos, levels, w="b64"):
-    """three scalar instructions per level of the bisection tree: bit position of node (L, p), its "early < late" bit, p = 2p + bit"""
-    b(f"s_mov_b32 {p}, 0")
-    for lw in range(levels):
-        b(f"s_lshl1_add_u32 {pos}, {p}, {2 * ((1 << lw) - 1)}")
-        b(f"s_bitcmp1_{w} {c}, {pos}")
-        b(f"s_addc_u32 {p}, {p}, {p}")
+# The TOA search's lane layout (this kernel's own: trx_kernel_nb.hip stages wa4f, ka and kb by nb_walk_src<LEVELS>()).  peakDetect()'s
+# early / late bisection moves right where |early| < |late| and left otherwise; the candidate positions of a round's levels form a
+# complete binary tree whose IN-ORDER traversal is the sorted list of positions.  Node (level k, index i) of a round of `levels`
+# levels sits at in-order rank r = (2 i + 1) * 2^(levels - 1 - k) - 1, on lanes 2 r (early) and 2 r + 1 (late).  The compare
+# gives, per lane, "my upper bound < my quad neighbour's lower bound": bit 2 r = a certain "early < late" (go right), bit 2 r + 1
+# a certain "early > late" (go left); the two exclude each other (hi_E < lo_L <= hi_L < lo_E <= hi_E is no order; a NaN bound
+# fails its compare).  Read in position order, a certified mask whose decisions are MONOTONE -- right, ..., right, left, ...,
+# left: n times right -- ends the bisection at leaf n (the walk leaves exactly the n nodes that say "right" on its left), and
+# such a mask is, on the round's 2 * nodes bits,
+#     c = 0101..01 (bits >= 2 n)  1010..10 (bits < 2 n),   that is   c ^ ODD = the run of ones bfm(2 n),   ODD = the odd bits:
+# one XOR, the first zero (2 n), and ONE compare with s_bfm of that length are certification and monotony at once (walk_first_zero).
+# Every other mask -- an uncertified node, or certified decisions out of order -- takes the level-by-level walk
+# (careful_walk: NB_ASM_COLD), which follows the reference's path whatever the mask is and asks certification of the nodes ON the
+# path only.  Both hand on TWICE the leaf index.  tests/test_nb_toa_walk_cpu.py models both forms.
+def walk_rank(levels, k, i):
+    """in-order rank of node (level k, index i) of a complete tree of `levels` levels"""
+    return (2 * i + 1) * (1 << (levels - 1 - k)) - 1
+
+
+def walk_first_zero(b, x, m, t, cold_label, w="b64"):
+    """x = c ^ ODD on the round's bits (no other bit set) -> m = 2 * leaf, or off to the level-by-level walk"""
+    b(f"s_ff0_i32_{w} {m}, {x}")                                   # (x has zeros above the round's bits: never -1)
+    b(f"s_bfm_{w} {t}, {m}, 0")
+    b(f"s_cmp_eq_u{w[1:]} {t}, {x}")
+    b(f"s_cbranch_scc0 {cold_label}")
 
 
 def careful_walk(b, c, cd, p, pos, levels, unsure_label, w="b64"):
-    """the same walk, checking that every node ON THE PATH has a certified decision (cd = c | c >> 1)"""
+    """the reference's walk on the in-order layout, checking that every node ON THE PATH has a certified decision (cd = c | c >> 1):
+    node (k, p) at bit 2 * rank = (p << (levels + 1 - k)) + (1 << (levels - k)) - 2.  Out: p = 2 * leaf"""
+    b(f"s_lshr_{w} {cd}, {c}, 1")
+    b(f"s_or_{w} {cd}, {cd}, {c}")
     b(f"s_mov_b32 {p}, 0")
     for lw in range(levels):
-        b(f"s_lshl1_add_u32 {pos}, {p}, {2 * ((1 << lw) - 1)}")
+        assert 2 * walk_rank(levels, lw, 1) == (1 << (levels + 1 - lw)) + (1 << (levels - lw)) - 2
+        b(f"s_lshl_b32 {pos}, {p}, {levels + 1 - lw}")
+        b(f"s_add_u32 {pos}, {pos}, {(1 << (levels - lw)) - 2}")
         b(f"s_bitcmp0_{w} {cd}, {pos}")
         b(f"s_cbranch_scc1 {unsure_label}")
         b(f"s_bitcmp1_{w} {c}, {pos}")
         b(f"s_addc_u32 {p}, {p}, {p}")
+    b(f"s_lshl_b32 {p}, {p}, 1")
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # block DETA: detectBurst() behind fastPeakDetect (sigProcLib.cpp:1683-1695): edge gate, computePeakRatio gate (:1541-1571)
-# on an estimate with a proven margin, round A of peakDetect()'s bisection (levels 0..4, trx_device.h peak_detect_fast) and
-# its certified tree walk.
+# on an estimate with a proven margin, round A of peakDetect()'s bisection (levels 0..4, trx_device.h peak_detect_fast; the 31
+# nodes on lanes 0..61 in position order -- walk_rank) and its certified walk.
 #   in : %[bidx] %[len] %[czb] SGPR (czb = LDS byte address of cz[0]); %[m] SGPR |corr[bidx]|^2 (block AMAX's maximum); %[kr] %[ka] VGPR lane constants (byte offsets of the
 #        lane's peak-ratio term and of round A's first tap, relative to &cz[bidx]); %[l16] VGPR 16 * lane; %[gkv] VGPR lane n =
 #        thresh^2 / n (n = 5..8); %[c0] VGPR thresh^2 * 1.0001e-5
@@ -773,11 +797,13 @@ def block_deta(wa4_off):
     fmas(X, 76, 80, True)
     b("s_waitcnt lgkmcnt(0)")
     fmas(Y, 104, 108, False)
-    b("s_nop 0")
+    # (the three wait states of the packed results carry scalar set-up: ODD of the walk -- the odd bits of round A's 31 nodes,
+    # bits 1 .. 61 -- and the status of a found burst)
+    b("s_mov_b32 s96, 0xaaaaaaaa")
     b("v_pk_add_f32 v[84:85], v[84:85], v[86:87]")
-    b("s_nop 0")
+    b("s_mov_b32 s97, 0x2aaaaaaa")
     b("v_pk_mul_f32 v[84:85], v[84:85], v[84:85]")
-    b("s_nop 0")
+    b(f"s_mov_b32 {ST}, 1")
     b("v_add_f32_e32 v88, v85, v84")                               # nv = |interp|^2
     # certified comparison: r = KAPPA (nv + m); sure "early < late" when hi_E < lo_L, sure "early > late" when hi_L < lo_E
     b(f"v_fmamk_f32 v89, v88, {fhex(KAPPA)}, %[km]")
@@ -786,18 +812,11 @@ def block_deta(wa4_off):
     b("s_lshl_b32 s94, %[bidx], 9")
     b(f"v_mov_b32_dpp v90, v90 quad_perm:[1,0,3,2] {D_ALL}")
     b("v_cmp_lt_f32_e64 s[88:89], v91, v90")
-    b(f"s_mov_b32 {ST}, 1")
-    b("s_lshr_b64 s[90:91], s[88:89], 1")
-    b("s_or_b64 s[90:91], s[90:91], s[88:89]")
-    b("s_mov_b32 s96, 0x55555555")
-    b("s_mov_b32 s97, 0x15555555")
-    b("s_and_b64 s[92:93], s[90:91], s[96:97]")
-    b("s_cmp_eq_u64 s[92:93], s[96:97]")
-    b("s_cbranch_scc0 .Lnbc_da_careful")
-    fast_walk(b, "s[88:89]", "s95", "s96", 5)
+    b("s_bfe_u64 s[90:91], s[88:89], 0x3e0000")                    # the 31 nodes' bits (lanes 62, 63 hold no node)
+    b("s_xor_b64 s[90:91], s[90:91], s[96:97]")
+    walk_first_zero(b, "s[90:91]", "s95", "s[92:93]", ".Lnbc_da_careful")
     b(".Lnb_da_walked:")
-    b("s_lshl_b32 s95, s95, 5")                                    # off = 32 p - 496; E = (bidx - 1) * 512 + off
-    b("s_add_u32 s94, s94, s95")
+    b("s_lshl4_add_u32 s94, s95, s94")                             # off = 32 leaf - 496 (s95 = 2 leaf); E = (bidx - 1) * 512 + off
     b("s_add_u32 %[e], s94, -1008")
     b(".Lnb_da_end:")
     # ---- cold (NB_ASM_COLD, behind the burst loop): fixed registers only
@@ -818,7 +837,7 @@ def block_deta(wa4_off):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# block DETB: round B of the bisection (levels 5..8 on lanes 0..29, the sixteen possible final positions on lanes 32..47),
+# block DETB: round B of the bisection (levels 5..8 on lanes 0..29 in position order -- walk_rank --, the sixteen possible final positions on lanes 32..47),
 # its certified walk, and the interpolated peak value at the final position (peakDetect(), :1141-1186).
 #   in : %[e] SGPR earlyIndex * 512; %[kb] VGPR lane constant offB; %[czb] SGPR; %[km] VGPR
 #   out: status 1 / 3 in the fixed register NB_ASM_ST; %[toa] SGPR final position * 512; %[xr] %[xi] SGPR interpolated value
@@ -845,7 +864,7 @@ def block_detb():
     V = lambda k: 120 + k
     # p0, p1 (v[64:65], v[66:67]) start as the products of taps 0 and 1 (chain_term), under the round's mask: lanes 30, 31 and
     # 48..63 keep whatever the block in front left there, the sum and the compare below run on it, and NOTHING reads the
-    # result -- the walks test bits 0..29 of the compare (fast: even bits up to 28, masked by 0x15555555; careful: bit pos and,
+    # result -- the walks test bits 0..29 of the compare (first zero: masked to them; level by level: bit pos and,
     # through c | c >> 1, bit pos + 1 <= 29), the v_readlane pair reads lanes 32 + p, p = 0..15.  (exec_ok: told to the checker.)
     # The sign of a zero: lanes 0..29 go through |interp|^2.  The final positions' value (lanes 32..47) is read as it is, per
     # component p0 + p1.  p1 holds tap fl, the tap AT the peak's floor: its weight is sincv[f], f = 0..511 -- sinc on [0, 1),
@@ -897,15 +916,13 @@ def block_detb():
     b("s_nop 0")
     b(f"v_mov_b32_dpp v96, v96 quad_perm:[1,0,3,2] {D_ALL}")
     b("v_cmp_lt_f32_e64 s[88:89], v97, v96")
-    b("s_lshr_b32 s90, s88, 1")
-    b("s_or_b32 s90, s90, s88")
-    b("s_and_b32 s91, s90, 0x15555555")
-    b("s_cmp_eq_u32 s91, 0x15555555")
-    b("s_cbranch_scc0 .Lnbc_db_careful")
-    fast_walk(b, "s88", "s94", "s95", 4, "b32")
+    b("s_and_b32 s90, s88, 0x3fffffff")                            # the 15 nodes' bits
+    b("s_xor_b32 s90, s90, 0x2aaaaaaa")
+    walk_first_zero(b, "s90", "s94", "s91", ".Lnbc_db_careful", "b32")
     b(".Lnb_db_walked:")
-    b("s_add_u32 s93, s94, 32")                                    # lane that evaluated the final position
-    b("s_lshl1_add_u32 %[toa], s94, s92")                          # E + offB + 512, offB = 2 p - 15
+    b("s_lshr_b32 s93, s94, 1")
+    b("s_add_u32 %[toa], s94, s92")                                # E + offB + 512, offB = 2 leaf - 15 (s94 = 2 leaf)
+    b("s_add_u32 s93, s93, 32")                                    # lane that evaluated the final position
     b("v_readlane_b32 %[xr], v74, s93")
     b("v_readlane_b32 %[xi], v75, s93")
     b(".Lnb_db_end:")
