@@ -347,6 +347,10 @@ int trxhip_scale_vector_cf32(trxhip_ctx *ctx, float *d_x_cf32, size_t len, float
  * d_soft[b][0..soft_stride): +-127 for the 148 (normal) / 88 (access) demodulated bits, 0 behind them; with
  * TRXHIP_FLAG_SLICE through vectorSlicer() (0 / 1).  d_starts (may be NULL): estimated burst start in samples.
  * Samples outside the burst read as 0.  soft_stride >= 148.
+ * One deliberate deviation: at tsc 1 the MLSE receivers (this one, TRXHIP_FLAG_USE_VA, trxhip_ms_rx_batch_*) use the training
+ * sequence of 3GPP TS 45.002, not row 1 of the reference's grgsm_vitac/constants.h, which has bit 20 inverted: the reference
+ * correlates with one of its 16 taps negated there and loses bits.  Every other tsc equals the reference's compiled code bit for
+ * bit; tsc 1 equals the same compiled code fed the 3GPP row (tests/test_vitac_ref_cpu.py, tests/test_gpu_vitac_ref.py).
  * d_detected (may be NULL): the result records of a preceding detection launch on the same batch; burst b is then
  * demodulated only if d_detected[b].rc > 0, with that rc as the CorrType (Transceiver.cpp:769-784); the others get
  * zeros and start -1.  This chains detection and the Viterbi demodulator on one stream without a host round trip. */

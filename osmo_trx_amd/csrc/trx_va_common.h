@@ -26,8 +26,12 @@
 // {1, j, -1, -j}: out[i] = (+-j) * out[i-1] from the start point 1 / -1 (normal burst, first bit 0 / 1) or -j (access),
 // then conjugated.  Stored as 2-bit quarter-turn codes (0: 1, 1: j, 2: -1, 3: -j) of the elements the channel
 // estimate uses, i = 5 .. 20 of the 26 TSC bits and i = 5 .. 35 of the 41 access bits (TRAIN_BEGINNING = 5), element
-// k at bits 2k, 2k+1 -- computed from the 3GPP TS 45.002 bit strings by the same walk (tests compare with the oracle,
-// which maps the bits at run time).
+// k at bits 2k, 2k+1 -- computed from the 3GPP TS 45.002 bit strings by the same walk.  tests/test_vitac_ref_cpu.py reads
+// these literals and compares them with what the reference's compiled gmsk_mapper() makes of its own tables.
+// VA_TSC_CODES1 is a deliberate deviation: row 1 of the reference's grgsm_vitac/constants.h has bit 20 inverted against
+// 3GPP TS 45.002 (and the reference's own transmit table), which negates the last of the 16 elements used here; the
+// reference therefore estimates TSC 1 channels with one tap negated and loses bits.  This is the 3GPP row, pinned to the
+// compiled reference fed that row (the tsc1b_* records of tests/golden/ref_vitac_vectors.npz).
 #define VA_TSC_CODES0 0x131319b9ull
 #define VA_TSC_CODES1 0x9311b9b9ull
 #define VA_TSC_CODES2 0x1913b3b3ull

@@ -54,8 +54,8 @@ def build(force=False):
     stale = (not os.path.exists(LIB_PATH)) or os.path.getmtime(LIB_PATH) < os.path.getmtime(src)
     if force or stale:
         subprocess.check_call(["make", "-C", ORACLE_DIR, "-B", "liboracle.so"], stdout=subprocess.DEVNULL)
-    if os.path.isdir("/root/reference/Transceiver52M") and not os.path.exists(
-            os.path.join(ORACLE_DIR, "_ref", "libref_generic.so")):
+    if os.path.isdir("/root/reference/Transceiver52M") and not all(
+            os.path.exists(os.path.join(ORACLE_DIR, "_ref", so)) for so in ("libref_generic.so", "libref_vitac.so")):
         subprocess.check_call(["make", "-C", ORACLE_DIR, "ref"], stdout=subprocess.DEVNULL)
 
 
@@ -176,6 +176,97 @@ def use_ref_arch(kind):
         R = _ref_libs[kind]
         L.orc_set_arch(C.cast(R.convolve_real, C.c_void_p), C.cast(R.convolve_complex, C.c_void_p))
     L.orc_setup()
+
+
+def ref_vitac_available():
+    return os.path.exists(os.path.join(REF_DIR, "libref_vitac.so"))
+
+
+class RefVitac:
+    """The reference's MLSE receiver (grgsm_vitac.cpp + viterbi_detector.cc compiled unmodified into oracle/_ref/libref_vitac.so
+    behind oracle/ref_shim_vitac.cpp).  x: complex64[n]; samples outside [0, n) read as zero.  cir: complex64[20]."""
+
+    def __init__(self, path):
+        R = self.R = C.CDLL(path)
+        vp, i, f = C.c_void_p, C.c_int, C.c_float
+        R.ref_vitac_norm_imp_resp.argtypes = [vp, i, i, vp, vp]
+        R.ref_vitac_access_imp_resp.argtypes = [vp, i, i, vp, vp]
+        R.ref_vitac_sch_imp_resp.argtypes = [vp, i, vp]
+        R.ref_vitac_sch_buffer_imp_resp.argtypes = [vp, i, vp, vp]
+        R.ref_vitac_chan_imp_resp.argtypes = [vp, i, i, i, vp, i, vp, vp]
+        R.ref_vitac_gmsk_mapper.argtypes = [vp, i, f, f, vp]
+        R.ref_vitac_training_seqs.argtypes = [vp, vp, vp]
+        R.ref_vitac_detect_burst_nb.argtypes = [vp, i, vp, i, i, vp]
+        R.ref_vitac_detect_burst_ab.argtypes = [vp, i, vp, i, i, vp]
+
+    @staticmethod
+    def _x(x):
+        return np.ascontiguousarray(x, dtype=np.complex64)
+
+    def _imp(self, fn, x, *args, with_max=True):
+        x = self._x(x)
+        cir, cm = np.zeros(20, dtype=np.complex64), np.zeros(1, dtype=np.float32)
+        start = fn(_ptr(x), len(x), *args, _ptr(cir), *([_ptr(cm)] if with_max else []))
+        assert start > -100000, "argument outside what the reference can be called with"
+        return (start, cir, cm[0]) if with_max else (start, cir)
+
+    def norm_imp_resp(self, x, bcc):
+        """get_norm_chan_imp_resp() -> (burst start, cir, corr_max)"""
+        return self._imp(self.R.ref_vitac_norm_imp_resp, x, int(bcc))
+
+    def access_imp_resp(self, x, max_delay=0):
+        """get_access_imp_resp() -> (burst start, cir, corr_max)"""
+        return self._imp(self.R.ref_vitac_access_imp_resp, x, int(max_delay))
+
+    def sch_imp_resp(self, x):
+        """get_sch_chan_imp_resp() -> (burst start, cir)"""
+        return self._imp(self.R.ref_vitac_sch_imp_resp, x, with_max=False)
+
+    def sch_buffer_imp_resp(self, x):
+        """get_sch_buffer_chan_imp_resp(.., len(x), ..) -> (burst start, cir, corr_max)"""
+        return self._imp(self.R.ref_vitac_sch_buffer_imp_resp, x)
+
+    def chan_imp_resp(self, x, start_pos, stop_pos, seq):
+        """get_chan_imp_resp() with the caller's sequence -> (position of the strongest window, cir, corr_max)"""
+        seq = self._x(seq)
+        return self._imp(self.R.ref_vitac_chan_imp_resp, x, int(start_pos), int(stop_pos), _ptr(seq), len(seq))
+
+    def gmsk_mapper(self, bits, start_point):
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        out = np.zeros(len(bits), dtype=np.complex64)
+        self.R.ref_vitac_gmsk_mapper(_ptr(bits), len(bits), float(np.real(start_point)), float(np.imag(start_point)), _ptr(out))
+        return out
+
+    def training_seqs(self):
+        """(d_norm_training_seq complex64[9, 26], d_acc_training_seq [41], d_sch_training_seq [64]) after initvita()"""
+        norm, acc, sch = np.zeros((9, 26), np.complex64), np.zeros(41, np.complex64), np.zeros(64, np.complex64)
+        self.R.ref_vitac_training_seqs(_ptr(norm), _ptr(acc), _ptr(sch))
+        return norm, acc, sch
+
+    def _detect(self, fn, x, cir, burst_start, ss):
+        x, cir = self._x(x), self._x(cir)
+        assert len(cir) == 20
+        out = np.zeros(148, dtype=np.int8)
+        assert fn(_ptr(x), len(x), _ptr(cir), int(burst_start), int(ss), _ptr(out)) == 0, (burst_start, ss)
+        return out
+
+    def detect_burst_nb(self, x, cir, burst_start, ss=3):
+        """detect_burst_nb(x, cir, burst_start, out, ss) -> sbits int8[148]"""
+        return self._detect(self.R.ref_vitac_detect_burst_nb, x, cir, burst_start, ss)
+
+    def detect_burst_ab(self, x, cir, burst_start, ss=3):
+        """detect_burst_ab(x, cir, burst_start, out, ss) -> sbits int8[148]: 88 written, zeros behind.  ss <= 15 only."""
+        return self._detect(self.R.ref_vitac_detect_burst_ab, x, cir, burst_start, ss)
+
+
+_ref_vitac = None
+
+
+def ref_vitac():
+    global _ref_vitac
+    if _ref_vitac is None:
+        _ref_vitac = RefVitac(os.path.join(REF_DIR, "libref_vitac.so"))
+    return _ref_vitac
 
 
 def tables():

@@ -94,8 +94,11 @@ def correlate(seq, x, lags):
         tr, ti = _cmul(F(seq[ii].real), F(seq[ii].imag), xv.real.astype(F), xv.imag.astype(F))
         re = (re + tr).astype(F)
         im = (im + ti).astype(F)
-    n = F(len(seq))
-    return (re / n).astype(F), (-im / n).astype(F)                   # conj(result) / gr_complex(length, 0)
+    # conj(result) / gr_complex(length, 0): the complex division the compiler expands in line, (a + jb) / (c + jd) with |c| >= |d|:
+    # ratio = d / c = 0, ((a + b * ratio) / c, (b - a * ratio) / c).  The values are a / c and b / c; the products with zero only
+    # decide the sign of an exact zero (an imaginary sum that cancels gives -0.0 where a >= 0 and +0.0 where a < 0)
+    n, ratio, b = F(len(seq)), F(0), (-im).astype(F)
+    return ((re + b * ratio) / n).astype(F), ((b - re * ratio) / n).astype(F)
 
 
 def get_chan_imp_resp(x, start_pos, stop_pos, seq):
@@ -119,7 +122,8 @@ def get_chan_imp_resp(x, start_pos, stop_pos, seq):
     for ii in range(FL):                                             # :220-226
         if mag[best + ii] > corr_max:
             corr_max = mag[best + ii]
-    cir = (cre[best:best + FL] + 1j * cim[best:best + FL]).astype(np.complex64)
+    cir = np.zeros(FL, dtype=np.complex64)                           # part by part: a + 1j * b turns an imaginary -0.0 into +0.0,
+    cir.real, cir.imag = cre[best:best + FL], cim[best:best + FL]    # which the reference's conj() of an exact zero sum is
     return start_pos + best, cir, corr_max
 
 

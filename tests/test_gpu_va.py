@@ -1,7 +1,8 @@
 """GPU parity of the Viterbi alternative (cfg->use_va): trxhip_demod_va_batch_cf32 vs the oracle restatement of
 scaleVector + demodAnyBurst_va (Transceiver.cpp:782-784, :620-645 over grgsm_vitac/).  The oracle's Viterbi core is
 pinned bit for bit to the reference's viterbi_detector.cc compiled unmodified (tests/test_oracle.py); the front end
-(channel estimate, matched filter) lives in grgsm_vitac.cpp, which needs libosmocore and is not buildable here.
+(channel estimate, matched filter) lives in grgsm_vitac.cpp, which is compiled unmodified too (oracle/_ref/libref_vitac.so) and
+pins the oracle in tests/test_vitac_ref_cpu.py and this kernel directly in tests/test_gpu_vitac_ref.py.
 Bar: burst start and every +-127 output identical."""
 import numpy as np
 import pytest
